@@ -3,13 +3,15 @@
 Silero-VAD f32, batch = 4096 synthetic 10 s @ 16 kHz clips per MI355X (weak scaling: every rank owns
 its own 4096 clips, no data-path collective), raw audio resident in HBM -> speech-segment tables.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1 without a launcher: this process starts N ranks itself (`python -m torch.distributed.run`, rendezvous on
 127.0.0.1) BEFORE anything touches a GPU and relays rank 0's line; under an external launcher (WORLD_SIZE set, the way
 the driver runs it) it is one of the ranks.  One "step" = one pass of the hot path over the resident batch: encoder
 kernel (STFT conv + conv stack + W_ih, f32 MFMA) -> persistent LSTM kernel -> device segmenter.  Rank 0 prints ONE JSON
-line.  Besides the contract keys it carries
+line.  A plain run sets up, warms up, times K steps, writes rank 0's outputs of the last timed step if `--dump-outputs DIR`
+is given (dump_outputs) and prints the contract keys only.  With `--full` the line also carries
+  * `rtf_batch1`, `kernel_ms`, `ms_per_step_by_arithmetic`: one clip at batch 1, per-kernel event times, the same step on every arithmetic;
   * `roofline` / `roofline_recurrent`: the two matrix-pipe kernels against the f32 MFMA peak, with SURVEY 8(d) byte accounting
     (`algorithmic_bytes_per_launch` = 2052 B / window, `traffic` from the committed PMC passes, `traffic_ratio`);
   * `hbm`: the north star's HBM fraction of the whole step;
@@ -20,8 +22,8 @@ line.  Besides the contract keys it carries
   * `cpu_baseline`: the oracle driven like the reference drives ORT, on this host's cores (N = 1, rank 0), beside the reference's
     own published README figure.
 The line is kept under 6 KB (the driver records its tail); everything it summarises -- per-entry-point splits, every roofline
-object in full, sample descriptions -- is written by rank 0 to `--detail` (default gpurun_out/bench_detail.json: scratch;
-the copy to keep is committed under profiles/ deliberately).
+object in full, sample descriptions -- is written by rank 0 of a `--full` run to `--detail` (scratch; the copy to keep is
+committed under profiles/ deliberately).
 `--dry-run` replaces the device work by a sleep and RCCL by gloo so the launch / barrier / collect path can be tested
 on a CPU-only box; its line says so (`data`: "dry-run") and carries no measurement.
 """
@@ -305,6 +307,32 @@ def cpu_baseline(budget_s=10.0):
             "batched_value": batched, "batched_note": f"same oracle, batch {bb}, {min(ncpu, 64)} threads (not the reference's mode)"}
 
 
+DUMP_LIMIT_BYTES = 60 << 20       # --dump-outputs stays under 64 MB, .npy headers included
+
+
+def dump_outputs(out_dir, probs, segs, counts, limit=DUMP_LIMIT_BYTES):
+    """What a caller of the timed step receives, as `out_dir`/<name>.npy: `probs` = per-window speech scores (float32, clips x windows),
+    `segments` = the device segment table in samples with the slots past each clip's count set to -1, `segment_counts` (both float64,
+    where every int64 offset of a 10 s clip is exact).  Over `limit` bytes in all, a fixed seeded sample of the clips stands for the
+    batch and `clip_index` says which.  Returns the names written."""
+    probs, segs, counts = (np.asarray(a) for a in (probs, segs, counts))
+    B, cap = segs.shape[:2]
+    out = {}
+    per_clip = probs[0].size * 4 + cap * 2 * 8 + 8
+    if B * per_clip > limit:
+        rows = np.sort(np.random.default_rng(0).choice(B, limit // (per_clip + 8), replace=False))
+        probs, segs, counts = probs[rows], segs[rows], counts[rows]
+        out["clip_index"] = rows.astype(np.float64)
+    live = np.arange(cap)[None, :] < counts[:, None]
+    out["probs"] = probs.astype(np.float32)
+    out["segments"] = np.where(live[:, :, None], segs, -1).astype(np.float64)
+    out["segment_counts"] = counts.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
+
+
 def compact_line(full, detail_path=None):
     """The driver's record keeps the TAIL of the line, so the line stays short (< 6 KB): the contract keys, the dominant kernel's
     roofline with its byte accounting, one small object per BASELINE config, the CPU baseline.  `full` (every number) is what
@@ -380,6 +408,10 @@ def parse_args(argv=None):
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="where rank 0 writes the full (long) result object; '' = nowhere")
     ap.add_argument("--dry-run", action="store_true", help="CPU-only: gloo + sleep instead of RCCL + kernels (launch-path test)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's scores and segment tables of the last step to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel times, other arithmetics, rooflines, feed, configs 3-5, CPU baseline")
     return ap.parse_args(argv)
 
 
@@ -415,14 +447,18 @@ def dry_run(args):
     elapsed = shard.max_over_ranks(dist, time.perf_counter() - t0)
     lo, hi = shard.shard_bounds(world * args.clips, rank, world)
     owned = shard.gather_ragged(dist, [(rank, lo, hi)])
-    c4 = shard.gather_ragged(dist, [(rank,) + tuple(shard.shard_bounds(8192, rank, world))])      # BASELINE config 4: strong shards
+    c4 = None
+    if args.full:
+        c4 = shard.gather_ragged(dist, [(rank,) + tuple(shard.shard_bounds(8192, rank, world))])      # BASELINE config 4: strong shards
     if rank == 0:
-        print(json.dumps({"metric": "audio frames/sec/GPU (16 kHz, 512-sample hop); RTF at batch=1", "value": None,
-                          "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                          "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-                          "vs_baseline": None, "dtype": "f32", "data": "dry-run (no GPU work: launch / barrier / collect path only)",
-                          "config": {"workload": "dry-run", "clips_per_gpu": args.clips, "shards": owned},
-                          "c4_sharded": {"clips": 8192, "scaling": "strong", "shards": c4}}), flush=True)
+        line = {"metric": "audio frames/sec/GPU (16 kHz, 512-sample hop); RTF at batch=1", "value": None,
+                "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": "f32", "data": "dry-run (no GPU work: launch / barrier / collect path only)",
+                "config": {"workload": "dry-run", "clips_per_gpu": args.clips, "shards": owned}}
+        if c4 is not None:
+            line["c4_sharded"] = {"clips": 8192, "scaling": "strong", "shards": c4}
+        print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -533,7 +569,8 @@ def main(argv=None):
     # the timed steps carry the HIP events of the DOMINANT kernel only (roofline.achieved is its mean launch duration over the timed region);
     # the other two kernels' durations come from an event-bracketed pass right behind it: every event between two launches is a marker the queue
     # waits on, and with the per-step flag read draining the queue their cost (0.1 - 0.2 ms per step) would sit in the headline
-    events = [[torch.cuda.Event(enable_timing=True) for _ in range(2)] for _ in range(args.steps)]
+    # (--full only: a plain run's steps carry no events)
+    events = [[torch.cuda.Event(enable_timing=True) for _ in range(2)] if args.full else None for _ in range(args.steps)]
     fence()
     t0 = time.perf_counter()
     for k in range(args.steps):
@@ -543,6 +580,35 @@ def main(argv=None):
     elapsed = shard.max_over_ranks(dist, elapsed, device)
 
     log(f"timed region done: {elapsed / args.steps * 1e3:.2f} ms/step")
+    assert int(counts.max().item()) <= cap, "segment table overflow"
+    assert bool(torch.isfinite(probs).all())
+    range_flag = eng.range_flag()       # fp16 x 2 kernels: no activation of the timed steps may have left the fp16 range
+    assert range_flag[0] == 0 and range_flags_seen[0] == 0, f"fp16 range flag raised during the timed steps: {range_flag}, {range_flags_seen}"
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, probs.cpu().numpy(), segs.cpu().numpy(), counts.cpu().numpy())
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {', '.join(names)}")
+    value = world * B * T * args.steps / elapsed
+    enc_mode = silero.encoder_mode()
+    head = {
+        "metric": "audio frames/sec/GPU (16 kHz, 512-sample hop); RTF at batch=1",
+        "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "Silero-VAD f32, batch=4096 synthetic 10 s @16 kHz clips per GPU "
+                               "(STFT conv + conv1d stack + LSTM cell HIP, seeded synthetic weights)",
+                   "arithmetic": ARITH_TEXT[enc_mode],
+                   "clips_per_gpu": B, "samples_per_clip": SAMPLES, "frames_per_clip": T,
+                   "parallelism": f"clip-sharded x{world}, no collective"},
+        "per_gpu_value": value / world,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     enc_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in events]))
     ev4 = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(max(3, min(args.steps, 10)))]
     for e4 in ev4:
@@ -556,10 +622,6 @@ def main(argv=None):
     enc_stats = {"mean": enc_ms, "median": float(np.median(enc_all)), "min": enc_all[0], "max": enc_all[-1], "launches": len(enc_all),
                  "basis": "roofline.achieved uses `mean` = the average of this run's HIP-event launch durations",
                  "committed_profile": profiled_launch_ms(enc_kernel_name()) if (B, T) == (CLIPS_PER_GPU, STEPS_PER_CLIP) else None}
-    assert int(counts.max().item()) <= cap, "segment table overflow"
-    assert bool(torch.isfinite(probs).all())
-    range_flag = eng.range_flag()       # fp16 x 2 kernels: no activation of the timed steps may have left the fp16 range
-    assert range_flag[0] == 0 and range_flags_seen[0] == 0, f"fp16 range flag raised during the timed steps: {range_flag}, {range_flags_seen}"
     n_seg = int(counts.sum().item())
     probs_resident = probs.clone()
     # the same step on every arithmetic, same run, same buffers: float32 MFMAs, bf16 x 3 (operands exact to float32's 24
@@ -583,9 +645,6 @@ def main(argv=None):
         assert bool(torch.equal(probs, probs_resident))
         log("ms/step by arithmetic: " + ", ".join(f"{k} {v:.3f}" for k, v in by_arith.items()))
 
-    frames_per_step = world * B * T
-    value = frames_per_step * args.steps / elapsed
-    enc_mode = silero.encoder_mode()
     enc_kernel, rec_kernel = ENC_KERNELS[enc_mode], REC_KERNELS[enc_mode]
     achieved, enc_peak, enc_flop, enc_note = encoder_roofline(enc_mode, B * T, enc_ms)
     rec_peak = {"f32": PEAK_F32_MFMA_TFLOPS, "split": PEAK_SPLIT_TFLOPS, "h2": PEAK_H2_TFLOPS}[enc_mode]
@@ -678,16 +737,8 @@ def main(argv=None):
         step_traffic = (tr_enc["bytes"] + tr_rec["bytes"]) if (tr_enc and tr_rec) else None
         step_s = elapsed / args.steps
         line = {
-            "metric": "audio frames/sec/GPU (16 kHz, 512-sample hop); RTF at batch=1",
-            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "Silero-VAD f32, batch=4096 synthetic 10 s @16 kHz clips per GPU "
-                                   "(STFT conv + conv1d stack + LSTM cell HIP, seeded synthetic weights)",
-                       "arithmetic": ARITH_TEXT[enc_mode],
-                       "clips_per_gpu": B, "samples_per_clip": SAMPLES, "frames_per_clip": T,
-                       "parallelism": f"clip-sharded x{world}, no collective"},
-            "per_gpu_value": value / world, "rtf_batch1": rtf_b1,
+            **head,
+            "rtf_batch1": rtf_b1,
             "kernel_ms": {enc_kernel: enc_ms, rec_kernel: rec_ms, "silero_segments_kernel": seg_ms},
             "ms_per_step_by_arithmetic": by_arith,
             "range_protocol": ("the timed step reads vadx_silero_range_flag after its launches (8 B + a stream synchronisation), as every caller of "

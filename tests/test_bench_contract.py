@@ -84,7 +84,7 @@ def test_self_launch_two_ranks_dry_run():
     one line with n_gpus == 2; --dry-run swaps RCCL + kernels for gloo + sleep so this runs on a CPU-only box."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1",
-                        "--clips", "10"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                        "--clips", "10", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -104,7 +104,7 @@ def test_gpus_flag_must_match_world_size():
 
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--clips", "64", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--clips", "64", "--steps", "2", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-secondary", "--no-c4-sharded", "--detail", os.path.join(ROOT, "gpurun_out", "test_detail.json")],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -131,6 +131,66 @@ def test_bench_prints_one_contract_line():
     assert d["hbm"]["algorithmic_bytes_per_frame"] == 2052 and 0 < d["hbm"]["frac"] < 1
     # the PCIe-inclusive mode ran, and feeding int16 through the in-kernel scaling gave the very same scores
     assert d["feed"]["scores_bit_identical_to_resident_f32_path"] is True and d["feed"]["value"] < d["value"] * 1.05
+
+
+HEADLINE = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+            "data", "config", "per_gpu_value"}
+
+
+def test_dump_outputs_masks_unused_slots_and_samples_over_the_limit(tmp_path):
+    """--dump-outputs: slots past a clip's segment count are -1, dtypes are float32 / float64, and a batch over the size limit is
+    replaced by the same seeded sample of clips every time, named by clip_index, within the limit."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    B, T, cap = 40, 313, 8
+    probs = rng.random((B, T), dtype=np.float32)
+    segs = rng.integers(0, 160000, (B, cap, 2), dtype=np.int64)
+    counts = rng.integers(0, cap + 1, B).astype(np.int32)
+    assert bench.dump_outputs(str(tmp_path / "all"), probs, segs, counts) == ["probs", "segment_counts", "segments"]
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in ("probs", "segments", "segment_counts")}
+    assert got["probs"].dtype == np.float32 and np.array_equal(got["probs"], probs)
+    assert got["segments"].dtype == np.float64 and got["segment_counts"].dtype == np.float64
+    assert np.array_equal(got["segment_counts"], counts)
+    for b in range(B):
+        assert np.array_equal(got["segments"][b, :counts[b]], segs[b, :counts[b]]) and (got["segments"][b, counts[b]:] == -1).all()
+    limit = 10 * (T * 4 + cap * 16 + 8)
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(str(tmp_path / d), probs, segs, counts, limit=limit) == ["clip_index", "probs", "segment_counts", "segments"]
+    rows = np.load(tmp_path / "s1" / "clip_index.npy")
+    assert 0 < len(rows) < B and np.array_equal(rows, np.load(tmp_path / "s2" / "clip_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "probs.npy"), probs[rows.astype(np.int64)])
+    assert sum(np.load(tmp_path / "s1" / f).nbytes for f in os.listdir(tmp_path / "s1")) <= limit
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) prints the contract keys alone; --dump-outputs writes the last timed step's scores and segment tables,
+    and with the same arguments but another step count they are the same bits (seeded inputs, deterministic kernels)."""
+    import numpy as np
+    dumps = []
+    for steps in (2, 3):
+        out = tmp_path / f"steps{steps}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--clips", "64", "--steps", str(steps), "--warmup", "1",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert set(d) == HEADLINE and d["steps"] == steps and d["warmup"] == 1 and d["n_gpus"] == 1
+        assert d["unit"] == "frames/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert abs(d["value"] - 64 * 313 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        dumps.append({n: np.load(out / f"{n}.npy") for n in ("probs", "segments", "segment_counts")})
+        assert sorted(os.listdir(out)) == ["probs.npy", "segment_counts.npy", "segments.npy"]
+    a, b = dumps
+    assert a["probs"].shape == (64, 313) and a["probs"].dtype == np.float32 and np.isfinite(a["probs"]).all()
+    assert ((a["probs"] >= 0) & (a["probs"] <= 1)).all()
+    assert a["segments"].shape == (64, 64, 2) and a["segment_counts"].shape == (64,) and a["segment_counts"].sum() > 0
+    live = np.arange(64)[None, :] < a["segment_counts"][:, None]
+    assert ((a["segments"] >= 0) & (a["segments"] <= 160000))[live].all() and (a["segments"][~live] == -1).all()
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
 
 
 @pytest.mark.gpu
