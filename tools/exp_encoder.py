@@ -3,7 +3,10 @@
 build : python tools/exp_encoder.py build 0 1 2 ...   -> voice-activity-detection-vad-onnx_amd/_exp/libvadx_expN.so
         (silero.hip compiled with -DVADX_EXP=N, N a BIT MASK of switches (bit 1 no global loads, 2 no barriers, 3 no conv2-4,
         4 no STFT pass, 5 no conv1, 6 no W_ih, 7 no Nyquist bin, 8 no gx stores; LSTM kernel: 9 no gate non-linearities, 10 no per-step barrier, 11 no gx loads, 12 no probs reduce); the variants skip or alter parts of silero_encode_kernel, so their
-        RESULTS ARE WRONG on purpose -- only the kernel time is of interest)
+        RESULTS ARE WRONG on purpose -- only the kernel time is of interest); silero_h2.hip (EXP_SPLIT=2, the default) reads its own
+        bits: 3 no conv2-4 MFMAs, 4 no STFT MFMAs, 5 no conv1, 6 no W_ih, 8 / 9 the STFT's / W_ih's fragments as single L1 accesses, 10 every
+        fragment load a single L1 access, 13 every fragment from one address, 14 per-phase cycles of wave 0 (the round-6 bits 11, 12, 15 --
+        the second of two tiles sharing the first one's fragments -- went with the four-tile workgroup)
 run   : python tools/exp_encoder.py run 0 1 2 ...     (on the GPU box) -> one line per variant with the mean
         silero_encode_kernel time at the bench shape.
 """

@@ -1,7 +1,7 @@
 """Barrier timeline of silero_encode_h2_kernel (development aid; csrc/silero_h2.hip built with -DH2_TRACE=1).
    build : python tools/h2_trace.py build           -> _exp/libvadx_h2trace.so   (silero sources only)
    run   : python tools/h2_trace.py run             (GPU box) config-2 launch; sixteen workgroups spread over the grid record lane 0's shader
-           clock of every wave right before / after each of the 23 barriers of a tile pair.  Prints, averaged over the traced workgroups:
+           clock of every wave right before / after each of the 46 barriers of a workgroup's four tiles and its tail.  Prints, averaged over the traced workgroups:
            per phase (= the code between two barriers) the time of the FASTEST, the mean and the SLOWEST wave, and the time the phase's
            barrier held the waves on average -- i.e. how much of a workgroup's life is work and how much is waiting for its slowest wave."""
 import ctypes as C
@@ -13,8 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "voice-activity-detection-vad-onnx_amd")
 LIB = os.path.join(PKG, "_exp", "libvadx_h2trace.so")
 PHASES = ["stage X (global loads -> LDS)", "samples -> registers", "e / o operand planes", "STFT GEMM + magnitudes", "|X| planes + scratch",
-          "bin 64 slot", "conv1 GEMM", "conv1 store", "conv2 GEMM + exchange", "conv2 finish + store"]
-TAIL = ["conv3 GEMM + exchange", "conv3 finish + store", "conv4", "W_ih + gx store"]
+          "bin 64 slot", "conv1 GEMM", "conv1 store", "conv2 GEMM + exchange", "conv2 finish + store", "conv3 GEMM + exchange"]
+NSUB = 4           # tile t's barriers are marks 32 t + 2 k (+ 1), k = 0 .. 10; the tail's H2_SYNC(11), (12) are marks 118 .. 121
+TAIL = ["conv3 finish + store", "conv4", "W_ih + gx store"]
 
 if sys.argv[1] == "build":
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
@@ -97,27 +98,27 @@ def phase(name, start_marks, arrive_idx, release_idx):
     tot_work += np.mean(me); tot_wait += np.mean(hold)
 
 
-for sub in range(2):
+for sub in range(NSUB):
     off = 32 * sub
     for k, name in enumerate(PHASES):
-        if k == 0:
-            start = (lambda g, off=off, sub=sub: tr[g, :, 126] if sub == 0 else tr[g, :, 32 * 0 + 2 * 9 + 1])
+        if k == 0:      # (tile > 0: the previous tile's conv3 finish and store run in front of this tile's staging, with no barrier between)
+            start = (lambda g, off=off, sub=sub: tr[g, :, 126] if sub == 0 else tr[g, :, off - 32 + 2 * 10 + 1])
         else:
             start = (lambda g, off=off, k=k: tr[g, :, off + 2 * (k - 1) + 1])
         phase("tile %d: %s" % (sub, name), start, off + 2 * k, off + 2 * k + 1)
-for k, name in enumerate(TAIL[:3]):
-    start = (lambda g, k=k: tr[g, :, 32 + 2 * 9 + 1] if k == 0 else tr[g, :, 64 + 2 * (k - 1) + 1])
-    phase("pair: " + name, start, 64 + 2 * k, 64 + 2 * k + 1)
+for k, name in enumerate(TAIL[:2]):
+    start = (lambda g, k=k: tr[g, :, 32 * (NSUB - 1) + 2 * 10 + 1] if k == 0 else tr[g, :, 118 + 2 * (k - 1) + 1])
+    phase("tail: " + name, start, 118 + 2 * k, 118 + 2 * k + 1)
 # the last phase ends at mark 127 (no barrier)
 fa, me, sl = [], [], []
 for g in ok:
-    d = tr[g, :, 127] - tr[g, :, 64 + 2 * 2 + 1]
+    d = tr[g, :, 127] - tr[g, :, 121]
     fa.append(d.min()); me.append(d.mean()); sl.append(d.max())
-rows.append(("pair: " + TAIL[3], np.mean(fa), np.mean(me), np.mean(sl), 0.0))
+rows.append(("tail: " + TAIL[2], np.mean(fa), np.mean(me), np.mean(sl), 0.0))
 tot_work += np.mean(me)
 life = np.mean([tr[g, :, 127].max() - tr[g, :, 126].min() for g in ok])
 print("%-44s %9s %9s %9s %12s" % ("phase (cycles)", "fastest", "mean", "slowest", "barrier hold"))
 for r in rows:
     print("%-44s %9.0f %9.0f %9.0f %12.0f" % r)
-print("workgroup life %.0f cycles for two tiles; sum of mean phase work %.0f (%.0f %%), sum of mean barrier holds %.0f (%.0f %%)" %
+print("workgroup life %.0f cycles for four tiles; sum of mean phase work %.0f (%.0f %%), sum of mean barrier holds %.0f (%.0f %%)" %
       (life, tot_work, 100 * tot_work / life, tot_wait, 100 * tot_wait / life))

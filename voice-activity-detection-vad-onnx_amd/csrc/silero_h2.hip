@@ -10,8 +10,9 @@
 //     class, all four frames), split, and parked as B planes for all four frames (64 KB, in place of the staged window); wave (bin tile,
 //     frame pair) then runs both classes and both parts of its two frames, so nothing has to meet through LDS; bin 64 (its own mirror) is
 //     row 0 of a fifth bin tile whose (class, part) pieces are dealt over the eight waves -- no VALU dot product;
-//   * a workgroup encodes NSUB = 2 tiles one after the other up to conv2 and runs conv3, conv4 and W_ih ONCE for both: those fragments
-//     (328 of a tile's 750 KB) serve 32 columns instead of 16;
+//   * a workgroup encodes NSUB = 4 tiles (consecutive windows of one clip group) one after the other up to conv3 and runs conv4 and W_ih
+//     ONCE for all of them: those two weight streams serve 64 columns instead of 16; a slot past the last window is
+//     skipped outright (no recomputed tile);
 //   * the kernels keep the running max |x| of everything they split; a workgroup that saw a value outside the fp16 range raises the
 //     blob's sticky flag (OFF_HFLAG + 1) and the host recomputes the batch on the bf16 x 3 kernels (vadx_silero_range_flag).
 // Reference being reproduced: the `session.run` of Silero/modeling_modified/utils_vad.py:116-119 (see silero.hip).
@@ -46,25 +47,15 @@
 #ifndef H2_AH1
 #define H2_AH1 2      // conv1
 #endif
-#ifndef H2_AHI
-#define H2_AHI 2      // W_ih (two tiles per workgroup)
-#endif
 #define H2_W(addr) (H2_SKIP(13) ? (P + vadx::silero::OFF_H1) : (addr))
-// bit 15: the SECOND tile of a workgroup takes its conv1 / conv2 fragments from one L1-resident address (bit 12: its STFT fragments too): an upper
-// bound on what sharing those weight streams between the two tiles of a workgroup (one pass over 128 columns) could save
-#define H2_W12(addr) ((((H2_SKIP(15) || H2_SKIP(11)) && sub == 1) || H2_SKIP(13)) ? (P + vadx::silero::OFF_H1) : (addr))
-// bit 11: ... and every lane reads the SAME 16 bytes (one L1 access per load instead of sixteen): what removing those loads altogether -- the
-// second tile multiplying the fragments the first tile's pass already holds -- could save if L1 request throughput is the limit
-#define H2_L12 (((H2_SKIP(11) && sub == 1) || H2_SKIP(10)) ? 0 : lane)
 // bit 10: EVERY fragment load reads one 16-byte piece (all lanes the same address): the kernel without its L1 request stream
 #define H2_LN (H2_SKIP(10) ? 0 : lane)
 // bit 9: the W_ih fragments alone as single L1 accesses from one address (what a W_ih pass over more columns per fragment could approach);
 // bit 8: the STFT's
 #define H2_WIH(addr) ((H2_SKIP(9) || H2_SKIP(13)) ? (P + vadx::silero::OFF_H1) : (addr))
 #define H2_LIH ((H2_SKIP(9) || H2_SKIP(10)) ? 0 : lane)
-#define H2_WST(addr) ((H2_SKIP(8) || (H2_SKIP(12) && sub == 1) || H2_SKIP(13)) ? (P + vadx::silero::OFF_H1) : (addr))
+#define H2_WST(addr) ((H2_SKIP(8) || H2_SKIP(13)) ? (P + vadx::silero::OFF_H1) : (addr))
 #define H2_LST ((H2_SKIP(8) || H2_SKIP(10)) ? 0 : lane)
-#define H2_WS(addr) (((H2_SKIP(12) && sub == 1) || H2_SKIP(13)) ? (P + vadx::silero::OFF_H1) : (addr))
 #if (VADX_EXP >> 14) & 1
 __device__ unsigned long long h2_dbg[16];
 #define H2_T0() long long h2_t_ = __builtin_readcyclecounter(); const long long h2_c0_ = h2_t_, h2_w0_ = wall_clock64()
@@ -141,22 +132,24 @@ constexpr int H2_THREADS = 512;
 //   R0 [0, 65536): X f32 [16 clips][642]
 //                  -> STFT operand planes [E|O][e|o][2 planes][8 k-groups][4 frames x 16 clips][8 fp16]                (65 536 B)
 //                  -> |X| planes [2][4 frames][16 k-groups][16 clips][8 fp16] at 0 (32 768 B) -> conv1 output planes (same shape, in place)
-//                  -> after the last tile's conv2: conv3 output planes [tile][2][8][16][8] at 0, conv4 output planes [tile][2][16][16][8] at 8192
-//      scratch (only while [32768, 65536) is free, i.e. from the STFT's last barrier on): Nyquist magnitudes f32 [4 frames][16 clips],
-//              bin-64 partial sums f32 [8 waves][2 frames][16 clips]; conv2's K-half exchange (8 KB), conv3's (8 KB)
-//   R1 [65536, 81920): conv2 output planes of the workgroup's tiles [tile][2 planes][2 frames][8 k-groups][16][8]
+//                  -> after the last tile's conv3: conv4 output planes [tile][2][16][16][8] at 0 (4 x 8 KB)
+//      from the STFT's last barrier of a tile on (the operand planes are dead): [32768, 65536) holds the f32 scratch (Nyquist magnitudes
+//              [4 frames][16 clips], bin-64 partial sums [8 waves][2 frames][16 clips], the range verdicts), conv2's K-half exchange (8 KB),
+//              conv3's (4 KB) and conv2's output planes [2 planes][2 frames][8 k-groups][16][8] (8 KB) at 53248.  The next tile's staged
+//              window (41 088 B) overwrites none of conv3's inputs, so conv3's epilogue needs no barrier behind it.
+//   R1 [65536, 81920): conv3 output planes of the workgroup's tiles [tile][2 planes][8 k-groups][16][8] -- the only region that lives
+//              through the next tile's staging
 constexpr int H2_EO_PL = 8192, H2_EO_KG = 1024;                 // one (class, e|o, plane) block; one k-group row of 64 columns
 constexpr int H2_PL128 = 16384, H2_FR128 = 4096;
 constexpr int H2_SCR = 32768;                                   // f32 scratch [512]: nyq at +0, bin-64 partials at +256 floats
 constexpr int H2_EXC2 = 36864, H2_EXC3 = 45056;
-#ifndef H2_R1_BASE
-#define H2_R1_BASE 65536      // debugging: 53248 keeps every LDS address below 64 KB (NSUB = 1 only)
-#endif
-constexpr int H2_R1 = H2_R1_BASE, H2_T2 = 8192, H2_PL2 = 4096, H2_FR2 = 2048;
-constexpr int H2_C3 = 0, H2_T3 = 4096, H2_PL3 = 2048;
-constexpr int H2_C4 = 8192, H2_T4 = 8192, H2_PL4 = 4096;
-constexpr int H2_LDS_BYTES = H2_R1 + 2 * H2_T2;
-static_assert(16 * X_LDM * 4 <= 65536 && 2 * H2_LDS_BYTES <= 160 * 1024 && H2_C4 + 2 * H2_T4 <= H2_SCR, "fp16 x 2 encoder LDS map");
+constexpr int H2_C2 = 53248, H2_PL2 = 4096, H2_FR2 = 2048;
+constexpr int H2_R1 = 65536, H2_T3 = 4096, H2_PL3 = 2048;
+constexpr int H2_C4 = 0, H2_T4 = 8192, H2_PL4 = 4096;
+constexpr int H2_NSUB_MAX = 4;
+constexpr int H2_LDS_BYTES = H2_R1 + H2_NSUB_MAX * H2_T3;
+static_assert(16 * X_LDM * 4 <= H2_EXC3 && H2_EXC3 + 4096 <= H2_C2 && H2_C2 + 2 * H2_PL2 <= H2_R1, "fp16 x 2 encoder LDS map: a tile");
+static_assert(H2_C4 + H2_NSUB_MAX * H2_T4 <= H2_SCR && 2 * H2_LDS_BYTES <= 160 * 1024, "fp16 x 2 encoder LDS map: the tail");
 
 __device__ __forceinline__ int hpl_off(int kg8, int clip) { return (kg8 * 16 + clip) * 16; }
 
@@ -202,6 +195,7 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
 
     int tid0 = threadIdx.x;
     const long long ntile = (long long)G * T;
+    (void)ntile;
 #if H2_TRACE
     const int h2_tr_slot = (blockIdx.x % 2503u == 1201u && blockIdx.x / 2503u < 16u) ? (int)(blockIdx.x / 2503u) : -1;
     int h2_tr_off = 0;
@@ -214,27 +208,29 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
     }
     H2_T0();
     const long long blk = blockIdx.x;
+    // the workgroup's tiles: a workgroup's NSUB tiles are CONSECUTIVE WINDOWS of one clip group (H2_PAIR_T: window t = NSUB * (blk / G) + sub
+    // of group blk % G): the next tile's samples are the next 2 KB of the same sixteen rows -- same pages, same DRAM rows as the loads the
+    // previous tile has just made -- instead of sixteen rows 10 MB away (adjacent groups of one window, the round-5 order).  The valid
+    // slots are a prefix of the NSUB; nvalid depends on blockIdx alone (workgroup-uniform), so a slot past the last window skips its whole
+    // tile, barriers included, and the tail multiplies only the nvalid column tiles.
+#if H2_PAIR_T
+    const int nvalid = (int)min((long long)NSUB, (long long)T - (blk / G) * NSUB);
+#else
+    const int nvalid = (int)min((long long)NSUB, ntile - blk * NSUB);
+#endif
     {
     // Cross-phase fragment prefetch: the first sets of a phase's weight stream are requested BEFORE the barrier that ends the phase in front of
     // it (global loads stay in flight across s_barrier, which only waits for lgkmcnt), so the L2 round trip that used to open every phase
     // runs under the previous phase's epilogue.  pre_* = those sets, named per consumer.
 #pragma unroll 1
-    for (int sub = 0; sub < NSUB; ++sub) {
+    for (int sub = 0; sub < nvalid; ++sub) {
     // per tile: nothing derived from the thread index is hoisted out of the tile loop (see silero_split.hip)
-    // the workgroup's tiles: an odd tile count leaves the last workgroup's last slot without work -- it recomputes the last tile (the
-    // barriers are workgroup-wide) and stores nothing
-    // a workgroup's NSUB tiles are CONSECUTIVE WINDOWS of one clip group (H2_PAIR_T: window t = NSUB * (blk / G) + sub of group blk % G): the
-    // second tile's samples are the next 2 KB of the same sixteen rows -- same pages, same DRAM rows as the loads the first tile has just made --
-    // instead of sixteen rows 10 MB away (adjacent groups of one window, the round-5 order)
 #if H2_PAIR_T
-    const int grp = (int)(blk % G), t_raw = (int)(blk / G) * NSUB + sub;
-    const bool tile_valid = t_raw < T;
-    const int t = tile_valid ? t_raw : T - 1;
+    const int grp = (int)(blk % G), t = (int)(blk / G) * NSUB + sub;
     const int tile_id = t * G + grp;
     (void)tile_id;
 #else
-    const long long tile_raw = blk * NSUB + sub;
-    const int tile_id = (int)(tile_raw < ntile ? tile_raw : ntile - 1);
+    const int tile_id = (int)(blk * NSUB + sub);
     const int grp = tile_id % G, t = tile_id / G;
 #endif
 #if H2_TRACE
@@ -471,8 +467,8 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
             load_a2(ab[1], H2_WST(wb + 2 * HF), H2_LST);
             if (H2_XP_ON(1)) {   // conv1's first two sets
                 const float *w1 = P + OFF_H1 + wave * (4 * 3 * 2 * HF);
-                load_a2(pre_1[0], H2_W12(w1), H2_L12);
-                load_a2(pre_1[1], H2_W12(w1 + 2 * HF), H2_L12);
+                load_a2(pre_1[0], H2_W(w1), H2_LN);
+                load_a2(pre_1[1], H2_W(w1 + 2 * HF), H2_LN);
             }
 #pragma unroll
             for (int fr = 0; fr < 2; ++fr) {
@@ -567,7 +563,7 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
 #pragma unroll
             for (int tap = 0; tap < 3; ++tap) {
                 const int s = kc * 3 + tap;
-                if (s + AH < 12) load_a2(a[(s + AH) % (AH + 1)], H2_W12(wq + (s + AH) * 2 * HF), H2_L12);
+                if (s + AH < 12) load_a2(a[(s + AH) % (AH + 1)], H2_W(wq + (s + AH) * 2 * HF), H2_LN);
                 const f16x8 (&ac)[2] = a[s % (AH + 1)];
                 // three products per (frame, tap), frames innermost so that consecutive MFMAs hit different accumulators
 #define H2_TERM(AP, BP, ACC)                                                                  \
@@ -582,8 +578,8 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
         H2_PRIO_OFF();
         if (H2_XP_ON(2)) {   // conv2's first two sets
             const float *w2 = P + OFF_H2 + ((wave & 3) * 4 + 2 * (wave >> 2)) * (3 * 2 * HF);
-            load_a2(pre_2[0], H2_W12(w2), H2_L12);
-            load_a2(pre_2[1], H2_W12(w2 + 2 * HF), H2_L12);
+            load_a2(pre_2[0], H2_W(w2), H2_LN);
+            load_a2(pre_2[1], H2_W(w2 + 2 * HF), H2_LN);
         }
         H2_SYNC(6);          // every wave is done reading the |X| planes: conv1's output may now overwrite them
         H2_MARK(5);
@@ -616,7 +612,7 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
         }
         if (RING == 6) {
 #pragma unroll
-            for (int s = 2; s < 6; ++s) load_a2(a[s % RING], H2_W12(wq + s * 2 * HF), H2_L12);
+            for (int s = 2; s < 6; ++s) load_a2(a[s % RING], H2_W(wq + s * 2 * HF), H2_LN);
         }
         H2_PRIO_ON();
 #pragma unroll
@@ -627,7 +623,7 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
 #pragma unroll
             for (int tap = 0; tap < 3; ++tap) {
                 const int s = kk * 3 + tap;
-                if (RING == 3 && s + 2 < 6) load_a2(a[(s + 2) % RING], H2_W12(wq + (s + 2) * 2 * HF), H2_L12);
+                if (RING == 3 && s + 2 < 6) load_a2(a[(s + 2) % RING], H2_W(wq + (s + 2) * 2 * HF), H2_LN);
                 const f16x8 (&ac)[2] = a[s % RING];
 #define H2_TERM(AP, BP, ACC)                                                                  \
     _Pragma("unroll") for (int o = 0; o < 2; ++o) {                                           \
@@ -654,68 +650,61 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
                 f32x4 y;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) y[r] = fmaxf(s2[o][r] + other[r] + bias[r], 0.f);
-                store_h4(smem + H2_R1 + sub * H2_T2 + o * H2_FR2, H2_PL2, 4 * rt + q, i, y, amax);
+                store_h4(smem + H2_C2 + o * H2_FR2, H2_PL2, 4 * rt + q, i, y, amax);
             }
         }
     }
-    H2_SYNC(9);
-    H2_MARK(7);
-    }      // sub
-
-#if H2_TRACE
-    h2_tr_off = 64 - 2 * 10;          // the joint tail's barriers (H2_SYNC(10) ...) land at marks 64 ...
-#endif
-    constexpr int AHEAD = NSUB > 1 ? H2_AHI : 3;      // W_ih's stream runs this many steps ahead
-    f16x8 pre_3[2][2], pre_4[2][2], pre_ih[AHEAD][2];
-    {   H2_IDS();
-        // conv3's two sets (not requested inside the tile loop: a value that only the last iteration defines would be carried, and spilled, around it)
+    f16x8 pre_3[2][2];                  // conv3's two sets: in flight across the barrier
+    {
+        H2_IDS();
         const float *w3 = P + OFF_H3 + ((wave & 3) * 2 + (wave >> 2)) * (2 * 2 * HF);
         load_a2(pre_3[0], H2_W(w3), H2_LN);
         load_a2(pre_3[1], H2_W(w3 + 2 * HF), H2_LN);
     }
-    // ---------------- phase 4: conv3 64->64, k3 s2 p1, ReLU (one output frame; tap 0 reads padding), both tiles: wave = (16 channels, tap 1 | 2)
+    H2_SYNC(9);
+    H2_MARK(7);
+
+    // ---------------- phase 4: conv3 64->64, k3 s2 p1, ReLU (one output frame; tap 0 reads padding): wave = (16 channels, tap 1 | 2).  Its
+    // output goes to the tile's slot of R1; the next tile's staging touches none of conv3's inputs (see the LDS map), so no barrier follows
     {
         H2_IDS();
         const int rt = wave & 3, th = wave >> 2;      // tap th + 1 reads conv2's frame th
-        f32x4 hi[NSUB], mid[NSUB];
+        f32x4 hi = {0.f, 0.f, 0.f, 0.f}, mid = hi;
 #pragma unroll
-        for (int sb = 0; sb < NSUB; ++sb) { hi[sb] = f32x4{0.f, 0.f, 0.f, 0.f}; mid[sb] = hi[sb]; }
-        if (H2_XP_ON(3)) {   // conv4's two sets
-            const float *w4 = P + OFF_H4 + wave * (2 * 2 * HF);
-            load_a2(pre_4[0], H2_W(w4), H2_LN);
-            load_a2(pre_4[1], H2_W(w4 + 2 * HF), H2_LN);
+        for (int kc = 0; kc < 2; ++kc) {
+            f16x8 b[2];
+            load_b2(b, smem + H2_C2 + th * H2_FR2, H2_PL2, kc, q, i);
+            if (!H2_SKIP(3)) mfma_split3(pre_3[kc], b, hi, mid);
         }
-        const f16x8 (&a)[2][2] = pre_3;
-#pragma unroll
-        for (int kc = 0; kc < 2; ++kc)
-#pragma unroll
-            for (int sb = 0; sb < NSUB; ++sb) {
-                f16x8 b[2];
-                load_b2(b, smem + H2_R1 + sb * H2_T2 + th * H2_FR2, H2_PL2, kc, q, i);
-                if (!H2_SKIP(3)) mfma_split3(a[kc], b, hi[sb], mid[sb]);
-            }
         float *exc = reinterpret_cast<float *>(smem + H2_EXC3);
-        if (th == 1) {
-#pragma unroll
-            for (int sb = 0; sb < NSUB; ++sb) *reinterpret_cast<f32x4 *>(exc + ((sb * 4 + rt) * 64 + lane) * 4) = join2(hi[sb], mid[sb]);
-        }
+        if (th == 1) *reinterpret_cast<f32x4 *>(exc + (rt * 64 + lane) * 4) = join2(hi, mid);
         H2_SYNC(10);
         if (th == 0) {
             const f32x4 bias = ldg4(P + OFF_B3 + 16 * rt + 4 * q);
+            const f32x4 s3 = join2(hi, mid), other = *reinterpret_cast<const f32x4 *>(exc + (rt * 64 + lane) * 4);
+            f32x4 y;
 #pragma unroll
-            for (int sb = 0; sb < NSUB; ++sb) {
-                const f32x4 s3 = join2(hi[sb], mid[sb]), other = *reinterpret_cast<const f32x4 *>(exc + ((sb * 4 + rt) * 64 + lane) * 4);
-                f32x4 y;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) y[r] = fmaxf(s3[r] + other[r] + bias[r], 0.f);
-                store_h4(smem + H2_C3 + sb * H2_T3, H2_PL3, 4 * rt + q, i, y, amax);
-            }
+            for (int r = 0; r < 4; ++r) y[r] = fmaxf(s3[r] + other[r] + bias[r], 0.f);
+            store_h4(smem + H2_R1 + sub * H2_T3, H2_PL3, 4 * rt + q, i, y, amax);
         }
     }
-    H2_SYNC(11);
     H2_MARK(8);
+    }      // sub
 
-    // ---------------- phase 5: conv4 64->128, k3 s1 p1, ReLU (one frame in / out: centre tap only), both tiles
+#if H2_TRACE
+    h2_tr_off = 96;                     // the tail's barriers (H2_SYNC(11), H2_SYNC(12)) land at marks 118 .. 121
+#endif
+    // W_ih step j (0 .. 15) multiplies fragment pair s = 4 kc + g: gate half gh = j / 8 (gates 2 gh, 2 gh + 1), kc = (j / 2) % 4, g = 2 gh + j % 2
+    auto ih_s = [](int j) { return 4 * ((j >> 1) & 3) + 2 * (j >> 3) + (j & 1); };
+    f16x8 pre_4[2][2], pre_ih[2][2];
+    if (H2_XP_ON(3)) {   // conv4's two sets, requested before the barrier that ends the last tile's conv3
+        H2_IDS();
+        const float *w4 = P + OFF_H4 + wave * (2 * 2 * HF);
+        load_a2(pre_4[0], H2_W(w4), H2_LN);
+        load_a2(pre_4[1], H2_W(w4 + 2 * HF), H2_LN);
+    }
+    H2_SYNC(11);         // every tile's conv3 planes are in R1; R0 is free
+    // ---------------- phase 5: conv4 64->128, k3 s1 p1, ReLU (one frame in / out: centre tap only), the nvalid tiles at once: R1 -> R0
     {
         H2_IDS();
         const int rt = wave;
@@ -723,12 +712,11 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
         f32x4 hi[NSUB], mid[NSUB];
 #pragma unroll
         for (int sb = 0; sb < NSUB; ++sb) { hi[sb] = bias; mid[sb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        if (H2_XP_ON(3)) {   // W_ih's first sets
+        if (H2_XP_ON(3)) {   // W_ih's first two sets
             const float *wi = P + OFF_HIH + wave * (4 * 4 * 2 * HF);
 #pragma unroll
-            for (int s0_ = 0; s0_ < AHEAD; ++s0_) load_a2(pre_ih[s0_], H2_WIH(wi + s0_ * 2 * HF), H2_LIH);
-        }
-        if (!H2_XP_ON(3)) {
+            for (int s0_ = 0; s0_ < 2; ++s0_) load_a2(pre_ih[s0_], H2_WIH(wi + ih_s(s0_) * 2 * HF), H2_LIH);
+        } else {
             const float *w4 = P + OFF_H4 + wave * (2 * 2 * HF);
             load_a2(pre_4[0], H2_W(w4), H2_LN);
             load_a2(pre_4[1], H2_W(w4 + 2 * HF), H2_LN);
@@ -738,17 +726,21 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
         for (int kc = 0; kc < 2; ++kc)
 #pragma unroll
             for (int sb = 0; sb < NSUB; ++sb) {
-                f16x8 b[2];
-                load_b2(b, smem + H2_C3 + sb * H2_T3, H2_PL3, kc, q, i);
-                if (!H2_SKIP(3)) mfma_split3(a[kc], b, hi[sb], mid[sb]);
+                if (sb < nvalid) {
+                    f16x8 b[2];
+                    load_b2(b, smem + H2_R1 + sb * H2_T3, H2_PL3, kc, q, i);
+                    if (!H2_SKIP(3)) mfma_split3(a[kc], b, hi[sb], mid[sb]);
+                }
             }
 #pragma unroll
         for (int sb = 0; sb < NSUB; ++sb) {
-            const f32x4 s = join2(hi[sb], mid[sb]);
-            f32x4 y;
+            if (sb < nvalid) {
+                const f32x4 s = join2(hi[sb], mid[sb]);
+                f32x4 y;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) y[r] = fmaxf(s[r], 0.f);
-            store_h4(smem + H2_C4 + sb * H2_T4, H2_PL4, 4 * rt + q, i, y, amax);
+                for (int r = 0; r < 4; ++r) y[r] = fmaxf(s[r], 0.f);
+                store_h4(smem + H2_C4 + sb * H2_T4, H2_PL4, 4 * rt + q, i, y, amax);
+            }
         }
         // nothing is split after this point: the workgroup's verdict on the fp16 range (one word per wave, read behind the barrier below)
         const bool bad = !(amax <= H_MAX);
@@ -758,66 +750,70 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
     H2_SYNC(12);
     H2_MARK(9);
 
-    // ---------------- phase 6: LSTM input projection for the workgroup's tiles at once, gate-major (D rows = hidden units
-    // 16 wave + 4 q + r, columns = clips): every W_ih fragment is loaded once and multiplies NSUB column tiles
+    // ---------------- phase 6: LSTM input projection for the workgroup's tiles at once (D rows = hidden units 16 wave + 4 q + r, columns =
+    // clips), in two gate halves {0, 1}, {2, 3} so that the accumulators of four column tiles fit: every W_ih fragment pair is loaded once
+    // and multiplies the nvalid column tiles (the B planes are read once per half)
     {
         H2_IDS();
-        f32x4 hi[NSUB][4], mid[NSUB][4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 bg = ldg4(P + OFF_BG + g * 128 + wave * 16 + 4 * q);
-#pragma unroll
-            for (int sb = 0; sb < NSUB; ++sb) { hi[sb][g] = bg; mid[sb][g] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        }
+        // a workgroup that split anything outside the fp16 range hands the recurrent kernel NaN, not numbers that look like gate
+        // pre-activations: a caller that never reads vadx_silero_range_flag gets NaN scores for these clips, not plausible ones
+        const unsigned *bw = reinterpret_cast<const unsigned *>(scr) + 128;
+        const bool poison = __builtin_amdgcn_readfirstlane((int)(bw[0] | bw[1] | bw[2] | bw[3] | bw[4] | bw[5] | bw[6] | bw[7])) != 0;
         const float *wq = P + OFF_HIH + wave * (4 * 4 * 2 * HF);
-        f16x8 a[AHEAD + 1][2];
+        // the fragment ring holds two k-chunks (the current one's two gates and the next one's, requested when the current one starts)
+        f16x8 a[2][2][2];
 #pragma unroll
-        for (int s0_ = 0; s0_ < AHEAD; ++s0_) {
-            if (H2_XP_ON(3)) { a[s0_][0] = pre_ih[s0_][0]; a[s0_][1] = pre_ih[s0_][1]; }
-            else load_a2(a[s0_], H2_W(wq + s0_ * 2 * HF), H2_LN);
+        for (int gg = 0; gg < 2; ++gg) {
+            if (H2_XP_ON(3)) { a[0][gg][0] = pre_ih[gg][0]; a[0][gg][1] = pre_ih[gg][1]; }
+            else load_a2(a[0][gg], H2_WIH(wq + ih_s(gg) * 2 * HF), H2_LIH);
         }
-        H2_PRIO_ON();
 #pragma unroll
-        for (int kc = 0; kc < 4; ++kc) {
-            f16x8 b[NSUB][2];
+        for (int gh = 0; gh < 2; ++gh) {
+            f32x4 hi[NSUB][2], mid[NSUB][2];
 #pragma unroll
-            for (int sb = 0; sb < NSUB; ++sb) load_b2(b[sb], smem + H2_C4 + sb * H2_T4, H2_PL4, kc, q, i);
+            for (int gg = 0; gg < 2; ++gg) {
+                const f32x4 bg = ldg4(P + OFF_BG + (2 * gh + gg) * 128 + wave * 16 + 4 * q);
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int s = kc * 4 + g;
-                if (s + AHEAD < 16) load_a2(a[(s + AHEAD) % (AHEAD + 1)], H2_WIH(wq + (s + AHEAD) * 2 * HF), H2_LIH);
-                const f16x8 (&ac)[2] = a[s % (AHEAD + 1)];
-                if (!H2_SKIP(6)) {
-#define H2_TERM(AP, BP, ACC) _Pragma("unroll") for (int sb = 0; sb < NSUB; ++sb) ACC[sb][g] = mfma_f16(ac[AP], b[sb][BP], ACC[sb][g]);
-                    H2_TERM(1, 0, mid) H2_TERM(0, 1, mid) H2_TERM(0, 0, hi)
-#undef H2_TERM
+                for (int sb = 0; sb < NSUB; ++sb) { hi[sb][gg] = bg; mid[sb][gg] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+            }
+            H2_PRIO_ON();
+#pragma unroll
+            for (int kc = 0; kc < 4; ++kc) {
+                const int j = 8 * gh + 2 * kc;            // the step of (kc, gate 2 gh)
+#pragma unroll
+                for (int gg = 0; gg < 2; ++gg)
+                    if (j + 2 < 16) load_a2(a[((j >> 1) + 1) & 1][gg], H2_WIH(wq + ih_s(j + 2 + gg) * 2 * HF), H2_LIH);
+                const f16x8 (&ac)[2][2] = a[(j >> 1) & 1];
+                // column tile outermost: one tile's B pair is live at a time (a single accumulation chain costs the 16x16x32 MFMA nothing)
+#pragma unroll
+                for (int sb = 0; sb < NSUB; ++sb) {
+                    if (sb < nvalid) {
+                        f16x8 b[2];
+                        load_b2(b, smem + H2_C4 + sb * H2_T4, H2_PL4, kc, q, i);
+#pragma unroll
+                        for (int gg = 0; gg < 2; ++gg)
+                            if (!H2_SKIP(6)) mfma_split3(ac[gg], b, hi[sb][gg], mid[sb][gg]);
+                    }
                 }
             }
-        }
-        H2_PRIO_OFF();
+            H2_PRIO_OFF();
 #pragma unroll
-        for (int sb = 0; sb < NSUB; ++sb) {
+            for (int sb = 0; sb < NSUB; ++sb) {
+                if (sb >= nvalid) continue;
 #if H2_PAIR_T
-            const int grp_s = (int)(blk % G), t_s = (int)(blk / G) * NSUB + sb;
-            const long long tile_raw = t_s < T ? 0 : ntile;          // (valid / not, for the test below)
-            float *dst = gx + ((size_t)(t_s < T ? t_s : T - 1) * Gws + g0 + grp_s) * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
+                const int t_s = (int)(blk / G) * NSUB + sb, grp_s = (int)(blk % G);
+                float *dst = gx + ((size_t)t_s * Gws + g0 + grp_s) * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
 #else
-            const long long tile_raw = blk * NSUB + sb;
-            const int tile_id = (int)(tile_raw < ntile ? tile_raw : ntile - 1);
-            float *dst = gx + ((size_t)(tile_id / G) * Gws + g0 + tile_id % G) * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
+                const int tile_s = (int)(blk * NSUB + sb);
+                float *dst = gx + ((size_t)(tile_s / G) * Gws + g0 + tile_s % G) * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
 #endif
-            // a workgroup that split anything outside the fp16 range hands the recurrent kernel NaN, not numbers that look like gate
-            // pre-activations: a caller that never reads vadx_silero_range_flag gets NaN scores for these clips, not plausible ones
-            const unsigned *bw = reinterpret_cast<const unsigned *>(scr) + 128;
-            const bool poison = __builtin_amdgcn_readfirstlane((int)(bw[0] | bw[1] | bw[2] | bw[3] | bw[4] | bw[5] | bw[6] | bw[7])) != 0;
-            if (tile_raw < ntile) {
                 if (!poison) {           // (workgroup-uniform: a branch, not 32 selects)
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x4 *>(dst + g * 256) = join2(hi[sb][g], mid[sb][g]);
+                    for (int gg = 0; gg < 2; ++gg) *reinterpret_cast<f32x4 *>(dst + (2 * gh + gg) * 256) = join2(hi[sb][gg], mid[sb][gg]);
                 } else {
                     const float qnan = __builtin_nanf("");
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x4 *>(dst + g * 256) = f32x4{qnan, qnan, qnan, qnan};
+                    for (int gg = 0; gg < 2; ++gg) *reinterpret_cast<f32x4 *>(dst + (2 * gh + gg) * 256) = f32x4{qnan, qnan, qnan, qnan};
                 }
             }
         }
@@ -988,15 +984,17 @@ int silero_lstm_h2_launch(const float *packed, const float *gx, const float *sta
     return VADX_OK;
 }
 
-// VADX_H2_NSUB: tiles a workgroup encodes one after the other before ONE joint conv3 / conv4 / W_ih pass
+// VADX_H2_NSUB: tiles a workgroup encodes one after the other before ONE joint conv4 / W_ih pass (at most H2_NSUB_MAX: R1 holds their
+// conv3 planes)
 #ifndef VADX_H2_NSUB
-#define VADX_H2_NSUB 2
+#define VADX_H2_NSUB 4
 #endif
 template <typename S>
 int silero_encode_h2_launch(const float *packed, const S *src, float in_scale, long long n_valid, long long row_stride,
                             long long origin, int batch, int G, int steps, int Gws, int first_group, float *gx, void *stream) {
     constexpr int NS = VADX_H2_NSUB;
-    constexpr int LDS = (H2_R1 + NS * H2_T2 > 65536 ? H2_R1 + NS * H2_T2 : 65536) + H2_LDS_PAD;
+    static_assert(NS >= 1 && NS <= H2_NSUB_MAX, "VADX_H2_NSUB");
+    constexpr int LDS = H2_LDS_BYTES + H2_LDS_PAD;
     VADX_DYN_LDS((silero_encode_h2_kernel<S, NS>), LDS);
     const long long nblk = H2_PAIR_T ? (long long)G * ((steps + NS - 1) / NS) : ((long long)G * steps + NS - 1) / NS;
     hipLaunchKernelGGL((silero_encode_h2_kernel<S, NS>), dim3((unsigned)nblk), dim3(H2_THREADS), LDS, static_cast<hipStream_t>(stream),
