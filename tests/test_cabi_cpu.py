@@ -265,8 +265,8 @@ def test_header_is_plain_c_and_a_c_client_links(tmp_path):
 
 def test_no_cross_swizzled_packed_f32_in_product_kernels():
     """DESIGN 4e / VERDICT r5 weak 4: a compiler-formed `v_pk_add_f32` whose second source is read with the CROSS swizzle
-    (op_sel:[0,1] op_sel_hi:[1,0]) gives wrong sums inside silero_encode_h2_kernel at four waves per SIMD (still reproducible: build with
-    -DH2_PK_NATURAL=1, tests/probes/pk_hazard.py), while the same instruction -- own destination, in place, fresh LDS data behind partial
+    (op_sel:[0,1] op_sel_hi:[1,0]) gives wrong sums inside silero_encode_h2_kernel at four waves per SIMD (profiles/r06_pk_hazard.txt;
+    reproducible with the -DH2_PK_NATURAL=1 build of commit 22abfc0, the last that has the switch), while the same instruction -- own destination, in place, fresh LDS data behind partial
     waits, sources overwritten at once -- is exact in the standalone reproducer (tests/hip/pk_hazard.hip): the root cause is not
     established, so the pattern is BANNED from the product.  The library is built with -fno-slp-vectorize (the SLP vectoriser is what forms
     the swizzled forms; vadx.build.FLAGS) and this test disassembles every gfx950 code object in libvadx.so (tools/pk_scan.py) and fails on

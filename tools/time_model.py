@@ -1,4 +1,4 @@
-"""Time one model's full-size secondary config with the library named by VADX_LIBRARY (what-if builds of tools/exp_lib.py) and print a
+"""Time one model's full-size secondary config with the library named by VADX_LIBRARY (an A/B build) and print a
    checksum of its decisions:  python tools/time_model.py fsmn [clips]"""
 import hashlib
 import sys

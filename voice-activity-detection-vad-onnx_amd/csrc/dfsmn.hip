@@ -18,13 +18,6 @@
 #include <type_traits>
 #include <string.h>
 
-// DFSMN_EXP: development-only what-if switches (bit mask; results are wrong when set): 1 lstm_f without its output
-// stores, 2 without input loads, 4 without gate non-linearities; dft_f: 8 one k-step instead of all, 16 no copy-out,
-// 32 no input request / park, 64 no per-channel barrier; lstm_f: 128 no input-half MFMAs, 256 no recurrent MFMAs
-#ifndef DFSMN_EXP
-#define DFSMN_EXP 0
-#endif
-
 namespace vadx {
 namespace dfsmn {
 
@@ -576,24 +569,24 @@ __device__ __forceinline__ void dft_f_body(const DftArgs &p, const int rt0, floa
     for (int c = 0; c < p.C; ++c) {
         const float *B = Bs[c & 1];
         float *O = Os[c & 1];
-        if (c + 1 < p.C && !(DFSMN_EXP & 32)) request(c + 1);
+        if (c + 1 < p.C) request(c + 1);
         f32x4 acc[RT];
 #pragma unroll
         for (int h = 0; h < RT; ++h) acc[h] = f32x4{0.f, 0.f, 0.f, 0.f};
         // the B column is read KB k-steps at a time, the next batch requested before this batch's MFMAs issue (left to
         // itself the compiler emits read -> wait -> 2 MFMAs: one exposed LDS round trip per k-step)
-        constexpr int KB = 8, KSX = (DFSMN_EXP & 8) ? 1 : KS;
+        constexpr int KB = 8;
         float bcur[KB], bnxt[KB];
 #pragma unroll
         for (int u = 0; u < KB; ++u) bcur[u] = B[(4 * u + q) * 16 + i];
 #pragma unroll
-        for (int s0 = 0; s0 < KSX; s0 += KB) {
+        for (int s0 = 0; s0 < KS; s0 += KB) {
 #pragma unroll
             for (int u = 0; u < KB; ++u) bnxt[u] = B[(4 * min(s0 + KB + u, KS - 1) + q) * 16 + i];
             __builtin_amdgcn_sched_barrier(0);           // keep the reads above the MFMAs (the scheduler sinks them back)
 #pragma unroll
             for (int u = 0; u < KB; ++u)
-                if (s0 + u < KSX) {
+                if (s0 + u < KS) {
 #pragma unroll
                     for (int h = 0; h < RT; ++h) acc[h] = mfma16(ta[h][s0 + u], bcur[u], acc[h]);
                 }
@@ -604,9 +597,8 @@ __device__ __forceinline__ void dft_f_body(const DftArgs &p, const int rt0, floa
         for (int h = 0; h < RT; ++h)
 #pragma unroll
             for (int r = 0; r < 4; ++r) O[((rt0 + h) * 16 + 4 * q + r) * 16 + i] = acc[h][r];
-        if (c + 1 < p.C && !(DFSMN_EXP & 32)) park(Bs[(c + 1) & 1]);
-        if (!(DFSMN_EXP & 64)) __syncthreads();
-        if ((DFSMN_EXP & 16) && acc[0][0] != 123.f) continue;
+        if (c + 1 < p.C) park(Bs[(c + 1) & 1]);
+        __syncthreads();
         // copy-out of channel c (reads O; O is next written two channels later, after the next barrier)
         if (!INV) {          // rows 0..80 = cos bins -> channel c; rows 81..159 = sin bins 1..79 -> channel C + c, whose bins 0, 80 are zero
             StatAcc st;
@@ -634,14 +626,13 @@ __device__ __forceinline__ void dft_f_body(const DftArgs &p, const int rt0, floa
     }
 }
 
+// bit mask of the two waves that own three row tiles: 0 and 2 measured best (fwd 1.30 ms; {0,1} 1.39, {0,3} 1.40, {1,2} 1.41)
+constexpr int DFT_HEAVY = 0x5;
 template <bool INV>
 __global__ __launch_bounds__(DFT_NT, 2) void dft_f_kernel(DftArgs p) {
     __shared__ __attribute__((aligned(16))) float Bs[2][DFT_K * 16];
     __shared__ __attribute__((aligned(16))) float Os[2][DFT_ROWS * 16];
     const int wave = threadIdx.x >> 6;
-#ifndef DFT_HEAVY
-#define DFT_HEAVY 0x5            /* bit mask of the two waves that own three row tiles: 0 and 2 measured best (fwd 1.30 ms; {0,1} 1.39, {0,3} 1.40, {1,2} 1.41) */
-#endif
     const bool heavy = (DFT_HEAVY >> wave) & 1;
     const int rank = __builtin_popcount((heavy ? DFT_HEAVY : ~DFT_HEAVY & 0xf) & ((1 << wave) - 1));     // 0 or 1 among its kind
     if (heavy) dft_f_body<INV, 3>(p, 3 * rank, Bs, Os);
@@ -710,7 +701,6 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void l
         for (int r = 0; r < NLD; ++r) {
             const int row = (lane >> 2) + 16 * r, b = row / IN, ch = row - b * IN, f = bin_of(ck, b);
             pre[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (DFSMN_EXP & 2) continue;
             const int fcl = f < 0 ? 0 : (f >= p.F ? p.F - 1 : f);        // unconditional (clamped) loads; bins past the end are never used
             pre[r] = *reinterpret_cast<const f32x4 *>(p.in.ptr + ft_idx(tile, p.in.c_total, p.in.c_off + ch, p.F, fcl) + 4 * tq);
             if constexpr (HAS_LN) { lw[r] = p.ln.w[ch * p.F + fcl]; lb[r] = p.ln.b[ch * p.F + fcl]; }
@@ -773,7 +763,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void l
 #pragma unroll
             for (int s = 0; s < MT; ++s)
 #pragma unroll
-                for (int mt = 0; mt < MT; ++mt) if (!(DFSMN_EXP & 256)) acc[mt] = mfma16(wh[mt][s], h[s], acc[mt]);
+                for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma16(wh[mt][s], h[s], acc[mt]);
             __builtin_amdgcn_sched_barrier(0);
             // The matrix pipe takes 32 cycles per MFMA, during which the wave can issue three to four other instructions.  Left
             // to itself the scheduler emits the next input half as two runs of MFMAs and the gate arithmetic as ~50-instruction
@@ -781,36 +771,35 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void l
             // input-half MFMAs of step t+1 + one slice of step t's gate arithmetic, fenced by sched_barriers.
             constexpr int NIN = MT * KI, PIECES = 5, PER = (NIN + MT * PIECES - 1) / (MT * PIECES);
             auto in_mfma = [&](int n) {                         // n-th MFMA of a = bias + W_ih x  (k-step n / MT, row tile n % MT)
-                if (n >= NIN || (DFSMN_EXP & 128)) return;
+                if (n >= NIN) return;
                 const int s2 = n / MT, m2 = n % MT;
                 if (s2 == 0) accn[m2] = f32x4{bias[m2][0], bias[m2][1], bias[m2][2], bias[m2][3]};
                 accn[m2] = mfma16(wi[m2][s2], xv[s2], accn[m2]);
             };
-            const bool lin = DFSMN_EXP & 4;
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 int n = mt * PIECES * PER;
 #pragma unroll
                 for (int u = 0; u < PER; ++u) in_mfma(n++);
-                const float ig = lin ? acc[mt][0] : gate_sigmoid(acc[mt][0]);
+                const float ig = gate_sigmoid(acc[mt][0]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < PER; ++u) in_mfma(n++);
-                const float fg = lin ? acc[mt][1] * 0.1f : gate_sigmoid(acc[mt][1]);
+                const float fg = gate_sigmoid(acc[mt][1]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < PER; ++u) in_mfma(n++);
-                const float gg = lin ? acc[mt][2] : gate_tanh(acc[mt][2]);
+                const float gg = gate_tanh(acc[mt][2]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < PER; ++u) in_mfma(n++);
-                const float og = lin ? acc[mt][3] : gate_sigmoid(acc[mt][3]);
+                const float og = gate_sigmoid(acc[mt][3]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < PER; ++u) in_mfma(n++);
                 c[mt] = fg * c[mt] + ig * gg;
-                h[mt] = lin ? og * c[mt] * 0.01f : og * gate_tanh(c[mt]);
-                if (!(DFSMN_EXP & 1) || h[mt] == 123.f) p.out.ptr[ft_idx(tile, p.out.c_total, p.out.c_off + dir * H + 4 * mt + q, p.F, f) + i] = h[mt];
+                h[mt] = og * gate_tanh(c[mt]);
+                p.out.ptr[ft_idx(tile, p.out.c_total, p.out.c_off + dir * H + 4 * mt + q, p.F, f) + i] = h[mt];
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -1340,9 +1329,6 @@ __global__ __launch_bounds__(128 * NTILE) void lstm_t2_kernel(LstmTArgs p) {
 //   The output Linear takes layer 1's NEW own chunk and chunk 2 (its weights are zero on the h0 / empty slots).  Biases are the
 //   accumulators' initial value (exact float32 adds, as in the f32 kernel).  h lies in (-1, 1); x and the weights feed the range check.
 // ---------------------------------------------------------------------------------------------
-#ifndef LT_EXP
-#define LT_EXP 0         /* development what-ifs of lstm_t2h_kernel: 1 no transcendentals, 2 no MFMAs, 4 no per-step loads, 8 no stores, 16 one fragment read per GEMM */
-#endif
 template <int NPAIR>
 __device__ __forceinline__ void gemm_h2_lds(f32x4 *hi, f32x4 *mid, const unsigned char *w, int frag_stride2, const f16x8 (&b)[2]) {
     // NPAIR pairs of row tiles against one chunk's operand b; fragment pair of row tile mt at w + mt * frag_stride2 (+ 1024 for plane 1).
@@ -1358,20 +1344,14 @@ __device__ __forceinline__ void gemm_h2_lds(f32x4 *hi, f32x4 *mid, const unsigne
     load(0, cur);
 #pragma unroll
     for (int pr = 0; pr < NPAIR; ++pr) {
-        if (pr + 1 < NPAIR && !(LT_EXP & 16)) load(pr + 1, nxt);
-        if (LT_EXP & 16) { nxt[0][0] = cur[0][0]; nxt[0][1] = cur[0][1]; nxt[1][0] = cur[1][0]; nxt[1][1] = cur[1][1]; }
+        if (pr + 1 < NPAIR) load(pr + 1, nxt);
         __builtin_amdgcn_sched_barrier(0);
-        if (!(LT_EXP & 2)) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) mid[2 * pr + u] = vadx::mfma_f16(cur[u][1], b[0], mid[2 * pr + u]);
 #pragma unroll
         for (int u = 0; u < 2; ++u) mid[2 * pr + u] = vadx::mfma_f16(cur[u][0], b[1], mid[2 * pr + u]);
 #pragma unroll
         for (int u = 0; u < 2; ++u) hi[2 * pr + u] = vadx::mfma_f16(cur[u][0], b[0], hi[2 * pr + u]);
-        } else {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) hi[2 * pr + u][0] += (float)cur[u][0][0] * (float)b[0][0];
-        }
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -1475,7 +1455,6 @@ __global__ __launch_bounds__(128 * NTILE) void lstm_t2h_kernel(LstmTArgs p, unsi
         tile = gfr >> 4; t16 = gfr & 15;
     };
     auto load_x_group = [&](int t0) {                            // layer 0: the next group's inputs
-        if ((LT_EXP & 4) && t0 > 0) return;
         int tile, t16;
         group_pos(t0, tile, t16);
 #pragma unroll
@@ -1488,7 +1467,6 @@ __global__ __launch_bounds__(128 * NTILE) void lstm_t2h_kernel(LstmTArgs p, unsi
         }
     };
     auto load_mul_group = [&](int t0) {                          // layer 1, MODE 0: this group's multipliers (first used at the step's end)
-        if ((LT_EXP & 4) && t0 > 0) return;
         int tile, t16;
         group_pos(t0, tile, t16);
 #pragma unroll
@@ -1550,11 +1528,10 @@ __global__ __launch_bounds__(128 * NTILE) void lstm_t2h_kernel(LstmTArgs p, unsi
                 for (int u = 0; u < 2 * NPR; ++u) {
                     const int mt = T0 + u;
                     const f32x4 a = vadx::join2(hi[u], mid[u]);
-                    const bool lin = LT_EXP & 1;
-                    const float ig = lin ? a[0] * 0.1f : gate_sigmoid(a[0]), fg = lin ? a[1] * 0.1f : gate_sigmoid(a[1]);
-                    const float gg = lin ? a[2] * 0.1f : gate_tanh(a[2]), og2 = lin ? a[3] * 0.1f : gate_sigmoid(a[3]);
+                    const float ig = gate_sigmoid(a[0]), fg = gate_sigmoid(a[1]);
+                    const float gg = gate_tanh(a[2]), og2 = gate_sigmoid(a[3]);
                     c[mt] = fg * c[mt] + ig * gg;
-                    h[mt] = lin ? og2 * c[mt] * 0.1f : og2 * gate_tanh(c[mt]);
+                    h[mt] = og2 * gate_tanh(c[mt]);
                 }
             };
             pass(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
@@ -1592,7 +1569,7 @@ __global__ __launch_bounds__(128 * NTILE) void lstm_t2h_kernel(LstmTArgs p, unsi
 #pragma unroll
                     for (int k = 0; k < 4; ++k) og[j][k] = (j4 == k) ? v : og[j][k];
                 }
-                if ((j4 == 3 || t == p.T - 1) && live && !(LT_EXP & 8)) {        // the group's outputs leave together
+                if ((j4 == 3 || t == p.T - 1) && live) {        // the group's outputs leave together
                     int tile, t16;
                     group_pos(t - j4, tile, t16);
 #pragma unroll

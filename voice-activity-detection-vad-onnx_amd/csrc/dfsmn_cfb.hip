@@ -31,32 +31,6 @@
 #include <string.h>
 #include <type_traits>
 
-// CFB_EXP: development-only what-if switches (bit mask; results are wrong when set; tools/exp_cfb.py): 1 no workgroup barriers in the
-// chunk loops, 2 no global loads of the chunk rows, 4 no gate / input conv MFMAs, 8 no (3,1) conv, 16 no DFT accumulation,
-// 32 no gate arithmetic / statistics, 64 no y1 stores, 128 no Linear + complex product (back), 256 no epilogue stores,
-// 512 no y1 loads in cfb_back's prologue, 1024 no prologue transposes
-#ifndef CFB_EXP
-#define CFB_EXP 0
-#endif
-#define CFB_SYNC() do { if (!(CFB_EXP & 1)) __syncthreads(); } while (0)
-// bit 2048: cycle accounting (s_memtime deltas of lane 0 of the first producer and the first DFT wave, summed over all workgroups
-// into cfb_dbg[slot]; vadx_cfb_debug_cycles reads / clears them): slot = 8 * kernel (0 front, 1 back) + 4 * role + section
-#if CFB_EXP & 2048
-__device__ unsigned long long cfb_dbg[32];
-#define CFB_T0() long long cfb_t_ = __builtin_readcyclecounter(); unsigned long long cfb_a_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define CFB_MARK(slot) do { const long long n_ = __builtin_readcyclecounter(); cfb_a_[(slot) & 7] += (unsigned long long)(n_ - cfb_t_); cfb_t_ = n_; } while (0)
-#define CFB_FLUSH(base) do { if ((threadIdx.x & 255) == 0) for (int k_ = 0; k_ < 8; ++k_) if (cfb_a_[k_]) atomicAdd(&cfb_dbg[(base) + k_], cfb_a_[k_]); } while (0)
-extern "C" int vadx_cfb_debug_cycles(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(cfb_dbg), sizeof(unsigned long long) * 32) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[32] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(cfb_dbg), z, sizeof(z)) != hipSuccess) return -1; }
-    return 0;
-}
-#else
-#define CFB_T0() do {} while (0)
-#define CFB_MARK(slot) do {} while (0)
-#define CFB_FLUSH(base) do {} while (0)
-#endif
-
 namespace vadx {
 namespace dfsmn_cfb {
 
@@ -127,7 +101,6 @@ __device__ __forceinline__ float sum_q(float v) {
 // LDS-only workgroup barrier: every wave's LDS writes are complete (lgkmcnt) before it arrives; outstanding GLOBAL loads / stores
 // are NOT waited for (a __syncthreads() is free to, and the chunk loops keep a prefetch and the y1 / S stores in flight across it).
 __device__ __forceinline__ void lds_barrier() {
-    if (CFB_EXP & 1) return;
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
@@ -233,7 +206,7 @@ __global__ __launch_bounds__(NTH) void cfb_front_kernel(FrontArgs p) {
             unsigned lql = lq;                      // laundered: left visible, the compiler forms one 64-bit pointer per k-step outside the
             asm volatile("" : "+v"(lql));           // loop and spills them; the reloads then wait out the whole prefetch queue
 #pragma unroll
-            for (int s = 0; s < KS; ++s) x[s] = (CFB_EXP & 2) ? 0.25f : ldg1o(s < ks_a ? abase : bbase, 4u * (lql + (unsigned)(s * 4 * F * 16) + f * 16u));
+            for (int s = 0; s < KS; ++s) x[s] = ldg1o(s < ks_a ? abase : bbase, 4u * (lql + (unsigned)(s * 4 * F * 16) + f * 16u));
         };
         load_x(0, x0);
         for (int e = tid; e < CH * 16; e += NTH) GXW[(e >> 4) * GP20 + (NSLOT - 1) * 16 + (e & 15)] = 0.f;      // bin -1: zero padding of the (3,1) conv
@@ -261,13 +234,13 @@ __global__ __launch_bounds__(NTH) void cfb_front_kernel(FrontArgs p) {
             for (int ks = 0; ks < 2; ++ks) {
                 float tf[5], rb[5];
                 __builtin_amdgcn_sched_barrier(0);      // one k-step's fragment reads at a time
-                if (DFT && !(CFB_EXP & 16)) {
+                if (DFT) {
 #pragma unroll
                     for (int u = 0; u < 5; ++u) { tf[u] = tbl_w[(u * KSF + 2 * (j - 1) + ks) * 64]; rb[u] = rb_p[u * RP8 + ks * 64]; }
                 }
 #pragma unroll
                 for (int g = 0; g < 5; ++g) {
-                    if (C31 && !(CFB_EXP & 8)) {
+                    if (C31) {
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
                             const int s = (ks * 5 + g) * 2 + h;          // 0..19; the fifteen k-steps run at s < 15
@@ -279,7 +252,7 @@ __global__ __launch_bounds__(NTH) void cfb_front_kernel(FrontArgs p) {
                             }
                         }
                     }
-                    if (DFT && !(CFB_EXP & 16)) {
+                    if (DFT) {
 #pragma unroll
                         for (int u = 0; u < 5; ++u) acc[g * 5 + u] = mfma16(tf[u], rb[g], acc[g * 5 + u]);
                     }
@@ -304,12 +277,10 @@ __global__ __launch_bounds__(NTH) void cfb_front_kernel(FrontArgs p) {
                     for (int k = 0; k < 4; ++k)
                         ta[k] = ldg4o(p.w.front_tab, 4u * ((unsigned)((f * 4 + k) * CH) + (m == 0 ? 4u * qv : 16u)));
                     f32x4 ag = {0.f, 0.f, 0.f, 0.f}, ai = {bi[m][0], bi[m][1], bi[m][2], bi[m][3]};
-                    if (!(CFB_EXP & 4)) {
 #pragma unroll
-                        for (int s = 0; s < KS; ++s) {
-                            ag = mfma16(wg_w[(m * KS + s) * 64], xw[s], ag);
-                            ai = mfma16(WI_LDS ? wi_w[(m * KS + s) * 64] : wif[WI_LDS ? 0 : m][WI_LDS ? 0 : s], xc[s], ai);
-                        }
+                    for (int s = 0; s < KS; ++s) {
+                        ag = mfma16(wg_w[(m * KS + s) * 64], xw[s], ag);
+                        ai = mfma16(WI_LDS ? wi_w[(m * KS + s) * 64] : wif[WI_LDS ? 0 : m][WI_LDS ? 0 : s], xc[s], ai);
                     }
                     if (m == 1 && !up_ok) continue;
 #pragma unroll
@@ -317,9 +288,9 @@ __global__ __launch_bounds__(NTH) void cfb_front_kernel(FrontArgs p) {
                         const int co = m * 16 + 4 * q + r;
                         // LN0 commuted behind the gate conv: inv0 * (Wg (w0 x)) + (Wg b0 + bias) - mean0 inv0 (Wg w0)
                         const float pre = fmaf(inv0, ag[r], fmaf(-mi0, ta[0][r], ta[1][r]));
-                        const float g = (CFB_EXP & 32) ? pre : gate_sigmoid(pre), xi = ai[r], gx = g * xi, rr = xi - gx;
+                        const float g = gate_sigmoid(pre), xi = ai[r], gx = g * xi, rr = xi - gx;
                         if (!C31 && m == 0 && r == 0) { sg.K = gx; sr.K = rr; }      // the tile's first iteration (no (3,1) conv yet): the shifts
-                        if (!(CFB_EXP & 32)) { sg.addk(gx); sr.addk(rr); }
+                        sg.addk(gx); sr.addk(rr);
                         GXW[co * GP20 + slot * 16 + i] = gx * ta[2][r];
                         R[(j & 1) * CH * RP8 + co * RP8 + wave * 16 + i] = rr * ta[3][r];
                     }
@@ -327,7 +298,7 @@ __global__ __launch_bounds__(NTH) void cfb_front_kernel(FrontArgs p) {
             } else if (j == NIT8 && wave == 0) {
                 for (int e = lane; e < CH * 16; e += 64) GXW[(e >> 4) * GP20 + (F % NSLOT) * 16 + (e & 15)] = 0.f;      // bin 160: zero padding
             }
-            if (C31 && fo >= 0 && fo < F && !(CFB_EXP & (8 | 64))) {
+            if (C31 && fo >= 0 && fo < F) {
                 const unsigned o = qv * (unsigned)(4 * F * 16) + iv + (unsigned)(fo * 16);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) stg1o(y1_t, 4u * (o + (unsigned)(r * F * 16)), a3[0][r]);
@@ -421,7 +392,7 @@ __global__ __launch_bounds__(NTH) void cfb_front_kernel(FrontArgs p) {
         }
         // ---- S -> li[40][81]: table rows 0..80 = cos bins of channel c, rows 81..159 = sin bins 1..79 of channel 20 + c; one 16-byte
         // store per lane and tile through the wave's transpose scratch
-        if (!(CFB_EXP & 256)) {
+        {
             float *li_t = p.li + (size_t)tile * (2 * CH * CF * 16);
             CFB_FENCE();
             put_d(ws, ql, il, acc[0]);
@@ -485,7 +456,6 @@ __global__ __launch_bounds__(NTH) void cfb_back_kernel(BackArgs p) {
     const float *o_w = OB + (5 * cg) * OP8 + q * 16 + i;
     float *ws = WS + wave * WS_FLOATS;
     __syncthreads();
-    CFB_T0();
 
     f32x4 acc[25];
     // this lane's place in a tile's row layout + the wave's first tile (uniform bases + unsigned 32-bit offsets everywhere: see cfb_front)
@@ -493,7 +463,7 @@ __global__ __launch_bounds__(NTH) void cfb_back_kernel(BackArgs p) {
     auto y1_load = [&](int tile) {                  // the accumulators START as y1 (row layout; transposed below)
         const float *y1_t = p.y1 + (size_t)tile * (CH * F * 16);
 #pragma unroll
-        for (int jj = 0; jj < 25; ++jj) acc[jj] = (CFB_EXP & 512) ? f32x4{0.f, 0.f, 0.f, 0.f} : ldg4o(y1_t, 4u * (rowoff + (unsigned)(((jj / 5) * F + 16 * (jj % 5)) * 16)));
+        for (int jj = 0; jj < 25; ++jj) acc[jj] = ldg4o(y1_t, 4u * (rowoff + (unsigned)(((jj / 5) * F + 16 * (jj % 5)) * 16)));
     };
     if ((int)blockIdx.x < p.tiles) y1_load(blockIdx.x);
     for (int tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
@@ -509,14 +479,14 @@ __global__ __launch_bounds__(NTH) void cfb_back_kernel(BackArgs p) {
             unsigned lql = lq + (unsigned)(bin * 16), lil = li_ + (unsigned)(bin * 16);      // laundered: the 22 offsets are formed at each call,
             asm volatile("" : "+v"(lql), "+v"(lil));                                            // not hoisted and spilled
 #pragma unroll
-            for (int s = 0; s < 10; ++s) h[s] = (CFB_EXP & 2) ? 0.25f : ldg1o(hf_t, 4u * (lql + (unsigned)(s * 4 * CF * 16)));
+            for (int s = 0; s < 10; ++s) h[s] = ldg1o(hf_t, 4u * (lql + (unsigned)(s * 4 * CF * 16)));
 #pragma unroll
             for (int m = 0; m < 3; ++m) {
                 const int ca = min(8 * m + 2 * q, CH - 2);
 #pragma unroll
                 for (int h2 = 0; h2 < 2; ++h2) {
-                    sv[4 * m + h2] = (CFB_EXP & 2) ? 0.5f : ldg1o(li_t, 4u * (lil + (unsigned)((ca + h2) * CF * 16)));
-                    sv[4 * m + 2 + h2] = (CFB_EXP & 2) ? 0.5f : ldg1o(li_t, 4u * (lil + (unsigned)((CH + ca + h2) * CF * 16)));
+                    sv[4 * m + h2] = ldg1o(li_t, 4u * (lil + (unsigned)((ca + h2) * CF * 16)));
+                    sv[4 * m + 2 + h2] = ldg1o(li_t, 4u * (lil + (unsigned)((CH + ca + h2) * CF * 16)));
                 }
             }
         };
@@ -547,7 +517,6 @@ __global__ __launch_bounds__(NTH) void cfb_back_kernel(BackArgs p) {
                 if (jj + 5 < 25) fx[jj % 5] = ldg1o(fix_w, 4u * (lane_u + (unsigned)((((jj + 5) / 5) * 10 + (jj + 5) % 5) * 64)));
             }
         }
-        CFB_MARK(0);
         lds_barrier();                              // the scratch aliases OB
         // One iteration: Linear + complex product of chunk c from (hc, sc) -> OB[c & 1], and NK k-steps of the inverse DFT of chunk
         // c - 1 from OB[(c - 1) & 1] (NK = 4: real 2 cm, 2 cm + 1, imaginary 2 cm, 2 cm + 1; NK = 1: the last chunk holds bin 80 only).
@@ -565,18 +534,18 @@ __global__ __launch_bounds__(NTH) void cfb_back_kernel(BackArgs p) {
                 const int part = ks >> 1, half = ks & 1;
                 float tf[5], ob[5];
                 __builtin_amdgcn_sched_barrier(0);      // one k-step's ten fragment reads at a time (hoisted together they spill)
-                if (ks < NK && !(CFB_EXP & 16)) {
+                if (ks < NK) {
 #pragma unroll
                     for (int u = 0; u < 5; ++u) { tf[u] = tbl_w[(u * KSI + part * 21 + 2 * cm + half) * 64]; ob[u] = ob_p[u * OP8 + part * 128 + half * 64]; }
                 }
 #pragma unroll
                 for (int g = 0; g < 5; ++g) {
-                    if (LIN && !(CFB_EXP & 128) && ((ks * 5 + g) & 1) == 0) {
+                    if (LIN && ((ks * 5 + g) & 1) == 0) {
                         const int s = (ks * 5 + g) >> 1;
 #pragma unroll
                         for (int m = 0; m < 3; ++m) P[m] = mfma16(wl_w[(m * 10 + s) * 64], hc[s], P[m]);
                     }
-                    if (ks < NK && !(CFB_EXP & 16)) {
+                    if (ks < NK) {
 #pragma unroll
                         for (int u = 0; u < 5; ++u) acc[g * 5 + u] = mfma16(tf[u], ob[g], acc[g * 5 + u]);
                     }
@@ -597,9 +566,7 @@ __global__ __launch_bounds__(NTH) void cfb_back_kernel(BackArgs p) {
                     }
                 }
             }
-            CFB_MARK(1);
             lds_barrier();
-            CFB_MARK(2);
         };
         using T_ = std::true_type; using F_ = std::false_type;
         load(1, h1, s1);
@@ -644,11 +611,11 @@ __global__ __launch_bounds__(NTH) void cfb_back_kernel(BackArgs p) {
             CFB_FENCE();
             const f32x4 v = get_rows(ws + (jj & 1) * WS_TILE, lane_l);
             CFB_FENCE();
-            if (!(CFB_EXP & 256)) stg4o(out_t, 4u * off, v);
+            stg4o(out_t, 4u * off, v);
             if (jj >= 1)        // tile jj - 1's registers are free now: the next tile's y1 lands in them during the reductions below
-                acc[jj - 1] = (CFB_EXP & 512) ? f32x4{0.f, 0.f, 0.f, 0.f} : ldg4o(y1_n, 4u * (ro + (unsigned)((((jj - 1) / 5) * F + 16 * ((jj - 1) % 5)) * 16)));
+                acc[jj - 1] = ldg4o(y1_n, 4u * (ro + (unsigned)((((jj - 1) / 5) * F + 16 * ((jj - 1) % 5)) * 16)));
         }
-        acc[24] = (CFB_EXP & 512) ? f32x4{0.f, 0.f, 0.f, 0.f} : ldg4o(y1_n, 4u * (ro + (unsigned)((4 * F + 16 * 4) * 16)));
+        acc[24] = ldg4o(y1_n, 4u * (ro + (unsigned)((4 * F + 16 * 4) * 16)));
         lds_barrier();
         if (p.part && tid < 16) {
             float M = 0.f;
@@ -659,9 +626,7 @@ __global__ __launch_bounds__(NTH) void cfb_back_kernel(BackArgs p) {
             float *z = o + 16 * 4;
             z[0] = z[1] = z[2] = z[3] = 0.f;
         }
-        CFB_MARK(3);
     }
-    CFB_FLUSH(8);
 }
 
 // =====================================================================================================================================
@@ -770,7 +735,6 @@ __global__ __launch_bounds__(NTH) void cfb_front_split_kernel(FrontQArgs pq) {
     const int cg = wave >> 1, mg = wave & 1;       // DFT tiles: channels 5 cg .. + 4, row tiles 5 mg .. + 4; tile jj = (jj / 5, jj % 5)
     float *ws = WS + wave * WS_FLOATS;
     __syncthreads();
-    CFB_T0();
 
     for (int tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
         f32x4 acc[25];
@@ -796,8 +760,8 @@ __global__ __launch_bounds__(NTH) void cfb_front_split_kernel(FrontQArgs pq) {
                 for (int e = 0; e < 5; ++e) {
                     // (uniform base per channel slot + ONE per-lane offset: the slot strides are beyond a load's immediate offset, and as
                     // per-lane additions they were two vector instructions per load)
-                    xn[ck][e] = (CFB_EXP & 2) ? 0.25f * (float)e : ldg1o((ck == 0 ? abase : bbase) + e * F * 16, 4u * (lql + fc * 16u));
-                    wn[ck][e] = (CFB_EXP & 2) ? 1.5f : ldg1o(p.w.ln0_w + (20 * ck + e) * F, 4u * (lqw + fc));
+                    xn[ck][e] = ldg1o((ck == 0 ? abase : bbase) + e * F * 16, 4u * (lql + fc * 16u));
+                    wn[ck][e] = ldg1o(p.w.ln0_w + (20 * ck + e) * F, 4u * (lqw + fc));
                 }
         };
         load_x(4 * wave);
@@ -816,8 +780,8 @@ __global__ __launch_bounds__(NTH) void cfb_front_split_kernel(FrontQArgs pq) {
                 float tb[4];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    ta[t] = (CFB_EXP & 8192) ? f32x4{0.5f, 0.25f, 1.f, 2.f} : ldg4o(p.w.front_tab + (f * 4 + t) * CH, 16u * qv);
-                    tb[t] = (CFB_EXP & 8192) ? 0.5f : ldg1o(p.w.front_tab + (f * 4 + t) * CH + 16, 4u * qv);
+                    ta[t] = ldg4o(p.w.front_tab + (f * 4 + t) * CH, 16u * qv);
+                    tb[t] = ldg1o(p.w.front_tab + (f * 4 + t) * CH + 16, 4u * qv);
                 }
                 f32x4 agh[2], agl[2], aih[2], ail[2];
 #pragma unroll
@@ -861,7 +825,7 @@ __global__ __launch_bounds__(NTH) void cfb_front_split_kernel(FrontQArgs pq) {
                     for (int r = 0; r < 4; ++r) {
                         // LN0 commuted behind the gate conv: inv0 * (Wg (w0 x)) + (Wg b0 + bias) - mean0 inv0 (Wg w0)
                         const float pre = fmaf(inv0, ag[r], fmaf(-mi0, ta[0][r], ta[1][r]));
-                        const float gt = (CFB_EXP & 32) ? pre : gate_sigmoid(pre), xi = ai[r], gx = gt * xi, rr = xi - gx;
+                        const float gt = gate_sigmoid(pre), xi = ai[r], gx = gt * xi, rr = xi - gx;
                         if (g == 0 && k == 0 && r == 0) { sg.K = gx; sr.K = rr; }      // the tile's first value of this lane: the shifts
                         sg.addk(gx); sr.addk(rr);
                         set_k(rw0[r], k, rr * ta[3][r]);
@@ -876,7 +840,7 @@ __global__ __launch_bounds__(NTH) void cfb_front_split_kernel(FrontQArgs pq) {
                 }
                 {   // channel 16 + q (row 4 q of the second tile)
                     const float pre = fmaf(inv0, agh[1][0] + agl[1][0], fmaf(-mi0, tb[0], tb[1]));
-                    const float gt = (CFB_EXP & 32) ? pre : gate_sigmoid(pre), xi = aih[1][0] + ail[1][0], gx = gt * xi, rr = xi - gx;
+                    const float gt = gate_sigmoid(pre), xi = aih[1][0] + ail[1][0], gx = gt * xi, rr = xi - gx;
                     sg.addk(gx); sr.addk(rr);
                     set_k(rw1, k, rr * tb[3]);
                     unsigned short h0, h1, h2;
@@ -885,7 +849,7 @@ __global__ __launch_bounds__(NTH) void cfb_front_split_kernel(FrontQArgs pq) {
                     d[0] = h0; d[RING_PLANE / 2] = h1; d[RING_PLANE] = h2;
                 }
             }
-            if (!(CFB_EXP & 4096)) {
+            {
                 // ln2_w r of the four bins -> positions 4 (w & 1) .. + 3 of k-group w / 2 of each channel's row: one 8-byte store per plane
                 unsigned char *d0 = RQ + (wave >> 1) * RQ_ROW + i * 16 + 8 * (wave & 1);
 #pragma unroll
@@ -904,9 +868,7 @@ __global__ __launch_bounds__(NTH) void cfb_front_split_kernel(FrontQArgs pq) {
                 *reinterpret_cast<u32x2 *>(d + RQ_PLANE) = p1;
                 *reinterpret_cast<u32x2 *>(d + 2 * RQ_PLANE) = p2;
             }
-            CFB_MARK(0);
             lds_barrier();                                       // A: the group's ring slots and B planes are complete
-            CFB_MARK(1);
             // ---- (3,1) conv of output bins fo = 32 g + 4 w - 1 + k (wave 7 of the last group: bin 159 too) from the bins fo - 1 .. fo + 1:
             // relative to this wave's slot 0 they are r = k + tap - 2 in [-2, 3] (4: bin 160, zero)
             // the DFT k-step's first two table fragments are requested before the (3,1) conv's y1 stores enter the memory queue
@@ -966,7 +928,6 @@ __global__ __launch_bounds__(NTH) void cfb_front_split_kernel(FrontQArgs pq) {
                     stg1o(y1_t, 4u * ((16u + qv) * (unsigned)(F * 16) + iv + (unsigned)(fo * 16)), a3h[1][0] + a3l[1][0]);
                 }
             }
-            CFB_MARK(2);
             // ---- the group's DFT k-step: 25 tiles, six products each into ONE accumulator (a lo set would be 100 more registers)
             {
                 bf16x8 bq[5][3];
@@ -995,9 +956,7 @@ __global__ __launch_bounds__(NTH) void cfb_front_split_kernel(FrontQArgs pq) {
                     for (int c5 = 0; c5 < 5; ++c5) acc[c5 * 5 + u] = mfma_bf16(cur[0], bq[c5][0], acc[c5 * 5 + u]);
                 }
             }
-            CFB_MARK(3);
             lds_barrier();                                       // B: every read of this group's slots and planes is done
-            CFB_MARK(1);
             if (wave == 7)                                       // bins 32 g + 30, 32 g + 31 for wave 0's (3,1) conv behind the next barrier A
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
@@ -1095,9 +1054,7 @@ __global__ __launch_bounds__(NTH) void cfb_front_split_kernel(FrontQArgs pq) {
                 li_t[((CH + (e >> 5)) * CF + (((e >> 4) & 1) ? 80 : 0)) * 16 + (e & 15)] = 0.f;
         }
         lds_barrier();                              // the scratch aliases the planes
-        CFB_MARK(4);
     }
-    CFB_FLUSH(16);
 }
 
 // ---- second half on split products.  CepsUnit's Linear 40 -> 40 (K = 40 as two k-steps of 5 channels per lane quarter) and the pinv

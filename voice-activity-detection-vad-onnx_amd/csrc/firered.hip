@@ -16,14 +16,6 @@
 #include <math.h>
 #include <string.h>
 
-// FR_EXP: development-only what-if switches (bit mask; results are wrong when set): 1 no FIR memory, 2 no barriers
-// inside the point-wise pairs, 4 no second (H->P) layer, 8 no first (P->H) layer, 16 no dnn / output section,
-// 32 no log-mel staging / zero fills
-#ifndef FR_EXP
-#define FR_EXP 0
-#endif
-#define FR_SYNC() do { if (!(FR_EXP & 2)) __syncthreads(); } while (0)
-
 namespace vadx {
 namespace firered {
 
@@ -180,7 +172,6 @@ __device__ __forceinline__ void fsmn_memory_generic(const Dev &d, const float *_
 }
 
 __device__ __forceinline__ void fsmn_memory(const Dev &d, const float *__restrict__ Pk, int r, bool skip, const float *p, float *mem) {
-    if (FR_EXP & 1) return;
     if (d.S1 == 1 && d.N1 <= 20 && (d.N2 == 0 || d.S2 == 1) && d.N2 <= 20 && d.T > 1 && d.T <= 112 && d.Pp <= 128) fsmn_memory_fast(d, Pk, r, skip, p, mem);
     else fsmn_memory_generic(d, Pk, r, skip, p, mem);
 }
@@ -387,19 +378,19 @@ __device__ __forceinline__ void pointwise_pair_split(const Dev &d, const float *
 
 __device__ __forceinline__ void pointwise_pair(const Dev &d, const float *W1, const float *b1, int k1b, const float *src,
                                                const float *W2, const float *b2, int relu2, float *dst, float *h) {
-    if (!FR_EXP && W2 && d.Hp == 256 && d.Pp == 128 && blockDim.x == 512) {
+    if (W2 && d.Hp == 256 && d.Pp == 128 && blockDim.x == 512) {
         if (k1b == 8) { pointwise_pair_resident<8>(d, W1, b1, src, W2, b2, relu2 != 0, dst, h); return; }      // DFSMN block
         if (k1b == 5) { pointwise_pair_resident<5>(d, W1, b1, src, W2, b2, relu2 != 0, dst, h); return; }      // fc1 (80 mels) / fc2
     }
     for (int f0 = 0; f0 < d.T; f0 += 32) {
         const bool half = (d.T - f0) <= 16;
         LayerArgs a{W1, k1b * 16, d.Hp / 16, 1, k1b, 0, 0, b1, 1, src, M_LD, f0, h, H_LD, 0, nullptr, nullptr};
-        if (!(FR_EXP & 8)) { if (half) layer<1, false>(a); else layer<2, false>(a); }
-        FR_SYNC();
-        if (W2 && !(FR_EXP & 4)) {
+        if (half) layer<1, false>(a); else layer<2, false>(a);
+        __syncthreads();
+        if (W2) {
             LayerArgs c{W2, d.Hp, d.Pp / 16, 1, d.Hp / 16, 0, 0, b2, relu2, h, H_LD, 0, dst, M_LD, f0, nullptr, nullptr};
             if (half) layer<1, false>(c); else layer<2, false>(c);
-            FR_SYNC();
+            __syncthreads();
         }
     }
 }
@@ -415,42 +406,32 @@ __global__ __launch_bounds__(THREADS, 2) void firered_kernel(Dev d, const float 
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *mem = lds, *p = lds + MEM_F, *h = p + P_F;
     const int tid = threadIdx.x;
-    long long tk0 = clock64(), tk_fir = 0, tk_pw = 0, tk_x;      // FR_EXP & 64: cycle accounting (development)
     const float *lm = logmel + (size_t)blockIdx.x * d.T * NMEL;
     // stage log-mel channel-first into `mem` rows 0..79; frames >= T are zero (finite operands)
-    for (int e = tid; e < ((FR_EXP & 32) ? 0 : MAX_T * NMEL); e += THREADS) {
+    for (int e = tid; e < MAX_T * NMEL; e += THREADS) {
         const int t = e / NMEL, mel = e - t * NMEL;
         const float v = lm[(size_t)(t < d.T ? t : d.T - 1) * NMEL + mel];      // unconditional (clamped) load, then select
         mem[mel * M_LD + t] = t < d.T ? v : 0.f;
     }
-    for (int e = tid; e < ((FR_EXP & 32) ? 0 : MAXP * M_LD); e += THREADS) p[e] = 0.f;
+    for (int e = tid; e < MAXP * M_LD; e += THREADS) p[e] = 0.f;
     __syncthreads();
     // dfsmn.fc1 (80->H, ReLU) ; dfsmn.fc2 (H->P, bias, ReLU) ; fsmn1
     if (SPLIT) pointwise_pair_split<SC, 3>(d, Pk + d.q_fc1, Pk + d.off_fc1b, NMEL, mem, Pk + d.q_fc2, Pk + d.off_fc2b, true, p, h, amax);
     else pointwise_pair(d, Pk + d.off_fc1, Pk + d.off_fc1b, NMEL / 16, mem, Pk + d.off_fc2, Pk + d.off_fc2b, 1, p, h);
-    for (int e = tid; e < ((FR_EXP & 32) ? 0 : MAXP * M_LD); e += THREADS) mem[e] = 0.f;        // log-mel rows are dead now
+    for (int e = tid; e < MAXP * M_LD; e += THREADS) mem[e] = 0.f;        // log-mel rows are dead now
     __syncthreads();
-    tk_x = clock64();
     fsmn_memory(d, Pk, 0, false, p, mem);
     __syncthreads();
-    tk_fir += clock64() - tk_x;
     for (int r = 1; r < d.R; ++r) {      // DFSMNBlock: fc1 (P->H, ReLU) ; fc2 (H->P, no bias) ; fsmn + skip
-        tk_x = clock64();
         if (SPLIT) pointwise_pair_split<SC, 4>(d, Pk + d.q_bfc1[r], Pk + d.off_bfc1b[r], d.Pp, mem, Pk + d.q_bfc2[r], nullptr, false, p, h, amax);
         else pointwise_pair(d, Pk + d.off_bfc1[r], Pk + d.off_bfc1b[r], d.Pp / 16, mem, Pk + d.off_bfc2[r], nullptr, 0, p, h);
-        tk_pw += clock64() - tk_x;
-        tk_x = clock64();
         fsmn_memory(d, Pk, r, true, p, mem);
         __syncthreads();
-        tk_fir += clock64() - tk_x;
     }
     // One dnn layer (the published configuration): dnn (P -> H, ReLU) + output head (H -> odim) are one more point-wise pair on split
     // products -- the head's rows padded to Pp with zeros (as many MFMAs as a block's second layer, at a third of the f32 MFMAs' cost) --
     // over the whole window at once instead of tile by tile on float32 MFMAs; logits land in p[o][t].
-#ifndef FR_OLD_DNN
-#define FR_OLD_DNN 0        /* development: 1 = the float32 tile-by-tile dnn + head (A/B timing) */
-#endif
-    if (SPLIT && d.M == 1 && !FR_EXP && !FR_OLD_DNN) {
+    if (SPLIT && d.M == 1) {
         pointwise_pair_split<SC, 4>(d, Pk + d.q_dnn0, Pk + d.off_dnnb[0], d.Pp, mem, Pk + d.q_head, Pk + d.off_headb, false, p, h, amax);
         __syncthreads();
         for (int e = tid; e < d.odim * d.T; e += THREADS) {
@@ -462,10 +443,10 @@ __global__ __launch_bounds__(THREADS, 2) void firered_kernel(Dev d, const float 
     }
     // dnns (P->H ReLU, then M-1 x H->H ReLU) and the 1x1 output conv + sigmoid, tile by tile
     float *h2 = p;                        // p is dead: second H-tile buffer for M > 1
-    const bool dnn_resident = !FR_EXP && d.Hp == 256 && d.Pp == 128 && blockDim.x == 512;
+    const bool dnn_resident = d.Hp == 256 && d.Pp == 128 && blockDim.x == 512;
     PairResident<8> RD;                   // dnn[0] (P -> H) stays in registers across the window's tiles, like the pairs
     if (dnn_resident) load_pair_resident<8, false>(RD, Pk + d.off_dnn[0], Pk + d.off_dnnb[0], nullptr, nullptr);
-    for (int f0 = 0; f0 < ((FR_EXP & 16) ? 0 : d.T); f0 += 32) {
+    for (int f0 = 0; f0 < d.T; f0 += 32) {
         const bool half = (d.T - f0) <= 16;
         if (dnn_resident) {
             if (half) pair_tile_resident<1, 8, false>(RD, mem, nullptr, h, f0, false);
@@ -492,10 +473,6 @@ __global__ __launch_bounds__(THREADS, 2) void firered_kernel(Dev d, const float 
             if (f0 + t < d.T) probs[((size_t)blockIdx.x * d.odim + o) * d.T + f0 + t] = sigmoidf_(lg[o * H_LD + t]);
         }
         __syncthreads();
-    }
-    if ((FR_EXP & 64) && tid == 0) {
-        float *dbg = probs + (size_t)blockIdx.x * d.odim * d.T;
-        dbg[0] = (float)tk_fir; dbg[1] = (float)tk_pw; dbg[2] = (float)(clock64() - tk0);
     }
     if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
 }

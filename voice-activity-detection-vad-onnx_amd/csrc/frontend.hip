@@ -28,29 +28,6 @@
 
 #include <type_traits>
 
-// FE_EXP: development-only cycle accounting (tools/exp_frontend.py)
-#ifndef FE_EXP
-#define FE_EXP 0
-#endif
-// FE_WHATIF: development-only switches of the folded kernel (results are wrong when set): 1 no residual product, 2 every table fragment
-// from block 0 (L1 instead of L2), 4 no u / v additions, 8 no symmetric product
-#ifndef FE_WHATIF
-#define FE_WHATIF 0
-#endif
-#if FE_EXP
-__device__ unsigned long long fe_dbg[8];
-#define FE_T0() long long fe_t_ = clock64()
-#define FE_ACC(slot) do { if (threadIdx.x == 0) { const long long n_ = clock64(); atomicAdd(&fe_dbg[slot], (unsigned long long)(n_ - fe_t_)); fe_t_ = n_; } } while (0)
-extern "C" int vadx_frontend_debug_cycles(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(fe_dbg), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(fe_dbg), z, sizeof(z)) != hipSuccess) return -1; }
-    return 0;
-}
-#else
-#define FE_T0() do {} while (0)
-#define FE_ACC(slot) do {} while (0)
-#endif
-
 namespace vadx {
 namespace frontend {
 
@@ -436,10 +413,7 @@ static size_t packed_total(const Dev &d) {
 
 // log of the mel energies: v_log_f32 (1 ulp in log2) times ln 2 instead of the library logf (~25 VALU instructions per value; VALU
 // time adds to f32-MFMA time on gfx950).  |difference| <= 4e-6 over the feature range, two orders inside the feature tolerance.
-#ifndef FE_FAST_LOG
-#define FE_FAST_LOG 1
-#endif
-__device__ __forceinline__ float FE_LOG(float x) { return FE_FAST_LOG ? __builtin_amdgcn_logf(x) * 0.6931471805599453f : logf(x); }
+__device__ __forceinline__ float FE_LOG(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
 
 // Phase 0 of both tile bodies: prep + polyphase staging  X2[r][g] = s'[(f0+g)*hop + r]  for g < cols (XLD = row stride of X2).
 // HALF: the same samples also go, scaled by the power of two `xscale` and rounded to f16, to XS[g][r] (row pitch xs_pitch
@@ -628,12 +602,9 @@ __device__ __forceinline__ void tile_body(const Dev &d, const float *__restrict_
     constexpr int NF = MT * 16;
     const int cols = NF + d.passes - 1;
 
-    FE_T0();
     // ---- phase 0: prep + polyphase staging  X2[r][g] = s'[(f0+g)*hop + r]  (stage_tile)
     stage_tile<X_LD, false>(d, win, fwin, mean, f0, cols, X2, nullptr, 0, 0.f);
-    FE_ACC(4);
     __syncthreads();
-    FE_ACC(0);
 
     // ---- phase 1: DFT GEMM, |.|^2 -> PW[bin][frame]
     for (int bt = wave; bt < d.nbt; bt += THREADS / 64) {
@@ -670,7 +641,6 @@ __device__ __forceinline__ void tile_body(const Dev &d, const float *__restrict_
         }
     }
     if (COMPLEX) return;
-    FE_ACC(1);
     if (d.nyq) {
         // Last bin (n_bins % 16 == 1, e.g. the Nyquist bin of a 512-point DFT): a 17th bin tile would hand one wave three
         // tiles instead of two (+50 % on the phase), and as a VALU dot product over all taps it cost a fifth of the kernel
@@ -713,10 +683,8 @@ __device__ __forceinline__ void tile_body(const Dev &d, const float *__restrict_
         }
     }
     __syncthreads();
-    FE_ACC(2);
 
     mel_phase<MT>(d, P, PW, P_LD, f0, out_win);
-    FE_ACC(3);
 }
 
 
@@ -736,13 +704,10 @@ __device__ __forceinline__ void fold_tile(const Dev &d, const float *__restrict_
     float *X2 = lds, *PW = lds;
     _Float16 *XS = reinterpret_cast<_Float16 *>(lds + (d.hop + 16) * XF_LD);
 
-    FE_T0();
     for (int e = tid; e < 16 * XF_LD; e += THREADS) X2[d.hop * XF_LD + e] = 0.f;                      // the zero rows (lone taps, padding pairs)
     for (int e = tid; e < xs_pitch; e += THREADS) XS[cols * xs_pitch + e] = (_Float16)0.f;            // column read by the residual's padded taps
     stage_tile<XF_LD, true>(d, win, nullptr, mean, f0, cols, X2, XS, xs_pitch, d.f_xscale);
-    FE_ACC(4);
     __syncthreads();
-    FE_ACC(0);
 
     // 16 pairs (4 k-steps) of the symmetric part: u -> real accumulators, v -> imaginary ones
     auto fold_block = [&](const f32x4 &e4, const f32x4 &o4, const float *pa, const float *pb, int strB, f32x4 (&are)[MT], f32x4 (&aim)[MT]) {
@@ -752,8 +717,8 @@ __device__ __forceinline__ void fold_tile(const Dev &d, const float *__restrict_
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 const float xa = pa[j * XF_LD + mt * 16], xb = pb[j * strB + mt * 16];
-                u[mt] = (FE_WHATIF & 4) ? xa : __fadd_rn(xa, xb);
-                v[mt] = (FE_WHATIF & 4) ? xb : __fsub_rn(xa, xb);
+                u[mt] = __fadd_rn(xa, xb);
+                v[mt] = __fsub_rn(xa, xb);
             }
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
@@ -822,7 +787,7 @@ __device__ __forceinline__ void fold_tile(const Dev &d, const float *__restrict_
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) acc[a][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
         // residual (f16): RX -> real, IX -> imaginary, both against the f16 samples of the frame; table fragments one block ahead
-        if (!(FE_WHATIF & 1)) {
+        {
             const f16x8 *r0 = reinterpret_cast<const f16x8 *>(P + d.off_res + (size_t)(bt0 * 2) * d.f_Kb32 * vadx::FRAG) + lane;
             const f16x8 *r1 = reinterpret_cast<const f16x8 *>(P + d.off_res + (size_t)(bt1 * 2) * d.f_Kb32 * vadx::FRAG) + lane;
             const int rs = d.f_Kb32 * 64;
@@ -830,7 +795,7 @@ __device__ __forceinline__ void fold_tile(const Dev &d, const float *__restrict_
             int a = 0, r = 8 * q;
             while (r >= d.hop) { r -= d.hop; ++a; }
             for (int S = 0; S < d.f_Kb32; ++S) {
-                const int Sn = ((FE_WHATIF & 2) ? 0 : (S + 1 < d.f_Kb32 ? S + 1 : S)) * 64;
+                const int Sn = (S + 1 < d.f_Kb32 ? S + 1 : S) * 64;
                 const f16x8 n0 = *(global_f16x8_ptr)(r0 + Sn), n1 = *(global_f16x8_ptr)(r0 + rs + Sn);
                 const f16x8 n2 = *(global_f16x8_ptr)(r1 + Sn), n3 = *(global_f16x8_ptr)(r1 + rs + Sn);
                 __builtin_amdgcn_sched_barrier(0);
@@ -855,7 +820,7 @@ __device__ __forceinline__ void fold_tile(const Dev &d, const float *__restrict_
         }
         // symmetric part (f32): table fragments one block ahead (requesting the LDS operands a k-step ahead as well, on two register
         // sets, measured no gain: four waves per SIMD already cover that latency)
-        if (!(FE_WHATIF & 8)) {
+        {
             const float *fe0 = vadx::frag_ptr(P + d.off_fold, Kp, bt0 * 2, 0, lane), *fo0 = vadx::frag_ptr(P + d.off_fold, Kp, bt0 * 2 + 1, 0, lane);
             const float *fe1 = vadx::frag_ptr(P + d.off_fold, Kp, bt1 * 2, 0, lane), *fo1 = vadx::frag_ptr(P + d.off_fold, Kp, bt1 * 2 + 1, 0, lane);
             f32x4 e0 = vadx::ldg4(fe0), o0 = vadx::ldg4(fo0), e1 = vadx::ldg4(fe1), o1 = vadx::ldg4(fo1);
@@ -864,7 +829,7 @@ __device__ __forceinline__ void fold_tile(const Dev &d, const float *__restrict_
                 const int nblk = plan[4 * rg], strB = plan[4 * rg + 3];
                 const float *pa = X2 + plan[4 * rg + 1] + 4 * q * XF_LD + i, *pb = X2 + plan[4 * rg + 2] + 4 * q * strB + i;
                 for (int S = 0; S < nblk; ++S, ++gb) {
-                    const int gn = vadx::FRAG * ((FE_WHATIF & 2) ? 0 : (gb + 1 < d.f_Pb ? gb + 1 : gb));
+                    const int gn = vadx::FRAG * (gb + 1 < d.f_Pb ? gb + 1 : gb);
                     const f32x4 en0 = vadx::ldg4(fe0 + gn), on0 = vadx::ldg4(fo0 + gn), en1 = vadx::ldg4(fe1 + gn), on1 = vadx::ldg4(fo1 + gn);
                     __builtin_amdgcn_sched_barrier(0);      // the next block's table fragments are requested before this block's MFMAs issue
                     const float *pas = pa + 16 * S * XF_LD, *pbs = pb + 16 * S * strB;
@@ -874,8 +839,8 @@ __device__ __forceinline__ void fold_tile(const Dev &d, const float *__restrict_
 #pragma unroll
                         for (int mt = 0; mt < MT; ++mt) {
                             const float xa = pas[j * XF_LD + mt * 16], xb = pbs[j * strB + mt * 16];
-                            u[mt] = (FE_WHATIF & 4) ? xa : __fadd_rn(xa, xb);
-                            v[mt] = (FE_WHATIF & 4) ? xb : __fsub_rn(xa, xb);
+                            u[mt] = __fadd_rn(xa, xb);
+                            v[mt] = __fsub_rn(xa, xb);
                         }
 #pragma unroll
                         for (int mt = 0; mt < MT; ++mt) {
@@ -901,7 +866,6 @@ __device__ __forceinline__ void fold_tile(const Dev &d, const float *__restrict_
                 for (int r = 0; r < 4; ++r)
                     pw[slot][mt][r] = __fadd_rn(__fmul_rn(acc[2 * slot][mt][r], acc[2 * slot][mt][r]), __fmul_rn(acc[2 * slot + 1][mt][r], acc[2 * slot + 1][mt][r]));
     }
-    FE_ACC(1);
     __syncthreads();                     // every wave is done with X2 / XS: the power rows take their place
 #pragma unroll
     for (int slot = 0; slot < 2; ++slot) {
@@ -923,9 +887,7 @@ __device__ __forceinline__ void fold_tile(const Dev &d, const float *__restrict_
         PW[(d.n_bins + r) * XF_LD + c2] = 0.f;
     }
     __syncthreads();
-    FE_ACC(2);
     mel_phase<MT, true>(d, P, PW, XF_LD, f0, out_win, plan + 4 * MAX_REGIONS);
-    FE_ACC(3);
 }
 
 __global__ __launch_bounds__(THREADS, 4) void frontend_fold_kernel(
@@ -961,13 +923,10 @@ __device__ __forceinline__ void fold3_tile(const Dev &d, const float *__restrict
     const int Kp = d.f_Pb * 16, pbc = d.f_Pb >> 1;                // pair slots; blocks per parity class
     const int *__restrict__ plan = reinterpret_cast<const int *>(P + d.off_plan);
 
-    FE_T0();
     for (int e = tid; e < 16 * XF_LD; e += THREADS) X2[d.hop * XF_LD + e] = 0.f;                      // the zero rows (lone taps, padding pairs)
     for (int e = tid; e < xs_pitch; e += THREADS) XS[cols * xs_pitch + e] = (_Float16)0.f;            // column read by the residual's padded taps
     stage_tile<XF_LD, true>(d, win, nullptr, mean, f0, cols, X2, XS, xs_pitch, d.f_xscale);
-    FE_ACC(4);
     __syncthreads();
-    FE_ACC(0);
 
     typedef int i32x4 __attribute__((ext_vector_type(4)));
     typedef const __attribute__((address_space(1))) i32x4 *global_i32x4_ptr;
@@ -1081,7 +1040,6 @@ __device__ __forceinline__ void fold3_tile(const Dev &d, const float *__restrict
                 pw[1][mt][r] = __fadd_rn(__fmul_rn(rm, rm), __fmul_rn(imm, imm));
             }
     }
-    FE_ACC(1);
     __syncthreads();                     // every wave is done with X2 / XS: the power rows take their place
     if (wave < nt3) {
         const int b = wave * 16 + i;
@@ -1102,9 +1060,7 @@ __device__ __forceinline__ void fold3_tile(const Dev &d, const float *__restrict
         PW[(d.n_bins + r) * XF_LD + c2] = 0.f;
     }
     __syncthreads();
-    FE_ACC(2);
     mel_phase<MT, true>(d, P, PW, XF_LD, f0, out_win, plan + d.f_Pb * 32);
-    FE_ACC(3);
 }
 
 __global__ __launch_bounds__(THREADS, 4) void frontend_fold3_kernel(
@@ -1141,9 +1097,7 @@ __device__ __forceinline__ int sq_slot(int b) { return b + 2 * ((b * 3277) >> 18
 constexpr int SQ_BLOCKS = 63 * 20 + 4 * 16;                                               // blocks of a 64-frame tile, taps <= 512
 constexpr int SQ_PLANE_BYTES = (SQ_BLOCKS + 2 * (SQ_BLOCKS / 80) + 2 + 7) / 8 * 8 * 16;
 constexpr int SQ_THREADS = 256, SQ_WAVES = SQ_THREADS / 64;
-#ifndef FE_RING
-#define FE_RING 2          /* table fragments requested FE_RING - 1 chunks ahead (layers_split.h: qgemm_group) */
-#endif
+constexpr int FE_RING = 2;          // table fragments requested FE_RING - 1 chunks ahead (layers_split.h: qgemm_group)
 static size_t split_lds_bytes(const Dev *d) {
     const size_t pw = (size_t)d->Fp * XF_LD * 4;
     return pw > 3 * (size_t)SQ_PLANE_BYTES ? pw : 3 * (size_t)SQ_PLANE_BYTES;
@@ -1163,7 +1117,6 @@ __device__ __forceinline__ void split_tile(const Dev &d, const float *__restrict
     const int q = lane >> 4, i = lane & 15;
     constexpr int NF = MT * 16;
     float *PW = reinterpret_cast<float *>(smem);
-    FE_T0();
     // ---- phase 0: prep + split: item = block of eight consecutive samples (all nine loads unconditional, from clamped indices)
     {
         const int n0 = f0 * d.hop + d.tap0 - d.center_pad, nblk = (NF - 1) * 20 + 4 * d.s_nch;
@@ -1199,9 +1152,7 @@ __device__ __forceinline__ void split_tile(const Dev &d, const float *__restrict
             for (int p = 0; p < NP; ++p) *reinterpret_cast<u32x4 *>(dp + p * SQ_PLANE_BYTES) = u32x4{pa[p][0], pa[p][1], pb[p][0], pb[p][1]};
         }
     }
-    FE_ACC(4);
     __syncthreads();
-    FE_ACC(0);
     // ---- phase 1: DFT as split products, |.|^2 kept in registers
     const float *tab = P + d.off_fold;
     const size_t tstride = (size_t)d.s_nch * NP * vadx::QFRAG;
@@ -1254,9 +1205,7 @@ __device__ __forceinline__ void split_tile(const Dev &d, const float *__restrict
             if (NP == 2) pl[rr] = __fmul_rn(pl[rr], d.s_ps);
         }
     }
-    FE_ACC(1);
     __syncthreads();                               // every sample block has been read: the power rows take the planes' place
-    FE_ACC(2);
     for (int r = 0; r < rounds; ++r) {
         const int bt = 4 * r + wave;
         if (bt >= d.s_nbt) break;
@@ -1272,7 +1221,6 @@ __device__ __forceinline__ void split_tile(const Dev &d, const float *__restrict
         for (int rr = 0; rr < 4; ++rr) PW[((d.s_nbt - 1) * 16 + 4 * q + rr) * XF_LD + wave * 16 + i] = pl[rr];
     __syncthreads();
     mel_phase<MT, true, SQ_WAVES>(d, P, PW, XF_LD, f0, out_win, reinterpret_cast<const int *>(P + d.off_plan));
-    FE_ACC(3);
 }
 
 template <typename SC>
@@ -1284,24 +1232,12 @@ __global__ __launch_bounds__(SQ_THREADS, 2) void frontend_split_kernel(
     const int widx = blockIdx.x / tiles, tile = blockIdx.x - widx * tiles;
     const int b = widx / windows_per_clip, w = widx - b * windows_per_clip;
     const int16_t *win = audio + (long long)b * row_stride + (long long)w * win_stride;
-#if FE_WHATIF & 16      // what-if: every workgroup stages window 0 of clip 0 (L2-warm samples): what a perfect prefetch of the samples could save
-    win = audio;
-#endif
     float *out_win = out + (size_t)widx * d.frames * d.out_stride;
     const float mean = means ? means[widx] : 0.f;
-#if FE_EXP
-    const long long fe_c0 = clock64(), fe_w0 = wall_clock64();
-#endif
     if (tile < d.tiles64) split_tile<SC, 4>(d, P, win, mean, tile * TF_FOLD, out_win, fsmem);
     else if (d.tail_mt == 3) split_tile<SC, 3>(d, P, win, mean, d.tiles64 * TF_FOLD, out_win, fsmem);
     else if (d.tail_mt == 2) split_tile<SC, 2>(d, P, win, mean, d.tiles64 * TF_FOLD, out_win, fsmem);
     else split_tile<SC, 1>(d, P, win, mean, d.tiles64 * TF_FOLD, out_win, fsmem);
-#if FE_EXP
-    if (threadIdx.x == 0) {     // shader clock against the constant 100 MHz counter
-        atomicAdd(&fe_dbg[5], (unsigned long long)(clock64() - fe_c0));
-        atomicAdd(&fe_dbg[6], (unsigned long long)(wall_clock64() - fe_w0));
-    }
-#endif
 }
 
 __global__ __launch_bounds__(THREADS, 4) void frontend_logmel_kernel(

@@ -19,24 +19,6 @@
 #include <math.h>
 #include <string.h>
 
-// FS_EXP: development-only cycle accounting (tools/exp_fsmn.py): per-section clock64 sums of thread 0, all workgroups
-#ifndef FS_EXP
-#define FS_EXP 0
-#endif
-#if FS_EXP
-__device__ unsigned long long fsmn_dbg[16];
-#define FS_T0() long long fs_t_ = clock64()
-#define FS_ACC(slot) do { if (threadIdx.x == 0) { const long long n_ = clock64(); atomicAdd(&fsmn_dbg[slot], (unsigned long long)(n_ - fs_t_)); fs_t_ = n_; } } while (0)
-extern "C" int vadx_fsmn_debug_cycles(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(fsmn_dbg), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(fsmn_dbg), z, sizeof(z)) != hipSuccess) return -1; }
-    return 0;
-}
-#else
-#define FS_T0() do {} while (0)
-#define FS_ACC(slot) do {} while (0)
-#endif
-
 namespace vadx {
 namespace fsmn {
 
@@ -118,7 +100,6 @@ __device__ __forceinline__ void tile(const Dev &d, const float *__restrict__ Pk,
     asm volatile("" : "+v"(tid));          // per tile: nothing derived from the thread index is hoisted out of the tile / window loops
     constexpr int NF = MTT * 16;
 
-    FS_T0();
     // ---- stage log-mel with LFR edge replication: bufB[mel][c] = lm[clamp(f0 + c - 2, 0, T-1)][mel]
     {   // batches of four loads per thread in flight (the index is always clamped into the chunk)
         constexpr int NE = (NF + 4) * NMEL, NIT = (NE + THREADS - 1) / THREADS;
@@ -140,18 +121,14 @@ __device__ __forceinline__ void tile(const Dev &d, const float *__restrict__ Pk,
             }
         }
     }
-    FS_ACC(0);
     __syncthreads();
-    FS_ACC(9);
 
     LayerArgs a;
     // in_linear1: K = 5 passes x 80 (LFR concat: frame offset j -> column offset j), CMVN on the operand
     a = LayerArgs{Pk + d.off_in1, 400, d.Ap / 16, LFR_M, NMEL / 16, NMEL, 1, Pk + d.off_b1, 0,
                   bufB, A_LD, 0, bufP, A_LD, 0, Pk + d.off_mean, Pk + d.off_var, bufA};      // bufA is idle: K-split scratch
     layer<MTT, true>(a);
-    FS_ACC(1);
     __syncthreads();
-    FS_ACC(9);
     // FIR caches: the five values a thread carries into bufP's history columns are requested one layer EARLY (layer 0's before in_linear2,
     // layer l + 1's before layer l's linear), so the round trip to the global cache hides behind a GEMM instead of opening every layer
     constexpr int NH = (PROJ * HIST + THREADS - 1) / THREADS;
@@ -165,9 +142,7 @@ __device__ __forceinline__ void tile(const Dev &d, const float *__restrict__ Pk,
     a = LayerArgs{Pk + d.off_in2, d.Ap, d.Lp / 16, 1, d.Ap / 16, 0, 0, Pk + d.off_b2, 1,
                   bufP, A_LD, 0, bufA, A_LD, 0, nullptr, nullptr};
     layer<MTT, false>(a);
-    FS_ACC(2);
     __syncthreads();
-    FS_ACC(9);
 
     for (int l = 0; l < NLAYER; ++l) {
         // history columns 1..19 of bufP <- cache (previous tile / previous chunk)
@@ -179,13 +154,10 @@ __device__ __forceinline__ void tile(const Dev &d, const float *__restrict__ Pk,
             }
             cache_fetch(l + 1 < NLAYER ? l + 1 : l, hv);      // next layer's values (the last iteration's request is unused)
         }
-        FS_ACC(3);
         a = LayerArgs{Pk + d.off_lin[l], d.Lp, PROJ / 16, 1, d.Lp / 16, 0, 0, nullptr, 0,
                       bufA, A_LD, 0, bufP, P_LD, P_CUR, nullptr, nullptr};
         layer<MTT, false>(a);
-        FS_ACC(4);
         __syncthreads();
-        FS_ACC(9);
         {   // FIR + skip: thread = (channel, quarter of the tile's frames)
             const int ch = tid >> 2, fq = tid & 3;
             constexpr int FPT = NF / 4;
@@ -210,15 +182,11 @@ __device__ __forceinline__ void tile(const Dev &d, const float *__restrict__ Pk,
                 stg1(cout[l] + e, bufP[c2 * P_LD + 1 + nvalid + h]);
             }
         }
-        FS_ACC(5);
         __syncthreads();
-        FS_ACC(9);
         a = LayerArgs{Pk + d.off_aff[l], PROJ, d.Lp / 16, 1, PROJ / 16, 0, 0, Pk + d.off_baff[l], 1,
                       bufB, A_LD, 0, bufA, A_LD, 0, nullptr, nullptr};
         layer<MTT, false>(a);
-        FS_ACC(6);
         __syncthreads();
-        FS_ACC(9);
     }
     a = LayerArgs{Pk + d.off_out1, d.Lp, d.A2p / 16, 1, d.Lp / 16, 0, 0, Pk + d.off_bo1, 0,
                   bufA, A_LD, 0, bufB, A_LD, 0, nullptr, nullptr, bufP};                      // bufP is idle: K-split scratch
@@ -227,10 +195,8 @@ __device__ __forceinline__ void tile(const Dev &d, const float *__restrict__ Pk,
     a = LayerArgs{Pk + d.off_out2, d.A2p, d.Op / 16, 1, d.A2p / 16, 0, 0, Pk + d.off_bo2, 0,
                   bufB, A_LD, 0, bufA, A_LD, 0, nullptr, nullptr};
     layer<MTT, false>(a);
-    FS_ACC(7);
     __syncthreads();
 
-    FS_ACC(9);
     // ---- softmax over the O logits of each frame, keep class 0: thread = (part 0..7, frame 0..63)
     {
         const int m = tid & 63, part = tid >> 6;
@@ -254,7 +220,6 @@ __device__ __forceinline__ void tile(const Dev &d, const float *__restrict__ Pk,
         }
         __syncthreads();
     }
-    FS_ACC(8);
 }
 
 
@@ -288,7 +253,6 @@ __device__ __forceinline__ void tile_split(const Dev &d, const float *__restrict
     const int lane = tid & 63, i = lane & 15;
     auto grp_pl = [](int kgrps, int ncol) { return kgrps * ncol * 16; };      // bytes of one plane
 
-    FS_T0();
     // ---- zero rows: k-groups of the A-wide tensors beyond Ap (their weights are zero, the operand must be finite), the log-mel's row 10
     {
         const int kg0 = d.Ap / 8, kg1 = 4 * d.nch_A, pl = grp_pl(kg1, NF);
@@ -325,18 +289,14 @@ __device__ __forceinline__ void tile_split(const Dev &d, const float *__restrict
             }
         }
     }
-    FS_ACC(0);
     __syncthreads();
-    FS_ACC(9);
 
     auto plain = [&](int ncol) { return [=](int kgrp, int mt) { return (kgrp * ncol + mt * 16 + i) * 16; }; };
     QLayerArgs a;
     // in_linear1: K = 5 LFR positions x 80 mels = 50 k-groups; k-group G = (position j = G / 10, mel group G % 10) reads column + j
     a = QLayerArgs{Pk + d.q_in1, d.Ap / 16, NCH_IN1, Pk + d.q_b1, 0, smem + SQ_LM, grp_pl(11, NCL), smem + SQ_H, grp_pl(4 * d.nch_A, NF), NF, nullptr};
     qlayer<SC, MTT, true>(a, [=](int G, int mt) { const int j = G / 10, mg = G - 10 * j; return G < 50 ? (mg * NCL + mt * 16 + i + j) * 16 : (10 * NCL + mt * 16 + i) * 16; }, amax);
-    FS_ACC(1);
     __syncthreads();
-    FS_ACC(9);
     constexpr int NH = (PROJ * HIST + THREADS - 1) / THREADS;
     auto cache_fetch = [&](int l, float (&hv)[NH]) {
 #pragma unroll
@@ -347,9 +307,7 @@ __device__ __forceinline__ void tile_split(const Dev &d, const float *__restrict
     // in_linear2 + ReLU
     a = QLayerArgs{Pk + d.q_in2, d.Lp / 16, d.nch_A, Pk + d.off_b2, 1, smem + SQ_H, grp_pl(4 * d.nch_A, NF), smem + SQ_HLM, grp_pl(4 * d.nch_L, NF), NF, nullptr};
     qlayer<SC, MTT, true>(a, plain(NF), amax);
-    FS_ACC(2);
     __syncthreads();
-    FS_ACC(9);
 
     for (int l = 0; l < NLAYER; ++l) {
         const bool even = (l & 1) == 0;
@@ -364,10 +322,8 @@ __device__ __forceinline__ void tile_split(const Dev &d, const float *__restrict
             }
             cache_fetch(l + 1 < NLAYER ? l + 1 : l, hv);
         }
-        FS_ACC(3);
         a = QLayerArgs{Pk + d.q_lin[l], PROJ / 16, d.nch_L, nullptr, 0, HLin, grp_pl(4 * d.nch_L, NF), reinterpret_cast<unsigned char *>(bufP), P_CUR, P_LD, nullptr};
         qlayer<SC, MTT, false>(a, plain(NF), amax);
-        FS_ACC(4);
         // the FIR taps of this thread's four channels (80 floats) are requested BEFORE the barrier: their L2 round trip hides behind the
         // wait for the slowest wave of the GEMM instead of opening the FIR (per channel: load, wait, 80 FMAs -- four times in a row)
         const int cg = tid >> 4, fg = tid & 15;
@@ -377,7 +333,6 @@ __device__ __forceinline__ void tile_split(const Dev &d, const float *__restrict
 #pragma unroll
             for (int k4 = 0; k4 < LORDER / 4; ++k4) fw[c][k4] = ldg4(Pk + d.off_fir[l] + (4 * cg + c) * LORDER + 4 * k4);
         __syncthreads();
-        FS_ACC(9);
         {   // FIR + skip: thread = (4 consecutive channels, 4 frames); the four channels of a frame leave as one 8-byte store per plane
             if (fg < NF / 4) {
                 f32x4 o[4];                                               // o[t][c]
@@ -418,14 +373,10 @@ __device__ __forceinline__ void tile_split(const Dev &d, const float *__restrict
                 stg1(cout[l] + e, bufP[c2 * P_LD + 1 + nvalid + h]);
             }
         }
-        FS_ACC(5);
         __syncthreads();
-        FS_ACC(9);
         a = QLayerArgs{Pk + d.q_aff[l], d.Lp / 16, PROJ / 32, Pk + d.off_baff[l], 1, FO, grp_pl(PROJ / 8, NF), HLout, grp_pl(4 * d.nch_L, NF), NF, nullptr};
         qlayer<SC, MTT, true>(a, plain(NF), amax);
-        FS_ACC(6);
         __syncthreads();
-        FS_ACC(9);
     }
     {   // zero rows of the A2-wide tensor (region 0 is free again)
         const int kg0 = d.A2p / 8, kg1 = 4 * d.nch_A2, pl = grp_pl(kg1, NF);
@@ -440,9 +391,7 @@ __device__ __forceinline__ void tile_split(const Dev &d, const float *__restrict
     float *logits = reinterpret_cast<float *>(smem + SQ_LOG);
     a = QLayerArgs{Pk + d.q_out2, d.Op / 16, d.nch_A2, Pk + d.off_bo2, 0, smem + SQ_H, grp_pl(4 * d.nch_A2, NF), reinterpret_cast<unsigned char *>(logits), 0, A_LD, nullptr};
     qlayer<SC, MTT, false>(a, plain(NF), amax);
-    FS_ACC(7);
     __syncthreads();
-    FS_ACC(9);
     {   // softmax over the O logits of each frame, keep class 0 (as tile<>)
         const int m = tid & 63, part = tid >> 6;
         float mx = -INFINITY;
@@ -465,7 +414,6 @@ __device__ __forceinline__ void tile_split(const Dev &d, const float *__restrict
         }
         __syncthreads();
     }
-    FS_ACC(8);
 }
 
 // score gate of one chunk (FSMN/Export_FSMN_VAD.py:87-101): returns noisy_dB (NaN if no frame is "noise")

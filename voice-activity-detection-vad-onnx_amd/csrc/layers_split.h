@@ -43,9 +43,6 @@ __device__ __forceinline__ void qgemm_group(f32x4 (&hi)[NT][MTT], f32x4 (&lo)[NT
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
-#if defined(QG_WHATIF) && (QG_WHATIF & 1)
-                if (kc > kc0) { a[nt][p] = ar[0][nt][p]; continue; }     // what-if: the weight stream costs nothing
-#endif
                 a[nt][p] = SC::ld(w[nt] + (size_t)(kc * NP + p) * QFRAG, lane);
             }
     };
@@ -59,10 +56,6 @@ __device__ __forceinline__ void qgemm_group(f32x4 (&hi)[NT][MTT], f32x4 (&lo)[NT
         for (int p = 0; p < NP; ++p)
 #pragma unroll
             for (int mt = 0; mt < MTT; ++mt) {
-#if defined(QG_WHATIF) && (QG_WHATIF & 2)
-                b[mt][p] = a[0][p];                 // what-if: the activation reads cost nothing
-                continue;
-#endif
                 b[mt][p] = SC::lds(act + boff[mt] + p * act_pl);
             }
         SC::template products<NT, MTT, OUT_PLANES>(a, b, hi, lo);

@@ -13,24 +13,6 @@
 #include "split_scheme.h"
 #include "layers_split.h"
 
-// MB_EXP: development-only cycle accounting of jasper_block2_kernel (tools/exp_marblenet.py): per-section clock64 sums of thread 0
-#ifndef MB_EXP
-#define MB_EXP 0
-#endif
-#if MB_EXP
-__device__ unsigned long long mb_dbg[16];
-#define MB_T0() long long mb_t_ = clock64()
-#define MB_ACC(slot) do { if (threadIdx.x == 0) { const long long n_ = clock64(); atomicAdd(&mb_dbg[slot], (unsigned long long)(n_ - mb_t_)); mb_t_ = n_; } } while (0)
-extern "C" int vadx_marblenet_debug_cycles(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mb_dbg), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(mb_dbg), z, sizeof(z)) != hipSuccess) return -1; }
-    return 0;
-}
-#else
-#define MB_T0() do {} while (0)
-#define MB_ACC(slot) do {} while (0)
-#endif
-
 #include <math.h>
 #include <type_traits>
 
@@ -317,9 +299,6 @@ __device__ __forceinline__ void kgemm(const KPre &p, int kdim, const float *act,
         if (u < nb) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-#if defined(MB_WHATIF) && (MB_WHATIF & 1)
-                if (j || (u & 1)) continue;                  // what-if: one MFMA in eight (the matrix time of an fp16 x 2 product)
-#endif
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) acc[mt] = vadx::mfma16(ap[(16 * u + j) * lda + mt * 16], p.w[u][j], acc[mt]);
             }
@@ -505,7 +484,6 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
     const int b = blockIdx.x / tiles, t0 = (blockIdx.x - b * tiles) * TILE;
     const float *xb = x + (long long)b * c.cin * c.T;
     const int tin0 = t0 - 2 * PAD;
-    MB_T0();
     const KP wres = kpre<AR>(rw, c.cinp);                    // in flight while the input tile is staged
     // ---- stage the block input (channel-first source: lane = time, wave = channel), unconditional clamped loads
     for (int ch0 = 0; ch0 < c.cinp; ch0 += 8 * (THREADS / 64)) {
@@ -522,9 +500,7 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
             if (lane < WIN0 && ch < c.cinp) IN[ch * IN_LD + lane] = (ch < c.cin && ti >= 0 && ti < c.T) ? v[u] : 0.f;
         }
     }
-    MB_ACC(0);
     __syncthreads();
-    MB_ACC(7);
     // pointwise 0's weights: in flight through the residual GEMM and depthwise 0 -- except at K = 17, whose 24-value window + 17 taps +
     // 16 prefetched weight registers no longer fit the 80 VGPRs of six waves per SIMD (20 B of scratch per lane doubled the kernel's
     // HBM writes): there they are requested behind the filter
@@ -535,13 +511,10 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
         split_rows_to_planes_n(IN, IN_LD, 2 * PAD, 8, TILE, PL, amax);
         __syncthreads();            // (the residual GEMM reads the planes only: depthwise 0 may overwrite IN behind this barrier)
         pgemm<2>(wres, PL, TILE, ROUT, A_LD, rb, false);
-        MB_ACC(1);
     } else {
         kmul<AR, 2>(wres, c.cinp, IN, IN_LD, 2 * PAD, ROUT, A_LD, rb, false, amax);
-        MB_ACC(1);
         __syncthreads();            // every residual operand is read: depthwise 0 may overwrite IN
     }
-    MB_ACC(7);
     // ---- depthwise 0 IN PLACE: register-window FIR, item = (channel, 8 outputs).  The six items of a channel are six neighbouring
     // lanes of ONE wave: a wave's window reads all precede its writes in program order (the FMAs in between depend on them), and
     // no two waves share a channel, so the overwrite needs no further barrier.
@@ -567,9 +540,7 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
         }
     }
     if (K >= 17) wpw0 = kpre<AR>(pw0, c.cinp);
-    MB_ACC(2);
     __syncthreads();
-    MB_ACC(7);
     KP wpw1;                                                 // pointwise 1's weights: in flight through pointwise 0 and depthwise 1
     if (K < 17) wpw1 = kpre<AR>(pw1, c.c1);
     // pointwise 0 + folded BN + ReLU on 48 columns
@@ -580,9 +551,7 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
     } else {
         kmul<AR, 3>(wpw0, c.cinp, D0, IN_LD, 0, H1, H_LD, b0, true, amax);
     }
-    MB_ACC(3);
     __syncthreads();
-    MB_ACC(7);
     // ---- depthwise 1 on H1 (column j = frame t0 - PAD + j; frames outside the clip are the conv's zero padding)
     for (int it = tid; it < c.c1 * (TILE / 8); it += THREADS) {
         const int ch = it / (TILE / 8), m0 = 8 * (it - ch * (TILE / 8));
@@ -607,9 +576,7 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
         store8(D1 + ch * A_LD + m0, o8);                                // D1 sits in IN's region (D0 is dead since the barrier above)
     }
     if (K >= 17) wpw1 = kpre<AR>(pw1, c.c1);
-    MB_ACC(4);
     __syncthreads();                // every H1 read is done: OUT may overwrite it
-    MB_ACC(7);
     if constexpr (AR == 3) {
         split_rows_to_planes_n(D1, A_LD, 0, 8, TILE, PL, amax);
         __syncthreads();
@@ -617,15 +584,12 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
     } else {
         kmul<AR, 2>(wpw1, c.c1, D1, A_LD, 0, OUT, A_LD, b1, false, amax);
     }
-    MB_ACC(5);
     __syncthreads();
-    MB_ACC(7);
     float *yb = y + (long long)b * c.c2 * c.T;
     for (int e = tid; e < c.c2 * TILE; e += THREADS) {
         const int ch = e / TILE, m = e - ch * TILE;
         if (t0 + m < c.T) yb[(long long)ch * c.T + t0 + m] = fmaxf(OUT[ch * A_LD + m] + ROUT[ch * A_LD + m], 0.f);
     }
-    MB_ACC(6);
     if (AR >= vadx::VADX_AR_H2 && !(amax <= vadx::H_MAX)) {          // an operand left the fp16 range: the host recomputes this batch on float32
         atomicOr(range_flag, 1u);
         atomicMax(range_flag + 1, __float_as_uint(amax));

@@ -19,43 +19,16 @@
 #include <stdlib.h>
 #include <string.h>
 
-#ifndef VADX_SILERO_ENCODER_DEFAULT
-// 0 = exact-f32 MFMA encoder, 1 = bf16 x 3 split-product encoder (silero_split.hip).  The split encoder is the default since
-// tests/test_gpu_silero.py::test_split_products_are_as_exact_as_f32_products showed it CLOSER to the float64 evaluation of the same
-// float32 network than the f32-MFMA encoder (max 9.3e-6 against 1.6e-5 on gx of scale 30, mean 2.1e-7 against 3.4e-7) and every
-// parity test of that file passes on both.
-#define VADX_SILERO_ENCODER_DEFAULT 2
-#endif
-
-// VADX_EXP: development-only what-if switches for tools/exp_encoder.py (results are wrong when set).
-#ifndef VADX_EXP
-#define VADX_EXP 0
-#endif
-#define ENC_SKIP(n) ((VADX_EXP >> (n)) & 1)          // VADX_EXP is a bit mask of what-if switches
-// bit 14: per-phase cycle accounting of wave 0 of every workgroup (s_memtime deltas summed into enc_dbg[slot]; read with
-// vadx_silero_debug_cycles, tools/exp_encoder.py) -- slot k = time from the previous mark to mark k
-#if (VADX_EXP >> 14) & 1
-__device__ unsigned long long enc_dbg[16];
-#define ENC_T0() long long enc_t_ = __builtin_readcyclecounter()
-#define ENC_MARK(slot) do { if (threadIdx.x == 0) { const long long n_ = __builtin_readcyclecounter(); atomicAdd(&enc_dbg[slot], (unsigned long long)(n_ - enc_t_)); enc_t_ = n_; } } while (0)
-extern "C" int vadx_silero_debug_cycles(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(enc_dbg), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(enc_dbg), z, sizeof(z)) != hipSuccess) return -1; }
-    return 0;
-}
-#else
-#define ENC_T0() do {} while (0)
-#define ENC_MARK(slot) do {} while (0)
-#endif
-#if (VADX_EXP >> 2) & 1
-#define ENC_SYNC() __builtin_amdgcn_wave_barrier()
-#else
-#define ENC_SYNC() __syncthreads()
-#endif
-
 namespace vadx {
 namespace silero {
 
+// The kernel set of VADX_ARITH_AUTO: 0 = exact-f32 MFMA encoder, 1 = bf16 x 3 split products (silero_split.hip), 2 = fp16 x 2 split
+// products (silero_h2.hip).  fp16 x 2 is the default: a batch that leaves the fp16 range raises the blob's range flag
+// (vadx_silero_range_flag), on which the caller recomputes it on bf16 x 3.  bf16 x 3 had replaced f32 as the default because
+// tests/test_gpu_silero.py::test_split_products_are_as_exact_as_f32_products showed it CLOSER to the float64 evaluation of the same
+// float32 network than the f32-MFMA encoder (max 9.3e-6 against 1.6e-5 on gx of scale 30, mean 2.1e-7 against 3.4e-7) and every
+// parity test of that file passes on both.
+constexpr int ENCODER_DEFAULT = 2;
 
 // ---- encoder LDS map (floats): 52 624 B per workgroup => THREE workgroups per CU ------------------
 // One region is reused by every phase; a phase whose output would overwrite its own input keeps the
@@ -124,7 +97,7 @@ __device__ __forceinline__ void gemm_planes3(f32x4 &a0, f32x4 &a1, f32x4 &a2, co
     for (int p = 0; p < 3; ++p) wc[p] = *reinterpret_cast<const f32x4 *>(w + p * KB * FRAG);
 #pragma unroll 4
     for (int S = 0; S < KB; ++S) {
-        const int Sn = ENC_SKIP(13) ? 0 : ((S + 1 < KB) ? S + 1 : S);
+        const int Sn = (S + 1 < KB) ? S + 1 : S;
 #pragma unroll
         for (int p = 0; p < 3; ++p) wn[p] = *reinterpret_cast<const f32x4 *>(w + (p * KB + Sn) * FRAG);
         const float *aps = ap + 16 * S * lda;
@@ -189,13 +162,12 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
     const int grp = blockIdx.x % G, t = blockIdx.x / G;
 
     const bool fold = P[OFF_FOLD] != 0.f;      // uniform: the basis has the DFT symmetries -> folded STFT pass
-    ENC_T0();
     // ---------------- phase 0: copy the 16 windows (576 samples each) + right reflect pad of 64
     // (folded pass: even / odd samples go to separate planes of the clip row)
     auto xslot = [fold](int pp) { return fold ? (pp & 1) * X_ODD + (pp >> 1) : pp; };
     {
         const long long base = (long long)t * 512 + origin;
-        const bool vec_ok = ((row_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(audio) & (SampleIO<SampleT>::VEC_ALIGN - 1)) == 0) && n_samples >= 4 && !ENC_SKIP(1);
+        const bool vec_ok = ((row_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(audio) & (SampleIO<SampleT>::VEC_ALIGN - 1)) == 0) && n_samples >= 4;
         // Work item e = (clip c, float4 p/4) of the 16 x 576-sample tile.  In the normal case every lane loads its
         // float4 UNCONDITIONALLY from a clamped address, all five loads back to back (a load under a condition -- even a
         // uniform one -- compiles to a branch plus a full wait: five serialised HBM round trips per tile); the rare edge
@@ -220,11 +192,6 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
                     xv[k2][j] = SampleIO<SampleT>::load4(src + 4 * f, in_scale);
                 }
             }
-#if (VADX_EXP >> 14) & 1
-            ENC_MARK(11);
-            if (xv[1][2][3] == 123.456f) X[0] = 0.f;
-            ENC_MARK(12);
-#endif
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2) {
                 float *row = X + (2 * wv + k2) * X_LDM;
@@ -257,11 +224,6 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
                 x4[it] = SampleIO<SampleT>::load4(src + idc, in_scale);
             }
         }
-#if (VADX_EXP >> 14) & 1
-        ENC_MARK(11);                                   // loads issued
-        if (x4[4][3] == 123.456f) X[0] = 0.f;           // (forces the wait here)
-        ENC_MARK(12);                                   // loads landed
-#endif
 #pragma unroll
         for (int it = 0; it < 5; ++it) {
             const int e = tid + ENC_THREADS * it;            // 16 clips x 144 float4
@@ -274,8 +236,6 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
                 float v[4];
                 if (vec_ok && bvalid && idx >= 0 && idx + 3 < n_samples) {
                     v[0] = x4[it][0]; v[1] = x4[it][1]; v[2] = x4[it][2]; v[3] = x4[it][3];
-                } else if (ENC_SKIP(1)) {
-                    v[0] = v[1] = v[2] = v[3] = 1e-3f * (float)(p & 63);
                 } else {
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj)
@@ -292,11 +252,7 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
         }
         }   // general path
     }
-#if (VADX_EXP >> 14) & 1
-    ENC_MARK(13);                                       // LDS writes issued
-#endif
-    ENC_SYNC();
-    ENC_MARK(0);
+    __syncthreads();
 
     // ---------------- phase 1: STFT conv -> magnitude (results stay in registers until every wave is done with X)
     if (fold) {
@@ -305,7 +261,7 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
         // bin 64 (its own mirror) on the VALU, spread over all eight waves: wave = (frame f = wave & 3, half h of n = 1..128),
         // lane = (clip i, quarter q of the half): 16 taps each, summed over q by shuffles and over h through the scratch
         float b64re = 0.f, b64im = 0.f;
-        if (!ENC_SKIP(7)) {
+        {
             const int f = wave & 3, h = wave >> 2, n0 = h * 64 + q * 16;
             // the lane's 16 + 16 coefficients as eight 16-byte loads, one group of four taps ahead of its use (they were 32 scalar
             // loads: 32 VMEM instructions per wave and tile).  This block runs BEFORE the folded MFMA pass: beside that pass's 32
@@ -349,14 +305,13 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
                 ore[f][r] = 0.f;
                 oim[f][r] = 0.f;
             }
-        if (!ENC_SKIP(4)) {
+        {
             const float *row = X + i * X_LDM + 128 * fp;                              // frame 2 fp starts 64 fp... x2 planes
             const float *wt = P + OFF_SF + tl * 16 * FRAG + lane * 4;                 // [E|O][re|im][4 blocks]
             stft_fold_class(ere, eim, row + 1 + q, row + 127 - q, wt, wt + 4 * FRAG);
             stft_fold_class(ore, oim, row + X_ODD + q, row + X_ODD + 127 - q, wt + 8 * FRAG, wt + 12 * FRAG);
         }
-        ENC_SYNC();          // every wave is done reading X: V may now overwrite it
-        ENC_MARK(1);
+        __syncthreads();          // every wave is done reading X: V may now overwrite it
         // Winograd input transform across the two waves that hold a bin's four frames: the fp = 0 wave stores its share
         // c[j][0] |X_0| + c[j][1] |X_1| of every plane, the fp = 1 wave adds c[j][2] |X_2| + c[j][3] |X_3| behind a barrier
         // (one store, one add: the sum does not depend on timing).
@@ -380,8 +335,7 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
             }
         }
         if (q == 0) { scr[wave * 32 + i] = b64re; scr[wave * 32 + 16 + i] = b64im; }      // partial (re, im) of bin 64, frame wave & 3
-        ENC_SYNC();
-        ENC_MARK(2);
+        __syncthreads();
         if (fp == 1) {
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
@@ -425,8 +379,7 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
             sim += __shfl_xor(sim, 16); sim += __shfl_xor(sim, 32);
             nyq = mag_sqrt(sre * sre + sim * sim);
         }
-        ENC_SYNC();          // every wave is done reading X: V may now overwrite it
-        ENC_MARK(3);
+        __syncthreads();          // every wave is done reading X: V may now overwrite it
         {   // this wave holds all four frames of its 16 bins: Winograd input transform in registers
             f32x4 m[4];
 #pragma unroll
@@ -439,15 +392,13 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
                 *reinterpret_cast<f32x4 *>(vr + j * 16) = WINO_BT[j][0] * m[0] + WINO_BT[j][1] * m[1] + WINO_BT[j][2] * m[2] + WINO_BT[j][3] * m[3];
         }
         if (wave < 4 && q == 0) scr[wave * 16 + i] = nyq;
-        ENC_SYNC();
-        ENC_MARK(4);
+        __syncthreads();
         if (tid < 96) {                                       // Nyquist bin: plane j = tid / 16, clip = tid % 16
             const int j = tid >> 4, c = tid & 15;
             V[128 * V_LD + j * 16 + c] = WINO_BT[j][0] * scr[c] + WINO_BT[j][1] * scr[16 + c] + WINO_BT[j][2] * scr[32 + c] + WINO_BT[j][3] * scr[48 + c];
         }
     }
-    ENC_SYNC();
-    ENC_MARK(5);
+    __syncthreads();
 
     // ---------------- phase 2: conv1 129->128, k3 s1 p1, ReLU as Winograd F(4,3) over the window's four frames:
     // six plane GEMMs M_j = U_j V_j (U_j = G g packed on the host in float64) instead of the ten tap GEMMs a direct
@@ -463,14 +414,13 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
 #pragma unroll
             for (int j = 0; j < 6; ++j) acc[j] = *reinterpret_cast<const f32x4 *>(vn + j * 16) * (j < 4 ? ua[j] : ub[j - 4]);
         }
-        if (!ENC_SKIP(5)) {
+        {
             const float *w0 = P + OFF_C1 + wave * 6 * 8 * FRAG + lane * 4;      // [oc tile][plane][8 blocks]
             gemm_planes3<8>(acc[0], acc[1], acc[2], V, V_LD, w0, lane);
             gemm_planes3<8>(acc[3], acc[4], acc[5], V + 48, V_LD, w0 + 3 * 8 * FRAG, lane);
         }
         const float bias = P[OFF_B1 + wave * 16 + i];
-        ENC_SYNC();          // every wave is done reading V: A1 may now overwrite it
-        ENC_MARK(6);
+        __syncthreads();          // every wave is done reading V: A1 may now overwrite it
         const f32x4 s12 = acc[1] + acc[2], d12 = acc[1] - acc[2], s34 = acc[3] + acc[4], d34 = acc[3] - acc[4];
         f32x4 y[4];
         y[0] = acc[0] + s12 + s34;
@@ -485,15 +435,13 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
             *reinterpret_cast<f32x4 *>(&A1[(wave * 16 + i) * A1_LD + f * 16 + 4 * q]) = v;
         }
     }
-    ENC_SYNC();
-    ENC_MARK(7);
+    __syncthreads();
 
     // ---------------- phase 3: conv2 128->64, k3 s2 p1, ReLU (out frame fp reads in frames 2fp-1..2fp+1)
     {
         const int nt = wave & 3, fp = wave >> 2;
         const float *w0 = P + OFF_C2 + nt * 24 * FRAG + lane * 4;      // [oc tile][tap*8 + S]: 24 blocks of 16 k
         f32x4 a2 = {0.f, 0.f, 0.f, 0.f};
-        if (ENC_SKIP(3)) {} else
         if (fp == 0) a2 = gemm_chain<8, 24, 8, 4>(A1, A1_LD, w0, lane, [](int b) { return (b / 8 - 1) * 16; });
         else a2 = gemm_chain<0, 24, 8, 4>(A1, A1_LD, w0, lane, [](int b) { return (b / 8 + 1) * 16; });
         const float bias = P[OFF_B2 + nt * 16 + i];
@@ -502,13 +450,12 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
         for (int r = 0; r < 4; ++r) v[r] = fmaxf(a2[r] + bias, 0.f);
         *reinterpret_cast<f32x4 *>(&A2[(nt * 16 + i) * A2_LD + fp * 16 + 4 * q]) = v;
     }
-    ENC_SYNC();
-    ENC_MARK(8);
+    __syncthreads();
 
     // ---------------- phase 4: conv3 64->64, k3 s2 p1, ReLU (1 out frame; tap 0 reads padding)
     if (wave < 4) {
         // [2 taps][64] contiguous: 8 blocks; tap ps reads A2 frame ps
-        const f32x4 a3 = ENC_SKIP(3) ? f32x4{0.f, 0.f, 0.f, 0.f} : gemm_chain<0, 8, 4, 4>(A2, A2_LD, P + OFF_C3 + wave * 8 * FRAG + lane * 4, lane,
+        const f32x4 a3 = gemm_chain<0, 8, 4, 4>(A2, A2_LD, P + OFF_C3 + wave * 8 * FRAG + lane * 4, lane,
                                                 [](int b) { return (b / 4) * 16; });
         const float bias = P[OFF_B3 + wave * 16 + i];
         f32x4 v;
@@ -516,20 +463,18 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
         for (int r = 0; r < 4; ++r) v[r] = fmaxf(a3[r] + bias, 0.f);
         *reinterpret_cast<f32x4 *>(&A3[(wave * 16 + i) * A3_LD + 4 * q]) = v;
     }
-    ENC_SYNC();
-    ENC_MARK(9);
+    __syncthreads();
 
     // ---------------- phase 5: conv4 64->128, k3 s1 p1, ReLU (1 frame in/out; centre tap only)
     {
-        const f32x4 a4 = ENC_SKIP(3) ? f32x4{0.f, 0.f, 0.f, 0.f} : gemm_chain<0, 4, 4, 4>(A3, A3_LD, P + OFF_C4 + wave * 4 * FRAG + lane * 4, lane, [](int) { return 0; });
+        const f32x4 a4 = gemm_chain<0, 4, 4, 4>(A3, A3_LD, P + OFF_C4 + wave * 4 * FRAG + lane * 4, lane, [](int) { return 0; });
         const float bias = P[OFF_B4 + wave * 16 + i];
         f32x4 v;
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = fmaxf(a4[r] + bias, 0.f);
         *reinterpret_cast<f32x4 *>(&A4[(wave * 16 + i) * A4_LD + 4 * q]) = v;
     }
-    ENC_SYNC();
-    ENC_MARK(10);
+    __syncthreads();
 
     // ---------------- phase 6: LSTM input projection, gate-major (D rows = hidden units)
     {
@@ -537,7 +482,7 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
 #pragma unroll
         for (int g = 0; g < 4; ++g)
             acc[g][0] = *reinterpret_cast<const f32x4 *>(P + OFF_BG + g * 128 + wave * 16 + 4 * q);
-        if (!ENC_SKIP(6)) {        // W_ih tiles [gate][wave][8 blocks]; D rows = hidden units (gate-major for the LSTM kernel)
+        {   // W_ih tiles [gate][wave][8 blocks]; D rows = hidden units (gate-major for the LSTM kernel)
             const float *wl = P + OFF_IH + wave * 8 * FRAG + lane * 4;
             const float *ap = A4 + (4 * q) * A4_LD + i;
             f32x4 wcur[4], wnxt[4];
@@ -545,9 +490,9 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
             for (int g = 0; g < 4; ++g) wcur[g] = *reinterpret_cast<const f32x4 *>(wl + g * 64 * FRAG);
 #pragma unroll
             for (int S = 0; S < 8; ++S) {
-                const int Sn = ENC_SKIP(13) ? 0 : ((S + 1 < 8) ? S + 1 : S);
+                const int Sn = (S + 1 < 8) ? S + 1 : S;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) wnxt[g] = *reinterpret_cast<const f32x4 *>(wl + (ENC_SKIP(13) ? 0 : g * 64 * FRAG) + Sn * FRAG);
+                for (int g = 0; g < 4; ++g) wnxt[g] = *reinterpret_cast<const f32x4 *>(wl + g * 64 * FRAG + Sn * FRAG);
                 __builtin_amdgcn_sched_barrier(0);
                 const float *aps = ap + 16 * S * A4_LD;
 #pragma unroll
@@ -563,9 +508,8 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
         float *dst = gx + ((size_t)t * Gws + g0 + grp) * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-            if (!ENC_SKIP(8) || acc[g][0][0] == 12345.f) *reinterpret_cast<f32x4 *>(dst + g * 256) = acc[g][0];
+            *reinterpret_cast<f32x4 *>(dst + g * 256) = acc[g][0];
     }
-    ENC_MARK(15);
 }
 
 // ---- persistent LSTM --------------------------------------------------------------------------
@@ -620,7 +564,7 @@ __global__ __launch_bounds__(LSTM_THREADS, 2) void silero_lstm_kernel(
     for (int t = 0; t < T; ++t) {
         const int tn = (t + 1 < T) ? t + 1 : t;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) gnxt[g] = ENC_SKIP(11) ? gcur[g] : *reinterpret_cast<const f32x4 *>(gsrc + tn * gstep + g * 256);
+        for (int g = 0; g < 4; ++g) gnxt[g] = *reinterpret_cast<const f32x4 *>(gsrc + tn * gstep + g * 256);
 
         // Gate-outer order: a gate's 32 MFMAs finish before the next gate's start, so its non-linearity (VALU +
         // transcendentals) runs in the shadow of the following gate's MFMAs instead of after all 128 of them; only
@@ -641,20 +585,20 @@ __global__ __launch_bounds__(LSTM_THREADS, 2) void silero_lstm_kernel(
         const f32x4 ai = gate(0), af = gate(1);
         f32x4 ig, fg, gg;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) ig[r] = ENC_SKIP(9) ? ai[r] * 1e-3f : gate_sigmoid(ai[r]);
+        for (int r = 0; r < 4; ++r) ig[r] = gate_sigmoid(ai[r]);
         const f32x4 ag = gate(2);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) fg[r] = ENC_SKIP(9) ? af[r] * 1e-3f : gate_sigmoid(af[r]);
+        for (int r = 0; r < 4; ++r) fg[r] = gate_sigmoid(af[r]);
         const f32x4 ao = gate(3);
         float dpart = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            gg[r] = ENC_SKIP(9) ? ag[r] * 1e-3f : gate_tanh(ag[r]);
+            gg[r] = gate_tanh(ag[r]);
             c[r] = fg[r] * c[r] + ig[r] * gg[r];
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            h[r] = ENC_SKIP(9) ? ao[r] * 1e-3f + c[r] * 1e-3f : gate_sigmoid(ao[r]) * gate_tanh(c[r]);
+            h[r] = gate_sigmoid(ao[r]) * gate_tanh(c[r]);
             dpart = fmaf(dw[r], fmaxf(h[r], 0.f), dpart);
         }
         const int nxt = cur ^ 1;
@@ -662,8 +606,8 @@ __global__ __launch_bounds__(LSTM_THREADS, 2) void silero_lstm_kernel(
         dpart += __shfl_xor(dpart, 16);
         dpart += __shfl_xor(dpart, 32);
         if (q == 0) part[(nxt * 8 + wave) * 16 + n] = dpart;
-        if (!ENC_SKIP(10)) __syncthreads();
-        if (wave == 0 && lane < 16 && bvalid && !ENC_SKIP(12)) {
+        __syncthreads();
+        if (wave == 0 && lane < 16 && bvalid) {
             float s = db;
 #pragma unroll
             for (int w = 0; w < 8; ++w) s += part[(nxt * 8 + w) * 16 + lane];
@@ -680,6 +624,9 @@ __global__ __launch_bounds__(LSTM_THREADS, 2) void silero_lstm_kernel(
 }
 
 // ---- segmenter: get_speech_timestamps' state machine (utils_vad.py:374-476), one clip/thread ----
+// SEG_CLIPS clips per wave: the state machine diverges per clip (a wave pays for every path its lanes take), and 64 clips per wave
+// leave three quarters of the CUs without work at 4096 clips
+constexpr int SEG_CLIPS = 16;
 __global__ void silero_segments_kernel(const float *__restrict__ probs, int B, int T,
                                        const long long *__restrict__ n_samples,
                                        vadx_silero_seg_params prm, long long *__restrict__ segs,
@@ -1067,7 +1014,7 @@ extern "C" int vadx_silero_pack_host(const vadx_silero_weights_host *w_in, float
 static int arith_of(const vadx_silero_cfg *cfg) {
     const int a = cfg ? cfg->arithmetic : VADX_ARITH_AUTO;
     switch (a) {
-        case VADX_ARITH_AUTO: return VADX_SILERO_ENCODER_DEFAULT;
+        case VADX_ARITH_AUTO: return ENCODER_DEFAULT;
         case VADX_ARITH_F32: return 0;
         case VADX_ARITH_BF16X3: return 1;
         case VADX_ARITH_F16X2: return 2;
@@ -1245,11 +1192,6 @@ extern "C" int vadx_silero_segments(const float *probs, int batch, int steps, co
     VADX_REQUIRE(batch > 0 && steps > 0 && cap > 0, "vadx_silero_segments: batch/steps/cap must be positive");
     VADX_REQUIRE(params->sampling_rate == 16000 || params->sampling_rate == 8000,
                  "Currently silero VAD models support 8000 and 16000 (or multiply of 16000) sample rates");
-    // SEG_CLIPS clips per wave: the state machine diverges per clip (a wave pays for every path its lanes take), and 64 clips per wave
-    // leave three quarters of the CUs without work at 4096 clips
-#ifndef SEG_CLIPS
-#define SEG_CLIPS 16
-#endif
     hipLaunchKernelGGL(silero_segments_kernel, dim3((batch + SEG_CLIPS - 1) / SEG_CLIPS), dim3(SEG_CLIPS), 0, static_cast<hipStream_t>(stream),
                        probs, batch, steps, reinterpret_cast<const long long *>(n_samples), *params,
                        reinterpret_cast<long long *>(segments), counts, cap);

@@ -19,19 +19,6 @@
 #include "silero_common.h"
 #include "split2.h"
 
-// VADX_EXP: development-only what-if switches for tools/exp_encoder.py (results are wrong when set): bit 3 no conv2..4 MFMAs, 4 no STFT
-// MFMAs, 5 no conv1 MFMAs, 6 no W_ih MFMAs, 13 every weight fragment from one address (L1 instead of L2), 14 per-phase cycle accounting
-// of wave 0 (h2_dbg, read with vadx_silero_h2_debug_cycles)
-#ifndef VADX_EXP
-#define VADX_EXP 0
-#endif
-#define H2_SKIP(n) ((VADX_EXP >> (n)) & 1)
-// H2_XP: which phases request their first weight fragments BEFORE the barrier that ends the phase in front of them (bit 0 STFT, 1 conv1,
-// 2 conv2, 3 conv4 / W_ih), bit 4: conv2 requests its whole stream (six sets) up front
-#ifndef H2_XP
-#define H2_XP 1
-#endif
-#define H2_XP_ON(n) ((H2_XP >> (n)) & 1)
 // Every phase re-derives its thread indices from a laundered copy of the thread id: nothing computed from them (LDS offsets, fragment
 // pointers of LATER phases) can then be hoisted to the top of the tile loop, where it would sit in registers -- or in scratch -- through
 // every phase in between.
@@ -40,94 +27,20 @@
     asm volatile("" : "+v"(t_));                                                                           \
     const int tid = t_, lane = tid & 63, wave = tid >> 6, q = lane >> 4, i = lane & 15;                    \
     (void)tid; (void)lane; (void)wave; (void)q; (void)i
-// how many steps ahead of the MFMAs each phase's fragment stream runs (register sets = steps + 1)
-#ifndef H2_AHS
-#define H2_AHS 2      // STFT
-#endif
-#ifndef H2_AH1
-#define H2_AH1 2      // conv1
-#endif
-#define H2_W(addr) (H2_SKIP(13) ? (P + vadx::silero::OFF_H1) : (addr))
-// bit 10: EVERY fragment load reads one 16-byte piece (all lanes the same address): the kernel without its L1 request stream
-#define H2_LN (H2_SKIP(10) ? 0 : lane)
-// bit 9: the W_ih fragments alone as single L1 accesses from one address (what a W_ih pass over more columns per fragment could approach);
-// bit 8: the STFT's
-#define H2_WIH(addr) ((H2_SKIP(9) || H2_SKIP(13)) ? (P + vadx::silero::OFF_H1) : (addr))
-#define H2_LIH ((H2_SKIP(9) || H2_SKIP(10)) ? 0 : lane)
-#define H2_WST(addr) ((H2_SKIP(8) || H2_SKIP(13)) ? (P + vadx::silero::OFF_H1) : (addr))
-#define H2_LST ((H2_SKIP(8) || H2_SKIP(10)) ? 0 : lane)
-#if (VADX_EXP >> 14) & 1
-__device__ unsigned long long h2_dbg[16];
-#define H2_T0() long long h2_t_ = __builtin_readcyclecounter(); const long long h2_c0_ = h2_t_, h2_w0_ = wall_clock64()
-#define H2_CLK() do { if (threadIdx.x == 0) { atomicAdd(&h2_dbg[14], (unsigned long long)(__builtin_readcyclecounter() - h2_c0_)); atomicAdd(&h2_dbg[15], (unsigned long long)(wall_clock64() - h2_w0_)); } } while (0)
-#define H2_MARK(slot) do { if (threadIdx.x == 0) { const long long n_ = __builtin_readcyclecounter(); atomicAdd(&h2_dbg[slot], (unsigned long long)(n_ - h2_t_)); h2_t_ = n_; } } while (0)
-extern "C" int vadx_silero_h2_debug_cycles(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(h2_dbg), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(h2_dbg), z, sizeof(z)) != hipSuccess) return -1; }
-    return 0;
-}
-#else
-#define H2_T0() do {} while (0)
-#define H2_MARK(slot) do {} while (0)
-#define H2_CLK() do {} while (0)
-#endif
-
-// H2_DUMP (debugging): per (tile, stage) an order-independent checksum of the LDS region the stage just produced, into a caller's buffer
-// (vadx_silero_h2_dump): stage 0 operand planes, 1 |X| planes + scratch, 2 conv1 planes, 3 conv2 planes
-#ifndef H2_DUMP
-#define H2_DUMP 0
-#endif
-#ifndef H2_PK_NATURAL
-#define H2_PK_NATURAL 0
-#endif
-// H2_TRACE (development, tools/h2_trace.py): sixteen workgroups spread over the grid record the shader clock of lane 0 of every wave right before
-// and right after each barrier (H2_SYNC(k): marks 2 k, 2 k + 1; the per-tile barriers at + 32 per tile of the workgroup) -- a timeline of
-// where the waves of a workgroup wait, with a few stores per phase as the only perturbation
-#ifndef H2_TRACE
-#define H2_TRACE 0
-#endif
-#ifndef H2_PAIR_T
-#define H2_PAIR_T 1
-#endif
-#if H2_TRACE
-__device__ unsigned long long h2_trace_buf[16][8][128];
-extern "C" int vadx_silero_h2_trace(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(h2_trace_buf), sizeof(unsigned long long) * 16 * 8 * 128) != hipSuccess) return -1;
-    if (reset) { static unsigned long long z[16 * 8 * 128]; if (hipMemcpyToSymbol(HIP_SYMBOL(h2_trace_buf), z, sizeof(z)) != hipSuccess) return -1; }
-    return 0;
-}
-#define H2_TR(m) do { if (h2_tr_slot >= 0 && (threadIdx.x & 63) == 0) h2_trace_buf[h2_tr_slot][threadIdx.x >> 6][(m) + h2_tr_off] = __builtin_readcyclecounter(); } while (0)
-#define H2_SYNC(k) do { H2_TR(2 * (k)); __syncthreads(); H2_TR(2 * (k) + 1); } while (0)
-#else
-#define H2_TR(m) do {} while (0)
-#define H2_SYNC(k) __syncthreads()
-#endif
-// H2_PRIO: wave priority (s_setprio) inside the GEMM loops, 0 elsewhere: the SIMD's arbiter then prefers the waves that feed the matrix pipe over
-// co-resident waves in their VALU phases
-#ifndef H2_PRIO
-#define H2_PRIO 0
-#endif
-
-#define H2_PRIO_ON() do { if (H2_PRIO) __builtin_amdgcn_s_setprio(H2_PRIO); } while (0)
-#define H2_PRIO_OFF() do { if (H2_PRIO) __builtin_amdgcn_s_setprio(0); } while (0)
-// (round 6, measured at config 2, built then removed: H2_PRIO = 1 -- 3.59 -> 3.85 ms, the waves in their VALU phases are starved and reach the
-//  barriers later; the second tile's samples requested at the start of the first tile's conv2 phase instead of in its own staging phase --
-//  3.59 -> 4.35 ms: the 24 registers do not exist beside conv2's, scratch 36 -> 148 B; a persistent grid of 512 workgroups walking the tile
-//  pairs, the upper half started 0 / 24 000 / 48 000 / 72 000 shader cycles late so that a CU's two workgroups run a fixed fraction of a tile
-//  period apart -- 3.55 -> 3.60 / 3.60 / 3.60 / 3.61 ms: no offset beats the dispatcher's own staggering.)
-#if H2_DUMP
-__device__ unsigned *h2_dump_ptr;
-extern "C" int vadx_silero_h2_dump(unsigned *buf) { return hipMemcpyToSymbol(HIP_SYMBOL(h2_dump_ptr), &buf, sizeof(buf)) == hipSuccess ? 0 : -1; }
-#define H2_SUM(stage, base, bytes) do { unsigned acc_ = 0; for (int o_ = threadIdx.x * 4; o_ < (bytes); o_ += 512 * 4) acc_ += *reinterpret_cast<const unsigned *>(smem + (base) + o_) * (unsigned)(2 * o_ + 1); \
-    atomicAdd(h2_dump_ptr + (size_t)tile_id * 4 + (stage), acc_); } while (0)
-#else
-#define H2_SUM(stage, base, bytes) do {} while (0)
-#endif
+// (round 6, measured at config 2, built then removed: wave priority 1 (s_setprio) inside the GEMM loops -- 3.59 -> 3.85 ms, the waves in their
+//  VALU phases are starved and reach the barriers later; the second tile's samples requested at the start of the first tile's conv2 phase
+//  instead of in its own staging phase -- 3.59 -> 4.35 ms: the 24 registers do not exist beside conv2's, scratch 36 -> 148 B; a persistent grid
+//  of 512 workgroups walking the tile pairs, the upper half started 0 / 24 000 / 48 000 / 72 000 shader cycles late so that a CU's two
+//  workgroups run a fixed fraction of a tile period apart -- 3.55 -> 3.60 / 3.60 / 3.60 / 3.61 ms: no offset beats the dispatcher's own
+//  staggering.)
 
 namespace vadx {
 namespace silero {
 
 constexpr int H2_THREADS = 512;
+constexpr int H2_WAVES_PER_SIMD = 4;
+// how many steps ahead of the MFMAs the STFT's and conv1's fragment streams run (register sets = steps + 1)
+constexpr int H2_AHS = 2, H2_AH1 = 2;
 // ---- LDS map (BYTES): 81 920 B per workgroup => two workgroups per CU (eight waves of <= 128 VGPRs each)
 //   R0 [0, 65536): X f32 [16 clips][642]
 //                  -> STFT operand planes [E|O][e|o][2 planes][8 k-groups][4 frames x 16 clips][8 fp16]                (65 536 B)
@@ -146,10 +59,11 @@ constexpr int H2_EXC2 = 36864, H2_EXC3 = 45056;
 constexpr int H2_C2 = 53248, H2_PL2 = 4096, H2_FR2 = 2048;
 constexpr int H2_R1 = 65536, H2_T3 = 4096, H2_PL3 = 2048;
 constexpr int H2_C4 = 0, H2_T4 = 8192, H2_PL4 = 4096;
-constexpr int H2_NSUB_MAX = 4;
-constexpr int H2_LDS_BYTES = H2_R1 + H2_NSUB_MAX * H2_T3;
+// tiles a workgroup encodes one after the other before ONE joint conv4 / W_ih pass (R1 holds their conv3 planes)
+constexpr int H2_NSUB = 4;
+constexpr int H2_LDS_BYTES = H2_R1 + H2_NSUB * H2_T3;
 static_assert(16 * X_LDM * 4 <= H2_EXC3 && H2_EXC3 + 4096 <= H2_C2 && H2_C2 + 2 * H2_PL2 <= H2_R1, "fp16 x 2 encoder LDS map: a tile");
-static_assert(H2_C4 + H2_NSUB_MAX * H2_T4 <= H2_SCR && 2 * H2_LDS_BYTES <= 160 * 1024, "fp16 x 2 encoder LDS map: the tail");
+static_assert(H2_C4 + H2_NSUB * H2_T4 <= H2_SCR && 2 * H2_LDS_BYTES <= 160 * 1024, "fp16 x 2 encoder LDS map: the tail");
 
 __device__ __forceinline__ int hpl_off(int kg8, int clip) { return (kg8 * 16 + clip) * 16; }
 
@@ -175,17 +89,11 @@ __device__ __forceinline__ void load_b2(f16x8 (&b)[2], const unsigned char *base
     b[1] = *reinterpret_cast<const f16x8 *>(s + plane_stride);
 }
 __device__ __forceinline__ void load_a2(f16x8 (&a)[2], const float *frag2, int lane) {
-    a[0] = ldh(frag2, H2_LN);
+    a[0] = ldh(frag2, lane);
     a[1] = ldh(frag2 + HF, lane);
 }
 
 template <typename SampleT, int NSUB>
-#ifndef H2_WAVES_PER_SIMD
-#define H2_WAVES_PER_SIMD 4
-#endif
-#ifndef H2_LDS_PAD
-#define H2_LDS_PAD 0          // debugging: extra dynamic LDS per workgroup (> 0 forces one workgroup per CU)
-#endif
 __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h2_kernel(
     const float *__restrict__ P, const SampleT *__restrict__ audio, float in_scale, long long n_samples,
     long long row_stride, long long origin, int B, int G, int T, int Gws, int g0, float *__restrict__ gx) {
@@ -194,48 +102,26 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
     float *scr = reinterpret_cast<float *>(smem + H2_SCR), *nyq = scr, *b64p = scr + 256;
 
     int tid0 = threadIdx.x;
-    const long long ntile = (long long)G * T;
-    (void)ntile;
-#if H2_TRACE
-    const int h2_tr_slot = (blockIdx.x % 2503u == 1201u && blockIdx.x / 2503u < 16u) ? (int)(blockIdx.x / 2503u) : -1;
-    int h2_tr_off = 0;
-    H2_TR(126);
-#endif
     float amax = 0.f;                   // running max |x| of everything this thread splits
     if (ldg1(P + OFF_HFLAG) == 0.f) {   // uniform: this blob cannot run on fp16 x 2 (basis without the fold, a weight outside the range)
         if (threadIdx.x == 0 && blockIdx.x == 0) atomicOr(reinterpret_cast<unsigned *>(const_cast<float *>(P)) + OFF_HFLAG + 1, 2u);
         return;
     }
-    H2_T0();
     const long long blk = blockIdx.x;
-    // the workgroup's tiles: a workgroup's NSUB tiles are CONSECUTIVE WINDOWS of one clip group (H2_PAIR_T: window t = NSUB * (blk / G) + sub
-    // of group blk % G): the next tile's samples are the next 2 KB of the same sixteen rows -- same pages, same DRAM rows as the loads the
+    // the workgroup's tiles: a workgroup's NSUB tiles are CONSECUTIVE WINDOWS of one clip group (window t = NSUB * (blk / G) + sub of
+    // group blk % G): the next tile's samples are the next 2 KB of the same sixteen rows -- same pages, same DRAM rows as the loads the
     // previous tile has just made -- instead of sixteen rows 10 MB away (adjacent groups of one window, the round-5 order).  The valid
     // slots are a prefix of the NSUB; nvalid depends on blockIdx alone (workgroup-uniform), so a slot past the last window skips its whole
     // tile, barriers included, and the tail multiplies only the nvalid column tiles.
-#if H2_PAIR_T
     const int nvalid = (int)min((long long)NSUB, (long long)T - (blk / G) * NSUB);
-#else
-    const int nvalid = (int)min((long long)NSUB, ntile - blk * NSUB);
-#endif
     {
-    // Cross-phase fragment prefetch: the first sets of a phase's weight stream are requested BEFORE the barrier that ends the phase in front of
-    // it (global loads stay in flight across s_barrier, which only waits for lgkmcnt), so the L2 round trip that used to open every phase
-    // runs under the previous phase's epilogue.  pre_* = those sets, named per consumer.
+    // Cross-phase fragment prefetch: the first sets of the STFT's weight stream are requested BEFORE the barrier that ends the staging phase
+    // (global loads stay in flight across s_barrier, which only waits for lgkmcnt), so the L2 round trip that used to open the STFT runs
+    // under the staging epilogue.  pre_s = those sets.
 #pragma unroll 1
     for (int sub = 0; sub < nvalid; ++sub) {
     // per tile: nothing derived from the thread index is hoisted out of the tile loop (see silero_split.hip)
-#if H2_PAIR_T
     const int grp = (int)(blk % G), t = (int)(blk / G) * NSUB + sub;
-    const int tile_id = t * G + grp;
-    (void)tile_id;
-#else
-    const int tile_id = (int)(blk * NSUB + sub);
-    const int grp = tile_id % G, t = tile_id / G;
-#endif
-#if H2_TRACE
-    h2_tr_off = 32 * sub;
-#endif
 
     // ---------------- phase 0: the 16 windows (576 samples each) + right reflect pad of 64, even / odd samples in separate planes of the
     // clip row (as silero_encode_kernel stages them for the folded pass)
@@ -322,21 +208,19 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
         }
     }
     f16x8 pre_s[H2_AHS][2];           // the STFT's first sets: in flight while the samples go to registers and the operand planes are built
-    if (H2_XP_ON(0)) {
+    {
         H2_IDS();
         const float *wq = P + OFF_HSF + (size_t)(wave & 3) * (2 * 2 * 2 * 2 * HF);
 #pragma unroll
-        for (int s0_ = 0; s0_ < H2_AHS; ++s0_) load_a2(pre_s[s0_], H2_WST(wq + s0_ * 2 * HF), H2_LST);
+        for (int s0_ = 0; s0_ < H2_AHS; ++s0_) load_a2(pre_s[s0_], wq + s0_ * 2 * HF, lane);
     }
-    H2_SYNC(0);
-    H2_MARK(0);
+    __syncthreads();
 
     // ---------------- phase 1: the folded STFT on split products -> magnitudes -> the two fp16 planes of conv1's input.
     // Per frame f (samples 128 f .. 128 f + 255 of the padded window) and pair index n = 1..128: e = x[n] + x[256 - n] (cos part),
     // o = the difference (sin part), in two classes (E: n = 2 m + 2, O: n = 2 m + 1: the frequency fold); bins k <= 63 of tile tl:
     //   X[k] = E + O, X[128 - k] = +-(E - O), with E / O = the class's partial sums (silero_common.h: stft_fold_class).
     // Input-channel slot s of conv1: s <= 64 = bin s, s = 64 + k = bin 128 - k; bin 128 (Nyquist) goes to the scratch.
-    f16x8 pre_1[2][2], pre_2[2][2];
     {
         H2_IDS();
         const int tl = wave & 3, fp = wave >> 2;                  // GEMM role: bins 16 tl + 4 q + r (and 128 - them), frames 2 fp, 2 fp + 1, clip i
@@ -359,18 +243,7 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
             // bin 64's piece of this wave: (class bc, part bp) of the fifth tile for the wave's two frames; the n = 0 tap rides in the
             // even class's accumulator (row 0 = lanes q = 0, element 0)
             const int bc = (wave >> 1) & 1, bp = wave & 1;
-#if H2_DUMP
-            {   // stage 0: the samples this thread holds, weighted by who holds them
-                unsigned acc_ = 0;
-                for (int f = 0; f < 4; ++f) for (int k = 0; k < 4; ++k) acc_ += (__float_as_uint(xa[f][k]) * 3u + __float_as_uint(xb[f][k])) * (unsigned)(2 * (tid * 16 + f * 4 + k) + 1);
-                atomicAdd(h2_dump_ptr + (size_t)tile_id * 4 + 0, acc_);
-            }
-#endif
-            H2_SYNC(1);          // every sample is in registers: the operand planes may overwrite X
-            H2_MARK(1);
-#if H2_DUMP
-            unsigned accr_ = 0, acce_ = 0;
-#endif
+            __syncthreads();          // every sample is in registers: the operand planes may overwrite X
 #pragma unroll
             for (int f = 0; f < 4; ++f) {
                 f32x4 ev, ov;
@@ -378,19 +251,11 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
                 for (int k = 0; k < 4; ++k) {
                     // (plain v_add_f32 / v_sub_f32, spelled out: left to the compiler the pair sums become v_pk_add_f32 with a CROSS op_sel swizzle
                     //  -- xb is read in descending order -- and that form returned wrong sums in roughly every second tile once two workgroups
-                    //  (four waves per SIMD) shared a CU, while the same binary was bit-exact at one workgroup per CU: tests/probes/h2_race.py,
+                    //  (four waves per SIMD) shared a CU, while the same binary was bit-exact at one workgroup per CU: profiles/r06_pk_hazard.txt,
                     //  DESIGN.md section 4e)
                     float e_, o_;
-#if H2_PK_NATURAL     // development only (tests/probes/pk_hazard.py): the plain-C sums the compiler turns into cross-swizzled v_pk_add_f32
-                    e_ = xa[f][k] + xb[f][k];
-                    o_ = xa[f][k] - xb[f][k];
-#if H2_PK_NATURAL == 2      // ... and nothing may follow the sums for a few cycles
-                    asm volatile("s_nop 7" : "+v"(e_), "+v"(o_));
-#endif
-#else
                     asm volatile("v_add_f32 %0, %1, %2" : "=v"(e_) : "v"(xa[f][k]), "v"(xb[f][k]));
                     asm volatile("v_sub_f32 %0, %1, %2" : "=v"(o_) : "v"(xa[f][k]), "v"(xb[f][k]));
-#endif
                     ev[k] = e_;
                     ov[k] = o_;
                 }
@@ -402,22 +267,8 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
                 split2x4(ov, p0, p1, amax);
                 *reinterpret_cast<u32x2 *>(d + 2 * H2_EO_PL) = p0;
                 *reinterpret_cast<u32x2 *>(d + 3 * H2_EO_PL) = p1;
-#if H2_PK_NATURAL == 3       // ... and the samples stay in their registers until the frame's planes are stored (no early reuse of a source register)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) asm volatile("" :: "v"(xa[f][k]), "v"(xb[f][k]));
-#endif
-#if H2_DUMP
-                for (int k = 0; k < 4; ++k) acce_ += (__float_as_uint(ev[k]) * 5u + __float_as_uint(ov[k])) * (unsigned)(2 * (tid * 16 + f * 4 + k) + 1);
-                accr_ += (p0[0] * 3u + p0[1] * 7u + p1[0] * 11u + p1[1] * 13u) * (unsigned)(2 * (tid * 4 + f) + 1);
-#endif
             }
-#if H2_DUMP
-            atomicAdd(h2_dump_ptr + (size_t)tile_id * 4 + 2, acce_);
-            atomicAdd(h2_dump_ptr + (size_t)tile_id * 4 + 3, accr_);
-#endif
-            H2_SYNC(2);
-            H2_MARK(2);
-            H2_SUM(1, 0, 65536);
+            __syncthreads();
             // ---- the wave's GEMM: (class, part) = (E re, E im, O re, O im) x two chunks x its two frames
             const f32x4 c0 = ldg4(P + OFF_S0 + tl * 16 + 4 * q), s0 = ldg4(P + OFF_S0 + 64 + tl * 16 + 4 * q);
             const float b64n0 = bc ? 0.f : ldg1(P + OFF_B64 + 256 + bp);
@@ -432,19 +283,15 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
                 for (int a4 = 0; a4 < 4; ++a4) mid[a4][fr] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
             const float *wb = P + OFF_HSF + (size_t)((4 * 2 + bc) * 2 + bp) * (2 * 2 * HF);
-            if (!H2_SKIP(4)) {
+            {
                 const float *wq = P + OFF_HSF + (size_t)tl * (2 * 2 * 2 * 2 * HF);
                 constexpr int AH = H2_AHS;
                 f16x8 a[AH + 1][2];
 #pragma unroll
-                for (int s0_ = 0; s0_ < AH; ++s0_) {
-                    if (H2_XP_ON(0)) { a[s0_][0] = pre_s[s0_][0]; a[s0_][1] = pre_s[s0_][1]; }
-                    else load_a2(a[s0_], H2_W(wq + s0_ * 2 * HF), H2_LN);
-                }
-                H2_PRIO_ON();
+                for (int s0_ = 0; s0_ < AH; ++s0_) { a[s0_][0] = pre_s[s0_][0]; a[s0_][1] = pre_s[s0_][1]; }
 #pragma unroll
                 for (int s8 = 0; s8 < 8; ++s8) {          // s8 = (class, part, chunk) in OFF_HSF's order
-                    if (s8 + AH < 8) load_a2(a[(s8 + AH) % (AH + 1)], H2_WST(wq + (s8 + AH) * 2 * HF), H2_LST);
+                    if (s8 + AH < 8) load_a2(a[(s8 + AH) % (AH + 1)], wq + (s8 + AH) * 2 * HF, lane);
                     f16x8 b[2][2];
 #pragma unroll
                     for (int fr = 0; fr < 2; ++fr) {
@@ -460,16 +307,10 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
 #pragma unroll
                     for (int fr = 0; fr < 2; ++fr) hi[s8 >> 1][fr] = mfma_f16(ac[0], b[fr][0], hi[s8 >> 1][fr]);
                 }
-                H2_PRIO_OFF();
             }
             f16x8 ab[2][2];                               // the bin-64 piece's two chunks: requested before the magnitudes, used after them
-            load_a2(ab[0], H2_WST(wb), H2_LST);
-            load_a2(ab[1], H2_WST(wb + 2 * HF), H2_LST);
-            if (H2_XP_ON(1)) {   // conv1's first two sets
-                const float *w1 = P + OFF_H1 + wave * (4 * 3 * 2 * HF);
-                load_a2(pre_1[0], H2_W(w1), H2_LN);
-                load_a2(pre_1[1], H2_W(w1 + 2 * HF), H2_LN);
-            }
+            load_a2(ab[0], wb, lane);
+            load_a2(ab[1], wb + 2 * HF, lane);
 #pragma unroll
             for (int fr = 0; fr < 2; ++fr) {
                 const f32x4 ere = join2(hi[0][fr], mid[0][fr]), eim = join2(hi[1][fr], mid[1][fr]);
@@ -490,13 +331,12 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
                     const unsigned char *bs = smem + ((bc * 2 + bp) * 2) * H2_EO_PL + (4 * ch + q) * H2_EO_KG + (16 * (2 * fp + fr) + i) * 16;
                     b[0] = *reinterpret_cast<const f16x8 *>(bs);
                     b[1] = *reinterpret_cast<const f16x8 *>(bs + H2_EO_PL);
-                    if (!H2_SKIP(4)) mfma_split3(ab[ch], b, bhi, bmid);
+                    mfma_split3(ab[ch], b, bhi, bmid);
                 }
                 b64[fr] = fmaf(bmid[0], H1_INV, bhi[0]);
             }
         }
-        H2_SYNC(3);          // every wave is done reading the operand planes: the |X| planes may overwrite them
-        H2_MARK(3);
+        __syncthreads();          // every wave is done reading the operand planes: the |X| planes may overwrite them
         {
             H2_IDS();             // (fresh indices: the store offsets below must not be computed -- and parked -- in front of the GEMM)
             const int g = 4 * (wave & 3) + q;
@@ -510,7 +350,7 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
                 if (q == 0) b64p[(wave * 2 + fr) * 16 + i] = b64[fr];
             }
         }
-        H2_SYNC(4);
+        __syncthreads();
         if (tid < 64) {                                                       // bin 64: frame tid / 16, clip tid % 16
             const int f = tid >> 4, c = tid & 15;
             const float *pp = b64p + ((f >> 1) * 8 + (f & 1)) * 16 + c;       // waves 4 (f >> 1) + (class, part), part fastest
@@ -518,8 +358,7 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
             store_h1(smem + f * H2_FR128, H2_PL128, 64, c, mag_sqrt(re * re + im * im), amax);
         }
     }
-    H2_SYNC(5);
-    H2_MARK(4);
+    __syncthreads();
 
     // ---------------- phase 2: conv1 129->128, k3 s1 p1, ReLU -- direct: out[f] = sum_tap W[tap] in[f + tap - 1], wave = 16 output channels
     {
@@ -550,11 +389,7 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
         constexpr int AH = H2_AH1;
         f16x8 a[AH + 1][2];
 #pragma unroll
-        for (int s0_ = 0; s0_ < AH; ++s0_) {
-            if (H2_XP_ON(1)) { a[s0_][0] = pre_1[s0_][0]; a[s0_][1] = pre_1[s0_][1]; }
-            else load_a2(a[s0_], H2_W(wq + s0_ * 2 * HF), H2_LN);
-        }
-        H2_PRIO_ON();
+        for (int s0_ = 0; s0_ < AH; ++s0_) load_a2(a[s0_], wq + s0_ * 2 * HF, lane);
 #pragma unroll
         for (int kc = 0; kc < 4; ++kc) {
             f16x8 b[4][2];
@@ -563,26 +398,19 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
 #pragma unroll
             for (int tap = 0; tap < 3; ++tap) {
                 const int s = kc * 3 + tap;
-                if (s + AH < 12) load_a2(a[(s + AH) % (AH + 1)], H2_W(wq + (s + AH) * 2 * HF), H2_LN);
+                if (s + AH < 12) load_a2(a[(s + AH) % (AH + 1)], wq + (s + AH) * 2 * HF, lane);
                 const f16x8 (&ac)[2] = a[s % (AH + 1)];
                 // three products per (frame, tap), frames innermost so that consecutive MFMAs hit different accumulators
 #define H2_TERM(AP, BP, ACC)                                                                  \
     _Pragma("unroll") for (int f = 0; f < 4; ++f) {                                           \
         const int fi = f + tap - 1;                                                           \
-        if (fi >= 0 && fi < 4 && !H2_SKIP(5)) ACC[f] = mfma_f16(ac[AP], b[fi][BP], ACC[f]);   \
+        if (fi >= 0 && fi < 4) ACC[f] = mfma_f16(ac[AP], b[fi][BP], ACC[f]);                  \
     }
                 H2_TERM(1, 0, mid) H2_TERM(0, 1, mid) H2_TERM(0, 0, hi)
 #undef H2_TERM
             }
         }
-        H2_PRIO_OFF();
-        if (H2_XP_ON(2)) {   // conv2's first two sets
-            const float *w2 = P + OFF_H2 + ((wave & 3) * 4 + 2 * (wave >> 2)) * (3 * 2 * HF);
-            load_a2(pre_2[0], H2_W(w2), H2_LN);
-            load_a2(pre_2[1], H2_W(w2 + 2 * HF), H2_LN);
-        }
-        H2_SYNC(6);          // every wave is done reading the |X| planes: conv1's output may now overwrite them
-        H2_MARK(5);
+        __syncthreads();          // every wave is done reading the |X| planes: conv1's output may now overwrite them
 #pragma unroll
         for (int f = 0; f < 4; ++f) {
             const f32x4 s = join2(hi[f], mid[f]);
@@ -592,8 +420,7 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
             store_h4(smem + f * H2_FR128, H2_PL128, 4 * rt + q, i, y, amax);
         }
     }
-    H2_SYNC(7);
-    H2_MARK(6);
+    __syncthreads();
 
     // ---------------- phase 3: conv2 128->64, k3 s2 p1, ReLU: out frame o reads in frames 2 o - 1 .. 2 o + 1; wave = (16 channels, half of K)
     {
@@ -603,18 +430,10 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
 #pragma unroll
         for (int o = 0; o < 2; ++o) { hi[o] = f32x4{0.f, 0.f, 0.f, 0.f}; mid[o] = hi[o]; }
         const float *wq = P + OFF_H2 + (rt * 4 + 2 * kh) * (3 * 2 * HF);
-        constexpr int RING = H2_XP_ON(4) ? 6 : 3;      // the wave's whole stream (six sets) up front, or two steps ahead on three register sets
+        constexpr int RING = 3;      // two steps ahead on three register sets
         f16x8 a[RING][2];
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            if (H2_XP_ON(2)) { a[s][0] = pre_2[s][0]; a[s][1] = pre_2[s][1]; }
-            else load_a2(a[s], H2_W(wq + s * 2 * HF), H2_LN);
-        }
-        if (RING == 6) {
-#pragma unroll
-            for (int s = 2; s < 6; ++s) load_a2(a[s % RING], H2_W(wq + s * 2 * HF), H2_LN);
-        }
-        H2_PRIO_ON();
+        for (int s = 0; s < 2; ++s) load_a2(a[s], wq + s * 2 * HF, lane);
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             f16x8 b[4][2];
@@ -623,25 +442,24 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
 #pragma unroll
             for (int tap = 0; tap < 3; ++tap) {
                 const int s = kk * 3 + tap;
-                if (RING == 3 && s + 2 < 6) load_a2(a[(s + 2) % RING], H2_W(wq + (s + 2) * 2 * HF), H2_LN);
+                if (s + 2 < 6) load_a2(a[(s + 2) % RING], wq + (s + 2) * 2 * HF, lane);
                 const f16x8 (&ac)[2] = a[s % RING];
 #define H2_TERM(AP, BP, ACC)                                                                  \
     _Pragma("unroll") for (int o = 0; o < 2; ++o) {                                           \
         const int fi = 2 * o + tap - 1;                                                       \
-        if (fi >= 0 && !H2_SKIP(3)) ACC[o] = mfma_f16(ac[AP], b[fi][BP], ACC[o]);             \
+        if (fi >= 0) ACC[o] = mfma_f16(ac[AP], b[fi][BP], ACC[o]);                            \
     }
                 H2_TERM(1, 0, mid) H2_TERM(0, 1, mid) H2_TERM(0, 0, hi)
 #undef H2_TERM
             }
         }
-        H2_PRIO_OFF();
         f32x4 s2[2] = {join2(hi[0], mid[0]), join2(hi[1], mid[1])};
         float *exc = reinterpret_cast<float *>(smem + H2_EXC2);
         if (kh == 1) {
 #pragma unroll
             for (int o = 0; o < 2; ++o) *reinterpret_cast<f32x4 *>(exc + ((rt * 2 + o) * 64 + lane) * 4) = s2[o];
         }
-        H2_SYNC(8);
+        __syncthreads();
         if (kh == 0) {
             const f32x4 bias = ldg4(P + OFF_B2 + 16 * rt + 4 * q);
 #pragma unroll
@@ -658,11 +476,10 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
     {
         H2_IDS();
         const float *w3 = P + OFF_H3 + ((wave & 3) * 2 + (wave >> 2)) * (2 * 2 * HF);
-        load_a2(pre_3[0], H2_W(w3), H2_LN);
-        load_a2(pre_3[1], H2_W(w3 + 2 * HF), H2_LN);
+        load_a2(pre_3[0], w3, lane);
+        load_a2(pre_3[1], w3 + 2 * HF, lane);
     }
-    H2_SYNC(9);
-    H2_MARK(7);
+    __syncthreads();
 
     // ---------------- phase 4: conv3 64->64, k3 s2 p1, ReLU (one output frame; tap 0 reads padding): wave = (16 channels, tap 1 | 2).  Its
     // output goes to the tile's slot of R1; the next tile's staging touches none of conv3's inputs (see the LDS map), so no barrier follows
@@ -674,11 +491,11 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
         for (int kc = 0; kc < 2; ++kc) {
             f16x8 b[2];
             load_b2(b, smem + H2_C2 + th * H2_FR2, H2_PL2, kc, q, i);
-            if (!H2_SKIP(3)) mfma_split3(pre_3[kc], b, hi, mid);
+            mfma_split3(pre_3[kc], b, hi, mid);
         }
         float *exc = reinterpret_cast<float *>(smem + H2_EXC3);
         if (th == 1) *reinterpret_cast<f32x4 *>(exc + (rt * 64 + lane) * 4) = join2(hi, mid);
-        H2_SYNC(10);
+        __syncthreads();
         if (th == 0) {
             const f32x4 bias = ldg4(P + OFF_B3 + 16 * rt + 4 * q);
             const f32x4 s3 = join2(hi, mid), other = *reinterpret_cast<const f32x4 *>(exc + (rt * 64 + lane) * 4);
@@ -688,22 +505,11 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
             store_h4(smem + H2_R1 + sub * H2_T3, H2_PL3, 4 * rt + q, i, y, amax);
         }
     }
-    H2_MARK(8);
     }      // sub
 
-#if H2_TRACE
-    h2_tr_off = 96;                     // the tail's barriers (H2_SYNC(11), H2_SYNC(12)) land at marks 118 .. 121
-#endif
     // W_ih step j (0 .. 15) multiplies fragment pair s = 4 kc + g: gate half gh = j / 8 (gates 2 gh, 2 gh + 1), kc = (j / 2) % 4, g = 2 gh + j % 2
     auto ih_s = [](int j) { return 4 * ((j >> 1) & 3) + 2 * (j >> 3) + (j & 1); };
-    f16x8 pre_4[2][2], pre_ih[2][2];
-    if (H2_XP_ON(3)) {   // conv4's two sets, requested before the barrier that ends the last tile's conv3
-        H2_IDS();
-        const float *w4 = P + OFF_H4 + wave * (2 * 2 * HF);
-        load_a2(pre_4[0], H2_W(w4), H2_LN);
-        load_a2(pre_4[1], H2_W(w4 + 2 * HF), H2_LN);
-    }
-    H2_SYNC(11);         // every tile's conv3 planes are in R1; R0 is free
+    __syncthreads();         // every tile's conv3 planes are in R1; R0 is free
     // ---------------- phase 5: conv4 64->128, k3 s1 p1, ReLU (one frame in / out: centre tap only), the nvalid tiles at once: R1 -> R0
     {
         H2_IDS();
@@ -712,16 +518,10 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
         f32x4 hi[NSUB], mid[NSUB];
 #pragma unroll
         for (int sb = 0; sb < NSUB; ++sb) { hi[sb] = bias; mid[sb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        if (H2_XP_ON(3)) {   // W_ih's first two sets
-            const float *wi = P + OFF_HIH + wave * (4 * 4 * 2 * HF);
-#pragma unroll
-            for (int s0_ = 0; s0_ < 2; ++s0_) load_a2(pre_ih[s0_], H2_WIH(wi + ih_s(s0_) * 2 * HF), H2_LIH);
-        } else {
-            const float *w4 = P + OFF_H4 + wave * (2 * 2 * HF);
-            load_a2(pre_4[0], H2_W(w4), H2_LN);
-            load_a2(pre_4[1], H2_W(w4 + 2 * HF), H2_LN);
-        }
-        const f16x8 (&a)[2][2] = pre_4;
+        const float *w4 = P + OFF_H4 + wave * (2 * 2 * HF);
+        f16x8 a[2][2];
+        load_a2(a[0], w4, lane);
+        load_a2(a[1], w4 + 2 * HF, lane);
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc)
 #pragma unroll
@@ -729,7 +529,7 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
                 if (sb < nvalid) {
                     f16x8 b[2];
                     load_b2(b, smem + H2_R1 + sb * H2_T3, H2_PL3, kc, q, i);
-                    if (!H2_SKIP(3)) mfma_split3(a[kc], b, hi[sb], mid[sb]);
+                    mfma_split3(a[kc], b, hi[sb], mid[sb]);
                 }
             }
 #pragma unroll
@@ -747,8 +547,7 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
         if (__ballot(bad) != 0ULL && lane == 0) reinterpret_cast<unsigned *>(scr)[128 + wave] = 1u;
         else if (lane == 0) reinterpret_cast<unsigned *>(scr)[128 + wave] = 0u;
     }
-    H2_SYNC(12);
-    H2_MARK(9);
+    __syncthreads();
 
     // ---------------- phase 6: LSTM input projection for the workgroup's tiles at once (D rows = hidden units 16 wave + 4 q + r, columns =
     // clips), in two gate halves {0, 1}, {2, 3} so that the accumulators of four column tiles fit: every W_ih fragment pair is loaded once
@@ -763,10 +562,7 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
         // the fragment ring holds two k-chunks (the current one's two gates and the next one's, requested when the current one starts)
         f16x8 a[2][2][2];
 #pragma unroll
-        for (int gg = 0; gg < 2; ++gg) {
-            if (H2_XP_ON(3)) { a[0][gg][0] = pre_ih[gg][0]; a[0][gg][1] = pre_ih[gg][1]; }
-            else load_a2(a[0][gg], H2_WIH(wq + ih_s(gg) * 2 * HF), H2_LIH);
-        }
+        for (int gg = 0; gg < 2; ++gg) load_a2(a[0][gg], wq + ih_s(gg) * 2 * HF, lane);
 #pragma unroll
         for (int gh = 0; gh < 2; ++gh) {
             f32x4 hi[NSUB][2], mid[NSUB][2];
@@ -776,13 +572,12 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
 #pragma unroll
                 for (int sb = 0; sb < NSUB; ++sb) { hi[sb][gg] = bg; mid[sb][gg] = f32x4{0.f, 0.f, 0.f, 0.f}; }
             }
-            H2_PRIO_ON();
 #pragma unroll
             for (int kc = 0; kc < 4; ++kc) {
                 const int j = 8 * gh + 2 * kc;            // the step of (kc, gate 2 gh)
 #pragma unroll
                 for (int gg = 0; gg < 2; ++gg)
-                    if (j + 2 < 16) load_a2(a[((j >> 1) + 1) & 1][gg], H2_WIH(wq + ih_s(j + 2 + gg) * 2 * HF), H2_LIH);
+                    if (j + 2 < 16) load_a2(a[((j >> 1) + 1) & 1][gg], wq + ih_s(j + 2 + gg) * 2 * HF, lane);
                 const f16x8 (&ac)[2][2] = a[(j >> 1) & 1];
                 // column tile outermost: one tile's B pair is live at a time (a single accumulation chain costs the 16x16x32 MFMA nothing)
 #pragma unroll
@@ -792,21 +587,15 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
                         load_b2(b, smem + H2_C4 + sb * H2_T4, H2_PL4, kc, q, i);
 #pragma unroll
                         for (int gg = 0; gg < 2; ++gg)
-                            if (!H2_SKIP(6)) mfma_split3(ac[gg], b, hi[sb][gg], mid[sb][gg]);
+                            mfma_split3(ac[gg], b, hi[sb][gg], mid[sb][gg]);
                     }
                 }
             }
-            H2_PRIO_OFF();
 #pragma unroll
             for (int sb = 0; sb < NSUB; ++sb) {
                 if (sb >= nvalid) continue;
-#if H2_PAIR_T
                 const int t_s = (int)(blk / G) * NSUB + sb, grp_s = (int)(blk % G);
                 float *dst = gx + ((size_t)t_s * Gws + g0 + grp_s) * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
-#else
-                const int tile_s = (int)(blk * NSUB + sb);
-                float *dst = gx + ((size_t)(tile_s / G) * Gws + g0 + tile_s % G) * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
-#endif
                 if (!poison) {           // (workgroup-uniform: a branch, not 32 selects)
 #pragma unroll
                     for (int gg = 0; gg < 2; ++gg) *reinterpret_cast<f32x4 *>(dst + (2 * gh + gg) * 256) = join2(hi[sb][gg], mid[sb][gg]);
@@ -826,12 +615,6 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
         atomicOr(fl, 1u);
         atomicMax(fl + 1, __float_as_uint(amax));
     }
-    H2_MARK(10);
-    H2_CLK();
-#if H2_TRACE
-    h2_tr_off = 0;
-    H2_TR(127);
-#endif
 }
 
 // ---- persistent LSTM on fp16 x 2 products ------------------------------------------------------
@@ -842,6 +625,10 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
 constexpr int LH_HPL = 4096, LH_HBUF = 8192;     // h planes [2 buffers][2 planes][16 k-groups][16 clips][8 fp16]
 constexpr int LH_PART = 2 * LH_HBUF;             // f32 [2][8 waves][16 clips]
 constexpr int LH_BYTES = LH_PART + 1024;
+// gx (the encoder's gate pre-activations, 32 KB per step and workgroup out of HBM: 2.6 GB per launch at config 2 = 4.3 TB/s) is requested
+// LH_GX_AHEAD steps ahead: with one step of lead a lone workgroup ran 1.42 us per step and the full grid 1.95 -- the loaded HBM's
+// latency exceeds a step.
+constexpr int LH_GX_AHEAD = 3;
 
 __global__ __launch_bounds__(512, 2) void silero_lstm_h2_kernel(
     const float *__restrict__ P, const float *__restrict__ gx, const float *__restrict__ state0,
@@ -886,15 +673,10 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_h2_kernel(
 
     const float *gsrc = gx + (size_t)grp * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
     const size_t gstep = (size_t)G * GX_TILE_FLOATS;
-    // gx (the encoder's gate pre-activations, 32 KB per step and workgroup out of HBM: 2.6 GB per launch at config 2 = 4.3 TB/s) is requested
-    // LH_GX_AHEAD steps ahead: with one step of lead a lone workgroup ran 1.42 us per step and the full grid 1.95 -- the loaded HBM's
-    // latency exceeds a step.  The ring is indexed statically (the step loop is unrolled by its depth).
+    // the gx ring (LH_GX_AHEAD steps) is indexed statically: the step loop is unrolled by its depth
 // (round 6, measured, removed: gate-major MFMA order -- a gate's twelve products finish before the next gate's start, so that its non-linearity
 //  runs under the next gate's MFMAs, all four B fragment pairs held in registers -- 0.590 -> 0.597 ms with gx two steps ahead, 0.65 with three
 //  (44 B of scratch): the compiler interleaves v_exp / v_rcp with the MFMAs as intended, the step is no shorter.)
-#ifndef LH_GX_AHEAD
-#define LH_GX_AHEAD 3
-#endif
     constexpr int GA = LH_GX_AHEAD;
     f32x4 gq[GA][4];
 #pragma unroll
@@ -984,19 +766,13 @@ int silero_lstm_h2_launch(const float *packed, const float *gx, const float *sta
     return VADX_OK;
 }
 
-// VADX_H2_NSUB: tiles a workgroup encodes one after the other before ONE joint conv4 / W_ih pass (at most H2_NSUB_MAX: R1 holds their
-// conv3 planes)
-#ifndef VADX_H2_NSUB
-#define VADX_H2_NSUB 4
-#endif
 template <typename S>
 int silero_encode_h2_launch(const float *packed, const S *src, float in_scale, long long n_valid, long long row_stride,
                             long long origin, int batch, int G, int steps, int Gws, int first_group, float *gx, void *stream) {
-    constexpr int NS = VADX_H2_NSUB;
-    static_assert(NS >= 1 && NS <= H2_NSUB_MAX, "VADX_H2_NSUB");
-    constexpr int LDS = H2_LDS_BYTES + H2_LDS_PAD;
+    constexpr int NS = H2_NSUB;
+    constexpr int LDS = H2_LDS_BYTES;
     VADX_DYN_LDS((silero_encode_h2_kernel<S, NS>), LDS);
-    const long long nblk = H2_PAIR_T ? (long long)G * ((steps + NS - 1) / NS) : ((long long)G * steps + NS - 1) / NS;
+    const long long nblk = (long long)G * ((steps + NS - 1) / NS);
     hipLaunchKernelGGL((silero_encode_h2_kernel<S, NS>), dim3((unsigned)nblk), dim3(H2_THREADS), LDS, static_cast<hipStream_t>(stream),
                        packed, src, in_scale, n_valid, row_stride, origin, batch, G, steps, Gws, first_group, gx);
     VADX_HIP_TRY(hipGetLastError());

@@ -16,38 +16,6 @@
 #include "silero_common.h"
 #include "split3.h"
 
-// VADX_EXP: development-only what-if switches for tools/exp_encoder.py (results are wrong when set): bit 3 no conv2..4 MFMAs, 4 no STFT
-// MFMAs, 5 no conv1 MFMAs, 6 no W_ih MFMAs, 11 no W_ih phase at all (neither fragments nor MFMAs), 13 every weight fragment from one address (L1 instead of L2), 12 no activation splits
-// (planes written from the raw bits), 14 per-phase cycle accounting of wave 0 (sp_dbg, read with vadx_silero_split_debug_cycles)
-#ifndef VADX_EXP
-#define VADX_EXP 0
-#endif
-#define SP_SKIP(n) ((VADX_EXP >> (n)) & 1)
-// VADX_SPLIT_STFT = 1 (or bit 15 of VADX_EXP): the folded STFT itself on split products -- built, parity-green on every test of
-// tests/test_gpu_silero.py, and measured EQUAL to the f32-MFMA fold (5.60 against 5.62 ms per launch): it issues 96 bf16 instead of 128
-// f32 MFMAs per wave and tile but streams 384 KB of table fragments per tile instead of 128 KB, and the fragment stream out of L2 is what
-// holds this kernel (every fragment from one L1-resident address: 4.10 ms with this STFT, 4.65 with the f32 fold, 5.95 as shipped on
-// the same box).  Not the default.
-#ifndef VADX_SPLIT_STFT
-#define VADX_SPLIT_STFT ((VADX_EXP >> 15) & 1)
-#endif
-#define SP_W(addr) (SP_SKIP(13) ? (P + vadx::silero::OFF_Q1) : (addr))        // what-if: every weight fragment from one (L1-resident) address
-#if (VADX_EXP >> 14) & 1
-__device__ unsigned long long sp_dbg[16];
-#define SP_T0() long long sp_t_ = __builtin_readcyclecounter(); const long long sp_c0_ = sp_t_, sp_w0_ = wall_clock64()
-// slots 14 / 15: shader cycles and 100 MHz ticks of the whole workgroup -> the clock the kernel sustains
-#define SP_CLK() do { if (threadIdx.x == 0) { atomicAdd(&sp_dbg[14], (unsigned long long)(__builtin_readcyclecounter() - sp_c0_)); atomicAdd(&sp_dbg[15], (unsigned long long)(wall_clock64() - sp_w0_)); } } while (0)
-#define SP_MARK(slot) do { if (threadIdx.x == 0) { const long long n_ = __builtin_readcyclecounter(); atomicAdd(&sp_dbg[slot], (unsigned long long)(n_ - sp_t_)); sp_t_ = n_; } } while (0)
-extern "C" int vadx_silero_split_debug_cycles(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(sp_dbg), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(sp_dbg), z, sizeof(z)) != hipSuccess) return -1; }
-    return 0;
-}
-#else
-#define SP_T0() do {} while (0)
-#define SP_MARK(slot) do {} while (0)
-#define SP_CLK() do {} while (0)
-#endif
 
 namespace vadx {
 namespace silero {
@@ -104,10 +72,10 @@ __device__ __forceinline__ void load_a3(bf16x8 (&a)[3], const float *frag3, int 
     for (int p = 0; p < 3; ++p) a[p] = ldq(frag3 + p * QF, lane);
 }
 
-// HALVES = 2 (an experiment kept for the record, not the default -- see VADX_SPLIT_HALVES): a 1024-thread workgroup whose two halves
+// HALVES = 2 (an experiment kept for the record, not the default -- see SP_HALVES): a 1024-thread workgroup whose two halves
 // encode two neighbouring tiles in lockstep, each in its own LDS region.  Same registers, same LDS and the same 16 waves per CU as two
 // 512-thread workgroups, but the halves stream the SAME weight fragments at the same moment, so the second request of every line is an
-// L1 hit instead of an L2 read (the weight stream out of L2 is the kernel's largest stall: tools/exp_encoder.py, "every fragment from
+// L1 hit instead of an L2 read (the weight stream out of L2 is the kernel's largest stall: a build that read "every fragment from
 // one address" 5.77 -> 4.51 ms).
 template <typename SampleT, int HALVES, int NSUB>
 __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_kernel(
@@ -122,7 +90,6 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
     int tid0 = threadIdx.x & (SP_THREADS - 1);
     const long long ntile = (long long)G * T;
     const bool fold = P[OFF_FOLD] != 0.f;      // uniform: the basis has the DFT symmetries -> folded STFT pass
-    SP_T0();
 #pragma unroll 1
     for (int sub = 0; sub < NSUB; ++sub) {
     // per tile: nothing derived from the thread index is hoisted out of the tile loop (every phase's per-lane LDS offsets and fragment
@@ -217,132 +184,12 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
         }
     }
     __syncthreads();
-    SP_MARK(0);
 
     // ---------------- phase 1: STFT (float32 MFMAs, table = A operand) -> magnitudes -> the three bf16 planes of conv1's input.
     // Input-channel slot s of conv1: s <= 64 = bin s, s = 64 + k = bin 128 - k; bin 128 (Nyquist) goes to the scratch.
-    if (fold && VADX_SPLIT_STFT) {
-        // ---- the folded STFT itself on split products.  The fold's operands are sums / differences of sample PAIRS: per frame f and pair
-        // index n = 1..128, e = x[128 f + n] + x[128 f + 256 - n] (cos part), o = the difference (sin part), in two classes (even / odd n:
-        // the frequency fold).  Thread (clip, class, four consecutive pairs of the class) reads its 32 samples out of X ONCE, into
-        // registers; the four frames then go in two pairs: its e / o values as 8-byte stores into the pair's B planes (which take X's
-        // place: [E e | E o | O e | O o][plane][k-group][2 frames x 16 clips][8]) | barrier | wave (bin tile, frame of the pair): four
-        // accumulators (E re, E im, O re, O im) x two k-steps x six products | barrier.  96 bf16 MFMAs per wave and tile instead of 128 f32,
-        // no operand arithmetic beside the matrix instructions.
-        const int cls = wave >> 2, pc = tid & 15, pj = (tid >> 4) & 15;
-        float xa[4][4], xb[4][4];                     // [frame][k]: the pair's two samples (plane indices: see stft_fold_class)
-        {
-            const float *row = X + pc * X_LDM + (cls ? X_ODD : 1) + 4 * pj, *rowb = X + pc * X_LDM + (cls ? X_ODD : 0) + 127 - 4 * pj;
-#pragma unroll
-            for (int f = 0; f < 4; ++f)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { xa[f][k] = row[64 * f + k]; xb[f][k] = rowb[64 * f - k]; }
-        }
-        const int tl = wave >> 1, ct = wave & 1;      // GEMM role: bins 16 tl + 4 q + r (and 128 - them), frame 2 pair + ct, clip i
-        float x0p[2];
-#pragma unroll
-        for (int pr = 0; pr < 2; ++pr) x0p[pr] = X[i * X_LDM + 64 * (2 * pr + ct)];        // n = 0 belongs to the even class
-        float b64re = 0.f, b64im = 0.f;               // bin 64 (its own mirror) on the VALU: wave = (frame wave & 3, half of n = 1..128)
-        {
-            const int f = wave & 3, h = wave >> 2, n0 = h * 64 + q * 16;
-            const float *xr = X + i * X_LDM + 64 * f;
-            f32x4 cre = ldg4(P + OFF_B64 + n0), cim = ldg4(P + OFF_B64 + 128 + n0);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int un = u + 1 < 4 ? u + 1 : u;
-                const f32x4 nre = ldg4(P + OFF_B64 + n0 + 4 * un), nim = ldg4(P + OFF_B64 + 128 + n0 + 4 * un);
-#pragma unroll
-                for (int k3 = 0; k3 < 4; ++k3) {
-                    const int n = n0 + 4 * u + k3 + 1;                                // 1..128, mirror 256 - n
-                    const float a = xr[(n & 1) * X_ODD + (n >> 1)], b = xr[(n & 1) * X_ODD + ((256 - n) >> 1)];
-                    b64re = fmaf(a + b, cre[k3], b64re);
-                    b64im = fmaf(a - b, cim[k3], b64im);
-                }
-                cre = nre;
-                cim = nim;
-            }
-            b64re += __shfl_xor(b64re, 16); b64re += __shfl_xor(b64re, 32);
-            b64im += __shfl_xor(b64im, 16); b64im += __shfl_xor(b64im, 32);
-            if (h == 0) {                                                             // the n = 0 tap
-                const float x0 = xr[0];
-                b64re = fmaf(x0, P[OFF_B64 + 256], b64re);
-                b64im = fmaf(x0, P[OFF_B64 + 257], b64im);
-            }
-        }
-        const f32x4 c0 = ldg4(P + OFF_S0 + tl * 16 + 4 * q), s0 = ldg4(P + OFF_S0 + 64 + tl * 16 + 4 * q);
-        __syncthreads();          // every sample is in registers: the pair planes may overwrite X
-        SP_MARK(1);
-        f32x4 mk[2], mn[2];
-#pragma unroll
-        for (int pr = 0; pr < 2; ++pr) {
-            // ---- this thread's e / o values of the pair's two frames -> planes
-#pragma unroll
-            for (int fl = 0; fl < 2; ++fl) {
-                f32x4 ev, ov;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { ev[k] = xa[2 * pr + fl][k] + xb[2 * pr + fl][k]; ov[k] = xa[2 * pr + fl][k] - xb[2 * pr + fl][k]; }
-                unsigned char *d = smem + ((2 * cls) * 3 * 8 + (pj >> 1)) * 512 + (16 * fl + pc) * 16 + 8 * (pj & 1);
-                u32x2 p0, p1, p2;
-                split3x4(ev, p0, p1, p2);
-                *reinterpret_cast<u32x2 *>(d) = p0;
-                *reinterpret_cast<u32x2 *>(d + 8 * 512) = p1;
-                *reinterpret_cast<u32x2 *>(d + 16 * 512) = p2;
-                split3x4(ov, p0, p1, p2);
-                *reinterpret_cast<u32x2 *>(d + 24 * 512) = p0;
-                *reinterpret_cast<u32x2 *>(d + 32 * 512) = p1;
-                *reinterpret_cast<u32x2 *>(d + 40 * 512) = p2;
-            }
-            __syncthreads();
-            // ---- the pair's GEMM: (class, part) = (E re, E im, O re, O im) x two k-steps
-            f32x4 hi[4], lo[4];
-            hi[0] = c0 * x0p[pr];
-            hi[1] = s0 * x0p[pr];
-            hi[2] = f32x4{0.f, 0.f, 0.f, 0.f};
-            hi[3] = hi[2];
-#pragma unroll
-            for (int a4 = 0; a4 < 4; ++a4) lo[a4] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (!SP_SKIP(4)) {
-                const float *wq = P + OFF_QSF + (size_t)tl * (2 * 2 * 2 * 3 * QF);
-                bf16x8 a[2][3];
-                load_a3(a[0], SP_W(wq), lane);
-#pragma unroll
-                for (int s8 = 0; s8 < 8; ++s8) {          // s8 = (class, part, chunk): the fragment order of OFF_QSF
-                    if (s8 + 1 < 8) load_a3(a[(s8 + 1) & 1], SP_W(wq + (s8 + 1) * 3 * QF), lane);
-                    bf16x8 b[3];
-                    const unsigned char *bp = smem + ((s8 >> 1) * 3 * 8 + 4 * (s8 & 1) + q) * 512 + (16 * ct + i) * 16;
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) b[pl] = *reinterpret_cast<const bf16x8 *>(bp + pl * 8 * 512);
-                    mfma_split6(a[s8 & 1], b, hi[s8 >> 1], lo[s8 >> 1]);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float ere = hi[0][r] + lo[0][r], eim = hi[1][r] + lo[1][r], ore = hi[2][r] + lo[2][r], oim = hi[3][r] + lo[3][r];
-                const float pre = ere + ore, pim = eim + oim, nre = ere - ore, nim = eim - oim;
-                mk[pr][r] = mag_sqrt(pre * pre + pim * pim);
-                mn[pr][r] = mag_sqrt(nre * nre + nim * nim);
-            }
-            __syncthreads();      // every wave is done reading the pair's planes
-        }
-        SP_MARK(1);
-        const int g = 4 * tl + q;
-#pragma unroll
-        for (int pr = 0; pr < 2; ++pr) {
-            const int f = 2 * pr + ct;
-            unsigned char *fr = smem + f * SP_FR128;
-            store_split4(fr, SP_PL128, g, i, mk[pr]);                 // slots 4 g + r        = bins 4 g + r
-            store_split4(fr, SP_PL128, 16 + g, i, mn[pr]);            // slots 64 + 4 g + r   = bins 128 - (4 g + r); g = 0, r = 0 is bin 128:
-            if (g == 0) nyq[f * 16 + i] = mn[pr][0];                  //   it goes to the scratch, and slot 64 is rewritten below with bin 64
-        }
-        if (q == 0) { scr[wave * 32 + i] = b64re; scr[wave * 32 + 16 + i] = b64im; }
-        __syncthreads();
-        SP_MARK(2);
-        if (tid < 64) {                                               // bin 64: frame tid / 16, clip tid % 16
-            const int f = tid >> 4, c = tid & 15;
-            const float re = scr[f * 32 + c] + scr[(f + 4) * 32 + c], im = scr[f * 32 + 16 + c] + scr[(f + 4) * 32 + 16 + c];
-            store_split1(smem + f * SP_FR128, SP_PL128, 64, c, mag_sqrt(re * re + im * im));
-        }
-    } else if (fold) {
+    // (measured, built then removed: the folded STFT itself on split products -- 96 bf16 instead of 128 f32 MFMAs per wave and tile, but 384 KB
+    //  of table fragments per tile instead of 128 KB -- measured equal to this f32-MFMA fold, 5.60 vs 5.62 ms per launch)
+    if (fold) {
         const int tl = wave & 3, fp = wave >> 2;      // wave = (bin tile tl, frame pair fp): bins k = 16 tl + 4 q + r and 128 - k
         float b64re = 0.f, b64im = 0.f;               // bin 64 (its own mirror) on the VALU: wave = (frame wave & 3, half of n = 1..128)
         {
@@ -382,7 +229,7 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
             ore[f] = f32x4{0.f, 0.f, 0.f, 0.f};
             oim[f] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        if (!SP_SKIP(4)) {
+        {
             const float *row = X + i * X_LDM + 128 * fp;
             const float *wt = P + OFF_SF + tl * 16 * FRAG + lane * 4;                 // [E|O][re|im][4 blocks]
             stft_fold_class<true>(ere, eim, row + 1 + q, row + 127 - q, wt, wt + 4 * FRAG);
@@ -399,7 +246,6 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
                 mn[f][r] = mag_sqrt(nr * nr + ni * ni);
             }
         __syncthreads();          // every wave is done reading X: the planes may now overwrite it
-        SP_MARK(1);
         const int g = 4 * tl + q;
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
@@ -410,7 +256,6 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
         }
         if (q == 0) { scr[wave * 32 + i] = b64re; scr[wave * 32 + 16 + i] = b64im; }
         __syncthreads();
-        SP_MARK(2);
         if (tid < 64) {                                               // bin 64: frame tid / 16, clip tid % 16
             const int f = tid >> 4, c = tid & 15;
             const float re = scr[f * 32 + c] + scr[(f + 4) * 32 + c], im = scr[f * 32 + 16 + c] + scr[(f + 4) * 32 + 16 + c];
@@ -460,7 +305,6 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
         if (wave < 4 && q == 0) nyq[wave * 16 + i] = nyqv;
     }
     __syncthreads();
-    SP_MARK(3);
 
     // ---------------- phase 2: conv1 129->128, k3 s1 p1, ReLU -- direct: out[f] = sum_tap W[tap] in[f + tap - 1], wave = 16 output channels
     {
@@ -488,7 +332,7 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
         }
         const float *wq = P + OFF_Q1 + rt * (4 * 3 * 3 * QF);
         bf16x8 a[2][3];
-        load_a3(a[0], SP_W(wq), lane);
+        load_a3(a[0], wq, lane);
 #pragma unroll
         for (int kc = 0; kc < 4; ++kc) {
             bf16x8 b[4][3];
@@ -497,20 +341,19 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
 #pragma unroll
             for (int tap = 0; tap < 3; ++tap) {
                 const int s = kc * 3 + tap;
-                if (s + 1 < 12) load_a3(a[(s + 1) & 1], SP_W(wq + (s + 1) * 3 * QF), lane);
+                if (s + 1 < 12) load_a3(a[(s + 1) & 1], wq + (s + 1) * 3 * QF, lane);
                 const bf16x8 (&ac)[3] = a[s & 1];
                 // six products per (frame, tap), frames innermost so that consecutive MFMAs hit different accumulators
 #define SP_TERM(AP, BP, ACC)                                                                  \
     _Pragma("unroll") for (int f = 0; f < 4; ++f) {                                           \
         const int fi = f + tap - 1;                                                           \
-        if (fi >= 0 && fi < 4 && !SP_SKIP(5)) ACC[f] = mfma_bf16(ac[AP], b[fi][BP], ACC[f]);  \
+        if (fi >= 0 && fi < 4) ACC[f] = mfma_bf16(ac[AP], b[fi][BP], ACC[f]);                 \
     }
                 SP_TERM(2, 0, lo) SP_TERM(1, 1, lo) SP_TERM(0, 2, lo) SP_TERM(1, 0, lo) SP_TERM(0, 1, lo) SP_TERM(0, 0, hi)
 #undef SP_TERM
             }
         }
         __syncthreads();          // every wave is done reading the |X| planes: conv1's output may now overwrite them
-        SP_MARK(4);
 #pragma unroll
         for (int f = 0; f < 4; ++f) {
             f32x4 y;
@@ -520,7 +363,6 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
         }
     }
     __syncthreads();
-    SP_MARK(5);
 
     // ---------------- phase 3: conv2 128->64, k3 s2 p1, ReLU: out frame o reads in frames 2 o - 1 .. 2 o + 1; wave = (16 channels, half of K)
     {
@@ -530,8 +372,8 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
         for (int o = 0; o < 2; ++o) { hi[o] = f32x4{0.f, 0.f, 0.f, 0.f}; lo[o] = hi[o]; }
         const float *wq = P + OFF_Q2 + (rt * 4 + 2 * kh) * (3 * 3 * QF);
         bf16x8 a[3][3];                    // (a step is 6 - 12 MFMAs: the fragment stream runs two steps ahead, see phase 6)
-        load_a3(a[0], SP_W(wq), lane);
-        load_a3(a[1], SP_W(wq + 3 * QF), lane);
+        load_a3(a[0], wq, lane);
+        load_a3(a[1], wq + 3 * QF, lane);
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             bf16x8 b[4][3];
@@ -540,12 +382,12 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
 #pragma unroll
             for (int tap = 0; tap < 3; ++tap) {
                 const int s = kk * 3 + tap;
-                if (s + 2 < 6) load_a3(a[(s + 2) % 3], SP_W(wq + (s + 2) * 3 * QF), lane);
+                if (s + 2 < 6) load_a3(a[(s + 2) % 3], wq + (s + 2) * 3 * QF, lane);
                 const bf16x8 (&ac)[3] = a[s % 3];
 #define SP_TERM(AP, BP, ACC)                                                                  \
     _Pragma("unroll") for (int o = 0; o < 2; ++o) {                                           \
         const int fi = 2 * o + tap - 1;                                                       \
-        if (fi >= 0 && !SP_SKIP(3)) ACC[o] = mfma_bf16(ac[AP], b[fi][BP], ACC[o]);            \
+        if (fi >= 0) ACC[o] = mfma_bf16(ac[AP], b[fi][BP], ACC[o]);                           \
     }
                 SP_TERM(2, 0, lo) SP_TERM(1, 1, lo) SP_TERM(0, 2, lo) SP_TERM(1, 0, lo) SP_TERM(0, 1, lo) SP_TERM(0, 0, hi)
 #undef SP_TERM
@@ -576,7 +418,6 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
         }
     }
     __syncthreads();
-    SP_MARK(6);
 
     // ---------------- phase 4: conv3 64->64, k3 s2 p1, ReLU (one output frame; tap 0 reads padding): wave = (16 channels, tap 1 | 2)
     {
@@ -584,12 +425,12 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
         f32x4 hi = {0.f, 0.f, 0.f, 0.f}, lo = hi;
         const float *wq = P + OFF_Q3 + (rt * 2 + th) * (2 * 3 * QF);
         bf16x8 a[2][3], b[2][3];
-        load_a3(a[0], SP_W(wq), lane);
-        load_a3(a[1], SP_W(wq + 3 * QF), lane);
+        load_a3(a[0], wq, lane);
+        load_a3(a[1], wq + 3 * QF, lane);
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) load_b3(b[kc], smem + SP_R1 + th * SP_FR2, SP_PL2, kc, q, i);
 #pragma unroll
-        for (int kc = 0; kc < 2; ++kc) if (!SP_SKIP(3)) mfma_split6(a[kc], b[kc], hi, lo);
+        for (int kc = 0; kc < 2; ++kc) mfma_split6(a[kc], b[kc], hi, lo);
         f32x4 s3 = hi + lo;
         float *exc = reinterpret_cast<float *>(smem + SP_EXC3);
         if (th == 1) *reinterpret_cast<f32x4 *>(exc + (rt * 64 + lane) * 4) = s3;
@@ -604,7 +445,6 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
         }
     }
     __syncthreads();
-    SP_MARK(7);
 
     // ---------------- phase 5: conv4 64->128, k3 s1 p1, ReLU (one frame in / out: centre tap only)
     {
@@ -612,19 +452,18 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
         f32x4 hi = ldg4(P + OFF_B4 + 16 * rt + 4 * q), lo = {0.f, 0.f, 0.f, 0.f};
         const float *wq = P + OFF_Q4 + rt * (2 * 3 * QF);
         bf16x8 a[2][3], b[2][3];
-        load_a3(a[0], SP_W(wq), lane);
-        load_a3(a[1], SP_W(wq + 3 * QF), lane);
+        load_a3(a[0], wq, lane);
+        load_a3(a[1], wq + 3 * QF, lane);
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) load_b3(b[kc], smem + SP_C3, SP_PL3, kc, q, i);
 #pragma unroll
-        for (int kc = 0; kc < 2; ++kc) if (!SP_SKIP(3)) mfma_split6(a[kc], b[kc], hi, lo);
+        for (int kc = 0; kc < 2; ++kc) mfma_split6(a[kc], b[kc], hi, lo);
         f32x4 y;
 #pragma unroll
         for (int r = 0; r < 4; ++r) y[r] = fmaxf(hi[r] + lo[r], 0.f);
         store_split4(smem + (sub + 1 < NSUB ? SP_STASH : SP_C4), SP_PL4, 4 * rt + q, i, y);      // the last tile's planes stay in R0
     }
     __syncthreads();
-    SP_MARK(8);
     }      // sub
 
     asm volatile("" : "+v"(tid0));
@@ -647,7 +486,7 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
         constexpr int AHEAD = 3;
         bf16x8 a[AHEAD + 1][3];
 #pragma unroll
-        for (int s0 = 0; s0 < AHEAD; ++s0) load_a3(a[s0], SP_W(wq + (SP_SKIP(11) ? 0 : s0) * 3 * QF), lane);
+        for (int s0 = 0; s0 < AHEAD; ++s0) load_a3(a[s0], wq + s0 * 3 * QF, lane);
 #pragma unroll
         for (int kc = 0; kc < 4; ++kc) {
             bf16x8 b[NSUB][3];
@@ -656,13 +495,11 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int s = kc * 4 + g;
-                if (s + AHEAD < 16 && !SP_SKIP(11)) load_a3(a[(s + AHEAD) % (AHEAD + 1)], SP_W(wq + (s + AHEAD) * 3 * QF), lane);
+                if (s + AHEAD < 16) load_a3(a[(s + AHEAD) % (AHEAD + 1)], wq + (s + AHEAD) * 3 * QF, lane);
                 const bf16x8 (&ac)[3] = a[s % (AHEAD + 1)];
-                if (!SP_SKIP(6) && !SP_SKIP(11)) {
 #define SP_TERM(AP, BP, ACC) _Pragma("unroll") for (int sb = 0; sb < NSUB; ++sb) ACC[sb][g] = mfma_bf16(ac[AP], b[sb][BP], ACC[sb][g]);
-                    SP_TERM(2, 0, lo) SP_TERM(1, 1, lo) SP_TERM(0, 2, lo) SP_TERM(1, 0, lo) SP_TERM(0, 1, lo) SP_TERM(0, 0, hi)
+                SP_TERM(2, 0, lo) SP_TERM(1, 1, lo) SP_TERM(0, 2, lo) SP_TERM(1, 0, lo) SP_TERM(0, 1, lo) SP_TERM(0, 0, hi)
 #undef SP_TERM
-                }
             }
         }
 #pragma unroll
@@ -675,8 +512,6 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
                 for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x4 *>(dst + g * 256) = hi[sb][g] + lo[sb][g];
         }
     }
-    SP_MARK(9);
-    SP_CLK();
 }
 
 // ---- persistent LSTM on split products ---------------------------------------------------------
@@ -809,22 +644,18 @@ int silero_lstm_split_launch(const float *packed, const float *gx, const float *
     return VADX_OK;
 }
 
-// VADX_SPLIT_HALVES: 1 = 512-thread workgroups (two independent ones per CU); 2 = the lockstep pair.  Measured on one box, B = 4096 x 10 s
+// SP_HALVES: 1 = 512-thread workgroups (two independent ones per CU); 2 = the lockstep pair.  Measured on one box, B = 4096 x 10 s
 // (one tile per workgroup half): 5.75 ms against 6.35 ms -- the L1 hits of the pair do not pay for what the lockstep costs: two
 // independent workgroups sit in DIFFERENT phases most of the time (one in its f32 STFT or its staging while the other streams
 // weights), the pair never does.
-// VADX_SPLIT_NSUB: tiles a workgroup encodes one after the other before ONE joint W_ih phase (2: every W_ih fragment serves 32 columns,
+// SP_NSUB: tiles a workgroup encodes one after the other before ONE joint W_ih phase (2: every W_ih fragment serves 32 columns,
 // at the price of the first tile's conv4 planes in a 12 KB stash and one more barrier in conv2).
-#ifndef VADX_SPLIT_HALVES
-#define VADX_SPLIT_HALVES 1
-#endif
-#ifndef VADX_SPLIT_NSUB
-#define VADX_SPLIT_NSUB 1       // 2 measured no faster on the same box (5.61 against 5.59 ms): the W_ih phase waits on fragment LATENCY, not on L2 bandwidth
-#endif
+constexpr int SP_HALVES = 1;
+constexpr int SP_NSUB = 1;       // 2 measured no faster on the same box (5.61 against 5.59 ms): the W_ih phase waits on fragment LATENCY, not on L2 bandwidth
 template <typename S>
 int silero_encode_split_launch(const float *packed, const S *src, float in_scale, long long n_valid, long long row_stride,
                                long long origin, int batch, int G, int steps, int Gws, int first_group, float *gx, void *stream) {
-    constexpr int HV = VADX_SPLIT_HALVES, NS = VADX_SPLIT_NSUB;
+    constexpr int HV = SP_HALVES, NS = SP_NSUB;
     VADX_DYN_LDS((silero_encode_split_kernel<S, HV, NS>), SP_LDS_BYTES * HV);
     const long long nblk = ((long long)G * steps + HV * NS - 1) / (HV * NS);
     hipLaunchKernelGGL((silero_encode_split_kernel<S, HV, NS>), dim3((unsigned)nblk), dim3(SP_THREADS * HV), SP_LDS_BYTES * HV, static_cast<hipStream_t>(stream),
