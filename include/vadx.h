@@ -43,8 +43,10 @@ extern "C" {
  *    stays F16X2, and (b) a Silero workgroup whose activations left the fp16 range writes NaN instead of its gate pre-activations, so that the
  *    scores of those clips are NaN for a caller that never reads vadx_silero_range_flag (tests/c/cabi_silero.c reads it).  (c) The pack_host
  *    functions rebalance chains of affine layers by exact powers of two when a weight tensor sits outside [2^-10, 2^7) (csrc/rebalance.h) and
- *    refuse F16X2 for a blob that keeps a weight tensor wholly below 2^-14. */
-#define VADX_ABI_VERSION 7
+ *    refuse F16X2 for a blob that keeps a weight tensor wholly below 2^-14.
+ * 8: new entry points only, no existing signature or behaviour changed: the Silero stream path vadx_silero_iter_params,
+ *    vadx_silero_stream_state_bytes, vadx_silero_stream_workspace_bytes, vadx_silero_stream_run. */
+#define VADX_ABI_VERSION 8
 
 /* Arithmetic of the products whose one operand is a constant (every weight matrix, every DFT table) -- float32 RESULTS in all of them:
  *   F32     v_mfma_f32_16x16x4_f32 on the float32 operands themselves;
@@ -182,6 +184,40 @@ int vadx_silero_segments(const float *probs, int batch, int steps, const int64_t
  * The underflow side needs no protocol: pack_host rebalances layers whose weights sit outside [2^-10, 2^7) by exact powers of two
  * (csrc/rebalance.h) and marks a blob with a weight tensor wholly below 2^-14 as unusable for this arithmetic (flag bit 1 on a launch). */
 int vadx_silero_range_flag(const float *packed, int reset, uint32_t *flag_host, float *amax_host, void *stream);
+
+/* Streaming Silero: S live streams advance by `windows` 512-sample windows per call, each stream's context, LSTM state and VADIterator
+ * machine kept in a device RECORD (vadx_silero_stream_state_bytes(S) bytes).  The record is opaque except that
+ *   - its first 2*S*128 floats are the LSTM state [2][S][128] (h, then c), laid out as state_n of every other Silero call;
+ *   - a record of all zero bytes is S streams in their reset state (no init call).
+ * samples: [S][row_stride], windows*512 valid per row; f32 on the +-1 scale (samples_int16 = 0), or int16 PCM (samples_int16 != 0) scaled
+ * by `scale` in one f32 rounding as vadx_silero_encode_pcm16 does.  reset (NULL or uint8 [S]): != 0 = reset_states() before this tick.
+ * active (NULL or uint8 [S]): 0 = no audio for this stream this tick -- its state_out record is a bitwise copy of state_in (a reset
+ * request on an inactive stream is ignored), its events are 0 and its probs NaN.  state_in is never written (a tick can be recomputed
+ * from it, which the range protocol needs); state_in and state_out must not overlap.  Per window: probs f32, event_kind int8 (0 none,
+ * 1 start, 2 end, -1 the window's score is not finite) and event_value f64 [S][windows], the value VADIterator computes BEFORE int()
+ * (the host applies int(v) or round(v / sampling_rate, time_resolution), utils_vad.py:571-584).  A NaN score poisons the stream's
+ * LSTM state in state_out, so its later windows stay -1 until it is reset: with F16X2 and no range-flag read, a flagged stream reads
+ * "invalid", never a plausible silence.  One arithmetic per call for the encoder and the recurrence (AUTO = F16X2: read
+ * vadx_silero_range_flag after the call and, when it is raised, recompute the tick on BF16X3 from the same state_in into the same
+ * state_out).  Scores are bit for bit those of vadx_silero_clips over the concatenated audio, and so is the LSTM state.  windows <= 65536;
+ * records and workspace (vadx_silero_stream_workspace_bytes) 16-byte aligned.
+ * Replaces VADIterator.__init__ / reset_states / __call__, Silero/modeling_modified/utils_vad.py:494-586, one object per stream
+ * (each call an OnnxWrapper call, utils_vad.py:93-128). */
+typedef struct vadx_silero_iter_params {   /* VADIterator.__init__, utils_vad.py:494-533 */
+    double  threshold;                     /* 0.5 */
+    int32_t sampling_rate;                 /* must be 16000 (the 8 kHz network is not built) */
+    double  min_silence_duration_ms;       /* 100 */
+    double  speech_pad_ms;                 /* 30 */
+} vadx_silero_iter_params;
+
+size_t vadx_silero_stream_state_bytes(int streams);
+size_t vadx_silero_stream_workspace_bytes(int streams, int windows);
+int vadx_silero_stream_run(const float *packed, const vadx_silero_iter_params *prm,
+                           const void *samples, int samples_int16, float scale, int64_t row_stride,
+                           int streams, int windows, const uint8_t *reset, const uint8_t *active,
+                           const void *state_in, void *state_out,
+                           float *probs, int8_t *event_kind, double *event_value,
+                           void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused signal front-end: int16 PCM -> prep -> framed windowed DFT against the

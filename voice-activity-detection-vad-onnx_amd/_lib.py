@@ -63,6 +63,12 @@ class SileroSegParams(C.Structure):
                 ("min_silence_at_max_speech", C.c_double), ("use_max_poss_sil_at_max_speech", C.c_int)]
 
 
+class SileroIterParams(C.Structure):
+    """vadx_silero_iter_params (include/vadx.h): VADIterator's constructor arguments for the stream path"""
+    _fields_ = [("threshold", C.c_double), ("sampling_rate", C.c_int32), ("min_silence_duration_ms", C.c_double),
+                ("speech_pad_ms", C.c_double)]
+
+
 class FrontendCfg(C.Structure):
     _fields_ = [("prep", C.c_int), ("k0", C.c_float), ("k1", C.c_float), ("center_pad", C.c_int),
                 ("tap0", C.c_int), ("taps", C.c_int), ("hop", C.c_int), ("n_bins", C.c_int),
@@ -155,6 +161,10 @@ SIGNATURES = {
     "vadx_silero_recur_span": (_I, [_P, _P, _Z, _I, _I, _P, _P, _L, _P, _P, _P]),
     "vadx_silero_segments": (_I, [_P, _I, _I, _P, C.POINTER(SileroSegParams), _P, _P, _I, _P]),
     "vadx_silero_range_flag": (_I, [_P, _I, _P, _P, _P]),
+    "vadx_silero_stream_state_bytes": (_Z, [_I]),
+    "vadx_silero_stream_workspace_bytes": (_Z, [_I, _I]),
+    "vadx_silero_stream_run": (_I, [_P, C.POINTER(SileroIterParams), _P, _I, C.c_float, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P,
+                                    _P, _Z, _P, _P]),
     "vadx_frontend_packed_floats": (_Z, [C.POINTER(FrontendCfg)]),
     "vadx_frontend_pack_host": (_I, [C.POINTER(FrontendCfg), _P, _P, _I, _P, _P, _P]),
     "vadx_frontend_fold_kind": (_I, [C.POINTER(FrontendCfg), _P, _P, _I]),

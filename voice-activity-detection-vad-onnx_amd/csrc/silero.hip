@@ -1047,9 +1047,9 @@ extern "C" size_t vadx_silero_workspace_bytes(int batch, int steps) {
 }
 
 template <typename S>
-static int silero_encode_launch(const float *packed, const S *src, float in_scale, long long n_valid, long long row_stride,
-                                long long origin, int batch, int steps, void *ws, size_t ws_bytes, void *stream,
-                                const vadx_silero_cfg *cfg, int first_group = 0, int total_batch = 0) {
+int vadx::silero::silero_encode_launch(const float *packed, const S *src, float in_scale, long long n_valid, long long row_stride,
+                                       long long origin, int batch, int steps, void *ws, size_t ws_bytes, void *stream,
+                                       const vadx_silero_cfg *cfg, int first_group, int total_batch) {
     VADX_SILERO_ARITH(cfg, "silero");
     VADX_REQUIRE(packed && src && ws, "silero: NULL pointer argument");
     VADX_REQUIRE(batch > 0 && steps > 0, "silero: batch=%d steps=%d must be positive", batch, steps);
@@ -1080,9 +1080,9 @@ static int silero_encode_launch(const float *packed, const S *src, float in_scal
     return VADX_OK;
 }
 
-static int silero_recur_launch(const float *packed, const void *ws, size_t ws_bytes, int batch, int steps,
-                               const float *state0, float *probs, long long probs_stride, float *state_n, void *stream,
-                               const vadx_silero_cfg *cfg) {
+int vadx::silero::silero_recur_launch(const float *packed, const void *ws, size_t ws_bytes, int batch, int steps,
+                                      const float *state0, float *probs, long long probs_stride, float *state_n, void *stream,
+                                      const vadx_silero_cfg *cfg) {
     VADX_SILERO_ARITH(cfg, "silero");
     VADX_REQUIRE(packed && ws && probs, "silero: NULL pointer argument");
     VADX_REQUIRE(batch > 0 && steps > 0, "silero: batch=%d steps=%d must be positive", batch, steps);
@@ -1101,6 +1101,11 @@ static int silero_recur_launch(const float *packed, const void *ws, size_t ws_by
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
+
+template int vadx::silero::silero_encode_launch<float>(const float *, const float *, float, long long, long long, long long, int, int,
+                                                       void *, size_t, void *, const vadx_silero_cfg *, int, int);
+template int vadx::silero::silero_encode_launch<int16_t>(const float *, const int16_t *, float, long long, long long, long long, int, int,
+                                                         void *, size_t, void *, const vadx_silero_cfg *, int, int);
 
 static int silero_run(const float *packed, const float *src, long long n_valid, long long row_stride,
                       long long origin, int batch, int steps, const float *state0, float *probs,

@@ -191,6 +191,16 @@ int silero_encode_h2_launch(const float *packed, const S *src, float in_scale, l
 int silero_lstm_h2_launch(const float *packed, const float *gx, const float *state0, int batch, int G, int steps, float *probs,
                           long long probs_stride, float *state_n, void *stream);
 
+// csrc/silero.hip: the encoder and recurrent launches behind every Silero entry point (the kernel set comes from cfg), also called by the
+// stream path (csrc/silero_stream.hip)
+template <typename S>
+int silero_encode_launch(const float *packed, const S *src, float in_scale, long long n_valid, long long row_stride,
+                         long long origin, int batch, int steps, void *ws, size_t ws_bytes, void *stream,
+                         const vadx_silero_cfg *cfg, int first_group = 0, int total_batch = 0);
+int silero_recur_launch(const float *packed, const void *ws, size_t ws_bytes, int batch, int steps,
+                        const float *state0, float *probs, long long probs_stride, float *state_n, void *stream,
+                        const vadx_silero_cfg *cfg);
+
 int silero_lstm_split_launch(const float *packed, const float *gx, const float *state0, int batch, int G, int steps, float *probs,
                              long long probs_stride, float *state_n, void *stream);
 

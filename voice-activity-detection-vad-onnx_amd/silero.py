@@ -4,8 +4,9 @@ Mirrors (same names / arguments / error behaviour):
   * `OnnxWrapper`            -- Silero/modeling_modified/utils_vad.py:10-146
   * `load_silero_vad`        -- Silero/modeling_modified/model.py:9-41
   * `get_speech_timestamps`  -- Silero/modeling_modified/utils_vad.py:248-491
+  * `VADIterator`            -- Silero/modeling_modified/utils_vad.py:494-586 (host drop-in)
 plus the batched entry points the reference does not have (`SileroEngine.clips`,
-`get_speech_timestamps_batch`).  All arithmetic runs in libvadx.so (HIP, gfx950); this file is
+`get_speech_timestamps_batch`, `VADIteratorBatch`: many live streams on the device).  All arithmetic runs in libvadx.so (HIP, gfx950); this file is
 plumbing: tensors in, C-ABI call, tensors out.  No CPU fallback.
 """
 from __future__ import annotations
@@ -482,6 +483,210 @@ class OnnxWrapper:
         self._state, self._context = state, xp[:, -CONTEXT_SIZE:]
         self._last_sr, self._last_batch_size = sr, x.shape[0]
         return probs.cpu()
+
+
+class _IterMachine:
+    """VADIterator's per-stream state machine (utils_vad.py:535-585) on one window's score; the device runs the same steps in double
+    (csrc/silero_stream.hip: silero_stream_iter_kernel).  step(p, n) -> (kind, value): kind 0 none / 1 start / 2 end, value the sample
+    position the reference computes before int()."""
+
+    def __init__(self, threshold, sampling_rate, min_silence_duration_ms, speech_pad_ms):
+        self.threshold = threshold
+        self.min_silence_samples = sampling_rate * min_silence_duration_ms / 1000
+        self.speech_pad_samples = sampling_rate * speech_pad_ms / 1000
+        self.reset()
+
+    def reset(self):
+        self.triggered, self.temp_end, self.current_sample = False, 0, 0
+
+    def step(self, p, n):
+        self.current_sample += n
+        speech = p >= self.threshold
+        if speech and self.temp_end:
+            self.temp_end = 0
+        if speech:
+            if self.triggered:
+                return 0, None
+            self.triggered = True
+            return 1, max(0, self.current_sample - self.speech_pad_samples - n)
+        if not (p < self.threshold - 0.15 and self.triggered):
+            return 0, None
+        if not self.temp_end:
+            self.temp_end = self.current_sample
+        if self.current_sample - self.temp_end < self.min_silence_samples:
+            return 0, None
+        end = self.temp_end + self.speech_pad_samples - n
+        self.temp_end, self.triggered = 0, False
+        return 2, end
+
+
+def _event(kind, value, sampling_rate, return_seconds, time_resolution):
+    if kind not in (1, 2):
+        return None
+    return {"start" if kind == 1 else "end": round(value / sampling_rate, time_resolution) if return_seconds else int(value)}
+
+
+class VADIterator:
+    """Drop-in for the reference's stream iterator (utils_vad.py:494-586): one stream, one model call per chunk on the host.
+    `model` is anything the reference accepts (vadx.silero.OnnxWrapper, or a stand-in with reset_states() and __call__(x, sr)).
+    Many streams at once: VADIteratorBatch."""
+
+    def __init__(self, model, threshold: float = 0.5, sampling_rate: int = 16000, min_silence_duration_ms: int = 100,
+                 speech_pad_ms: int = 30):
+        self.model = model
+        self.threshold = threshold
+        self.sampling_rate = sampling_rate
+        if sampling_rate not in [8000, 16000]:
+            raise ValueError("VADIterator does not support sampling rates other than [8000, 16000]")
+        self._m = _IterMachine(threshold, sampling_rate, min_silence_duration_ms, speech_pad_ms)
+        self.min_silence_samples = self._m.min_silence_samples
+        self.speech_pad_samples = self._m.speech_pad_samples
+        self.reset_states()
+
+    def reset_states(self):
+        self.model.reset_states()
+        self._m.reset()
+
+    triggered = property(lambda self: self._m.triggered)
+    temp_end = property(lambda self: self._m.temp_end)
+    current_sample = property(lambda self: self._m.current_sample)
+
+    def __call__(self, x, return_seconds=False, time_resolution: int = 1):
+        import torch
+        if not torch.is_tensor(x):
+            try:
+                x = torch.Tensor(x)
+            except Exception:
+                raise TypeError("Audio cannot be casted to tensor. Cast it manually")
+        n = len(x[0]) if x.dim() == 2 else len(x)
+        with torch.no_grad():
+            p = self.model(x, self.sampling_rate).item()
+        kind, value = self._m.step(p, n)
+        return _event(kind, value, self.sampling_rate, return_seconds, time_resolution)
+
+
+class VADIteratorBatch:
+    """`streams` live Silero streams on the device (vadx_silero_stream_run): every call advances each stream by k windows of 512
+    samples; context, LSTM state and VADIterator machine of every stream stay in a device record (two, ping-ponged), and the start /
+    end events come back from the device.  Per stream, the scores are bit for bit what `SileroEngine.clips` gives for the concatenated
+    audio.  On "h2" every tick reads the range flag and, when it is raised, recomputes the tick on "split" from the same record."""
+
+    def __init__(self, model, streams, threshold: float = 0.5, sampling_rate: int = 16000, min_silence_duration_ms: int = 100,
+                 speech_pad_ms: int = 30):
+        self.engine = model.engine if isinstance(model, OnnxWrapper) else model
+        if not isinstance(self.engine, SileroEngine):
+            raise TypeError("VADIteratorBatch needs a vadx.silero.OnnxWrapper or SileroEngine")
+        if sampling_rate not in [8000, 16000]:
+            raise ValueError("VADIterator does not support sampling rates other than [8000, 16000]")
+        if sampling_rate != 16000:
+            raise ValueError(f"sr={sampling_rate}: only the 16 kHz sub-graph of the Silero network is built on the HIP path "
+                             "(the 8 kHz network itself is not implemented)")
+        self.streams = int(streams)
+        if self.streams <= 0:
+            raise ValueError(f"streams={streams} must be positive")
+        self.sampling_rate = sampling_rate
+        p = _lib.SileroIterParams()
+        p.threshold, p.sampling_rate = float(threshold), int(sampling_rate)
+        p.min_silence_duration_ms, p.speech_pad_ms = float(min_silence_duration_ms), float(speech_pad_ms)
+        self._prm = p
+        t = self.engine.torch
+        nb = _lib.lib().vadx_silero_stream_state_bytes(self.streams)
+        self._rec = [t.zeros(nb, dtype=t.uint8, device=self.engine.device) for _ in range(2)]
+        self._cur = 0
+        self._ws = None
+        self._pending = np.zeros(self.streams, dtype=bool)       # reset_states() requests not yet applied to an active tick
+
+    @property
+    def record(self):
+        """The current device record (uint8); its first 2*S*128 floats are the LSTM state [2,S,128]."""
+        return self._rec[self._cur]
+
+    @property
+    def state(self):
+        return self.record[:2 * self.streams * HIDDEN * 4].view(self.engine.torch.float32).view(2, self.streams, HIDDEN)
+
+    def reset_states(self, streams=None):
+        """None = every stream; else stream indices or a bool mask [S].  Applies at the next tick in which the stream is active."""
+        if streams is None:
+            self._pending[:] = True
+            return
+        idx = np.asarray(streams.cpu() if hasattr(streams, "cpu") else streams)
+        if idx.dtype == bool:
+            if idx.shape != (self.streams,):
+                raise ValueError(f"reset mask must have shape ({self.streams},), got {idx.shape}")
+            self._pending |= idx
+        else:
+            self._pending[idx.astype(np.int64).reshape(-1)] = True
+
+    def _samples(self, x):
+        t = self.engine.torch
+        if not t.is_tensor(x):
+            x = t.from_numpy(np.ascontiguousarray(x))
+        if x.dtype != t.int16:
+            if not x.is_floating_point():
+                raise ValueError(f"samples must be float32 or int16, got {x.dtype}")
+            x = x.to(t.float32)
+        if x.dim() != 2 or x.shape[0] != self.streams or x.shape[1] == 0 or x.shape[1] % NUM_SAMPLES:
+            raise ValueError(f"samples must be [{self.streams}, k*{NUM_SAMPLES}], got {tuple(x.shape)}")
+        return x.to(self.engine.device).contiguous()
+
+    def _mask(self, m, name):
+        a = np.asarray(m.cpu() if hasattr(m, "cpu") else m).astype(bool).reshape(-1)
+        if a.shape != (self.streams,):
+            raise ValueError(f"{name} must have shape ({self.streams},), got {a.shape}")
+        return a
+
+    def _dev_u8(self, a):
+        return self.engine.torch.from_numpy(a.astype(np.uint8)).to(self.engine.device)
+
+    def step(self, x, active=None):
+        """x [S, k*512] (float32 on the +-1 scale, or int16 PCM; host or device, numpy or torch) -> device tensors
+        (kind int8 [S,k], value float64 [S,k], probs float32 [S,k]); kind 0 none / 1 start / 2 end / -1 score not finite,
+        value the sample position before int().  active (bool [S], None = all): False = no audio for that stream this tick."""
+        eng, t = self.engine, self.engine.torch
+        x = self._samples(x)
+        S, k = self.streams, x.shape[1] // NUM_SAMPLES
+        act_h = None if active is None else self._mask(active, "active")
+        act_d = None if act_h is None else self._dev_u8(act_h)
+        applied = self._pending if act_h is None else (self._pending & act_h)
+        reset_d = self._dev_u8(applied) if applied.any() else None
+        L = _lib.lib()
+        need = L.vadx_silero_stream_workspace_bytes(S, k)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = t.empty(need, dtype=t.uint8, device=eng.device)
+        kind = t.empty((S, k), dtype=t.int8, device=eng.device)
+        value = t.empty((S, k), dtype=t.float64, device=eng.device)
+        probs = t.empty((S, k), dtype=t.float32, device=eng.device)
+        src, dst = self._rec[self._cur], self._rec[1 - self._cur]
+        pcm = x.dtype == t.int16
+
+        def run(mode):
+            with t.cuda.device(eng.device):
+                _lib.check(L.vadx_silero_stream_run(eng.packed.data_ptr(), C.byref(self._prm), x.data_ptr(), 1 if pcm else 0,
+                                                    eng.PCM16_SCALE, k * NUM_SAMPLES, S, k,
+                                                    None if reset_d is None else reset_d.data_ptr(),
+                                                    None if act_d is None else act_d.data_ptr(), src.data_ptr(), dst.data_ptr(),
+                                                    probs.data_ptr(), kind.data_ptr(), value.data_ptr(), self._ws.data_ptr(),
+                                                    self._ws.numel(), _lib.stream_ptr(), eng.cfg(mode)))
+        eng._guarded(run)
+        self._cur = 1 - self._cur
+        self._pending &= ~applied
+        return kind, value, probs
+
+    def __call__(self, x, active=None, return_seconds=False, time_resolution: int = 1):
+        """Per stream, what k calls of the reference's VADIterator would return: a list of k entries (dict or None); [] for an
+        inactive stream."""
+        kind, value, _ = self.step(x, active)
+        kind, value = kind.cpu().numpy(), value.cpu().numpy()
+        act = np.ones(self.streams, dtype=bool) if active is None else self._mask(active, "active")
+        out = []
+        for s in range(self.streams):
+            if not act[s]:
+                out.append([])
+                continue
+            out.append([_event(int(kd), float(v), self.sampling_rate, return_seconds, time_resolution)
+                        for kd, v in zip(kind[s], value[s])])
+        return out
 
 
 def segments_from_probs(engine, probs, lengths, **kw):
