@@ -45,8 +45,10 @@ extern "C" {
  *    functions rebalance chains of affine layers by exact powers of two when a weight tensor sits outside [2^-10, 2^7) (csrc/rebalance.h) and
  *    refuse F16X2 for a blob that keeps a weight tensor wholly below 2^-14.
  * 8: new entry points only, no existing signature or behaviour changed: the Silero stream path vadx_silero_iter_params,
- *    vadx_silero_stream_state_bytes, vadx_silero_stream_workspace_bytes, vadx_silero_stream_run. */
-#define VADX_ABI_VERSION 8
+ *    vadx_silero_stream_state_bytes, vadx_silero_stream_workspace_bytes, vadx_silero_stream_run.
+ * 9: additive: vadx_silero_cfg's reserved words became `ext` {sample_rate, reserved1, reserved2} (same size; 0 = 16000, as before), 8000 selects the 8 kHz
+ *    network on every Silero launch; vadx_silero_packed_floats_sr, vadx_silero_pack_host_sr pack the 8 kHz blob. */
+#define VADX_ABI_VERSION 9
 
 /* Arithmetic of the products whose one operand is a constant (every weight matrix, every DFT table) -- float32 RESULTS in all of them:
  *   F32     v_mfma_f32_16x16x4_f32 on the float32 operands themselves;
@@ -72,7 +74,9 @@ const char *vadx_last_error(void);
 /* Original-layout float32 weights on the HOST (same tensors as the ONNX initialisers):
  * stft_basis [258][256]; enc_w[i] [c_out][c_in][3], enc_b[i] [c_out] for the four encoder convs
  * (129->128 s1, 128->64 s2, 64->64 s2, 64->128 s1); LSTM cell [512][128] x2 + biases [512] x2 in
- * torch gate order (i,f,g,o); decoder conv [128] + bias [1]. */
+ * torch gate order (i,f,g,o); decoder conv [128] + bias [1].
+ * The 8 kHz network (vadx_silero_pack_host_sr(8000, ...)) has the same tensors except stft_basis [130][128] (65 bins re, then im;
+ * stride 64) and enc_w[0] [128][65][3]. */
 typedef struct vadx_silero_weights_host {
     const float *stft_basis;
     const float *enc_w[4];
@@ -86,7 +90,11 @@ typedef struct vadx_silero_cfg {
     int32_t arithmetic;     /* VADX_ARITH_*: AUTO = F16X2 (run the range protocol: vadx_silero_range_flag below).  The three kernel sets read the same packed blob and write the same workspace, so the
                              * encoder and recurrent launches of one batch may even differ.  Replaces nothing in the reference: onnxruntime has
                              * one CPU kernel set. */
-    int32_t reserved[3];    /* must be zero */
+    struct {                /* ABI 9: formerly int32_t reserved[3] -- same size, and `{arithmetic, {0, 0, 0}}` initialisers still compile */
+        int32_t sample_rate;    /* 0 or 16000 = the 16 kHz network (windows of 512 samples, 64 of context), 8000 = the 8 kHz network (256,
+                                 * 32); anything else is VADX_EINVAL.  `packed` must be the blob packed for this rate */
+        int32_t reserved1, reserved2;    /* must be zero */
+    } ext;
 } vadx_silero_cfg;
 
 /* Number of floats of the packed (kernel-layout) weight blob. */
@@ -94,6 +102,12 @@ size_t vadx_silero_packed_floats(void);
 /* Repack on the host (init time only); the caller uploads `packed_host` to the device once.
  * Replaces: onnxruntime.InferenceSession(path) construction, Silero/modeling_modified/utils_vad.py:39. */
 int vadx_silero_pack_host(const vadx_silero_weights_host *w, float *packed_host);
+/* The same for either network: sample_rate 16000 is vadx_silero_pack_host, 8000 packs the 8 kHz network (its tensors' shapes above) into a
+ * blob of the same size, tagged: an 8 kHz launch on a blob without the tag (a 16 kHz blob) writes NaN gate pre-activations and raises bit 2
+ * (value 4) of vadx_silero_range_flag, it never scores.  A 16 kHz launch must be given a 16 kHz blob -- the caller's contract, as
+ * vadx_fsmn_dims' "pass the same dims": an 8 kHz blob there is not detected.  vadx_silero_packed_floats_sr returns 0 for another rate. */
+size_t vadx_silero_packed_floats_sr(int sample_rate);
+int vadx_silero_pack_host_sr(int sample_rate, const vadx_silero_weights_host *w, float *packed_host);
 
 /* Scratch needed by the two calls below, in bytes. `steps` = windows per clip (1 for vadx_silero_step). */
 size_t vadx_silero_workspace_bytes(int batch, int steps);
@@ -102,13 +116,15 @@ size_t vadx_silero_workspace_bytes(int batch, int steps);
  *   feeds  {'input': f32 [B,576], 'state': f32 [2,B,128], 'sr': int64 scalar}
  *   fetches(out f32 [B,1], stateN f32 [2,B,128])
  * Replaces: self.session.run(None, ort_inputs), Silero/modeling_modified/utils_vad.py:116-119.
- * sr must be 16000 (the reference wrapper's '16k' model path, utils_vad.py:62-64). */
+ * sr must equal the cfg's sample_rate (16000 by default; the reference model's sr input, utils_vad.py:62-67); at 8000 the input is [B,288]
+ * (32 context + 256 samples). */
 int vadx_silero_step(const float *packed, const float *input, const float *state, int64_t sr,
                      int batch, float *out, float *state_n,
                      void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg);
 
 /* Whole clips, batched: audio f32 [B][row_stride] (first n_samples valid per row, +-1 scale),
- * zero state and zero context at t=0, last window zero-padded; probs f32 [B][T], T = ceil(n/512).
+ * zero state and zero context at t=0, last window zero-padded; probs f32 [B][T], T = ceil(n/512) (ceil(n/256) at 8 kHz: every launch
+ * below takes the window of the cfg's sample_rate).
  * state_n (optional, may be NULL) receives the final [2,B,128].
  * Replaces the window loop of get_speech_timestamps, utils_vad.py:350,359-372, and
  * OnnxWrapper.audio_forward, utils_vad.py:130-146 (context carry :111-114,:123 is done in-kernel). */
@@ -118,7 +134,7 @@ int vadx_silero_clips(const float *packed, const float *audio, int batch, int64_
 
 /* The two halves of vadx_silero_clips as separate launches (same buffers, same results), so a
  * harness can time the state-independent encoder (STFT conv + conv stack + W_ih, the dominant
- * kernel) and the recurrent kernel separately.  `steps` = ceil(n_samples/512). */
+ * kernel) and the recurrent kernel separately.  `steps` = ceil(n_samples/512) (/256 at 8 kHz). */
 int vadx_silero_encode(const float *packed, const float *audio, int batch, int64_t n_samples,
                        int64_t row_stride, void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg);
 /* The same encoder fed int16 PCM: sample = (float)pcm * scale in one f32 rounding -- with scale = 0.000030517578f exactly the
@@ -185,11 +201,11 @@ int vadx_silero_segments(const float *probs, int batch, int steps, const int64_t
  * (csrc/rebalance.h) and marks a blob with a weight tensor wholly below 2^-14 as unusable for this arithmetic (flag bit 1 on a launch). */
 int vadx_silero_range_flag(const float *packed, int reset, uint32_t *flag_host, float *amax_host, void *stream);
 
-/* Streaming Silero: S live streams advance by `windows` 512-sample windows per call, each stream's context, LSTM state and VADIterator
+/* Streaming Silero: S live streams advance by `windows` 512-sample windows per call (256 at 8 kHz), each stream's context, LSTM state and VADIterator
  * machine kept in a device RECORD (vadx_silero_stream_state_bytes(S) bytes).  The record is opaque except that
  *   - its first 2*S*128 floats are the LSTM state [2][S][128] (h, then c), laid out as state_n of every other Silero call;
  *   - a record of all zero bytes is S streams in their reset state (no init call).
- * samples: [S][row_stride], windows*512 valid per row; f32 on the +-1 scale (samples_int16 = 0), or int16 PCM (samples_int16 != 0) scaled
+ * samples: [S][row_stride], windows*512 (windows*256) valid per row; f32 on the +-1 scale (samples_int16 = 0), or int16 PCM (samples_int16 != 0) scaled
  * by `scale` in one f32 rounding as vadx_silero_encode_pcm16 does.  reset (NULL or uint8 [S]): != 0 = reset_states() before this tick.
  * active (NULL or uint8 [S]): 0 = no audio for this stream this tick -- its state_out record is a bitwise copy of state_in (a reset
  * request on an inactive stream is ignored), its events are 0 and its probs NaN.  state_in is never written (a tick can be recomputed
@@ -205,7 +221,7 @@ int vadx_silero_range_flag(const float *packed, int reset, uint32_t *flag_host, 
  * (each call an OnnxWrapper call, utils_vad.py:93-128). */
 typedef struct vadx_silero_iter_params {   /* VADIterator.__init__, utils_vad.py:494-533 */
     double  threshold;                     /* 0.5 */
-    int32_t sampling_rate;                 /* must be 16000 (the 8 kHz network is not built) */
+    int32_t sampling_rate;                 /* must equal the cfg's sample_rate (16000 by default; 8000 with the 8 kHz blob and cfg) */
     double  min_silence_duration_ms;       /* 100 */
     double  speech_pad_ms;                 /* 30 */
 } vadx_silero_iter_params;

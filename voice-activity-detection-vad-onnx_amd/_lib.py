@@ -50,7 +50,7 @@ class MarbleNetCfg(C.Structure):
 
 class SileroCfg(C.Structure):
     """vadx_silero_cfg (include/vadx.h): per-call configuration of the Silero launches"""
-    _fields_ = [("arithmetic", C.c_int32), ("reserved", C.c_int32 * 3)]
+    _fields_ = [("arithmetic", C.c_int32), ("sample_rate", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 ARITH = {"auto": 0, "f32": 1, "split": 2, "bf16x3": 2, "h2": 3, "f16x2": 3}       # VADX_ARITH_*
@@ -149,6 +149,8 @@ SIGNATURES = {
     "vadx_last_error": (C.c_char_p, []),
     "vadx_silero_packed_floats": (_Z, []),
     "vadx_silero_pack_host": (_I, [C.POINTER(SileroWeightsHost), _P]),
+    "vadx_silero_packed_floats_sr": (_Z, [_I]),
+    "vadx_silero_pack_host_sr": (_I, [_I, C.POINTER(SileroWeightsHost), _P]),
     "vadx_silero_workspace_bytes": (_Z, [_I, _I]),
     # (every Silero launch ends with (stream, const vadx_silero_cfg *); None = the library's defaults)
     "vadx_silero_step": (_I, [_P, _P, _P, _L, _I, _P, _P, _P, _Z, _P, _P]),

@@ -368,21 +368,72 @@ def silero_from_onnx(path_or_bytes, sample_rate=16000):
     W [1,4H,I] / R [1,4H,H] / B [1,8H] in i-o-f-c gate order, or as plain [4H,I] / [4H,H] matrices named weight_ih / weight_hh
     in torch order) and a 1x1 output conv.  Tensors are picked per scope by SHAPE (16 kHz: basis [258,1,256], convs
     [128,129,3] [64,128,3] [64,64,3] [128,64,3]), biases through the Conv node that consumes each weight; names are used only
-    to tell weight_ih from weight_hh.  Raises with the scope's tensor listing when the file does not look like that."""
+    to tell weight_ih from weight_hh.  Raises with the scope's tensor listing when the file does not look like that.
+    The 8 kHz sub-graph is read by silero_8k_from_onnx."""
     from . import onnx_reader
     g = onnx_reader.read_onnx(path_or_bytes)
     if sample_rate != 16000:
-        raise ValueError("the HIP Silero network implements the 16 kHz sub-graph only (the 8 kHz one has a 128-point STFT and a "
-                         "65-channel first conv); use sampling_rate=16000")
-    want = {"stft_basis": (258, 1, 256), "enc0_w": (128, 129, 3), "enc1_w": (64, 128, 3), "enc2_w": (64, 64, 3), "enc3_w": (128, 64, 3)}
+        raise ValueError("silero_from_onnx reads the 16 kHz sub-graph only (the 8 kHz one has a 128-point STFT and a 65-channel first "
+                         "conv): read it with silero_8k_from_onnx, or use sampling_rate=16000")
+    w, _vis, _nodes, _basis = _silero_branch(g, 16000)
+    return w
+
+
+def silero_8k_from_onnx(path_or_bytes, missing_ok=False):
+    """The 8 kHz sub-graph of a Silero-VAD v5 `.onnx` -> the 8 kHz weight dict of vadx.silero.SileroEngine (`weights_8k`), read like
+    silero_from_onnx's 16 kHz one: by shape (basis [130,1,128], convs [128,65,3] [64,128,3] [64,64,3] [128,64,3]), biases through their
+    Conv nodes, either LSTM encoding.  The restated network's geometry is checked against the file where the branch has the nodes: the
+    STFT Conv's `strides` must be [64] and a reflect `Pad` must pad the last axis by (0, 32); a contradiction raises (such a file is not
+    the network the kernels compute).  A file without an 8 kHz branch raises with a listing of its weight shapes (missing_ok=True:
+    returns None instead)."""
+    from . import onnx_reader
+    g = onnx_reader.read_onnx(path_or_bytes)
+    if _silero_scope(g, _SILERO_SHAPES[8000]) is None:
+        if missing_ok:
+            return None
+    w, vis, nodes, basis = _silero_branch(g, 8000)
+    for n in nodes:
+        if n.op_type == "Conv" and len(n.inputs) >= 2 and n.inputs[1] == basis:
+            strides = [int(v) for v in n.attrs.get("strides", [1])]
+            if strides != [64]:
+                raise ValueError(f"8 kHz Silero branch: the STFT Conv {n.name!r} has strides {strides}; the restated network has a hop of 64")
+        if n.op_type == "Pad" and bytes(n.attrs.get("mode", b"constant")) == b"reflect":
+            pads = n.attrs.get("pads")
+            if pads is None and len(n.inputs) >= 2 and n.inputs[1] in vis:
+                pads = vis[n.inputs[1]].reshape(-1).tolist()
+            if pads is None:
+                continue          # computed at run time: nothing to check
+            k = len(pads) // 2
+            lr = (int(pads[k - 1]), int(pads[2 * k - 1]))
+            if lr != (0, 32):
+                raise ValueError(f"8 kHz Silero branch: the reflect Pad {n.name!r} pads the last axis by {lr}; the restated network pads (0, 32)")
+    return w
+
+
+_SILERO_SHAPES = {
+    16000: {"stft_basis": (258, 1, 256), "enc0_w": (128, 129, 3), "enc1_w": (64, 128, 3), "enc2_w": (64, 64, 3), "enc3_w": (128, 64, 3)},
+    8000: {"stft_basis": (130, 1, 128), "enc0_w": (128, 65, 3), "enc1_w": (64, 128, 3), "enc2_w": (64, 64, 3), "enc3_w": (128, 64, 3)},
+}
+
+
+def _silero_scope(g, want):
+    """the innermost (sub)graph scope that sees one tensor of every shape in `want`, or None"""
     chosen = None
     for sc in g.scopes():
         vis = g.in_scope(sc)
         if all(any(v.shape == shp for v in vis.values()) for shp in want.values()):
             chosen = sc if chosen is None or len(sc) > len(chosen) else chosen
+    return chosen
+
+
+def _silero_branch(g, rate):
+    """-> (weight dict, tensors visible from the branch, its nodes, the basis tensor's name) of the sub-graph of `rate`"""
+    want = _SILERO_SHAPES[rate]
+    label = "16 kHz" if rate == 16000 else "8 kHz"
+    chosen = _silero_scope(g, want)
     if chosen is None:
         listing = sorted({(tuple(v.shape)) for v in g.tensors.values() if v.ndim >= 2})
-        raise ValueError(f"no (sub)graph holds the 16 kHz Silero tensors {sorted(want.values())}; weight shapes present: {listing[:24]}")
+        raise ValueError(f"no (sub)graph holds the {label} Silero tensors {sorted(want.values())}; weight shapes present: {listing[:24]}")
     vis = g.in_scope(chosen)
     nodes = [n for n in g.nodes if n.scope == chosen[:len(n.scope)] and len(n.scope) <= len(chosen)]
 
@@ -403,7 +454,8 @@ def silero_from_onnx(path_or_bytes, sample_rate=16000):
             return hits[0]
         raise ValueError(f"cannot find the bias of conv weight {wname!r}")
 
-    w = {"stft_basis": vis[by_shape(want["stft_basis"])].reshape(258, 256)}
+    basis = by_shape(want["stft_basis"])
+    w = {"stft_basis": vis[basis].reshape(want["stft_basis"][0], want["stft_basis"][2])}
     for i in range(4):
         name = by_shape(want[f"enc{i}_w"])
         w[f"enc{i}_w"] = vis[name]
@@ -428,11 +480,11 @@ def silero_from_onnx(path_or_bytes, sample_rate=16000):
         w["lstm_b_ih"], w["lstm_b_hh"] = named("bias_ih", (4 * H,)), named("bias_hh", (4 * H,))
     dname = by_shape((1, H, 1))
     w["dec_w"], w["dec_b"] = vis[dname].reshape(H), bias_of(dname, 1).reshape(1)
-    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in w.items()}
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in w.items()}, vis, nodes, basis
 
 
 # --------------------------------------------------------------------------- what an engine's `weights` argument means
-_SYNTH = {"silero": "silero_synthetic", "fsmn": "fsmn_synthetic", "firered": "firered_synthetic",
+_SYNTH = {"silero": "silero_synthetic", "silero8k": "silero8k_synthetic", "fsmn": "fsmn_synthetic", "firered": "firered_synthetic",
           "marblenet": "marblenet_synthetic", "dfsmn": "dfsmn_synthetic"}
 
 
@@ -461,6 +513,10 @@ def resolve(kind, spec):
         if low.endswith(".onnx"):
             return silero_from_onnx(s)
         raise ValueError(f"silero: {s!r} is neither a .onnx file nor a .npz of arrays (a TorchScript .jit cannot be read without its code)")
+    if kind == "silero8k":
+        if low.endswith(".onnx"):
+            return silero_8k_from_onnx(s)
+        raise ValueError(f"silero8k: {s!r} is neither a .onnx file nor a .npz of arrays")
     if kind == "fsmn":
         return load_fsmn(s)
     if kind == "firered":
@@ -475,5 +531,5 @@ def resolve(kind, spec):
     raise ValueError(f"unknown model kind {kind!r}")
 
 
-_HINT = {"silero": "silero_vad.onnx or .npz", "fsmn": "FunASR model dir with model.pt + am.mvn", "firered": "dir with model.pth.tar + cmvn.ark",
+_HINT = {"silero": "silero_vad.onnx or .npz", "silero8k": "silero_vad.onnx with an 8 kHz branch, or .npz", "fsmn": "FunASR model dir with model.pt + am.mvn", "firered": "dir with model.pth.tar + cmvn.ark",
          "marblenet": "frame_vad_multilingual_marblenet_v2.0.nemo", "dfsmn": "dict from load_dfsmn_aec + mask-net arrays"}

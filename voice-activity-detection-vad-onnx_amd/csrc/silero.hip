@@ -16,6 +16,7 @@
 #include "split2.h"
 
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -770,6 +771,108 @@ using vadx::FRAG;
 
 extern "C" size_t vadx_silero_packed_floats(void) { return (size_t)PACKED_FLOATS; }
 
+// Every section the 16 kHz and 8 kHz networks share (conv2..4, W_ih, W_hh in all three layouts, their biases, the decoder), from the
+// rebalanced weights; hmax / reb_min collect what the fp16 x 2 refusal rule needs (see vadx_silero_pack_host)
+void vadx::silero::silero_pack_shared(const vadx_silero_weights_host *w, float *p, float &hmax, int &reb_min) {
+    auto frag = [](size_t base, int i, int k) { return base + ((size_t)(k / 16) * 64 + ((k % 16) / 4) * 16 + i) * 4 + (k % 4); };
+    for (int co = 0; co < 64; ++co)
+        for (int kk = 0; kk < 3; ++kk)
+            for (int ci = 0; ci < 128; ++ci)
+                p[frag(OFF_C2 + (size_t)(co / 16) * 24 * FRAG, co % 16, kk * 128 + ci)] = w->enc_w[1][((size_t)co * 128 + ci) * 3 + kk];
+    memcpy(p + OFF_B2, w->enc_b[1], 64 * sizeof(float));
+    for (int co = 0; co < 64; ++co)
+        for (int ps = 0; ps < 2; ++ps)
+            for (int ci = 0; ci < 64; ++ci)
+                p[frag(OFF_C3 + (size_t)(co / 16) * 8 * FRAG, co % 16, ps * 64 + ci)] = w->enc_w[2][((size_t)co * 64 + ci) * 3 + (ps + 1)];
+    memcpy(p + OFF_B3, w->enc_b[2], 64 * sizeof(float));
+    for (int co = 0; co < 128; ++co)
+        for (int ci = 0; ci < 64; ++ci)
+            p[frag(OFF_C4 + (size_t)(co / 16) * 4 * FRAG, co % 16, ci)] = w->enc_w[3][((size_t)co * 64 + ci) * 3 + 1];
+    memcpy(p + OFF_B4, w->enc_b[3], 128 * sizeof(float));
+    for (int r = 0; r < 512; ++r)          // row r = gate*128 + unit; tile = gate*8 + unit/16
+        for (int k = 0; k < 128; ++k) p[frag(OFF_IH + (size_t)(r / 16) * 8 * FRAG, r % 16, k)] = w->lstm_w_ih[(size_t)r * 128 + k];
+    for (int r = 0; r < 512; ++r) p[OFF_BG + r] = w->lstm_b_ih[r] + w->lstm_b_hh[r];
+    memcpy(p + OFF_HH, w->lstm_w_hh, 512 * 128 * sizeof(float));
+    memcpy(p + OFF_DW, w->dec_w, 128 * sizeof(float));
+    p[OFF_DB] = w->dec_b[0];
+    // ---- the same weights as bf16 x 3 fragments (silero_split.hip, split3.h)
+    for (int rt = 0; rt < 4; ++rt)
+        for (int kc = 0; kc < 4; ++kc)
+            for (int tap = 0; tap < 3; ++tap) {
+                float *f3 = p + OFF_Q2 + (size_t)(((rt * 4 + kc) * 3 + tap) * 3) * QF;
+                for (int i = 0; i < 16; ++i)
+                    for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->enc_w[1][((size_t)(16 * rt + i) * 128 + 32 * kc + k) * 3 + tap]);
+            }
+    for (int rt = 0; rt < 4; ++rt)
+        for (int th = 0; th < 2; ++th)
+            for (int kc = 0; kc < 2; ++kc) {
+                float *f3 = p + OFF_Q3 + (size_t)(((rt * 2 + th) * 2 + kc) * 3) * QF;
+                for (int i = 0; i < 16; ++i)
+                    for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->enc_w[2][((size_t)(16 * rt + i) * 64 + 32 * kc + k) * 3 + th + 1]);
+            }
+    for (int rt = 0; rt < 8; ++rt)
+        for (int kc = 0; kc < 2; ++kc) {
+            float *f3 = p + OFF_Q4 + (size_t)((rt * 2 + kc) * 3) * QF;
+            for (int i = 0; i < 16; ++i)
+                for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->enc_w[3][((size_t)(16 * rt + i) * 64 + 32 * kc + k) * 3 + 1]);
+        }
+    for (int wv = 0; wv < 8; ++wv)
+        for (int kc = 0; kc < 4; ++kc)
+            for (int g = 0; g < 4; ++g) {
+                float *f3 = p + OFF_QIH + (size_t)(((wv * 4 + kc) * 4 + g) * 3) * QF;
+                for (int i = 0; i < 16; ++i)
+                    for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->lstm_w_ih[(size_t)(g * 128 + wv * 16 + i) * 128 + 32 * kc + k]);
+            }
+    for (int wv = 0; wv < 8; ++wv)
+        for (int g = 0; g < 4; ++g)
+            for (int kc = 0; kc < 4; ++kc) {
+                float *f3 = p + OFF_QHH + (size_t)(((wv * 4 + g) * 4 + kc) * 3) * QF;
+                for (int i = 0; i < 16; ++i)
+                    for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->lstm_w_hh[(size_t)(g * 128 + wv * 16 + i) * 128 + 32 * kc + k]);
+            }
+    // ---- ... and as fp16 x 2 fragment pairs (silero_h2.hip, split2.h), same orders
+    for (int rt = 0; rt < 4; ++rt)
+        for (int kc = 0; kc < 4; ++kc)
+            for (int tap = 0; tap < 3; ++tap) {
+                float *f2 = p + OFF_H2 + (size_t)(((rt * 4 + kc) * 3 + tap) * 2) * HF;
+                for (int i = 0; i < 16; ++i)
+                    for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->enc_w[1][((size_t)(16 * rt + i) * 128 + 32 * kc + k) * 3 + tap]));
+            }
+    for (int rt = 0; rt < 4; ++rt)
+        for (int th = 0; th < 2; ++th)
+            for (int kc = 0; kc < 2; ++kc) {
+                float *f2 = p + OFF_H3 + (size_t)(((rt * 2 + th) * 2 + kc) * 2) * HF;
+                for (int i = 0; i < 16; ++i)
+                    for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->enc_w[2][((size_t)(16 * rt + i) * 64 + 32 * kc + k) * 3 + th + 1]));
+            }
+    for (int rt = 0; rt < 8; ++rt)
+        for (int kc = 0; kc < 2; ++kc) {
+            float *f2 = p + OFF_H4 + (size_t)((rt * 2 + kc) * 2) * HF;
+            for (int i = 0; i < 16; ++i)
+                for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->enc_w[3][((size_t)(16 * rt + i) * 64 + 32 * kc + k) * 3 + 1]));
+        }
+    for (int wv = 0; wv < 8; ++wv)
+        for (int kc = 0; kc < 4; ++kc)
+            for (int g = 0; g < 4; ++g) {
+                float *f2 = p + OFF_HIH + (size_t)(((wv * 4 + kc) * 4 + g) * 2) * HF;
+                for (int i = 0; i < 16; ++i)
+                    for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->lstm_w_ih[(size_t)(g * 128 + wv * 16 + i) * 128 + 32 * kc + k]));
+            }
+    for (int wv = 0; wv < 8; ++wv)
+        for (int g = 0; g < 4; ++g)
+            for (int kc = 0; kc < 4; ++kc) {
+                float *f2 = p + OFF_HHH + (size_t)(((wv * 4 + g) * 4 + kc) * 2) * HF;
+                for (int i = 0; i < 16; ++i)
+                    for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->lstm_w_hh[(size_t)(g * 128 + wv * 16 + i) * 128 + 32 * kc + k]));
+            }
+    // ... and no weight tensor wholly below the smallest normal fp16 once the chain is rebalanced (csrc/rebalance.h)
+    {
+        std::vector<float> whh(w->lstm_w_hh, w->lstm_w_hh + 512 * 128);
+        const int e = vadx::reb_exponent(whh);
+        if (e > -100000 && e < reb_min) reb_min = e;
+    }
+}
+
 extern "C" int vadx_silero_pack_host(const vadx_silero_weights_host *w_in, float *p) {
     VADX_REQUIRE(w_in && p, "vadx_silero_pack_host: NULL argument");
     VADX_REQUIRE(w_in->stft_basis && w_in->lstm_w_ih && w_in->lstm_w_hh && w_in->lstm_b_ih && w_in->lstm_b_hh && w_in->dec_w && w_in->dec_b,
@@ -886,26 +989,6 @@ extern "C" int vadx_silero_pack_host(const vadx_silero_weights_host *w_in, float
                 }
     }
     memcpy(p + OFF_B1, w->enc_b[0], 128 * sizeof(float));
-    for (int co = 0; co < 64; ++co)
-        for (int kk = 0; kk < 3; ++kk)
-            for (int ci = 0; ci < 128; ++ci)
-                p[frag(OFF_C2 + (size_t)(co / 16) * 24 * FRAG, co % 16, kk * 128 + ci)] = w->enc_w[1][((size_t)co * 128 + ci) * 3 + kk];
-    memcpy(p + OFF_B2, w->enc_b[1], 64 * sizeof(float));
-    for (int co = 0; co < 64; ++co)
-        for (int ps = 0; ps < 2; ++ps)
-            for (int ci = 0; ci < 64; ++ci)
-                p[frag(OFF_C3 + (size_t)(co / 16) * 8 * FRAG, co % 16, ps * 64 + ci)] = w->enc_w[2][((size_t)co * 64 + ci) * 3 + (ps + 1)];
-    memcpy(p + OFF_B3, w->enc_b[2], 64 * sizeof(float));
-    for (int co = 0; co < 128; ++co)
-        for (int ci = 0; ci < 64; ++ci)
-            p[frag(OFF_C4 + (size_t)(co / 16) * 4 * FRAG, co % 16, ci)] = w->enc_w[3][((size_t)co * 64 + ci) * 3 + 1];
-    memcpy(p + OFF_B4, w->enc_b[3], 128 * sizeof(float));
-    for (int r = 0; r < 512; ++r)          // row r = gate*128 + unit; tile = gate*8 + unit/16
-        for (int k = 0; k < 128; ++k) p[frag(OFF_IH + (size_t)(r / 16) * 8 * FRAG, r % 16, k)] = w->lstm_w_ih[(size_t)r * 128 + k];
-    for (int r = 0; r < 512; ++r) p[OFF_BG + r] = w->lstm_b_ih[r] + w->lstm_b_hh[r];
-    memcpy(p + OFF_HH, w->lstm_w_hh, 512 * 128 * sizeof(float));
-    memcpy(p + OFF_DW, w->dec_w, 128 * sizeof(float));
-    p[OFF_DB] = w->dec_b[0];
     // ---- the same conv / W_ih weights as bf16 x 3 fragments for the split-product encoder (silero_split.hip, split3.h)
     for (int rt = 0; rt < 8; ++rt)
         for (int kc = 0; kc < 4; ++kc)
@@ -919,40 +1002,6 @@ extern "C" int vadx_silero_pack_host(const vadx_silero_weights_host *w_in, float
             }
     for (int co = 0; co < 128; ++co)
         for (int tap = 0; tap < 3; ++tap) p[OFF_Q1N + co * 4 + tap] = w->enc_w[0][((size_t)co * 129 + 128) * 3 + tap];
-    for (int rt = 0; rt < 4; ++rt)
-        for (int kc = 0; kc < 4; ++kc)
-            for (int tap = 0; tap < 3; ++tap) {
-                float *f3 = p + OFF_Q2 + (size_t)(((rt * 4 + kc) * 3 + tap) * 3) * QF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->enc_w[1][((size_t)(16 * rt + i) * 128 + 32 * kc + k) * 3 + tap]);
-            }
-    for (int rt = 0; rt < 4; ++rt)
-        for (int th = 0; th < 2; ++th)
-            for (int kc = 0; kc < 2; ++kc) {
-                float *f3 = p + OFF_Q3 + (size_t)(((rt * 2 + th) * 2 + kc) * 3) * QF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->enc_w[2][((size_t)(16 * rt + i) * 64 + 32 * kc + k) * 3 + th + 1]);
-            }
-    for (int rt = 0; rt < 8; ++rt)
-        for (int kc = 0; kc < 2; ++kc) {
-            float *f3 = p + OFF_Q4 + (size_t)((rt * 2 + kc) * 3) * QF;
-            for (int i = 0; i < 16; ++i)
-                for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->enc_w[3][((size_t)(16 * rt + i) * 64 + 32 * kc + k) * 3 + 1]);
-        }
-    for (int wv = 0; wv < 8; ++wv)
-        for (int kc = 0; kc < 4; ++kc)
-            for (int g = 0; g < 4; ++g) {
-                float *f3 = p + OFF_QIH + (size_t)(((wv * 4 + kc) * 4 + g) * 3) * QF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->lstm_w_ih[(size_t)(g * 128 + wv * 16 + i) * 128 + 32 * kc + k]);
-            }
-    for (int wv = 0; wv < 8; ++wv)
-        for (int g = 0; g < 4; ++g)
-            for (int kc = 0; kc < 4; ++kc) {
-                float *f3 = p + OFF_QHH + (size_t)(((wv * 4 + g) * 4 + kc) * 3) * QF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->lstm_w_hh[(size_t)(g * 128 + wv * 16 + i) * 128 + 32 * kc + k]);
-            }
     // ---- ... and as fp16 x 2 fragment pairs for silero_h2.hip (split2.h), same orders
     for (int rt = 0; rt < 8; ++rt)
         for (int kc = 0; kc < 4; ++kc)
@@ -964,47 +1013,9 @@ extern "C" int vadx_silero_pack_host(const vadx_silero_weights_host *w_in, float
                         hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->enc_w[0][((size_t)(16 * rt + i) * 129 + bin) * 3 + tap]));
                     }
             }
-    for (int rt = 0; rt < 4; ++rt)
-        for (int kc = 0; kc < 4; ++kc)
-            for (int tap = 0; tap < 3; ++tap) {
-                float *f2 = p + OFF_H2 + (size_t)(((rt * 4 + kc) * 3 + tap) * 2) * HF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->enc_w[1][((size_t)(16 * rt + i) * 128 + 32 * kc + k) * 3 + tap]));
-            }
-    for (int rt = 0; rt < 4; ++rt)
-        for (int th = 0; th < 2; ++th)
-            for (int kc = 0; kc < 2; ++kc) {
-                float *f2 = p + OFF_H3 + (size_t)(((rt * 2 + th) * 2 + kc) * 2) * HF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->enc_w[2][((size_t)(16 * rt + i) * 64 + 32 * kc + k) * 3 + th + 1]));
-            }
-    for (int rt = 0; rt < 8; ++rt)
-        for (int kc = 0; kc < 2; ++kc) {
-            float *f2 = p + OFF_H4 + (size_t)((rt * 2 + kc) * 2) * HF;
-            for (int i = 0; i < 16; ++i)
-                for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->enc_w[3][((size_t)(16 * rt + i) * 64 + 32 * kc + k) * 3 + 1]));
-        }
-    for (int wv = 0; wv < 8; ++wv)
-        for (int kc = 0; kc < 4; ++kc)
-            for (int g = 0; g < 4; ++g) {
-                float *f2 = p + OFF_HIH + (size_t)(((wv * 4 + kc) * 4 + g) * 2) * HF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->lstm_w_ih[(size_t)(g * 128 + wv * 16 + i) * 128 + 32 * kc + k]));
-            }
-    for (int wv = 0; wv < 8; ++wv)
-        for (int g = 0; g < 4; ++g)
-            for (int kc = 0; kc < 4; ++kc) {
-                float *f2 = p + OFF_HHH + (size_t)(((wv * 4 + g) * 4 + kc) * 2) * HF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->lstm_w_hh[(size_t)(g * 128 + wv * 16 + i) * 128 + 32 * kc + k]));
-            }
+    silero_pack_shared(w, p, hmax, reb_min);
     // the fp16 x 2 kernels need the folded STFT pass and every weight inside the fp16 range (NaN fails the comparison too)
     // ... and no weight tensor wholly below the smallest normal fp16 once the chain is rebalanced (csrc/rebalance.h)
-    {
-        std::vector<float> whh(w->lstm_w_hh, w->lstm_w_hh + 512 * 128);
-        const int e = vadx::reb_exponent(whh);
-        if (e > -100000 && e < reb_min) reb_min = e;
-    }
     p[OFF_HFLAG] = (p[OFF_FOLD] != 0.f && hmax <= vadx::H_MAX && reb_min >= vadx::REB_REFUSE) ? 1.f : 0.f;
     return VADX_OK;
 }
@@ -1024,6 +1035,19 @@ static int arith_of(const vadx_silero_cfg *cfg) {
 #define VADX_SILERO_ARITH(cfg, who)                                                                               \
     const int arith = arith_of(cfg);                                                                              \
     VADX_REQUIRE(arith >= 0, who ": cfg->arithmetic=%d is not one of VADX_ARITH_*", (cfg) ? (cfg)->arithmetic : 0)
+// Which network a launch runs (vadx_silero_cfg.ext.sample_rate, ABI 9): 0 / 16000 = the 16 kHz network (windows of 512 samples after a 64-sample
+// context), 8000 = the 8 kHz one (256 after 32); anything else -1.  The blob must be the one packed for that rate.
+// the cfg's C layout is ABI: 16 bytes, the rate in the second word (ABI 8 callers' zero-initialised reserved words select 16 kHz)
+static_assert(sizeof(vadx_silero_cfg) == 16 && offsetof(vadx_silero_cfg, ext) == 4 && sizeof(((vadx_silero_cfg *)nullptr)->ext) == 12,
+              "vadx_silero_cfg layout");
+static int rate_of(const vadx_silero_cfg *cfg) {
+    const int r = cfg ? cfg->ext.sample_rate : 0;
+    return (r == 0 || r == 16000) ? 16000 : (r == 8000 ? 8000 : -1);
+}
+#define VADX_SILERO_RATE(cfg, who)                                                                                \
+    const int rate = rate_of(cfg);                                                                                \
+    VADX_REQUIRE(rate > 0, who ": cfg->ext.sample_rate=%d is not 16000 or 8000 (0 = 16000)", (cfg) ? (cfg)->ext.sample_rate : 0); \
+    const long long win = rate == 8000 ? 256 : 512, ctx = win / 8
 
 // The fp16 x 2 kernels' sticky range flag (silero_common.h: OFF_HFLAG): copies the two words [flag, bits of the largest |activation|]
 // to the host (synchronises `stream`) and, with reset != 0, clears them on the device.
@@ -1051,6 +1075,8 @@ int vadx::silero::silero_encode_launch(const float *packed, const S *src, float 
                                        long long origin, int batch, int steps, void *ws, size_t ws_bytes, void *stream,
                                        const vadx_silero_cfg *cfg, int first_group, int total_batch) {
     VADX_SILERO_ARITH(cfg, "silero");
+    VADX_SILERO_RATE(cfg, "silero");
+    (void)ctx;
     VADX_REQUIRE(packed && src && ws, "silero: NULL pointer argument");
     VADX_REQUIRE(batch > 0 && steps > 0, "silero: batch=%d steps=%d must be positive", batch, steps);
     VADX_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0,
@@ -1066,6 +1092,9 @@ int vadx::silero::silero_encode_launch(const float *packed, const S *src, float 
     }
     const long long nblk = (long long)G * steps;
     VADX_REQUIRE(nblk < (1LL << 31), "silero: too many tiles (%lld)", nblk);
+    if (win == 256)
+        return silero8k_encode_launch<S>(arith, packed, src, in_scale, n_valid, row_stride, origin, batch, G, steps, Gws, first_group,
+                                         static_cast<float *>(ws), stream);
     if (arith == 2)
         return silero_encode_h2_launch<S>(packed, src, in_scale, n_valid, row_stride, origin, batch, G, steps, Gws, first_group,
                                           static_cast<float *>(ws), stream);
@@ -1084,6 +1113,8 @@ int vadx::silero::silero_recur_launch(const float *packed, const void *ws, size_
                                       const float *state0, float *probs, long long probs_stride, float *state_n, void *stream,
                                       const vadx_silero_cfg *cfg) {
     VADX_SILERO_ARITH(cfg, "silero");
+    VADX_SILERO_RATE(cfg, "silero");
+    (void)win; (void)ctx;
     VADX_REQUIRE(packed && ws && probs, "silero: NULL pointer argument");
     VADX_REQUIRE(batch > 0 && steps > 0, "silero: batch=%d steps=%d must be positive", batch, steps);
     if (ws_bytes < vadx_silero_workspace_bytes(batch, steps)) {
@@ -1117,33 +1148,36 @@ static int silero_run(const float *packed, const float *src, long long n_valid, 
 
 extern "C" int vadx_silero_encode(const float *packed, const float *audio, int batch, int64_t n_samples,
                                   int64_t row_stride, void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg) {
+    VADX_SILERO_RATE(cfg, "vadx_silero_encode");
     VADX_REQUIRE(n_samples > 0 && row_stride >= n_samples, "vadx_silero_encode: n_samples=%lld row_stride=%lld",
                  (long long)n_samples, (long long)row_stride);
-    const long long steps = (n_samples + 511) / 512;
+    const long long steps = (n_samples + win - 1) / win;
     VADX_REQUIRE(steps < (1LL << 30), "vadx_silero_encode: clip too long");
-    return silero_encode_launch(packed, audio, 1.0f, n_samples, row_stride, -64, batch, (int)steps, workspace, workspace_bytes, stream, cfg);
+    return silero_encode_launch(packed, audio, 1.0f, n_samples, row_stride, -ctx, batch, (int)steps, workspace, workspace_bytes, stream, cfg);
 }
 
 extern "C" int vadx_silero_encode_pcm16(const float *packed, const int16_t *audio, float scale, int batch, int64_t n_samples,
                                         int64_t row_stride, void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg) {
+    VADX_SILERO_RATE(cfg, "vadx_silero_encode_pcm16");
     VADX_REQUIRE(n_samples > 0 && row_stride >= n_samples, "vadx_silero_encode_pcm16: n_samples=%lld row_stride=%lld",
                  (long long)n_samples, (long long)row_stride);
-    const long long steps = (n_samples + 511) / 512;
+    const long long steps = (n_samples + win - 1) / win;
     VADX_REQUIRE(steps < (1LL << 30), "vadx_silero_encode_pcm16: clip too long");
-    return silero_encode_launch(packed, audio, scale, n_samples, row_stride, -64, batch, (int)steps, workspace, workspace_bytes, stream, cfg);
+    return silero_encode_launch(packed, audio, scale, n_samples, row_stride, -ctx, batch, (int)steps, workspace, workspace_bytes, stream, cfg);
 }
 
 extern "C" int vadx_silero_encode_pcm16_part(const float *packed, const int16_t *audio, float scale, int batch, int64_t n_samples,
                                              int64_t row_stride, int first_clip, int total_batch, void *workspace,
                                              size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg) {
+    VADX_SILERO_RATE(cfg, "vadx_silero_encode_pcm16_part");
     VADX_REQUIRE(n_samples > 0 && row_stride >= n_samples, "vadx_silero_encode_pcm16_part: n_samples=%lld row_stride=%lld",
                  (long long)n_samples, (long long)row_stride);
     VADX_REQUIRE(first_clip >= 0 && first_clip % 16 == 0 && first_clip + batch <= total_batch,
                  "vadx_silero_encode_pcm16_part: first_clip=%d must be a multiple of 16 and first_clip + batch <= total_batch=%d",
                  first_clip, total_batch);
-    const long long steps = (n_samples + 511) / 512;
+    const long long steps = (n_samples + win - 1) / win;
     VADX_REQUIRE(steps < (1LL << 30), "vadx_silero_encode_pcm16_part: clip too long");
-    return silero_encode_launch(packed, audio, scale, n_samples, row_stride, -64, batch, (int)steps, workspace, workspace_bytes, stream,
+    return silero_encode_launch(packed, audio, scale, n_samples, row_stride, -ctx, batch, (int)steps, workspace, workspace_bytes, stream,
                                 cfg, first_clip / 16, total_batch);
 }
 
@@ -1155,12 +1189,13 @@ extern "C" int vadx_silero_recur(const float *packed, const void *workspace, siz
 extern "C" int vadx_silero_encode_span(const float *packed, const float *audio, int batch, int64_t n_samples,
                                        int64_t row_stride, int first_step, int n_steps, void *workspace,
                                        size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg) {
+    VADX_SILERO_RATE(cfg, "vadx_silero_encode_span");
     VADX_REQUIRE(n_samples > 0 && row_stride >= n_samples, "vadx_silero_encode_span: n_samples=%lld row_stride=%lld",
                  (long long)n_samples, (long long)row_stride);
-    const long long steps = (n_samples + 511) / 512;
+    const long long steps = (n_samples + win - 1) / win;
     VADX_REQUIRE(first_step >= 0 && n_steps > 0 && (long long)first_step + n_steps <= steps,
                  "vadx_silero_encode_span: span [%d, %d + %d) outside the clip's %lld windows", first_step, first_step, n_steps, steps);
-    return silero_encode_launch(packed, audio, 1.0f, n_samples, row_stride, (long long)first_step * 512 - 64, batch, n_steps,
+    return silero_encode_launch(packed, audio, 1.0f, n_samples, row_stride, (long long)first_step * win - ctx, batch, n_steps,
                                 workspace, workspace_bytes, stream, cfg);
 }
 
@@ -1174,19 +1209,21 @@ extern "C" int vadx_silero_recur_span(const float *packed, const void *workspace
 extern "C" int vadx_silero_step(const float *packed, const float *input, const float *state, int64_t sr,
                                 int batch, float *out, float *state_n, void *workspace,
                                 size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg) {
-    VADX_REQUIRE(sr == 16000, "Supported sampling rates: [16000] (got %lld)", (long long)sr);
+    VADX_SILERO_RATE(cfg, "vadx_silero_step");
+    VADX_REQUIRE(sr == rate, "Supported sampling rates: [%d] (got %lld; vadx_silero_cfg.ext.sample_rate selects the network)", rate, (long long)sr);
     VADX_REQUIRE(state && state_n, "vadx_silero_step: state / state_n must not be NULL");
-    return silero_run(packed, input, 576, 576, 0, batch, 1, state, out, 1, state_n, workspace, workspace_bytes, stream, cfg);
+    return silero_run(packed, input, win + ctx, win + ctx, 0, batch, 1, state, out, 1, state_n, workspace, workspace_bytes, stream, cfg);
 }
 
 extern "C" int vadx_silero_clips(const float *packed, const float *audio, int batch, int64_t n_samples,
                                  int64_t row_stride, float *probs, float *state_n, void *workspace,
                                  size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg) {
+    VADX_SILERO_RATE(cfg, "vadx_silero_clips");
     VADX_REQUIRE(n_samples > 0 && row_stride >= n_samples, "vadx_silero_clips: n_samples=%lld row_stride=%lld",
                  (long long)n_samples, (long long)row_stride);
-    const long long steps = (n_samples + 511) / 512;
+    const long long steps = (n_samples + win - 1) / win;
     VADX_REQUIRE(steps < (1LL << 30), "vadx_silero_clips: clip too long");
-    return silero_run(packed, audio, n_samples, row_stride, -64, batch, (int)steps, nullptr, probs, steps,
+    return silero_run(packed, audio, n_samples, row_stride, -ctx, batch, (int)steps, nullptr, probs, steps,
                       state_n, workspace, workspace_bytes, stream, cfg);
 }
 

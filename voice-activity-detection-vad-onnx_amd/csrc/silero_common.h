@@ -201,6 +201,13 @@ int silero_recur_launch(const float *packed, const void *ws, size_t ws_bytes, in
                         const float *state0, float *probs, long long probs_stride, float *state_n, void *stream,
                         const vadx_silero_cfg *cfg);
 
+// csrc/silero8k.hip: the 8 kHz network's encoder (arith = VADX_AR_*; arguments otherwise as silero_encode_split_launch, windows of 256)
+template <typename S>
+int silero8k_encode_launch(int arith, const float *packed, const S *src, float in_scale, long long n_valid, long long row_stride,
+                           long long origin, int batch, int G, int steps, int Gws, int first_group, float *gx, void *stream);
+// host: the packed sections the 16 kHz and 8 kHz blobs share (csrc/silero.hip)
+void silero_pack_shared(const vadx_silero_weights_host *w, float *p, float &hmax, int &reb_min);
+
 int silero_lstm_split_launch(const float *packed, const float *gx, const float *state0, int batch, int G, int steps, float *probs,
                              long long probs_stride, float *state_n, void *stream);
 

@@ -1,6 +1,6 @@
 // silero_stream.hip -- streaming Silero: S live streams advance by k windows per call, every stream's context, LSTM state and VADIterator
 // machine held in a device record (include/vadx.h: vadx_silero_stream_run).  One tick = four stream-ordered launches:
-//   silero_stream_stage_kernel<SampleT>: staged f32 rows [context(64) | k*512 samples] in the workspace, the initial LSTM state (zeros for a
+//   silero_stream_stage_kernel<SampleT, CW, WW>: staged f32 rows [context(64) | k*512 samples] (32 | k*256 at 8 kHz) in the workspace, the initial LSTM state (zeros for a
 //       reset stream), NaN pre-filled into probs and state_out's h/c (a launch that writes nothing leaves NaN, never stale numbers);
 //   the tuned encoder over the staged rows (origin 0, as vadx_silero_step runs it) and the recurrent launch, unchanged (csrc/silero.hip);
 //   silero_stream_iter_kernel: VADIterator's machine (utils_vad.py:535-586), one stream per thread, then the record's context.
@@ -44,7 +44,9 @@ inline size_t state0_bytes(long long S) { return align256((size_t)S * 2 * 128 * 
 
 constexpr int STAGE_THREADS = 256, STAGE_PER_BLOCK = 4 * STAGE_THREADS;      // floats of one staged row per block
 
-template <typename SampleT>
+// CW / WW: the network's context and window (64 / 512 at 16 kHz, 32 / 256 at 8 kHz); the record keeps CTX floats of context per stream
+// either way (an 8 kHz stream uses the first 32)
+template <typename SampleT, int CW, int WW>
 __global__ __launch_bounds__(STAGE_THREADS) void silero_stream_stage_kernel(
     const SampleT *__restrict__ samples, float scale, long long row_stride, int S, int k, const unsigned char *__restrict__ reset,
     const unsigned char *__restrict__ active, const float *__restrict__ hc_in, const float *__restrict__ ctx_in, float *__restrict__ hc_out,
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(STAGE_THREADS) void silero_stream_stage_kernel(
     const int tid = threadIdx.x;
     const bool act = active == nullptr || active[s] != 0;
     const bool fresh = !act || (reset != nullptr && reset[s] != 0);     // inactive rows run on zeros: their results are discarded, and
-    const long long L = CTX + (long long)k * WIN;                      // garbage there must not raise the fp16 range flag
+    const long long L = CW + (long long)k * WW;                        // garbage there must not raise the fp16 range flag
     float *row = staged + s * L;
     const long long i0 = (long long)blockIdx.y * STAGE_PER_BLOCK;
 #pragma unroll
@@ -61,10 +63,10 @@ __global__ __launch_bounds__(STAGE_THREADS) void silero_stream_stage_kernel(
         const long long i = i0 + tid + j * STAGE_THREADS;
         if (i >= L) break;
         float v = 0.f;
-        if (i < CTX) {
+        if (i < CW) {
             if (!fresh) v = ctx_in[s * CTX + i];
         } else if (act) {
-            v = SampleIO<SampleT>::load1(samples + s * row_stride + (i - CTX), scale);
+            v = SampleIO<SampleT>::load1(samples + s * row_stride + (i - CW), scale);
         }
         row[i] = v;
     }
@@ -84,6 +86,7 @@ struct IterConsts {
     double thr, neg, pad, min_sil;
 };
 
+template <int CW, int WW>
 __global__ __launch_bounds__(ITER_THREADS) void silero_stream_iter_kernel(
     IterConsts q, int S, int k, const unsigned char *__restrict__ reset, const unsigned char *__restrict__ active, StreamRecord in,
     StreamRecord out, const float *__restrict__ staged, float *__restrict__ probs, signed char *__restrict__ kind,
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(ITER_THREADS) void silero_stream_iter_kernel(
                 const float p = probs[s * k + t];
                 signed char e = 0;
                 double v = 0.0;
-                cur += WIN;
+                cur += WW;
                 if (!isfinite(p)) {                // NaN score: "invalid", and the stream stays so until reset (its h is poisoned below)
                     e = -1;
                     poison = true;
@@ -121,14 +124,14 @@ __global__ __launch_bounds__(ITER_THREADS) void silero_stream_iter_kernel(
                     if (!trig) {
                         trig = true;
                         e = 1;
-                        const double x = ((double)cur - q.pad) - (double)WIN;
+                        const double x = ((double)cur - q.pad) - (double)WW;
                         v = x > 0.0 ? x : 0.0;                   // max(0, x): the int 0 unless x is larger
                     }
                 } else if ((double)p < q.neg && trig) {
                     if (!temp_end) temp_end = cur;
                     if ((double)(cur - temp_end) >= q.min_sil) {
                         e = 2;
-                        v = ((double)temp_end + q.pad) - (double)WIN;
+                        v = ((double)temp_end + q.pad) - (double)WW;
                         temp_end = 0;
                         trig = false;
                     }
@@ -143,12 +146,12 @@ __global__ __launch_bounds__(ITER_THREADS) void silero_stream_iter_kernel(
         }
     }
     __syncthreads();
-    const long long L = CTX + (long long)k * WIN;
+    const long long L = CW + (long long)k * WW;
     const int n = S - s0 < ITER_THREADS ? (int)(S - s0) : ITER_THREADS;
     for (int i = 0; i < n; ++i) {
         const long long r = s0 + i;
         const unsigned char w = what[i];
-        out.ctx[r * CTX + tid] = w == 2 ? in.ctx[r * CTX + tid] : staged[r * L + L - CTX + tid];
+        out.ctx[r * CTX + tid] = w == 2 ? in.ctx[r * CTX + tid] : (tid < CW ? staged[r * L + L - CW + tid] : 0.f);
         if (w == 2) {
             for (int u = tid; u < 2 * 128; u += ITER_THREADS) {
                 const long long off = ((long long)(u >> 7) * S + r) * 128 + (u & 127);
@@ -179,12 +182,15 @@ extern "C" int vadx_silero_stream_run(const float *packed, const vadx_silero_ite
                                       const vadx_silero_cfg *cfg) {
     VADX_REQUIRE(packed && prm && samples && state_in && state_out && probs && event_kind && event_value && workspace,
                  "vadx_silero_stream_run: NULL pointer argument");
-    VADX_REQUIRE(prm->sampling_rate == 16000,
-                 "sr=%d: only the 16 kHz sub-graph of the Silero network is built on the HIP path (the 8 kHz network itself is not "
-                 "implemented)", (int)prm->sampling_rate);
+    const int rate = (cfg == nullptr || cfg->ext.sample_rate == 0) ? 16000 : cfg->ext.sample_rate;
+    VADX_REQUIRE(rate == 16000 || rate == 8000, "vadx_silero_stream_run: cfg->ext.sample_rate=%d is not 16000 or 8000 (0 = 16000)", rate);
+    VADX_REQUIRE(prm->sampling_rate == rate,
+                 "sr=%d: the cfg selects the %d kHz sub-graph of the Silero network (vadx_silero_cfg.ext.sample_rate and the blob must be "
+                 "packed for the same rate)", (int)prm->sampling_rate, rate / 1000);
+    const int win = rate == 8000 ? 256 : WIN, cw = win / 8;
     VADX_REQUIRE(streams > 0 && windows > 0 && windows <= MAX_WINDOWS, "vadx_silero_stream_run: streams=%d windows=%d", streams, windows);
-    VADX_REQUIRE(row_stride >= (int64_t)windows * WIN, "vadx_silero_stream_run: row_stride=%lld < windows * 512 = %lld",
-                 (long long)row_stride, (long long)windows * WIN);
+    VADX_REQUIRE(row_stride >= (int64_t)windows * win, "vadx_silero_stream_run: row_stride=%lld < windows * %d = %lld",
+                 (long long)row_stride, win, (long long)windows * win);
     const int a = cfg ? cfg->arithmetic : VADX_ARITH_AUTO;
     VADX_REQUIRE(a >= VADX_ARITH_AUTO && a <= VADX_ARITH_F16X2, "vadx_silero_stream_run: cfg->arithmetic=%d is not one of VADX_ARITH_*", a);
     const size_t rb = record_bytes(streams);
@@ -205,15 +211,28 @@ extern "C" int vadx_silero_stream_run(const float *packed, const vadx_silero_ite
     const size_t gx_bytes = workspace_bytes - (size_t)(gx - ws);
     const StreamRecord rin = record_at(const_cast<void *>(state_in), streams), rout = record_at(state_out, streams);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const long long L = CTX + (long long)windows * WIN;
+    const long long L = cw + (long long)windows * win;      // (the workspace is laid out for the 16 kHz geometry, an upper bound)
 
     const dim3 sgrid((unsigned)streams, (unsigned)((L + STAGE_PER_BLOCK - 1) / STAGE_PER_BLOCK));
-    if (samples_int16)
-        hipLaunchKernelGGL(silero_stream_stage_kernel<int16_t>, sgrid, dim3(STAGE_THREADS), 0, st, static_cast<const int16_t *>(samples),
-                           scale, (long long)row_stride, streams, windows, reset, active, rin.hc, rin.ctx, rout.hc, staged, state0, probs);
-    else
-        hipLaunchKernelGGL(silero_stream_stage_kernel<float>, sgrid, dim3(STAGE_THREADS), 0, st, static_cast<const float *>(samples), 1.0f,
-                           (long long)row_stride, streams, windows, reset, active, rin.hc, rin.ctx, rout.hc, staged, state0, probs);
+    if (win == 256) {
+        if (samples_int16)
+            hipLaunchKernelGGL((silero_stream_stage_kernel<int16_t, 32, 256>), sgrid, dim3(STAGE_THREADS), 0, st,
+                               static_cast<const int16_t *>(samples), scale, (long long)row_stride, streams, windows, reset, active, rin.hc,
+                               rin.ctx, rout.hc, staged, state0, probs);
+        else
+            hipLaunchKernelGGL((silero_stream_stage_kernel<float, 32, 256>), sgrid, dim3(STAGE_THREADS), 0, st,
+                               static_cast<const float *>(samples), 1.0f, (long long)row_stride, streams, windows, reset, active, rin.hc,
+                               rin.ctx, rout.hc, staged, state0, probs);
+    } else {
+        if (samples_int16)
+            hipLaunchKernelGGL((silero_stream_stage_kernel<int16_t, CTX, WIN>), sgrid, dim3(STAGE_THREADS), 0, st,
+                               static_cast<const int16_t *>(samples), scale, (long long)row_stride, streams, windows, reset, active, rin.hc,
+                               rin.ctx, rout.hc, staged, state0, probs);
+        else
+            hipLaunchKernelGGL((silero_stream_stage_kernel<float, CTX, WIN>), sgrid, dim3(STAGE_THREADS), 0, st,
+                               static_cast<const float *>(samples), 1.0f, (long long)row_stride, streams, windows, reset, active, rin.hc,
+                               rin.ctx, rout.hc, staged, state0, probs);
+    }
     VADX_HIP_TRY(hipGetLastError());
 
     int rc = silero_encode_launch<float>(packed, staged, 1.0f, L, L, 0, streams, windows, gx, gx_bytes, stream, cfg);
@@ -227,8 +246,13 @@ extern "C" int vadx_silero_stream_run(const float *packed, const vadx_silero_ite
     q.neg = prm->threshold - 0.15;
     q.pad = sr * prm->speech_pad_ms / 1000.0;
     q.min_sil = sr * prm->min_silence_duration_ms / 1000.0;
-    hipLaunchKernelGGL(silero_stream_iter_kernel, dim3((unsigned)((streams + ITER_THREADS - 1) / ITER_THREADS)), dim3(ITER_THREADS), 0, st, q,
-                       streams, windows, reset, active, rin, rout, staged, probs, reinterpret_cast<signed char *>(event_kind), event_value);
+    const dim3 igrid((unsigned)((streams + ITER_THREADS - 1) / ITER_THREADS));
+    if (win == 256)
+        hipLaunchKernelGGL((silero_stream_iter_kernel<32, 256>), igrid, dim3(ITER_THREADS), 0, st, q, streams, windows, reset, active, rin,
+                           rout, staged, probs, reinterpret_cast<signed char *>(event_kind), event_value);
+    else
+        hipLaunchKernelGGL((silero_stream_iter_kernel<CTX, WIN>), igrid, dim3(ITER_THREADS), 0, st, q, streams, windows, reset, active, rin,
+                           rout, staged, probs, reinterpret_cast<signed char *>(event_kind), event_value);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }

@@ -23,6 +23,13 @@ from . import weights as _weights
 CONTEXT_SIZE = 64
 NUM_SAMPLES = 512
 HIDDEN = 128
+GEOMETRY = {16000: (512, 64), 8000: (256, 32)}      # sampling rate -> (window, context) of the network
+
+
+def _geom(sampling_rate):
+    if int(sampling_rate) not in GEOMETRY:
+        raise ValueError(f"Supported sampling rates: [8000, 16000] (got {sampling_rate})")
+    return GEOMETRY[int(sampling_rate)]
 
 
 def _as_weight_dict(path_or_weights):
@@ -34,6 +41,52 @@ def _as_weight_dict(path_or_weights):
     w = {k: np.ascontiguousarray(np.asarray(v), dtype=np.float32) for k, v in w.items()}
     _weights.silero_check(w)
     return w
+
+
+def _as_weight_dict_8k(spec):
+    """The 8 kHz network's weights: dict | .npz | "synthetic:<seed>" (checkpoints.resolve("silero8k"))."""
+    from . import checkpoints
+    w = checkpoints.resolve("silero8k", spec)
+    w = {k: np.ascontiguousarray(np.asarray(v), dtype=np.float32) for k, v in w.items()}
+    _weights.silero_check(w, sample_rate=8000)
+    return w
+
+
+def _weights_8k_spec(path_or_weights, weights_8k):
+    """What SileroEngine loads as its 8 kHz network: `weights_8k` when given; otherwise, for an .onnx `path_or_weights`, that file's
+    8 kHz branch when it has one (silero_8k_from_onnx, geometry checked: a branch that contradicts the restated network raises);
+    otherwise None."""
+    if weights_8k is not None:
+        return _as_weight_dict_8k(weights_8k)
+    if isinstance(path_or_weights, (str, os.PathLike)) and str(path_or_weights).lower().endswith(".onnx"):
+        from . import checkpoints
+        w = checkpoints.silero_8k_from_onnx(str(path_or_weights), missing_ok=True)
+        if w is not None:
+            w = {k: np.ascontiguousarray(np.asarray(v), dtype=np.float32) for k, v in w.items()}
+            _weights.silero_check(w, sample_rate=8000)
+        return w
+    return None
+
+
+def _pack(w, sample_rate):
+    L = _lib.lib()
+    hw = _lib.SileroWeightsHost()
+    keep = []
+
+    def ptr(a):
+        keep.append(a)
+        return a.ctypes.data_as(C.c_void_p)
+
+    hw.stft_basis = ptr(w["stft_basis"])
+    for i in range(4):
+        hw.enc_w[i] = ptr(w[f"enc{i}_w"]).value
+        hw.enc_b[i] = ptr(w[f"enc{i}_b"]).value
+    hw.lstm_w_ih, hw.lstm_w_hh = ptr(w["lstm_w_ih"]), ptr(w["lstm_w_hh"])
+    hw.lstm_b_ih, hw.lstm_b_hh = ptr(w["lstm_b_ih"]), ptr(w["lstm_b_hh"])
+    hw.dec_w, hw.dec_b = ptr(w["dec_w"]), ptr(w["dec_b"])
+    packed = np.zeros(L.vadx_silero_packed_floats_sr(int(sample_rate)), dtype=np.float32)
+    _lib.check(L.vadx_silero_pack_host_sr(int(sample_rate), C.byref(hw), packed.ctypes.data_as(C.c_void_p)))
+    return packed
 
 
 WORKSPACE_CAP_BYTES = 8 << 30     # clips(): above this the gate-preactivation workspace is reused span by span
@@ -65,60 +118,71 @@ def encoder_mode(mode=None):
 class SileroEngine:
     """Device-resident packed weights + workspace; thin wrappers over the C ABI."""
 
-    def __init__(self, path_or_weights=None, device="cuda:0"):
+    def __init__(self, path_or_weights=None, device="cuda:0", weights_8k=None):
+        """path_or_weights: the 16 kHz network (see _as_weight_dict).  weights_8k: the 8 kHz network (dict, .npz, "synthetic:<seed>" or
+        an .onnx file's 8 kHz branch); None with an .onnx `path_or_weights` loads that file's 8 kHz branch when it has one, otherwise the
+        engine has none (sampling_rate=8000 then raises).  `has_8k` says whether it is there."""
         torch = _lib.require_gpu()
         self.torch = torch
         self.device = torch.device(device)
         L = _lib.lib()
         w = _as_weight_dict(path_or_weights)
-        hw = _lib.SileroWeightsHost()
-        keep = []
-
-        def ptr(a):
-            keep.append(a)
-            return a.ctypes.data_as(C.c_void_p)
-
-        hw.stft_basis = ptr(w["stft_basis"])
-        for i in range(4):
-            hw.enc_w[i] = ptr(w[f"enc{i}_w"]).value
-            hw.enc_b[i] = ptr(w[f"enc{i}_b"]).value
-        hw.lstm_w_ih, hw.lstm_w_hh = ptr(w["lstm_w_ih"]), ptr(w["lstm_w_hh"])
-        hw.lstm_b_ih, hw.lstm_b_hh = ptr(w["lstm_b_ih"]), ptr(w["lstm_b_hh"])
-        hw.dec_w, hw.dec_b = ptr(w["dec_w"]), ptr(w["dec_b"])
-        packed = np.zeros(L.vadx_silero_packed_floats(), dtype=np.float32)
-        _lib.check(L.vadx_silero_pack_host(C.byref(hw), packed.ctypes.data_as(C.c_void_p)))
+        packed = _pack(w, 16000)
         self.packed = torch.from_numpy(packed).to(self.device)
         self._ws = None
         self.arithmetic = None            # None = the module default (encoder_mode()); or "f32" | "split" | "h2" for this engine
         self.h2_ok = bool(packed[L.vadx_silero_packed_floats() - 4] != 0.0)      # the blob's fp16 x 2 section is usable (pack-time check)
         self.range_fallbacks = 0          # batches recomputed on bf16 x 3 because an activation left the fp16 range
+        self.packed_8k, self.h2_ok_8k = None, False
+        w8 = _weights_8k_spec(path_or_weights, weights_8k)
+        if w8 is not None:
+            p8 = _pack(w8, 8000)
+            self.packed_8k = torch.from_numpy(p8).to(self.device)
+            self.h2_ok_8k = bool(p8[L.vadx_silero_packed_floats() - 4] != 0.0)
+
+    @property
+    def has_8k(self):
+        """True when the engine holds the 8 kHz network (sampling_rate=8000 on every entry point)"""
+        return self.packed_8k is not None
+
+    def blob(self, sampling_rate=16000):
+        """the device blob of the network for `sampling_rate`"""
+        _geom(sampling_rate)
+        if int(sampling_rate) == 16000:
+            return self.packed
+        if self.packed_8k is None:
+            raise ValueError(f"sr={sampling_rate}: this engine holds only the 16 kHz sub-graph of the Silero network (build it from an "
+                             ".onnx file with an 8 kHz branch, or pass weights_8k= to SileroEngine)")
+        return self.packed_8k
 
     # -- arithmetic selection + the fp16 x 2 range protocol
-    def mode(self):
+    def mode(self, sampling_rate=16000):
         m = self.arithmetic or encoder_mode()
-        return "split" if (m == "h2" and not self.h2_ok) else m
+        ok = self.h2_ok if int(sampling_rate) == 16000 else self.h2_ok_8k
+        return "split" if (m == "h2" and not ok) else m
 
-    def cfg(self, mode=None):
-        """ctypes pointer to a vadx_silero_cfg for `mode` (default: this engine's current mode)"""
+    def cfg(self, mode=None, sampling_rate=16000):
+        """ctypes pointer to a vadx_silero_cfg for `mode` (default: this engine's current mode) and the network of `sampling_rate`"""
         c = _lib.SileroCfg()
-        c.arithmetic = ENCODER_MODES[mode or self.mode()]
+        c.arithmetic = ENCODER_MODES[mode or self.mode(sampling_rate)]
+        c.sample_rate = 8000 if int(sampling_rate) == 8000 else 0
         return C.byref(c)
 
-    def range_flag(self, reset=True):
+    def range_flag(self, reset=True, sampling_rate=16000):
         """(flag, largest |activation|) of the fp16 x 2 kernels since the last reset; synchronises the stream (vadx_silero_range_flag)"""
         flag, amax = C.c_uint32(0), C.c_float(0.0)
         with self.torch.cuda.device(self.device):
-            _lib.check(_lib.lib().vadx_silero_range_flag(self.packed.data_ptr(), 1 if reset else 0, C.byref(flag), C.byref(amax),
-                                                         _lib.stream_ptr()))
+            _lib.check(_lib.lib().vadx_silero_range_flag(self.blob(sampling_rate).data_ptr(), 1 if reset else 0, C.byref(flag),
+                                                         C.byref(amax), _lib.stream_ptr()))
         return int(flag.value), float(amax.value)
 
-    def _guarded(self, run):
+    def _guarded(self, run, sampling_rate=16000):
         """run(mode) -> result.  On "h2" the result stands only if no activation left the fp16 range; otherwise the batch is recomputed on
         "split" (bf16 terms have float32's range).  One 8-byte read-back + stream synchronisation per guarded call."""
-        m = self.mode()
+        m = self.mode(sampling_rate)
         out = run(m)
         if m == "h2":
-            flag, amax = self.range_flag()
+            flag, amax = self.range_flag(sampling_rate=sampling_rate)
             if flag:
                 self.range_fallbacks += 1
                 out = run("split")
@@ -147,13 +211,15 @@ class SileroEngine:
             x = t.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
         return x.to(device=self.device, dtype=t.float32).contiguous()
 
-    def step(self, x, state):
-        """session.run equivalent: x [B,576], state [2,B,128] -> (out [B,1], stateN [2,B,128]) on device."""
+    def step(self, x, state, sampling_rate=16000):
+        """session.run equivalent: x [B,576] ([B,288] at 8000), state [2,B,128] -> (out [B,1], stateN [2,B,128]) on device."""
         t = self.torch
+        win, ctx = _geom(sampling_rate)
+        blob = self.blob(sampling_rate)
         x = self._dev_f32(x)
         state = self._dev_f32(state)
-        if x.dim() != 2 or x.shape[1] != CONTEXT_SIZE + NUM_SAMPLES:
-            raise ValueError(f"input must be [B,{CONTEXT_SIZE + NUM_SAMPLES}], got {tuple(x.shape)}")
+        if x.dim() != 2 or x.shape[1] != ctx + win:
+            raise ValueError(f"input must be [B,{ctx + win}], got {tuple(x.shape)}")
         B = x.shape[0]
         if tuple(state.shape) != (2, B, HIDDEN):
             raise ValueError(f"state must be [2,{B},{HIDDEN}], got {tuple(state.shape)}")
@@ -163,15 +229,17 @@ class SileroEngine:
 
         def run(mode):
             with t.cuda.device(self.device):
-                _lib.check(_lib.lib().vadx_silero_step(self.packed.data_ptr(), x.data_ptr(), state.data_ptr(), 16000, B,
+                _lib.check(_lib.lib().vadx_silero_step(blob.data_ptr(), x.data_ptr(), state.data_ptr(), int(sampling_rate), B,
                                                        out.data_ptr(), state_n.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                       _lib.stream_ptr(), self.cfg(mode)))
+                                                       _lib.stream_ptr(), self.cfg(mode, sampling_rate)))
             return out, state_n
-        return self._guarded(run)
+        return self._guarded(run, sampling_rate)
 
-    def clips(self, audio, n_samples=None, return_state=False):
-        """audio f32 [B,N] (+-1 scale) -> probs [B, ceil(n/512)] on device (zero state/context at t=0)."""
+    def clips(self, audio, n_samples=None, return_state=False, sampling_rate=16000):
+        """audio f32 [B,N] (+-1 scale) -> probs [B, ceil(n/512)] (ceil(n/256) at 8000) on device (zero state/context at t=0)."""
         t = self.torch
+        win, _ = _geom(sampling_rate)
+        blob = self.blob(sampling_rate)
         audio = self._dev_f32(audio)
         if audio.dim() == 1:
             audio = audio.unsqueeze(0)
@@ -181,23 +249,23 @@ class SileroEngine:
         n = int(N if n_samples is None else n_samples)
         if n <= 0 or n > N:
             raise ValueError(f"n_samples={n} outside (0,{N}]")
-        steps = (n + NUM_SAMPLES - 1) // NUM_SAMPLES
+        steps = (n + win - 1) // win
         probs = t.empty((B, steps), dtype=t.float32, device=self.device)
         state_n = t.empty((2, B, HIDDEN), dtype=t.float32, device=self.device) if return_state else None
         if _lib.lib().vadx_silero_workspace_bytes(B, steps) > WORKSPACE_CAP_BYTES:
-            state_n = self.clips_spanned(audio, n, probs, state_n)
+            state_n = self.clips_spanned(audio, n, probs, state_n, sampling_rate=sampling_rate)
             return (probs, state_n) if return_state else probs
         ws = self._workspace(B, steps)
 
         def run(mode):
             with t.cuda.device(self.device):
-                _lib.check(_lib.lib().vadx_silero_clips(self.packed.data_ptr(), audio.data_ptr(), B, n, _lib.row_stride(audio),
+                _lib.check(_lib.lib().vadx_silero_clips(blob.data_ptr(), audio.data_ptr(), B, n, _lib.row_stride(audio),
                                                         probs.data_ptr(), None if state_n is None else state_n.data_ptr(),
-                                                        ws.data_ptr(), ws.numel(), _lib.stream_ptr(), self.cfg(mode)))
+                                                        ws.data_ptr(), ws.numel(), _lib.stream_ptr(), self.cfg(mode, sampling_rate)))
             return (probs, state_n) if return_state else probs
-        return self._guarded(run)
+        return self._guarded(run, sampling_rate)
 
-    def clips_spanned(self, audio, n, probs, state=None, span=None):
+    def clips_spanned(self, audio, n, probs, state=None, span=None, sampling_rate=16000):
         """`clips` for recordings whose whole-clip workspace (32 KB per 16-clip group and window) would not fit: the
         encoder and the recurrent kernel run span by span over windows [first, first + span) on the caller's stream,
         reusing one span-sized workspace, the LSTM state carried in `state` [2,B,128].  Same kernels and arithmetic
@@ -205,7 +273,9 @@ class SileroEngine:
         t = self.torch
         L = _lib.lib()
         B = int(audio.shape[0])
-        steps = (int(n) + NUM_SAMPLES - 1) // NUM_SAMPLES
+        win, _ = _geom(sampling_rate)
+        blob = self.blob(sampling_rate)
+        steps = (int(n) + win - 1) // win
         tile_bytes = L.vadx_silero_workspace_bytes(B, 1)
         if span is None:
             span = max(1, min(steps, WORKSPACE_CAP_BYTES // tile_bytes))
@@ -218,30 +288,31 @@ class SileroEngine:
                 st = _lib.stream_ptr()
                 for first in range(0, steps, span):
                     ns = min(span, steps - first)
-                    _lib.check(L.vadx_silero_encode_span(self.packed.data_ptr(), audio.data_ptr(), B, int(n), _lib.row_stride(audio),
-                                                         first, ns, ws.data_ptr(), ns * tile_bytes, st, self.cfg(mode)))
-                    _lib.check(L.vadx_silero_recur_span(self.packed.data_ptr(), ws.data_ptr(), ns * tile_bytes, B, ns,
+                    _lib.check(L.vadx_silero_encode_span(blob.data_ptr(), audio.data_ptr(), B, int(n), _lib.row_stride(audio),
+                                                         first, ns, ws.data_ptr(), ns * tile_bytes, st, self.cfg(mode, sampling_rate)))
+                    _lib.check(L.vadx_silero_recur_span(blob.data_ptr(), ws.data_ptr(), ns * tile_bytes, B, ns,
                                                         None if first == 0 else state.data_ptr(), probs.data_ptr() + 4 * first,
-                                                        steps, state.data_ptr(), st, self.cfg(mode)))
+                                                        steps, state.data_ptr(), st, self.cfg(mode, sampling_rate)))
             return state
-        return self._guarded(run)
+        return self._guarded(run, sampling_rate)
 
-    def encode(self, audio, n_samples=None, mode=None):
+    def encode(self, audio, n_samples=None, mode=None, sampling_rate=16000):
         """First half of `clips` as its own launch (fills the workspace); returns (batch, steps).  (The separate halves do not run the
         fp16 x 2 range protocol themselves: pair them through `clips*`, or call `range_flag()` before trusting an "h2" result.)"""
         t = self.torch
         B, N = audio.shape
         n = int(N if n_samples is None else n_samples)
-        steps = (n + NUM_SAMPLES - 1) // NUM_SAMPLES
+        win, _ = _geom(sampling_rate)
+        steps = (n + win - 1) // win
         ws = self._workspace(B, steps)
         with t.cuda.device(self.device):
-            _lib.check(_lib.lib().vadx_silero_encode(self.packed.data_ptr(), audio.data_ptr(), B, n, _lib.row_stride(audio),
-                                                     ws.data_ptr(), ws.numel(), _lib.stream_ptr(), self.cfg(mode)))
+            _lib.check(_lib.lib().vadx_silero_encode(self.blob(sampling_rate).data_ptr(), audio.data_ptr(), B, n, _lib.row_stride(audio),
+                                                     ws.data_ptr(), ws.numel(), _lib.stream_ptr(), self.cfg(mode, sampling_rate)))
         return B, steps
 
     PCM16_SCALE = 0.000030517578       # Silero/Inference_Silero_VAD_ONNX.py:83: float32 = int16 * this
 
-    def encode_pcm16(self, pcm, n_samples=None, scale=PCM16_SCALE, mode=None):
+    def encode_pcm16(self, pcm, n_samples=None, scale=PCM16_SCALE, mode=None, sampling_rate=16000):
         """`encode` fed the int16 samples themselves (device tensor [B,N]): the kernel applies the reference's
         int16 -> float32 scaling while staging, bit-identical to encoding `pcm.float() * float32(scale)`."""
         t = self.torch
@@ -249,21 +320,23 @@ class SileroEngine:
             raise ValueError("encode_pcm16 expects a device int16 tensor [B,N]")
         B, N = pcm.shape
         n = int(N if n_samples is None else n_samples)
-        steps = (n + NUM_SAMPLES - 1) // NUM_SAMPLES
+        win, _ = _geom(sampling_rate)
+        steps = (n + win - 1) // win
         self._check_workspace_cap(B, steps, "encode_pcm16")
         ws = self._workspace(B, steps)
         with t.cuda.device(self.device):
-            _lib.check(_lib.lib().vadx_silero_encode_pcm16(self.packed.data_ptr(), pcm.data_ptr(), float(scale), B, n,
+            _lib.check(_lib.lib().vadx_silero_encode_pcm16(self.blob(sampling_rate).data_ptr(), pcm.data_ptr(), float(scale), B, n,
                                                            _lib.row_stride(pcm), ws.data_ptr(), ws.numel(), _lib.stream_ptr(),
-                                                           self.cfg(mode)))
+                                                           self.cfg(mode, sampling_rate)))
         return B, steps
 
-    def clips_pcm16(self, pcm, n_samples=None, scale=PCM16_SCALE):
-        """int16 PCM [B,N] on the device -> probs [B, ceil(n/512)] (encode_pcm16 + recur)."""
+    def clips_pcm16(self, pcm, n_samples=None, scale=PCM16_SCALE, sampling_rate=16000):
+        """int16 PCM [B,N] on the device -> probs [B, ceil(n/512)] (/256 at 8000) (encode_pcm16 + recur)."""
         def run(mode):
-            B, steps = self.encode_pcm16(pcm, n_samples, scale, mode=mode)
-            return self.recur(B, steps, self.torch.empty((B, steps), dtype=self.torch.float32, device=self.device), mode=mode)
-        return self._guarded(run)
+            B, steps = self.encode_pcm16(pcm, n_samples, scale, mode=mode, sampling_rate=sampling_rate)
+            return self.recur(B, steps, self.torch.empty((B, steps), dtype=self.torch.float32, device=self.device), mode=mode,
+                              sampling_rate=sampling_rate)
+        return self._guarded(run, sampling_rate)
 
     def host_feed(self, batch, n_samples, chunk_clips=512):
         """A reusable upload pipeline for `batch` clips of `n_samples` int16 samples held in HOST memory (the host link,
@@ -288,13 +361,13 @@ class SileroEngine:
             return self.recur(B, feed.T, t.empty((B, feed.T), dtype=t.float32, device=self.device), mode=mode)
         return self._guarded(run)
 
-    def recur(self, batch, steps, probs, mode=None):
+    def recur(self, batch, steps, probs, mode=None, sampling_rate=16000):
         """Second half of `clips`: workspace -> probs [B,steps] (zero initial state)."""
         t = self.torch
         ws = self._workspace(batch, steps)
         with t.cuda.device(self.device):
-            _lib.check(_lib.lib().vadx_silero_recur(self.packed.data_ptr(), ws.data_ptr(), ws.numel(), batch, steps,
-                                                    None, probs.data_ptr(), None, _lib.stream_ptr(), self.cfg(mode)))
+            _lib.check(_lib.lib().vadx_silero_recur(self.blob(sampling_rate).data_ptr(), ws.data_ptr(), ws.numel(), batch, steps,
+                                                    None, probs.data_ptr(), None, _lib.stream_ptr(), self.cfg(mode, sampling_rate)))
         return probs
 
     def segments(self, probs, n_samples, cap=64, **kw):
@@ -384,19 +457,19 @@ def seg_params(threshold=0.5, sampling_rate=16000, min_speech_duration_ms=250,
 
 class SileroSession:
     """What the reference's OnnxWrapper holds as `self.session`: run(None, {'input' [B, ctx + n], 'state' [2,B,128], 'sr' int64})
-    -> [out [B,1], stateN [2,B,128]] (utils_vad.py:116-119).  The 16 kHz sub-graph (576-sample input) runs on the HIP engine;
-    the upstream file's 8 kHz sub-graph (288-sample input, 128-point STFT, 65-channel first conv) is a different network
-    whose weights only exist inside the un-vendored silero_vad.onnx -- it is not built, and asking for it fails loudly."""
+    -> [out [B,1], stateN [2,B,128]] (utils_vad.py:116-119).  sr = 16000 runs the 16 kHz sub-graph (576-sample input), sr = 8000 the 8 kHz
+    one (288-sample input, 128-point STFT, 65-channel first conv: csrc/silero8k.hip) when the engine holds its weights (`has_8k`);
+    otherwise an 8000 Hz call fails loudly."""
 
     def __init__(self, engine):
         self.engine = engine
 
     def run(self, output_names, feeds):
         sr = int(np.asarray(feeds["sr"]))
-        if sr != 16000:
-            raise ValueError(f"sr={sr}: only the 16 kHz sub-graph of the Silero network is built on the HIP path "
-                             "(the wrapper and the segmenter handle 8000 Hz; the 8 kHz network itself is not implemented)")
-        out, state = self.engine.step(feeds["input"], feeds["state"])
+        if sr != 16000 and not (sr == 8000 and self.engine.has_8k):
+            raise ValueError(f"sr={sr}: only the 16 kHz sub-graph of the Silero network is loaded on the HIP path "
+                             "(the engine has no 8 kHz weights: SileroEngine(..., weights_8k=...))")
+        out, state = self.engine.step(feeds["input"], feeds["state"], sampling_rate=sr)
         return [out, state]
 
 
@@ -412,7 +485,7 @@ class OnnxWrapper:
             warnings.warn("This model support only 16000 sampling rate!")
             self.sample_rates = [16000]
         else:
-            self.sample_rates = [8000, 16000]        # utils_vad.py:63-67; an 8000 Hz call reaches SileroSession.run, which refuses it
+            self.sample_rates = [8000, 16000]        # utils_vad.py:63-67; an 8000 Hz call reaches SileroSession.run (8 kHz net or refusal)
 
     def _validate_input(self, x, sr: int):
         if x.dim() == 1:
@@ -464,13 +537,21 @@ class OnnxWrapper:
         return out.cpu() if t.is_tensor(out) else t.as_tensor(np.asarray(out))
 
     def audio_forward(self, x, sr: int):
-        """Whole clips in ONE device call at 16 kHz (the reference loops window by window, utils_vad.py:130-146; at 8000 Hz
-        this does too, through `__call__`, so a substituted session sees exactly the reference's feeds)."""
+        """Whole clips in ONE device call (the reference loops window by window, utils_vad.py:130-146).  At 8000 Hz that needs the
+        wrapper's own session over an engine with the 8 kHz network; otherwise this loops through `__call__` as the reference does, so a
+        substituted session sees exactly the reference's feeds."""
         t = self.torch
         if not t.is_tensor(x):
             x = t.as_tensor(np.asarray(x, dtype=np.float32))
         x, sr = self._validate_input(x, sr)
         self.reset_states()
+        if sr == 8000 and type(self.session) is SileroSession and self.session.engine is self.engine and self.engine.has_8k:
+            probs, state = self.engine.clips(x, return_state=True, sampling_rate=8000)
+            pad = (-x.shape[1]) % 256
+            xp = t.nn.functional.pad(x.to(self.engine.device, t.float32), (0, pad))
+            self._state, self._context = state, xp[:, -32:]
+            self._last_sr, self._last_batch_size = sr, x.shape[0]
+            return probs.cpu()
         if sr != 16000:
             num_samples = 256
             if x.shape[1] % num_samples:
@@ -567,7 +648,7 @@ class VADIterator:
 
 class VADIteratorBatch:
     """`streams` live Silero streams on the device (vadx_silero_stream_run): every call advances each stream by k windows of 512
-    samples; context, LSTM state and VADIterator machine of every stream stay in a device record (two, ping-ponged), and the start /
+    samples (256 at 8 kHz); context, LSTM state and VADIterator machine of every stream stay in a device record (two, ping-ponged), and the start /
     end events come back from the device.  Per stream, the scores are bit for bit what `SileroEngine.clips` gives for the concatenated
     audio.  On "h2" every tick reads the range flag and, when it is raised, recomputes the tick on "split" from the same record."""
 
@@ -578,9 +659,9 @@ class VADIteratorBatch:
             raise TypeError("VADIteratorBatch needs a vadx.silero.OnnxWrapper or SileroEngine")
         if sampling_rate not in [8000, 16000]:
             raise ValueError("VADIterator does not support sampling rates other than [8000, 16000]")
-        if sampling_rate != 16000:
-            raise ValueError(f"sr={sampling_rate}: only the 16 kHz sub-graph of the Silero network is built on the HIP path "
-                             "(the 8 kHz network itself is not implemented)")
+        if sampling_rate != 16000 and not self.engine.has_8k:
+            raise ValueError(f"sr={sampling_rate}: only the 16 kHz sub-graph of the Silero network is loaded on the HIP path "
+                             "(the engine has no 8 kHz weights: SileroEngine(..., weights_8k=...))")
         self.streams = int(streams)
         if self.streams <= 0:
             raise ValueError(f"streams={streams} must be positive")
@@ -626,8 +707,9 @@ class VADIteratorBatch:
             if not x.is_floating_point():
                 raise ValueError(f"samples must be float32 or int16, got {x.dtype}")
             x = x.to(t.float32)
-        if x.dim() != 2 or x.shape[0] != self.streams or x.shape[1] == 0 or x.shape[1] % NUM_SAMPLES:
-            raise ValueError(f"samples must be [{self.streams}, k*{NUM_SAMPLES}], got {tuple(x.shape)}")
+        win, _ = _geom(self.sampling_rate)
+        if x.dim() != 2 or x.shape[0] != self.streams or x.shape[1] == 0 or x.shape[1] % win:
+            raise ValueError(f"samples must be [{self.streams}, k*{win}], got {tuple(x.shape)}")
         return x.to(self.engine.device).contiguous()
 
     def _mask(self, m, name):
@@ -640,12 +722,13 @@ class VADIteratorBatch:
         return self.engine.torch.from_numpy(a.astype(np.uint8)).to(self.engine.device)
 
     def step(self, x, active=None):
-        """x [S, k*512] (float32 on the +-1 scale, or int16 PCM; host or device, numpy or torch) -> device tensors
+        """x [S, k*512] ([S, k*256] at 8 kHz; float32 on the +-1 scale, or int16 PCM; host or device, numpy or torch) -> device tensors
         (kind int8 [S,k], value float64 [S,k], probs float32 [S,k]); kind 0 none / 1 start / 2 end / -1 score not finite,
         value the sample position before int().  active (bool [S], None = all): False = no audio for that stream this tick."""
         eng, t = self.engine, self.engine.torch
         x = self._samples(x)
-        S, k = self.streams, x.shape[1] // NUM_SAMPLES
+        win, _ = _geom(self.sampling_rate)
+        S, k = self.streams, x.shape[1] // win
         act_h = None if active is None else self._mask(active, "active")
         act_d = None if act_h is None else self._dev_u8(act_h)
         applied = self._pending if act_h is None else (self._pending & act_h)
@@ -662,13 +745,13 @@ class VADIteratorBatch:
 
         def run(mode):
             with t.cuda.device(eng.device):
-                _lib.check(L.vadx_silero_stream_run(eng.packed.data_ptr(), C.byref(self._prm), x.data_ptr(), 1 if pcm else 0,
-                                                    eng.PCM16_SCALE, k * NUM_SAMPLES, S, k,
+                _lib.check(L.vadx_silero_stream_run(eng.blob(self.sampling_rate).data_ptr(), C.byref(self._prm), x.data_ptr(),
+                                                    1 if pcm else 0, eng.PCM16_SCALE, k * win, S, k,
                                                     None if reset_d is None else reset_d.data_ptr(),
                                                     None if act_d is None else act_d.data_ptr(), src.data_ptr(), dst.data_ptr(),
                                                     probs.data_ptr(), kind.data_ptr(), value.data_ptr(), self._ws.data_ptr(),
-                                                    self._ws.numel(), _lib.stream_ptr(), eng.cfg(mode)))
-        eng._guarded(run)
+                                                    self._ws.numel(), _lib.stream_ptr(), eng.cfg(mode, self.sampling_rate)))
+        eng._guarded(run, self.sampling_rate)
         self._cur = 1 - self._cur
         self._pending &= ~applied
         return kind, value, probs
@@ -708,7 +791,7 @@ def load_silero_vad(onnx=True, opset_version=16, use_cpu=True, path="", device="
     """Constructor of the boundary object (reference signature; `use_cpu` is accepted and ignored: this build runs on the
     MI355X only).  `path` = the silero_vad.onnx the reference would hand to onnxruntime (its initialisers are read by
     vadx.onnx_reader), a .npz of arrays, or "synthetic:<seed>"; the reference's `path=""` default (the pip package's bundled
-    file) cannot be honoured here and raises."""
+    file) cannot be honoured here and raises.  An .onnx file's 8 kHz branch is loaded too, so the model serves sr = 8000 as well."""
     if onnx and opset_version not in (15, 16):
         raise Exception("Available ONNX opset_version: [15, 16]")
     return OnnxWrapper(path or None, force_onnx_cpu=use_cpu, device=device)
@@ -754,9 +837,9 @@ def get_speech_timestamps_batch(audio, model, lengths=None, threshold: float = 0
         warnings.warn("Sampling rate is a multiply of 16000, casting to 16000 manually!")
     if sampling_rate not in (8000, 16000):
         raise ValueError("Currently silero VAD models support 8000 and 16000 (or multiply of 16000) sample rates")
-    if sampling_rate == 8000:
-        raise ValueError("sampling_rate=8000: only the 16 kHz sub-graph of the Silero network is built on the HIP path; "
-                         "window probabilities from elsewhere can be segmented with segments_from_probs(..., sampling_rate=8000)")
+    if sampling_rate == 8000 and not engine.has_8k:
+        raise ValueError("sampling_rate=8000: only the 16 kHz sub-graph of the Silero network is loaded on the HIP path (the engine has no "
+                         "8 kHz weights); window probabilities from elsewhere can be segmented with segments_from_probs(..., sampling_rate=8000)")
     B, N = audio.shape
     if N == 0:           # empty audio: the reference's chunk loop never runs and it returns [] (utils_vad.py:330-344)
         res = [[] for _ in range(B)]
@@ -772,7 +855,7 @@ def get_speech_timestamps_batch(audio, model, lengths=None, threshold: float = 0
         if lens.min() != N:      # zero everything past each clip's end (the reference zero-pads the last window)
             mask = t.arange(N, device=engine.device).unsqueeze(0) < t.as_tensor(lens, device=engine.device).unsqueeze(1)
             audio = audio * mask
-    probs = engine.clips(audio, n_samples=int(lens.max()))
+    probs = engine.clips(audio, n_samples=int(lens.max()), sampling_rate=sampling_rate)
     segs, counts = engine.segments(probs, lens, threshold=threshold, sampling_rate=sampling_rate,
                                    min_speech_duration_ms=min_speech_duration_ms,
                                    max_speech_duration_s=max_speech_duration_s,

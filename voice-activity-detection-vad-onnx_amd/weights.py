@@ -58,12 +58,38 @@ def silero_synthetic(seed=1234):
     return w
 
 
-def silero_check(w):
-    """Shape/dtype validation of a Silero weight dict (raises ValueError)."""
-    want = {"stft_basis": (258, 256), "lstm_w_ih": (512, 128), "lstm_w_hh": (512, 128),
+def silero8k_stft_basis():
+    """[130,128] hann-windowed real DFT basis of the 8 kHz sub-network, filter 128 / hop 64: rows 0..64 = cos, rows 65..129 = -sin
+    (the layout of silero_stft_basis at n = 128)."""
+    n = 128
+    k = np.arange(65, dtype=np.float64)[:, None]
+    t = np.arange(n, dtype=np.float64)[None, :]
+    win = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n, dtype=np.float64) / n)     # periodic hann
+    ang = 2.0 * np.pi * k * t / n
+    basis = np.concatenate([np.cos(ang), -np.sin(ang)], axis=0) * win[None, :]
+    return basis.astype(np.float32)
+
+
+def silero8k_synthetic(seed=1234):
+    """Seeded weights of the 8 kHz sub-network (65-channel first conv on a 128-point STFT, the rest shaped as the 16 kHz network).
+    conv2 .. the decoder are silero_synthetic(seed + 7919) -- the same tags, another seed, so other values than the 16 kHz network of
+    the same seed; the first conv has tags of its own and is scaled so that burst_clips(..., sample_rate=8000) crosses both the 0.5 and
+    the 0.35 thresholds, as the 16 kHz synthetic weights do."""
+    w = silero_synthetic(seed + 7919)
+    w["stft_basis"] = silero8k_stft_basis()
+    w["enc0_w"] = (_normal(seed, "enc0_w_8k", (128, 65, 3), 1.6 / np.sqrt(3 * 65)) * np.float32(2.0)).astype(np.float32)
+    w["enc0_b"] = _normal(seed, "enc0_b_8k", (128,), 0.05)
+    return w
+
+
+def silero_check(w, sample_rate=16000):
+    """Shape/dtype validation of a Silero weight dict (raises ValueError); sample_rate 8000 checks the 8 kHz network's shapes."""
+    if sample_rate not in (8000, 16000):
+        raise ValueError(f"silero weights: sample_rate must be 8000 or 16000, got {sample_rate}")
+    want = {"stft_basis": (258, 256) if sample_rate == 16000 else (130, 128), "lstm_w_ih": (512, 128), "lstm_w_hh": (512, 128),
             "lstm_b_ih": (512,), "lstm_b_hh": (512,), "dec_w": (128,), "dec_b": (1,)}
     for i, (ci, co, _s) in enumerate(SILERO_ENC):
-        want[f"enc{i}_w"] = (co, ci, 3)
+        want[f"enc{i}_w"] = (co, 65 if (i == 0 and sample_rate == 8000) else ci, 3)
         want[f"enc{i}_b"] = (co,)
     for k, shp in want.items():
         if k not in w:
