@@ -175,3 +175,100 @@ def test_silero_8k_onnx_loader_without_the_branch(tmp_path):
     other.write_bytes(b"")
     with pytest.raises(ValueError, match="neither a .onnx"):
         checkpoints.resolve("silero8k", str(other))
+
+
+# ------------------------------------------------------------------ every split section of both blobs, rebuilt from the weights
+def _b3(w):
+    """bf16 x 3 (csrc/split3.h): the three truncation-exact terms of w, w - t0, w - t0 - t1 as bf16 bit patterns [3][...]"""
+    def top(x):
+        return (x.view(np.uint32) & np.uint32(0xffff0000)).view(np.float32)
+    t0 = top(w)
+    r1 = w - t0
+    t1 = top(r1)
+    return np.stack([(x.view(np.uint32) >> 16).astype(np.uint16) for x in (t0, t1, r1 - t1)])
+
+
+def _h2(w):
+    """fp16 x 2 (csrc/split2.h): h0 = RN16(w), h1 = RN16((w - h0) * 2^11) as fp16 bit patterns [2][...]"""
+    h0 = w.astype(np.float16)
+    h1 = ((w - h0.astype(np.float32)) * np.float32(2048.0)).astype(np.float16)
+    return np.stack([h0, h1]).view(np.uint16)
+
+
+def _section(view, split):
+    """view [n0][n1][n2][16 rows][32 k] float32 -> the section [n0][n1][n2][plane][q][i][8] (k = 8 q + e) as 16-bit words"""
+    v = np.ascontiguousarray(view, dtype=np.float32)
+    planes = split(v).reshape((-1,) + v.shape[:3] + (16, 4, 8))             # plane, n0, n1, n2, i, q, e
+    return planes.transpose(1, 2, 3, 0, 5, 4, 6).reshape(-1)
+
+
+def _shared_views(w):
+    """conv2 .. W_hh as [section order ..][16][32] (csrc/silero_common.h documents the order per offset)"""
+    ih = w["lstm_w_ih"].reshape(4, 8, 16, 4, 32)                           # gate, unit tile, i, chunk, k
+    hh = w["lstm_w_hh"].reshape(4, 8, 16, 4, 32)
+    return {"2": w["enc1_w"].reshape(4, 16, 4, 32, 3).transpose(0, 2, 4, 1, 3),                  # [oc tile][chunk][tap]
+            "3": w["enc2_w"][:, :, 1:].reshape(4, 16, 2, 32, 2).transpose(0, 4, 2, 1, 3),       # [oc tile][tap 1, 2][chunk]
+            "4": w["enc3_w"][:, :, 1].reshape(8, 16, 2, 32).transpose(0, 2, 1, 3)[:, :, None],    # [oc tile][chunk], centre tap
+            "IH": ih.transpose(1, 3, 0, 2, 4),                                                   # [unit tile][chunk][gate]
+            "HH": hh.transpose(1, 0, 3, 2, 4)}                                                   # [unit tile][gate][chunk]
+
+
+def _folded_stft_view(basis):
+    """the folded 16 kHz STFT basis [5 bin tiles][E|O x re|im][2 chunks][16][32] in the packer's own float32 arithmetic: bins 0..63 symmetrised
+    over the four table entries that must agree, bin 64 (tile 4, row 0) time-folded; pair m of a class = sample n = 2 m + 2 (E) / 2 m + 1 (O)"""
+    re, im = basis[:129], basis[129:]
+    q, h = np.float32(0.25), np.float32(0.5)
+    out = np.zeros((80, 2, 2, 64), np.float32)                             # bin, class, re | im, pair
+    k = np.arange(64)
+    for cls in range(2):
+        for m in range(64):
+            n = 2 * m + 1 if cls else 2 * m + 2
+            sg, nm = np.float32(-1.0 if n & 1 else 1.0), (256 - n) & 255
+            c = q * (re[k, n] + re[k, nm] + sg * (re[128 - k, n] + re[128 - k, nm]))
+            s = q * (im[k, n] - im[k, nm] - sg * (im[128 - k, n] - im[128 - k, nm]))
+            out[:64, cls, 0, m] = h * c if n == 128 else c                 # n = 128 is its own mirror
+            out[:64, cls, 1, m] = 0.0 if n == 128 else s
+            out[64, cls, 0, m] = (h if n == 128 else np.float32(1.0)) * h * (re[64, n] + re[64, nm])
+            out[64, cls, 1, m] = 0.0 if n == 128 else h * (im[64, n] - im[64, 256 - n])
+    return out.reshape(5, 16, 4, 2, 32).transpose(0, 2, 3, 1, 4)
+
+
+def _check_sections(blob, o, expected):
+    """expected: (first offset name, next offset name, view) per section; both layouts of every view, bitwise, each filling its section"""
+    words = blob.view(np.uint16)
+    for lo, hi, view, split in expected:
+        want = _section(view, split)
+        assert want.size == 2 * (o[hi] - o[lo]), (lo, hi, want.size)
+        got = words[2 * o[lo]:2 * o[hi]]
+        assert got.any() and np.array_equal(got, want), (lo, hi)
+
+
+def test_every_split_section_is_the_documented_layout_of_its_weights():
+    """Every bf16 x 3 (OFF_Q*, OFF8_*Q) and fp16 x 2 (OFF_H*, OFF8_*H) section of the 16 kHz and the 8 kHz blob, rebuilt in numpy from the
+    tensors it was packed from ([.. section order ..][plane][q][i][8], k = 8 q + e) and compared bitwise."""
+    o = _blob_offsets()
+    w16 = weights.silero_synthetic(3)
+    order = np.array([s if s <= 64 else 192 - s for s in range(128)])      # conv1's input slots: the order the STFT pass leaves the bins in
+    c1 = w16["enc0_w"][:, order].reshape(8, 16, 4, 32, 3).transpose(0, 2, 4, 1, 3)                # [oc tile][chunk][tap]
+    sf = _folded_stft_view(w16["stft_basis"])
+    sv = _shared_views(w16)
+    expected = [("OFF_Q1", "OFF_Q1N", c1, _b3), ("OFF_QSF", "OFF_H1", sf[:4], _b3), ("OFF_H1", "OFF_H2", c1, _h2), ("OFF_HSF", "OFF_HFLAG", sf, _h2)]
+    nxt = {"2": "3", "3": "4", "4": "IH", "IH": "HH"}
+    for name, view in sv.items():
+        expected += [(f"OFF_Q{name}", f"OFF_Q{nxt[name]}" if name in nxt else "OFF_QSF", view, _b3),
+                     (f"OFF_H{name}", f"OFF_H{nxt[name]}" if name in nxt else "OFF_HSF", view, _h2)]
+    assert len(expected) == 14
+    _check_sections(silero._pack(w16, 16000), o, expected)
+
+    w8 = weights.silero8k_synthetic(3)
+    b = w8["stft_basis"]
+    rows = np.zeros((144, 128), np.float32)                                # tiles 0..3 re of bins 0..63, 4..7 im, 8 = re / im of bin 64 in rows 0 / 1
+    rows[:64], rows[64:128], rows[128], rows[129] = b[:64], b[65:129], b[64], b[129]
+    st = rows.reshape(9, 16, 4, 32).transpose(0, 2, 1, 3)[:, :, None]                             # [row tile][chunk]
+    c1 = w8["enc0_w"][:, :64].reshape(8, 16, 2, 32, 3).transpose(0, 4, 2, 1, 3)                   # [oc tile][tap][chunk]
+    expected = [("OFF8_SQ", "OFF8_SH", st, _b3), ("OFF8_SH", "OFF8_C1F", st, _h2), ("OFF8_C1Q", "OFF8_C1H", c1, _b3), ("OFF8_C1H", "OFF8_C1N", c1, _h2)]
+    for name, view in _shared_views(w8).items():
+        expected += [(f"OFF_Q{name}", f"OFF_Q{nxt[name]}" if name in nxt else "OFF_QSF", view, _b3),
+                     (f"OFF_H{name}", f"OFF_H{nxt[name]}" if name in nxt else "OFF_HSF", view, _h2)]
+    assert len(expected) == 14
+    _check_sections(silero._pack(w8, 8000), o, expected)

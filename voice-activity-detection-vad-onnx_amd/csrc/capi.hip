@@ -1,6 +1,6 @@
 // capi.hip -- error plumbing and the weight-layout helper shared by every libvadx entry point.
 #include "common.h"
-#include "split2.h"
+#include "pack.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -29,8 +29,7 @@ extern "C" int vadx_frag_major_host(const float *src, int rows, int cols, float 
     const int ldw = (cols + 15) & ~15;
     const size_t n = vadx_frag_major_floats(rows, cols);
     for (size_t e = 0; e < n; ++e) dst[e] = 0.f;
-    for (int r = 0; r < rows; ++r)
-        for (int k = 0; k < cols; ++k) dst[vadx::frag_index(ldw, r, k)] = src[(size_t)r * cols + k];
+    vadx::pack::f32(dst, ldw, rows, cols, vadx::pack::rowmajor(src, rows, cols));
     return VADX_OK;
 }
 
@@ -47,17 +46,13 @@ extern "C" size_t vadx_frag_h2_floats(int rows, int cols) {
 extern "C" int vadx_frag_h2_host(const float *src, int rows, int cols, int k_order, float *dst, float *wmax_out) {
     VADX_REQUIRE(src && dst && rows > 0 && cols > 0, "vadx_frag_h2_host: bad argument");
     VADX_REQUIRE(k_order == VADX_H2_K_PLAIN || k_order == VADX_H2_K_QUARTER, "vadx_frag_h2_host: k_order must be VADX_H2_K_PLAIN or VADX_H2_K_QUARTER");
-    const size_t n = vadx_frag_h2_floats(rows, cols);
     const int nch = (cols + 31) / 32;
-    memset(dst, 0, n * sizeof(float));
     float wmax = 0.f;
-    for (int r = 0; r < rows; ++r)
-        for (int k = 0; k < cols; ++k) {
-            const int kk = k & 31, q = (kk >> 2) & 3, e = ((kk >> 4) << 2) | (kk & 3);
-            const float a = vadx::hfrag_put(dst + (size_t)(((r / 16) * nch + k / 32) * 2) * vadx::HFRAG, r % 16,
-                                            k_order == VADX_H2_K_QUARTER ? 8 * q + e : kk, src[(size_t)r * cols + k]);
-            if (!(a <= wmax)) wmax = a;
-        }
+    const auto w = vadx::pack::rowmajor(src, rows, cols);
+    if (k_order == VADX_H2_K_QUARTER)       // fragment position 8 q + e of a chunk holds its k = 16 (e >> 2) + 4 q + (e & 3)
+        vadx::pack::split<vadx::SchemeH2>(dst, (rows + 15) / 16, nch, [&](int r, int c) { return w(r, (c & ~31) + 16 * ((c & 7) >> 2) + 4 * ((c & 31) >> 3) + (c & 3)); }, wmax);
+    else
+        vadx::pack::split<vadx::SchemeH2>(dst, (rows + 15) / 16, nch, w, wmax);
     if (wmax_out) *wmax_out = wmax;
     VADX_REQUIRE(wmax <= vadx::H_MAX, "vadx_frag_h2_host: a weight (|w| = %g) is outside the fp16 range: keep this matrix on VADX_ARITH_F32", (double)wmax);
     return VADX_OK;

@@ -11,7 +11,7 @@
 #include "rebalance.h"
 #include "common.h"
 #include "layers.h"
-#include "split_scheme.h"
+#include "pack.h"
 
 #include <math.h>
 #include <string.h>
@@ -659,6 +659,7 @@ __global__ void vadpost_kernel(PostDev q, const float *__restrict__ probs, int s
 }  // namespace vadx
 
 using namespace vadx::firered;
+namespace pack = vadx::pack;
 
 extern "C" size_t vadx_firered_packed_floats(const vadx_firered_cfg *cfg) {
     Dev d;
@@ -671,9 +672,6 @@ extern "C" int vadx_firered_pack_host(const vadx_firered_cfg *cfg, const vadx_fi
     VADX_REQUIRE(cfg && w_in && p, "vadx_firered_pack_host: NULL argument");
     VADX_REQUIRE(derive(cfg, &d) == 0, "vadx_firered_pack_host: unsupported config (idim 80, H<=256, P<=128, frames<=112, odim<=4)");
     memset(p, 0, sizeof(float) * d.total);
-    auto mat = [&](int off, const float *src, int rows, int cols, int ld) {
-        for (int r = 0; r < rows; ++r) memcpy(p + off + (size_t)r * ld, src + (size_t)r * cols, cols * sizeof(float));
-    };
     VADX_REQUIRE(w_in->fc1_w && w_in->fc1_b && w_in->fc2_w && w_in->fc2_b && w_in->out_w && w_in->out_b, "vadx_firered_pack_host: NULL weight pointer");
     for (int r = 1; r < d.R; ++r)
         VADX_REQUIRE(w_in->blk_fc1_w[r] && w_in->blk_fc1_b[r] && w_in->blk_fc2_w[r], "vadx_firered_pack_host: NULL block %d weight", r);
@@ -709,8 +707,8 @@ extern "C" int vadx_firered_pack_host(const vadx_firered_cfg *cfg, const vadx_fi
         w_reb.out_w = r_out.data(); w_reb.out_b = r_outb.data();
     }
     const vadx_firered_weights_host *w = &w_reb;
-    mat(d.off_fc1, w->fc1_w, d.H, NMEL, NMEL); memcpy(p + d.off_fc1b, w->fc1_b, d.H * sizeof(float));
-    mat(d.off_fc2, w->fc2_w, d.P, d.H, d.Hp); memcpy(p + d.off_fc2b, w->fc2_b, d.P * sizeof(float));
+    pack::rows_ld(p + d.off_fc1, w->fc1_w, d.H, NMEL, NMEL); memcpy(p + d.off_fc1b, w->fc1_b, d.H * sizeof(float));
+    pack::rows_ld(p + d.off_fc2, w->fc2_w, d.P, d.H, d.Hp); memcpy(p + d.off_fc2b, w->fc2_b, d.P * sizeof(float));
     for (int r = 0; r < d.R; ++r) {
         VADX_REQUIRE(w->fsmn_lb[r] && (d.N2 == 0 || w->fsmn_la[r]), "vadx_firered_pack_host: NULL FSMN filter %d", r);
         memcpy(p + d.off_lb[r], w->fsmn_lb[r], (size_t)d.P * d.N1 * sizeof(float));
@@ -722,16 +720,16 @@ extern "C" int vadx_firered_pack_host(const vadx_firered_cfg *cfg, const vadx_fi
             }
         if (r > 0) {
             VADX_REQUIRE(w->blk_fc1_w[r] && w->blk_fc1_b[r] && w->blk_fc2_w[r], "vadx_firered_pack_host: NULL block %d weight", r);
-            mat(d.off_bfc1[r], w->blk_fc1_w[r], d.H, d.P, d.Pp); memcpy(p + d.off_bfc1b[r], w->blk_fc1_b[r], d.H * sizeof(float));
-            mat(d.off_bfc2[r], w->blk_fc2_w[r], d.P, d.H, d.Hp);
+            pack::rows_ld(p + d.off_bfc1[r], w->blk_fc1_w[r], d.H, d.P, d.Pp); memcpy(p + d.off_bfc1b[r], w->blk_fc1_b[r], d.H * sizeof(float));
+            pack::rows_ld(p + d.off_bfc2[r], w->blk_fc2_w[r], d.P, d.H, d.Hp);
         }
     }
     for (int m = 0; m < d.M; ++m) {
         VADX_REQUIRE(w->dnn_w[m] && w->dnn_b[m], "vadx_firered_pack_host: NULL dnn %d weight", m);
-        mat(d.off_dnn[m], w->dnn_w[m], d.H, m == 0 ? d.P : d.H, m == 0 ? d.Pp : d.Hp);
+        pack::rows_ld(p + d.off_dnn[m], w->dnn_w[m], d.H, m == 0 ? d.P : d.H, m == 0 ? d.Pp : d.Hp);
         memcpy(p + d.off_dnnb[m], w->dnn_b[m], d.H * sizeof(float));
     }
-    mat(d.off_out, w->out_w, d.odim, d.H, d.Hp); memcpy(p + d.off_outb, w->out_b, d.odim * sizeof(float));
+    pack::rows_ld(p + d.off_out, w->out_w, d.odim, d.H, d.Hp); memcpy(p + d.off_outb, w->out_b, d.odim * sizeof(float));
     // GEMM operands go fragment-major (common.h); the FIR taps stay row-major (VALU)
     vadx::frag_major_inplace(p + d.off_out, 16, d.Hp);
     vadx::frag_major_inplace(p + d.off_fc1, d.Hp, NMEL);
@@ -743,28 +741,15 @@ extern "C" int vadx_firered_pack_host(const vadx_firered_cfg *cfg, const vadx_fi
     for (int m = 0; m < d.M; ++m) vadx::frag_major_inplace(p + d.off_dnn[m], d.Hp, m == 0 ? d.Pp : d.Hp);
     if (d.np) {              // split A fragments [n-tile][chunk][np planes][QFRAG] from the ORIGINAL row-major weights, in cfg->arithmetic
         float wmax = 0.f;
-        auto qmat = [&](int off, int rows_p, int nch, const float *W, int rows, int cols) {
-            for (int nt = 0; nt < rows_p / 16; ++nt)
-                for (int kc = 0; kc < nch; ++kc) {
-                    float *f3 = p + off + (size_t)((nt * nch + kc) * d.np) * vadx::QFRAG;
-                    for (int i = 0; i < 16; ++i)
-                        for (int k = 0; k < 32; ++k) {
-                            const int r = 16 * nt + i, c = 32 * kc + k;
-                            const float v = (r < rows && c < cols) ? W[(size_t)r * cols + c] : 0.f;
-                            if (d.np == 3) vadx::SchemeB3::put_host(f3, i, k, v, wmax);
-                            else vadx::SchemeH2::put_host(f3, i, k, v, wmax);
-                        }
-                }
-        };
-        qmat(d.q_fc1, d.Hp, 3, w->fc1_w, d.H, NMEL);
-        qmat(d.q_fc2, d.Pp, 8, w->fc2_w, d.P, d.H);
+        pack::split(d.np, p + d.q_fc1, d.Hp / 16, 3, pack::rowmajor(w->fc1_w, d.H, NMEL), wmax);
+        pack::split(d.np, p + d.q_fc2, d.Pp / 16, 8, pack::rowmajor(w->fc2_w, d.P, d.H), wmax);
         for (int r = 1; r < d.R; ++r) {
-            qmat(d.q_bfc1[r], d.Hp, 4, w->blk_fc1_w[r], d.H, d.P);
-            qmat(d.q_bfc2[r], d.Pp, 8, w->blk_fc2_w[r], d.P, d.H);
+            pack::split(d.np, p + d.q_bfc1[r], d.Hp / 16, 4, pack::rowmajor(w->blk_fc1_w[r], d.H, d.P), wmax);
+            pack::split(d.np, p + d.q_bfc2[r], d.Pp / 16, 8, pack::rowmajor(w->blk_fc2_w[r], d.P, d.H), wmax);
         }
         if (d.M == 1) {
-            qmat(d.q_dnn0, d.Hp, 4, w->dnn_w[0], d.H, d.P);
-            qmat(d.q_head, d.Pp, 8, w->out_w, d.odim, d.H);
+            pack::split(d.np, p + d.q_dnn0, d.Hp / 16, 4, pack::rowmajor(w->dnn_w[0], d.H, d.P), wmax);
+            pack::split(d.np, p + d.q_head, d.Pp / 16, 8, pack::rowmajor(w->out_w, d.odim, d.H), wmax);
             memcpy(p + d.off_headb, w->out_b, d.odim * sizeof(float));
         }
         VADX_REQUIRE(d.arith != vadx::VADX_AR_H2 || wmax <= vadx::H_MAX,
@@ -781,14 +766,7 @@ extern "C" int vadx_firered_range_flag(const vadx_firered_cfg *cfg, const float 
     Dev d;
     VADX_REQUIRE(cfg && packed && flag_host, "vadx_firered_range_flag: NULL argument");
     VADX_REQUIRE(derive(cfg, &d) == 0, "vadx_firered_range_flag: unsupported config");
-    uint32_t w[2] = {0, 0};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    VADX_HIP_TRY(hipMemcpyAsync(w, packed + d.off_flag, sizeof(w), hipMemcpyDeviceToHost, st));
-    VADX_HIP_TRY(hipStreamSynchronize(st));
-    if (reset && (w[0] | w[1])) VADX_HIP_TRY(hipMemsetAsync(const_cast<float *>(packed) + d.off_flag, 0, sizeof(w), st));
-    *flag_host = w[0];
-    if (amax_host) memcpy(amax_host, &w[1], sizeof(float));
-    return VADX_OK;
+    return vadx::range_flag_read(packed + d.off_flag, reset, flag_host, amax_host, stream);
 }
 
 extern "C" int vadx_firered_run(const vadx_firered_cfg *cfg, const float *packed, const float *logmel, int windows,

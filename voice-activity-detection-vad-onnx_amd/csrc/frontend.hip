@@ -19,6 +19,7 @@
 // frontend_fold3_kernel: time x frequency fold, opt-in) -- see "Folded DFT" below.
 #include "common.h"
 #include "layers_split.h"
+#include "pack.h"
 
 #include <math.h>
 #include <string.h>
@@ -1357,18 +1358,10 @@ extern "C" int vadx_frontend_pack_host(const vadx_frontend_cfg *cfg, const float
     vadx::frag_major_inplace(packed_host + d.off_mel, d.n_mels, d.Fp);
     if (d.fold == 4 || d.fold == 5) {   // the reference table itself as split fragments (three bf16 planes, exact, or two fp16 planes): [bin tile][re | im][chunk][plane][QFRAG]
         float wmax = 0.f;
-        for (int bt = 0; bt < d.s_nbt; ++bt)
-            for (int part = 0; part < 2; ++part)
-                for (int kc = 0; kc < d.s_nch; ++kc) {
-                    float *f3 = packed_host + d.off_fold + (size_t)(((bt * 2 + part) * d.s_nch + kc) * d.s_np) * vadx::QFRAG;
-                    for (int i = 0; i < 16; ++i)
-                        for (int k = 0; k < 32; ++k) {
-                            const int f = bt * 16 + i, t = 32 * kc + k;
-                            const float v = (f < d.n_bins && t < d.taps) ? (part ? sin_tab : cos_tab)[(size_t)f * n_fft + cfg->tap0 + t] : 0.f;
-                            if (d.s_np == 3) vadx::SchemeB3::put_host(f3, i, k, v, wmax);
-                            else vadx::SchemeH2::put_host(f3, i, k, v, wmax);
-                        }
-                }
+        // rows 32 bt + 16 part + i of the [s_nbt x (re 16 | im 16)] tile stack = bin 16 bt + i of the cos (part 0) / sin (part 1) table
+        vadx::pack::split(d.s_np, packed_host + d.off_fold, 2 * d.s_nbt, d.s_nch, [&](int r, int t) {
+            const int f = (r / 32) * 16 + r % 16;
+            return (f < d.n_bins && t < d.taps) ? ((r & 16) ? sin_tab : cos_tab)[(size_t)f * n_fft + cfg->tap0 + t] : 0.f; }, wmax);
         VADX_REQUIRE(d.fold != 5 || wmax <= vadx::H_MAX, "vadx_frontend_pack_host: a table entry (|.| up to %g) is outside the fp16 range: use fold = 4", wmax);
         int32_t *pi = reinterpret_cast<int32_t *>(packed_host + d.off_plan);
         for (int mt = 0; mt < d.nmt; ++mt) { pi[2 * mt] = mel_kb[2 * mt]; pi[2 * mt + 1] = mel_kb[2 * mt + 1]; }

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "layers.h"
 #include "layers_split.h"
+#include "pack.h"
 
 #include <math.h>
 #include <string.h>
@@ -683,6 +684,7 @@ __global__ __launch_bounds__(ST_THREADS) void fsmn_stats_kernel(const int16_t *_
 
 using namespace vadx::fsmn;
 using vadx::QFRAG;
+namespace pack = vadx::pack;
 
 extern "C" size_t vadx_fsmn_packed_floats(const vadx_fsmn_dims *dims) {
     Dev d;
@@ -695,9 +697,6 @@ extern "C" int vadx_fsmn_pack_host(const vadx_fsmn_dims *dims, const vadx_fsmn_w
     VADX_REQUIRE(dims && w_in && p, "vadx_fsmn_pack_host: NULL argument");
     VADX_REQUIRE(derive(dims, &d) == 0, "vadx_fsmn_pack_host: unsupported dims (affine <= 144, linear/output <= 256)");
     memset(p, 0, sizeof(float) * d.total);
-    auto mat = [&](int off, const float *src, int rows, int cols, int ld) {
-        for (int r = 0; r < rows; ++r) memcpy(p + off + (size_t)r * ld, src + (size_t)r * cols, cols * sizeof(float));
-    };
     VADX_REQUIRE(w_in->in1_w && w_in->in1_b && w_in->in2_w && w_in->in2_b && w_in->out1_w && w_in->out1_b && w_in->out2_w && w_in->out2_b &&
                  w_in->cmvn_means && w_in->cmvn_vars, "vadx_fsmn_pack_host: NULL weight pointer");
     for (int l = 0; l < NLAYER; ++l)
@@ -725,17 +724,17 @@ extern "C" int vadx_fsmn_pack_host(const vadx_fsmn_dims *dims, const vadx_fsmn_w
     w_reb.out1_w = r_out1.data(); w_reb.out1_b = r_out1b.data(); w_reb.out2_w = r_out2.data(); w_reb.out2_b = r_out2b.data();
     for (int l = 0; l < NLAYER; ++l) { w_reb.lin_w[l] = r_lin[l].data(); w_reb.aff_w[l] = r_aff[l].data(); w_reb.aff_b[l] = r_affb[l].data(); }
     const vadx_fsmn_weights_host *w = &w_reb;
-    mat(d.off_in1, w->in1_w, d.A, 400, 400); memcpy(p + d.off_b1, w->in1_b, d.A * sizeof(float));
+    pack::rows_ld(p + d.off_in1, w->in1_w, d.A, 400, 400); memcpy(p + d.off_b1, w->in1_b, d.A * sizeof(float));
     memcpy(p + d.off_mean, w->cmvn_means, 400 * sizeof(float)); memcpy(p + d.off_var, w->cmvn_vars, 400 * sizeof(float));
-    mat(d.off_in2, w->in2_w, d.L, d.A, d.Ap); memcpy(p + d.off_b2, w->in2_b, d.L * sizeof(float));
+    pack::rows_ld(p + d.off_in2, w->in2_w, d.L, d.A, d.Ap); memcpy(p + d.off_b2, w->in2_b, d.L * sizeof(float));
     for (int l = 0; l < NLAYER; ++l) {
         VADX_REQUIRE(w->lin_w[l] && w->fir_w[l] && w->aff_w[l] && w->aff_b[l], "vadx_fsmn_pack_host: NULL layer %d weight", l);
-        mat(d.off_lin[l], w->lin_w[l], PROJ, d.L, d.Lp);
+        pack::rows_ld(p + d.off_lin[l], w->lin_w[l], PROJ, d.L, d.Lp);
         memcpy(p + d.off_fir[l], w->fir_w[l], PROJ * LORDER * sizeof(float));
-        mat(d.off_aff[l], w->aff_w[l], d.L, PROJ, PROJ); memcpy(p + d.off_baff[l], w->aff_b[l], d.L * sizeof(float));
+        pack::rows_ld(p + d.off_aff[l], w->aff_w[l], d.L, PROJ, PROJ); memcpy(p + d.off_baff[l], w->aff_b[l], d.L * sizeof(float));
     }
-    mat(d.off_out1, w->out1_w, d.A2, d.L, d.Lp); memcpy(p + d.off_bo1, w->out1_b, d.A2 * sizeof(float));
-    mat(d.off_out2, w->out2_w, d.O, d.A2, d.A2p); memcpy(p + d.off_bo2, w->out2_b, d.O * sizeof(float));
+    pack::rows_ld(p + d.off_out1, w->out1_w, d.A2, d.L, d.Lp); memcpy(p + d.off_bo1, w->out1_b, d.A2 * sizeof(float));
+    pack::rows_ld(p + d.off_out2, w->out2_w, d.O, d.A2, d.A2p); memcpy(p + d.off_bo2, w->out2_b, d.O * sizeof(float));
     // GEMM operands go fragment-major (common.h): one contiguous 1 KB run per wave-wide weight load
     vadx::frag_major_inplace(p + d.off_in1, d.Ap, 400);
     vadx::frag_major_inplace(p + d.off_in2, d.Lp, d.Ap);
@@ -748,35 +747,23 @@ extern "C" int vadx_fsmn_pack_host(const vadx_fsmn_dims *dims, const vadx_fsmn_w
     // ---- split-product copies (layers_split.h): A fragments [n-tile][chunk][np planes][QFRAG] from the ORIGINAL row-major weights, in the
     // arithmetic dims->arithmetic names (none for float32 MFMAs)
     float wmax = 0.f;                                                  // largest |weight| handed to fp16 fragments
-    auto qmat = [&](int off, int rows, int nch, auto wfn) {            // wfn(row, k) -> weight (0 outside the matrix)
-        if (d.np == 0) return;
-        for (int nt = 0; nt < (rows + 15) / 16; ++nt)
-            for (int kc = 0; kc < nch; ++kc) {
-                float *fr = p + off + (size_t)((nt * nch + kc) * d.np) * vadx::QFRAG;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) {
-                        if (d.np == 3) vadx::SchemeB3::put_host(fr, i, k, wfn(16 * nt + i, 32 * kc + k), wmax);
-                        else vadx::SchemeH2::put_host(fr, i, k, wfn(16 * nt + i, 32 * kc + k), wmax);
-                    }
-            }
-    };
     // in_linear1 with the CMVN folded in (double): W1' = W1 var, b1' = b1 + sum_k W1' (mean_k - mbar_{k % 80}), mbar = the centre LFR position's means
     for (int m = 0; m < NMEL; ++m) p[d.q_mbar + m] = w->cmvn_means[2 * NMEL + m];
-    qmat(d.q_in1, d.Ap, NCH_IN1, [&](int r, int k) {
-        return (r < d.A && k < 400) ? (float)((double)w->in1_w[(size_t)r * 400 + k] * (double)w->cmvn_vars[k]) : 0.f; });
+    pack::split(d.np, p + d.q_in1, d.Ap / 16, NCH_IN1, [&](int r, int k) {
+        return (r < d.A && k < 400) ? (float)((double)w->in1_w[(size_t)r * 400 + k] * (double)w->cmvn_vars[k]) : 0.f; }, wmax);
     for (int r = 0; r < d.A; ++r) {
         double acc = (double)w->in1_b[r];
         for (int k = 0; k < 400; ++k)
             acc += (double)(float)((double)w->in1_w[(size_t)r * 400 + k] * (double)w->cmvn_vars[k]) * ((double)w->cmvn_means[k] - (double)p[d.q_mbar + k % NMEL]);
         p[d.q_b1 + r] = (float)acc;
     }
-    qmat(d.q_in2, d.Lp, d.nch_A, [&](int r, int k) { return (r < d.L && k < d.A) ? w->in2_w[(size_t)r * d.A + k] : 0.f; });
+    pack::split(d.np, p + d.q_in2, d.Lp / 16, d.nch_A, pack::rowmajor(w->in2_w, d.L, d.A), wmax);
     for (int l = 0; l < NLAYER; ++l) {
-        qmat(d.q_lin[l], PROJ, d.nch_L, [&](int r, int k) { return k < d.L ? w->lin_w[l][(size_t)r * d.L + k] : 0.f; });
-        qmat(d.q_aff[l], d.Lp, PROJ / 32, [&](int r, int k) { return r < d.L ? w->aff_w[l][(size_t)r * PROJ + k] : 0.f; });
+        pack::split(d.np, p + d.q_lin[l], PROJ / 16, d.nch_L, pack::rowmajor(w->lin_w[l], PROJ, d.L), wmax);
+        pack::split(d.np, p + d.q_aff[l], d.Lp / 16, PROJ / 32, pack::rowmajor(w->aff_w[l], d.L, PROJ), wmax);
     }
-    qmat(d.q_out1, d.A2p, d.nch_L, [&](int r, int k) { return (r < d.A2 && k < d.L) ? w->out1_w[(size_t)r * d.L + k] : 0.f; });
-    qmat(d.q_out2, d.Op, d.nch_A2, [&](int r, int k) { return (r < d.O && k < d.A2) ? w->out2_w[(size_t)r * d.A2 + k] : 0.f; });
+    pack::split(d.np, p + d.q_out1, d.A2p / 16, d.nch_L, pack::rowmajor(w->out1_w, d.A2, d.L), wmax);
+    pack::split(d.np, p + d.q_out2, d.Op / 16, d.nch_A2, pack::rowmajor(w->out2_w, d.O, d.A2), wmax);
     VADX_REQUIRE(d.arith != vadx::VADX_AR_H2 || wmax <= vadx::H_MAX,
                  "vadx_fsmn_pack_host: a weight (|w| up to %g) is outside the fp16 range: pack with dims->arithmetic = VADX_ARITH_BF16X3", wmax);
     VADX_REQUIRE(d.arith != vadx::VADX_AR_H2 || reb_min >= vadx::REB_REFUSE,
@@ -790,14 +777,7 @@ extern "C" int vadx_fsmn_range_flag(const vadx_fsmn_dims *dims, const float *pac
     Dev d;
     VADX_REQUIRE(dims && packed && flag_host, "vadx_fsmn_range_flag: NULL argument");
     VADX_REQUIRE(derive(dims, &d) == 0, "vadx_fsmn_range_flag: unsupported dims");
-    uint32_t w[2] = {0, 0};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    VADX_HIP_TRY(hipMemcpyAsync(w, packed + d.off_flag, sizeof(w), hipMemcpyDeviceToHost, st));
-    VADX_HIP_TRY(hipStreamSynchronize(st));
-    if (reset && (w[0] | w[1])) VADX_HIP_TRY(hipMemsetAsync(const_cast<float *>(packed) + d.off_flag, 0, sizeof(w), st));
-    *flag_host = w[0];
-    if (amax_host) memcpy(amax_host, &w[1], sizeof(float));
-    return VADX_OK;
+    return vadx::range_flag_read(packed + d.off_flag, reset, flag_host, amax_host, stream);
 }
 
 static int set_lds_attr() {

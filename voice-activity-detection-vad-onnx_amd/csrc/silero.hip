@@ -11,9 +11,7 @@
 //       in the VGPRs of its 8 waves for all T steps; h is exchanged through double-buffered LDS.
 //   silero_segments_kernel: get_speech_timestamps' state machine, one clip per thread.
 #include "silero_common.h"
-#include "rebalance.h"
-#include "split3.h"
-#include "split2.h"
+#include "split_scheme.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -769,271 +767,10 @@ __global__ void silero_segments_kernel(const float *__restrict__ probs, int B, i
 using namespace vadx::silero;
 using vadx::FRAG;
 
-extern "C" size_t vadx_silero_packed_floats(void) { return (size_t)PACKED_FLOATS; }
-
-// Every section the 16 kHz and 8 kHz networks share (conv2..4, W_ih, W_hh in all three layouts, their biases, the decoder), from the
-// rebalanced weights; hmax / reb_min collect what the fp16 x 2 refusal rule needs (see vadx_silero_pack_host)
-void vadx::silero::silero_pack_shared(const vadx_silero_weights_host *w, float *p, float &hmax, int &reb_min) {
-    auto frag = [](size_t base, int i, int k) { return base + ((size_t)(k / 16) * 64 + ((k % 16) / 4) * 16 + i) * 4 + (k % 4); };
-    for (int co = 0; co < 64; ++co)
-        for (int kk = 0; kk < 3; ++kk)
-            for (int ci = 0; ci < 128; ++ci)
-                p[frag(OFF_C2 + (size_t)(co / 16) * 24 * FRAG, co % 16, kk * 128 + ci)] = w->enc_w[1][((size_t)co * 128 + ci) * 3 + kk];
-    memcpy(p + OFF_B2, w->enc_b[1], 64 * sizeof(float));
-    for (int co = 0; co < 64; ++co)
-        for (int ps = 0; ps < 2; ++ps)
-            for (int ci = 0; ci < 64; ++ci)
-                p[frag(OFF_C3 + (size_t)(co / 16) * 8 * FRAG, co % 16, ps * 64 + ci)] = w->enc_w[2][((size_t)co * 64 + ci) * 3 + (ps + 1)];
-    memcpy(p + OFF_B3, w->enc_b[2], 64 * sizeof(float));
-    for (int co = 0; co < 128; ++co)
-        for (int ci = 0; ci < 64; ++ci)
-            p[frag(OFF_C4 + (size_t)(co / 16) * 4 * FRAG, co % 16, ci)] = w->enc_w[3][((size_t)co * 64 + ci) * 3 + 1];
-    memcpy(p + OFF_B4, w->enc_b[3], 128 * sizeof(float));
-    for (int r = 0; r < 512; ++r)          // row r = gate*128 + unit; tile = gate*8 + unit/16
-        for (int k = 0; k < 128; ++k) p[frag(OFF_IH + (size_t)(r / 16) * 8 * FRAG, r % 16, k)] = w->lstm_w_ih[(size_t)r * 128 + k];
-    for (int r = 0; r < 512; ++r) p[OFF_BG + r] = w->lstm_b_ih[r] + w->lstm_b_hh[r];
-    memcpy(p + OFF_HH, w->lstm_w_hh, 512 * 128 * sizeof(float));
-    memcpy(p + OFF_DW, w->dec_w, 128 * sizeof(float));
-    p[OFF_DB] = w->dec_b[0];
-    // ---- the same weights as bf16 x 3 fragments (silero_split.hip, split3.h)
-    for (int rt = 0; rt < 4; ++rt)
-        for (int kc = 0; kc < 4; ++kc)
-            for (int tap = 0; tap < 3; ++tap) {
-                float *f3 = p + OFF_Q2 + (size_t)(((rt * 4 + kc) * 3 + tap) * 3) * QF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->enc_w[1][((size_t)(16 * rt + i) * 128 + 32 * kc + k) * 3 + tap]);
-            }
-    for (int rt = 0; rt < 4; ++rt)
-        for (int th = 0; th < 2; ++th)
-            for (int kc = 0; kc < 2; ++kc) {
-                float *f3 = p + OFF_Q3 + (size_t)(((rt * 2 + th) * 2 + kc) * 3) * QF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->enc_w[2][((size_t)(16 * rt + i) * 64 + 32 * kc + k) * 3 + th + 1]);
-            }
-    for (int rt = 0; rt < 8; ++rt)
-        for (int kc = 0; kc < 2; ++kc) {
-            float *f3 = p + OFF_Q4 + (size_t)((rt * 2 + kc) * 3) * QF;
-            for (int i = 0; i < 16; ++i)
-                for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->enc_w[3][((size_t)(16 * rt + i) * 64 + 32 * kc + k) * 3 + 1]);
-        }
-    for (int wv = 0; wv < 8; ++wv)
-        for (int kc = 0; kc < 4; ++kc)
-            for (int g = 0; g < 4; ++g) {
-                float *f3 = p + OFF_QIH + (size_t)(((wv * 4 + kc) * 4 + g) * 3) * QF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->lstm_w_ih[(size_t)(g * 128 + wv * 16 + i) * 128 + 32 * kc + k]);
-            }
-    for (int wv = 0; wv < 8; ++wv)
-        for (int g = 0; g < 4; ++g)
-            for (int kc = 0; kc < 4; ++kc) {
-                float *f3 = p + OFF_QHH + (size_t)(((wv * 4 + g) * 4 + kc) * 3) * QF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) vadx::qfrag_put(f3, i, k, w->lstm_w_hh[(size_t)(g * 128 + wv * 16 + i) * 128 + 32 * kc + k]);
-            }
-    // ---- ... and as fp16 x 2 fragment pairs (silero_h2.hip, split2.h), same orders
-    for (int rt = 0; rt < 4; ++rt)
-        for (int kc = 0; kc < 4; ++kc)
-            for (int tap = 0; tap < 3; ++tap) {
-                float *f2 = p + OFF_H2 + (size_t)(((rt * 4 + kc) * 3 + tap) * 2) * HF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->enc_w[1][((size_t)(16 * rt + i) * 128 + 32 * kc + k) * 3 + tap]));
-            }
-    for (int rt = 0; rt < 4; ++rt)
-        for (int th = 0; th < 2; ++th)
-            for (int kc = 0; kc < 2; ++kc) {
-                float *f2 = p + OFF_H3 + (size_t)(((rt * 2 + th) * 2 + kc) * 2) * HF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->enc_w[2][((size_t)(16 * rt + i) * 64 + 32 * kc + k) * 3 + th + 1]));
-            }
-    for (int rt = 0; rt < 8; ++rt)
-        for (int kc = 0; kc < 2; ++kc) {
-            float *f2 = p + OFF_H4 + (size_t)((rt * 2 + kc) * 2) * HF;
-            for (int i = 0; i < 16; ++i)
-                for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->enc_w[3][((size_t)(16 * rt + i) * 64 + 32 * kc + k) * 3 + 1]));
-        }
-    for (int wv = 0; wv < 8; ++wv)
-        for (int kc = 0; kc < 4; ++kc)
-            for (int g = 0; g < 4; ++g) {
-                float *f2 = p + OFF_HIH + (size_t)(((wv * 4 + kc) * 4 + g) * 2) * HF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->lstm_w_ih[(size_t)(g * 128 + wv * 16 + i) * 128 + 32 * kc + k]));
-            }
-    for (int wv = 0; wv < 8; ++wv)
-        for (int g = 0; g < 4; ++g)
-            for (int kc = 0; kc < 4; ++kc) {
-                float *f2 = p + OFF_HHH + (size_t)(((wv * 4 + g) * 4 + kc) * 2) * HF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->lstm_w_hh[(size_t)(g * 128 + wv * 16 + i) * 128 + 32 * kc + k]));
-            }
-    // ... and no weight tensor wholly below the smallest normal fp16 once the chain is rebalanced (csrc/rebalance.h)
-    {
-        std::vector<float> whh(w->lstm_w_hh, w->lstm_w_hh + 512 * 128);
-        const int e = vadx::reb_exponent(whh);
-        if (e > -100000 && e < reb_min) reb_min = e;
-    }
-}
-
-extern "C" int vadx_silero_pack_host(const vadx_silero_weights_host *w_in, float *p) {
-    VADX_REQUIRE(w_in && p, "vadx_silero_pack_host: NULL argument");
-    VADX_REQUIRE(w_in->stft_basis && w_in->lstm_w_ih && w_in->lstm_w_hh && w_in->lstm_b_ih && w_in->lstm_b_hh && w_in->dec_w && w_in->dec_b,
-                 "vadx_silero_pack_host: NULL weight pointer");
-    for (int k = 0; k < 4; ++k) VADX_REQUIRE(w_in->enc_w[k] && w_in->enc_b[k], "vadx_silero_pack_host: NULL encoder weight %d", k);
-    memset(p, 0, sizeof(float) * PACKED_FLOATS);
-    // conv1 -> ReLU -> conv2 -> ReLU -> conv3 -> ReLU -> conv4 -> ReLU -> W_ih is one chain of affine layers with only ReLU between them: exact
-    // power-of-two rebalancing (csrc/rebalance.h) when a layer's weights sit outside [2^-10, 2^7); ordinary checkpoints pass through untouched.
-    // gx (b_ih + b_hh, then the LSTM's non-linearities) stays at its true scale: W_ih is the segment's last layer.
-    static const size_t enc_nw[4] = {128 * 129 * 3, 64 * 128 * 3, 64 * 64 * 3, 128 * 64 * 3}, enc_nb[4] = {128, 64, 64, 128};
-    std::vector<float> rw[5], rb[4];
-    for (int k = 0; k < 4; ++k) { rw[k].assign(w_in->enc_w[k], w_in->enc_w[k] + enc_nw[k]); rb[k].assign(w_in->enc_b[k], w_in->enc_b[k] + enc_nb[k]); }
-    rw[4].assign(w_in->lstm_w_ih, w_in->lstm_w_ih + 512 * 128);
-    int reb_min = 1000;
-    vadx::rebalance_chain({{&rw[0], &rb[0]}, {&rw[1], &rb[1]}, {&rw[2], &rb[2]}, {&rw[3], &rb[3]}, {&rw[4], nullptr}}, &reb_min);
-    vadx_silero_weights_host w_reb = *w_in;
-    for (int k = 0; k < 4; ++k) { w_reb.enc_w[k] = rw[k].data(); w_reb.enc_b[k] = rb[k].data(); }
-    w_reb.lstm_w_ih = rw[4].data();
-    const vadx_silero_weights_host *w = &w_reb;
-    // STFT basis rows regrouped per wave: [wave][re 16 bins | im 16 bins][256]
-    for (int wv = 0; wv < 8; ++wv)
-        for (int part = 0; part < 2; ++part)
-            for (int i = 0; i < 16; ++i)
-                for (int S = 0; S < 16; ++S)          // k permutation of the m-major STFT pass: slot 4q+j <- k = q+4j
-                    for (int qq = 0; qq < 4; ++qq)
-                        for (int j = 0; j < 4; ++j)
-                            p[OFF_STFT + (size_t)(wv * 32 + part * 16 + i) * 256 + 16 * S + 4 * qq + j] =
-                                w->stft_basis[(size_t)(part * 129 + wv * 16 + i) * 256 + 16 * S + qq + 4 * j];
-    memcpy(p + OFF_NYQ, w->stft_basis + (size_t)128 * 256, 256 * sizeof(float));
-    memcpy(p + OFF_NYQ + 256, w->stft_basis + (size_t)257 * 256, 256 * sizeof(float));
-    // fragment-major slot of element (row i of its tile, contraction index k) inside a tile that starts at `base`
-    auto frag = [](size_t base, int i, int k) { return base + ((size_t)(k / 16) * 64 + ((k % 16) / 4) * 16 + i) * 4 + (k % 4); };
-    float hmax = 0.f;       // largest |weight| handed to the fp16 x 2 fragments (must stay inside the fp16 range)
-    {   // folded basis: valid when the table has the time symmetry c[k][256-n] == c[k][n], s[k][256-n] == -s[k][n]
-        // (n = 1..127; s[k][128] == 0) AND the frequency symmetry c[128-k][n] == (-1)^n c[k][n],
-        // s[128-k][n] == -(-1)^n s[k][n], both up to f32 rounding of the table (1e-6 of the largest entry) -- which
-        // every windowed real-DFT basis satisfies.  Otherwise the kernel takes the dense pass.
-        const float *re = w->stft_basis, *im = w->stft_basis + (size_t)129 * 256;
-        float amax = 0.f, dev = 0.f;
-        for (size_t e = 0; e < (size_t)258 * 256; ++e) amax = fmaxf(amax, fabsf(w->stft_basis[e]));
-        for (int k = 0; k <= 128; ++k) {
-            for (int n = 1; n < 128; ++n) {
-                dev = fmaxf(dev, fabsf(re[k * 256 + n] - re[k * 256 + 256 - n]));
-                dev = fmaxf(dev, fabsf(im[k * 256 + n] + im[k * 256 + 256 - n]));
-            }
-            dev = fmaxf(dev, fabsf(im[k * 256 + 128]));
-        }
-        for (int k = 0; k < 64; ++k)
-            for (int n = 0; n < 256; ++n) {
-                const float sg = (n & 1) ? -1.f : 1.f;
-                dev = fmaxf(dev, fabsf(re[(128 - k) * 256 + n] - sg * re[k * 256 + n]));
-                dev = fmaxf(dev, fabsf(im[(128 - k) * 256 + n] + sg * im[k * 256 + n]));
-            }
-        const bool fold = dev <= 1e-6f * amax;
-        p[OFF_FOLD] = fold ? 1.f : 0.f;
-        if (fold) {
-            // symmetrised coefficient of bin k (<= 64) at sample n: average of the four table entries that must agree
-            auto C = [&](int k, int n) {
-                const float sg = (n & 1) ? -1.f : 1.f;
-                const int nm = (256 - n) & 255;
-                return 0.25f * (re[k * 256 + n] + re[k * 256 + nm] + sg * (re[(128 - k) * 256 + n] + re[(128 - k) * 256 + nm]));
-            };
-            auto S = [&](int k, int n) {
-                const float sg = (n & 1) ? -1.f : 1.f;
-                const int nm = (256 - n) & 255;
-                return 0.25f * (im[k * 256 + n] - im[k * 256 + nm] - sg * (im[(128 - k) * 256 + n] - im[(128 - k) * 256 + nm]));
-            };
-            for (int k = 0; k < 64; ++k) {
-                const int tl = k / 16, i = k % 16;
-                for (int cls = 0; cls < 2; ++cls)
-                    for (int m = 0; m < 64; ++m) {
-                        const int n = cls ? 2 * m + 1 : 2 * m + 2;
-                        // n = 128 is its own mirror: x[128] gets added to itself, so its coefficient is halved
-                        const float cv = (n == 128) ? 0.5f * C(k, 128) : C(k, n), sv = (n == 128) ? 0.f : S(k, n);
-                        const int slot = 16 * (m / 16) + 4 * (m % 4) + (m % 16) / 4;     // m = 16S + q + 4j -> slot 16S + 4q + j
-                        p[frag(OFF_SF + (size_t)((tl * 2 + cls) * 2 + 0) * 4 * FRAG, i, slot)] = cv;
-                        p[frag(OFF_SF + (size_t)((tl * 2 + cls) * 2 + 1) * 4 * FRAG, i, slot)] = sv;
-                        // the same coefficients as split fragments (silero_split.hip's STFT), pairs in natural order
-                        vadx::qfrag_put(p + OFF_QSF + (size_t)((((tl * 2 + cls) * 2 + 0) * 2 + m / 32) * 3) * QF, i, m % 32, cv);
-                        vadx::qfrag_put(p + OFF_QSF + (size_t)((((tl * 2 + cls) * 2 + 1) * 2 + m / 32) * 3) * QF, i, m % 32, sv);
-                        // ... and as fp16 x 2 fragment pairs (silero_h2.hip)
-                        hmax = fmaxf(hmax, vadx::hfrag_put(p + OFF_HSF + (size_t)((((tl * 2 + cls) * 2 + 0) * 2 + m / 32) * 2) * HF, i, m % 32, cv));
-                        hmax = fmaxf(hmax, vadx::hfrag_put(p + OFF_HSF + (size_t)((((tl * 2 + cls) * 2 + 1) * 2 + m / 32) * 2) * HF, i, m % 32, sv));
-                    }
-                p[OFF_S0 + k] = 0.5f * (re[k * 256] + re[(128 - k) * 256]);
-                p[OFF_S0 + 64 + k] = 0.5f * (im[k * 256] - im[(128 - k) * 256]);
-            }
-            for (int n = 1; n <= 128; ++n) {          // bin 64, time-folded only
-                const float h = (n == 128) ? 0.5f : 1.f;
-                p[OFF_B64 + n - 1] = h * 0.5f * (re[64 * 256 + n] + re[64 * 256 + ((256 - n) & 255)]);
-                p[OFF_B64 + 128 + n - 1] = (n == 128) ? 0.f : 0.5f * (im[64 * 256 + n] - im[64 * 256 + 256 - n]);
-            }
-            p[OFF_B64 + 256] = re[64 * 256];
-            p[OFF_B64 + 257] = im[64 * 256];
-            // bin 64 as row 0 of a fifth bin tile of the fp16 x 2 STFT (its coefficients are OFF_B64's, per class)
-            for (int cls = 0; cls < 2; ++cls)
-                for (int m = 0; m < 64; ++m) {
-                    const int n = cls ? 2 * m + 1 : 2 * m + 2;
-                    hmax = fmaxf(hmax, vadx::hfrag_put(p + OFF_HSF + (size_t)((((4 * 2 + cls) * 2 + 0) * 2 + m / 32) * 2) * HF, 0, m % 32, p[OFF_B64 + n - 1]));
-                    hmax = fmaxf(hmax, vadx::hfrag_put(p + OFF_HSF + (size_t)((((4 * 2 + cls) * 2 + 1) * 2 + m / 32) * 2) * HF, 0, m % 32, p[OFF_B64 + 128 + n - 1]));
-                }
-        }
-    }
-    {   // conv1 in the Winograd F(4,3) domain: U_j[co][ci] = sum_t G[j][t] g[co][ci][t], evaluated in float64
-        static const double G[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                       {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-        for (int co = 0; co < 128; ++co)
-            for (int j = 0; j < 6; ++j)
-                for (int ci = 0; ci < 129; ++ci) {
-                    const float *g = w->enc_w[0] + ((size_t)co * 129 + ci) * 3;
-                    const float u = (float)(G[j][0] * (double)g[0] + G[j][1] * (double)g[1] + G[j][2] * (double)g[2]);
-                    if (ci < 128) p[frag(OFF_C1 + (size_t)((co / 16) * 6 + j) * 8 * FRAG, co % 16, ci)] = u;
-                    else p[OFF_C1N + co * 8 + j] = u;
-                }
-    }
-    memcpy(p + OFF_B1, w->enc_b[0], 128 * sizeof(float));
-    // ---- the same conv / W_ih weights as bf16 x 3 fragments for the split-product encoder (silero_split.hip, split3.h)
-    for (int rt = 0; rt < 8; ++rt)
-        for (int kc = 0; kc < 4; ++kc)
-            for (int tap = 0; tap < 3; ++tap) {
-                float *f3 = p + OFF_Q1 + (size_t)(((rt * 4 + kc) * 3 + tap) * 3) * QF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) {
-                        const int slot = 32 * kc + k, bin = slot <= 64 ? slot : 192 - slot;        // the order the STFT pass leaves the bins in
-                        vadx::qfrag_put(f3, i, k, w->enc_w[0][((size_t)(16 * rt + i) * 129 + bin) * 3 + tap]);
-                    }
-            }
-    for (int co = 0; co < 128; ++co)
-        for (int tap = 0; tap < 3; ++tap) p[OFF_Q1N + co * 4 + tap] = w->enc_w[0][((size_t)co * 129 + 128) * 3 + tap];
-    // ---- ... and as fp16 x 2 fragment pairs for silero_h2.hip (split2.h), same orders
-    for (int rt = 0; rt < 8; ++rt)
-        for (int kc = 0; kc < 4; ++kc)
-            for (int tap = 0; tap < 3; ++tap) {
-                float *f2 = p + OFF_H1 + (size_t)(((rt * 4 + kc) * 3 + tap) * 2) * HF;
-                for (int i = 0; i < 16; ++i)
-                    for (int k = 0; k < 32; ++k) {
-                        const int slot = 32 * kc + k, bin = slot <= 64 ? slot : 192 - slot;
-                        hmax = fmaxf(hmax, vadx::hfrag_put(f2, i, k, w->enc_w[0][((size_t)(16 * rt + i) * 129 + bin) * 3 + tap]));
-                    }
-            }
-    silero_pack_shared(w, p, hmax, reb_min);
-    // the fp16 x 2 kernels need the folded STFT pass and every weight inside the fp16 range (NaN fails the comparison too)
-    // ... and no weight tensor wholly below the smallest normal fp16 once the chain is rebalanced (csrc/rebalance.h)
-    p[OFF_HFLAG] = (p[OFF_FOLD] != 0.f && hmax <= vadx::H_MAX && reb_min >= vadx::REB_REFUSE) ? 1.f : 0.f;
-    return VADX_OK;
-}
-
 // Which kernel set a launch uses comes with the call (include/vadx.h: vadx_silero_cfg.arithmetic); NULL / VADX_ARITH_AUTO = the
 // library's default.  Internal numbering: 0 = exact-f32 MFMAs, 1 = bf16 x 3 (silero_split.hip), 2 = fp16 x 2 (silero_h2.hip).
-static int arith_of(const vadx_silero_cfg *cfg) {
-    const int a = cfg ? cfg->arithmetic : VADX_ARITH_AUTO;
-    switch (a) {
-        case VADX_ARITH_AUTO: return ENCODER_DEFAULT;
-        case VADX_ARITH_F32: return 0;
-        case VADX_ARITH_BF16X3: return 1;
-        case VADX_ARITH_F16X2: return 2;
-        default: return -1;
-    }
-}
 #define VADX_SILERO_ARITH(cfg, who)                                                                               \
-    const int arith = arith_of(cfg);                                                                              \
+    const int arith = vadx::arith_internal((cfg) ? (cfg)->arithmetic : VADX_ARITH_AUTO, ENCODER_DEFAULT);         \
     VADX_REQUIRE(arith >= 0, who ": cfg->arithmetic=%d is not one of VADX_ARITH_*", (cfg) ? (cfg)->arithmetic : 0)
 // Which network a launch runs (vadx_silero_cfg.ext.sample_rate, ABI 9): 0 / 16000 = the 16 kHz network (windows of 512 samples after a 64-sample
 // context), 8000 = the 8 kHz one (256 after 32); anything else -1.  The blob must be the one packed for that rate.
@@ -1053,15 +790,7 @@ static int rate_of(const vadx_silero_cfg *cfg) {
 // to the host (synchronises `stream`) and, with reset != 0, clears them on the device.
 extern "C" int vadx_silero_range_flag(const float *packed, int reset, uint32_t *flag_host, float *amax_host, void *stream) {
     VADX_REQUIRE(packed && flag_host, "vadx_silero_range_flag: NULL argument");
-    uint32_t w[2] = {0, 0};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    VADX_HIP_TRY(hipMemcpyAsync(w, packed + OFF_HFLAG + 1, sizeof(w), hipMemcpyDeviceToHost, st));
-    VADX_HIP_TRY(hipStreamSynchronize(st));
-    if (reset && (w[0] | w[1]))
-        VADX_HIP_TRY(hipMemsetAsync(const_cast<float *>(packed) + OFF_HFLAG + 1, 0, sizeof(w), st));
-    *flag_host = w[0];
-    if (amax_host) memcpy(amax_host, &w[1], sizeof(float));
-    return VADX_OK;
+    return vadx::range_flag_read(packed + OFF_HFLAG + 1, reset, flag_host, amax_host, stream);
 }
 
 extern "C" size_t vadx_silero_workspace_bytes(int batch, int steps) {

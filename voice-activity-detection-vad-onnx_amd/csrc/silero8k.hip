@@ -1,5 +1,5 @@
 // silero8k.hip -- Silero-VAD v5, the 8 kHz sub-network's encoder for gfx950: one tile kernel written once for the three arithmetics
-// (float32 MFMAs, bf16 x 3 and fp16 x 2 split products, csrc/split_scheme.h), plus its packed blob.
+// (float32 MFMAs, bf16 x 3 and fp16 x 2 split products, csrc/split_scheme.h).  Its packed blob: csrc/silero_common.h (map), csrc/silero_pack.hip.
 //
 // The 8 kHz network differs from the 16 kHz one only before conv2:
 //   x [288] = 32 context + 256 new samples, reflect-padded right by 32 -> [320]
@@ -13,35 +13,12 @@
 // recurrent kernels read ([T][G][8 waves][4 gates][64 lanes][4], b_ih + b_hh folded in), so they run unchanged.  A tile's numbers do
 // not depend on the workgroup that computes it (one tile per workgroup, one instruction sequence).
 #include "silero_common.h"
-#include "rebalance.h"
 #include "split_scheme.h"
 
 #include <math.h>
-#include <string.h>
-#include <vector>
 
 namespace vadx {
 namespace silero {
-
-// ---- the 8 kHz blob: the 16 kHz layout (PACKED_FLOATS floats), every section the two networks share at its 16 kHz offset (conv2..4, W_ih,
-// W_hh in all three layouts, biases, decoder, OFF_HFLAG), the 8 kHz STFT and conv1 in [0, OFF_B1) -- where a 16 kHz blob keeps ITS STFT and
-// conv1, which an 8 kHz launch never reads.  conv1's bias sits at OFF_B1.  Fragment orders: [row tile][tap][32-k chunk] x one chunk's
-// fragments (f32: two FRAG blocks; bf16 x 3: three QF planes; fp16 x 2: two HF planes).
-constexpr int OFF8_SF = 0;                                // STFT f32  [9 row tiles][4 chunks][2 FRAG]
-constexpr int OFF8_SQ = OFF8_SF + 9 * 4 * 2 * FRAG;       //      bf16 x 3 [9][4][3][QF]
-constexpr int OFF8_SH = OFF8_SQ + 9 * 4 * 3 * QF;         //      fp16 x 2 [9][4][2][HF]
-constexpr int OFF8_C1F = OFF8_SH + 9 * 4 * 2 * HF;        // conv1 (input channels 0..63) f32 [8 oc tiles][3 taps][2 chunks][2 FRAG]
-constexpr int OFF8_C1Q = OFF8_C1F + 8 * 3 * 2 * 2 * FRAG; //      bf16 x 3 [8][3][2][3][QF]
-constexpr int OFF8_C1H = OFF8_C1Q + 8 * 3 * 2 * 3 * QF;   //      fp16 x 2 [8][3][2][2][HF]
-constexpr int OFF8_C1N = OFF8_C1H + 8 * 3 * 2 * 2 * HF;   // [128 oc][4]: taps 0..2 of input channel 64 (+1 pad), f32
-constexpr int OFF8_END = OFF8_C1N + 128 * 4;
-// the tag: a pad word of the 16 kHz layout (behind OFF_FOLD), zero in every 16 kHz blob.  An 8 kHz launch on a blob without it writes NaN gx
-// and raises bit 2 of the range flag.
-constexpr int OFF8_TAG = OFF_FOLD + 1;
-constexpr float TAG8K = 8000.f;
-static_assert(OFF8_END <= OFF_B1 && OFF8_SF % FRAG_ALIGN == 0 && OFF8_SQ % FRAG_ALIGN == 0 && OFF8_SH % FRAG_ALIGN == 0 &&
-                  OFF8_C1F % FRAG_ALIGN == 0 && OFF8_C1Q % FRAG_ALIGN == 0 && OFF8_C1H % FRAG_ALIGN == 0,
-              "8 kHz blob map");
 
 // ---- LDS map (floats): 51 456 B per workgroup.  R0: X [16 clips][320 (+4)] -> conv1 output [4 frames][16][128 (+4)] -> conv3 output [16][64 (+4)];
 // R1: |STFT| [4 frames][16][64 (+4)] + bin 64 [4][16] -> conv2 output [2][16][64 (+4)] -> conv4 output [16][128 (+4)].
@@ -412,73 +389,3 @@ template int silero8k_encode_launch<int16_t>(int, const float *, const int16_t *
 
 }  // namespace silero
 }  // namespace vadx
-
-// =================================================================================================
-// C ABI: the 8 kHz blob
-// =================================================================================================
-using namespace vadx::silero;
-using vadx::FRAG;
-
-extern "C" size_t vadx_silero_packed_floats_sr(int sample_rate) {
-    return (sample_rate == 16000 || sample_rate == 8000) ? (size_t)PACKED_FLOATS : 0;
-}
-
-extern "C" int vadx_silero_pack_host_sr(int sample_rate, const vadx_silero_weights_host *w_in, float *p) {
-    if (sample_rate == 16000) return vadx_silero_pack_host(w_in, p);
-    VADX_REQUIRE(sample_rate == 8000, "vadx_silero_pack_host_sr: sample_rate=%d is not 16000 or 8000", sample_rate);
-    VADX_REQUIRE(w_in && p, "vadx_silero_pack_host_sr: NULL argument");
-    VADX_REQUIRE(w_in->stft_basis && w_in->lstm_w_ih && w_in->lstm_w_hh && w_in->lstm_b_ih && w_in->lstm_b_hh && w_in->dec_w && w_in->dec_b,
-                 "vadx_silero_pack_host_sr: NULL weight pointer");
-    for (int k = 0; k < 4; ++k) VADX_REQUIRE(w_in->enc_w[k] && w_in->enc_b[k], "vadx_silero_pack_host_sr: NULL encoder weight %d", k);
-    memset(p, 0, sizeof(float) * PACKED_FLOATS);
-    // the same rebalancing chain as the 16 kHz network (conv1 .. conv4 -> W_ih), conv1 with 65 input channels
-    static const size_t enc_nw[4] = {128 * 65 * 3, 64 * 128 * 3, 64 * 64 * 3, 128 * 64 * 3}, enc_nb[4] = {128, 64, 64, 128};
-    std::vector<float> rw[5], rb[4];
-    for (int k = 0; k < 4; ++k) { rw[k].assign(w_in->enc_w[k], w_in->enc_w[k] + enc_nw[k]); rb[k].assign(w_in->enc_b[k], w_in->enc_b[k] + enc_nb[k]); }
-    rw[4].assign(w_in->lstm_w_ih, w_in->lstm_w_ih + 512 * 128);
-    int reb_min = 1000;
-    vadx::rebalance_chain({{&rw[0], &rb[0]}, {&rw[1], &rb[1]}, {&rw[2], &rb[2]}, {&rw[3], &rb[3]}, {&rw[4], nullptr}}, &reb_min);
-    vadx_silero_weights_host w_reb = *w_in;
-    for (int k = 0; k < 4; ++k) { w_reb.enc_w[k] = rw[k].data(); w_reb.enc_b[k] = rb[k].data(); }
-    w_reb.lstm_w_ih = rw[4].data();
-    const vadx_silero_weights_host *w = &w_reb;
-
-    float hmax = 0.f;
-    silero_pack_shared(w, p, hmax, reb_min);
-    auto frag = [](size_t base, int i, int k) { return base + ((size_t)(k / 16) * 64 + ((k % 16) / 4) * 16 + i) * 4 + (k % 4); };
-    // STFT: row tiles 0..3 = re of bins 0..63, 4..7 = im of bins 0..63, 8 = re (row 0) and im (row 1) of bin 64
-    for (int rt = 0; rt < 9; ++rt)
-        for (int i = 0; i < 16; ++i) {
-            int src = -1;
-            if (rt < 4) src = 16 * rt + i;
-            else if (rt < 8) src = 65 + 16 * (rt - 4) + i;
-            else if (i < 2) src = i == 0 ? 64 : 129;
-            if (src < 0) continue;
-            for (int k = 0; k < 128; ++k) {
-                const float v = w->stft_basis[(size_t)src * 128 + k];
-                const int kc = k / 32;
-                p[frag(OFF8_SF + (size_t)(rt * 4 + kc) * 2 * FRAG, i, k % 32)] = v;
-                vadx::qfrag_put(p + OFF8_SQ + (size_t)(rt * 4 + kc) * 3 * QF, i, k % 32, v);
-                hmax = fmaxf(hmax, vadx::hfrag_put(p + OFF8_SH + (size_t)(rt * 4 + kc) * 2 * HF, i, k % 32, v));
-            }
-        }
-    // conv1 [128][65][3]: input channels 0..63 as fragments, channel 64 as VALU taps
-    for (int co = 0; co < 128; ++co) {
-        const int rt = co / 16, i = co % 16;
-        for (int tap = 0; tap < 3; ++tap) {
-            for (int ci = 0; ci < 64; ++ci) {
-                const float v = w->enc_w[0][((size_t)co * 65 + ci) * 3 + tap];
-                const size_t c = (size_t)(rt * 3 + tap) * 2 + ci / 32;
-                p[frag(OFF8_C1F + c * 2 * FRAG, i, ci % 32)] = v;
-                vadx::qfrag_put(p + OFF8_C1Q + c * 3 * QF, i, ci % 32, v);
-                hmax = fmaxf(hmax, vadx::hfrag_put(p + OFF8_C1H + c * 2 * HF, i, ci % 32, v));
-            }
-            p[OFF8_C1N + co * 4 + tap] = w->enc_w[0][((size_t)co * 65 + 64) * 3 + tap];
-        }
-    }
-    memcpy(p + OFF_B1, w->enc_b[0], 128 * sizeof(float));
-    p[OFF8_TAG] = TAG8K;
-    // fp16 x 2: every weight inside the fp16 range and no weight tensor wholly below 2^-14 after rebalancing (no fold needed: the STFT is dense)
-    p[OFF_HFLAG] = (hmax <= vadx::H_MAX && reb_min >= vadx::REB_REFUSE) ? 1.f : 0.f;
-    return VADX_OK;
-}

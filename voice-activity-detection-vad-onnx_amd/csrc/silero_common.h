@@ -1,4 +1,4 @@
-// silero_common.h -- what the two Silero encoder kernels share: the packed-blob map, the staged-window layout, the STFT passes.
+// silero_common.h -- what the two Silero encoder kernels share: the packed-blob map (filled by csrc/silero_pack.hip), the staged-window layout, the STFT passes.
 // (csrc/silero.hip: exact-f32 MFMA encoder; csrc/silero_split.hip: bf16 x 3 split-product encoder, csrc/split3.h)
 #pragma once
 #include "common.h"
@@ -71,6 +71,25 @@ constexpr int OFF_HSF = OFF_HHH + 8 * 4 * 4 * 2 * HF;
 // [2] bits of the largest |activation| seen by a flagged workgroup; [3] pad
 constexpr int OFF_HFLAG = OFF_HSF + 5 * 2 * 2 * 2 * 2 * HF;
 constexpr int PACKED_FLOATS = OFF_HFLAG + 4;
+// ---- the 8 kHz blob (csrc/silero8k.hip): the 16 kHz layout (PACKED_FLOATS floats), every section the two networks share at its 16 kHz offset
+// (conv2..4, W_ih, W_hh in all three layouts, biases, decoder, OFF_HFLAG), the 8 kHz STFT and conv1 in [0, OFF_B1) -- where a 16 kHz blob keeps
+// ITS STFT and conv1, which an 8 kHz launch never reads.  conv1's bias sits at OFF_B1.  Fragment orders: [row tile][tap][32-k chunk] x one
+// chunk's fragments (f32: two FRAG blocks of 256 floats; bf16 x 3: three QF planes; fp16 x 2: two HF planes).
+constexpr int OFF8_SF = 0;                                // STFT f32  [9 row tiles][4 chunks][2 FRAG]
+constexpr int OFF8_SQ = OFF8_SF + 9 * 4 * 2 * 256;        //      bf16 x 3 [9][4][3][QF]
+constexpr int OFF8_SH = OFF8_SQ + 9 * 4 * 3 * QF;         //      fp16 x 2 [9][4][2][HF]
+constexpr int OFF8_C1F = OFF8_SH + 9 * 4 * 2 * HF;        // conv1 (input channels 0..63) f32 [8 oc tiles][3 taps][2 chunks][2 FRAG]
+constexpr int OFF8_C1Q = OFF8_C1F + 8 * 3 * 2 * 2 * 256;  //      bf16 x 3 [8][3][2][3][QF]
+constexpr int OFF8_C1H = OFF8_C1Q + 8 * 3 * 2 * 3 * QF;   //      fp16 x 2 [8][3][2][2][HF]
+constexpr int OFF8_C1N = OFF8_C1H + 8 * 3 * 2 * 2 * HF;   // [128 oc][4]: taps 0..2 of input channel 64 (+1 pad), f32
+constexpr int OFF8_END = OFF8_C1N + 128 * 4;
+// the tag: a pad word of the 16 kHz layout (behind OFF_FOLD), zero in every 16 kHz blob.  An 8 kHz launch on a blob without it writes NaN gx
+// and raises bit 2 of the range flag.
+constexpr int OFF8_TAG = OFF_FOLD + 1;
+constexpr float TAG8K = 8000.f;
+static_assert(FRAG == 256 && OFF8_END <= OFF_B1 && OFF8_SF % FRAG_ALIGN == 0 && OFF8_SQ % FRAG_ALIGN == 0 && OFF8_SH % FRAG_ALIGN == 0 &&
+                  OFF8_C1F % FRAG_ALIGN == 0 && OFF8_C1Q % FRAG_ALIGN == 0 && OFF8_C1H % FRAG_ALIGN == 0,
+              "8 kHz blob map");
 
 constexpr int X_LDM = 642;            // staged window row: 576 samples + 64 reflect pad (+2: bank = 2 clip + q, conflict free)
 // gx: per (t, group) 8 waves x 4 gates x 64 lanes x 4 floats
@@ -205,8 +224,6 @@ int silero_recur_launch(const float *packed, const void *ws, size_t ws_bytes, in
 template <typename S>
 int silero8k_encode_launch(int arith, const float *packed, const S *src, float in_scale, long long n_valid, long long row_stride,
                            long long origin, int batch, int G, int steps, int Gws, int first_group, float *gx, void *stream);
-// host: the packed sections the 16 kHz and 8 kHz blobs share (csrc/silero.hip)
-void silero_pack_shared(const vadx_silero_weights_host *w, float *p, float &hmax, int &reb_min);
 
 int silero_lstm_split_launch(const float *packed, const float *gx, const float *state0, int batch, int G, int steps, float *probs,
                              long long probs_stride, float *state_n, void *stream);

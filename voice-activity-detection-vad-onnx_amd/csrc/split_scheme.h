@@ -68,6 +68,19 @@ struct SchemeH2 {
     }
 };
 
+// host: read a SchemeH2 kernel's two range-flag words [sticky flag, bits of the largest |x|] from the device (synchronises `stream`) and, with
+// reset != 0, clear them there
+inline int range_flag_read(const float *two_words, int reset, uint32_t *flag_host, float *amax_host, void *stream) {
+    uint32_t w[2] = {0, 0};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    VADX_HIP_TRY(hipMemcpyAsync(w, two_words, sizeof(w), hipMemcpyDeviceToHost, st));
+    VADX_HIP_TRY(hipStreamSynchronize(st));
+    if (reset && (w[0] | w[1])) VADX_HIP_TRY(hipMemsetAsync(const_cast<float *>(two_words), 0, sizeof(w), st));
+    *flag_host = w[0];
+    if (amax_host) memcpy(amax_host, &w[1], sizeof(float));
+    return VADX_OK;
+}
+
 #if defined(__HIPCC__)
 // the end-of-kernel range check of a SchemeH2 kernel: `flag` = two words inside the kernel's packed blob [sticky flag, bits of the largest |x|]
 __device__ __forceinline__ void range_flag_raise(const float *flag_words, float amax) {
