@@ -1,5 +1,7 @@
 """GPU parity: DFSMN near+far building blocks and full path vs the oracle (itself pinned against the
 reference's ICCRN / wrapper classes by tests/golden/dfsmn_forward.npz)."""
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -306,3 +308,101 @@ def test_whole_config_decision_record():
     r = decision_records.dfsmn_c5(torch, torch.device("cuda", 0))
     print(r)
     assert r["unexcused"] == 0, r
+
+
+# ---- vadx_dfsmn_lstm_f called directly: CepsUnit geometry, the three arithmetics against float64 ------------------------------------
+LF_IN, LF_H, LF_F = 40, 20, 81          # 40 input channels with LayerNorm, hidden 20 per direction; F = 81 is odd: the last chunk of two bins holds one
+LF_R = 1.25 * 1.2069                    # 1.25 x the worst ratio of the pre-merge kernels, see test_lstm_f_direct_against_float64
+
+
+def _lstm_f_launch(case, mode, ln_w=None):
+    """One vadx_dfsmn_lstm_f launch on `case`'s inputs -> (out FT [tiles, 40, F, 16], the two range-flag words as (flag, amax))"""
+    out = torch.empty_like(case["x"])
+    flag = torch.zeros(2, dtype=torch.int32, device=out.device)
+    pair = lambda k: (C.c_void_p * 2)(case[k][0].data_ptr(), case[k][1].data_ptr())      # noqa: E731
+    inp, outv = _lib.FtView(case["x"].data_ptr(), LF_IN, 0, LF_IN), _lib.FtView(out.data_ptr(), 2 * LF_H, 0, 2 * LF_H)
+    ln = _lib.FtLn(case["stats"].data_ptr(), (case["ln_w"] if ln_w is None else ln_w).data_ptr(), case["ln_b"].data_ptr())
+    wi, wh, bi, bh = pair("w_ih"), pair("w_hh"), pair("b_ih"), pair("b_hh")
+    _lib.check(_lib.lib().vadx_dfsmn_lstm_f(C.byref(inp), C.byref(ln), C.byref(wi), C.byref(wh), C.byref(bi), C.byref(bh), C.byref(outv),
+                                            LF_F, case["tiles"], _lib.stream_ptr(), _lib.ARITH[mode], flag.data_ptr()))
+    words = flag.cpu().numpy()
+    return out, (int(words[0]), float(words[1:].view(np.float32)[0]))
+
+
+def _lstm_f_float64(case, tile_ids):
+    """float64 restatement for the tiles `tile_ids`: LayerNorm as (x - mean) * inv * w + b from the given statistics, then a bidirectional
+    LSTM along F (torch's gate order i, f, g, o; batch = the 16 frames of each tile) -> [len(tile_ids), 40, F, 16]"""
+    f8 = lambda a: a.detach().cpu().numpy().astype(np.float64)      # noqa: E731
+    idx = torch.as_tensor(tile_ids, device=case["x"].device)
+    x, st = f8(case["x"][idx]), f8(case["stats"][idx])                                   # [n, 40, F, 16], [n, 16, 2]
+    xn = (x - st[:, None, None, :, 0]) * st[:, None, None, :, 1] * f8(case["ln_w"])[None, :, :, None] + f8(case["ln_b"])[None, :, :, None]
+    n = x.shape[0]
+    seq = xn.transpose(2, 0, 3, 1).reshape(LF_F, n * 16, LF_IN)
+    out = np.empty((n, 2 * LF_H, LF_F, 16))
+    sig = lambda v: 1.0 / (1.0 + np.exp(-v))      # noqa: E731
+    for d in range(2):
+        wih, whh, b = f8(case["w_ih"][d]), f8(case["w_hh"][d]), f8(case["b_ih"][d]) + f8(case["b_hh"][d])
+        h, c = np.zeros((n * 16, LF_H)), np.zeros((n * 16, LF_H))
+        for f in (range(LF_F) if d == 0 else range(LF_F - 1, -1, -1)):
+            g = seq[f] @ wih.T + h @ whh.T + b
+            c = sig(g[:, LF_H:2 * LF_H]) * c + sig(g[:, :LF_H]) * np.tanh(g[:, 2 * LF_H:3 * LF_H])
+            h = sig(g[:, 3 * LF_H:]) * np.tanh(c)
+            out[:, d * LF_H:(d + 1) * LF_H, f, :] = h.reshape(n, 16, LF_H).transpose(0, 2, 1)
+    return out
+
+
+_lstm_f_cases = {}
+
+
+def _lstm_f_case(tiles):
+    """Seeded inputs of one shape, their float64 result on the compared tiles and the float32 kernel's error there: made once per shape,
+    shared by the three arithmetics' runs of the test and left unchanged."""
+    if tiles not in _lstm_f_cases:
+        dev = torch.device("cuda", 0)
+        g = torch.Generator(device=dev).manual_seed(8100 + tiles)
+        rnd = lambda *shape: torch.randn(*shape, generator=g, device=dev, dtype=torch.float32)      # noqa: E731
+        k = 1.0 / np.sqrt(LF_H)                                                          # torch.nn.LSTM's initialisation range
+        case = {"tiles": tiles, "x": rnd(tiles, LF_IN, LF_F, 16),
+                "stats": torch.stack([0.3 * rnd(tiles, 16), 0.5 + torch.rand(tiles, 16, generator=g, device=dev)], dim=2).contiguous(),
+                "ln_w": 1.0 + 0.1 * rnd(LF_IN, LF_F), "ln_b": 0.1 * rnd(LF_IN, LF_F)}
+        for name, cols in (("w_ih", (LF_IN,)), ("w_hh", (LF_H,)), ("b_ih", ()), ("b_hh", ())):
+            case[name] = [(2 * torch.rand(4 * LF_H, *cols, generator=g, device=dev) - 1) * k for _ in range(2)]
+        case["compare"] = [0, 1, 1024] if tiles > 2 else list(range(tiles))
+        case["want"] = _lstm_f_float64(case, case["compare"])
+        case["err_f32"] = _lstm_f_error(case, _lstm_f_launch(case, "f32")[0])
+        _lstm_f_cases[tiles] = case
+    return _lstm_f_cases[tiles]
+
+
+def _lstm_f_error(case, out):
+    idx = torch.as_tensor(case["compare"], device=out.device)
+    return float(np.max(np.abs(out[idx].cpu().numpy().astype(np.float64) - case["want"])))
+
+
+@pytest.mark.parametrize("tiles", [1, 2, 1025])
+def test_lstm_f_direct_against_float64(gemm, tiles):
+    """vadx_dfsmn_lstm_f itself (no engine around it) on the arithmetic of the `gemm` fixture, against the float64 restatement above.
+    tiles = 1025 is the smallest launch in which a persistent workgroup of the split kernels (at most 1024 of them) walks a second
+    tile and crosses the wave barrier between tiles; there tiles 0, 1 and 1024 are compared.
+      "split" / "h2": max |error| <= LF_R x that of the float32 kernel on the same inputs; neither raises the range flag in range.
+      "h2" with the LayerNorm weight x 1e6 (normalised inputs of the order 1e6..1e7 > 65504): flag bit 0 and a finite amax above 65504.
+      "f32": the yardstick itself is a rounding-level error -- below 1e-4 = 81 steps x the 1e-6 that 61-term float32 sums of magnitude
+      <= 10 lose per pre-activation, with no credit for the gates' contraction (a wrong gate or bin is off by 1e-2 and more) -- and
+      not zero.
+    LF_R: on the two kernels this one replaced (lstm_f_split_kernel, lstm_f_h2_kernel) these inputs gave max |error| ratios to the float32
+    kernel of 0.840 / 0.757 / 1.066 ("split", tiles 1 / 2 / 1025) and 1.207 / 1.014 / 1.039 ("h2"), float32 errors 2.9e-7 / 3.5e-7 / 3.7e-7:
+    not both below 1, so LF_R = 1.25 x the worst of them, 1.2069 (1.25: the margin the encoder proof test gives split arithmetics over
+    the float32 kernel).  The merged kernel gives the same figures, bit for bit the same outputs."""
+    case = _lstm_f_case(tiles)
+    out, flag = _lstm_f_launch(case, gemm)
+    err = _lstm_f_error(case, out)
+    print(f"lstm_f tiles={tiles} {gemm}: max|err| {err:.3e}, f32 kernel {case['err_f32']:.3e}, ratio {err / case['err_f32']:.3f}, flag {flag}")
+    assert flag == (0, 0.0)
+    if gemm == "f32":
+        assert 0.0 < case["err_f32"] < 1e-4 and err == case["err_f32"]
+        return
+    assert err <= LF_R * case["err_f32"]
+    if gemm == "h2":
+        _, (raised, amax) = _lstm_f_launch(case, "h2", ln_w=case["ln_w"] * 1e6)
+        print(f"lstm_f tiles={tiles} h2, LayerNorm weight x 1e6: flag {raised}, amax {amax:.4g}")
+        assert raised & 1 and np.isfinite(amax) and amax > 65504.0

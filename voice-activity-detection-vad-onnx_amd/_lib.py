@@ -303,8 +303,25 @@ class trace:
         return False
 
 
-GEMM_MODES = {"f32": ARITH["f32"], "split": ARITH["split"], "h2": ARITH["h2"]}      # name -> VADX_ARITH_*
+GEMM_MODES = {m: ARITH[m] for m in ("f32", "split", "h2")}      # the three arithmetics an engine can run on (an alias table of ARITH)
 _gemm_default = [None]
+
+
+def default_arith(store, env, what, mode=None):
+    """A module-level default arithmetic kept in `store[0]`: read once from the environment variable `env` ("f32" | "split" | "h2", or
+    the spellings 0 / 1 / 2 / bf16x3 / f16x2; unset = "h2"), replaced by `mode` when that is given.  Returns the value that was active."""
+    if store[0] is None:
+        e = os.environ.get(env, "").strip().lower()
+        v = {"0": "f32", "1": "split", "2": "h2", "bf16x3": "split", "f16x2": "h2"}.get(e, e) if e else "h2"
+        if v not in GEMM_MODES:
+            raise ValueError(f"{env} must be one of {sorted(GEMM_MODES)}, got {e!r}")
+        store[0] = v
+    prev = store[0]
+    if mode is not None:
+        if mode not in GEMM_MODES:
+            raise ValueError(f"{what} mode must be one of {sorted(GEMM_MODES)}, got {mode!r}")
+        store[0] = mode
+    return prev
 
 
 def gemm_mode(mode=None):
@@ -313,17 +330,27 @@ def gemm_mode(mode=None):
     range are detected and the batch recomputed on "split").  A Python-side default only: the C ABI takes the arithmetic with every
     cfg / dims struct (include/vadx.h: VADX_ARITH_*).  Returns the mode that was active; None only queries.  Initial value: VADX_GEMM,
     read once here."""
-    if _gemm_default[0] is None:
-        e = os.environ.get("VADX_GEMM", "").strip().lower()
-        _gemm_default[0] = {"0": "f32", "1": "split", "2": "h2", "bf16x3": "split", "f16x2": "h2"}.get(e, e) if e else "h2"
-        if _gemm_default[0] not in GEMM_MODES:
-            raise ValueError(f"VADX_GEMM must be one of {sorted(GEMM_MODES)}, got {e!r}")
-    prev = _gemm_default[0]
-    if mode is not None:
-        if mode not in GEMM_MODES:
-            raise ValueError(f"gemm mode must be one of {sorted(GEMM_MODES)}, got {mode!r}")
-        _gemm_default[0] = mode
-    return prev
+    return default_arith(_gemm_default, "VADX_GEMM", "gemm", mode)
+
+
+def range_guarded(owner, mode, run, read_flag, fallback):
+    """The fp16 x 2 range protocol, once for every engine: `run(mode)` is the result unless `mode` is "h2" and an operand left the fp16
+    range -- `read_flag()` says so (it synchronises, and clears a raised flag; it is called on "h2" only, once) -- in which case
+    `owner.range_fallbacks` counts the batch and the result is `run(fallback)`'s."""
+    out = run(mode)
+    if mode == "h2" and read_flag():
+        owner.range_fallbacks += 1
+        out = run(fallback)
+    return out
+
+
+def take_flag(words):
+    """read_flag of `range_guarded` for an engine that owns its two flag words as a device int32 tensor: True when the sticky flag is
+    raised (one 4-byte read-back, synchronises), clearing both words then."""
+    raised = int(words[0].item()) != 0
+    if raised:
+        words.zero_()
+    return raised
 
 
 class ArithBlobs:
@@ -355,14 +382,7 @@ class ArithBlobs:
         return self._blobs[mode]
 
     def guarded(self, run):
-        m = self.mode()
-        out = run(m, *self.get(m))
-        if m == "h2":
-            flag, _ = self._flag(*self.get(m))
-            if flag:
-                self.range_fallbacks += 1
-                out = run("split", *self.get("split"))
-        return out
+        return range_guarded(self, self.mode(), lambda m: run(m, *self.get(m)), lambda: self._flag(*self.get("h2"))[0], "split")
 
 
 def check(rc, exc=VadxError):

@@ -10,8 +10,7 @@
 // LSTM recurrences keep h and c in registers: with gate rows ordered (unit-quad q, gate r) the D
 // fragment of step t is exactly the B fragment of step t+1 -- no LDS, no shuffles.
 #include "common.h"
-#include "split3.h"
-#include "split2.h"
+#include "split_scheme.h"
 #include "layers.h"
 
 #include <math.h>
@@ -808,7 +807,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void l
 
 
 // ---------------------------------------------------------------------------------------------
-// lstm_f on bf16 x 3 split products (csrc/split3.h), CepsUnit geometry (IN = 40, hidden 20).  Same decomposition as lstm_f_kernel<40>:
+// lstm_f on split products (csrc/split_scheme.h), CepsUnit geometry (IN = 40, hidden 20): ONE kernel, instantiated for bf16 x 3 and
+// fp16 x 2; `if constexpr` on the scheme marks the only parts that differ -- where weight plane 2 lives, the product block, the join of
+// its accumulators and the range epilogue.  Described for bf16 x 3 first.  Same decomposition as lstm_f_kernel<40>:
 // one wave per direction, gate rows ordered so that the cell update is lane-local, x streamed through the wave's private LDS chunks.
 // The step's matrix product is ONE GEMM over the concatenated operand [h (20) ; x (40) ; 1 (bias)] = 61 of the 64 k-slots of two
 // 32-k chunks: 5 row tiles x 2 chunks x 6 = 60 v_mfma_f32_16x16x32_bf16 (1020 matrix cycles) instead of 75 v_mfma_f32_16x16x4_f32
@@ -818,152 +819,41 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void l
 //              cross-lane traffic, as in the f32 kernel);  e = 5..7 -> x channel 3 g + e - 5
 //     chunk 1: x channel 12 + 8 g + e (< 40), channel 40 = the constant 1.0 whose "weight" is b_ih + b_hh, beyond: zero
 // Weights are split by each lane at kernel start from the torch layouts (80 loads + splits; the workgroups are persistent over tiles).
+// fp16 x 2: both planes of the weights in registers (80 VGPRs, no LDS plane), three v_mfma_f32_16x16x32_f16 per (row tile, chunk) = 30 per
+// step instead of 60 bf16, 3 VALU per split value instead of 5.5.  h lies in (-1, 1); the LayerNorm'd inputs and the weights feed the
+// range check (vadx_dfsmn_lstm_f's range_flag).
+// Both instances sit at 256 VGPRs with a little scratch (as inlined functions of a policy struct the four parts cost fp16 x 2 more of it).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void split3x8(const float (&v)[8], bf16x8 &p0, bf16x8 &p1, bf16x8 &p2) {
+// eight float32 values (the k-slots of one lane's chunk) -> the planes of its A / B fragment (two bodies: over split4's arrays the callers' code reorders)
+__device__ __forceinline__ void split8(const float (&v)[8], bf16x8 (&p)[3], float &) {
     u32x2 a0, a1, a2, b0, b1, b2;
     split3x4(f32x4{v[0], v[1], v[2], v[3]}, a0, a1, a2);
     split3x4(f32x4{v[4], v[5], v[6], v[7]}, b0, b1, b2);
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    union { u32x4 u; bf16x8 h; } c0, c1, c2;
-    c0.u = u32x4{a0[0], a0[1], b0[0], b0[1]}; c1.u = u32x4{a1[0], a1[1], b1[0], b1[1]}; c2.u = u32x4{a2[0], a2[1], b2[0], b2[1]};
-    p0 = c0.h; p1 = c1.h; p2 = c2.h;
+    p[0] = __builtin_bit_cast(bf16x8, u32x4{a0[0], a0[1], b0[0], b0[1]});
+    p[1] = __builtin_bit_cast(bf16x8, u32x4{a1[0], a1[1], b1[0], b1[1]});
+    p[2] = __builtin_bit_cast(bf16x8, u32x4{a2[0], a2[1], b2[0], b2[1]});
 }
-
-// eight float32 values (the slots of one lane's chunk) -> the two fp16 planes of its B / A fragment
-__device__ __forceinline__ void split8_h2(const float (&v)[8], f16x8 (&b)[2], float &amax) {
-    u32x2 a0, a1, c0, c1;
+__device__ __forceinline__ void split8(const float (&v)[8], f16x8 (&p)[2], float &amax) {
+    u32x2 a0, a1, b0, b1;
     vadx::split2x4(f32x4{v[0], v[1], v[2], v[3]}, a0, a1, amax);
-    vadx::split2x4(f32x4{v[4], v[5], v[6], v[7]}, c0, c1, amax);
-    typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-    b[0] = __builtin_bit_cast(f16x8, u32x4_{a0[0], a0[1], c0[0], c0[1]});
-    b[1] = __builtin_bit_cast(f16x8, u32x4_{a1[0], a1[1], c1[0], c1[1]});
+    vadx::split2x4(f32x4{v[4], v[5], v[6], v[7]}, b0, b1, amax);
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    p[0] = __builtin_bit_cast(f16x8, u32x4{a0[0], a0[1], b0[0], b0[1]});
+    p[1] = __builtin_bit_cast(f16x8, u32x4{a1[0], a1[1], b1[0], b1[1]});
 }
 
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void lstm_f_split_kernel(LstmFArgs p, int tiles) {
+template <class SC>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void lstm_f_split_kernel(LstmFArgs p, int tiles, unsigned *__restrict__ range_flag) {
     constexpr int IN = 40, H = 20, MT = 5, NB = 2;
     constexpr int CH_FLOATS = NB * IN * 16, NLD = NB * IN / 16;
+    constexpr bool W2_IN_LDS = SC::NP == 3;
     __shared__ __attribute__((aligned(16))) float xs[2][2][CH_FLOATS];      // [direction][buffer]
-    __shared__ bf16x8 w2s[2][MT][2][64];              // plane 2 of the weights (used by one product in six): 20 KB, read back per step
+    __shared__ bf16x8 w2s[2][MT][2][64];              // bf16 x 3: plane 2 of the weights (used by one product in six): 20 KB, read back per step
+                                                      // (fp16 x 2 never names it, so that instance has no such LDS)
     const int lane = threadIdx.x & 63, dir = threadIdx.x >> 6, q = lane >> 4, i = lane & 15;
     const int grow = (i & 3) * H + (i >> 2);          // A-fragment row i <-> gate (i&3), unit-in-quad (i>>2)
-    bf16x8 wa[MT][2][2];                              // [row tile][chunk][plane 0, 1]: 80 VGPRs, resident for every tile of this workgroup
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        const int row = grow + 4 * mt;
-        float v0[8], v1[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            v0[e] = e < 5 ? p.w_hh[dir][(size_t)row * H + 4 * e + q] : p.w_ih[dir][(size_t)row * IN + 3 * q + e - 5];
-            const int ch = 12 + 8 * q + e;
-            v1[e] = ch < IN ? p.w_ih[dir][(size_t)row * IN + ch] : (ch == IN ? p.b_ih[dir][row] + p.b_hh[dir][row] : 0.f);
-        }
-        bf16x8 t2;
-        split3x8(v0, wa[mt][0][0], wa[mt][0][1], t2);
-        w2s[dir][mt][0][lane] = t2;
-        split3x8(v1, wa[mt][1][0], wa[mt][1][1], t2);
-        w2s[dir][mt][1][lane] = t2;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");          // w2s is written and read by the same wave only
-    __builtin_amdgcn_wave_barrier();
-    const int tq = lane & 3;
-    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    float h[MT], c[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) { h[mt] = 0.f; c[mt] = 0.f; }
-    f32x4 ln_mean, ln_inv;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        ln_mean[r] = p.ln.stats[((size_t)tile * 16 + 4 * tq + r) * 2];
-        ln_inv[r] = p.ln.stats[((size_t)tile * 16 + 4 * tq + r) * 2 + 1];
-    }
-    const int nchunk = (p.F + NB - 1) / NB;
-    auto bin_of = [&](int ck, int b) { const int st = ck * NB + b; return dir ? p.F - 1 - st : st; };
-    f32x4 pre[NLD];
-    float lw[NLD], lb[NLD];
-    auto request = [&](int ck) {
-#pragma unroll
-        for (int r = 0; r < NLD; ++r) {
-            const int row = (lane >> 2) + 16 * r, b = row / IN, ch = row - b * IN, f = bin_of(ck, b);
-            const int fcl = f < 0 ? 0 : (f >= p.F ? p.F - 1 : f);        // unconditional (clamped) loads; bins past the end are never used
-            pre[r] = *reinterpret_cast<const f32x4 *>(p.in.ptr + ft_idx(tile, p.in.c_total, p.in.c_off + ch, p.F, fcl) + 4 * tq);
-            lw[r] = p.ln.w[ch * p.F + fcl]; lb[r] = p.ln.b[ch * p.F + fcl];
-        }
-    };
-    auto park = [&](float *dst) {
-#pragma unroll
-        for (int r = 0; r < NLD; ++r)
-            *reinterpret_cast<f32x4 *>(dst + ((lane >> 2) + 16 * r) * 16 + 4 * tq) = (pre[r] - ln_mean) * ln_inv * lw[r] + lb[r];
-    };
-    __builtin_amdgcn_wave_barrier();                  // the previous tile's last reads of xs precede this tile's first park
-    request(0);
-    park(xs[dir][0]);
-    if (nchunk > 1) request(1);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (int ck = 0; ck < nchunk; ++ck) {
-        const float *xb = xs[dir][ck & 1];
-        if (ck + 1 < nchunk) {
-            park(xs[dir][(ck + 1) & 1]);                  // the buffer last read by chunk ck - 1
-            if (ck + 2 < nchunk) request(ck + 2);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-#pragma unroll 1
-        for (int b = 0; b < NB; ++b) {
-            const int f = bin_of(ck, b);
-            if (f < 0 || f >= p.F) break;
-            const float *xrow = xb + b * IN * 16 + i;
-            float v0[8], v1[8];
-#pragma unroll
-            for (int e = 0; e < 5; ++e) v0[e] = h[e];
-#pragma unroll
-            for (int e = 5; e < 8; ++e) v0[e] = xrow[(3 * q + e - 5) * 16];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int ch = 12 + 8 * q + e;               // (q is per-lane: clamp the read, select afterwards)
-                const float xv = xrow[(ch < IN ? ch : IN - 1) * 16];
-                v1[e] = ch < IN ? xv : (ch == IN ? 1.0f : 0.f);
-            }
-            bf16x8 b0[3], b1[3];
-            split3x8(v0, b0[0], b0[1], b0[2]);
-            split3x8(v1, b1[0], b1[1], b1[2]);
-            // ONE accumulator per row tile, small products first (at 256 VGPRs the separate accumulator of the small products spilled
-            // into the chunk code; measured on its own -- tools/bf16x3_probe.sh "s6" -- the single accumulator is still closer to the float64
-            // product than the f32 MFMA chain: 1.4e-7 against 2.5e-7 of sum |w x|).  Row tiles innermost: consecutive MFMAs are independent.
-            f32x4 acc[MT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#define LF_TERM(CH, BF, AP, BP) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma_bf16(wa[mt][CH][AP], BF[BP], acc[mt]);
-#define LF_TERM2(CH, BF) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma_bf16(w2s[dir][mt][CH][lane], BF[0], acc[mt]);
-            LF_TERM2(0, b0) LF_TERM(0, b0, 1, 1) LF_TERM(0, b0, 0, 2) LF_TERM2(1, b1) LF_TERM(1, b1, 1, 1) LF_TERM(1, b1, 0, 2)
-            LF_TERM(0, b0, 1, 0) LF_TERM(0, b0, 0, 1) LF_TERM(1, b1, 1, 0) LF_TERM(1, b1, 0, 1) LF_TERM(0, b0, 0, 0) LF_TERM(1, b1, 0, 0)
-#undef LF_TERM
-#undef LF_TERM2
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                const f32x4 a = acc[mt];
-                const float ig = gate_sigmoid(a[0]), fg = gate_sigmoid(a[1]), gg = gate_tanh(a[2]), og = gate_sigmoid(a[3]);
-                c[mt] = fg * c[mt] + ig * gg;
-                h[mt] = og * gate_tanh(c[mt]);
-                p.out.ptr[ft_idx(tile, p.out.c_total, p.out.c_off + dir * H + 4 * mt + q, p.F, f) + i] = h[mt];
-            }
-        }
-    }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same kernel on fp16 x 2 split products (csrc/split2.h): both planes of the weights in registers (80 VGPRs, no LDS plane), three
-// v_mfma_f32_16x16x32_f16 per (row tile, chunk) = 30 per step instead of 60 bf16, 3 VALU per split value instead of 5.5.  h lies in
-// (-1, 1); the LayerNorm'd inputs and the weights feed the range check (vadx_dfsmn_lstm_f's range_flag).
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void lstm_f_h2_kernel(LstmFArgs p, int tiles, unsigned *__restrict__ range_flag) {
-    constexpr int IN = 40, H = 20, MT = 5, NB = 2;
-    constexpr int CH_FLOATS = NB * IN * 16, NLD = NB * IN / 16;
-    __shared__ __attribute__((aligned(16))) float xs[2][2][CH_FLOATS];      // [direction][buffer]
-    const int lane = threadIdx.x & 63, dir = threadIdx.x >> 6, q = lane >> 4, i = lane & 15;
-    const int grow = (i & 3) * H + (i >> 2);          // A-fragment row i <-> gate (i&3), unit-in-quad (i>>2)
-    f16x8 wa[MT][2][2];                               // [row tile][chunk][plane]: 80 VGPRs, resident for every tile of this workgroup
+    typename SC::frag wa[MT][2][2];                   // [row tile][chunk][plane 0, 1]: 80 VGPRs, resident for every tile of this workgroup
     float amax = 0.f;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
@@ -975,8 +865,20 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void l
             const int ch = 12 + 8 * q + e;
             v1[e] = ch < IN ? p.w_ih[dir][(size_t)row * IN + ch] : (ch == IN ? p.b_ih[dir][row] + p.b_hh[dir][row] : 0.f);
         }
-        split8_h2(v0, wa[mt][0], amax);
-        split8_h2(v1, wa[mt][1], amax);
+        if constexpr (W2_IN_LDS) {
+            typename SC::frag t[3];
+            split8(v0, t, amax);
+            wa[mt][0][0] = t[0]; wa[mt][0][1] = t[1]; w2s[dir][mt][0][lane] = t[2];
+            split8(v1, t, amax);
+            wa[mt][1][0] = t[0]; wa[mt][1][1] = t[1]; w2s[dir][mt][1][lane] = t[2];
+        } else {
+            split8(v0, wa[mt][0], amax);
+            split8(v1, wa[mt][1], amax);
+        }
+    }
+    if constexpr (W2_IN_LDS) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");          // the LDS plane is written and read by the same wave only
+        __builtin_amdgcn_wave_barrier();
     }
     const int tq = lane & 3;
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -1037,21 +939,38 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void l
                 const float xv = xrow[(ch < IN ? ch : IN - 1) * 16];
                 v1[e] = ch < IN ? xv : (ch == IN ? 1.0f : 0.f);
             }
-            f16x8 b0[2], b1[2];
-            split8_h2(v0, b0, amax);
-            split8_h2(v1, b1, amax);
-            // three products per (row tile, chunk): the two cross terms into `mid`, the leading one into `hi`; row tiles innermost so that
-            // consecutive MFMAs are independent
-            f32x4 hi[MT], mid[MT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) { hi[mt] = f32x4{0.f, 0.f, 0.f, 0.f}; mid[mt] = hi[mt]; }
-#define LF_TERM(ACC, CH, BF, AP, BP) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) ACC[mt] = vadx::mfma_f16(wa[mt][CH][AP], BF[BP], ACC[mt]);
-            LF_TERM(mid, 0, b0, 1, 0) LF_TERM(mid, 1, b1, 1, 0) LF_TERM(mid, 0, b0, 0, 1) LF_TERM(mid, 1, b1, 0, 1)
-            LF_TERM(hi, 0, b0, 0, 0) LF_TERM(hi, 1, b1, 0, 0)
-#undef LF_TERM
+            typename SC::frag b0[SC::NP], b1[SC::NP];
+            split8(v0, b0, amax);
+            split8(v1, b1, amax);
+            f32x4 acc[MT];                                   // bf16 x 3: every product; fp16 x 2: the leading ones
+            [[maybe_unused]] f32x4 mid[MT];                  // fp16 x 2: the cross terms
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
-                const f32x4 a = vadx::join2(hi[mt], mid[mt]);
+                acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if constexpr (SC::NP == 2) mid[mt] = acc[mt];
+            }
+            if constexpr (SC::NP == 3) {
+                // ONE accumulator per row tile, small products first (at 256 VGPRs the separate accumulator of the small products spilled
+                // into the chunk code; measured on its own -- tools/bf16x3_probe.sh "s6" -- the single accumulator is still closer to the float64
+                // product than the f32 MFMA chain: 1.4e-7 against 2.5e-7 of sum |w x|).  Row tiles innermost: consecutive MFMAs are independent.
+#define LF_TERM(CH, BF, AP, BP) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma_bf16(wa[mt][CH][AP], BF[BP], acc[mt]);
+#define LF_TERM2(CH, BF) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma_bf16(w2s[dir][mt][CH][lane], BF[0], acc[mt]);
+                LF_TERM2(0, b0) LF_TERM(0, b0, 1, 1) LF_TERM(0, b0, 0, 2) LF_TERM2(1, b1) LF_TERM(1, b1, 1, 1) LF_TERM(1, b1, 0, 2)
+                LF_TERM(0, b0, 1, 0) LF_TERM(0, b0, 0, 1) LF_TERM(1, b1, 1, 0) LF_TERM(1, b1, 0, 1) LF_TERM(0, b0, 0, 0) LF_TERM(1, b1, 0, 0)
+#undef LF_TERM
+#undef LF_TERM2
+            } else {
+                // three products per (row tile, chunk): the two cross terms into `mid`, the leading one into `acc`; row tiles innermost so that
+                // consecutive MFMAs are independent
+#define LF_TERM(ACC, CH, BF, AP, BP) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) ACC[mt] = vadx::mfma_f16(wa[mt][CH][AP], BF[BP], ACC[mt]);
+                LF_TERM(mid, 0, b0, 1, 0) LF_TERM(mid, 1, b1, 1, 0) LF_TERM(mid, 0, b0, 0, 1) LF_TERM(mid, 1, b1, 0, 1)
+                LF_TERM(acc, 0, b0, 0, 0) LF_TERM(acc, 1, b1, 0, 0)
+#undef LF_TERM
+            }
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                f32x4 a = acc[mt];
+                if constexpr (SC::NP == 2) a = vadx::join2(acc[mt], mid[mt]);
                 const float ig = gate_sigmoid(a[0]), fg = gate_sigmoid(a[1]), gg = gate_tanh(a[2]), og = gate_sigmoid(a[3]);
                 c[mt] = fg * c[mt] + ig * gg;
                 h[mt] = og * gate_tanh(c[mt]);
@@ -1060,7 +979,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void l
         }
     }
     }
-    if (!(amax <= vadx::H_MAX)) { atomicOr(range_flag, 1u); atomicMax(range_flag + 1, __float_as_uint(amax)); }
+    if constexpr (SC::RANGE_CHECK) vadx::range_flag_raise(range_flag, amax);
 }
 
 
@@ -1492,7 +1411,7 @@ __global__ __launch_bounds__(128 * NTILE) void lstm_t2h_kernel(LstmTArgs p, unsi
                 const float mean_c = pick(st_m, j4), inv_c = pick(st_i, j4);
 #pragma unroll
                 for (int s = 0; s < 5; ++s) { const float xv = pick(xg[s], j4); v1[2 + s] = p.ln.stats ? (xv - mean_c) * inv_c * lnw[s] + lnb[s] : xv; }
-                split8_h2(v1, bop[0], amax);
+                split8(v1, bop[0], amax);
                 {   // slots 0, 1 of chunk 1 = the own units of row tiles 8, 9 (split at the end of the previous step)
                     typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
                     u32x4_ w0 = __builtin_bit_cast(u32x4_, bop[0][0]), w1 = __builtin_bit_cast(u32x4_, bop[0][1]);
@@ -1540,7 +1459,7 @@ __global__ __launch_bounds__(128 * NTILE) void lstm_t2h_kernel(LstmTArgs p, unsi
                 float v0[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v0[e] = h[e];
-                split8_h2(v0, bown, amax);
+                split8(v0, bown, amax);
                 unsigned short a0, a1, c0, c1;
                 vadx::split2x1(h[8], a0, a1, amax);
                 vadx::split2x1(h[9], c0, c1, amax);
@@ -1585,7 +1504,7 @@ __global__ __launch_bounds__(128 * NTILE) void lstm_t2h_kernel(LstmTArgs p, unsi
         }
         __syncthreads();
     }
-    if (!(amax <= vadx::H_MAX)) { atomicOr(range_flag, 1u); atomicMax(range_flag + 1, __float_as_uint(amax)); }
+    vadx::range_flag_raise(range_flag, amax);
 }
 
 // Memory path.  In the FT layout one time step of a 16-bin group is 16 B out of each of IN*16 different 64-B rows, so
@@ -1971,10 +1890,11 @@ extern "C" int vadx_dfsmn_lstm_f(const vadx_ft_view *in, const vadx_ft_ln *ln, c
     for (int d = 0; d < 2; ++d) { p.w_ih[d] = w_ih[d]; p.w_hh[d] = w_hh[d]; p.b_ih[d] = b_ih[d]; p.b_hh[d] = b_hh[d]; }
     if (in->c == 4) hipLaunchKernelGGL(lstm_f_kernel<4>, dim3(tiles), dim3(128), 0, static_cast<hipStream_t>(stream), p);
     else if (in->c == 40 && arithmetic == VADX_ARITH_F16X2)
-        hipLaunchKernelGGL(lstm_f_h2_kernel, dim3(tiles < 1024 ? tiles : 1024), dim3(128), 0, static_cast<hipStream_t>(stream), p, tiles,
+        hipLaunchKernelGGL(lstm_f_split_kernel<vadx::SchemeH2>, dim3(tiles < 1024 ? tiles : 1024), dim3(128), 0, static_cast<hipStream_t>(stream), p, tiles,
                            static_cast<unsigned *>(range_flag));
     else if (in->c == 40 && arithmetic != VADX_ARITH_F32)      // split products: persistent workgroups (each lane splits its weights once), four per CU
-        hipLaunchKernelGGL(lstm_f_split_kernel, dim3(tiles < 1024 ? tiles : 1024), dim3(128), 0, static_cast<hipStream_t>(stream), p, tiles);
+        hipLaunchKernelGGL(lstm_f_split_kernel<vadx::SchemeB3>, dim3(tiles < 1024 ? tiles : 1024), dim3(128), 0, static_cast<hipStream_t>(stream), p, tiles,
+                           static_cast<unsigned *>(nullptr));
     else if (in->c == 40) hipLaunchKernelGGL(lstm_f_kernel<40>, dim3(tiles), dim3(128), 0, static_cast<hipStream_t>(stream), p);
     else { vadx::set_error("vadx_dfsmn_lstm_f: input channels must be 4 or 40"); return VADX_EINVAL; }
     VADX_HIP_TRY(hipGetLastError());

@@ -68,7 +68,7 @@ static int derive(const vadx_firered_cfg *c, Dev *d) {
     // split arithmetic elsewhere is refused
     d->arith = vadx::arith_internal(c->arithmetic, d->split_ok ? vadx::VADX_AR_B3 : vadx::VADX_AR_F32);
     if (d->arith < 0 || (d->arith != vadx::VADX_AR_F32 && !d->split_ok)) return -1;
-    d->np = d->arith == vadx::VADX_AR_B3 ? 3 : (d->arith == vadx::VADX_AR_H2 ? 2 : 0);
+    d->np = vadx::planes_of(d->arith);
     if (d->np) {
         const int np = d->np;
         d->q_fc1 = take(16 * 3 * np * vadx::QFRAG);                // 80 mels -> 3 chunks of 32 (k-groups 10, 11 are zero rows)
@@ -395,13 +395,11 @@ __device__ __forceinline__ void pointwise_pair(const Dev &d, const float *W1, co
     }
 }
 
-template <int AR> struct FrSchemeOf { typedef vadx::SchemeB3 type; };
-template <> struct FrSchemeOf<vadx::VADX_AR_H2> { typedef vadx::SchemeH2 type; };
 template <int AR>
 __global__ __launch_bounds__(THREADS, 2) void firered_kernel(Dev d, const float *__restrict__ Pk,
                                                              const float *__restrict__ logmel, float *__restrict__ probs) {
     constexpr bool SPLIT = AR != vadx::VADX_AR_F32;
-    typedef typename FrSchemeOf<AR>::type SC;
+    typedef typename vadx::SchemeFor<AR>::type SC;
     float amax = 0.f;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *mem = lds, *p = lds + MEM_F, *h = p + P_F;

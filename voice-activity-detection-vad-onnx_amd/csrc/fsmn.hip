@@ -74,7 +74,7 @@ static int derive(const vadx_fsmn_dims *c, Dev *d) {
     // callers that run the range protocol, as FsmnEngine does; an explicit split arithmetic on dims outside the tile is refused
     d->arith = vadx::arith_internal(c->arithmetic, d->split_ok ? vadx::VADX_AR_B3 : vadx::VADX_AR_F32);
     if (d->arith < 0 || (d->arith != vadx::VADX_AR_F32 && !d->split_ok)) return -1;
-    d->np = d->arith == vadx::VADX_AR_B3 ? 3 : (d->arith == vadx::VADX_AR_H2 ? 2 : 0);
+    d->np = vadx::planes_of(d->arith);
     const int np = d->np;
     d->q_in1 = take(d->Ap / 16 * NCH_IN1 * np * QFRAG); d->q_b1 = take(d->Ap); d->q_mbar = take(NMEL);
     d->q_in2 = take(d->Lp / 16 * d->nch_A * np * QFRAG);
@@ -448,13 +448,11 @@ __device__ __forceinline__ float gate(const Dev &d, const float *ps, const float
 }
 
 // AR: the arithmetic of the dense layers (split_scheme.h: 0 float32 MFMAs, 1 bf16 x 3, 2 fp16 x 2)
-template <int AR> struct SchemeOf { typedef vadx::SchemeB3 type; };
-template <> struct SchemeOf<vadx::VADX_AR_H2> { typedef vadx::SchemeH2 type; };
 template <int AR>
 __device__ __forceinline__ void run_chunk(const Dev &d, const float *Pk, const float *lm, const float *const *cin,
                                           float *const *cout, float *lds, float &amax) {
     constexpr bool SPLIT = AR != vadx::VADX_AR_F32;
-    typedef typename SchemeOf<AR>::type SC;
+    typedef typename vadx::SchemeFor<AR>::type SC;
     float *bufA = lds, *bufB = lds + BUFA, *bufP = bufB + BUFB;
     float *small = SPLIT ? reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(lds) + SQ_ARENA) : bufP + BUFP;
     float *ps = small, *red = small + 128;

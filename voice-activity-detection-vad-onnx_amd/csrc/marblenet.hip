@@ -100,9 +100,6 @@ __device__ __forceinline__ void gemm8_h2(const vadx::QLayerArgs &a, float &amax)
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) vadx::qlayer_store<SC, 2, OUT_PLANES>(a, wave, mt, SC::join(hi[0][mt], lo[0][mt]), lane, amax);
 }
-__device__ __forceinline__ void range_flag_words(unsigned *flag, float amax) {
-    if (!(amax <= vadx::H_MAX)) { atomicOr(flag, 1u); atomicMax(flag + 1, __float_as_uint(amax)); }
-}
 
 // AR = 2: the prologue form only (depthwise, no residual branch, 128 filters): filter -> split pass -> gemm8_h2 (fp16 x 2 split products)
 template <int KT, int DT, int ST, int AR = 0>
@@ -225,7 +222,7 @@ __global__ __launch_bounds__(THREADS, 2) void sepconv_block_kernel(
         __syncthreads();
         gemm8_h2<false>(vadx::QLayerArgs{pw_w, c.coutp / 16, kgroups / 4, pw_b, c.relu ? 1 : 0, DP, kgroups * TILE * 16,
                                          reinterpret_cast<unsigned char *>(OUT), 0, A_LD, nullptr}, amax);
-        range_flag_words(range_flag, amax);
+        vadx::range_flag_raise(range_flag, amax);
     } else {
         LayerArgs a{pw_w, c.cinp, c.coutp / 16, 1, c.cinp / 16, 0, 0, pw_b, (c.relu && !c.cres) ? 1 : 0,
                     act, lda, 0, OUT, A_LD, 0, nullptr, nullptr};
@@ -590,10 +587,7 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
         const int ch = e / TILE, m = e - ch * TILE;
         if (t0 + m < c.T) yb[(long long)ch * c.T + t0 + m] = fmaxf(OUT[ch * A_LD + m] + ROUT[ch * A_LD + m], 0.f);
     }
-    if (AR >= vadx::VADX_AR_H2 && !(amax <= vadx::H_MAX)) {          // an operand left the fp16 range: the host recomputes this batch on float32
-        atomicOr(range_flag, 1u);
-        atomicMax(range_flag + 1, __float_as_uint(amax));
-    }
+    if (AR >= vadx::VADX_AR_H2) vadx::range_flag_raise(range_flag, amax);          // an operand left the fp16 range: the host recomputes this batch on float32
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -702,7 +696,7 @@ __global__ __launch_bounds__(THREADS, 6) void marblenet_tail_kernel(
         s0[(long long)b * c.T + t0 + tid] = e0 * inv;
         s1[(long long)b * c.T + t0 + tid] = e1 * inv;
     }
-    if (AR == vadx::VADX_AR_H2) range_flag_words(range_flag, amax);
+    if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(range_flag, amax);
 }
 
 // decoder Linear(C -> 2) + softmax (wrapper :270-274): one thread per (clip, frame)

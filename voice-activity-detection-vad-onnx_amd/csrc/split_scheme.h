@@ -68,6 +68,11 @@ struct SchemeH2 {
     }
 };
 
+// internal arithmetic number -> its scheme (kernels templated on AR), and -> its number of planes (0 = float32, no split)
+template <int AR> struct SchemeFor { typedef SchemeB3 type; };
+template <> struct SchemeFor<VADX_AR_H2> { typedef SchemeH2 type; };
+inline int planes_of(int arith) { return arith == VADX_AR_B3 ? SchemeB3::NP : (arith == VADX_AR_H2 ? SchemeH2::NP : 0); }
+
 // host: read a SchemeH2 kernel's two range-flag words [sticky flag, bits of the largest |x|] from the device (synchronises `stream`) and, with
 // reset != 0, clear them there
 inline int range_flag_read(const float *two_words, int reset, uint32_t *flag_host, float *amax_host, void *stream) {
@@ -82,13 +87,16 @@ inline int range_flag_read(const float *two_words, int reset, uint32_t *flag_hos
 }
 
 #if defined(__HIPCC__)
-// the end-of-kernel range check of a SchemeH2 kernel: `flag` = two words inside the kernel's packed blob [sticky flag, bits of the largest |x|]
-__device__ __forceinline__ void range_flag_raise(const float *flag_words, float amax) {
+// the end-of-kernel range check of a SchemeH2 kernel: `flag` = two words [sticky flag, bits of the largest |x|], the caller's own or (the
+// const float * form) inside the kernel's packed blob
+__device__ __forceinline__ void range_flag_raise(unsigned *flag_words, float amax) {
     if (!(amax <= H_MAX)) {
-        unsigned *fl = reinterpret_cast<unsigned *>(const_cast<float *>(flag_words));
-        atomicOr(fl, 1u);
-        atomicMax(fl + 1, __float_as_uint(amax));
+        atomicOr(flag_words, 1u);
+        atomicMax(flag_words + 1, __float_as_uint(amax));
     }
+}
+__device__ __forceinline__ void range_flag_raise(const float *flag_words, float amax) {
+    range_flag_raise(reinterpret_cast<unsigned *>(const_cast<float *>(flag_words)), amax);
 }
 #endif
 

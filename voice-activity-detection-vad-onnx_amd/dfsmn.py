@@ -501,24 +501,22 @@ class DfsmnEngine:
         per = max(1, self.sub_batch // W)                  # clips per sub-batch (activations are ~30 MB per window)
         # (alternating the independent sub-batches over two or three side streams so that one's HBM-bound launches overlap another's
         # matrix-pipe-bound ones was measured: 2986 / 2985 ms against 2990 -- every launch fills the chip by itself)
-        def sweep():
-            for b0 in range(0, B, per):
-                nb = min(per, B - b0)
-                v, a = self._run_sub(near[b0:b0 + nb], None if far is None else far[b0:b0 + nb], W, ws)
-                vad[b0 * W:(b0 + nb) * W] = v
-                if return_aec:
-                    aec_all[b0 * W:(b0 + nb) * W] = a
-        sweep()
         net = self.iccrn
-        if (net.arithmetic or _lib.gemm_mode()) == "h2" and int(net.range_flag[0].item()) != 0:
-            # an input of the fp16 x 2 time LSTM left the fp16 range (one 4-byte read-back, synchronises): the batch again on float32 MFMAs
-            self.range_fallbacks += 1
-            net.range_flag.zero_()
-            net.lstm_t_h2 = False
+
+        def sweep(lstm_h2):
+            prev, net.lstm_t_h2 = net.lstm_t_h2, net.lstm_t_h2 and lstm_h2
             try:
-                sweep()
+                for b0 in range(0, B, per):
+                    nb = min(per, B - b0)
+                    v, a = self._run_sub(near[b0:b0 + nb], None if far is None else far[b0:b0 + nb], W, ws)
+                    vad[b0 * W:(b0 + nb) * W] = v
+                    if return_aec:
+                        aec_all[b0 * W:(b0 + nb) * W] = a
             finally:
-                net.lstm_t_h2 = True
+                net.lstm_t_h2 = prev
+        # an input of an fp16 x 2 LSTM that leaves the fp16 range (one 4-byte read-back, synchronises): the batch again with the LSTMs' fp16 x 2
+        # forms off (the fallback is no arithmetic of its own: the net keeps its mode, see Iccrn.lstm_t_h2)
+        _lib.range_guarded(self, net.arithmetic or _lib.gemm_mode(), lambda m: sweep(m is not None), lambda: _lib.take_flag(net.range_flag), None)
         return (vad, aec_all) if return_aec else vad
 
     def run_from_host(self, host_near_i16, host_far_i16, windows_per_clip=1, win_stride=None, chunk_clips=64, feed=None):

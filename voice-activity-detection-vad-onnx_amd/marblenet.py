@@ -117,13 +117,8 @@ class MarbleNetEngine:
         block_in = None
         lib = _lib.lib()
         if self.fused:
-            mode = self.mode()
-            out = self._run_fused(x, N, T, mode)
-            if mode == "h2" and int(self._flag[0].item()) != 0:      # (synchronises) an activation left the fp16 range: float32 MFMAs
-                self.range_fallbacks += 1
-                self._flag.zero_()
-                out = self._run_fused(x, N, T, "f32")
-            return out
+            # an activation that leaves the fp16 range: the batch again on float32 MFMAs
+            return _lib.range_guarded(self, self.mode(), lambda m: self._run_fused(x, N, T, m), lambda: _lib.take_flag(self._flag), "f32")
         with t.cuda.device(self.device):
             for st in self.stages:
                 cfg = st["cfg"]

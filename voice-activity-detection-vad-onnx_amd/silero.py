@@ -92,7 +92,6 @@ def _pack(w, sample_rate):
 WORKSPACE_CAP_BYTES = 8 << 30     # clips(): above this the gate-preactivation workspace is reused span by span
 
 
-ENCODER_MODES = {"f32": _lib.ARITH["f32"], "split": _lib.ARITH["split"], "h2": _lib.ARITH["h2"]}      # name -> VADX_ARITH_*
 _default_mode = [None]
 
 
@@ -102,17 +101,7 @@ def encoder_mode(mode=None):
     outside the fp16 range are detected and the batch recomputed on "split").  A Python-side default only -- the C ABI takes the
     arithmetic with every call (include/vadx.h: vadx_silero_cfg).  Returns the mode that was active; `None` only queries.  The initial
     value comes from VADX_SILERO_ENCODER, read once here."""
-    if _default_mode[0] is None:
-        e = os.environ.get("VADX_SILERO_ENCODER", "").strip().lower()
-        _default_mode[0] = {"0": "f32", "1": "split", "2": "h2", "bf16x3": "split", "f16x2": "h2"}.get(e, e) if e else "h2"
-        if _default_mode[0] not in ENCODER_MODES:
-            raise ValueError(f"VADX_SILERO_ENCODER must be one of {sorted(ENCODER_MODES)}, got {e!r}")
-    prev = _default_mode[0]
-    if mode is not None:
-        if mode not in ENCODER_MODES:
-            raise ValueError(f"encoder mode must be one of {sorted(ENCODER_MODES)}, got {mode!r}")
-        _default_mode[0] = mode
-    return prev
+    return _lib.default_arith(_default_mode, "VADX_SILERO_ENCODER", "encoder", mode)
 
 
 class SileroEngine:
@@ -164,7 +153,7 @@ class SileroEngine:
     def cfg(self, mode=None, sampling_rate=16000):
         """ctypes pointer to a vadx_silero_cfg for `mode` (default: this engine's current mode) and the network of `sampling_rate`"""
         c = _lib.SileroCfg()
-        c.arithmetic = ENCODER_MODES[mode or self.mode(sampling_rate)]
+        c.arithmetic = _lib.ARITH[mode or self.mode(sampling_rate)]
         c.sample_rate = 8000 if int(sampling_rate) == 8000 else 0
         return C.byref(c)
 
@@ -179,14 +168,7 @@ class SileroEngine:
     def _guarded(self, run, sampling_rate=16000):
         """run(mode) -> result.  On "h2" the result stands only if no activation left the fp16 range; otherwise the batch is recomputed on
         "split" (bf16 terms have float32's range).  One 8-byte read-back + stream synchronisation per guarded call."""
-        m = self.mode(sampling_rate)
-        out = run(m)
-        if m == "h2":
-            flag, amax = self.range_flag(sampling_rate=sampling_rate)
-            if flag:
-                self.range_fallbacks += 1
-                out = run("split")
-        return out
+        return _lib.range_guarded(self, self.mode(sampling_rate), run, lambda: self.range_flag(sampling_rate=sampling_rate)[0], "split")
 
     def _check_workspace_cap(self, batch, steps, who):
         """The whole-batch gx workspace is 32 KB per 16-clip group and window; `clips` falls back to spans above WORKSPACE_CAP_BYTES,
