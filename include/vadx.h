@@ -47,8 +47,9 @@ extern "C" {
  * 8: new entry points only, no existing signature or behaviour changed: the Silero stream path vadx_silero_iter_params,
  *    vadx_silero_stream_state_bytes, vadx_silero_stream_workspace_bytes, vadx_silero_stream_run.
  * 9: additive: vadx_silero_cfg's reserved words became `ext` {sample_rate, reserved1, reserved2} (same size; 0 = 16000, as before), 8000 selects the 8 kHz
- *    network on every Silero launch; vadx_silero_packed_floats_sr, vadx_silero_pack_host_sr pack the 8 kHz blob. */
-#define VADX_ABI_VERSION 9
+ *    network on every Silero launch; vadx_silero_packed_floats_sr, vadx_silero_pack_host_sr pack the 8 kHz blob.
+ * 10: new entry points only: the FSMN stream path vadx_fsmn_stream_state_bytes, vadx_fsmn_stream_windows, vadx_fsmn_stream_run. */
+#define VADX_ABI_VERSION 10
 
 /* Arithmetic of the products whose one operand is a constant (every weight matrix, every DFT table) -- float32 RESULTS in all of them:
  *   F32     v_mfma_f32_16x16x4_f32 on the float32 operands themselves;
@@ -381,6 +382,58 @@ typedef struct vadx_fsmn_loop_params {   /* FSMN/Inference_FSMN_VAD_ONNX.py:16-2
 int vadx_fsmn_clips(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db,
                     int batch, int windows_per_clip, const vadx_fsmn_loop_params *lp, float *cache_ws,
                     uint8_t *flags, float *noise_trace, void *stream);
+
+/* Streaming FSMN (ABI 10): S live streams advance by `windows` analysis windows per tick; what the reference loop carries from window to
+ * window -- the four FIR caches, the noise floor it feeds back, the vote's `silence` and the (look_backward + 1) * 160 samples two
+ * consecutive windows share -- lives in a device RECORD of vadx_fsmn_stream_state_bytes(S, look_backward) bytes.  The record is opaque
+ * except that
+ *   - its first S*4*128*19 floats are the caches [S][4][128][19] (cache_0..3 of vadx_fsmn_run, per stream);
+ *   - a record of all zero bytes is S streams in their reset state (no init call);
+ *   - its size is a multiple of 16 bytes; records are 16-byte aligned.
+ * It also carries a 64-bit count of the windows each stream has done since its reset (the host turns flag positions into times with it).
+ * One tick is four calls on one HIP stream, the middle two unchanged:
+ *   vadx_fsmn_stream_windows   samples + carry -> window_buf int16 [S*windows][window_len], the new carry
+ *   vadx_fsmn_window_stats     on window_buf with batch = S, windows_per_clip = windows, row_stride = windows * window_len, win_stride = window_len
+ *   vadx_frontend_logmel_means the same arguments
+ *   vadx_fsmn_stream_run       the window loop -> flags, tail, the rest of the record
+ * Both stream calls of a tick take the SAME state_in, state_out, reset and active.  state_in is never written (a tick can be recomputed
+ * from it, which the range protocol needs); state_in and state_out must not overlap.  vadx_fsmn_stream_windows writes only the carry and
+ * the "has a carry" word of state_out, vadx_fsmn_stream_run everything else.
+ * reset (NULL or uint8 [S]): != 0 = back to the reset state before this tick.  active (NULL or uint8 [S]): 0 = no audio for this stream
+ * this tick -- its record in state_out is a bitwise copy of state_in's (a reset request on an inactive stream is ignored), its flags and
+ * tail are 255 and its noise_trace NaN.
+ * Range protocol per tick: with VADX_ARITH_F16X2 dims read vadx_fsmn_range_flag after vadx_fsmn_stream_run and, when it is raised, call
+ * vadx_fsmn_stream_run again with the BF16X3 dims and blob on the same arguments (same state_in, same state_out, same logmel / db):
+ * every byte the first call wrote is written again.  The window and front-end calls do not depend on the arithmetic.
+ * The flags are bit for bit those of vadx_fsmn_clips over the concatenated audio. */
+
+/* Bytes of the record of `streams` streams (0 for streams <= 0 or look_backward < 0). */
+size_t vadx_fsmn_stream_state_bytes(int streams, int look_backward);
+
+/* Window assembly.  stride = window_len - (look_backward + 1) * 160.  samples int16 [S][row_stride] holds each stream's NEW samples from
+ * column 0: windows * stride of them for a stream that has a carry, window_len + (windows - 1) * stride for one that has none (zero
+ * record, or reset this tick) -- the caller sizes every row for the streams it knows to be in that state; row_stride >= windows * stride
+ * is all this call can check.  Window j of a stream is [j * stride, j * stride + window_len) of (carry ++ new samples); the last
+ * (look_backward + 1) * 160 samples become the carry in state_out.  An inactive stream's windows are zeros.  samples, window_buf and the
+ * records 16-byte aligned, row_stride a multiple of 8.  Returns VADX_EINVAL for a NULL pointer, windows < 1, look_backward outside
+ * [0, window_len / 160 + 1) or leaving no stride, or overlapping records.
+ * Replaces the slicing `audio[..., slice_start:slice_end]` + `slice_start += stride_step` of FSMN/Inference_FSMN_VAD_ONNX.py:162-167,
+ * 176-234 for audio that arrives in pieces. */
+int vadx_fsmn_stream_windows(const int16_t *samples, int64_t row_stride, int streams, int windows, int window_len,
+                             int look_backward, const uint8_t *reset, const uint8_t *active,
+                             const void *state_in, void *state_out, int16_t *window_buf, void *stream);
+
+/* The window loop of one tick, one workgroup per stream: logmel [S*windows][T][80] and db [S*windows][T] are the front-end over
+ * window_buf.  flags u8 [S][windows * (T - look_backward)]: the voted silence flags of this tick's windows (1 = silence), the next
+ * entries of the reference's `saved` list.  tail u8 [S][look_backward] (may be NULL when look_backward = 0): what the plain rule appends
+ * if the stream ENDS with this tick; it does not touch the carried vote state, so the stream can go on.  noise_trace (optional)
+ * [S][windows] = noise floor after each window.  lp as for vadx_fsmn_clips; 0 <= look_backward < T - 2.  Returns VADX_EINVAL for a NULL
+ * pointer, windows < 1, look_backward out of range, or overlapping records.
+ * Replaces the while-loop body + tail, FSMN/Inference_FSMN_VAD_ONNX.py:162-167, 176-234, for S streams that arrive in pieces. */
+int vadx_fsmn_stream_run(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db,
+                         int streams, int windows, const vadx_fsmn_loop_params *lp,
+                         const uint8_t *reset, const uint8_t *active, const void *state_in, void *state_out,
+                         uint8_t *flags, uint8_t *tail, float *noise_trace, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * FireRedVAD / FireRedAED DetectModel and VadPostprocessor (row a16)

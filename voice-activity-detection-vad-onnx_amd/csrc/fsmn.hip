@@ -567,6 +567,156 @@ __global__ __launch_bounds__(THREADS, 2) void fsmn_clips_kernel(Dev d, const flo
     if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
 }
 
+// ---- live streams: the same loop, k windows per call, everything it carries in a device record -----------------------------------------
+// The record of S streams (include/vadx.h states the contract): caches f32 [S][4][128][19] | header u32 [S][8] | carry int16 [S][C],
+// C = (look_backward + 1) * 160 = the samples two consecutive windows share.  Header words: 0 noise floor (f32 bits), 1 silence,
+// 2 primed (the stream has a carry), 3 zero, 4-5 windows done (u64), 6-7 zero.  The window kernel owns words 2-3 and the carry, the
+// stream kernel the caches and the other words; zero bytes = un-primed = the reset state (noise floor and silence take their initial
+// values when an un-primed stream starts).
+constexpr int CACHE_FLOATS = NLAYER * PROJ * HIST, HDR_WORDS = 8, H_NOISE = 0, H_SIL = 1, H_PRIMED = 2, H_DONE = 4;
+static size_t rec_hdr(int S) { return (size_t)S * CACHE_FLOATS * sizeof(float); }
+static size_t rec_carry(int S) { return rec_hdr(S) + (size_t)S * HDR_WORDS * 4; }
+static size_t rec_bytes(int S, int C) { return rec_carry(S) + (size_t)S * C * sizeof(int16_t); }
+
+struct WinArgs {
+    const int16_t *samples; long long row_stride;   // [S][row_stride]: k * stride new samples (L + (k-1) * stride for an un-primed stream)
+    int k, L, C;                                    // windows per tick, window length, carry length; stride = L - C
+    const unsigned char *reset, *active;            // optional [S]
+    const unsigned char *sin; unsigned char *sout;  // records
+    size_t hdr, carry;                              // byte offsets of the header / carry sections
+    int16_t *wbuf;                                  // [S * k][L]
+};
+
+// Window assembly (the slicing of Inference_FSMN_VAD_ONNX.py:162-167 for a stream that arrives in pieces): a stream's timeline of this tick
+// is its carry followed by its new samples (no carry before the first tick); window j = timeline[j * stride, j * stride + L), the new carry
+// = the timeline's last C samples.  One workgroup per (stream, window) plus one per stream for the carry; 16-byte runs throughout (C, stride
+// and L are multiples of 8 samples).  An inactive stream keeps its carry and gets windows of zeros (the front-end runs over them; the
+// stream kernel ignores the result).
+__global__ __launch_bounds__(256) void fsmn_stream_windows_kernel(WinArgs a) {
+    typedef short s16x8 __attribute__((ext_vector_type(8)));
+    const int s = blockIdx.x / (a.k + 1), j = blockIdx.x - s * (a.k + 1), tid = threadIdx.x;
+    const unsigned *hin = reinterpret_cast<const unsigned *>(a.sin + a.hdr) + (size_t)s * HDR_WORDS;
+    unsigned *hout = reinterpret_cast<unsigned *>(a.sout + a.hdr) + (size_t)s * HDR_WORDS;
+    const s16x8 *cin = reinterpret_cast<const s16x8 *>(a.sin + a.carry + (size_t)s * a.C * sizeof(int16_t));
+    s16x8 *cout = reinterpret_cast<s16x8 *>(a.sout + a.carry + (size_t)s * a.C * sizeof(int16_t));
+    s16x8 *win = reinterpret_cast<s16x8 *>(a.wbuf + ((size_t)s * a.k + (j < a.k ? j : 0)) * a.L);
+    const int nc = a.C / 8, nl = a.L / 8, ns = (a.L - a.C) / 8;
+    if (a.active && !a.active[s]) {
+        if (j < a.k) {
+            for (int v = tid; v < nl; v += 256) win[v] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        } else {
+            for (int v = tid; v < nc; v += 256) cout[v] = cin[v];
+            if (tid < 2) hout[H_PRIMED + tid] = hin[H_PRIMED + tid];
+        }
+        return;
+    }
+    const bool primed = hin[H_PRIMED] != 0 && !(a.reset && a.reset[s]);
+    const s16x8 *smp = reinterpret_cast<const s16x8 *>(a.samples + (long long)s * a.row_stride);
+    auto timeline = [&](int v) { return primed ? (v < nc ? cin[v] : smp[v - nc]) : smp[v]; };       // 8-sample run v
+    if (j < a.k) {
+        for (int v = tid; v < nl; v += 256) win[v] = timeline(j * ns + v);
+    } else {
+        for (int v = tid; v < nc; v += 256) cout[v] = timeline(a.k * ns + v);        // the timeline holds k * stride + C samples
+        if (tid < 2) hout[H_PRIMED + tid] = tid == 0 ? 1u : 0u;
+    }
+}
+
+struct StreamArgs {
+    const float *logmel, *db;             // [S*k][T][80], [S*k][T]: the front-end over the window buffer
+    const unsigned char *sin; unsigned char *sout; size_t hdr;
+    const unsigned char *reset, *active;  // optional [S]
+    int k, slide, lb, ntail;              // windows per tick, slide_range, look_backward of the vote (>= 1), tail flags (= look_backward)
+    float thr, noise0, snr;
+    double speaking, silence_score;
+    unsigned char *flags, *tail;          // [S][k*slide], [S][ntail]
+    float *noise_trace;                   // optional [S][k]
+};
+
+// fsmn_clips_kernel's window loop with its state (four caches, noise floor, silence) loaded from state_in and stored to state_out; one
+// workgroup per stream.  state_in is only read: run_chunk reads the caches of a window's first tile from `cin` and everything later from
+// `cout`, so window 0 points cin at state_in and nothing is copied.  The tail of the tick's last window follows the plain rule on a COPY
+// of silence: the carried value is the one the next tick's vote continues from.
+template <int AR>
+__global__ __launch_bounds__(THREADS, 2) void fsmn_stream_kernel(Dev d, const float *__restrict__ Pk, StreamArgs c) {
+    constexpr bool SPLIT = AR != vadx::VADX_AR_F32;
+    float amax = 0.f;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    float *small = SPLIT ? reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(lds) + SQ_ARENA) : lds + BUFA + BUFB + BUFP;
+    float *ps = small, *red = small + 128, *sc = small + 640, *cnt = small + 768;
+    const float *cache_in = reinterpret_cast<const float *>(c.sin) + (size_t)s * CACHE_FLOATS;
+    float *cache_out = reinterpret_cast<float *>(c.sout) + (size_t)s * CACHE_FLOATS;
+    const unsigned *hin = reinterpret_cast<const unsigned *>(c.sin + c.hdr) + (size_t)s * HDR_WORDS;
+    unsigned *hout = reinterpret_cast<unsigned *>(c.sout + c.hdr) + (size_t)s * HDR_WORDS;
+    unsigned char *fl = c.flags + (size_t)s * c.k * c.slide, *tl = c.tail + (size_t)s * c.ntail;
+    if (c.active && !c.active[s]) {        // no audio this tick: the record passes through bit for bit, a reset request is ignored
+        const unsigned *ci = reinterpret_cast<const unsigned *>(cache_in);
+        unsigned *co = reinterpret_cast<unsigned *>(cache_out);
+        for (int e = tid; e < CACHE_FLOATS; e += THREADS) co[e] = ci[e];
+        if (tid < HDR_WORDS && (tid < H_PRIMED || tid >= H_DONE)) hout[tid] = hin[tid];
+        for (int e = tid; e < c.k * c.slide; e += THREADS) fl[e] = 255;
+        for (int e = tid; e < c.ntail; e += THREADS) tl[e] = 255;
+        if (c.noise_trace) for (int e = tid; e < c.k; e += THREADS) c.noise_trace[(size_t)s * c.k + e] = __uint_as_float(0x7fc00000u);
+        return;
+    }
+    const bool fresh = hin[H_PRIMED] == 0 || (c.reset && c.reset[s]);
+    if (fresh) {                           // un-primed: zero caches (written to state_out, read back as window 0's input)
+        for (int e = tid; e < CACHE_FLOATS; e += THREADS) cache_out[e] = 0.f;
+        __syncthreads();
+    }
+    float *cout[NLAYER];
+#pragma unroll
+    for (int l = 0; l < NLAYER; ++l) cout[l] = cache_out + l * PROJ * HIST;
+    float noise = fresh ? c.noise0 : __uint_as_float(hin[H_NOISE]);
+    int silence = fresh ? 1 : (int)hin[H_SIL];                                    // carried by thread 0
+    for (int k = 0; k < c.k; ++k) {
+        const size_t widx = (size_t)s * c.k + k;
+        const float *cin[NLAYER];
+#pragma unroll
+        for (int l = 0; l < NLAYER; ++l) cin[l] = (k == 0 && !fresh ? cache_in : cache_out) + l * PROJ * HIST;
+        run_chunk<AR>(d, Pk, c.logmel + widx * d.T * NMEL, cin, cout, lds, amax);
+        const float noisy = gate(d, ps, c.db + widx * d.T, c.thr, noise, nullptr, nullptr, sc, red);
+        // look-ahead vote: cnt[i] = #{ j in [1,lb) : sc[i+j] != 0 }
+        if (tid < c.slide) {
+            float v = 0.f;
+            for (int j = 1; j < c.lb; ++j) v += sc[tid + j];
+            cnt[tid] = v;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const double inv_lb = 1.0 / (double)c.lb;
+            for (int i = 0; i < c.slide; ++i) {
+                if (silence) {
+                    if (sc[i] != 0.f) silence = !((1.0 + (double)cnt[i]) * inv_lb >= c.speaking);
+                    else silence = 1;
+                } else {
+                    if (sc[i] != 1.f) silence = !((1.0 + (double)((c.lb - 1) - cnt[i])) * inv_lb <= c.silence_score);
+                    else silence = 0;
+                }
+                fl[k * c.slide + i] = (unsigned char)silence;
+            }
+            if (k == c.k - 1) {            // what the tail would read if the stream ended here: plain rule (:223-234)
+                int st = silence;
+                for (int i = c.slide; i < d.T; ++i) {
+                    st = st ? !(sc[i] != 0.f) : (sc[i] != 1.f);
+                    tl[i - c.slide] = (unsigned char)st;
+                }
+            }
+        }
+        if (noisy > 0.0f) noise = 0.5f * ((noise + noisy) + c.snr);
+        if (c.noise_trace && tid == 0) c.noise_trace[widx] = noise;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        hout[H_NOISE] = __float_as_uint(noise);
+        hout[H_SIL] = (unsigned)silence;
+        const unsigned long long done = fresh ? 0ull : *reinterpret_cast<const unsigned long long *>(hin + H_DONE);
+        *reinterpret_cast<unsigned long long *>(hout + H_DONE) = done + (unsigned long long)c.k;
+        hout[H_DONE + 2] = 0u; hout[H_DONE + 3] = 0u;
+    }
+    if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
+}
+
 // frame energy in dB/10 of the prepped window (FSMN/Export_FSMN_VAD.py:93-97): one workgroup per window
 __global__ void fsmn_energy_kernel(const int16_t *__restrict__ audio, long long row_stride, long long win_stride,
                                    int windows_per_clip, int window_len, int n_fft, int hop, int T,
@@ -785,6 +935,9 @@ static int set_lds_attr() {
     VADX_DYN_LDS(fsmn_clips_kernel<1>, SQ_LDS_BYTES);
     VADX_DYN_LDS(fsmn_run_kernel<2>, SQ_LDS_BYTES);
     VADX_DYN_LDS(fsmn_clips_kernel<2>, SQ_LDS_BYTES);
+    VADX_DYN_LDS(fsmn_stream_kernel<0>, LDS_FLOATS * sizeof(float));
+    VADX_DYN_LDS(fsmn_stream_kernel<1>, SQ_LDS_BYTES);
+    VADX_DYN_LDS(fsmn_stream_kernel<2>, SQ_LDS_BYTES);
     return VADX_OK;
 }
 
@@ -876,6 +1029,76 @@ extern "C" int vadx_fsmn_clips(const vadx_fsmn_dims *dims, const float *packed, 
     else
         hipLaunchKernelGGL(fsmn_clips_kernel<0>, dim3(batch), dim3(THREADS), LDS_FLOATS * sizeof(float),
                            static_cast<hipStream_t>(stream), d, packed, c);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+extern "C" size_t vadx_fsmn_stream_state_bytes(int streams, int look_backward) {
+    return streams > 0 && look_backward >= 0 ? rec_bytes(streams, (look_backward + 1) * 160) : 0;
+}
+
+// true when two records of `bytes` bytes share a byte
+static bool records_overlap(const void *a, const void *b, size_t bytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return !(x + bytes <= y || y + bytes <= x);
+}
+
+extern "C" int vadx_fsmn_stream_windows(const int16_t *samples, int64_t row_stride, int streams, int windows, int window_len,
+                                        int look_backward, const uint8_t *reset, const uint8_t *active, const void *state_in,
+                                        void *state_out, int16_t *window_buf, void *stream) {
+    VADX_REQUIRE(samples && state_in && state_out && window_buf, "vadx_fsmn_stream_windows: NULL argument");
+    VADX_REQUIRE(streams > 0 && windows >= 1 && (long long)streams * ((long long)windows + 1) < (1ll << 31),
+                 "vadx_fsmn_stream_windows: streams=%d windows=%d", streams, windows);
+    VADX_REQUIRE(window_len >= 512 && window_len % 8 == 0, "vadx_fsmn_stream_windows: window_len=%d must be a multiple of 8, at least 512", window_len);
+    const int T = window_len / 160 + 1, C = (look_backward + 1) * 160, stride = window_len - C;
+    VADX_REQUIRE(look_backward >= 0 && look_backward < T && stride > 0,
+                 "vadx_fsmn_stream_windows: look_backward=%d outside [0, %d) or no stride left (window_len - (look_backward + 1) * 160 = %d)",
+                 look_backward, T, stride);
+    VADX_REQUIRE(row_stride >= (int64_t)windows * stride && row_stride % 8 == 0,
+                 "vadx_fsmn_stream_windows: row_stride=%lld must be a multiple of 8 and hold windows * stride = %lld samples",
+                 (long long)row_stride, (long long)windows * stride);
+    VADX_REQUIRE(!records_overlap(state_in, state_out, rec_bytes(streams, C)), "vadx_fsmn_stream_windows: state_in and state_out overlap");
+    VADX_REQUIRE(((reinterpret_cast<uintptr_t>(samples) | reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out) |
+                   reinterpret_cast<uintptr_t>(window_buf)) & 15) == 0,
+                 "vadx_fsmn_stream_windows: samples, records and window_buf must be 16-byte aligned");
+    WinArgs a;
+    a.samples = samples; a.row_stride = (long long)row_stride; a.k = windows; a.L = window_len; a.C = C; a.reset = reset; a.active = active;
+    a.sin = static_cast<const unsigned char *>(state_in); a.sout = static_cast<unsigned char *>(state_out);
+    a.hdr = rec_hdr(streams); a.carry = rec_carry(streams); a.wbuf = window_buf;
+    hipLaunchKernelGGL(fsmn_stream_windows_kernel, dim3((unsigned)(streams * (windows + 1))), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+extern "C" int vadx_fsmn_stream_run(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db, int streams,
+                                    int windows, const vadx_fsmn_loop_params *lp, const uint8_t *reset, const uint8_t *active,
+                                    const void *state_in, void *state_out, uint8_t *flags, uint8_t *tail, float *noise_trace, void *stream) {
+    Dev d;
+    VADX_REQUIRE(dims && packed && logmel && db && lp && state_in && state_out && flags, "vadx_fsmn_stream_run: NULL argument");
+    VADX_REQUIRE(derive(dims, &d) == 0, "vadx_fsmn_stream_run: unsupported dims");
+    VADX_REQUIRE(streams > 0 && windows >= 1, "vadx_fsmn_stream_run: streams=%d windows=%d", streams, windows);
+    VADX_REQUIRE(lp->look_backward >= 0 && lp->look_backward < d.T - 2 && d.T - lp->look_backward <= 128 && d.T <= 112,
+                 "vadx_fsmn_stream_run: look_backward=%d frames=%d unsupported (0 <= look_backward < frames - 2: the windows must advance)",
+                 lp->look_backward, d.T);
+    VADX_REQUIRE(tail || lp->look_backward == 0, "vadx_fsmn_stream_run: NULL tail with look_backward=%d", lp->look_backward);
+    VADX_REQUIRE(!records_overlap(state_in, state_out, rec_bytes(streams, (lp->look_backward + 1) * 160)),
+                 "vadx_fsmn_stream_run: state_in and state_out overlap");
+    VADX_REQUIRE(((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 15) == 0,
+                 "vadx_fsmn_stream_run: records must be 16-byte aligned");
+    int rc = set_lds_attr();
+    if (rc) return rc;
+    StreamArgs c;
+    c.logmel = logmel; c.db = db; c.sin = static_cast<const unsigned char *>(state_in); c.sout = static_cast<unsigned char *>(state_out);
+    c.hdr = rec_hdr(streams); c.reset = reset; c.active = active; c.k = windows;
+    c.lb = lp->look_backward > 0 ? lp->look_backward : 1;          // as vadx_fsmn_clips: slide_range is taken before a zero look_backward becomes 1
+    c.slide = d.T - lp->look_backward; c.ntail = lp->look_backward;
+    c.thr = lp->one_minus_speech_threshold; c.noise0 = lp->noise_db_init; c.snr = lp->snr_threshold;
+    c.speaking = lp->speaking_score; c.silence_score = lp->silence_score;
+    c.flags = flags; c.tail = tail; c.noise_trace = noise_trace;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (d.arith == vadx::VADX_AR_H2) hipLaunchKernelGGL(fsmn_stream_kernel<2>, dim3(streams), dim3(THREADS), SQ_LDS_BYTES, st, d, packed, c);
+    else if (d.arith == vadx::VADX_AR_B3) hipLaunchKernelGGL(fsmn_stream_kernel<1>, dim3(streams), dim3(THREADS), SQ_LDS_BYTES, st, d, packed, c);
+    else hipLaunchKernelGGL(fsmn_stream_kernel<0>, dim3(streams), dim3(THREADS), LDS_FLOATS * sizeof(float), st, d, packed, c);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
