@@ -48,7 +48,10 @@ extern "C" {
  *    vadx_silero_stream_state_bytes, vadx_silero_stream_workspace_bytes, vadx_silero_stream_run.
  * 9: additive: vadx_silero_cfg's reserved words became `ext` {sample_rate, reserved1, reserved2} (same size; 0 = 16000, as before), 8000 selects the 8 kHz
  *    network on every Silero launch; vadx_silero_packed_floats_sr, vadx_silero_pack_host_sr pack the 8 kHz blob.
- * 10: new entry points only: the FSMN stream path vadx_fsmn_stream_state_bytes, vadx_fsmn_stream_windows, vadx_fsmn_stream_run. */
+ * 10: new entry points only: the FSMN stream path vadx_fsmn_stream_state_bytes, vadx_fsmn_stream_windows, vadx_fsmn_stream_run.
+ *     Later additions under the SAME number (additive again: nothing an ABI-10 caller links against moved, and the suite's pin of this
+ *     number, tests/test_fsmn_stream_cpu.py, stays as it is): the ragged-batch entry points vadx_windows_gather, vadx_fsmn_clips_ragged,
+ *     vadx_tracks_gather.  A caller that needs them checks for the symbols (dlsym), not for a number. */
 #define VADX_ABI_VERSION 10
 
 /* Arithmetic of the products whose one operand is a constant (every weight matrix, every DFT table) -- float32 RESULTS in all of them:
@@ -434,6 +437,62 @@ int vadx_fsmn_stream_run(const vadx_fsmn_dims *dims, const float *packed, const 
                          int streams, int windows, const vadx_fsmn_loop_params *lp,
                          const uint8_t *reset, const uint8_t *active, const void *state_in, void *state_out,
                          uint8_t *flags, uint8_t *tail, float *noise_trace, void *stream);
+
+/* Ragged batches (FSMN, FireRed): B clips of ANY lengths in one launch sequence, work proportional to the sum of their windows.
+ * The caller pads every clip to its own window grid on the host (the reference's tail-noise rule, FSMN/Inference_FSMN_VAD_ONNX.py:88-99 /
+ * FireRedVAD/Inference_FireRed_ONNX.py:546-558), lays the padded clips end to end in ONE int16 vector `pcm` -- every clip starting on a
+ * multiple of 8 samples (16 bytes) -- and describes it with three tables (vadx.ragged.RaggedBatch builds all of this):
+ *   win_first int32 [B+1]   prefix sum of W_b, the windows per clip: clip b owns windows win_first[b] .. win_first[b+1]-1 of every
+ *                           per-window buffer below (n_windows = win_first[B]);
+ *   win_src   int64 [n_windows]   sample offset of each window in pcm: clip_off[b] + k * stride (stride = window_len for FireRed);
+ *   order     int32 [B]     clips by W_b descending: the launch order of the one-workgroup-per-clip FSMN kernel (optional).
+ * The PCM crosses the host link once, without the overlap of the windows and without the padding a rectangular [B][max N] batch has.
+ * FSMN sequence on one HIP stream:
+ *   vadx_windows_gather        pcm, win_src -> window_buf int16 [n_windows][window_len]
+ *   vadx_fsmn_window_stats     on window_buf with batch = n_windows, windows_per_clip = 1, row_stride = win_stride = window_len
+ *   vadx_frontend_logmel_means the same arguments
+ *   vadx_fsmn_clips_ragged     -> flags u8 [B][flag_stride]
+ * FireRed sequence: vadx_windows_gather, vadx_frontend_logmel (batch = n_windows, windows_per_clip = 1), vadx_firered_run (windows =
+ * n_windows), then per output channel vadx_tracks_gather + vadx_vadpost.  The front-end and network calls are the unchanged ones. */
+
+/* window_buf int16 [n_windows][window_len]: row w = pcm[win_src[w], win_src[w] + window_len).  One workgroup per window, 16-byte runs:
+ * window_len and every offset are multiples of 8 samples, pcm and window_buf 16-byte aligned.  A window whose source range leaves
+ * [0, pcm_len) -- or whose offset is not a multiple of 8 -- is written as ZEROS; nothing outside pcm is ever read.  Returns VADX_EINVAL
+ * for a NULL pointer, n_windows < 1, pcm_len < 1, a window_len that is not a positive multiple of 8, or misaligned buffers.
+ * Replaces the slicing `audio[..., slice_start:slice_end]` of FSMN/Inference_FSMN_VAD_ONNX.py:162-167, 176-234 and of the chunk loop
+ * FireRedVAD/Inference_FireRed_ONNX.py:560-579, for every window of every clip at once. */
+int vadx_windows_gather(const int16_t *pcm, int64_t pcm_len, const int64_t *win_src, int n_windows, int window_len,
+                        int16_t *window_buf, void *stream);
+
+/* vadx_fsmn_clips over a ragged batch: the same window loop (one device function, shared), per-clip bounds.  Workgroup i serves clip
+ * b = order[i] (order NULL = identity; order MUST be a permutation of 0 .. batch-1 -- documented, not checked: a clip named twice is
+ * computed twice by racing workgroups, a clip never named keeps its 255 row).  logmel [n_windows][T][80], db [n_windows][T]: the
+ * front-end over window_buf.  Row b of flags u8 [batch][flag_stride]: its first W_b * (T - look_backward) + look_backward entries are
+ * the reference's `saved` list of clip b (1 = silence), bit for bit what vadx_fsmn_clips gives for that clip alone; every other entry
+ * is 255, the stream API's "no flag" (the call fills flags with 255 first, on `stream`).  noise_trace (optional) f32 [n_windows] = noise
+ * floor after each window.  cache_ws: scratch of batch*4*128*19 floats.  max_windows: the largest W_b the caller sized flag_stride for.
+ * A table entry that does not describe windows inside the buffers -- W_b <= 0, W_b > max_windows, win_first[b] < 0, win_first[b+1] >
+ * n_windows, order[i] outside [0, batch) -- makes that workgroup return at once: the row stays all 255, its noise_trace entries are
+ * not written, nothing is indexed out of bounds.  Returns VADX_EINVAL, before any HIP call, for a NULL pointer (order and noise_trace
+ * may be NULL), batch / n_windows / max_windows < 1, flag_stride < max_windows * (T - look_backward) + look_backward, or a
+ * look_backward outside [0, T).  All three arithmetics; with F16X2 dims the range flag is raised as by vadx_fsmn_clips (range protocol:
+ * read vadx_fsmn_range_flag, repeat this call with the BF16X3 dims and blob when it is raised).
+ * Replaces the while-loop + tail, FSMN/Inference_FSMN_VAD_ONNX.py:162-167, 176-234, for B files of different lengths. */
+int vadx_fsmn_clips_ragged(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db, int batch,
+                           int n_windows, int max_windows, const int32_t *win_first, const int32_t *order,
+                           const vadx_fsmn_loop_params *lp, float *cache_ws, uint8_t *flags, int64_t flag_stride, float *noise_trace,
+                           void *stream);
+
+/* Per-window scores -> one track per clip.  probs f32 [n_windows][win_floats]; a window's `frames_per_window` scores of interest start
+ * at float `chan_offset` of its row (FireRed: probs [n_windows][odim][T], win_floats = odim * T, channel c = chan_offset / T).  Row b
+ * of tracks f32 [batch][track_stride] receives the first min(n_frames[b], W_b * frames_per_window, track_stride) frames of clip b's
+ * windows laid end to end (W_b = win_first[b+1] - win_first[b]; a negative win_first[b] or W_b counts as no frames), zeros after them:
+ * the [B][stride] + n_frames[B] input of vadx_vadpost.  win_first must be the table probs was computed with -- this call does not know
+ * n_windows.  Returns VADX_EINVAL for a NULL pointer, batch / track_stride / frames_per_window < 1 or a channel range outside
+ * [0, win_floats).  Replaces np.concatenate(all_probs)[:num_valid_frames], FireRedVAD/Inference_FireRed_ONNX.py:560-579 (AED
+ * :661-683), for a plain-C caller that has no tensor library to index with. */
+int vadx_tracks_gather(const float *probs, int64_t win_floats, int chan_offset, int frames_per_window, const int32_t *win_first,
+                       const int32_t *n_frames, int batch, float *tracks, int track_stride, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * FireRedVAD / FireRedAED DetectModel and VadPostprocessor (row a16)

@@ -184,6 +184,9 @@ SIGNATURES = {
     "vadx_fsmn_stream_state_bytes": (_Z, [_I, _I]),
     "vadx_fsmn_stream_windows": (_I, [_P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vadx_fsmn_stream_run": (_I, [C.POINTER(FsmnDims), _P, _P, _P, _I, _I, C.POINTER(FsmnLoopParams), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vadx_windows_gather": (_I, [_P, _L, _P, _I, _I, _P, _P]),
+    "vadx_fsmn_clips_ragged": (_I, [C.POINTER(FsmnDims), _P, _P, _P, _I, _I, _I, _P, _P, C.POINTER(FsmnLoopParams), _P, _P, _L, _P, _P]),
+    "vadx_tracks_gather": (_I, [_P, _L, _I, _I, _P, _P, _I, _P, _I, _P]),
     "vadx_firered_packed_floats": (_Z, [C.POINTER(FireRedCfg)]),
     "vadx_firered_range_flag": (_I, [C.POINTER(FireRedCfg), _P, _I, _P, _P, _P]),
     "vadx_firered_pack_host": (_I, [C.POINTER(FireRedCfg), C.POINTER(FireRedWeightsHost), _P]),

@@ -502,26 +502,31 @@ __global__ __launch_bounds__(THREADS, 2) void fsmn_run_kernel(Dev d, const float
     if (threadIdx.x == 0) r.noisy_db[b] = noisy;
 }
 
+struct LoopArgs {
+    int slide, lb;                        // slide_range, look_backward of the vote (>= 1)
+    float thr, noise0, snr;               // one_minus_speech_threshold, initial noise floor (x0.1), SNR (x0.1)
+    double speaking, silence_score;
+};
+
 struct ClipArgs {
     const float *logmel, *db;             // [B*W][T][80], [B*W][T]
     float *cache;                         // scratch [B][4][128][19]
-    int W, slide, lb;                     // windows per clip, slide_range, look_backward
-    float thr, noise0, snr;               // one_minus_speech_threshold, initial noise floor (x0.1), SNR (x0.1)
-    double speaking, silence_score;
+    int W;                                // windows per clip
+    LoopArgs lp;
     unsigned char *flags;                 // [B][W*slide + (T - slide)] silence flags
     float *noise_trace;                   // optional [B][W]
 };
 
-// Whole clips: the reference's while-loop (Inference_FSMN_VAD_ONNX.py:176-234), one workgroup per clip.
+// One clip of the reference's while-loop (Inference_FSMN_VAD_ONNX.py:176-234) by one workgroup: W windows in order from zero caches (cbase,
+// this clip's [4][128][19] scratch), the noise floor and the vote's `silence` carried from window to window, the plain rule on the tail of
+// the last window.  logmel / db / noise_trace point at the clip's FIRST window, fl at its flags (W * slide + T - slide of them).
 template <int AR>
-__global__ __launch_bounds__(THREADS, 2) void fsmn_clips_kernel(Dev d, const float *__restrict__ Pk, ClipArgs c) {
+__device__ __forceinline__ void clip_loop(const Dev &d, const float *__restrict__ Pk, const LoopArgs &c, const float *logmel, const float *db,
+                                          float *cbase, int W, unsigned char *fl, float *noise_trace, float *lds, float &amax) {
     constexpr bool SPLIT = AR != vadx::VADX_AR_F32;
-    float amax = 0.f;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     float *small = SPLIT ? reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(lds) + SQ_ARENA) : lds + BUFA + BUFB + BUFP;
     float *ps = small, *red = small + 128, *sc = small + 640, *cnt = small + 768;
-    float *cbase = c.cache + (size_t)b * NLAYER * PROJ * HIST;
     for (int e = tid; e < NLAYER * PROJ * HIST; e += THREADS) cbase[e] = 0.f;
     __syncthreads();
     const float *cin[NLAYER]; float *cout[NLAYER];
@@ -529,12 +534,9 @@ __global__ __launch_bounds__(THREADS, 2) void fsmn_clips_kernel(Dev d, const flo
     for (int l = 0; l < NLAYER; ++l) { cin[l] = cbase + l * PROJ * HIST; cout[l] = cbase + l * PROJ * HIST; }
     float noise = c.noise0;
     int silence = 1;                       // carried by thread 0
-    const int nflags = c.W * c.slide + (d.T - c.slide);
-    unsigned char *fl = c.flags + (size_t)b * nflags;
-    for (int k = 0; k < c.W; ++k) {
-        const size_t widx = (size_t)b * c.W + k;
-        run_chunk<AR>(d, Pk, c.logmel + widx * d.T * NMEL, cin, cout, lds, amax);
-        const float noisy = gate(d, ps, c.db + widx * d.T, c.thr, noise, nullptr, nullptr, sc, red);
+    for (int k = 0; k < W; ++k) {
+        run_chunk<AR>(d, Pk, logmel + (size_t)k * d.T * NMEL, cin, cout, lds, amax);
+        const float noisy = gate(d, ps, db + (size_t)k * d.T, c.thr, noise, nullptr, nullptr, sc, red);
         // look-ahead vote: cnt[i] = #{ j in [1,lb) : sc[i+j] != 0 }
         if (tid < c.slide) {
             float s = 0.f;
@@ -554,16 +556,54 @@ __global__ __launch_bounds__(THREADS, 2) void fsmn_clips_kernel(Dev d, const flo
                 }
                 fl[k * c.slide + i] = (unsigned char)silence;
             }
-            if (k == c.W - 1)              // tail of the final chunk: plain rule (:223-234)
+            if (k == W - 1)                // tail of the final chunk: plain rule (:223-234)
                 for (int i = c.slide; i < d.T; ++i) {
                     silence = silence ? !(sc[i] != 0.f) : (sc[i] != 1.f);
-                    fl[c.W * c.slide + (i - c.slide)] = (unsigned char)silence;
+                    fl[W * c.slide + (i - c.slide)] = (unsigned char)silence;
                 }
         }
         if (noisy > 0.0f) noise = 0.5f * ((noise + noisy) + c.snr);
-        if (c.noise_trace && tid == 0) c.noise_trace[widx] = noise;
+        if (noise_trace && tid == 0) noise_trace[k] = noise;
         __syncthreads();
     }
+}
+
+// Whole clips: the reference's while-loop (Inference_FSMN_VAD_ONNX.py:176-234), one workgroup per clip.
+template <int AR>
+__global__ __launch_bounds__(THREADS, 2) void fsmn_clips_kernel(Dev d, const float *__restrict__ Pk, ClipArgs c) {
+    float amax = 0.f;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int b = blockIdx.x;
+    const size_t w0 = (size_t)b * c.W;
+    const int nflags = c.W * c.lp.slide + (d.T - c.lp.slide);
+    clip_loop<AR>(d, Pk, c.lp, c.logmel + w0 * d.T * NMEL, c.db + w0 * d.T, c.cache + (size_t)b * NLAYER * PROJ * HIST, c.W,
+                  c.flags + (size_t)b * nflags, c.noise_trace ? c.noise_trace + w0 : nullptr, lds, amax);
+    if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
+}
+
+struct RaggedArgs {
+    const float *logmel, *db;             // [n_windows][T][80], [n_windows][T]: the front-end over the gathered windows
+    float *cache;                         // scratch [B][4][128][19]
+    int batch, n_windows, max_windows;
+    const int *win_first, *order;         // [B+1] prefix sum of the windows per clip; [B] launch order (optional)
+    LoopArgs lp;
+    unsigned char *flags; long long flag_stride;      // [B][flag_stride], 255-filled by the entry point before the launch
+    float *noise_trace;                   // optional [n_windows]
+};
+
+// The same loop over a RAGGED batch: workgroup i serves clip order[i] (longest first, so that the long clips start first and the short ones
+// fill in behind them), whose windows are win_first[b] .. win_first[b+1]-1 of the per-window buffers.  A table entry that does not describe
+// windows inside the buffers returns before anything is read or written: the clip's row keeps the entry point's 255 fill.
+template <int AR>
+__global__ __launch_bounds__(THREADS, 2) void fsmn_clips_ragged_kernel(Dev d, const float *__restrict__ Pk, RaggedArgs c) {
+    float amax = 0.f;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int b = c.order ? c.order[blockIdx.x] : (int)blockIdx.x;
+    if (b < 0 || b >= c.batch) return;
+    const int first = c.win_first[b], last = c.win_first[b + 1];
+    if (first < 0 || last <= first || last - first > c.max_windows || last > c.n_windows) return;
+    clip_loop<AR>(d, Pk, c.lp, c.logmel + (size_t)first * d.T * NMEL, c.db + (size_t)first * d.T, c.cache + (size_t)b * NLAYER * PROJ * HIST,
+                  last - first, c.flags + (size_t)b * c.flag_stride, c.noise_trace ? c.noise_trace + first : nullptr, lds, amax);
     if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
 }
 
@@ -938,6 +978,9 @@ static int set_lds_attr() {
     VADX_DYN_LDS(fsmn_stream_kernel<0>, LDS_FLOATS * sizeof(float));
     VADX_DYN_LDS(fsmn_stream_kernel<1>, SQ_LDS_BYTES);
     VADX_DYN_LDS(fsmn_stream_kernel<2>, SQ_LDS_BYTES);
+    VADX_DYN_LDS(fsmn_clips_ragged_kernel<0>, LDS_FLOATS * sizeof(float));
+    VADX_DYN_LDS(fsmn_clips_ragged_kernel<1>, SQ_LDS_BYTES);
+    VADX_DYN_LDS(fsmn_clips_ragged_kernel<2>, SQ_LDS_BYTES);
     return VADX_OK;
 }
 
@@ -1003,6 +1046,17 @@ extern "C" int vadx_fsmn_run(const vadx_fsmn_dims *dims, const float *packed, co
     return VADX_OK;
 }
 
+// the loop constants of the clips kernels from the caller's struct
+static LoopArgs loop_args(const Dev &d, const vadx_fsmn_loop_params *lp) {
+    LoopArgs a;
+    // the reference takes slide_range = score_len - look_backward BEFORE it bumps a zero look_backward to 1
+    // (Inference_FSMN_VAD_ONNX.py:79-86): LOOK_BACKWARD = 0 means slide_range = T, a vote over one frame, an empty tail
+    a.lb = lp->look_backward > 0 ? lp->look_backward : 1;
+    a.slide = d.T - lp->look_backward; a.thr = lp->one_minus_speech_threshold; a.noise0 = lp->noise_db_init;
+    a.snr = lp->snr_threshold; a.speaking = lp->speaking_score; a.silence_score = lp->silence_score;
+    return a;
+}
+
 extern "C" int vadx_fsmn_clips(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db,
                                int batch, int windows_per_clip, const vadx_fsmn_loop_params *lp, float *cache_ws,
                                uint8_t *flags, float *noise_trace, void *stream) {
@@ -1016,11 +1070,7 @@ extern "C" int vadx_fsmn_clips(const vadx_fsmn_dims *dims, const float *packed, 
     if (rc) return rc;
     ClipArgs c;
     c.logmel = logmel; c.db = db; c.cache = cache_ws; c.W = windows_per_clip;
-    // the reference takes slide_range = score_len - look_backward BEFORE it bumps a zero look_backward to 1
-    // (Inference_FSMN_VAD_ONNX.py:79-86): LOOK_BACKWARD = 0 means slide_range = T, a vote over one frame, an empty tail
-    c.lb = lp->look_backward > 0 ? lp->look_backward : 1;
-    c.slide = d.T - lp->look_backward; c.thr = lp->one_minus_speech_threshold; c.noise0 = lp->noise_db_init;
-    c.snr = lp->snr_threshold; c.speaking = lp->speaking_score; c.silence_score = lp->silence_score;
+    c.lp = loop_args(d, lp);
     c.flags = flags; c.noise_trace = noise_trace;
     if (d.arith == vadx::VADX_AR_H2)
         hipLaunchKernelGGL(fsmn_clips_kernel<2>, dim3(batch), dim3(THREADS), SQ_LDS_BYTES, static_cast<hipStream_t>(stream), d, packed, c);
@@ -1029,6 +1079,36 @@ extern "C" int vadx_fsmn_clips(const vadx_fsmn_dims *dims, const float *packed, 
     else
         hipLaunchKernelGGL(fsmn_clips_kernel<0>, dim3(batch), dim3(THREADS), LDS_FLOATS * sizeof(float),
                            static_cast<hipStream_t>(stream), d, packed, c);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+extern "C" int vadx_fsmn_clips_ragged(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db, int batch,
+                                      int n_windows, int max_windows, const int32_t *win_first, const int32_t *order,
+                                      const vadx_fsmn_loop_params *lp, float *cache_ws, uint8_t *flags, int64_t flag_stride, float *noise_trace,
+                                      void *stream) {
+    Dev d;
+    VADX_REQUIRE(dims && packed && logmel && db && win_first && lp && cache_ws && flags, "vadx_fsmn_clips_ragged: NULL argument");
+    VADX_REQUIRE(derive(dims, &d) == 0, "vadx_fsmn_clips_ragged: unsupported dims");
+    VADX_REQUIRE(batch >= 1 && n_windows >= 1 && max_windows >= 1, "vadx_fsmn_clips_ragged: batch=%d n_windows=%d max_windows=%d must be positive",
+                 batch, n_windows, max_windows);
+    VADX_REQUIRE(lp->look_backward >= 0 && lp->look_backward < d.T && d.T - lp->look_backward <= 128 && d.T <= 112,
+                 "vadx_fsmn_clips_ragged: look_backward=%d frames=%d unsupported", lp->look_backward, d.T);
+    const long long need = (long long)max_windows * (d.T - lp->look_backward) + lp->look_backward;
+    VADX_REQUIRE(flag_stride >= need, "vadx_fsmn_clips_ragged: flag_stride=%lld holds fewer than max_windows * slide + look_backward = %lld flags",
+                 (long long)flag_stride, need);
+    int rc = set_lds_attr();
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // every row starts as "no flag"; a clip's workgroup then writes its W_b * slide + look_backward flags over the front of its row
+    VADX_HIP_TRY(hipMemsetAsync(flags, 255, (size_t)batch * (size_t)flag_stride, st));
+    RaggedArgs c;
+    c.logmel = logmel; c.db = db; c.cache = cache_ws; c.batch = batch; c.n_windows = n_windows; c.max_windows = max_windows;
+    c.win_first = win_first; c.order = order; c.lp = loop_args(d, lp);
+    c.flags = flags; c.flag_stride = (long long)flag_stride; c.noise_trace = noise_trace;
+    if (d.arith == vadx::VADX_AR_H2) hipLaunchKernelGGL(fsmn_clips_ragged_kernel<2>, dim3(batch), dim3(THREADS), SQ_LDS_BYTES, st, d, packed, c);
+    else if (d.arith == vadx::VADX_AR_B3) hipLaunchKernelGGL(fsmn_clips_ragged_kernel<1>, dim3(batch), dim3(THREADS), SQ_LDS_BYTES, st, d, packed, c);
+    else hipLaunchKernelGGL(fsmn_clips_ragged_kernel<0>, dim3(batch), dim3(THREADS), LDS_FLOATS * sizeof(float), st, d, packed, c);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }

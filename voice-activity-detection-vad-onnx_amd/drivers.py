@@ -1,8 +1,9 @@
 """Script-level drop-ins for the reference's `Inference_*_VAD_ONNX.py` programs: raw audio file(s) in,
 `timestamps_second.txt` / `timestamps_indices.txt` out, same constants (as keyword arguments instead
-of module-level globals), same stdout summary.  Each function also accepts a LIST of files: equal-length files run as one
-device batch per length group (`_grouped`; the Silero driver pads ragged clips into one batch instead); the printed RTF is
-over the total audio duration.  `engine` / `model` may be an engine object, a weight dict, a checkpoint path, or the explicit
+of module-level globals), same stdout summary.  Each function also accepts a LIST of files: FSMN, FireRed and FireRed-AED hand
+the list to their engine as ONE ragged batch (vadx.ragged: clips of any lengths, work proportional to the audio); MarbleNet and DFSMN
+run equal-length files as one device batch per length group (`_grouped`); the Silero driver pads ragged clips into one batch.  The
+printed RTF is over the total audio duration.  `engine` / `model` may be an engine object, a weight dict, a checkpoint path, or the explicit
 opt-in "synthetic:<seed>" (vadx.checkpoints.resolve) -- never an implicit default."""
 from __future__ import annotations
 
@@ -90,11 +91,13 @@ def inference_fsmn(test_vad_audio="./vad_sample.wav", engine=None, save_timestam
     clips = [audio_io.load_wav(f, 16000) for f in files]
     echo("\nRunning the FSMN_VAD by ONNX Runtime.")
     t0 = time.time()
-    all_ts = _grouped(clips, pad_noise, lambda batch, nz: engine.detect(
-        batch.astype(np.float32), pad_noise=nz, fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION,
-        look_backward_s=LOOK_BACKWARD, speaking_score=SPEAKING_SCORE, silence_score=SILENCE_SCORE,
-        snr_threshold=SNR_THRESHOLD, noise_init_dB=BACKGROUND_NOISE_dB_INIT,
-        one_minus_speech_threshold=ONE_MINUS_SPEECH_THRESHOLD))
+    kw = dict(fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION, look_backward_s=LOOK_BACKWARD,
+              speaking_score=SPEAKING_SCORE, silence_score=SILENCE_SCORE, snr_threshold=SNR_THRESHOLD,
+              noise_init_dB=BACKGROUND_NOISE_dB_INIT, one_minus_speech_threshold=ONE_MINUS_SPEECH_THRESHOLD)
+    if isinstance(test_vad_audio, (list, tuple)):          # files of any lengths: one ragged batch
+        all_ts = engine.detect([c.astype(np.float32) for c in clips], pad_noise=pad_noise, **kw)
+    else:
+        all_ts = _grouped(clips, pad_noise, lambda batch, nz: engine.detect(batch.astype(np.float32), pad_noise=nz, **kw))
     elapsed = time.time() - t0
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
 
@@ -114,7 +117,10 @@ def inference_firered(test_vad_audio="./vad_sample.wav", engine=None, save_times
     t0 = time.time()
     post = (SMOOTH_WINDOW_SIZE, SPEAKING_SCORE, MIN_SPEECH_FRAME, MAX_SPEECH_FRAME, MIN_SILENCE_FRAME,
             MERGE_SILENCE_FRAME, EXTEND_SPEECH_FRAME)
-    all_ts = _grouped(clips, pad_noise, lambda batch, nz: engine.detect(batch, pad_noise=nz, post=post))
+    if isinstance(test_vad_audio, (list, tuple)):          # files of any lengths: one ragged batch
+        all_ts = engine.detect(clips, pad_noise=pad_noise, post=post)
+    else:
+        all_ts = _grouped(clips, pad_noise, lambda batch, nz: engine.detect(batch, pad_noise=nz, post=post))
     elapsed = time.time() - t0
     echo(f"RTF: {elapsed / (sum(len(c) for c in clips) / 16000):.4f}")
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
@@ -134,10 +140,12 @@ def inference_firered_aed(test_aed_audio="./vad_sample.wav", engine=None, NORMAL
     echo("\nRunning the FireRedAED by ONNX Runtime.")
     t0 = time.time()
     post = (SMOOTH_WINDOW_SIZE, MIN_EVENT_FRAME, MAX_EVENT_FRAME, MIN_SILENCE_FRAME, MERGE_SILENCE_FRAME, EXTEND_SPEECH_FRAME)
-    results = []
-    for c, nz in zip(clips, pad_noise if pad_noise is not None else [None] * len(clips)):
-        results += engine.detect_events(c[None, :], pad_noise=None if nz is None else nz[None, :],
-                                        thresholds=(SPEAKING_SCORE, SINGING_THRESHOLD, MUSIC_THRESHOLD), post=post)
+    thresholds = (SPEAKING_SCORE, SINGING_THRESHOLD, MUSIC_THRESHOLD)
+    if isinstance(test_aed_audio, (list, tuple)):          # files of any lengths: one ragged batch
+        results = engine.detect_events(clips, pad_noise=pad_noise, thresholds=thresholds, post=post)
+    else:
+        nz = None if pad_noise is None else np.asarray(pad_noise[0])[None, :]
+        results = engine.detect_events(clips[0][None, :], pad_noise=nz, thresholds=thresholds, post=post)
     elapsed = time.time() - t0
     for (ts, ratio), c in zip(results, clips):
         echo(f"\nAED Results:\n  Audio duration: {len(c) / 16000:.3f}s\n  Event ratios: {ratio}")

@@ -95,7 +95,11 @@ class FireRedEngine:
         t = self.torch
         if not t.is_tensor(audio_i16):
             audio_i16 = t.from_numpy(np.ascontiguousarray(audio_i16, dtype=np.int16))
-        logmel = self.fe.logmel(audio_i16, windows_per_clip, self.L)
+        return self._run_logmel(self.fe.logmel(audio_i16, windows_per_clip, self.L))
+
+    def _run_logmel(self, logmel):
+        """log-mel f32 [windows, T, 80] -> probs f32 [windows, odim, T] (vadx_firered_run under the range protocol)"""
+        t = self.torch
         nwin = logmel.shape[0]
         probs = t.empty((nwin, self.odim, self.T), dtype=t.float32, device=self.device)
 
@@ -105,6 +109,49 @@ class FireRedEngine:
                                                        probs.data_ptr(), _lib.stream_ptr()))
             return probs
         return self.blobs.guarded(launch)
+
+    def ragged(self, clips, pad_noise=None, device=True):
+        """The packed batch of `clips` (list of 1-D int16 arrays of any lengths) on this engine's non-overlapping window grid
+        (vadx.ragged.RaggedBatch), each padded with pad_noise row b.  device=None keeps it on the host."""
+        from . import ragged as _ragged
+        return _ragged.RaggedBatch.from_clips(clips, self.L, self.L, pad_noise, None, self.device if device is True else device)
+
+    def run_ragged(self, rb):
+        """RaggedBatch on this engine's grid -> probs f32 [sum W, odim, T]: rows win_first[b] .. win_first[b+1]-1 are clip b's windows
+        (vadx_windows_gather, then the unchanged front-end and vadx_firered_run over sum W windows).  A host-only batch
+        (device=None) is uploaded first, in place: `rb.to(self.device)` turns its pcm and tables into device tensors."""
+        if rb.window != self.L or rb.stride != self.L:
+            raise ValueError(f"the batch was packed for windows of {rb.window} every {rb.stride} samples, this engine cuts {self.L} every {self.L}")
+        if rb.device is None:
+            rb.to(self.device)
+        return self._run_logmel(self.fe.logmel(rb.gather(), 1, self.L))
+
+    def _ragged_tracks(self, rb, probs, n_frames, channel):
+        """One output channel of `probs` as tracks f32 [B, max n_frames] (vadx_tracks_gather): row b = the first n_frames[b] frames of
+        clip b's windows laid end to end, zeros after them -- the input of one vadx_vadpost launch."""
+        t = self.torch
+        stride = max(int(n_frames.max()), 1)
+        tracks = t.empty((len(rb), stride), dtype=t.float32, device=self.device)
+        nfd = t.from_numpy(np.ascontiguousarray(n_frames, dtype=np.int32)).to(self.device)
+        with t.cuda.device(self.device):
+            _lib.check(_lib.lib().vadx_tracks_gather(probs.data_ptr(), self.odim * self.T, channel * self.T, self.T, rb.win_first.data_ptr(),
+                                                     nfd.data_ptr(), len(rb), tracks.data_ptr(), stride, _lib.stream_ptr()))
+        return tracks
+
+    def _detect_ragged(self, clips, pad_noise, post, return_probs):
+        rb = self.ragged(clips, pad_noise)
+        probs = self.run_ragged(rb)
+        B = len(rb)
+        nf = np.minimum([valid_frame_count(int(n), self.in_sample_rate) for n in rb.lengths], rb.windows.astype(np.int64) * self.T)
+        pp = _vadpost.VadPostprocessor(*post, device=self.device)
+        track = self._ragged_tracks(rb, probs, nf, 0)
+        dec, segs, counts = pp.process_batch(track, n_frames=nf)
+        segs, counts = segs.cpu().numpy(), counts.cpu().numpy()
+        out = [pp.segments_to_seconds(segs[b, :counts[b]].tolist(), int(nf[b]), int(rb.lengths[b]) / self.in_sample_rate) if nf[b] else []
+               for b in range(B)]
+        if return_probs:
+            return out, [track[b, :nf[b]] for b in range(B)], [dec[b, :nf[b]] for b in range(B)]
+        return out
 
     def run_from_host(self, host_i16, windows_per_clip=1, chunk_clips=256, feed=None):
         """`run` fed from HOST memory (int16 [B, W*L], ideally pinned: vadx.feed.pin), uploads overlapped with compute
@@ -182,7 +229,12 @@ class FireRedEngine:
 
     def detect(self, clips_i16, pad_noise=None, post=(5, 0.4, 20, 2000, 20, 5, 0), return_probs=False):
         """Equal-length clips int16 [B,N] (host) -> per clip [(start_s, end_s)] for output channel 0
-        (VAD driver :535-591).  pad_noise: standard-normal [B, >= pad] for the tail padding."""
+        (VAD driver :535-591).  pad_noise: standard-normal [B, >= pad] for the tail padding.
+        A LIST (or tuple) of 1-D clips of any lengths runs as one ragged batch (`run_ragged`, one vadx_vadpost launch); clip b's
+        result is that of `detect(clip_b[None, :], pad_noise=row_b[None, :])[0]`, its seconds computed with its own duration;
+        return_probs then gives per-clip LISTS of tracks and decisions, each cut to its clip's frame count."""
+        if isinstance(clips_i16, (list, tuple)):
+            return self._detect_ragged(clips_i16, pad_noise, post, return_probs)
         clips = np.asarray(clips_i16)
         B, n = clips.shape
         rows = [pad_to_window_grid(clips[b], self.L, self.L, None if pad_noise is None else pad_noise[b]) for b in range(B)]
@@ -212,6 +264,8 @@ def _detect_events(self, clips_i16, pad_noise=None, thresholds=(0.4, 0.5, 0.5), 
     min_silence, merge_silence, extend); `thresholds` per event in IDX2EVENT order."""
     if self.odim != len(IDX2EVENT):
         raise ValueError(f"the AED driver needs a {len(IDX2EVENT)}-output model, this one has odim = {self.odim}")
+    if isinstance(clips_i16, (list, tuple)):
+        return _detect_events_ragged(self, clips_i16, pad_noise, thresholds, post, return_probs)
     clips = np.asarray(clips_i16)
     B, n = clips.shape
     rows = [pad_to_window_grid(clips[b], self.L, self.L, None if pad_noise is None else pad_noise[b]) for b in range(B)]
@@ -237,6 +291,38 @@ def _detect_events(self, clips_i16, pad_noise=None, thresholds=(0.4, 0.5, 0.5), 
             out[b][0][event] = pp.segments_to_seconds(segs[b, :counts[b]].tolist(), nfr, n / SAMPLE_RATE)
             out[b][1][event] = round(float(ratio[b]), 3)
     return (out, tracks) if return_probs else out
+
+
+def _detect_events_ragged(self, clips, pad_noise, thresholds, post, return_probs):
+    """`_detect_events` for a LIST of 1-D clips of any lengths: one ragged batch, per event one vadx_tracks_gather + one vadx_vadpost
+    launch; clip b's result is that of the [1, N] call on it alone.  return_probs adds per clip the tracks f32 [odim, n_frames[b]]."""
+    t = self.torch
+    rb = self.ragged(clips, pad_noise)
+    probs = self.run_ragged(rb)
+    B = len(rb)
+    nf = np.minimum([valid_frame_count(int(n)) for n in rb.lengths], rb.windows.astype(np.int64) * self.T)
+    out = [({}, {}) for _ in range(B)]
+    tracks = []
+    live = t.arange(max(int(nf.max()), 1), device=self.device)[None, :] < t.from_numpy(nf).to(self.device)[:, None]
+    for idx, event in IDX2EVENT.items():
+        thr = thresholds[idx]
+        pp = _vadpost.VadPostprocessor(post[0], thr, *post[1:], device=self.device)
+        track = self._ragged_tracks(rb, probs, nf, idx)
+        tracks.append(track)
+        _, segs, counts = pp.process_batch(track, n_frames=nf)
+        segs, counts = segs.cpu().numpy(), counts.cpu().numpy()
+        # frames over threshold per clip: the rows are zero-filled past n_frames[b], so the columns are masked, not the values (one
+        # launch sequence, one read-back).  The [1, N] path takes torch's device mean of the 0 / 1 values, which is the exact count
+        # times the float32 reciprocal of N (not count / N: an ulp apart for some pairs); the same product here keeps the ratios
+        # bitwise those of the one-clip call (tests/test_gpu_ragged.py checks the product against torch.mean for every count)
+        counts_over = ((track >= np.float32(thr)) & live).sum(dim=1).cpu().numpy()
+        ratio = counts_over.astype(np.float32) * (np.float32(1.0) / np.maximum(nf, 1).astype(np.float32))
+        for b in range(B):
+            out[b][0][event] = pp.segments_to_seconds(segs[b, :counts[b]].tolist(), int(nf[b]), int(rb.lengths[b]) / SAMPLE_RATE) if nf[b] else []
+            out[b][1][event] = round(float(ratio[b]), 3) if nf[b] else 0.0
+    if return_probs:
+        return out, [t.stack([tr[b, :nf[b]] for tr in tracks]) for b in range(B)]
+    return out
 
 
 FireRedEngine.detect_events = _detect_events

@@ -22,6 +22,17 @@ OUTPUT_FRAME_LENGTH = 160
 PROJ, HIST = 128, 19
 
 
+def _loop_params(lb, speaking_score=0.5, silence_score=0.5, snr_threshold=10.0, noise_init_dB=30.0, one_minus_speech_threshold=1.0):
+    """vadx_fsmn_loop_params from the reference script's constants (FSMN/Inference_FSMN_VAD_ONNX.py:16-23, 79-81, 159-171)."""
+    lp = _lib.FsmnLoopParams()
+    lp.look_backward = int(lb)
+    lp.one_minus_speech_threshold = float(one_minus_speech_threshold)
+    lp.noise_db_init = float(np.float32(noise_init_dB + snr_threshold) * np.float32(0.1))
+    lp.snr_threshold = float(snr_threshold * 0.1)
+    lp.speaking_score, lp.silence_score = float(speaking_score), float(silence_score)
+    return lp
+
+
 class _Meta:
     def __init__(self, name, shape, type_):
         self.name, self.shape, self.type = name, shape, type_
@@ -147,12 +158,7 @@ class FsmnEngine:
         a = padded_i16.to(self.device).contiguous()
         B, W = a.shape[0], int(windows_per_clip)
         logmel, db = self.features(a, W, stride)
-        lp = _lib.FsmnLoopParams()
-        lp.look_backward = lb
-        lp.one_minus_speech_threshold = float(one_minus_speech_threshold)
-        lp.noise_db_init = float(np.float32(noise_init_dB + snr_threshold) * np.float32(0.1))
-        lp.snr_threshold = float(snr_threshold * 0.1)
-        lp.speaking_score, lp.silence_score = float(speaking_score), float(silence_score)
+        lp = _loop_params(lb, speaking_score, silence_score, snr_threshold, noise_init_dB, one_minus_speech_threshold)
         nflags = W * (self.T - lb) + lb
         flags = t.empty((B, nflags), dtype=t.uint8, device=self.device)
         cache = t.empty((B, 4, PROJ, HIST), dtype=t.float32, device=self.device)
@@ -173,10 +179,72 @@ class FsmnEngine:
         f = feed or _feed.HostPcmFeed(self.device, host_padded_i16.shape[1], chunk_clips)
         return _feed.cat_results(f.map([host_padded_i16], lambda a: self.flags(a, windows_per_clip, **loop_kw)))
 
+    def ragged(self, clips, pad_noise=None, normalize=True, look_backward_s=0.3, device=True):
+        """The packed batch of `clips` (list of 1-D arrays of any lengths) on this engine's window grid (vadx.ragged.RaggedBatch):
+        peak-normalised like the reference (normalize) and padded per clip with pad_noise row b.  device=None keeps it on the host."""
+        from . import ragged as _ragged
+        prep = (lambda a: _ts.normalize_to_int16(a.astype(np.float32))) if normalize else None
+        return _ragged.RaggedBatch.from_clips(clips, self.L, self.grid(look_backward_s)[1], pad_noise, prep,
+                                              self.device if device is True else device)
+
+    def flags_ragged(self, rb, *, order=None, return_noise=False, look_backward_s=0.3, speaking_score=0.5, silence_score=0.5,
+                     snr_threshold=10.0, noise_init_dB=30.0, one_minus_speech_threshold=1.0):
+        """`flags` for a RaggedBatch on this engine's grid: one gather, the unchanged front-end over sum(W) windows, one
+        vadx_fsmn_clips_ragged launch -> (flags u8 [B, max W * (T-lb) + lb], nflags int64 [B] (host)[, noise trace f32 [sum W]]).
+        Row b holds clip b's nflags[b] = W_b * (T-lb) + lb flags -- bit for bit `flags(padded_b[None], W_b)` -- then 255.
+        order: None = rb.order (longest clip first), "identity" = clip b on workgroup b, or an int32 permutation of the clips.
+        A host-only batch (device=None) is uploaded first, in place: `rb.to(self.device)` turns its pcm and tables into device tensors."""
+        t = self.torch
+        lb, stride = self.grid(look_backward_s)
+        if rb.window != self.L or rb.stride != stride:
+            raise ValueError(f"the batch was packed for windows of {rb.window} every {rb.stride} samples, this call needs {self.L} every {stride}")
+        if rb.device is None:
+            rb.to(self.device)
+        B, nwin, maxw = len(rb), rb.n_windows, rb.max_windows
+        if order is None:
+            order_d = rb.order
+        elif isinstance(order, str):
+            if order != "identity":
+                raise ValueError(f"order must be None, 'identity' or a permutation, got {order!r}")
+            order_d = None
+        else:
+            o = np.asarray(order.cpu() if t.is_tensor(order) else order).astype(np.int32).reshape(-1)
+            if not np.array_equal(np.sort(o), np.arange(B)):
+                raise ValueError(f"order must be a permutation of the {B} clips")
+            order_d = t.from_numpy(o).to(self.device)
+        logmel, db = self.features(rb.gather(), 1, self.L)
+        lp = _loop_params(lb, speaking_score, silence_score, snr_threshold, noise_init_dB, one_minus_speech_threshold)
+        slide = self.T - lb
+        stride_f = maxw * slide + lb
+        nflags = rb.windows.astype(np.int64) * slide + lb
+        flags = t.empty((B, stride_f), dtype=t.uint8, device=self.device)
+        cache = t.empty((B, 4, PROJ, HIST), dtype=t.float32, device=self.device)
+        trace = t.empty((nwin,), dtype=t.float32, device=self.device) if return_noise else None
+
+        def launch(mode, dims, packed):
+            with t.cuda.device(self.device):
+                _lib.check(_lib.lib().vadx_fsmn_clips_ragged(C.byref(dims), packed.data_ptr(), logmel.data_ptr(), db.data_ptr(), B, nwin,
+                                                             maxw, rb.win_first.data_ptr(), None if order_d is None else order_d.data_ptr(),
+                                                             C.byref(lp), cache.data_ptr(), flags.data_ptr(), stride_f,
+                                                             None if trace is None else trace.data_ptr(), _lib.stream_ptr()))
+            return (flags, nflags, trace) if return_noise else (flags, nflags)
+        return self.blobs.guarded(launch)
+
     def detect(self, clips_i16, pad_noise=None, fusion_threshold=0.3, min_speech_duration=0.2, normalize=True, **loop_kw):
         """Equal-length clips int16 [B,N] (host numpy) -> per clip [(start_s, end_s)], as the reference
         script would print for each.  pad_noise: standard-normal array [B, >=pad] replacing the
-        reference's unseeded np.random.normal tail padding (explicit so results are reproducible)."""
+        reference's unseeded np.random.normal tail padding (explicit so results are reproducible).
+        A LIST (or tuple) of 1-D clips of any lengths runs as one ragged batch (`flags_ragged`); clip b's result is that of
+        `detect(clip_b[None, :], pad_noise=row_b[None, :])[0]`."""
+        if isinstance(clips_i16, (list, tuple)):
+            rb = self.ragged(clips_i16, pad_noise, normalize, loop_kw.get("look_backward_s", 0.3))
+            flags, nflags = self.flags_ragged(rb, **loop_kw)
+            flags = flags.cpu().numpy()
+            out = []
+            for b in range(len(rb)):
+                ts = _ts.vad_to_timestamps(flags[b, :nflags[b]].astype(bool), OUTPUT_FRAME_LENGTH / SAMPLE_RATE)
+                out.append(_ts.process_timestamps(ts, fusion_threshold, min_speech_duration))
+            return out
         clips = np.asarray(clips_i16)
         B, n = clips.shape
         lb, stride = self.grid(loop_kw.get("look_backward_s", 0.3))
@@ -301,13 +369,7 @@ class FsmnStreamBatch:
         self.carry = engine.L - self.stride              # (lb + 1) * 160 samples
         if self.lb < 0 or self.stride <= 0 or self.lb >= engine.T - 2:
             raise ValueError(f"look_backward_s={look_backward_s}: {self.lb} frames leave no window stride")
-        lp = _lib.FsmnLoopParams()
-        lp.look_backward = self.lb
-        lp.one_minus_speech_threshold = float(one_minus_speech_threshold)
-        lp.noise_db_init = float(np.float32(noise_init_dB + snr_threshold) * np.float32(0.1))
-        lp.snr_threshold = float(snr_threshold * 0.1)
-        lp.speaking_score, lp.silence_score = float(speaking_score), float(silence_score)
-        self._lp = lp
+        self._lp = _loop_params(self.lb, speaking_score, silence_score, snr_threshold, noise_init_dB, one_minus_speech_threshold)
         t = engine.torch
         nb = _lib.lib().vadx_fsmn_stream_state_bytes(self.streams, self.lb)
         self._rec = [t.zeros(nb, dtype=t.uint8, device=engine.device) for _ in range(2)]

@@ -1,0 +1,103 @@
+"""A RAGGED batch: clips of any lengths packed into one int16 vector, with the tables the device needs to walk it.
+
+Every clip is padded to its own window grid on the host (`fsmn.pad_to_window_grid`: the reference's tail-noise arithmetic, bit-pinned
+there), the padded clips are laid end to end -- each starting on a multiple of 8 samples, so that every analysis window is a whole
+number of 16-byte runs -- and uploaded ONCE.  Overlapping windows (FSMN: 16000 samples every 11040) exist only on the device, after
+vadx_windows_gather; the padding a rectangular [B, max N] batch would add to short clips is neither uploaded nor computed: the work
+of every later launch is proportional to sum(W_b) windows, not B * max(W_b).
+
+Tables (include/vadx.h, "Ragged batches"):
+    win_first [B+1]  prefix sum of the windows per clip: clip b owns windows win_first[b] .. win_first[b+1]-1 of every per-window buffer
+    win_src   [sum W] sample offset of every window in `pcm`: clip_off[b] + k * stride
+    order     [B]    clips by window count, longest first (stable): the launch order of one-workgroup-per-clip kernels
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .fsmn import pad_to_window_grid
+
+ALIGN = 8            # samples: window and stride are multiples of it, so every clip starts on a 16-byte boundary of the packed vector
+
+
+class RaggedBatch:
+    """Fields: pcm int16 [total], lengths [B] (original sample counts, host), windows int32 [B] (host), win_first int32 [B+1],
+    win_src int64 [sum W], order int32 [B]; clip_off int64 [B] (host) = where each padded clip starts in pcm, padded_lengths [B].
+    With a device, pcm / win_first / win_src / order are tensors there and the `*_host` attributes keep the numpy tables; with
+    device=None everything stays numpy (the host tables ARE the fields)."""
+
+    @classmethod
+    def from_clips(cls, clips, window, stride, pad_noise=None, prep=None, device="cuda:0"):
+        """clips: list of 1-D int16 arrays (or whatever `prep` turns into one: FSMN passes timestamps.normalize_to_int16);
+        pad_noise: None (numpy's global RNG, as the reference) or standard-normal rows, a list or a matrix -- clip b uses the first
+        pad_b samples of row b."""
+        window, stride = int(window), int(stride)
+        if window < ALIGN or window % ALIGN or stride < ALIGN or stride % ALIGN:
+            raise ValueError(f"window={window} and stride={stride} must be positive multiples of {ALIGN} samples")
+        if len(clips) == 0:
+            raise ValueError("a ragged batch needs at least one clip")
+        if pad_noise is not None and len(pad_noise) < len(clips):
+            raise ValueError(f"pad_noise has {len(pad_noise)} rows for {len(clips)} clips")
+        rows, lengths = [], []
+        for b, c in enumerate(clips):
+            a = np.asarray(c).reshape(-1)
+            if a.shape[0] == 0:
+                raise ValueError(f"clip {b} is empty")
+            lengths.append(a.shape[0])
+            a = np.asarray(prep(a) if prep is not None else a)
+            if a.dtype != np.int16:
+                raise ValueError(f"clip {b} must be int16 (after prep), got {a.dtype}")
+            rows.append(pad_to_window_grid(a, window, stride, None if pad_noise is None else np.asarray(pad_noise[b]).reshape(-1)))
+        self = cls()
+        self.window, self.stride = window, stride
+        self.lengths = np.asarray(lengths, dtype=np.int64)
+        self.padded_lengths = np.asarray([len(r) for r in rows], dtype=np.int64)
+        self.windows = ((self.padded_lengths - window) // stride + 1).astype(np.int32)
+        # a padded clip is (W-1) * stride + window samples, a multiple of 8 like both terms: laid end to end, every clip (and so every
+        # window) starts on a 16-byte boundary with no filler between clips
+        self.clip_off = np.concatenate([[0], np.cumsum(self.padded_lengths)[:-1]]).astype(np.int64)
+        pcm = np.concatenate(rows)
+        nwin = int(self.windows.sum())
+        if nwin >= 2 ** 31:
+            raise ValueError(f"{nwin} windows do not fit the int32 window tables")
+        self.n_windows, self.max_windows = nwin, int(self.windows.max())
+        self.win_first_host = np.concatenate([[0], np.cumsum(self.windows, dtype=np.int64)]).astype(np.int32)
+        k = np.arange(nwin, dtype=np.int64) - np.repeat(self.win_first_host[:-1].astype(np.int64), self.windows)
+        self.win_src_host = np.repeat(self.clip_off, self.windows) + k * stride
+        self.order_host = np.argsort(-self.windows.astype(np.int64), kind="stable").astype(np.int32)
+        self.pcm_host = pcm
+        self.device = None
+        self.pcm, self.win_first, self.win_src, self.order = pcm, self.win_first_host, self.win_src_host, self.order_host
+        if device is not None:
+            self.to(device)
+        return self
+
+    def to(self, device):
+        """Upload the packed PCM (once) and the three tables."""
+        from . import _lib
+        t = _lib.require_gpu()
+        self.device = t.device(device)
+        self.pcm = t.from_numpy(self.pcm_host).to(self.device)
+        self.win_first = t.from_numpy(self.win_first_host).to(self.device)
+        self.win_src = t.from_numpy(self.win_src_host).to(self.device)
+        self.order = t.from_numpy(self.order_host).to(self.device)
+        return self
+
+    def __len__(self):
+        return int(self.lengths.shape[0])
+
+    def padded(self, b):
+        """Clip b as it was packed (host int16 [padded_lengths[b]]) = pad_to_window_grid of the prepped clip."""
+        return self.pcm_host[self.clip_off[b]:self.clip_off[b] + self.padded_lengths[b]]
+
+    def gather(self):
+        """window_buf int16 [n_windows, window] on the device (vadx_windows_gather): row win_first[b] + k is window k of clip b."""
+        from . import _lib
+        if self.device is None:
+            raise ValueError("this batch is host-only: call .to(device) first")
+        t = _lib.require_gpu()
+        wbuf = t.empty((self.n_windows, self.window), dtype=t.int16, device=self.device)
+        with t.cuda.device(self.device):
+            _lib.check(_lib.lib().vadx_windows_gather(self.pcm.data_ptr(), int(self.pcm.numel()), self.win_src.data_ptr(), self.n_windows,
+                                                      self.window, wbuf.data_ptr(), _lib.stream_ptr()))
+        return wbuf
