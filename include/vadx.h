@@ -324,7 +324,8 @@ int vadx_frontend_stft_ft(const vadx_frontend_cfg *cfg, const float *packed, con
  * ------------------------------------------------------------------------------------------- */
 typedef struct vadx_fsmn_dims {          /* FunASR FSMN(input 400, proj 128, lorder 20, 4 layers pinned in-tree) */
     int   input_affine_dim, linear_dim, output_affine_dim, output_dim;   /* external config: 140/250/140/248 */
-    int   frames;                         /* T = window_len // 160 + 1 (101) */
+    int   frames;                         /* T = window_len // 160 + 1 (101); vadx_fsmn_run takes T <= 128 (window_len <= 20479), the clips, ragged
+                                           * and stream entry points T <= 112 (window_len <= 17919); more is VADX_EINVAL */
     float speech_2_noise_ratio;           /* FSMN/Export_FSMN_VAD.py:34,87-92 */
     int   arithmetic;                     /* VADX_ARITH_* of the dense layers (0 = AUTO = BF16X3: float32's exponent range, nothing to check; F16X2
                                            * is for callers that read vadx_fsmn_range_flag with the results and recompute a flagged batch on
@@ -363,6 +364,7 @@ int vadx_fsmn_window_stats(const int16_t *audio, int64_t row_stride, int64_t win
  *   feeds   audio -> (logmel [B][T][80], db [B][T]); cache_0..3 f32 [B][128][19];
  *           one_minus_speech_threshold f32 [B]; noise_average_dB f32 [B]
  *   fetches score u8 [B][T]; cache_0..3; noisy_dB f32 [B]      (+ optional P(silence) f32 [B][T])
+ * dims->frames <= 128: the kernel keeps a window's scores in a 128-entry LDS array; a longer window returns VADX_EINVAL before any device call.
  * Replaces ort_session_A.run(...), FSMN/Inference_FSMN_VAD_ONNX.py:177-187 (graph :75-101). */
 int vadx_fsmn_run(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db,
                   const float *const cache_in[4], float *const cache_out[4], const float *thr,

@@ -159,6 +159,35 @@ def test_dfsmn_entry_points_validate_before_touching_the_device():
     assert lib.vadx_frag_h2_host(ptr, 16, 32, 7, ptr, None) == -1 and b"k_order" in lib.vadx_last_error()
 
 
+def test_fsmn_run_refuses_a_window_longer_than_its_score_scratch(lib):
+    """vadx_fsmn_run keeps a window's P(silence) and gate output in 128-entry LDS arrays: frames = 129 (a window of 20 480 samples) is refused
+    with a message on the host, before any device call (no GPU here: a HIP call would fail with another code), as the clips, ragged and
+    stream entry points refuse more than 112."""
+    import ctypes as C
+    buf = (C.c_float * 64)()
+    ptr = C.cast(buf, C.c_void_p).value
+    four = (C.c_void_p * 4)(ptr, ptr, ptr, ptr)
+    d = _lib.FsmnDims()
+    d.input_affine_dim, d.linear_dim, d.output_affine_dim, d.output_dim = 140, 250, 140, 248
+    d.speech_2_noise_ratio, d.arithmetic = 1.0, _lib.GEMM_MODES["f32"]
+    run = lambda: lib.vadx_fsmn_run(C.byref(d), ptr, ptr, ptr, C.byref(four), C.byref(four), ptr, ptr, 1, ptr, ptr, None, None)      # noqa: E731
+    for frames in (129, 385, 1 << 20):
+        d.frames = frames
+        assert run() == -1
+        msg = lib.vadx_last_error()
+        assert b"frames=%d" % frames in msg and b"128" in msg, msg
+    d.frames = 128
+    assert lib.vadx_fsmn_packed_floats(C.byref(d)) > 0      # the dims themselves are fine at every length: the limit is vadx_fsmn_run's
+    d.frames = 129
+    assert lib.vadx_fsmn_packed_floats(C.byref(d)) > 0
+    lp = _lib.FsmnLoopParams()
+    lp.look_backward = 30
+    for frames in (113, 129):
+        d.frames = frames
+        assert lib.vadx_fsmn_clips(C.byref(d), ptr, ptr, ptr, 1, 1, C.byref(lp), ptr, ptr, None, None) == -1
+        assert b"frames=%d unsupported" % frames in lib.vadx_last_error()
+
+
 def test_weight_validation():
     w = weights.silero_synthetic(1)
     assert weights.silero_check(w)

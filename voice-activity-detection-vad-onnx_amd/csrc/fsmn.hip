@@ -31,6 +31,7 @@ constexpr int P_CUR = 20;                // first "current frame" column of bufP
 constexpr int BUFA_ROWS = 256, BUFB_ROWS = 144;
 constexpr int BUFA = BUFA_ROWS * A_LD, BUFB = BUFB_ROWS * A_LD, BUFP = PROJ * P_LD;
 constexpr int SMALL = 1024;              // ps[128] | red[512] | sc[128] | misc
+constexpr int MAX_T = 128;               // frames per window of vadx_fsmn_run: ps and sc hold 128 (the clips / ragged / stream entries take 112)
 constexpr int LDS_FLOATS = BUFA + BUFB + BUFP + SMALL;
 
 struct Dev {
@@ -254,13 +255,21 @@ __device__ __forceinline__ void tile_split(const Dev &d, const float *__restrict
     const int lane = tid & 63, i = lane & 15;
     auto grp_pl = [](int kgrps, int ncol) { return kgrps * ncol * 16; };      // bytes of one plane
 
-    // ---- zero rows: k-groups of the A-wide tensors beyond Ap (their weights are zero, the operand must be finite), the log-mel's row 10
-    {
-        const int kg0 = d.Ap / 8, kg1 = 4 * d.nch_A, pl = grp_pl(kg1, NF);
-        for (int e = tid; e < NP * (kg1 - kg0) * NF; e += THREADS) {
-            const int p = e / ((kg1 - kg0) * NF), r = e - p * (kg1 - kg0) * NF;
-            *reinterpret_cast<f32x4 *>(smem + SQ_H + p * pl + (kg0 * NF + r) * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
+    // A layer's last 32-k chunk reads four k-groups whatever the tensor's width: k-groups kg0 .. kg1 - 1 of the NP planes [kg1][NF][8] at
+    // `base` lie beyond the padded width (Ap, Lp or A2p, multiples of 16 but not of 32), no layer writes them, and what they overlap in the
+    // LDS map (float32 P and logits, other tensors' planes) read as fp16 / bf16 can be Inf or NaN -- the weights there are zero, the
+    // operand must be finite.  Called by every thread before the layer that writes the tensor (the region is free then, and P / FO of the
+    // next layers overwrite it again: once per tile would not do).  Nothing to do when the width is a multiple of 32.
+    auto zero_rows = [&](unsigned char *base, int kg0, int kg1) {
+        const int pl = grp_pl(kg1, NF), n = (kg1 - kg0) * NF;
+        for (int e = tid; e < NP * n; e += THREADS) {
+            const int p = e / n, r = e - p * n;
+            *reinterpret_cast<f32x4 *>(base + p * pl + (kg0 * NF + r) * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
+    };
+    // ---- zero rows: k-groups of the A-wide tensor beyond Ap, the log-mel's row 10
+    {
+        zero_rows(smem + SQ_H, d.Ap / 8, 4 * d.nch_A);
         for (int e = tid; e < NP * NCL; e += THREADS) {
             const int p = e / NCL, c = e - p * NCL;
             *reinterpret_cast<f32x4 *>(smem + SQ_LM + p * grp_pl(11, NCL) + (10 * NCL + c) * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -306,6 +315,7 @@ __device__ __forceinline__ void tile_split(const Dev &d, const float *__restrict
     float hv[NH];
     cache_fetch(0, hv);
     // in_linear2 + ReLU
+    zero_rows(smem + SQ_HLM, d.Lp / 8, 4 * d.nch_L);
     a = QLayerArgs{Pk + d.q_in2, d.Lp / 16, d.nch_A, Pk + d.off_b2, 1, smem + SQ_H, grp_pl(4 * d.nch_A, NF), smem + SQ_HLM, grp_pl(4 * d.nch_L, NF), NF, nullptr};
     qlayer<SC, MTT, true>(a, plain(NF), amax);
     __syncthreads();
@@ -375,17 +385,12 @@ __device__ __forceinline__ void tile_split(const Dev &d, const float *__restrict
             }
         }
         __syncthreads();
+        zero_rows(HLout, d.Lp / 8, 4 * d.nch_L);
         a = QLayerArgs{Pk + d.q_aff[l], d.Lp / 16, PROJ / 32, Pk + d.off_baff[l], 1, FO, grp_pl(PROJ / 8, NF), HLout, grp_pl(4 * d.nch_L, NF), NF, nullptr};
         qlayer<SC, MTT, true>(a, plain(NF), amax);
         __syncthreads();
     }
-    {   // zero rows of the A2-wide tensor (region 0 is free again)
-        const int kg0 = d.A2p / 8, kg1 = 4 * d.nch_A2, pl = grp_pl(kg1, NF);
-        for (int e = tid; e < NP * (kg1 - kg0) * NF; e += THREADS) {
-            const int p = e / ((kg1 - kg0) * NF), r = e - p * (kg1 - kg0) * NF;
-            *reinterpret_cast<f32x4 *>(smem + SQ_H + p * pl + (kg0 * NF + r) * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    }
+    zero_rows(smem + SQ_H, d.A2p / 8, 4 * d.nch_A2);       // the A2-wide tensor (region 0 is free again)
     a = QLayerArgs{Pk + d.q_out1, d.A2p / 16, d.nch_L, Pk + d.off_bo1, 0, smem + SQ_HLM, grp_pl(4 * d.nch_L, NF), smem + SQ_H, grp_pl(4 * d.nch_A2, NF), NF, nullptr};
     qlayer<SC, MTT, true>(a, plain(NF), amax);
     __syncthreads();
@@ -1026,6 +1031,7 @@ extern "C" int vadx_fsmn_run(const vadx_fsmn_dims *dims, const float *packed, co
     VADX_REQUIRE(dims && packed && logmel && db && cache_in && cache_out && thr && noise_db && score && noisy_db,
                  "vadx_fsmn_run: NULL argument");
     VADX_REQUIRE(derive(dims, &d) == 0, "vadx_fsmn_run: unsupported dims");
+    VADX_REQUIRE(d.T <= MAX_T, "vadx_fsmn_run: frames=%d unsupported (at most %d per window: window_len <= %d)", d.T, MAX_T, MAX_T * 160 - 1);
     VADX_REQUIRE(batch > 0, "vadx_fsmn_run: batch must be positive");
     int rc = set_lds_attr();
     if (rc) return rc;

@@ -20,6 +20,7 @@ from . import weights as _weights
 SAMPLE_RATE = 16000
 OUTPUT_FRAME_LENGTH = 160
 PROJ, HIST = 128, 19
+MAX_FRAMES = 128             # frames per window the kernel's score scratch holds (vadx_fsmn_run); `flags`, ragged batches and streams take 112
 
 
 def _loop_params(lb, speaking_score=0.5, silence_score=0.5, snr_threshold=10.0, noise_init_dB=30.0, one_minus_speech_threshold=1.0):
@@ -46,6 +47,10 @@ class FsmnEngine:
         w = _checkpoints.resolve("fsmn", weights)
         w = {k: np.ascontiguousarray(np.asarray(v), dtype=np.float32) for k, v in w.items()}
         self.L = int(input_audio_length)
+        if self.L // OUTPUT_FRAME_LENGTH + 1 > MAX_FRAMES:
+            raise ValueError(f"input_audio_length={self.L} gives {self.L // OUTPUT_FRAME_LENGTH + 1} frames per window: the FSMN kernel takes at most "
+                             f"{MAX_FRAMES} (input_audio_length <= {MAX_FRAMES * OUTPUT_FRAME_LENGTH - 1}); `flags`, ragged batches and streams "
+                             f"need at most 112 (input_audio_length <= {112 * OUTPUT_FRAME_LENGTH - 1})")
         self.fe = _frontend.Frontend("fsmn", self.L, device=device)
         self.T = self.fe.frames
         dims = _lib.FsmnDims()
