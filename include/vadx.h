@@ -502,6 +502,10 @@ int vadx_tracks_gather(const float *probs, int64_t win_floats, int chan_offset, 
 typedef struct vadx_firered_cfg {        /* checkpoint `args` (FireRedVAD/Export_FireRedVAD.py:336-337) */
     int idim, R, M, H, P, N1, S1, N2, S2, odim;
     int frames;                           /* frames per window: (L-400)//160+1 = 98 */
+    /* Limits (a cfg outside them: vadx_firered_packed_floats returns 0, every other entry point VADX_EINVAL): idim = 80; 1 <= R <= 16; 1 <= M <= 4; 1 <= H <= 256;
+     * 1 <= P <= 128; 1 <= N1 <= 32 and 0 <= N2 <= 32 taps at any dilation S1, S2 >= 1 (a filter may reach beyond the window);
+     * 1 <= odim <= 4; 1 <= frames <= 112, for a window of vadx_firered_run and for a chunk of vadx_firered_stream_run alike (18 160
+     * samples).  tests/test_gpu_firered_shapes.py runs the edges of each. */
     int arithmetic;                       /* VADX_ARITH_* of the point-wise layer pairs (0 = AUTO = BF16X3 where H = 256, P = 128; float32 MFMAs
                                            * elsewhere; F16X2 on request, with vadx_firered_range_flag).  As vadx_fsmn_dims.arithmetic: the blob
                                            * carries the fragments of this arithmetic only. */

@@ -16,6 +16,7 @@ from .fsmn import _Meta, pad_to_window_grid
 
 SAMPLE_RATE, WINDOW_LENGTH, HOP_LENGTH = 16000, 400, 160
 STREAM_CHUNK_SAMPLES = 2560          # 160 ms (Export_FireRedVAD.py:52-53)
+MAX_FRAMES = 112                     # frames of one window / stream chunk the kernels keep in LDS (csrc/firered.hip: MAX_T)
 
 
 def valid_frame_count(num_samples, in_sample_rate=SAMPLE_RATE):
@@ -36,6 +37,9 @@ class FireRedEngine:
         w = {k: (np.ascontiguousarray(np.asarray(v), dtype=np.float32) if k != "cfg" else v) for k, v in w.items()}
         self.L = int(input_audio_length)
         self.in_sample_rate = int(in_sample_rate)
+        if valid_frame_count(self.L, self.in_sample_rate) > MAX_FRAMES:      # refused by name, before anything is packed or uploaded
+            raise ValueError(f"a FireRed window holds at most {MAX_FRAMES} frames, {self.L} samples at {self.in_sample_rate} Hz are "
+                             f"{valid_frame_count(self.L, self.in_sample_rate)}")
         self.fe = _frontend.Frontend("firered", self.L, device=device, in_sample_rate=self.in_sample_rate)
         self._fes = {self.L: self.fe}
         self.T = self.fe.frames
@@ -184,6 +188,8 @@ class FireRedEngine:
         S, n = audio_i16.shape
         if n < WINDOW_LENGTH:
             raise ValueError(f"a stream chunk needs at least {WINDOW_LENGTH} samples, got {n}")
+        if valid_frame_count(n, self.in_sample_rate) > MAX_FRAMES:           # before the front-end runs: the net would refuse its log-mel
+            raise ValueError(f"a stream chunk holds at most {MAX_FRAMES} frames, {n} samples are {valid_frame_count(n, self.in_sample_rate)}")
         R, _, P, pad = self.cache_shape
         if tuple(caches_in.shape) != (R, S, P, pad) or caches_in.dtype != t.float32:
             raise ValueError(f"caches_in must be float32 {[R, S, P, pad]}, got {list(caches_in.shape)}")
