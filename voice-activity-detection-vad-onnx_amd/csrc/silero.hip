@@ -9,7 +9,8 @@
 //       Output gx[T][B/16][wave][gate][lane][4] in exactly the register order the LSTM kernel reads.
 //   silero_lstm_kernel   : one persistent workgroup per 16 clips; W_hh (512x128 f32 = 256 KB) lives
 //       in the VGPRs of its 8 waves for all T steps; h is exchanged through double-buffered LDS.
-//   silero_segments_kernel: get_speech_timestamps' state machine, one clip per thread.
+//   silero_segments_kernel: get_speech_timestamps' state machine, one clip per wave: lanes are windows, ballots give the
+//       threshold masks, and the (wave-uniform) state machine visits only the windows at which it can act.
 #include "silero_common.h"
 #include "split_scheme.h"
 
@@ -622,15 +623,20 @@ __global__ __launch_bounds__(LSTM_THREADS, 2) void silero_lstm_kernel(
     }
 }
 
-// ---- segmenter: get_speech_timestamps' state machine (utils_vad.py:374-476), one clip/thread ----
-// SEG_CLIPS clips per wave: the state machine diverges per clip (a wave pays for every path its lanes take), and 64 clips per wave
-// leave three quarters of the CUs without work at 4096 clips
-constexpr int SEG_CLIPS = 16;
-__global__ void silero_segments_kernel(const float *__restrict__ probs, int B, int T,
+// ---- segmenter: get_speech_timestamps' state machine (utils_vad.py:374-476), one clip per wave, event driven ----
+// Lanes are windows: 64 scores are read coalesced, two ballots turn them into the masks ge (p >= threshold) and lt (p < neg_threshold),
+// and the state machine -- wave-uniform, so scalar -- is fed only the positions at which step() can change anything:
+//   not triggered: the next set bit of ge;
+//   triggered:     the next set bit of lt | (temp_end ? ge : 0), or cur_start + d_max_speech + 1 if that comes first.
+// Everywhere else step() provably falls through all four of its conditions.  A NaN score sets neither bit, as in the plain loop.
+// (One clip per lane walked all T windows on a divergent wave at ~1000 cycles each: 0.13 ms per 4096 x 313 for about four segments a clip.)
+constexpr int SEG_WAVES = 4;                     // clips (waves) per workgroup
+__global__ __launch_bounds__(64 * SEG_WAVES) void silero_segments_kernel(const float *__restrict__ probs, int B, int T,
                                        const long long *__restrict__ n_samples,
                                        vadx_silero_seg_params prm, long long *__restrict__ segs,
                                        int *__restrict__ counts, int cap) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * SEG_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (b >= B) return;
     const double sr = (double)prm.sampling_rate;
     const long long W = (prm.sampling_rate == 16000) ? 512 : 256;
@@ -647,7 +653,7 @@ __global__ void silero_segments_kernel(const float *__restrict__ probs, int B, i
     long long *out = segs + (size_t)b * cap * 2;
     int ns = 0;
     auto push = [&](long long s, long long e) {
-        if (ns < cap) { out[2 * ns] = s; out[2 * ns + 1] = e; }
+        if (ns < cap && lane == 0) { out[2 * ns] = s; out[2 * ns + 1] = e; }
         ++ns;
     };
 
@@ -660,82 +666,101 @@ __global__ void silero_segments_kernel(const float *__restrict__ probs, int B, i
     auto win_ceil = [&](double x) { const double q = ceil(x / (double)W); return q >= 2147483647.0 ? 2147483647 : (q <= -2147483648.0 ? (int)-2147483647 - 1 : (int)q); };
     auto f32_not_below = [](double x) { float f = (float)x; if ((double)f < x) f = nextafterf(f, INFINITY); return f; };
     const float thr_f = f32_not_below(thr), neg_f = f32_not_below(neg);
-    const int d_sil_at_max = win_floor(min_sil_at_max), d_max_speech = win_floor(max_speech), d_min_sil = win_ceil(min_sil),
-              d_min_speech = win_floor(min_speech);
+    // (readfirstlane: the thresholds come out of double arithmetic, which only the vector unit has; the state machine compares them on the scalar one)
+    const int d_sil_at_max = __builtin_amdgcn_readfirstlane(win_floor(min_sil_at_max)), d_max_speech = __builtin_amdgcn_readfirstlane(win_floor(max_speech)),
+              d_min_sil = __builtin_amdgcn_readfirstlane(win_ceil(min_sil)), d_min_speech = __builtin_amdgcn_readfirstlane(win_floor(min_speech));
     auto pushw = [&](int s_, int e_) { push((long long)s_ * W, (long long)e_ * W); };
 
     bool triggered = false, have_cur = false, have_possible = false;
     int cur_start = 0, temp_end = 0, prev_end = 0, next_start = 0;      // window indices (0 doubles as "unset", like the reference)
     int best_end = 0, best_dur = 0;
-    auto step = [&](int pos, float p) {          // one probability through the state machine (`continue` -> return)
-        if (p >= thr_f && temp_end) {
-            const int gap = pos - temp_end;
-            if (gap > d_sil_at_max) {
-                if (!have_possible || gap > best_dur) { best_end = temp_end; best_dur = gap; }
-                have_possible = true;
+    // 64 windows at a time, the next chunk's scores requested before the current one is walked
+    const float *pr = probs + (size_t)b * T;
+    const float qnan = __builtin_nanf("");
+    float p = lane < nwin ? pr[lane] : qnan;
+    for (int k0 = 0; k0 < nwin; k0 += 64) {      // (leaves through the break below: k0 + 64 may not be representable)
+        const float pn = (nwin - k0 > 64 + lane) ? pr[k0 + 64 + lane] : qnan;
+        const unsigned long long ge_m = __ballot(p >= thr_f), lt_m = __ballot(p < neg_f);
+        const int len = nwin - k0 < 64 ? nwin - k0 : 64;
+        int i = 0;                               // the first position of this chunk not yet looked at
+        while (i < len) {
+            const unsigned long long m = (triggered ? (lt_m | (temp_end ? ge_m : 0ULL)) : ge_m) & (~0ULL << i);
+            int nx = m ? (int)__builtin_ctzll(m) : 64;
+            if (triggered) {
+                // pos - cur_start > d_max_speech first holds at cur_start + d_max_speech + 1; beyond INT_MAX (d_max_speech may be INT_MAX, cur_start is
+                // never negative) that is nowhere.  In 32 bits on purpose: the scalar unit has no 64-bit ordered compare, and one on the vector unit
+                // drags the whole state machine over there.
+                int last;                        // the last position that is still within d_max_speech
+                const bool nowhere = __builtin_sadd_overflow(cur_start, d_max_speech, &last) || last == 2147483647;
+                const int li = (nowhere || last + 1 >= k0 + len) ? 64 : (last + 1 <= k0 + i ? i : last + 1 - k0);
+                nx = li < nx ? li : nx;
             }
-            temp_end = 0;
-            if (next_start < prev_end) next_start = pos;
-        }
-        if (p >= thr_f && !triggered) {
-            triggered = true; cur_start = pos; have_cur = true;
-            return;
-        }
-        if (triggered && (pos - cur_start) > d_max_speech) {
-            if (prm.use_max_poss_sil_at_max_speech && have_possible) {
-                prev_end = best_end;
-                pushw(cur_start, prev_end);
-                have_cur = false;
-                next_start = prev_end + best_dur;
-                if (next_start < prev_end + pos) { cur_start = next_start; have_cur = true; }
-                else triggered = false;
-                prev_end = next_start = temp_end = 0;
-                have_possible = false;
-            } else if (prev_end) {
-                pushw(cur_start, prev_end);
-                have_cur = false;
-                if (next_start < prev_end) triggered = false;
-                else { cur_start = next_start; have_cur = true; }
-                prev_end = next_start = temp_end = 0;
-                have_possible = false;
-            } else {
-                pushw(cur_start, pos);
+            if (nx >= len) break;
+            // step(): window k0 + nx through the reference's loop body, `continue` as there.  It needs the two bits only.  (In place, not a lambda
+            // that captures the state by reference: compiled on its own, such a lambda merges stores to different state variables into one store
+            // through a selected address, the state then lives in scratch, and every value read back from there counts as divergent.)
+            const int pos = k0 + nx;
+            const bool ge = (ge_m >> nx) & 1ULL, lt = (lt_m >> nx) & 1ULL;
+            i = nx + 1;
+            if (ge && temp_end) {
+                const int gap = pos - temp_end;
+                if (gap > d_sil_at_max) {
+                    if (!have_possible || gap > best_dur) { best_end = temp_end; best_dur = gap; }
+                    have_possible = true;
+                }
+                temp_end = 0;
+                if (next_start < prev_end) next_start = pos;
+            }
+            if (ge && !triggered) {
+                triggered = true; cur_start = pos; have_cur = true;
+                continue;
+            }
+            if (triggered && (pos - cur_start) > d_max_speech) {
+                if (prm.use_max_poss_sil_at_max_speech && have_possible) {
+                    prev_end = best_end;
+                    pushw(cur_start, prev_end);
+                    have_cur = false;
+                    next_start = prev_end + best_dur;
+                    if (next_start < prev_end + pos) { cur_start = next_start; have_cur = true; }
+                    else triggered = false;
+                    prev_end = next_start = temp_end = 0;
+                    have_possible = false;
+                } else if (prev_end) {
+                    pushw(cur_start, prev_end);
+                    have_cur = false;
+                    if (next_start < prev_end) triggered = false;
+                    else { cur_start = next_start; have_cur = true; }
+                    prev_end = next_start = temp_end = 0;
+                    have_possible = false;
+                } else {
+                    pushw(cur_start, pos);
+                    have_cur = false;
+                    prev_end = next_start = temp_end = 0;
+                    triggered = false;
+                    have_possible = false;
+                    continue;
+                }
+            }
+            if (lt && triggered) {
+                if (!temp_end) temp_end = pos;
+                const int sil_now = pos - temp_end;
+                if (!prm.use_max_poss_sil_at_max_speech && sil_now > d_sil_at_max) prev_end = temp_end;
+                if (sil_now < d_min_sil) continue;
+                if ((temp_end - cur_start) > d_min_speech) pushw(cur_start, temp_end);
                 have_cur = false;
                 prev_end = next_start = temp_end = 0;
                 triggered = false;
                 have_possible = false;
-                return;
+                continue;
             }
         }
-        if (p < neg_f && triggered) {
-            if (!temp_end) temp_end = pos;
-            const int sil_now = pos - temp_end;
-            if (!prm.use_max_poss_sil_at_max_speech && sil_now > d_sil_at_max) prev_end = temp_end;
-            if (sil_now < d_min_sil) return;
-            if ((temp_end - cur_start) > d_min_speech) pushw(cur_start, temp_end);
-            have_cur = false;
-            prev_end = next_start = temp_end = 0;
-            triggered = false;
-            have_possible = false;
-            return;
-        }
-        };
-    // probabilities are fetched eight at a time, unconditionally (clamped index): a per-step load sat on the serial path
-    // of all T steps (0.23 ms per batch for what is a few microseconds of arithmetic).  (Staging them through LDS with
-    // coalesced row reads was tried: no further gain -- what remains is the divergent state machine itself, ~1000
-    // cycles per step for one wave per 64 clips.)
-    const float *pr = probs + (size_t)b * T;
-    for (int k0 = 0; k0 < nwin; k0 += 8) {
-        float buf[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) buf[j] = pr[k0 + j < T ? k0 + j : T - 1];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (k0 + j < nwin) step(k0 + j, buf[j]);
+        if (nwin - k0 <= 64) break;
+        p = pn;
     }
     if (have_cur && (double)(L - (long long)cur_start * W) > min_speech) push((long long)cur_start * W, L);
 
     // +-speech_pad with midpoint split of short gaps (utils_vad.py:464-476)
+    if (lane != 0) return;                       // lane 0 wrote the table (push), lane 0 pads it
     const int m = ns < cap ? ns : cap;
     for (int s = 0; s < m; ++s) {
         if (s == 0) out[0] = (long long)fmax(0.0, (double)out[0] - pad);
@@ -963,7 +988,7 @@ extern "C" int vadx_silero_segments(const float *probs, int batch, int steps, co
     VADX_REQUIRE(batch > 0 && steps > 0 && cap > 0, "vadx_silero_segments: batch/steps/cap must be positive");
     VADX_REQUIRE(params->sampling_rate == 16000 || params->sampling_rate == 8000,
                  "Currently silero VAD models support 8000 and 16000 (or multiply of 16000) sample rates");
-    hipLaunchKernelGGL(silero_segments_kernel, dim3((batch + SEG_CLIPS - 1) / SEG_CLIPS), dim3(SEG_CLIPS), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(silero_segments_kernel, dim3((batch + SEG_WAVES - 1) / SEG_WAVES), dim3(64 * SEG_WAVES), 0, static_cast<hipStream_t>(stream),
                        probs, batch, steps, reinterpret_cast<const long long *>(n_samples), *params,
                        reinterpret_cast<long long *>(segments), counts, cap);
     VADX_HIP_TRY(hipGetLastError());

@@ -623,8 +623,15 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
 // clip (128 registers: no weight bytes in LDS at all); 48 v_mfma_f32_16x16x32_f16 per wave and step instead of 96 bf16.  |h| <= 1 and W_hh
 // passed the pack-time range check, so nothing here can leave the fp16 range.
 constexpr int LH_HPL = 4096, LH_HBUF = 8192;     // h planes [2 buffers][2 planes][16 k-groups][16 clips][8 fp16]
-constexpr int LH_PART = 2 * LH_HBUF;             // f32 [2][8 waves][16 clips]
-constexpr int LH_BYTES = LH_PART + 1024;
+// The decoder's per-wave partial sums wait in an LDS ring and the scores leave in blocks of LH_BLK steps: after the barrier of a block's last
+// step (and of the clip's last step) 256 lanes -- 16 clips x 16 steps -- add db + part[0] + ... + part[7] in that order, take the sigmoid and store
+// 64 contiguous bytes per clip.  (Per step, wave 0 alone used to read the eight partials and issue sixteen scattered 4-byte stores behind every
+// barrier, and the other seven waves met it late at the next one.)  Two blocks: the waves that do not flush run ahead into the next block's
+// slots while the other one is read; a block is written again only after a later barrier, which the flushing waves pass after their reads.
+constexpr int LH_BLK = 16;
+constexpr int LH_SLOT = 8 * 16 + 4;              // floats per step [8 waves][16 clips], +4: the flush's reads (lane = 16 clip + step) hit 64 banks
+constexpr int LH_PART = 2 * LH_HBUF;             // f32 [2 blocks][LH_BLK steps][LH_SLOT]
+constexpr int LH_BYTES = LH_PART + 2 * LH_BLK * LH_SLOT * 4;
 // gx (the encoder's gate pre-activations, 32 KB per step and workgroup out of HBM: 2.6 GB per launch at config 2 = 4.3 TB/s) is requested
 // LH_GX_AHEAD steps ahead: with one step of lead a lone workgroup ran 1.42 us per step and the full grid 1.95 -- the loaded HBM's
 // latency exceeds a step.
@@ -726,13 +733,18 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_h2_kernel(
         store_h4(smem + nxt * LH_HBUF, LH_HPL, 4 * wave + q, n, h, amax);
         dpart += __shfl_xor(dpart, 16);
         dpart += __shfl_xor(dpart, 32);
-        if (q == 0) part[(nxt * 8 + wave) * 16 + n] = dpart;
+        if (q == 0) part[(t & (2 * LH_BLK - 1)) * LH_SLOT + wave * 16 + n] = dpart;
         __syncthreads();
-        if (wave == 0 && lane < 16 && bvalid) {
-            float s = db;
+        if ((t & (LH_BLK - 1)) == LH_BLK - 1 || t == T - 1) {        // uniform: this block's scores leave
+            const int fc = tid >> 4, fs = tid & (LH_BLK - 1), t_blk = t & ~(LH_BLK - 1);
+            const long long fb = (long long)grp * 16 + fc;
+            if (tid < 16 * LH_BLK && fb < B && t_blk + fs <= t) {
+                const float *pp = part + ((t_blk + fs) & (2 * LH_BLK - 1)) * LH_SLOT + fc;
+                float s = db;
 #pragma unroll
-            for (int w = 0; w < 8; ++w) s += part[(nxt * 8 + w) * 16 + lane];
-            probs[b * probs_stride + t] = sigmoidf_(s);
+                for (int w = 0; w < 8; ++w) s += pp[w * 16];
+                probs[fb * probs_stride + t_blk + fs] = sigmoidf_(s);
+            }
         }
         cur = nxt;
     }
@@ -746,7 +758,9 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_h2_kernel(
         atomicOr(fl, 1u);
         atomicMax(fl + 1, __float_as_uint(amax));
     }
-    // ... and then this clip group's scores are NaN, not numbers (cf. the encoder's gx)
+    // ... and then this clip group's scores are NaN, not numbers (cf. the encoder's gx).  The overwrite comes from other lanes than the flushes'
+    // stores to the same addresses: those are drained (the fence waits for them) before the barrier, so that the NaNs land last.
+    __threadfence();
     __syncthreads();
     if (__ballot(!(amax <= H_MAX)) != 0ULL && lane == 0) reinterpret_cast<unsigned *>(part)[wave] = 1u;
     else if (lane == 0) reinterpret_cast<unsigned *>(part)[wave] = 0u;
