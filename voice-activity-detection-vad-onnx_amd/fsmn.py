@@ -21,6 +21,9 @@ SAMPLE_RATE = 16000
 OUTPUT_FRAME_LENGTH = 160
 PROJ, HIST = 128, 19
 MAX_FRAMES = 128             # frames per window the kernel's score scratch holds (vadx_fsmn_run); `flags`, ragged batches and streams take 112
+# The stream record of S streams, mirroring the contract in include/vadx.h, as three sections in this order:
+CACHES, HEADER, CARRY = 0, 1, 2      # f32 [S][4][128][19] | u32 [S][8]: word H_PRIMED = has a carry, H_DONE and the next = windows done (u64) | int16 [S][(lb + 1) * 160]
+CACHE_BYTES, HDR_BYTES, H_PRIMED, H_DONE = 4 * PROJ * HIST * 4, 8 * 4, 2, 4
 
 
 def _loop_params(lb, speaking_score=0.5, silence_score=0.5, snr_threshold=10.0, noise_init_dB=30.0, one_minus_speech_threshold=1.0):
@@ -32,6 +35,12 @@ def _loop_params(lb, speaking_score=0.5, silence_score=0.5, snr_threshold=10.0, 
     lp.snr_threshold = float(snr_threshold * 0.1)
     lp.speaking_score, lp.silence_score = float(speaking_score), float(silence_score)
     return lp
+
+
+def _timestamps(flags, fusion_threshold, min_speech_duration):
+    """One clip's or stream's silence flags (1-D) -> [(start_s, end_s)]: the reference's vad_to_timestamps + process_timestamps over its `saved` list."""
+    ts = _ts.vad_to_timestamps(np.asarray(flags).astype(bool), OUTPUT_FRAME_LENGTH / SAMPLE_RATE)
+    return _ts.process_timestamps(ts, fusion_threshold, min_speech_duration)
 
 
 class _Meta:
@@ -245,11 +254,7 @@ class FsmnEngine:
             rb = self.ragged(clips_i16, pad_noise, normalize, loop_kw.get("look_backward_s", 0.3))
             flags, nflags = self.flags_ragged(rb, **loop_kw)
             flags = flags.cpu().numpy()
-            out = []
-            for b in range(len(rb)):
-                ts = _ts.vad_to_timestamps(flags[b, :nflags[b]].astype(bool), OUTPUT_FRAME_LENGTH / SAMPLE_RATE)
-                out.append(_ts.process_timestamps(ts, fusion_threshold, min_speech_duration))
-            return out
+            return [_timestamps(flags[b, :nflags[b]], fusion_threshold, min_speech_duration) for b in range(len(rb))]
         clips = np.asarray(clips_i16)
         B, n = clips.shape
         lb, stride = self.grid(loop_kw.get("look_backward_s", 0.3))
@@ -260,11 +265,7 @@ class FsmnEngine:
         padded = np.stack(rows)
         W = (padded.shape[1] - self.L) // stride + 1
         flags = self.flags(self.torch.from_numpy(padded), W, **loop_kw).cpu().numpy()
-        out = []
-        for b in range(B):
-            ts = _ts.vad_to_timestamps(flags[b].astype(bool), OUTPUT_FRAME_LENGTH / SAMPLE_RATE)
-            out.append(_ts.process_timestamps(ts, fusion_threshold, min_speech_duration))
-        return out
+        return [_timestamps(flags[b], fusion_threshold, min_speech_duration) for b in range(B)]
 
 
 def pad_to_window_grid(audio_i16, window, stride, noise=None):
@@ -389,22 +390,25 @@ class FsmnStreamBatch:
         """The current device record (uint8); its first S*4*128*19 floats are the FIR caches [S,4,128,19]."""
         return self._rec[self._cur]
 
+    def _section(self, record, i):
+        """Section i (CACHES, HEADER or CARRY) of `record` as a uint8 view [S, that section's bytes per stream]."""
+        per = (CACHE_BYTES, HDR_BYTES, self.carry * 2)
+        at = self.streams * sum(per[:i])
+        return record[at:at + self.streams * per[i]].view(self.streams, per[i])
+
     @property
     def caches(self):
-        return self.record[:self.streams * 4 * PROJ * HIST * 4].view(self.engine.torch.float32).view(self.streams, 4, PROJ, HIST)
+        return self._section(self.record, CACHES).view(self.engine.torch.float32).view(self.streams, 4, PROJ, HIST)
 
     def stream_bytes(self, record, s):
         """Every byte of `record` that belongs to stream s (caches, header, carry), as one uint8 tensor."""
-        S, cb, hb, kb = self.streams, 4 * PROJ * HIST * 4, 32, self.carry * 2
-        return self.engine.torch.cat([record[s * cb:(s + 1) * cb], record[S * cb + s * hb:S * cb + (s + 1) * hb],
-                                      record[S * (cb + hb) + s * kb:S * (cb + hb) + (s + 1) * kb]])
+        return self.engine.torch.cat([self._section(record, i)[s] for i in (CACHES, HEADER, CARRY)])
 
     @property
     def windows_done(self):
         """int64 [S] (host): windows each stream has done since its reset, read from the device record.  Flag i of a stream's next tick
         is frame windows_done * (T - look_backward) + i of its audio, 10 ms per frame."""
-        S, cb = self.streams, 4 * PROJ * HIST * 4
-        return self.record[S * cb:S * (cb + 32)].view(self.engine.torch.int64).view(S, 4)[:, 2].cpu().numpy()
+        return self._section(self.record, HEADER).view(self.engine.torch.int64)[:, H_DONE // 2].cpu().numpy()
 
     def load_record(self, record):
         """Continue from a saved copy of `record` (uint8, same streams and look-back): the bytes are copied into the current record."""
@@ -412,8 +416,7 @@ class FsmnStreamBatch:
         if r.dtype != self.engine.torch.uint8 or r.numel() != self.record.numel():
             raise ValueError(f"record must be uint8 [{self.record.numel()}], got {r.dtype} [{r.numel()}]")
         self.record.copy_(r.reshape(-1))
-        S, cb = self.streams, 4 * PROJ * HIST * 4
-        self._primed = self.record[S * cb:S * (cb + 32)].view(self.engine.torch.int32).view(S, 8)[:, 2].cpu().numpy() != 0
+        self._primed = self._section(self.record, HEADER).view(self.engine.torch.int32)[:, H_PRIMED].cpu().numpy() != 0
         self._pending[:] = False
 
     def reset_states(self, streams=None):
@@ -451,8 +454,6 @@ class FsmnStreamBatch:
         reset / active: bool [S] or None; an inactive stream keeps its record bit for bit, ignores a reset, and reads 255."""
         eng, t = self.engine, self.engine.torch
         k, S, L = int(windows), self.streams, self.engine.L
-        if k < 1:
-            raise ValueError(f"windows={windows} must be at least 1")
         x = samples_i16 if t.is_tensor(samples_i16) else t.from_numpy(np.ascontiguousarray(samples_i16))
         if x.dtype != t.int16:
             raise ValueError(f"samples must be int16, got {x.dtype}")
@@ -460,8 +461,7 @@ class FsmnStreamBatch:
             raise ValueError(f"samples must be [{S}, n], got {tuple(x.shape)}")
         act = np.ones(S, dtype=bool) if active is None else self._mask(active, "active")
         req = (self._pending | self._mask(reset, "reset") if reset is not None else self._pending) & act      # resets this tick applies
-        fresh = (~self._primed | req) & act
-        need = int(np.where(fresh, L + (k - 1) * self.stride, k * self.stride)[act].max(initial=0))
+        need = int(self.samples_needed(k, reset)[act].max(initial=0))       # refuses windows < 1; an active stream is fresh without a carry or with a reset
         if x.shape[1] < need:
             raise ValueError(f"samples rows hold {x.shape[1]} samples, this tick needs {need} (samples_needed)")
         x = x.to(eng.device)
@@ -504,5 +504,4 @@ class FsmnStreamBatch:
         """One stream's accumulated flags (1-D, every tick so far) + the last tick's tail -> [(start_s, end_s)], the reference's
         vad_to_timestamps + process_timestamps over its `saved` list."""
         f = np.concatenate([np.asarray(a.cpu() if hasattr(a, "cpu") else a).reshape(-1) for a in (flags_so_far, tail)])
-        ts = _ts.vad_to_timestamps(f.astype(bool), OUTPUT_FRAME_LENGTH / SAMPLE_RATE)
-        return _ts.process_timestamps(ts, fusion_threshold, min_speech_duration)
+        return _timestamps(f, fusion_threshold, min_speech_duration)
