@@ -583,6 +583,10 @@ typedef struct vadx_sepconv_cfg {
     int residual_cin;         /* 0: no residual branch; else channels of the block input */
     int relu;
 } vadx_sepconv_cfg;
+/* Limits, refused with VADX_EINVAL before any device call: channels in [1, 128]; a 32-frame tile's receptive field
+ * 31 * stride + (kernel - 1) * dilation + 1 <= 100; and the residual contract -- the block input xres is read with this sub-block's
+ * OUTPUT frame index and row length, so residual_cin > 0 needs stride == 1 and t_in == t_out (an odd kernel), and every earlier
+ * sub-block of the same Jasper block must have kept the frame count too (the caller's side: MarbleNetEngine refuses such a layout). */
 
 /* x: element (b, c, t) at x[b*xs_b + c*xs_c + t*xs_t] (lets the first block read the time-major
  * log-mel directly); xres [B][residual_cin][t_out]; y [B][cout][t_out].  Weights on the device:

@@ -64,11 +64,12 @@ def _bn(x, w, p):
     return F.batch_norm(x, w[p + "_mean"], w[p + "_var"], w[p + "_gamma"], w[p + "_beta"], False, 0.0, EPS)
 
 
-def encoder(w, x):
-    """[B,80,T] -> ([B,128,T'], lengths).  Unfolded weights (conv + BatchNorm in eval mode)."""
+def encoder(w, x, blocks=BLOCKS):
+    """[B,80,T] -> ([B,128,T'], lengths).  Unfolded weights (conv + BatchNorm in eval mode).  `blocks`: another Jasper stack in BLOCKS'
+    form (a plain block is a 1x1 conv whatever its kernel entry says, as in the product)."""
     length = x.shape[-1]
     cin = x.shape[1]
-    for bi, (filt, rep, k, stride, dil, residual, sep) in enumerate(BLOCKS):
+    for bi, (filt, rep, k, stride, dil, residual, sep) in enumerate(blocks):
         block_in = x
         for r in range(rep):
             p = f"b{bi}r{r}"

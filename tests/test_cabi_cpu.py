@@ -188,6 +188,112 @@ def test_fsmn_run_refuses_a_window_longer_than_its_score_scratch(lib):
         assert b"frames=%d unsupported" % frames in lib.vadx_last_error()
 
 
+def test_sepconv_block_refuses_what_its_kernel_would_read_wrongly(lib):
+    """vadx_sepconv_block reads the residual tile xres[b][ch][t0 + m] with the OUTPUT's row length, so a residual sub-block that changes the
+    frame count (a stride, or an even kernel: 'same' padding gives T - 1) would add the wrong frames: refused with a message on the host,
+    before any device call (no GPU here: a HIP call would fail with another code), like channels beyond 128, a tile's receptive field
+    beyond 100 frames and a plain conv that is not 1x1.  MarbleNetEngine refuses the same layouts by name before it needs a device."""
+    import ctypes as C
+    from vadx import marblenet
+    buf = (C.c_float * 64)()
+    ptr = C.cast(buf, C.c_void_p).value
+
+    def run(t_in, t_out, **kw):
+        f = dict(cin=64, cout=64, kernel=13, stride=1, dilation=1, depthwise=1, residual_cin=0, relu=1)
+        f.update(kw)
+        cfg = _lib.SepConvCfg(*[f[k] for k, _ in _lib.SepConvCfg._fields_])
+        return lib.vadx_sepconv_block(C.byref(cfg), ptr, ptr, ptr, ptr, ptr, ptr, 64 * t_in, t_in, 1, t_in, ptr, ptr, 1, t_out, None, None)
+
+    for kw, t_in, t_out in ((dict(stride=2, residual_cin=64), 64, 32), (dict(kernel=12, residual_cin=64), 64, 63),
+                            (dict(kernel=4, stride=2, residual_cin=128), 65, 32)):
+        assert run(t_in, t_out, **kw) == -1
+        msg = lib.vadx_last_error()
+        assert b"residual branch needs stride 1 and t_in == t_out" in msg and b"t_in=%d t_out=%d" % (t_in, t_out) in msg, msg
+    assert run(64, 64, cin=129) == -1 and b"[1,128]" in lib.vadx_last_error()
+    assert run(64, 64, residual_cin=129) == -1 and b"[1,128]" in lib.vadx_last_error()
+    assert run(64, 64, kernel=70) == -1 and b"receptive field" in lib.vadx_last_error()             # 31 + 69 + 1 = 101
+    assert run(64, 22, kernel=8, stride=3) == -1 and b"receptive field" in lib.vadx_last_error()    # 93 + 7 + 1 = 101
+    assert run(64, 64, kernel=3, depthwise=0) == -1 and b"plain conv" in lib.vadx_last_error()
+    ok = ((128, 1, 11, 2, 1, False, True), (64, 2, 13, 1, 1, True, True), (128, 1, 1, 1, 1, False, False))
+    marblenet.check_blocks(weights.MARBLENET_BLOCKS)
+    marblenet.check_blocks(ok)
+    marblenet.check_blocks(((128, 1, 69, 1, 1, False, True), (128, 1, 7, 3, 1, False, True), (1, 1, 8, 1, 1, False, True)))
+    for bad, match in ((((64, 2, 13, 2, 1, True, True),), "frame count"), (((64, 2, 12, 1, 1, True, True),), "frame count"),
+                       (((64, 3, 4, 1, 3, True, True),), "frame count"), (((129, 1, 11, 2, 1, False, True),), r"\[1, 128\]"),
+                       (((128, 1, 70, 1, 1, False, True),), "receptive field"), (((128, 1, 8, 3, 1, False, True),), "receptive field"),
+                       (((128, 1, 3, 1, 1, False, False),), "1x1"), (((128, 1, 1, 2, 1, False, False),), "1x1")):
+        with pytest.raises(ValueError, match=match):
+            marblenet.check_blocks(ok[:1] + bad + ok[2:])
+        with pytest.raises(ValueError, match=match):                 # the engine refuses before it asks for a device
+            marblenet.MarbleNetEngine(None, blocks=ok[:1] + bad + ok[2:])
+
+
+def _parent_marblenet_synthetic(seed):
+    """weights.marblenet_synthetic as it was before it took `blocks`: the recipe tests/golden/marblenet_fold.npz and the decision records
+    were made with, restated tensor by tensor"""
+    rng, normal = weights._rng, weights._normal
+    w, cin = {}, 80
+
+    def bn(prefix, c):
+        w[prefix + "_gamma"] = (1.0 + 0.1 * rng(seed, prefix + "g").standard_normal(c)).astype(np.float32)
+        w[prefix + "_beta"] = normal(seed, prefix + "b", (c,), 0.1)
+        w[prefix + "_mean"] = normal(seed, prefix + "m", (c,), 0.2)
+        w[prefix + "_var"] = (0.5 + rng(seed, prefix + "v").uniform(0, 1, c)).astype(np.float32)
+
+    layout = ((128, 1, 11, False, True), (64, 2, 13, True, True), (64, 2, 15, True, True), (64, 2, 17, True, True), (128, 1, 29, False, True),
+              (128, 1, 1, False, False))
+    for bi, (filt, rep, k, residual, sep) in enumerate(layout):
+        block_cin = cin
+        for r in range(rep):
+            p = f"b{bi}r{r}"
+            if sep:
+                w[p + "_dw"] = normal(seed, p + "_dw", (cin, k), 1.0 / np.sqrt(k))
+            w[p + "_pw"] = normal(seed, p + "_pw", (filt, cin), 1.0 / np.sqrt(cin))
+            bn(p, filt)
+            cin = filt
+        if residual:
+            w[f"b{bi}res_pw"] = normal(seed, f"b{bi}res_pw", (filt, block_cin), 0.7 / np.sqrt(block_cin))
+            bn(f"b{bi}res", filt)
+    w["b0r0_mean"] = (w["b0r0_mean"] + (-8.0 * (w["b0r0_pw"] * w["b0r0_dw"].sum(axis=1)[None, :]).sum(axis=1))).astype(np.float32)
+    w["dec_w"] = normal(seed, f"dec_w_mb{weights._MARBLENET_DEC_TAG.get(seed, 0)}", (2, 128), 1.0 / np.sqrt(128))
+    w["dec_b"] = normal(seed, "dec_b_mb", (2,), 0.05)
+    s, t = weights._MARBLENET_DEC_CALIB.get(seed, (1.0, 0.0))
+    w["dec_w"][1] = w["dec_w"][0] + (w["dec_w"][1] - w["dec_w"][0]) * np.float32(s)
+    w["dec_b"][1] = w["dec_b"][0] + (w["dec_b"][1] - w["dec_b"][0]) * np.float32(s) + np.float32(t)
+    return w
+
+
+def test_marblenet_synthetic_default_is_bitwise_unchanged_and_other_layouts_can_be_written():
+    """`blocks` left at its default draws every tensor exactly as before (keyed by tensor name; the calibrated seeds 1234 and 7 and an
+    uncalibrated one); another layout has the tensors its blocks name, a decoder as wide as its last block, and a first block without
+    depthwise taps (plain, or k = 1) is centred on its pointwise gain alone.  The oracle runs such a layout."""
+    import torch
+    from oracle import marblenet as omb
+    assert tuple(weights.MARBLENET_BLOCKS) == tuple(omb.BLOCKS)
+    for seed in (1234, 7, 31):
+        want = _parent_marblenet_synthetic(seed)
+        for got in (weights.marblenet_synthetic(seed), weights.marblenet_synthetic(seed, weights.MARBLENET_BLOCKS)):
+            assert list(got) == list(want)
+            for k in want:
+                assert got[k].dtype == want[k].dtype == np.float32 and np.array_equal(got[k], want[k]), k
+    blocks = ((40, 1, 1, 1, 1, False, False), (100, 3, 5, 1, 3, True, True), (17, 1, 8, 3, 1, False, True))
+    w = weights.marblenet_synthetic(7, blocks)
+    assert "b0r0_dw" not in w and w["b0r0_pw"].shape == (40, 80) and w["b1r2_dw"].shape == (100, 5) and w["b1res_pw"].shape == (100, 40)
+    assert w["b2r0_dw"].shape == (100, 8) and w["dec_w"].shape == (2, 17)
+    drawn = weights._normal(7, "b0r0m", (40,), 0.2)
+    assert np.array_equal(w["b0r0_mean"], (drawn + -8.0 * w["b0r0_pw"].sum(axis=1)).astype(np.float32))
+    k1 = weights.marblenet_synthetic(7, ((40, 1, 1, 1, 1, False, True),) + blocks[1:])
+    assert np.array_equal(k1["b0r0_mean"], (drawn + -8.0 * (k1["b0r0_pw"] * k1["b0r0_dw"][:, 0][None, :]).sum(axis=1)).astype(np.float32))
+    wt = {k: torch.from_numpy(v) for k, v in w.items()}
+    x = torch.full((2, 80, 50), -8.0)
+    with torch.no_grad():
+        enc, length = omb.encoder(wt, x, blocks)
+        pre = torch.nn.functional.conv1d(x, wt["b0r0_pw"].unsqueeze(-1))[:, :, 0]
+    assert enc.shape == (2, 17, length) and length == (50 + 2 * 3 - 7 - 1) // 3 + 1 == 17
+    # a -8 log-mel leaves the first conv at the centred BatchNorm mean, up to the drawn N(0, 0.2) offset
+    assert float((pre[0] - wt["b0r0_mean"]).abs().max()) < 1.0
+
+
 def test_weight_validation():
     w = weights.silero_synthetic(1)
     assert weights.silero_check(w)

@@ -754,6 +754,10 @@ extern "C" int vadx_sepconv_block(const vadx_sepconv_cfg *cfg, const float *dw_w
     VADX_REQUIRE(!c.cres || (res_w && res_b && xres), "vadx_sepconv_block: residual branch needs res_w/res_b/xres");
     VADX_REQUIRE(batch > 0 && t_in > 0 && t_out > 0 && t_out == (t_in + 2 * c.pad - c.dil * (c.k - 1) - 1) / c.stride + 1,
                  "vadx_sepconv_block: t_out=%d inconsistent with t_in=%d", t_out, t_in);
+    // the residual tile is read as xres[b][ch][t0 + m] with row length t_out: the block input must have this sub-block's output frames
+    VADX_REQUIRE(!c.cres || (c.stride == 1 && t_in == t_out),
+                 "vadx_sepconv_block: a residual branch needs stride 1 and t_in == t_out (xres is [B][residual_cin][t_out]); got stride=%d "
+                 "t_in=%d t_out=%d", c.stride, t_in, t_out);
     const int tiles = (t_out + TILE - 1) / TILE;
     VADX_REQUIRE((long long)batch * tiles < (1LL << 31), "vadx_sepconv_block: too many tiles");
 #define SEPCONV_LAUNCH(...)                                                                                                     \

@@ -28,10 +28,34 @@ def _pad16(a, axes):
     return np.ascontiguousarray(np.pad(a, pads), dtype=np.float32)
 
 
+MAX_CHANNELS, MAX_TILE_FIELD = 128, 100      # csrc/marblenet.hip: MAXC, IN_LD_MAX
+
+
+def check_blocks(blocks):
+    """The layouts vadx_sepconv_block takes (include/vadx.h, next to vadx_sepconv_cfg), checked before anything is uploaded or launched:
+    at most 128 channels, a 32-frame tile's receptive field of at most 100 frames, plain blocks 1x1 at stride 1, and the residual
+    contract -- the kernel reads the block input with the output's frame index, so no sub-block of a residual block may change the frame
+    count (a stride, or an even kernel, which 'same' padding turns into T - 1)."""
+    for bi, (filt, rep, k, stride, dil, residual, sep) in enumerate(blocks):
+        what = f"MarbleNet block {bi} {(filt, rep, k, stride, dil, residual, sep)}"
+        if not (1 <= filt <= MAX_CHANNELS and rep >= 1 and k >= 1 and stride >= 1 and dil >= 1):
+            raise ValueError(f"{what}: filters must be in [1, {MAX_CHANNELS}], repeat / kernel / stride / dilation at least 1")
+        if not sep and (k != 1 or stride != 1):
+            raise ValueError(f"{what}: a plain (non-separable) block must be a 1x1 conv at stride 1")
+        if 31 * stride + (k - 1) * dil + 1 > MAX_TILE_FIELD:
+            raise ValueError(f"{what}: the receptive field of a 32-frame tile, 31 * stride + (kernel - 1) * dilation + 1 = "
+                             f"{31 * stride + (k - 1) * dil + 1}, exceeds {MAX_TILE_FIELD} frames")
+        if residual and (stride != 1 or (dil * (k - 1)) % 2):
+            raise ValueError(f"{what}: a residual block must keep the frame count (stride 1 and an odd kernel in every sub-block): "
+                             "its input is added frame by frame to its output")
+
+
 class MarbleNetEngine:
     def __init__(self, weights=None, device="cuda:0", blocks=None, bn_eps=None, in_sample_rate=16000):
         """in_sample_rate: the export's IN_SAMPLE_RATE (Export_NVIDIA_MarbleNet_VAD.py:237-254): audio arrives at that rate and
         the graph resamples every window to 16 kHz itself."""
+        if blocks is not None:
+            check_blocks(blocks)
         torch = _lib.require_gpu()
         self.in_sample_rate = int(in_sample_rate)
         self.torch = torch
@@ -109,8 +133,15 @@ class MarbleNetEngine:
             audio_i16 = t.from_numpy(np.ascontiguousarray(audio_i16, dtype=np.int16))
         a = audio_i16.to(self.device)
         L = int(a.shape[-1] // windows_per_clip if window_len is None else window_len)
-        fe = self.frontend(L)
-        x = fe.logmel(a, windows_per_clip, L)               # [N, T, 80] time-major
+        return self.run_features(self.frontend(L).logmel(a, windows_per_clip, L))
+
+    def run_features(self, x):
+        """log-mel float32 [N, T, 80], time-major and contiguous, on the device (what `frontend(L).logmel` returns)
+        -> (score_silence, score_active f32 [N, T'], signal_len = T' - 1): everything of `run` behind the front-end."""
+        t = self.torch
+        if not (t.is_tensor(x) and x.dtype == t.float32 and x.dim() == 3 and x.shape[2] == 80 and x.is_contiguous()
+                and x.shape[0] > 0 and x.shape[1] > 0):
+            raise ValueError("run_features takes a contiguous float32 [N, T, 80] tensor")
         N, T = x.shape[0], x.shape[1]
         xs = (T * 80, 1, 80)
         cur, cur_T = x, T

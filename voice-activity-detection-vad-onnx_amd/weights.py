@@ -201,8 +201,9 @@ MARBLENET_BLOCKS = (  # (filters, repeat, kernel, stride, dilation, residual, se
 MARBLENET_BN_EPS = 1e-3
 
 
-def marblenet_synthetic(seed=1234):
-    """Unfolded (conv + BatchNorm statistics) weights of the published MarbleNet 3x2x64 layout."""
+def marblenet_synthetic(seed=1234, blocks=MARBLENET_BLOCKS):
+    """Unfolded (conv + BatchNorm statistics) weights of a Jasper stack `blocks` on 80 log-mel channels (default: the published MarbleNet
+    3x2x64 layout).  Every tensor is drawn from a stream keyed by its name, so the default layout's tensors do not depend on this parameter."""
     w = {}
     cin = 80
 
@@ -212,7 +213,7 @@ def marblenet_synthetic(seed=1234):
         w[prefix + "_mean"] = _normal(seed, prefix + "m", (c,), 0.2)
         w[prefix + "_var"] = (0.5 + _rng(seed, prefix + "v").uniform(0, 1, c)).astype(np.float32)
 
-    for bi, (filt, rep, k, _s, _d, residual, sep) in enumerate(MARBLENET_BLOCKS):
+    for bi, (filt, rep, k, _s, _d, residual, sep) in enumerate(blocks):
         block_cin = cin
         for r in range(rep):
             p = f"b{bi}r{r}"
@@ -224,9 +225,11 @@ def marblenet_synthetic(seed=1234):
         if residual:
             w[f"b{bi}res_pw"] = _normal(seed, f"b{bi}res_pw", (filt, block_cin), 0.7 / np.sqrt(block_cin))
             bn(f"b{bi}res", filt)
-    # log-mel of 1/32768-scaled audio sits around -12..-3: centre the first depthwise/pointwise pair
-    w["b0r0_mean"] = (w["b0r0_mean"] + (-8.0 * (w["b0r0_pw"] * w["b0r0_dw"].sum(axis=1)[None, :]).sum(axis=1))).astype(np.float32)
-    w["dec_w"] = _normal(seed, f"dec_w_mb{_MARBLENET_DEC_TAG.get(seed, 0)}", (2, 128), 1.0 / np.sqrt(128))
+    # log-mel of 1/32768-scaled audio sits around -12..-3: centre the first depthwise/pointwise pair (a plain first block has no
+    # depthwise taps: its gain per input channel is the pointwise weight alone)
+    gain = w["b0r0_dw"].sum(axis=1) if "b0r0_dw" in w else np.ones(80, dtype=np.float32)
+    w["b0r0_mean"] = (w["b0r0_mean"] + (-8.0 * (w["b0r0_pw"] * gain[None, :]).sum(axis=1))).astype(np.float32)
+    w["dec_w"] = _normal(seed, f"dec_w_mb{_MARBLENET_DEC_TAG.get(seed, 0)}", (2, cin), 1.0 / np.sqrt(cin))
     w["dec_b"] = _normal(seed, "dec_b_mb", (2,), 0.05)
     s, t = _MARBLENET_DEC_CALIB.get(seed, (1.0, 0.0))
     w["dec_w"][1] = w["dec_w"][0] + (w["dec_w"][1] - w["dec_w"][0]) * np.float32(s)
