@@ -270,19 +270,29 @@ typedef struct vadx_frontend_cfg {
     int   window_len;  /* samples per window (at 16 kHz, i.e. after the in-graph resample of prep 6 / 7) */
     int   in_window_len; /* prep 6 / 7: samples per window in the audio buffer (input rate); 0 otherwise */
     float rs_scale;    /* prep 6 / 7: source samples per output sample, float32(1 / scale_factor) as torch computes it */
-    int   fold;        /* 0: dense DFT product.  1 / 2: folded product of vadx_frontend_logmel (mirror-paired taps about the window
-                          centre + f16 residual; same table bits, half the f32 MFMAs) -- the value vadx_frontend_fold_kind returned
-                          for this table; set it before vadx_frontend_packed_floats / _pack_host.  3: opt-in, periodic windows centred on
-                          n_fft/2 only (FSMN): time x frequency fold, a quarter of the dense MACs, noisier on bands far below the
-                          frame's peak (csrc/frontend.hip "kind 3"); _pack_host refuses it for a table that does not admit it.
-                          4: dense product of the reference table itself on bf16 x 3 exactly split operands (csrc/split3.h: six bf16
-                          MFMAs per 32 taps, float32-class accuracy, no symmetry assumption about the table); hop 160, preps 0 - 2,
-                          taps <= 512 -- the Python front-end's default where it applies.
-                          Ignored by _logmel_ex / _stft_ft callers' kernels (they take the dense tables, which every blob carries) */
+    int   fold;        /* the DFT product of vadx_frontend_logmel / _logmel_means, one of VADX_FE_KIND_* below; set it before
+                          vadx_frontend_packed_floats / _pack_host (the blob's layout depends on it).  _logmel_ex and _stft_ft ignore
+                          it: they run the dense kernels on the dense tables, which every blob carries */
 } vadx_frontend_cfg;
 
-/* Which fold (0 = none) the reference's windowed DFT table admits for this geometry: the table must equal, about the window
- * centre, an even real / odd imaginary pair to within what the f16 residual carries (1.5e-4 of the table scale). */
+/* vadx_frontend_cfg.fold.  A geometry a kind does not take is refused like any other (packed_floats 0, VADX_EINVAL); a TABLE a fold
+ * does not admit is refused by _pack_host. */
+#define VADX_FE_KIND_DENSE    0   /* float32 product: any geometry the front-end takes */
+#define VADX_FE_KIND_FOLD_SYM 1   /* mirror fold: taps paired about the window centre + an f16 residual, same table bits, half the f32 */
+#define VADX_FE_KIND_FOLD_PER 2   /* MFMAs; centre of a symmetric (1) / periodic (2) window.  Preps 0 - 2, 6, 7; <= 257 bins; hop >= 32.
+                                     Use the one vadx_frontend_fold_kind answers for the table */
+#define VADX_FE_KIND_FOLD_TF  3   /* opt-in: periodic windows centred on n_fft/2 only (FSMN), time x frequency fold, a quarter of the dense
+                                     MACs, noisier on bands far below the frame's peak (csrc/frontend.hip "kind 3") */
+#define VADX_FE_KIND_SPLIT_B3 4   /* dense product of the reference table itself on bf16 x 3 exactly split operands (csrc/split3.h: six
+                                     bf16 MFMAs per 32 taps, float32-class accuracy, no symmetry assumption); hop 160, preps 0 - 2,
+                                     taps <= 512, <= 272 bins */
+#define VADX_FE_KIND_SPLIT_H2 5   /* the same on fp16 x 2 split operands (csrc/split2.h; the samples are pre-scaled exactly into the
+                                     fp16 range; _pack_host refuses a table entry outside it) -- the Python front-end's default where
+                                     it applies */
+
+/* Which mirror fold the reference's windowed DFT table admits for this geometry -- VADX_FE_KIND_FOLD_SYM, _FOLD_PER, or 0 for neither:
+ * the table must equal, about the window centre, an even real / odd imaginary pair to within what the f16 residual carries (1.5e-4 of
+ * the table scale). */
 int vadx_frontend_fold_kind(const vadx_frontend_cfg *cfg, const float *cos_tab, const float *sin_tab, int n_fft);
 
 

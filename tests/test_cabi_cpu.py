@@ -622,3 +622,56 @@ def test_kind3_fold_is_refused_where_the_table_does_not_admit_it(lib):
     fb = np.zeros((80, 257), np.float32)
     assert lib.vadx_frontend_pack_host(ctypes.byref(cfg), c.ctypes.data, s.ctypes.data, 512, fb.ctypes.data, blob.ctypes.data, mel_kb.ctypes.data) != 0
     assert b"kind-3" in lib.vadx_last_error()
+
+
+def _other_geometry(n_fft, win, hop):
+    return dict(n_fft=n_fft, win=win, hop=hop, window="hann_sym", variant="v2", center=True, prep=1, k=(-0.97 / 32768.0, 1.0 / 32768.0),
+                mel=("torchaudio", 0, 8000, "slaney", "slaney"), log_mode=1, log_floor=1e-7)
+
+
+_E = ValueError
+# The kind frontend.Frontend chooses, transcribed by hand from the rules Frontend.__init__ held before select_kind existed (fold=False: dense;
+# fold=True: vadx_frontend_fold_kind's answer, ValueError if 0; fold=k: kind k or the packer's ValueError; fold=None: env "0" dense, env
+# "3" / "4" / "5" (unset = "5") that kind if the packer takes it else fold_kind's answer, any other env fold_kind's answer) and from what
+# the library answers for each table: fold_kind (A) and the kinds the packer takes (P).
+# geometry: (preset, window_len, in_sample_rate, fold=None under env [unset, "0", "1", "3", "4", "5"], fold = [False, True, 1, 2, 3, 4, 5])
+_LADDER = {
+    "fsmn": ("fsmn", 16000, 16000, [5, 0, 2, 3, 4, 5], [0, 2, _E, 2, 3, 4, 5]),                          # A = 2, P = {0, 2, 3, 4, 5}
+    "marblenet": ("marblenet", 16000, 16000, [5, 0, 1, 1, 4, 5], [0, 1, 1, _E, _E, 4, 5]),             # A = 1, P = {0, 1, 4, 5}
+    "firered": ("firered", 16000, 16000, [5, 0, 1, 1, 4, 5], [0, 1, 1, _E, _E, 4, 5]),                 # A = 1, P = {0, 1, 4, 5}
+    "marblenet 48 kHz": ("marblenet", 48000, 48000, [1, 0, 1, 1, 1, 1], [0, 1, 1, _E, _E, _E, _E]),    # A = 1, P = {0, 1}: prep 6 is not staged by the split kinds
+    "1024 / 640 / 160": (_other_geometry(1024, 640, 160), 20000, 16000, [0, 0, 0, 0, 0, 0], [0, _E, _E, _E, _E, _E, _E]),      # A = 0, P = {0}
+    # (the two other geometries whose kind tests/test_gpu_frontend.py::test_folded_product_on_other_geometries asserts)
+    "512 / 320 / 160": (_other_geometry(512, 320, 160), 20000, 16000, [5, 0, 1, 1, 4, 5], [0, 1, 1, _E, _E, 4, 5]),          # A = 1, P = {0, 1, 4, 5}
+    "512 / 512 / 128": (_other_geometry(512, 512, 128), 20000, 16000, [1, 0, 1, 1, 1, 1], [0, 1, 1, _E, _E, _E, _E]),        # A = 1, P = {0, 1}: hop 128
+}
+
+
+@pytest.mark.parametrize("geometry", list(_LADDER))
+def test_frontend_kind_ladder(lib, geometry):
+    """frontend.select_kind -- the choice of the DFT product, which needs only the host library -- answers what Frontend answered before
+    the choice moved there, for every `fold` argument under every VADX_FRONTEND_FOLD value; the blob it returns is the chosen kind's, packed
+    once, and cfg.fold is left at the kind."""
+    from vadx import frontend
+    preset, L, rate, by_env, by_fold = _LADDER[geometry]
+    p, cfg, c, s, fb = frontend.host_tables(preset, L, in_sample_rate=rate)
+    envs = [None, "0", "1", "3", "4", "5"]
+    for fold, wants in [(None, by_env)] + [(f, [w] * len(envs)) for f, w in zip([False, True, 1, 2, 3, 4, 5], by_fold)]:
+        for env, want in zip(envs, wants):
+            if want is _E:
+                with pytest.raises(ValueError):
+                    frontend.select_kind(cfg, c, s, p["n_fft"], fb, fold, env)
+                continue
+            kind, packed, mel_kb = frontend.select_kind(cfg, c, s, p["n_fft"], fb, fold, env)
+            assert kind == want and cfg.fold == want, (geometry, fold, env, kind, want)
+            assert packed.dtype == np.float32 and packed.size == lib.vadx_frontend_packed_floats(ctypes.byref(cfg)) and mel_kb.size == 10
+
+
+def test_frontend_kind_ladder_keeps_raw_stft_users_dense(lib):
+    """A preset without a mel stage (DFSMN's raw STFT: the "zeros" mel) runs the dense kernels only: dense whatever the environment says,
+    although its geometry (hop 160, prep 2) has split and folded products."""
+    from vadx import frontend
+    p, cfg, c, s, fb = frontend.host_tables(dict(n_fft=319, win=319, hop=160, window="hamming", variant="v1b", center=True, prep=2,
+                                                 k=(0.0, 1.0 / 32768.0), mel=("zeros",), log_mode=0, log_floor=1e-6), 16000)
+    assert [frontend.select_kind(cfg, c, s, 319, fb, None, env)[0] for env in (None, "0", "1", "3", "4", "5")] == [0] * 6
+    assert frontend.select_kind(cfg, c, s, 319, fb, 5, None)[0] == 5

@@ -1,22 +1,25 @@
-// frontend.hip -- fused signal front-end for gfx950 (reference: the five STFT_Process.py copies +
-// the wrapper code around them): int16 PCM -> prep (DC / pre-emphasis / scaling) -> framed
-// windowed DFT against the REFERENCE'S OWN float32 table -> |.|^2 -> mel -> log, one kernel.
-//
-// Tile = one analysis window of one clip x 32 (or 16) consecutive frames; 512 threads.
-//   * The PCM span of the tile is read from HBM once (coalesced int16), prepped in registers and
-//     laid out in LDS as the hop-polyphase matrix  X2[r][g] = s'[g*hop + r]  (r < hop): frame f,
-//     tap k = a*hop + r is then X2[r][f + a], i.e. the framed DFT becomes ceil(taps/hop) GEMM
-//     passes that differ only by a COLUMN offset a -- overlapping frames are served from LDS and
-//     every sample is stored exactly once.
-//   * DFT = f32 MFMA GEMM [frames x taps] x [taps x 2F]; table rows stream from L2 into operand
-//     registers (each wave owns whole bin tiles, re+im accumulate side by side so |.|^2 is lane-local).
-//   * power spectrum goes to LDS k-major [bin][frame]; mel = second MFMA GEMM that only visits the
-//     16-bin blocks each 16-mel tile actually touches (triangular filters are banded); log epilogue,
-//     time-major output [window][frame][mel] (mel contiguous: LFR rows are contiguous slices).
-// Three kernels share the staging and the mel + log phase: the dense product above (frontend_logmel_kernel: DFSMN's feature streams,
-// the raw STFT, any geometry without a fold plan), and two FOLDED products of the log-mel path on 64-frame tiles
-// (frontend_fold_kernel: mirror-paired taps + f16 residual, kinds 1 / 2, the default of the FSMN / MarbleNet / FireRed front-ends;
-// frontend_fold3_kernel: time x frequency fold, opt-in) -- see "Folded DFT" below.
+// frontend.hip -- fused signal front-end for gfx950 (reference: the five STFT_Process.py copies + the wrapper code around them):
+// int16 PCM -> prep (DC / pre-emphasis / scaling) -> framed windowed DFT against the REFERENCE'S OWN float32 table -> |.|^2 -> mel -> log,
+// one kernel.  The DENSE product: tile = one analysis window of one clip x 32 (or 16) consecutive frames; 512 threads.
+//   * The PCM span of the tile is read from HBM once (coalesced int16), prepped in registers and laid out in LDS as the hop-polyphase
+//     matrix  X2[r][g] = s'[g*hop + r]  (r < hop): frame f, tap k = a*hop + r is then X2[r][f + a], i.e. the framed DFT becomes
+//     ceil(taps/hop) GEMM passes that differ only by a COLUMN offset a -- overlapping frames are served from LDS and every sample is
+//     stored exactly once.
+//   * DFT = f32 MFMA GEMM [frames x taps] x [taps x 2F]; table rows stream from L2 into operand registers (each wave owns whole bin
+//     tiles, re+im accumulate side by side so |.|^2 is lane-local).
+//   * power spectrum goes to LDS k-major [bin][frame]; mel = second MFMA GEMM that only visits the 16-bin blocks each 16-mel tile actually
+//     touches (triangular filters are banded); log epilogue, time-major output [window][frame][mel] (mel contiguous: LFR rows are slices).
+// cfg.fold names the product of the log-mel path (enum Kind = VADX_FE_KIND_* of include/vadx.h; frontend.py's select_kind holds the order
+// of preference).  Five kernels share the staging conventions and the mel + log phase (mel_phase):
+//   frontend_logmel_kernel  K_DENSE, as above: DFSMN's feature streams (vadx_frontend_logmel_ex), any geometry no other kind takes, and
+//                           what the table-level tests compare the other kinds against
+//   stft_complex_kernel     the same product without |.|^2 / mel / log: DFSMN's raw STFT (vadx_frontend_stft_ft)
+//   frontend_split_kernel   K_SPLIT_H2 (fp16 x 2 split operands: the default of the FSMN / MarbleNet / FireRed front-ends) and K_SPLIT_B3
+//                           (bf16 x 3): the dense product on split operands, hop 160 -- "Dense DFT product on ... split operands" below
+//   frontend_fold_kernel    K_FOLD_SYM / K_FOLD_PER: mirror-paired taps + f16 residual -- what vadx_frontend_fold_kind answers, the
+//                           default where the split kernel does not apply (resampling preps, other hops); "Folded DFT" below
+//   frontend_fold3_kernel   K_FOLD_TF: time x frequency fold, opt-in; "K_FOLD_TF" below
+// The last three run on 64-frame tiles and differ only in their tile body; the first two read the dense tables, which every blob carries.
 #include "common.h"
 #include "layers_split.h"
 #include "pack.h"
@@ -25,9 +28,8 @@
 #include <string.h>
 
 #include <algorithm>
-#include <vector>
-
 #include <type_traits>
+#include <vector>
 
 namespace vadx {
 namespace frontend {
@@ -43,6 +45,14 @@ constexpr int XF_LD = 68;         // folded kernel: X2 and power row stride (64 
 constexpr int TF_FOLD = 64;       // frames per full tile of the folded kernel
 constexpr double FOLD_MAX_RATIO = 1.5e-4;   // residual / table scale the f16 product may carry (x 2^-11 each operand: ~1.5e-7)
 constexpr float RES_SCALE = 8192.f;   // residual table entries are stored as f16(value * 2^13)
+constexpr double F16_HEADROOM = 30000.0;    // ... and |value * 2^13| stays below this (f16 max 65504)
+
+// The DFT product kinds = the values of cfg.fold, described in include/vadx.h ("kind 1 ... 5" in the comments below are these)
+enum Kind : int { K_DENSE = VADX_FE_KIND_DENSE, K_FOLD_SYM = VADX_FE_KIND_FOLD_SYM, K_FOLD_PER = VADX_FE_KIND_FOLD_PER,
+                  K_FOLD_TF = VADX_FE_KIND_FOLD_TF, K_SPLIT_B3 = VADX_FE_KIND_SPLIT_B3, K_SPLIT_H2 = VADX_FE_KIND_SPLIT_H2 };
+static bool is_split(int k) { return k == K_SPLIT_B3 || k == K_SPLIT_H2; }
+static bool is_mirror_fold(int k) { return k == K_FOLD_SYM || k == K_FOLD_PER; }
+static bool on_tiles64(int k) { return is_split(k) || is_mirror_fold(k) || k == K_FOLD_TF; }      // every kind but K_DENSE
 
 struct Dev {
     // geometry
@@ -59,24 +69,23 @@ struct Dev {
     int off_dft, off_nyq, off_mel;    // float offsets in the packed blob
     int tiles32, tiles16;   // per window: number of 32-frame tiles, then 16-frame tiles
     int out_stride, out_off; // floats per output frame row / first column (lets several streams share one row)
-    // folded DFT (cfg.fold != 0): pair regions of the symmetric part, the f16 residual, the 64-frame tiling
+    // fold = cfg.fold (a Kind).  The three folds: pair regions of the symmetric part, the f16 residual; on_tiles64 kinds: the 64-frame tiling
     int fold, f_regions, f_blocks[MAX_REGIONS], f_offA[MAX_REGIONS], f_offB[MAX_REGIONS], f_strB[MAX_REGIONS];
     int f_Pb, f_Kb32;       // 16-pair blocks of the symmetric part / 32-tap blocks of the residual
     int off_fold, off_res, off_plan;  // float offsets of the folded tables in the blob; off_plan: int32 [region][blocks, offA, offB, strB], then [mel tile][lo, hi]
                                       // (the kernel reads the regions from there: indexing the by-value Dev arrays dynamically costs scratch)
     float f_xscale, f_rinv; // power-of-two scale of the f16 samples; 1 / (f_xscale * RES_SCALE)
     int tiles64, tail_mt;   // 64-frame tiles of a window, then ONE tail tile of tail_mt m-tiles (0: none; 1 - 3: 16 - 48 frames)
-    // split-product dense DFT (cfg.fold == 4): A fragments of the reference table at off_fold, [bin tile][re | im][32-tap chunk][plane][QFRAG]
+    // split-product dense DFT (K_SPLIT_B3): A fragments of the reference table at off_fold, [bin tile][re | im][32-tap chunk][plane][QFRAG]
     int s_nch, s_nbt;       // 32-tap chunks of a table row; 16-bin tiles (the last one zero-padded)
-    // cfg.fold == 5: the same product on fp16 x 2 split operands (split_scheme.h: SchemeH2, two planes per fragment).  The prepped samples
+    // K_SPLIT_H2: the same product on fp16 x 2 split operands (split_scheme.h: SchemeH2, two planes per fragment).  The prepped samples
     // are bounded by the int16 input, so they are pre-scaled by a power of two that puts their bound at 2^15 (inside the fp16 range, far
     // above its subnormals) and the power is scaled back -- both exact: no range check is needed here.
-    int s_np;               // planes per fragment: 3 (fold 4) or 2 (fold 5)
-    float s_xs, s_ps;       // sample pre-scale 2^e, power post-scale 2^(-2e) (1, 1 for fold 4)
+    int s_np;               // planes per fragment: 3 (K_SPLIT_B3) or 2 (K_SPLIT_H2)
+    float s_xs, s_ps;       // sample pre-scale 2^e, power post-scale 2^(-2e) (1, 1 for K_SPLIT_B3)
 };
 
 static int round16(int x) { return (x + 15) & ~15; }
-
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Folded DFT (cfg.fold): only |X|^2 leaves the log-mel kernel, so the spectrum may be rotated by any per-bin phase.  About the
@@ -87,7 +96,7 @@ static int round16(int x) { return (x + 15) & ~15; }
 // E / O = f32 even / odd parts of the rotated REFERENCE table (half the f32 MFMAs of the dense product), RX / IX = the table
 // minus what E / O reproduce, computed in double from the table's own bits and applied as an f16 MFMA product on f16 copies of
 // the samples (16x the f32 rate; |RX| 2^-11 |x| 2^-11 relative rounding on a term that is itself 6e-5 of the sum).
-// kind 1: c = tap0 + (taps-1)/2 (symmetric windows), kind 2: c = tap0 + taps/2 (periodic windows: tap 0 has no partner and is
+// K_FOLD_SYM (1): c = tap0 + (taps-1)/2 (symmetric windows), K_FOLD_PER (2): c = tap0 + taps/2 (periodic windows: tap 0 has no partner and is
 // paired with a row of zeros, tap taps/2 is its own partner).
 // ---------------------------------------------------------------------------------------------------------------------------
 struct FoldPair { int k, kp, kind; };          // kind 0: (k, kp); 1: k == kp; 2: k with the zero row; -1: padding (zero weights)
@@ -98,11 +107,11 @@ struct FoldPlan {
 
 static int fold_plan(const vadx_frontend_cfg *c, int kind, FoldPlan *pl) {
     const int taps = c->taps, hop = c->hop;
-    pl->T = kind == 1 ? taps - 1 : taps;
+    pl->T = kind == K_FOLD_SYM ? taps - 1 : taps;
     pl->regions = 0;
     pl->pairs.clear();
     std::vector<FoldPair> seq;
-    int k = kind == 1 ? 0 : 1;
+    int k = kind == K_FOLD_SYM ? 0 : 1;
     for (; k < pl->T - k; ++k) seq.push_back(FoldPair{k, pl->T - k, 0});
     if (k == pl->T - k && k < taps) seq.push_back(FoldPair{k, k, 1});
     auto close_region = [&](int first, int last, bool zero_partner) -> int {      // seq[first..last]
@@ -126,7 +135,7 @@ static int fold_plan(const vadx_frontend_cfg *c, int kind, FoldPlan *pl) {
             if (e > first && close_region(first, e - 1, false)) return -1;
             first = e;
         }
-    if (kind == 2) {                           // tap 0 alone
+    if (kind == K_FOLD_PER) {                  // tap 0 alone
         seq.push_back(FoldPair{0, 0, 2});
         if (close_region((int)seq.size() - 1, (int)seq.size() - 1, true)) return -1;
     }
@@ -184,7 +193,7 @@ static void fold_tables(const vadx_frontend_cfg *c, const FoldPlan &pl, const fl
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// kind 3 = kind 2 composed with the FREQUENCY fold (periodic windows centred on an integer c, n_fft % 64 == 0).  With m = n - c the
+// K_FOLD_TF (kind 3) = kind 2 composed with the FREQUENCY fold (periodic windows centred on an integer c, n_fft % 64 == 0).  With m = n - c the
 // rotated rows of bins b and b' = n_fft/2 - b satisfy  R'[b'][m] = (-1)^m R'[b][m],  I'[b'][m] = -(-1)^m I'[b][m]  (cos / sin of
 // pi m - w_b m), and the mirror pairs (m, -m) of kind 2 keep the parity of m.  So per bin b < n_fft/4 the four sums
 //     Ce = sum_{m even} E u,  Co = sum_{m odd} E u,  Se = sum_{m even} O v,  So = sum_{m odd} O v
@@ -305,6 +314,13 @@ static size_t fold_pw_off_bytes(const Dev *d) {
 }
 static size_t fold_lds_bytes(const Dev *d) { return fold_pw_off_bytes(d) + 8 * 2 * 64 * 4; }
 
+// 64-frame tiling of a window: full tiles, then one tail tile of 1 - 3 m-tiles (a tail of four m-tiles is a full tile)
+static void tile64(int frames, Dev *d) {
+    d->tiles64 = frames / TF_FOLD;
+    d->tail_mt = (frames - d->tiles64 * TF_FOLD + 15) / 16;
+    if (d->tail_mt == 4) { d->tiles64 += 1; d->tail_mt = 0; }
+}
+
 static int derive(const vadx_frontend_cfg *c, Dev *d) {
     memset(d, 0, sizeof(*d));
     d->prep = c->prep; d->center_pad = c->center_pad; d->tap0 = c->tap0; d->taps = c->taps; d->hop = c->hop;
@@ -339,14 +355,17 @@ static int derive(const vadx_frontend_cfg *c, Dev *d) {
     d->tiles16 = (rem + 15) / 16;
     if (rem > 16) { d->tiles32 += 1; d->tiles16 = 0; }
     d->out_stride = c->n_mels; d->out_off = 0;
-    if (c->fold == 4 || c->fold == 5) {
-        // dense product on split operands (frontend_split_kernel; 4 = bf16 x 3, 5 = fp16 x 2): the flat sample planes need hop = 160 (their
-        // skew), the staging knows the int16 preps 0 - 2
+    // (The sample bound below is worked out TWICE on purpose: the split kinds take it in double over preps 0 - 2, the folds in float with
+    // the resampling preps 6 / 7 included, and each feeds a power-of-two scale of its own (2^15 / bound against 2^14 / bound) -- a merged
+    // form would have to reproduce both roundings to leave every blob and every scale as it is.)
+    if (is_split(c->fold)) {
+        // dense product on split operands (frontend_split_kernel): the flat sample planes need hop = 160 (their skew), the staging knows
+        // the int16 preps 0 - 2
         if (c->hop != 160 || c->prep > 2 || c->taps > 512 || c->n_bins > 17 * 16) return -1;
         d->fold = c->fold;
-        d->s_np = c->fold == 4 ? 3 : 2;
+        d->s_np = c->fold == K_SPLIT_B3 ? 3 : 2;
         d->s_xs = d->s_ps = 1.f;
-        if (c->fold == 5) {
+        if (c->fold == K_SPLIT_H2) {
             // |prepped sample| <= bound: prep 0 (x - mean) - 0.97 (x[-1] - mean) with |x - mean| < 65536; prep 1 k0 x[-1] + k1 x; prep 2 k1 x - mean
             const double bound = c->prep == 0 ? 65536.0 * 1.97 : (c->prep == 1 ? 32768.0 * (fabs((double)c->k0) + fabs((double)c->k1)) : 65536.0 * fabs((double)c->k1));
             if (!(bound > 0.0) || !(bound < 1e30)) return -1;
@@ -358,20 +377,17 @@ static int derive(const vadx_frontend_cfg *c, Dev *d) {
         d->s_nbt = (c->n_bins + 15) / 16;
         d->off_fold = (d->off_mel + d->n_mels * d->Fp + 255) / 256 * 256;      // fragments on 1 KiB boundaries: a wave's 1 KiB load touches 16 lines, not 17
         d->off_plan = d->off_fold + d->s_nbt * 2 * d->s_nch * d->s_np * vadx::QFRAG;
-        d->tiles64 = c->frames / TF_FOLD;
-        const int rem64 = c->frames - d->tiles64 * TF_FOLD;
-        d->tail_mt = (rem64 + 15) / 16;
-        if (d->tail_mt == 4) { d->tiles64 += 1; d->tail_mt = 0; }
+        tile64(c->frames, d);
         return 0;
     }
-    if (c->fold) {
-        if (c->fold < 1 || c->fold > 3) return -1;
+    if (c->fold != K_DENSE) {
+        if (!on_tiles64(c->fold)) return -1;                                // not a kind
         if (!(c->prep <= 2 || c->prep >= 6) || d->nbt > 16) return -1;      // int16-derived samples; two power tiles per wave
         if (TF_FOLD + d->passes - 1 >= XF_LD || c->hop < 32) return -1;
         d->fold = c->fold;
         d->f_Kb32 = (c->taps + 31) / 32;
         d->off_fold = d->off_mel + d->n_mels * d->Fp;
-        if (c->fold == 3) {
+        if (c->fold == K_FOLD_TF) {
             Fold3Plan p3;
             if (fold3_plan(c, 2 * (c->n_bins - 1), &p3)) return -1;
             d->f_Pb = p3.Pb;
@@ -396,21 +412,40 @@ static int derive(const vadx_frontend_cfg *c, Dev *d) {
         if (!(M > 0.f)) return -1;
         d->f_xscale = exp2f(floorf(log2f(16384.f / M)));
         d->f_rinv = 1.0f / (d->f_xscale * RES_SCALE);
-        d->tiles64 = c->frames / TF_FOLD;
-        const int rem64 = c->frames - d->tiles64 * TF_FOLD;
-        d->tail_mt = (rem64 + 15) / 16;
-        if (d->tail_mt == 4) { d->tiles64 += 1; d->tail_mt = 0; }
+        tile64(c->frames, d);
         if (fold_lds_bytes(d) > 80 * 1024) return -1;
     }
     return 0;
 }
 
 static size_t packed_total(const Dev &d) {
-    if (d.fold == 4 || d.fold == 5) return (size_t)d.off_plan + 2 * MAX_MEL_TILES + 4;       // + the mel bands
-    if (d.fold == 3) return (size_t)d.off_plan + (size_t)d.f_Pb * 32 + 2 * MAX_MEL_TILES;      // [block][quarter][offA x 4 | offB x 4], then the mel bands
-    if (d.fold) return (size_t)d.off_plan + 4 * MAX_REGIONS + 2 * MAX_MEL_TILES + 4;      // + last-bin mode (one int, padded to four)
+    if (is_split(d.fold)) return (size_t)d.off_plan + 2 * MAX_MEL_TILES + 4;       // + the mel bands
+    if (d.fold == K_FOLD_TF) return (size_t)d.off_plan + (size_t)d.f_Pb * 32 + 2 * MAX_MEL_TILES;      // [block][quarter][offA x 4 | offB x 4], then the mel bands
+    if (is_mirror_fold(d.fold)) return (size_t)d.off_plan + 4 * MAX_REGIONS + 2 * MAX_MEL_TILES + 4;      // + last-bin mode (one int, padded to four)
     return (size_t)d.off_mel + (size_t)d.n_mels * d.Fp;
 }
+__host__ __device__ static inline int tiles64_per_window(const Dev &d) { return d.tiles64 + (d.tail_mt ? 1 : 0); }
+
+// What the f16 residual product may carry: FOLD_MAX_RATIO of the table scale, inside the f16 range once scaled
+static bool residual_fits(double res_max, double tab_max) { return res_max <= FOLD_MAX_RATIO * tab_max && res_max * RES_SCALE < F16_HEADROOM; }
+
+// An f16 residual as MFMA B fragments [tile][part][Kb32 32-tap blocks][64 lanes][8]: lane (q, i) holds taps 32 S + 8 q .. + 7 of row i of
+// the tile; value(tile, part, i, tap) in double, stored as f16(value * RES_SCALE), zero past `taps`
+template <typename F>
+static void pack_residual(_Float16 *rh, int tiles, int parts, int Kb32, int taps, F value) {
+    for (int t = 0; t < tiles; ++t)
+        for (int part = 0; part < parts; ++part)
+            for (int S = 0; S < Kb32; ++S)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int e = 0; e < 8; ++e) {
+                        const int k = 32 * S + 8 * (lane >> 4) + e;
+                        const double v = k < taps ? value(t, part, lane & 15, k) : 0.0;
+                        rh[((((size_t)t * parts + part) * Kb32 + S) * 64 + lane) * 8 + e] = (_Float16)(float)(v * RES_SCALE);
+                    }
+}
+
+// The mel bands [mel tile][lo, hi] behind a kind's plan, where its kernel reads them (mel_phase<.., BANDS>)
+static void put_bands(int32_t *dst, const Dev &d, const int32_t *mel_kb) { memcpy(dst, mel_kb, 2 * d.nmt * sizeof(int32_t)); }
 
 // log of the mel energies: v_log_f32 (1 ulp in log2) times ln 2 instead of the library logf (~25 VALU instructions per value; VALU
 // time adds to f32-MFMA time on gfx950).  |difference| <= 4e-6 over the feature range, two orders inside the feature tolerance.
@@ -592,6 +627,28 @@ __device__ __forceinline__ void mel_phase(const Dev &d, const float *__restrict_
     }
 }
 
+// What a kernel makes of blockIdx.x (`tiles` tiles per window, windows_per_clip windows per clip row): the window's index, its tile, its
+// samples and its output rows (not its mean, and not in the dense kernel: DESIGN.md "Front-end: what is written once")
+struct Block { int widx, tile; const int16_t *win; float *out_win; };
+__device__ __forceinline__ Block block_window(const Dev &d, int tiles, const int16_t *audio, long long row_stride, long long win_stride,
+                                              int windows_per_clip, float *out) {
+    Block k;
+    k.widx = blockIdx.x / tiles; k.tile = blockIdx.x - k.widx * tiles;
+    const int b = k.widx / windows_per_clip, w = k.widx - b * windows_per_clip;
+    k.win = audio + (long long)b * row_stride + (long long)w * win_stride;
+    k.out_win = out + (size_t)k.widx * d.frames * d.out_stride;
+    return k;
+}
+
+// The three 64-frame kernels: the statement after `tile` with MT = 4 m-tiles and f0 = its first frame for a full tile, MT = tail_mt for the tail
+#define FE_TILE64_LADDER(d, tile, ...)                                                                         \
+    do {                                                                                                       \
+        if ((tile) < (d).tiles64) { constexpr int MT = 4; const int f0 = (tile) * TF_FOLD; __VA_ARGS__; }      \
+        else if ((d).tail_mt == 3) { constexpr int MT = 3; const int f0 = (d).tiles64 * TF_FOLD; __VA_ARGS__; } \
+        else if ((d).tail_mt == 2) { constexpr int MT = 2; const int f0 = (d).tiles64 * TF_FOLD; __VA_ARGS__; } \
+        else { constexpr int MT = 1; const int f0 = (d).tiles64 * TF_FOLD; __VA_ARGS__; }                      \
+    } while (0)
+
 struct FtOut { float *ptr; int tile0, c_total, c_off; };      // COMPLEX: FT destination (re -> c_off, im -> c_off+1)
 
 template <int MT, bool COMPLEX = false>
@@ -688,7 +745,6 @@ __device__ __forceinline__ void tile_body(const Dev &d, const float *__restrict_
     mel_phase<MT>(d, P, PW, P_LD, f0, out_win);
 }
 
-
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef const __attribute__((address_space(1))) f16x8 *global_f16x8_ptr;
 __device__ __forceinline__ f32x4 mfma16h(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
@@ -704,7 +760,6 @@ __device__ __forceinline__ void fold_tile(const Dev &d, const float *__restrict_
     const int cols = NF + d.passes - 1, xs_pitch = d.hop + 8;
     float *X2 = lds, *PW = lds;
     _Float16 *XS = reinterpret_cast<_Float16 *>(lds + (d.hop + 16) * XF_LD);
-
     for (int e = tid; e < 16 * XF_LD; e += THREADS) X2[d.hop * XF_LD + e] = 0.f;                      // the zero rows (lone taps, padding pairs)
     for (int e = tid; e < xs_pitch; e += THREADS) XS[cols * xs_pitch + e] = (_Float16)0.f;            // column read by the residual's padded taps
     stage_tile<XF_LD, true>(d, win, nullptr, mean, f0, cols, X2, XS, xs_pitch, d.f_xscale);
@@ -895,17 +950,10 @@ __global__ __launch_bounds__(THREADS, 4) void frontend_fold_kernel(
     Dev d, const float *__restrict__ P, const int16_t *__restrict__ audio, long long row_stride,
     long long win_stride, int windows_per_clip, const float *__restrict__ means, float *__restrict__ out, int nq_off) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tiles = d.tiles64 + (d.tail_mt ? 1 : 0);
-    const int widx = blockIdx.x / tiles, tile = blockIdx.x - widx * tiles;
-    const int b = widx / windows_per_clip, w = widx - b * windows_per_clip;
-    const int16_t *win = audio + (long long)b * row_stride + (long long)w * win_stride;
-    float *out_win = out + (size_t)widx * d.frames * d.out_stride;
-    const float mean = means ? means[widx] : 0.f;
+    const Block k = block_window(d, tiles64_per_window(d), audio, row_stride, win_stride, windows_per_clip, out);
+    const float mean = means ? means[k.widx] : 0.f;
     float *NQ = lds + nq_off;
-    if (tile < d.tiles64) fold_tile<4>(d, P, win, mean, tile * TF_FOLD, out_win, lds, NQ);
-    else if (d.tail_mt == 3) fold_tile<3>(d, P, win, mean, d.tiles64 * TF_FOLD, out_win, lds, NQ);
-    else if (d.tail_mt == 2) fold_tile<2>(d, P, win, mean, d.tiles64 * TF_FOLD, out_win, lds, NQ);
-    else fold_tile<1>(d, P, win, mean, d.tiles64 * TF_FOLD, out_win, lds, NQ);
+    FE_TILE64_LADDER(d, k.tile, fold_tile<MT>(d, P, k.win, mean, f0, k.out_win, lds, NQ));
 }
 
 // One tile of MT*16 frames of the kind-3 kernel (time x frequency fold, see "kind 3" above): wave w owns bins 16 w .. 16 w + 15 AND
@@ -923,7 +971,6 @@ __device__ __forceinline__ void fold3_tile(const Dev &d, const float *__restrict
     const int nq = (d.n_bins - 1) >> 1, nt3 = nq >> 4;            // bin n_fft/4; row tiles below it (8 for 257 bins)
     const int Kp = d.f_Pb * 16, pbc = d.f_Pb >> 1;                // pair slots; blocks per parity class
     const int *__restrict__ plan = reinterpret_cast<const int *>(P + d.off_plan);
-
     for (int e = tid; e < 16 * XF_LD; e += THREADS) X2[d.hop * XF_LD + e] = 0.f;                      // the zero rows (lone taps, padding pairs)
     for (int e = tid; e < xs_pitch; e += THREADS) XS[cols * xs_pitch + e] = (_Float16)0.f;            // column read by the residual's padded taps
     stage_tile<XF_LD, true>(d, win, nullptr, mean, f0, cols, X2, XS, xs_pitch, d.f_xscale);
@@ -1068,22 +1115,14 @@ __global__ __launch_bounds__(THREADS, 4) void frontend_fold3_kernel(
     Dev d, const float *__restrict__ P, const int16_t *__restrict__ audio, long long row_stride,
     long long win_stride, int windows_per_clip, const float *__restrict__ means, float *__restrict__ out, int nq_off) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tiles = d.tiles64 + (d.tail_mt ? 1 : 0);
-    const int widx = blockIdx.x / tiles, tile = blockIdx.x - widx * tiles;
-    const int b = widx / windows_per_clip, w = widx - b * windows_per_clip;
-    const int16_t *win = audio + (long long)b * row_stride + (long long)w * win_stride;
-    float *out_win = out + (size_t)widx * d.frames * d.out_stride;
-    const float mean = means ? means[widx] : 0.f;
+    const Block k = block_window(d, tiles64_per_window(d), audio, row_stride, win_stride, windows_per_clip, out);
+    const float mean = means ? means[k.widx] : 0.f;
     float *NQ = lds + nq_off;
-    if (tile < d.tiles64) fold3_tile<4>(d, P, win, mean, tile * TF_FOLD, out_win, lds, NQ);
-    else if (d.tail_mt == 3) fold3_tile<3>(d, P, win, mean, d.tiles64 * TF_FOLD, out_win, lds, NQ);
-    else if (d.tail_mt == 2) fold3_tile<2>(d, P, win, mean, d.tiles64 * TF_FOLD, out_win, lds, NQ);
-    else fold3_tile<1>(d, P, win, mean, d.tiles64 * TF_FOLD, out_win, lds, NQ);
+    FE_TILE64_LADDER(d, k.tile, fold3_tile<MT>(d, P, k.win, mean, f0, k.out_win, lds, NQ));
 }
 
-
 // ---------------------------------------------------------------------------------------------------------------------------
-// Dense DFT product on bf16 x 3 split operands (cfg.fold == 4; csrc/split3.h, layers_split.h).  The reference's own float32 table, split
+// Dense DFT product on bf16 x 3 split operands (K_SPLIT_B3; K_SPLIT_H2 = fp16 x 2, see Dev::s_np; csrc/split3.h, layers_split.h).  The reference's own float32 table, split
 // exactly into three bf16 planes on the host, times the prepped samples, split exactly by the lanes that stage them: six
 // v_mfma_f32_16x16x32_bf16 per 32 taps, i.e. 6/16 of the dense f32 product's matrix time and 3/4 of the folded f32 product's -- with no
 // fold plan, no residual table and no symmetry assumption about the table (any window, any centre).
@@ -1229,16 +1268,9 @@ __global__ __launch_bounds__(SQ_THREADS, 2) void frontend_split_kernel(
     Dev d, const float *__restrict__ P, const int16_t *__restrict__ audio, long long row_stride,
     long long win_stride, int windows_per_clip, const float *__restrict__ means, float *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char fsmem[];
-    const int tiles = d.tiles64 + (d.tail_mt ? 1 : 0);
-    const int widx = blockIdx.x / tiles, tile = blockIdx.x - widx * tiles;
-    const int b = widx / windows_per_clip, w = widx - b * windows_per_clip;
-    const int16_t *win = audio + (long long)b * row_stride + (long long)w * win_stride;
-    float *out_win = out + (size_t)widx * d.frames * d.out_stride;
-    const float mean = means ? means[widx] : 0.f;
-    if (tile < d.tiles64) split_tile<SC, 4>(d, P, win, mean, tile * TF_FOLD, out_win, fsmem);
-    else if (d.tail_mt == 3) split_tile<SC, 3>(d, P, win, mean, d.tiles64 * TF_FOLD, out_win, fsmem);
-    else if (d.tail_mt == 2) split_tile<SC, 2>(d, P, win, mean, d.tiles64 * TF_FOLD, out_win, fsmem);
-    else split_tile<SC, 1>(d, P, win, mean, d.tiles64 * TF_FOLD, out_win, fsmem);
+    const Block k = block_window(d, tiles64_per_window(d), audio, row_stride, win_stride, windows_per_clip, out);
+    const float mean = means ? means[k.widx] : 0.f;
+    FE_TILE64_LADDER(d, k.tile, split_tile<SC, MT>(d, P, k.win, mean, f0, k.out_win, fsmem));
 }
 
 __global__ __launch_bounds__(THREADS, 4) void frontend_logmel_kernel(
@@ -1248,6 +1280,7 @@ __global__ __launch_bounds__(THREADS, 4) void frontend_logmel_kernel(
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *X2 = lds;
     float *PW = lds + d.hop * X_LD;                   // a pass never reads past row hop - 1: its rows round up to 16 <= hop (hop % 16 == 0)
+    // (block_window written out: prep 4 has no int16 source, and the compiler keeps the division by windows_per_clip under `audio ?` too)
     const int tiles = d.tiles32 + d.tiles16;
     const int widx = blockIdx.x / tiles, tile = blockIdx.x - widx * tiles;
     const int b = widx / windows_per_clip, w = widx - b * windows_per_clip;
@@ -1267,14 +1300,11 @@ __global__ __launch_bounds__(THREADS, 4) void stft_complex_kernel(
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *X2 = lds;
     float *PW = lds + d.hop * X_LD;
-    const int tiles = (d.frames + TF - 1) / TF;
-    const int widx = blockIdx.x / tiles, tile = blockIdx.x - widx * tiles;
-    const int b = widx / windows_per_clip, w = widx - b * windows_per_clip;
-    const int16_t *win = audio + (long long)b * row_stride + (long long)w * win_stride;
-    const float mean = means ? means[widx] : 0.f;
-    FtOut ft{ft_out, widx * ft_nt, ft_ctotal, ft_coff};
-    if (tile * TF + 16 < ft_nt * 16) tile_body<2, true>(d, P, win, nullptr, mean, tile * TF, nullptr, X2, PW, ft);
-    else tile_body<1, true>(d, P, win, nullptr, mean, tile * TF, nullptr, X2, PW, ft);
+    const Block k = block_window(d, (d.frames + TF - 1) / TF, audio, row_stride, win_stride, windows_per_clip, nullptr);
+    const float mean = means ? means[k.widx] : 0.f;
+    FtOut ft{ft_out, k.widx * ft_nt, ft_ctotal, ft_coff};
+    if (k.tile * TF + 16 < ft_nt * 16) tile_body<2, true>(d, P, k.win, nullptr, mean, k.tile * TF, nullptr, X2, PW, ft);
+    else tile_body<1, true>(d, P, k.win, nullptr, mean, k.tile * TF, nullptr, X2, PW, ft);
 }
 
 // window means for the DC-removing preps: exact integer sum -> float (one wave per window)
@@ -1356,25 +1386,23 @@ extern "C" int vadx_frontend_pack_host(const vadx_frontend_cfg *cfg, const float
     vadx::frag_major_inplace(packed_host + d.off_dft, d.nbt * 32, d.Kp);
     if (d.nyq) vadx::frag_major_inplace(packed_host + d.off_nyq, 16, d.Kp);
     vadx::frag_major_inplace(packed_host + d.off_mel, d.n_mels, d.Fp);
-    if (d.fold == 4 || d.fold == 5) {   // the reference table itself as split fragments (three bf16 planes, exact, or two fp16 planes): [bin tile][re | im][chunk][plane][QFRAG]
+    int32_t *pi = reinterpret_cast<int32_t *>(packed_host + d.off_plan);      // (the kinds on 64-frame tiles: the plan, then the mel bands)
+    if (is_split(d.fold)) {   // the reference table itself as split fragments (three bf16 planes, exact, or two fp16 planes): [bin tile][re | im][chunk][plane][QFRAG]
         float wmax = 0.f;
         // rows 32 bt + 16 part + i of the [s_nbt x (re 16 | im 16)] tile stack = bin 16 bt + i of the cos (part 0) / sin (part 1) table
         vadx::pack::split(d.s_np, packed_host + d.off_fold, 2 * d.s_nbt, d.s_nch, [&](int r, int t) {
             const int f = (r / 32) * 16 + r % 16;
             return (f < d.n_bins && t < d.taps) ? ((r & 16) ? sin_tab : cos_tab)[(size_t)f * n_fft + cfg->tap0 + t] : 0.f; }, wmax);
-        VADX_REQUIRE(d.fold != 5 || wmax <= vadx::H_MAX, "vadx_frontend_pack_host: a table entry (|.| up to %g) is outside the fp16 range: use fold = 4", wmax);
-        int32_t *pi = reinterpret_cast<int32_t *>(packed_host + d.off_plan);
-        for (int mt = 0; mt < d.nmt; ++mt) { pi[2 * mt] = mel_kb[2 * mt]; pi[2 * mt + 1] = mel_kb[2 * mt + 1]; }
-        return VADX_OK;
-    }
-    if (d.fold == 3) {
+        VADX_REQUIRE(d.fold != K_SPLIT_H2 || wmax <= vadx::H_MAX, "vadx_frontend_pack_host: a table entry (|.| up to %g) is outside the fp16 range: use fold = 4", wmax);
+        put_bands(pi, d, mel_kb);
+    } else if (d.fold == K_FOLD_TF) {
         Fold3Plan p3;
         VADX_REQUIRE(fold3_plan(cfg, n_fft, &p3) == 0, "vadx_frontend_pack_host: no kind-3 fold plan for this geometry");
         std::vector<float> E, O;
         std::vector<double> RES;
         double res_max = 0.0, tab_max = 0.0;
         fold3_tables(cfg, p3, cos_tab, sin_tab, n_fft, E, O, RES, &res_max, &tab_max);
-        VADX_REQUIRE(res_max <= FOLD_MAX_RATIO * tab_max && res_max * RES_SCALE < 30000.0,
+        VADX_REQUIRE(residual_fits(res_max, tab_max),
                      "vadx_frontend_pack_host: table is too far from the kind-3 model (residual %.3g of %.3g): ask vadx_frontend_fold_kind", res_max, tab_max);
         const int P = 2 * p3.Pc, nq = n_fft / 4, nt3 = nq / 16, ntl3 = nt3 + 1;
         // columns in MFMA contraction order: column 16 S + kappa of a row = slot 16 S + tau(kappa)
@@ -1388,22 +1416,12 @@ extern "C" int vadx_frontend_pack_host(const vadx_frontend_cfg *cfg, const float
         put_cols(fm + (size_t)(nt3 * 32) * P, E.data() + (size_t)nq * P);                 // bin n_fft/4: u tile row 0 = E, v tile row 1 = O
         put_cols(fm + (size_t)(nt3 * 32 + 17) * P, O.data() + (size_t)nq * P);
         vadx::frag_major_inplace(fm, ntl3 * 32, P);
-        _Float16 *rh = reinterpret_cast<_Float16 *>(packed_host + d.off_res);           // [ntl3][4 accumulators][Kb32][64 lanes][8]
-        for (int t = 0; t < ntl3; ++t)
-            for (int a = 0; a < 4; ++a)
-                for (int S = 0; S < d.f_Kb32; ++S)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int i = lane & 15, k = 32 * S + 8 * (lane >> 4) + e;
-                            double v = 0.0;
-                            if (k < d.taps) {
-                                if (t < nt3) v = RES[((size_t)(t * 16 + i) * 4 + a) * d.taps + k];
-                                else if (a == 0 && i < 2) v = RES[((size_t)nq * 4 + i) * d.taps + k];      // rows 0, 1 = (re, im) residual of bin n_fft/4
-                            }
-                            rh[((((size_t)t * 4 + a) * d.f_Kb32 + S) * 64 + lane) * 8 + e] = (_Float16)(float)(v * RES_SCALE);
-                        }
-        int32_t *pi = reinterpret_cast<int32_t *>(packed_host + d.off_plan);          // [block][quarter q][offA j0..3 | offB j0..3]: LDS word offsets in X2
-        auto off = [&](int k) { return k < 0 ? d.hop * XF_LD : (k % d.hop) * XF_LD + k / d.hop; };
+        // [ntl3][4 accumulators]; the last tile: rows 0, 1 of accumulator 0 = (re, im) residual of bin n_fft/4
+        pack_residual(reinterpret_cast<_Float16 *>(packed_host + d.off_res), ntl3, 4, d.f_Kb32, d.taps, [&](int t, int a, int i, int k) {
+            if (t < nt3) return RES[((size_t)(t * 16 + i) * 4 + a) * d.taps + k];
+            return (a == 0 && i < 2) ? RES[((size_t)nq * 4 + i) * d.taps + k] : 0.0;
+        });
+        auto off = [&](int k) { return k < 0 ? d.hop * XF_LD : (k % d.hop) * XF_LD + k / d.hop; };      // [block][quarter q][offA j0..3 | offB j0..3]: LDS word offsets in X2
         for (int S = 0; S < p3.Pb; ++S)
             for (int q = 0; q < 4; ++q)
                 for (int j = 0; j < 4; ++j) {
@@ -1411,15 +1429,15 @@ extern "C" int vadx_frontend_pack_host(const vadx_frontend_cfg *cfg, const float
                     pi[(S * 4 + q) * 8 + j] = off(p3.ka[slot]);
                     pi[(S * 4 + q) * 8 + 4 + j] = off(p3.kb[slot]);
                 }
-        for (int mt = 0; mt < d.nmt; ++mt) { pi[p3.Pb * 32 + 2 * mt] = mel_kb[2 * mt]; pi[p3.Pb * 32 + 2 * mt + 1] = mel_kb[2 * mt + 1]; }
-    } else if (d.fold) {
+        put_bands(pi + p3.Pb * 32, d, mel_kb);
+    } else if (is_mirror_fold(d.fold)) {
         FoldPlan pl;
         VADX_REQUIRE(fold_plan(cfg, cfg->fold, &pl) == 0, "vadx_frontend_pack_host: no fold plan for this geometry");
         std::vector<float> E, O;
         std::vector<double> RX, IX;
         double res_max = 0.0, tab_max = 0.0;
         fold_tables(cfg, pl, cos_tab, sin_tab, n_fft, E, O, RX, IX, &res_max, &tab_max);
-        VADX_REQUIRE(res_max <= FOLD_MAX_RATIO * tab_max && res_max * RES_SCALE < 30000.0,
+        VADX_REQUIRE(residual_fits(res_max, tab_max),
                      "vadx_frontend_pack_host: table is not symmetric enough about the window centre for cfg.fold = %d (residual %.3g of %.3g): "
                      "ask vadx_frontend_fold_kind", cfg->fold, res_max, tab_max);
         const int P = d.f_Pb * 16, ntl = d.nbt + d.nyq, last = d.n_bins - 1;
@@ -1454,44 +1472,33 @@ extern "C" int vadx_frontend_pack_host(const vadx_frontend_cfg *cfg, const float
                 }
             }
             for (int t2 = 0; t2 < d.taps && last_mode; ++t2)
-                VADX_REQUIRE(fabs(RX[(size_t)last * d.taps + t2]) * RES_SCALE < 30000.0 && fabs(IX[(size_t)last * d.taps + t2]) * RES_SCALE < 30000.0,
+                VADX_REQUIRE(fabs(RX[(size_t)last * d.taps + t2]) * RES_SCALE < F16_HEADROOM && fabs(IX[(size_t)last * d.taps + t2]) * RES_SCALE < F16_HEADROOM,
                              "vadx_frontend_pack_host: last-bin residual out of the f16 range");
             memcpy(fm + (size_t)(d.nbt * 32) * P, E.data() + (size_t)last * P, P * sizeof(float));
             memcpy(fm + (size_t)(d.nbt * 32 + 16 + 1) * P, O.data() + (size_t)last * P, P * sizeof(float));
         }
         vadx::frag_major_inplace(fm, ntl * 32, P);
-        int32_t *pi = reinterpret_cast<int32_t *>(packed_host + d.off_plan);
         for (int r = 0; r < d.f_regions; ++r) { pi[4 * r] = d.f_blocks[r]; pi[4 * r + 1] = d.f_offA[r]; pi[4 * r + 2] = d.f_offB[r]; pi[4 * r + 3] = d.f_strB[r]; }
-        for (int mt = 0; mt < d.nmt; ++mt) { pi[4 * MAX_REGIONS + 2 * mt] = mel_kb[2 * mt]; pi[4 * MAX_REGIONS + 2 * mt + 1] = mel_kb[2 * mt + 1]; }      // the mel bands, for the kernel
+        put_bands(pi + 4 * MAX_REGIONS, d, mel_kb);
         pi[4 * MAX_REGIONS + 2 * MAX_MEL_TILES] = last_mode;
-        _Float16 *rh = reinterpret_cast<_Float16 *>(packed_host + d.off_res);      // [ntl][RX | IX][Kb32][64 lanes][8]
-        for (int t = 0; t < ntl; ++t)
-            for (int part = 0; part < 2; ++part)
-                for (int S = 0; S < d.f_Kb32; ++S)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int i = lane & 15, k = 32 * S + 8 * (lane >> 4) + e;
-                            double v = 0.0;
-                            if (k < d.taps) {
-                                if (t < d.nbt) {
-                                    const int f = t * 16 + i;
-                                    if (f < d.n_bins && !(d.nyq && f == last)) v = (part ? IX : RX)[(size_t)f * d.taps + k];
-                                } else if (part == 0 && i < 2) v = (i ? IX : RX)[(size_t)last * d.taps + k];
-                            }
-                            rh[((((size_t)t * 2 + part) * d.f_Kb32 + S) * 64 + lane) * 8 + e] = (_Float16)(float)(v * RES_SCALE);
-                        }
+        // [ntl][RX | IX]; the last bin's own tile: rows 0, 1 of part 0 = its (RX, IX)
+        pack_residual(reinterpret_cast<_Float16 *>(packed_host + d.off_res), ntl, 2, d.f_Kb32, d.taps, [&](int t, int part, int i, int k) {
+            const int f = t * 16 + i;
+            if (t < d.nbt) return (f < d.n_bins && !(d.nyq && f == last)) ? (part ? IX : RX)[(size_t)f * d.taps + k] : 0.0;
+            return (part == 0 && i < 2) ? (i ? IX : RX)[(size_t)last * d.taps + k] : 0.0;
+        });
     }
     return VADX_OK;
 }
 
-// Which fold the reference table admits by default: 1 / 2 (see "Folded DFT") or 0 -- the geometry has no plan, or the table is further from
-// the symmetric model than the f16 residual may carry (FOLD_MAX_RATIO of the table scale).  The caller stores the answer in cfg.fold
-// BEFORE vadx_frontend_packed_floats / vadx_frontend_pack_host / the launches.
+// Which MIRROR fold the reference table admits: K_FOLD_SYM / K_FOLD_PER (see "Folded DFT"; the better fit of the two) or 0 -- the geometry
+// has no plan, or the table is further from the symmetric model than the f16 residual may carry (residual_fits).  The caller stores the
+// answer in cfg.fold BEFORE vadx_frontend_packed_floats / vadx_frontend_pack_host / the launches.
 extern "C" int vadx_frontend_fold_kind(const vadx_frontend_cfg *cfg, const float *cos_tab, const float *sin_tab, int n_fft) {
     if (!cfg || !cos_tab || !sin_tab) return 0;
-    int best = 0;
+    int best = K_DENSE;
     double best_res = 0.0;
-    for (int kind = 1; kind <= 2; ++kind) {
+    for (int kind : {K_FOLD_SYM, K_FOLD_PER}) {
         vadx_frontend_cfg c = *cfg;
         c.fold = kind;
         Dev d;
@@ -1502,37 +1509,54 @@ extern "C" int vadx_frontend_fold_kind(const vadx_frontend_cfg *cfg, const float
         std::vector<double> RX, IX;
         double res_max = 0.0, tab_max = 0.0;
         fold_tables(&c, pl, cos_tab, sin_tab, n_fft, E, O, RX, IX, &res_max, &tab_max);
-        if (!(res_max <= FOLD_MAX_RATIO * tab_max && res_max * RES_SCALE < 30000.0)) continue;
+        if (!residual_fits(res_max, tab_max)) continue;
         if (!best || res_max < best_res) { best = kind; best_res = res_max; }
     }
     return best;
 }
 
-extern "C" int vadx_frontend_window_means(const int16_t *audio, int64_t row_stride, int64_t win_stride, int batch, int windows_per_clip,
-                                          int window_len, float scale, float *means, void *stream) {
-    VADX_REQUIRE(audio && means && batch > 0 && windows_per_clip > 0 && window_len > 0, "vadx_frontend_window_means: bad argument");
-    const long long nwin = (long long)batch * windows_per_clip;
-    hipLaunchKernelGGL(window_mean_kernel, dim3((unsigned)((nwin + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), audio,
-                       (long long)row_stride, (long long)win_stride, windows_per_clip, (int)nwin, window_len, scale, means);
+// window means for the DC-removing preps (window_mean_kernel) into means[nwin]
+static int launch_window_means(const int16_t *audio, int64_t row_stride, int64_t win_stride, int windows_per_clip, long long nwin,
+                               int window_len, float scale, float *means, hipStream_t st) {
+    hipLaunchKernelGGL(window_mean_kernel, dim3((unsigned)((nwin + 3) / 4)), dim3(256), 0, st, audio, (long long)row_stride,
+                       (long long)win_stride, windows_per_clip, (int)nwin, window_len, scale, means);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
 
-static int logmel_impl(const vadx_frontend_cfg *cfg, const float *packed, const int32_t *mel_kb_host, const int16_t *audio, int64_t row_stride,
-                       int64_t win_stride, int batch, int windows_per_clip, float *means_ws, bool means_given, float *out, void *stream);
-
-extern "C" int vadx_frontend_logmel(const vadx_frontend_cfg *cfg, const float *packed, const int32_t *mel_kb_host,
-                                    const int16_t *audio, int64_t row_stride, int64_t win_stride, int batch,
-                                    int windows_per_clip, float *means_ws, float *out, void *stream) {
-    return logmel_impl(cfg, packed, mel_kb_host, audio, row_stride, win_stride, batch, windows_per_clip, means_ws, false, out, stream);
+extern "C" int vadx_frontend_window_means(const int16_t *audio, int64_t row_stride, int64_t win_stride, int batch, int windows_per_clip,
+                                          int window_len, float scale, float *means, void *stream) {
+    VADX_REQUIRE(audio && means && batch > 0 && windows_per_clip > 0 && window_len > 0, "vadx_frontend_window_means: bad argument");
+    return launch_window_means(audio, row_stride, win_stride, windows_per_clip, (long long)batch * windows_per_clip, window_len, scale, means,
+                               static_cast<hipStream_t>(stream));
 }
 
-extern "C" int vadx_frontend_logmel_means(const vadx_frontend_cfg *cfg, const float *packed, const int32_t *mel_kb_host,
-                                          const int16_t *audio, int64_t row_stride, int64_t win_stride, int batch,
-                                          int windows_per_clip, const float *means, float *out, void *stream) {
-    VADX_REQUIRE(means, "vadx_frontend_logmel_means: NULL means");
-    return logmel_impl(cfg, packed, mel_kb_host, audio, row_stride, win_stride, batch, windows_per_clip, const_cast<float *>(means), true, out, stream);
+// The dense kernel over nwin windows (`who`: the entry point, for its messages).  LDS = X2 + the power rows; FSMN / FireRed: 52 992 B --
+// three workgroups per CU (it was 2.3 KB more: two); above the 64 KiB default (513 bins) the limit is raised to what this launch needs
+static int launch_dense(const char *who, const Dev &d, const float *packed, const int16_t *audio, int64_t row_stride, int64_t win_stride,
+                        int windows_per_clip, long long nwin, const float *means, float *out, const float *faux, hipStream_t st) {
+    const size_t lds = ((size_t)d.hop * X_LD + (size_t)d.Fp * P_LD) * sizeof(float);
+    VADX_REQUIRE(lds <= 160 * 1024, "%s: geometry needs %zu B of LDS", who, lds);
+    if (lds > 64 * 1024)
+        VADX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(frontend_logmel_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(frontend_logmel_kernel, dim3((unsigned)(nwin * (d.tiles32 + d.tiles16))), dim3(THREADS), lds, st, d,
+                       packed, audio, (long long)row_stride, (long long)win_stride, windows_per_clip, means, out, faux);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
 }
+
+// Launch one of the three 64-frame-tile kernels from logmel_impl (its d, nwin, st and window arguments; the kernel's further arguments
+// follow): the instantiation's dynamic-LDS limit is raised right here (once per device, VADX_DYN_LDS), the grid is bounded, the launch checked
+#define FE_LAUNCH64(KERNEL, threads, limit, bytes, ...)                                                                                  \
+    do {                                                                                                                                 \
+        const long long nblk_ = nwin * tiles64_per_window(d);                                                                            \
+        VADX_REQUIRE(nblk_ < (1LL << 31), "vadx_frontend_logmel: too many tiles");                                                       \
+        VADX_DYN_LDS(KERNEL, limit);                                                                                                     \
+        hipLaunchKernelGGL(KERNEL, dim3((unsigned)nblk_), dim3(threads), bytes, st, d, packed, audio, (long long)row_stride,             \
+                           (long long)win_stride, windows_per_clip, __VA_ARGS__);                                                        \
+        VADX_HIP_TRY(hipGetLastError());                                                                                                 \
+    } while (0)
 
 static int logmel_impl(const vadx_frontend_cfg *cfg, const float *packed, const int32_t *mel_kb_host, const int16_t *audio, int64_t row_stride,
                        int64_t win_stride, int batch, int windows_per_clip, float *means_ws, bool means_given, float *out, void *stream) {
@@ -1551,59 +1575,39 @@ static int logmel_impl(const vadx_frontend_cfg *cfg, const float *packed, const 
     const float *means = nullptr;
     if (cfg->prep != 1 && cfg->prep < 6) {
         if (!means_given) {             // (vadx_frontend_logmel_means: the caller computed them, e.g. with vadx_fsmn_window_stats)
-            const float scale = (cfg->prep == 2) ? cfg->k1 : 1.0f;
-            hipLaunchKernelGGL(window_mean_kernel, dim3((unsigned)((nwin + 3) / 4)), dim3(256), 0, st, audio, (long long)row_stride,
-                               (long long)win_stride, windows_per_clip, (int)nwin, cfg->window_len, scale, means_ws);
-            VADX_HIP_TRY(hipGetLastError());
+            const float scale = cfg->prep == 2 ? cfg->k1 : 1.0f;
+            if (int rc = launch_window_means(audio, row_stride, win_stride, windows_per_clip, nwin, cfg->window_len, scale, means_ws, st)) return rc;
         }
         means = means_ws;
     }
-    if (d.fold == 4 || d.fold == 5) {
+    if (is_split(d.fold)) {
         const size_t slds = split_lds_bytes(&d);
         VADX_REQUIRE(slds <= 160 * 1024, "vadx_frontend_logmel: geometry needs %zu B of LDS", slds);
-        const long long nblk = nwin * (d.tiles64 + (d.tail_mt ? 1 : 0));
-        VADX_REQUIRE(nblk < (1LL << 31), "vadx_frontend_logmel: too many tiles");
-        if (d.fold == 4) {
-            VADX_DYN_LDS(frontend_split_kernel<vadx::SchemeB3>, 160 * 1024);
-            hipLaunchKernelGGL(frontend_split_kernel<vadx::SchemeB3>, dim3((unsigned)nblk), dim3(SQ_THREADS), slds, st, d, packed, audio, (long long)row_stride,
-                               (long long)win_stride, windows_per_clip, means, out);
-        } else {
-            VADX_DYN_LDS(frontend_split_kernel<vadx::SchemeH2>, 160 * 1024);
-            hipLaunchKernelGGL(frontend_split_kernel<vadx::SchemeH2>, dim3((unsigned)nblk), dim3(SQ_THREADS), slds, st, d, packed, audio, (long long)row_stride,
-                               (long long)win_stride, windows_per_clip, means, out);
-        }
-        VADX_HIP_TRY(hipGetLastError());
+        if (d.fold == K_SPLIT_B3) FE_LAUNCH64(frontend_split_kernel<vadx::SchemeB3>, SQ_THREADS, 160 * 1024, slds, means, out);
+        else FE_LAUNCH64(frontend_split_kernel<vadx::SchemeH2>, SQ_THREADS, 160 * 1024, slds, means, out);
         return VADX_OK;
     }
-    if (d.fold) {
-        const size_t flds = fold_lds_bytes(&d);
-        const long long nblk = nwin * (d.tiles64 + (d.tail_mt ? 1 : 0));
-        VADX_REQUIRE(nblk < (1LL << 31), "vadx_frontend_logmel: too many tiles");
-        if (d.fold == 3) {
-            VADX_DYN_LDS(frontend_fold3_kernel, 80 * 1024);
-            hipLaunchKernelGGL(frontend_fold3_kernel, dim3((unsigned)nblk), dim3(THREADS), flds, st, d, packed, audio, (long long)row_stride,
-                               (long long)win_stride, windows_per_clip, means, out, (int)(fold_pw_off_bytes(&d) / 4));
-            VADX_HIP_TRY(hipGetLastError());
-            return VADX_OK;
-        }
-        VADX_DYN_LDS(frontend_fold_kernel, 80 * 1024);
-        hipLaunchKernelGGL(frontend_fold_kernel, dim3((unsigned)nblk), dim3(THREADS), flds, st, d, packed, audio, (long long)row_stride,
-                           (long long)win_stride, windows_per_clip, means, out, (int)(fold_pw_off_bytes(&d) / 4));
-        VADX_HIP_TRY(hipGetLastError());
+    if (d.fold != K_DENSE) {
+        const int nq_off = (int)(fold_pw_off_bytes(&d) / 4);
+        if (d.fold == K_FOLD_TF) FE_LAUNCH64(frontend_fold3_kernel, THREADS, 80 * 1024, fold_lds_bytes(&d), means, out, nq_off);
+        else FE_LAUNCH64(frontend_fold_kernel, THREADS, 80 * 1024, fold_lds_bytes(&d), means, out, nq_off);
         return VADX_OK;
     }
-    const size_t lds = ((size_t)d.hop * X_LD + (size_t)d.Fp * P_LD) * sizeof(float);      // FSMN / FireRed: 52 992 B -- three workgroups per CU (it was 2.3 KB more: two)
-    VADX_REQUIRE(lds <= 160 * 1024, "vadx_frontend_logmel: geometry needs %zu B of LDS", lds);
-    if (lds > 64 * 1024)
-        VADX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(frontend_logmel_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(frontend_logmel_kernel, dim3((unsigned)(nwin * (d.tiles32 + d.tiles16))), dim3(THREADS), lds, st, d,
-                       packed, audio, (long long)row_stride, (long long)win_stride, windows_per_clip, means, out,
-                       static_cast<const float *>(nullptr));
-    VADX_HIP_TRY(hipGetLastError());
-    return VADX_OK;
+    return launch_dense("vadx_frontend_logmel", d, packed, audio, row_stride, win_stride, windows_per_clip, nwin, means, out, nullptr, st);
 }
 
+extern "C" int vadx_frontend_logmel(const vadx_frontend_cfg *cfg, const float *packed, const int32_t *mel_kb_host,
+                                    const int16_t *audio, int64_t row_stride, int64_t win_stride, int batch,
+                                    int windows_per_clip, float *means_ws, float *out, void *stream) {
+    return logmel_impl(cfg, packed, mel_kb_host, audio, row_stride, win_stride, batch, windows_per_clip, means_ws, false, out, stream);
+}
+
+extern "C" int vadx_frontend_logmel_means(const vadx_frontend_cfg *cfg, const float *packed, const int32_t *mel_kb_host,
+                                          const int16_t *audio, int64_t row_stride, int64_t win_stride, int batch,
+                                          int windows_per_clip, const float *means, float *out, void *stream) {
+    VADX_REQUIRE(means, "vadx_frontend_logmel_means: NULL means");
+    return logmel_impl(cfg, packed, mel_kb_host, audio, row_stride, win_stride, batch, windows_per_clip, const_cast<float *>(means), true, out, stream);
+}
 
 // DFSMN feature streams: same fused kernel, sources = int16 near window (+ its scaled mean) and/or the float AEC
 // waveform [windows][window_len]; writes n_mels columns at out_off of rows of out_stride floats.
@@ -1619,17 +1623,8 @@ extern "C" int vadx_frontend_logmel_ex(const vadx_frontend_cfg *cfg, const float
     VADX_REQUIRE(out_stride >= out_off + cfg->n_mels && out_stride % 4 == 0 && out_off % 4 == 0, "vadx_frontend_logmel_ex: bad output stride/offset");
     for (int mt = 0; mt < d.nmt; ++mt) { d.mel_kb_lo[mt] = mel_kb_host[2 * mt]; d.mel_kb_hi[mt] = mel_kb_host[2 * mt + 1]; }
     d.out_stride = out_stride; d.out_off = out_off;
-    const long long nwin = (long long)batch * windows_per_clip;
-    const size_t lds = ((size_t)d.hop * X_LD + (size_t)d.Fp * P_LD) * sizeof(float);      // FSMN / FireRed: 52 992 B -- three workgroups per CU (it was 2.3 KB more: two)
-    VADX_REQUIRE(lds <= 160 * 1024, "vadx_frontend_logmel_ex: geometry needs %zu B of LDS", lds);
-    if (lds > 64 * 1024)
-        VADX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(frontend_logmel_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(frontend_logmel_kernel, dim3((unsigned)(nwin * (d.tiles32 + d.tiles16))), dim3(THREADS), lds,
-                       static_cast<hipStream_t>(stream), d, packed, audio, (long long)row_stride, (long long)win_stride,
-                       windows_per_clip, means, out, faux);
-    VADX_HIP_TRY(hipGetLastError());
-    return VADX_OK;
+    return launch_dense("vadx_frontend_logmel_ex", d, packed, audio, row_stride, win_stride, windows_per_clip, (long long)batch * windows_per_clip,
+                        means, out, faux, static_cast<hipStream_t>(stream));
 }
 
 // Raw complex STFT of int16 windows into an FT tensor [window*ft_nt + t/16][c_total][n_bins][16] at channels
@@ -1644,9 +1639,7 @@ extern "C" int vadx_frontend_stft_ft(const vadx_frontend_cfg *cfg, const float *
     VADX_REQUIRE((windows_per_clip - 1) * win_stride + cfg->window_len <= row_stride, "vadx_frontend_stft_ft: windows run past the clip row");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long nwin = (long long)batch * windows_per_clip;
-    hipLaunchKernelGGL(window_mean_kernel, dim3((unsigned)((nwin + 3) / 4)), dim3(256), 0, st, audio, (long long)row_stride,
-                       (long long)win_stride, windows_per_clip, (int)nwin, cfg->window_len, cfg->k1, means_ws);
-    VADX_HIP_TRY(hipGetLastError());
+    if (int rc = launch_window_means(audio, row_stride, win_stride, windows_per_clip, nwin, cfg->window_len, cfg->k1, means_ws, st)) return rc;
     const int ft_nt = (d.frames + 15) / 16, tiles = (d.frames + TF - 1) / TF;
     const size_t lds = ((size_t)d.hop * X_LD) * sizeof(float);
     hipLaunchKernelGGL(stft_complex_kernel, dim3((unsigned)(nwin * tiles)), dim3(THREADS), lds, st, d, packed, audio,

@@ -36,18 +36,104 @@ def resampled_length(in_len, in_sample_rate):
     return int(np.floor(float(in_len) * scale_factor)), np.float32(1.0 / scale_factor)
 
 
+# The DFT product kinds = vadx_frontend_cfg.fold (include/vadx.h: VADX_FE_KIND_*)
+KIND_DENSE, KIND_FOLD_SYM, KIND_FOLD_PER, KIND_FOLD_TF, KIND_SPLIT_B3, KIND_SPLIT_H2 = range(6)
+ENV_KINDS = {"3": KIND_FOLD_TF, "4": KIND_SPLIT_B3, "5": KIND_SPLIT_H2}      # the kinds VADX_FRONTEND_FOLD asks for by number
+ENV_DEFAULT = "5"
+
+
+def host_tables(preset, window_len, n_mels=80, sample_rate=16000, in_sample_rate=16000):
+    """Host side of one preset (a PRESETS name or a dict like its entries) and one window length: (preset dict with the resampling prep
+    resolved, vadx_frontend_cfg with fold = 0, cos table, sin table [n_bins][n_fft], mel filterbank [n_mels][n_bins]) -- the reference's
+    own float32 tables as numpy arrays.  Needs no GPU."""
+    p = dict(PRESETS[preset]) if isinstance(preset, str) else dict(preset)
+    n_fft, win, hop = p["n_fft"], p["win"], p["hop"]
+    half = n_fft // 2
+    out_len, rs_scale = resampled_length(int(window_len), int(in_sample_rate))
+    if rs_scale is not None:
+        if p["prep"] != 1:
+            raise ValueError("in-graph resampling exists only in the two-tap (MarbleNet / FireRed) exports")
+        p["prep"] = 6 if int(in_sample_rate) > 16000 else 7
+    frames = (out_len // hop + 1) if p["center"] else ((out_len - n_fft) // hop + 1)
+    if frames <= 0:
+        raise ValueError(f"window of {int(window_len)} samples at {int(in_sample_rate)} Hz is shorter than one analysis frame")
+    w = tables.analysis_window(p["window"], win, n_fft, p["variant"])
+    cos_t, sin_t = tables.windowed_dft(n_fft, w, p["variant"])
+    if p["mel"][0] == "torchaudio":
+        _, fmin, fmax, norm, scale = p["mel"]
+        fb = tables.mel_filters_torchaudio(half + 1, fmin, fmax, n_mels, sample_rate, norm, scale)
+    elif p["mel"][0] == "zeros":          # raw-spectrum users (vadx_frontend_stft_ft) never touch the mel stage
+        import torch
+        fb = torch.zeros((n_mels, half + 1), dtype=torch.float32)
+    else:
+        fb = tables.mel_filters_kaldi(n_fft, n_mels, sample_rate, p["mel"][1], p["mel"][2])
+    cfg = _lib.FrontendCfg()
+    cfg.prep, cfg.k0, cfg.k1 = p["prep"], p["k"][0], p["k"][1]
+    cfg.center_pad = half if p["center"] else 0
+    cfg.tap0 = (n_fft - win) // 2 if win < n_fft else 0
+    cfg.taps = min(win, n_fft)
+    cfg.hop, cfg.n_bins, cfg.n_mels = hop, half + 1, n_mels
+    cfg.log_mode, cfg.log_floor = p["log_mode"], p["log_floor"]
+    cfg.frames, cfg.window_len = frames, out_len
+    cfg.in_window_len, cfg.rs_scale = (int(window_len), float(rs_scale)) if rs_scale is not None else (0, 0.0)
+    return p, cfg, tables.as_np(cos_t), tables.as_np(sin_t), tables.as_np(fb)
+
+
+def select_kind(cfg, cos, sin, n_fft, fbank, fold=None, env=None):
+    """Choose the DFT product for one table and pack its blob, once: -> (kind, packed float32 blob, mel_kb int32); cfg.fold = kind on return.
+    Host library only (no GPU).  `fold` is Frontend's argument, `env` the value of VADX_FRONTEND_FOLD (None = unset = "5").  The ladder:
+      fold False / 0          KIND_DENSE
+      fold True               the mirror fold the table admits (`vadx_frontend_fold_kind`); ValueError if it admits none
+      fold k > 0              kind k, or the packer's ValueError (a geometry the kind does not take, a table it does not admit)
+      fold None               env "0", or an all-zero filterbank (the "zeros" mel of the raw-STFT users): KIND_DENSE;
+                              env "3" / "4" / "5": that kind if the packer takes it, else the admitted mirror fold, else KIND_DENSE;
+                              any other env: the admitted mirror fold, else KIND_DENSE."""
+    L = _lib.lib()
+
+    def admitted():
+        return int(L.vadx_frontend_fold_kind(C.byref(cfg), cos.ctypes.data, sin.ctypes.data, n_fft))
+
+    def pack(kind):
+        cfg.fold = kind
+        n = L.vadx_frontend_packed_floats(C.byref(cfg))
+        if n == 0:
+            raise ValueError("front-end geometry not supported by the HIP kernel (hop % 16, n_mels % 16, <= 4 passes)")
+        packed, mel_kb = np.zeros(n, dtype=np.float32), np.zeros(2 * (cfg.n_mels // 16), dtype=np.int32)
+        _lib.check(L.vadx_frontend_pack_host(C.byref(cfg), cos.ctypes.data, sin.ctypes.data, n_fft, fbank.ctypes.data,
+                                             packed.ctypes.data, mel_kb.ctypes.data))
+        return kind, packed, mel_kb
+
+    if fold is None:
+        env = ENV_DEFAULT if env is None else env
+        if env == "0" or not fbank.any():
+            return pack(KIND_DENSE)
+        if env in ENV_KINDS:
+            try:
+                return pack(ENV_KINDS[env])
+            except ValueError:      # asked for through the environment: where the kind does not apply, what the table admits
+                pass
+    elif not isinstance(fold, bool) and isinstance(fold, int) and fold > 0:
+        return pack(int(fold))
+    elif not fold:
+        return pack(KIND_DENSE)
+    kind = admitted()
+    if fold is True and kind == KIND_DENSE:
+        raise ValueError("this table / geometry has no folded DFT product")
+    return pack(kind)
+
+
 class Frontend:
     """Device-resident packed tables for one preset and one window length."""
 
     def __init__(self, preset, window_len, device="cuda:0", n_mels=80, sample_rate=16000, in_sample_rate=16000, fold=None):
-        """fold: None = the fastest DFT product that holds the dense f32 product's error bound: kind 5 (the reference table times the
-        prepped samples as fp16 x 2 split products, csrc/split2.h; the samples are bounded by the int16 input and pre-scaled exactly, so no
-        range check is involved) where the geometry has it (hop 160, int16 preps), else the folded f32 product the table admits
-        (`vadx_frontend_fold_kind`), else the dense f32 product.  VADX_FRONTEND_FOLD overrides process-wide: 0 = dense f32, 1 = the folded
-        f32 product (round 3's default), 3 = opt into kind 3 (time x frequency fold: faster, noisier on weak bands), 4 = the same dense
-        product on bf16 x 3 exactly split operands (round 4's default), 5 = the default.  False = dense f32 product (the table-level parity
-        tests compare against it), True = require a folded f32 product, 1 ... 5 = that kind (pack_host refuses a kind the
-        table does not admit).
+        """fold: None = the fastest DFT product that holds the dense f32 product's error bound: KIND_SPLIT_H2 (the reference table times
+        the prepped samples as fp16 x 2 split products, csrc/split2.h; the samples are bounded by the int16 input and pre-scaled exactly,
+        so no range check is involved) where the geometry has it (hop 160, int16 preps), else the mirror-folded f32 product the table
+        admits (KIND_FOLD_SYM / KIND_FOLD_PER, `vadx_frontend_fold_kind`), else KIND_DENSE.  VADX_FRONTEND_FOLD, read at every
+        construction, overrides that: 0 = dense, 1 = the admitted mirror fold, 3 = opt into KIND_FOLD_TF (time x frequency fold: faster,
+        noisier on weak bands), 4 = KIND_SPLIT_B3 (the dense product on bf16 x 3 exactly split operands), 5 = the default.  False = dense
+        (the table-level parity tests compare against it), True = require a mirror fold, 1 ... 5 = that kind or a ValueError.  The
+        precedence is `select_kind`'s; self.fold is the kind chosen.
         window_len = samples per window IN THE AUDIO BUFFER.  in_sample_rate != 16000 reproduces the exports built with
         IN_SAMPLE_RATE set (Export_NVIDIA_MarbleNet_VAD.py:237-254, FireRedVAD/Export_FireRedVAD.py:431-449): the graph itself
         resamples each window to 16 kHz with F.interpolate(linear, align_corners=False), before the pre-emphasis when the
@@ -55,69 +141,11 @@ class Frontend:
         torch = _lib.require_gpu()
         self.torch = torch
         self.device = torch.device(device)
-        p = dict(PRESETS[preset]) if isinstance(preset, str) else dict(preset)
-        self.p = p
-        n_fft, win, hop = p["n_fft"], p["win"], p["hop"]
-        half = n_fft // 2
-        self.in_window_len = int(window_len)
-        self.in_sample_rate = int(in_sample_rate)
-        self.window_len, rs_scale = resampled_length(self.in_window_len, self.in_sample_rate)
-        if rs_scale is not None:
-            if p["prep"] != 1:
-                raise ValueError("in-graph resampling exists only in the two-tap (MarbleNet / FireRed) exports")
-            p["prep"] = 6 if self.in_sample_rate > 16000 else 7
-        self.frames = (self.window_len // hop + 1) if p["center"] else ((self.window_len - n_fft) // hop + 1)
-        if self.frames <= 0:
-            raise ValueError(f"window of {self.in_window_len} samples at {self.in_sample_rate} Hz is shorter than one analysis frame")
-        w = tables.analysis_window(p["window"], win, n_fft, p["variant"])
-        cos_t, sin_t = tables.windowed_dft(n_fft, w, p["variant"])
-        if p["mel"][0] == "torchaudio":
-            _, fmin, fmax, norm, scale = p["mel"]
-            fb = tables.mel_filters_torchaudio(half + 1, fmin, fmax, n_mels, sample_rate, norm, scale)
-        elif p["mel"][0] == "zeros":          # raw-spectrum users (vadx_frontend_stft_ft) never touch the mel stage
-            fb = torch.zeros((n_mels, half + 1), dtype=torch.float32)
-        else:
-            fb = tables.mel_filters_kaldi(n_fft, n_mels, sample_rate, p["mel"][1], p["mel"][2])
-        cfg = _lib.FrontendCfg()
-        cfg.prep, cfg.k0, cfg.k1 = p["prep"], p["k"][0], p["k"][1]
-        cfg.center_pad = half if p["center"] else 0
-        cfg.tap0 = (n_fft - win) // 2 if win < n_fft else 0
-        cfg.taps = min(win, n_fft)
-        cfg.hop, cfg.n_bins, cfg.n_mels = hop, half + 1, n_mels
-        cfg.log_mode, cfg.log_floor = p["log_mode"], p["log_floor"]
-        cfg.frames, cfg.window_len = self.frames, self.window_len
-        cfg.in_window_len, cfg.rs_scale = (self.in_window_len, float(rs_scale)) if rs_scale is not None else (0, 0.0)
-        self.cfg = cfg
-        self.n_mels = n_mels
-        L = _lib.lib()
-        cos_n, sin_n, fb_n = tables.as_np(cos_t), tables.as_np(sin_t), tables.as_np(fb)
-        required = fold is True
-        kind = int(fold) if (not isinstance(fold, bool) and isinstance(fold, int) and fold > 0) else None      # a specific kind
-        env = os.environ.get("VADX_FRONTEND_FOLD", "5")
-        from_env = False
-        if fold is None:
-            fold = env != "0" and p["mel"][0] != "zeros"
-            if fold and env in ("3", "4", "5"):
-                kind, from_env = int(env), True               # 3 = time x frequency fold, 4 / 5 = dense product on bf16 x 3 / fp16 x 2 split operands, wherever they apply
-        auto = lambda: int(L.vadx_frontend_fold_kind(C.byref(cfg), cos_n.ctypes.data, sin_n.ctypes.data, n_fft))      # noqa: E731
-        cfg.fold = kind if kind else (auto() if fold else 0)
-        if from_env:
-            # requested through the environment: fall back to the default kind where kind 3 does not apply (symmetric windows, other geometries)
-            probe = np.zeros(max(1, L.vadx_frontend_packed_floats(C.byref(cfg))), dtype=np.float32)
-            kb = np.zeros(2 * (n_mels // 16), dtype=np.int32)
-            if probe.size <= 1 or L.vadx_frontend_pack_host(C.byref(cfg), cos_n.ctypes.data, sin_n.ctypes.data, n_fft, fb_n.ctypes.data,
-                                                            probe.ctypes.data, kb.ctypes.data) != 0:
-                cfg.fold = auto()
-        if required and not cfg.fold:
-            raise ValueError("this table / geometry has no folded DFT product")
-        self.fold = cfg.fold
-        n = L.vadx_frontend_packed_floats(C.byref(cfg))
-        if n == 0:
-            raise ValueError("front-end geometry not supported by the HIP kernel (hop % 16, n_mels % 16, <= 4 passes)")
-        packed = np.zeros(n, dtype=np.float32)
-        self.mel_kb = np.zeros(2 * (n_mels // 16), dtype=np.int32)
-        _lib.check(L.vadx_frontend_pack_host(C.byref(cfg), cos_n.ctypes.data, sin_n.ctypes.data, n_fft,
-                                             fb_n.ctypes.data, packed.ctypes.data, self.mel_kb.ctypes.data))
+        self.p, cfg, cos_n, sin_n, fb_n = host_tables(preset, window_len, n_mels, sample_rate, in_sample_rate)
+        self.cfg, self.n_mels = cfg, n_mels
+        self.in_window_len, self.in_sample_rate = int(window_len), int(in_sample_rate)
+        self.window_len, self.frames = cfg.window_len, cfg.frames
+        self.fold, packed, self.mel_kb = select_kind(cfg, cos_n, sin_n, self.p["n_fft"], fb_n, fold, os.environ.get("VADX_FRONTEND_FOLD"))
         self.packed = torch.from_numpy(packed).to(self.device)
 
     def logmel(self, audio_i16, windows_per_clip=1, win_stride=None, out=None):
