@@ -738,7 +738,9 @@ int vadx_dfsmn_lstm_t_ex(int which, const vadx_ft_view *in, const vadx_ft_ln *ln
 int vadx_dfsmn_ft_repack(const float *src, float *dst, int channels, int F, int frames, int chunks, int src_stride, int dst_stride, void *stream);
 /* NET.istft :220-224: y_ft FT [2 ch x 160] -> out f32 [chunks][(frames-1)*160 + 1]; basis_t [320 j][320 ch]
  * (transposed inverse basis, row 319 zero), wsum_inv = the reference's window_sum_inv buffer; z_ws scratch
- * of chunks*frames*320 floats. */
+ * of chunks*frames*320 floats.  wsum_inv must hold at least (frames-1)*160 + 319 floats -- it is read at samples 159 ..
+ * (frames-1)*160 + 159 of the uncropped signal -- and the entry point cannot check that: the caller bounds `frames` by
+ * the frame count its buffer was built for (200 in NET.__init__; vadx.dfsmn.ISTFT_MAX_FRAMES). */
 int vadx_dfsmn_istft(const float *y_ft, const float *basis_t, const float *wsum_inv, float *z_ws, float *out,
                      int chunks, int frames, void *stream);
 /* mask-net head: device pointers; linear weights zero-padded to multiples of 16 in BOTH dims
@@ -749,7 +751,9 @@ typedef struct vadx_dfsmn_mask_weights {
     const float *fsmn_linear_w[8], *fsmn_linear_b[8], *fsmn_project_w[8], *fsmn_conv_w[8];
 } vadx_dfsmn_mask_weights;
 /* feat f32 [chunks][frames][240] (3 x 80 log-fbank streams) -> vad f32 [chunks][frames]
- * (DFSMN_VAD.forward :349-353 + UniDeepFsmn.compute1, uni_deep_fsmn.py:311-329). */
+ * (DFSMN_VAD.forward :349-353 + UniDeepFsmn.compute1, uni_deep_fsmn.py:311-329).  One workgroup per chunk with the activations in
+ * LDS: frames in [1, 64], hidden in [1, 128], fsmn_hidden in [1, 256], layers in [0, 8], lorder in [1, 20]; anything else is
+ * VADX_EINVAL with a message naming the limit. */
 int vadx_dfsmn_mask_net(const vadx_dfsmn_mask_weights *w, const float *feat, int chunks, int frames, float *vad,
                         void *stream);
 /* Look-ahead vote + tail of the DFSMN driver (Inference_DFSMN_VAD_ONNX.py:231-273): vad f32 [B][W][frames]

@@ -1,8 +1,13 @@
 """Oracle: DFSMN near+far path (SURVEY §8 rows a18, a19, a20 + the DFSMN half of a9).
 
-TEST INFRASTRUCTURE -- CPU restatement in torch float32 (batch 1 like the reference; the ICCRN's
+TEST INFRASTRUCTURE -- CPU restatement in torch (batch 1 like the reference; the ICCRN's
 views hard-code batch 1).  Weight dict keys are the reference modules' state_dict names so a real
 SDAEC `ICCRN.ckpt` / `alpha.ckpt` drops in unchanged.
+
+The dtype follows the input: float32 tensors give the reference's float32 graph bit for bit (pinned by the
+fixtures); float64 tensors, with tables built as `IccrnTables(dtype=torch.float64)` / `Frontend(dtype=torch.float64)`
+and the float32 weights cast to double, evaluate the reference's own float32 table bits and weights in double --
+the yardstick of tests/test_gpu_dfsmn_shapes.py.
 
 In tree and pinned by fixtures (tests/golden/dfsmn_forward.npz): AlphaPredictor, ICCRN `NET`
 (CFB, CepsUnit, LayerNorm, CH_LSTM_F, CH_LSTM_T), the `DFSMN_VAD` wrapper, `UniDeepFsmn.compute1`.
@@ -29,7 +34,7 @@ CEPS_F = CEPS_N // 2 + 1          # 81
 
 def _lstm(x, w, prefix, in_dim, hid, layers=1, bi=False):
     """torch.nn.LSTM(batch_first=True) forward with weights from dict (state_dict names)."""
-    m = torch.nn.LSTM(in_dim, hid, num_layers=layers, batch_first=True, bidirectional=bi)
+    m = torch.nn.LSTM(in_dim, hid, num_layers=layers, batch_first=True, bidirectional=bi).to(x.dtype)
     sd = {k[len(prefix):]: v for k, v in w.items() if k.startswith(prefix)}
     m.load_state_dict(sd, strict=True)
     m.eval()
@@ -62,18 +67,18 @@ def ch_lstm_t(x, w, p, in_ch, feat, out_ch, layers, f=F_BINS):
 
 class CepsTables:
     """Buffers of CepsUnit.__init__ (:104-130): rectangular-window real DFT of length 160 along
-    the frequency axis and its pinv-based inverse."""
+    the frequency axis and its pinv-based inverse: float32 torch ops in the reference's order, then cast to `dtype`."""
 
-    def __init__(self):
+    def __init__(self, dtype=torch.float32):
         n, half = CEPS_N, CEPS_N // 2
         t = torch.arange(n, dtype=torch.float32).unsqueeze(0)
         f = torch.arange(half + 1, dtype=torch.float32).unsqueeze(1)
         omega = 2 * torch.pi * f * t / n
-        self.cos_k = torch.cos(omega).unsqueeze(1)
-        self.sin_k = (-torch.sin(omega)).unsqueeze(1)
+        self.cos_k = torch.cos(omega).unsqueeze(1).to(dtype)
+        self.sin_k = (-torch.sin(omega)).unsqueeze(1).to(dtype)
         fb = torch.fft.fft(torch.eye(n, dtype=torch.float32))
         basis = torch.vstack([torch.real(fb[:half + 1]), torch.imag(fb[:half + 1])]).float()
-        self.inv_basis = torch.linalg.pinv(basis).T.unsqueeze(1)          # [162,1,160] (window = ones)
+        self.inv_basis = torch.linalg.pinv(basis).T.unsqueeze(1).to(dtype)          # [162,1,160] (window = ones)
 
 
 def ceps_unit(x0, w, p, ch, tb):
@@ -102,15 +107,15 @@ def cfb(x, w, p, tb, ch=20):
 
 
 class IccrnTables:
-    """ISTFT buffers of NET.__init__ (:183-207)."""
+    """ISTFT buffers of NET.__init__ (:183-207): float32 torch ops in the reference's order, then cast to `dtype`."""
 
-    def __init__(self, max_frames=200):
+    def __init__(self, max_frames=200, dtype=torch.float32):
         n, hop, half = NFFT_B, HOP_B, NFFT_B // 2
         self.window = torch.hamming_window(n)
         fe = torch.fft.fft(torch.eye(n, dtype=torch.float32))
         fb = torch.vstack([torch.real(fe[:half + 1]), torch.imag(fe[:half + 1])]).float()
         pinv_t = torch.linalg.pinv((fb * n) / hop).T
-        self.inverse_basis = pinv_t.unsqueeze(1) * self.window.view(1, 1, -1)        # [320,1,319]
+        self.inverse_basis = (pinv_t.unsqueeze(1) * self.window.view(1, 1, -1)).to(dtype)        # [320,1,319]
         out_len = (max_frames - 1) * hop + n
         ws = torch.zeros(out_len, dtype=torch.float32)
         wsq = self.window ** 2
@@ -120,12 +125,12 @@ class IccrnTables:
             if L <= 0:
                 break
             ws[s:s + L] += wsq[:L]
-        self.window_sum_inv = n / (ws * hop + 1e-6)
-        self.ceps = CepsTables()
+        self.window_sum_inv = (n / (ws * hop + 1e-6)).to(dtype)
+        self.ceps = CepsTables(dtype)
 
 
-def iccrn(x, w, tb, ch=20):
-    """[1,4,160,T] -> (aec waveform [1,1,L], L). ref: NET.forward :226-249 (+ istft :220-224)."""
+def iccrn_spectrum(x, w, tb, ch=20):
+    """[1,4,160,T] -> the AEC spectrum [1,2,160,T] (re, im) in front of the ISTFT. ref: NET.forward :226-249."""
     c = tb.ceps
     e0 = ch_lstm_f(x, w, "in_ch_lstm", 4, ch, ch, F_BINS)
     e0 = F.conv2d(torch.cat([e0, x], 1), w["in_conv.weight"], w["in_conv.bias"])
@@ -141,53 +146,76 @@ def iccrn(x, w, tb, ch=20):
     d2 = cfb(torch.cat([e2, d3], 1), w, "cfb_d2", c)
     d1 = cfb(torch.cat([e1, d2], 1), w, "cfb_d1", c)
     d0 = ch_lstm_t(torch.cat([e0, d1], 1), w, "out_ch_lstm", 2 * ch, ch, 2 * ch, 1)
-    out = F.conv2d(torch.cat([d0, d1], 1), w["out_conv.weight"], w["out_conv.bias"])
+    return F.conv2d(torch.cat([d0, d1], 1), w["out_conv.weight"], w["out_conv.bias"])
+
+
+def istft(spec, tb):
+    """spectrum [1,2,160,T] -> (waveform [1,1,L], L = (T-1)*160 + 1). ref: NET.istft :220-224."""
     half = NFFT_B // 2
-    inv = F.conv_transpose1d(out.reshape(1, 2 * F_BINS, -1), tb.inverse_basis, stride=HOP_B)
+    inv = F.conv_transpose1d(spec.reshape(1, 2 * F_BINS, -1), tb.inverse_basis, stride=HOP_B)
     e = inv.size(-1) - half
     return inv[..., half:e] * tb.window_sum_inv[half:e], e - half
+
+
+def iccrn(x, w, tb, ch=20):
+    """[1,4,160,T] -> (aec waveform [1,1,L], L). ref: NET.forward :226-249 (+ istft :220-224)."""
+    return istft(iccrn_spectrum(x, w, tb, ch), tb)
 
 
 def uni_deep_fsmn(x, w, p, lorder=20):
     """x [1,T,H]. ref: UniDeepFsmn.compute1, uni_deep_fsmn.py:311-329 (dilation 1, skip_connect)."""
     h = F.relu(F.linear(x, w[p + ".linear.weight"], w[p + ".linear.bias"]))
     pr = F.linear(h, w[p + ".project.weight"]).transpose(1, 2).unsqueeze(-1)          # [1,H,T,1]
-    y = torch.cat([torch.zeros(1, pr.shape[1], lorder - 1, 1), pr], dim=-2)
+    y = torch.cat([torch.zeros(1, pr.shape[1], lorder - 1, 1, dtype=pr.dtype), pr], dim=-2)
     out = F.conv2d(y, w[p + ".conv1.weight"], groups=pr.shape[1]) + pr
     return x + out.transpose(1, 2).squeeze(-1)
 
 
+def mask_head(feat, w, n_fsmn=None):
+    """The mask-net head on its 240-dim features [1,T,240] (log filterbank energies of the three streams) -> the logit [1,T,1] in front of the
+    sigmoid: shift / scale, linear1, the first n_fsmn `mask.deepfsmn.{i}` layers (None: every layer the weights hold), each with the
+    lorder its conv1 has taps for, linear3. ref: DFSMN_VAD.forward :349-353."""
+    if n_fsmn is None:
+        n_fsmn = len([k for k in w if k.startswith("mask.deepfsmn.") and k.endswith(".linear.weight")])
+    feat = (feat + w["mask.shift"].view(1, 1, -1)) * w["mask.scale"].view(1, 1, -1)
+    x = F.relu(F.linear(feat, w["mask.linear1.weight"], w["mask.linear1.bias"]))
+    for i in range(n_fsmn):
+        x = uni_deep_fsmn(x, w, f"mask.deepfsmn.{i}", w[f"mask.deepfsmn.{i}.conv1.weight"].shape[2])
+    return F.linear(x, w["mask.linear3.weight"], w["mask.linear3.bias"])
+
+
 class Frontend:
-    def __init__(self, max_frames=200):
+    """The wrapper's tables: float32 torch ops in the reference's order, then cast to `dtype`."""
+
+    def __init__(self, max_frames=200, dtype=torch.float32):
         wb = ostft.padded_window(NFFT_B, NFFT_B, "hamming", "v1b")
-        self.cos_b, self.sin_b = ostft.dft_tables(NFFT_B, wb, "v1b")
+        self.cos_b, self.sin_b = (t.to(dtype) for t in ostft.dft_tables(NFFT_B, wb, "v1b"))
         wa = ostft.padded_window(WIN_A, NFFT_A, "hamming", "v1b")
-        self.cos_a, self.sin_a = ostft.dft_tables(NFFT_A, wa, "v1b")
-        self.fbank = omel.melscale_fbanks(NFFT_A // 2 + 1, 20, 8000, 80, 16000, None, "htk").t().unsqueeze(0)
-        self.tb = IccrnTables(max_frames)
+        self.cos_a, self.sin_a = (t.to(dtype) for t in ostft.dft_tables(NFFT_A, wa, "v1b"))
+        self.fbank = omel.melscale_fbanks(NFFT_A // 2 + 1, 20, 8000, 80, 16000, None, "htk").t().unsqueeze(0).to(dtype)
+        self.dtype = dtype
+        self.tb = IccrnTables(max_frames, dtype)
         self.frame_starts = torch.arange(max_frames).unsqueeze(1) + torch.arange(ALPHA_K).unsqueeze(0)
 
 
-def forward(fe, w, near_i16, far_i16, n_fsmn, near_only=None):
-    """session.run equivalent: two int16 [1,1,L] -> vad_results f32 [T_A].
-    ref: DFSMN_VAD.forward, DFSMN/near_and_far_end_audio/Export_DFSMN_VAD.py:317-354.  far_i16 None = the near-end-only
-    model (DFSMN/only_near_end_audio/Export_DFSMN_VAD.py:318-350): near_only = (pow_far [160,T',10], far_comp [2,160,T'])
-    are its baked white-noise tensors.  Returns (vad, aec waveform) for staged tests."""
+def scaled_input(fe, w, near_i16, far_i16, near_only=None):
+    """two int16 [1,1,L] -> (near [1,1,L] mean-removed, x4 [1,4,160,T] = mix re, mix im, |alpha| far re, |alpha| far im) in fe.dtype.
+    ref: DFSMN_VAD.forward :317-335; far_i16 None = the near-end-only model, see `forward`."""
     inv = float(1.0 / 32768.0)
-    near = near_i16.float() * inv
+    near = near_i16.to(fe.dtype) * inv
     near = near - torch.mean(near)
     nre, nim = ostft.stft(near, fe.cos_b, fe.sin_b, HOP_B, True)
     mix = torch.cat([nre, nim], dim=0).unsqueeze(0)                      # [1,2,160,T]
     T = mix.shape[-1]
-    pad = torch.zeros((1, 2, F_BINS, ALPHA_K - 1))
+    pad = torch.zeros((1, 2, F_BINS, ALPHA_K - 1), dtype=fe.dtype)
     idx = fe.frame_starts[:T]
     mu = torch.cat([pad, mix], dim=-1)[..., idx]                         # [1,2,160,T,10]
     pow_mix = (mu * mu).sum(dim=1, keepdim=True)
     if far_i16 is None:
-        pow_far = near_only[0][:, :T, :].float().reshape(1, 1, F_BINS, T, ALPHA_K)
-        farc = near_only[1][:, :, :T].float().reshape(1, 1, 2, F_BINS, T)[0]          # [1,2,160,T]
+        pow_far = near_only[0][:, :T, :].to(fe.dtype).reshape(1, 1, F_BINS, T, ALPHA_K)
+        farc = near_only[1][:, :, :T].to(fe.dtype).reshape(1, 1, 2, F_BINS, T)[0]          # [1,2,160,T]
     else:
-        far = far_i16.float() * inv
+        far = far_i16.to(fe.dtype) * inv
         far = far - torch.mean(far)
         fre, fim = ostft.stft(far, fe.cos_b, fe.sin_b, HOP_B, True)
         farc = torch.cat([fre, fim], dim=0).unsqueeze(0)
@@ -197,24 +225,34 @@ def forward(fe, w, near_i16, far_i16, n_fsmn, near_only=None):
     alpha = F.linear(torch.sum(ci, dim=2, keepdim=True), w["alpha.linear1.weight"], w["alpha.linear1.bias"]).squeeze(dim=-1)
     alpha = F.linear(alpha, w["alpha.linear2.weight"], w["alpha.linear2.bias"]).squeeze(dim=-1)
     farc = farc * torch.abs(alpha)
-    iw = {k[len("iccrn."):]: v for k, v in w.items() if k.startswith("iccrn.")}
-    aec, min_len = iccrn(torch.cat([mix, farc.squeeze(1)], dim=1), iw, fe.tb)
-    near = near[..., :min_len]
-    pe = torch.tensor(0.97, dtype=torch.float32)
+    return near, torch.cat([mix, farc.squeeze(1)], dim=1)
+
+
+def features(fe, near, aec):
+    """near [1,1,L] (mean-removed), aec [1,1,L] -> the 240-dim log filterbank energies [1,T_A,240] of the near, AEC and echo streams
+    (pre-emphasis 0.97 and the echo gain 1.15 are the reference's float32 constants). ref: DFSMN_VAD.forward :338-348."""
+    pe = torch.tensor(0.97, dtype=torch.float32).to(near.dtype)
+    gain = torch.tensor(1.15, dtype=torch.float32).to(near.dtype)
     near = torch.cat([near[:, :, :1], near[:, :, 1:] - pe * near[:, :, :-1]], dim=-1)
     aec_pe = torch.cat([aec[:, :, :1], aec[:, :, 1:] - pe * aec[:, :, :-1]], dim=-1)
-    echo = near - float(1.15) * aec_pe
+    echo = near - gain * aec_pe
     feats = []
     for sig in (near, aec_pe, echo):
         re, im = ostft.stft(sig, fe.cos_a, fe.sin_a, HOP_A, True)
         feats.append(torch.matmul(fe.fbank, re * re + im * im))
-    feat = torch.cat(feats, dim=1).transpose(1, 2).clamp(1e-6).log()
-    feat = (feat + w["mask.shift"].view(1, 1, -1)) * w["mask.scale"].view(1, 1, -1)
-    x = F.relu(F.linear(feat, w["mask.linear1.weight"], w["mask.linear1.bias"]))
-    for i in range(n_fsmn):
-        x = uni_deep_fsmn(x, w, f"mask.deepfsmn.{i}")
-    vad = torch.sigmoid(F.linear(x, w["mask.linear3.weight"], w["mask.linear3.bias"])).squeeze()
-    return vad, aec
+    return torch.cat(feats, dim=1).transpose(1, 2).clamp(1e-6).log()
+
+
+def forward(fe, w, near_i16, far_i16, n_fsmn, near_only=None):
+    """session.run equivalent: two int16 [1,1,L] -> vad_results [T_A] in fe.dtype.
+    ref: DFSMN_VAD.forward, DFSMN/near_and_far_end_audio/Export_DFSMN_VAD.py:317-354.  far_i16 None = the near-end-only
+    model (DFSMN/only_near_end_audio/Export_DFSMN_VAD.py:318-350): near_only = (pow_far [160,T',10], far_comp [2,160,T'])
+    are its baked white-noise tensors.  Returns (vad, aec waveform) for staged tests."""
+    near, x4 = scaled_input(fe, w, near_i16, far_i16, near_only)
+    iw = {k[len("iccrn."):]: v for k, v in w.items() if k.startswith("iccrn.")}
+    aec, min_len = iccrn(x4, iw, fe.tb)
+    feat = features(fe, near[..., :min_len], aec)
+    return torch.sigmoid(mask_head(feat, w, n_fsmn)).squeeze(), aec
 
 
 def tail_flags(score, start, stop, silence, hi=0.5, lo=0.5):

@@ -157,6 +157,28 @@ def test_dfsmn_entry_points_validate_before_touching_the_device():
     assert blk(C.byref(mc)) == -1 and b"arithmetic" in lib.vadx_last_error()
     assert lib.vadx_marblenet_tail(ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, 1, 32, None, C.byref(mc)) == -1
     assert lib.vadx_frag_h2_host(ptr, 16, 32, 7, ptr, None) == -1 and b"k_order" in lib.vadx_last_error()
+    # the mask-net head keeps a chunk's activations in LDS: every dimension outside its limits is refused by name, with the limit
+    def mask(frames=51, **dims):
+        mw = _lib.DfsmnMaskWeights()
+        mw.hidden, mw.fsmn_hidden, mw.layers, mw.lorder = 128, 256, 4, 20
+        for k, val in dims.items():
+            setattr(mw, k, val)
+        return lib.vadx_dfsmn_mask_net(C.byref(mw), ptr, 1, frames, ptr, None)
+    for kw, name, limit in ((dict(frames=0), b"frames", b"[1, 64]"), (dict(frames=65), b"frames", b"[1, 64]"),
+                            (dict(hidden=0), b"hidden", b"[1, 128]"), (dict(hidden=129), b"hidden", b"[1, 128]"),
+                            (dict(fsmn_hidden=257), b"fsmn_hidden", b"[1, 256]"), (dict(layers=9), b"layers", b"[0, 8]"),
+                            (dict(lorder=0), b"lorder", b"[1, 20]"), (dict(lorder=21), b"lorder", b"[1, 20]")):
+        assert mask(**kw) == -1, kw
+        msg = lib.vadx_last_error()
+        assert b"vadx_dfsmn_mask_net: " + name + b" must" in msg and limit in msg, (kw, msg)
+    # ft_repack moves aligned 4-frame quads: both strides are multiples of 4 and cover the frames
+    rp = lambda src, dst: lib.vadx_dfsmn_ft_repack(ptr, ptr, 4, 160, 17, 1, src, dst, None)      # noqa: E731
+    for src, dst in ((32, 22), (22, 32), (32, 16), (16, 32)):
+        assert rp(src, dst) == -1 and b"multiples of 4 that cover the frames" in lib.vadx_last_error(), (src, dst)
+    # alpha_scale with the near-end-only model's constant far power [160][frames][10]: frames beyond the nt tiles are refused
+    al = lambda nt, frames: lib.vadx_dfsmn_alpha_scale(ptr, ptr, 1, nt, ptr, ptr, ptr, ptr, ptr, frames, None)      # noqa: E731
+    for nt, frames in ((1, 17), (7, 113), (1, 0)):
+        assert al(nt, frames) == -1 and b"frames out of range" in lib.vadx_last_error(), (nt, frames)
 
 
 def test_fsmn_run_refuses_a_window_longer_than_its_score_scratch(lib):

@@ -2016,9 +2016,11 @@ extern "C" int vadx_dfsmn_vote(const float *vad, int batch, int windows, int fra
 extern "C" int vadx_dfsmn_mask_net(const vadx_dfsmn_mask_weights *w, const float *feat, int chunks, int frames, float *vad,
                                    void *stream) {
     VADX_REQUIRE(w && feat && vad && chunks > 0, "vadx_dfsmn_mask_net: NULL argument");
-    VADX_REQUIRE(frames > 0 && frames <= 64, "vadx_dfsmn_mask_net: frames must be <= 64 (got %d)", frames);
-    VADX_REQUIRE(w->hidden > 0 && w->hidden <= 128 && w->fsmn_hidden > 0 && w->fsmn_hidden <= 256 && w->layers >= 0 && w->layers <= 8 &&
-                 w->lorder >= 1 && w->lorder <= 20, "vadx_dfsmn_mask_net: unsupported dims");
+    VADX_REQUIRE(frames > 0 && frames <= 64, "vadx_dfsmn_mask_net: frames must be in [1, 64] (got %d)", frames);
+    VADX_REQUIRE(w->hidden > 0 && w->hidden <= 128, "vadx_dfsmn_mask_net: hidden must be in [1, 128] (got %d)", w->hidden);
+    VADX_REQUIRE(w->fsmn_hidden > 0 && w->fsmn_hidden <= 256, "vadx_dfsmn_mask_net: fsmn_hidden must be in [1, 256] (got %d)", w->fsmn_hidden);
+    VADX_REQUIRE(w->layers >= 0 && w->layers <= 8, "vadx_dfsmn_mask_net: layers must be in [0, 8] (got %d)", w->layers);
+    VADX_REQUIRE(w->lorder >= 1 && w->lorder <= 20, "vadx_dfsmn_mask_net: lorder must be in [1, 20] (got %d)", w->lorder);
     MaskArgs p;
     p.feat = feat; p.shift = w->shift; p.scale = w->scale; p.w1 = w->linear1_w; p.b1 = w->linear1_b; p.w3 = w->linear3_w; p.b3 = w->linear3_b;
     p.vad = vad; p.T = frames; p.H = w->hidden; p.Hp = (w->hidden + 15) & ~15; p.H2p = (w->fsmn_hidden + 15) & ~15;

@@ -20,6 +20,18 @@ def ft_tiles(frames):
 
 
 STAT_PARTS = 2             # VADX_DFSMN_STAT_PARTS (include/vadx.h)
+ISTFT_MAX_FRAMES = 200     # frames the ISTFT's window_sum_inv buffer is built for (NET.__init__ :183-207): vadx_dfsmn_istft reads it up to
+                           # sample (frames - 1) * 160 + 319 and checks no bound of its own
+# vadx_dfsmn_mask_net's limits (include/vadx.h): name -> (lowest, highest)
+MASK_NET_LIMITS = dict(hidden=(1, 128), fsmn_hidden=(1, 256), layers=(0, 8), lorder=(1, 20))
+
+# front-end presets (vadx.frontend.Frontend): STFT-B (hamming 319/319/160, centre pad 159) raw complex; STFT-A (hamming 640 in 1024, hop 320)
+# + htk fbank, one per feature stream (prep 3 near / 4 AEC / 5 echo, include/vadx.h: vadx_frontend_logmel_ex)
+_INV_I16 = 1.0 / 32768.0
+STFT_B_PRESET = dict(n_fft=319, win=319, hop=160, window="hamming", variant="v1b", center=True, prep=2, k=(0.0, _INV_I16), mel=("zeros",),
+                     log_mode=0, log_floor=1e-6)
+STFT_A_PRESETS = {prep: dict(n_fft=1024, win=640, hop=320, window="hamming", variant="v1b", center=True, prep=prep, k=(1.15, _INV_I16),
+                             mel=("torchaudio", 20, 8000, None, "htk"), log_mode=0, log_floor=1e-6) for prep in (3, 4, 5)}
 
 
 def packed_stride(frames):
@@ -412,6 +424,16 @@ class DfsmnEngine:
         from . import checkpoints as _ck
         w = _ck.resolve("dfsmn", weights)
         w = {k: np.ascontiguousarray(np.asarray(v), dtype=np.float32) for k, v in w.items()}
+        # the head's dimensions, checked against the kernel's limits before anything is packed or launched
+        m = dict(_w.DFSMN_MASK)
+        m["hidden"] = w["mask.linear1.weight"].shape[0]
+        m["layers"] = len([k for k in w if k.startswith("mask.deepfsmn.") and k.endswith(".linear.weight")])
+        if m["layers"]:
+            m["fsmn_hidden"] = w["mask.deepfsmn.0.linear.weight"].shape[0]
+            m["lorder"] = w["mask.deepfsmn.0.conv1.weight"].shape[2]
+        for name, (lo, hi) in MASK_NET_LIMITS.items():
+            if not lo <= m[name] <= hi:
+                raise ValueError(f"DFSMN mask net: {name} = {m[name]} is outside vadx_dfsmn_mask_net's [{lo}, {hi}]")
         self.sub_batch = int(sub_batch)
         self.range_fallbacks = 0       # batches recomputed because the fp16 x 2 time LSTM flagged an out-of-range operand
         self.iccrn = Iccrn(w, device)
@@ -425,7 +447,7 @@ class DfsmnEngine:
         inverse_basis = t.linalg.pinv((fb * n) / hop).T * window.view(1, -1)          # [320 ch][319]
         bt = t.zeros((320, 320), dtype=t.float32)
         bt[:319, :] = inverse_basis.t()
-        max_frames = 200
+        max_frames = ISTFT_MAX_FRAMES
         out_len = (max_frames - 1) * hop + n
         ws = t.zeros(out_len, dtype=t.float32)
         wsq = window ** 2
@@ -436,20 +458,8 @@ class DfsmnEngine:
                 break
             ws[s0:s0 + ln_] += wsq[:ln_]
         self.basis_t, self.wsum_inv = bt.to(self.device), (n / (ws * hop + 1e-6)).to(self.device)
-        # front-ends: STFT-B (hamming 319/319/160, centre pad 159) raw complex; STFT-A (hamming 640 in 1024, hop 320) + htk fbank
-        inv = 1.0 / 32768.0
-        self.fe_b = _fe.Frontend(dict(n_fft=319, win=319, hop=160, window="hamming", variant="v1b", center=True, prep=2,
-                                      k=(0.0, inv), mel=("zeros",), log_mode=0, log_floor=1e-6), self.L, device=device)
-        mk = lambda prep: _fe.Frontend(dict(n_fft=1024, win=640, hop=320, window="hamming", variant="v1b", center=True, prep=prep,   # noqa: E731
-                                            k=(1.15, inv), mel=("torchaudio", 20, 8000, None, "htk"), log_mode=0, log_floor=1e-6),
-                                       self.L, device=device)
-        self.fe_a = {3: mk(3), 4: mk(4), 5: mk(5)}
-        m = dict(_w.DFSMN_MASK)
-        m["hidden"] = w["mask.linear1.weight"].shape[0]
-        m["layers"] = len([k for k in w if k.startswith("mask.deepfsmn.") and k.endswith(".linear.weight")])
-        if m["layers"]:
-            m["fsmn_hidden"] = w["mask.deepfsmn.0.linear.weight"].shape[0]
-            m["lorder"] = w["mask.deepfsmn.0.conv1.weight"].shape[2]
+        self.fe_b = _fe.Frontend(STFT_B_PRESET, self.L, device=device)
+        self.fe_a = {prep: _fe.Frontend(preset, self.L, device=device) for prep, preset in STFT_A_PRESETS.items()}
         mw = _lib.DfsmnMaskWeights()
         mw.hidden, mw.fsmn_hidden, mw.layers, mw.lorder = m["hidden"], m["fsmn_hidden"], m["layers"], m["lorder"]
         self._mask_keep = []
@@ -483,6 +493,24 @@ class DfsmnEngine:
             raise ValueError(f"near-only constants must cover [160, {self.T_B}, 10] and [2, 160, {self.T_B}]")
         self.pow_far = t.from_numpy(np.ascontiguousarray(pf)).to(self.device)
         self.far_ft = to_ft(t, t.from_numpy(np.ascontiguousarray(fc)).unsqueeze(0), self.device).data      # [nt, 2, 160, 16]
+
+    def istft(self, y_ft, n, frames):
+        """FT spectrum [2 ch x 160] of n chunks (its device data tensor) -> waveforms f32 [n, (frames - 1) * 160 + 1] (vadx_dfsmn_istft)."""
+        t = self.torch
+        if not 1 <= frames <= ISTFT_MAX_FRAMES:
+            raise ValueError(f"DFSMN ISTFT: frames = {frames} is outside [1, {ISTFT_MAX_FRAMES}], what the window_sum_inv table covers")
+        z = t.empty((n, frames, 320), dtype=t.float32, device=self.device)
+        aec = t.empty((n, (frames - 1) * 160 + 1), dtype=t.float32, device=self.device)
+        _lib.check(self.lib.vadx_dfsmn_istft(y_ft.data_ptr(), self.basis_t.data_ptr(), self.wsum_inv.data_ptr(), z.data_ptr(),
+                                             aec.data_ptr(), n, frames, _lib.stream_ptr()))
+        return aec
+
+    def mask_net(self, feat, n, frames):
+        """features f32 [n, frames, 240] (device) -> scores f32 [n, frames] (vadx_dfsmn_mask_net)."""
+        t = self.torch
+        vad = t.empty((n, frames), dtype=t.float32, device=self.device)
+        _lib.check(self.lib.vadx_dfsmn_mask_net(C.byref(self.mask), feat.data_ptr(), n, frames, vad.data_ptr(), _lib.stream_ptr()))
+        return vad
 
     def run(self, near_i16, far_i16=None, windows_per_clip=1, win_stride=None, return_aec=False):
         """near/far int16 [B, N] on the window grid -> vad f32 [B*W, 51] (each window stateless, as the reference).
@@ -547,10 +575,7 @@ class DfsmnEngine:
             _lib.check(lib.vadx_dfsmn_alpha_scale(xraw.data.data_ptr(), x4.data.data_ptr(), n, nt, *[a.data_ptr() for a in self.alpha],
                                                   None if far is not None else self.pow_far.data_ptr(), self.T_B, st))
             y = self.iccrn.forward(x4, n, self.T_B)
-            z = t.empty((n, self.T_B, 320), dtype=t.float32, device=self.device)
-            aec = t.empty((n, self.L), dtype=t.float32, device=self.device)
-            _lib.check(lib.vadx_dfsmn_istft(y.data.data_ptr(), self.basis_t.data_ptr(), self.wsum_inv.data_ptr(), z.data_ptr(),
-                                            aec.data_ptr(), n, self.T_B, st))
+            aec = self.istft(y.data, n, self.T_B)
             feat = t.empty((n, self.T_A, 240), dtype=t.float32, device=self.device)
             for prep, off in ((3, 0), (4, 80), (5, 160)):
                 fe = self.fe_a[prep]
@@ -558,8 +583,7 @@ class DfsmnEngine:
                                                        None if prep == 4 else near.data_ptr(), _lib.row_stride(near), ws, B, W,
                                                        None if prep == 4 else mean_near.data_ptr(),
                                                        None if prep == 3 else aec.data_ptr(), 240, off, feat.data_ptr(), st))
-            vad = t.empty((n, self.T_A), dtype=t.float32, device=self.device)
-            _lib.check(lib.vadx_dfsmn_mask_net(C.byref(self.mask), feat.data_ptr(), n, self.T_A, vad.data_ptr(), st))
+            vad = self.mask_net(feat, n, self.T_A)
         return vad, aec
 
     def grid(self):
