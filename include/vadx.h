@@ -51,7 +51,8 @@ extern "C" {
  * 10: new entry points only: the FSMN stream path vadx_fsmn_stream_state_bytes, vadx_fsmn_stream_windows, vadx_fsmn_stream_run.
  *     Later additions under the SAME number (additive again: nothing an ABI-10 caller links against moved, and the suite's pin of this
  *     number, tests/test_fsmn_stream_cpu.py, stays as it is): the ragged-batch entry points vadx_windows_gather, vadx_fsmn_clips_ragged,
- *     vadx_tracks_gather.  A caller that needs them checks for the symbols (dlsym), not for a number. */
+ *     vadx_tracks_gather; then MarbleNet over ragged batches: vadx_marblenet_ragged, vadx_frontend_logmel_ragged, vadx_sepconv_block_ragged,
+ *     vadx_marblenet_block2_ragged, vadx_marblenet_tail_ragged.  A caller that needs them checks for the symbols (dlsym), not for a number. */
 #define VADX_ABI_VERSION 10
 
 /* Arithmetic of the products whose one operand is a constant (every weight matrix, every DFT table) -- float32 RESULTS in all of them:
@@ -628,6 +629,68 @@ int vadx_marblenet_block2(int cin, int kernel, const float *dw0, const float *pw
 int vadx_marblenet_tail(const float *dw, const float *pw, const float *pb, const float *w6, const float *b6,
                         const float *dec_w, const float *dec_b, const float *x, float *score0, float *score1,
                         int batch, int frames, void *stream, const vadx_marblenet_cfg *cfg);
+/* ---- MarbleNet over a RAGGED batch: B clips of ANY lengths in one launch sequence, dynamic-axis mode (one window = one whole clip, so a
+ * clip's length sets its own frame count: NVIDIA_.../Inference_NVIDIA_MarbleNet_VAD_ONNX.py:130-135).  The clips lie end to end in ONE
+ * int16 vector `pcm`, NO padding and no alignment between them (the front-end reads samples as single int16 loads from clamped indices).
+ * Per clip b of n_b samples: F_b = n_b / 160 + 1 log-mel frames (the centre-padded preset) and T1_b = (F_b - 1) / 2 + 1 encoder frames
+ * (the stride-2, k 11 prologue).  Tables, all on the device (vadx.ragged.RaggedFrames builds them; every sum is checked against int32 there):
+ *   clip_off  int64 [B]      first sample of clip b in pcm           clip_len  int32 [B]   n_b
+ *   mel_first int32 [B+1]    prefix sum of F_b: clip b owns rows mel_first[b] .. of the log-mel buffer f32 [sum F][n_mels]
+ *   enc_first int32 [B+1]    prefix sum of T1_b: clip b's activations are [C][T1_b] at FLOAT offset C * enc_first[b] of every buffer
+ *                            between the launches, its scores s0 / s1 [enc_first[b] .. enc_first[b+1])
+ *   tile tables              the front-end works in 64-frame tiles, the encoder in 32-frame tiles; each has tile_first int32 [B+1] (prefix
+ *                            sum of ceil(F_b / 64) resp. ceil(T1_b / 32)) and tile_clip int32 [n_tiles] (the clip of every tile): a
+ *                            workgroup finds (clip, tile) with two uniform loads -- no search, one int per tile.
+ * Sequence on one HIP stream (a plain-C caller: INTEGRATION.md section 7):
+ *   vadx_frontend_logmel_ragged    pcm + tables -> logmel f32 [sum F][80]
+ *   vadx_sepconv_block_ragged      -> a0 f32, sum T1 * 128 floats         (block 1: the prologue)
+ *   vadx_marblenet_block2_ragged   x 3 (kernel 13, 15, 17; cin 128, 64, 64) -> sum T1 * 64 floats each
+ *   vadx_marblenet_tail_ragged     -> score0, score1 f32 [sum T1]
+ *   vadx_tracks_gather (win_floats = 1, frames_per_window = 1, win_first = enc_first) + vadx_vadpost as for any ragged batch.
+ * Every workgroup computes the very tile the rectangular launches compute for that clip alone (one device function per kernel, shared),
+ * so clip b's slice of every output is bit for bit what the one-clip call gives.  Device-side guard of all four launches: a workgroup
+ * whose table entries name a clip outside [0, B), a tile outside its clip's tiles, a negative, empty or decreasing prefix range, a range
+ * beyond the totals passed by value, or tables that disagree about the clip (tile count against frame count; T1 against F; F against
+ * clip_len) returns before its first read or write of the buffers: its rows keep what they held.  The arithmetic and the range-flag
+ * protocol are vadx_marblenet_cfg's (F16X2 raised flag: repeat the whole sequence from vadx_sepconv_block_ragged on VADX_ARITH_F32). */
+
+/* Log-mel of every clip of a ragged batch in one launch; replaces the per-file front-end of the dynamic-axis session call,
+ * NVIDIA_.../Inference_NVIDIA_MarbleNet_VAD_ONNX.py:130-147, 369-402, for B files of different lengths.  cfg / packed / mel_kb_host as
+ * for vadx_frontend_logmel (nothing in the blob depends on a window length: one blob serves every clip; cfg->frames and cfg->window_len
+ * only have to be valid).  tile_first / tile_clip: the 64-frame tile tables.  out f32 [mel_total][n_mels].  Built for cfg->fold
+ * VADX_FE_KIND_SPLIT_H2 / VADX_FE_KIND_SPLIT_B3 and the two-tap prep 1 of a centre-padded preset, no in-graph resampling.  Returns
+ * VADX_EINVAL, before any HIP call, for a NULL pointer, any other kind or prep (the message names it), clips / n_tiles / mel_total /
+ * pcm_len < 1, or counts that do not fit each other (clips <= n_tiles <= mel_total <= 64 * n_tiles). */
+int vadx_frontend_logmel_ragged(const vadx_frontend_cfg *cfg, const float *packed, const int32_t *mel_kb_host, const int16_t *pcm,
+                                int64_t pcm_len, const int64_t *clip_off, const int32_t *clip_len, const int32_t *mel_first,
+                                const int32_t *tile_first, const int32_t *tile_clip, int clips, int n_tiles, int mel_total,
+                                float *out, void *stream);
+
+/* The encoder's tables (device pointers): the 32-frame tile tables, frame_first = enc_first, src_first = mel_first (read by
+ * vadx_sepconv_block_ragged only; the other two ignore src_first / src_total). */
+typedef struct vadx_marblenet_ragged {
+    const int32_t *tile_first;    /* [clips + 1] */
+    const int32_t *tile_clip;     /* [n_tiles] */
+    const int32_t *frame_first;   /* [clips + 1], frame_first[clips] = frames_total */
+    const int32_t *src_first;     /* [clips + 1], src_first[clips] = src_total */
+    int32_t clips, n_tiles, frames_total, src_total;
+} vadx_marblenet_ragged;
+/* Ragged forms of vadx_sepconv_block (the prologue of the published layout only: depthwise k 11, stride 2, no residual; x = the
+ * time-major log-mel rows, row stride xs_t floats, channel stride 1), vadx_marblenet_block2 and vadx_marblenet_tail: the same weights,
+ * the same arithmetics, `batch` and `frames` replaced by the tables.  They replace the per-file session calls of
+ * NVIDIA_.../Inference_NVIDIA_MarbleNet_VAD_ONNX.py:130-147, 369-402 for B files of different lengths.  Each returns VADX_EINVAL,
+ * before any HIP call, for a NULL pointer or table, clips / n_tiles / frames_total < 1, counts that do not fit each other (clips <=
+ * n_tiles <= frames_total <= 32 * n_tiles; the prologue also frames_total <= src_total <= 2 * frames_total), an arithmetic other than
+ * AUTO / F32 / F16X2 (named in the message), F16X2 without range_flag, or a layer shape outside the published layout. */
+int vadx_sepconv_block_ragged(const vadx_sepconv_cfg *cfg, const float *dw_w, const float *pw_w, const float *pw_b, const float *x,
+                              int64_t xs_t, float *y, const vadx_marblenet_ragged *rt, void *stream, const vadx_marblenet_cfg *mcfg);
+int vadx_marblenet_block2_ragged(int cin, int kernel, const float *dw0, const float *pw0, const float *b0, const float *dw1,
+                                 const float *pw1, const float *b1, const float *res_w, const float *res_b, const float *x, float *y,
+                                 const vadx_marblenet_ragged *rt, void *stream, const vadx_marblenet_cfg *cfg);
+int vadx_marblenet_tail_ragged(const float *dw, const float *pw, const float *pb, const float *w6, const float *b6,
+                               const float *dec_w, const float *dec_b, const float *x, float *score0, float *score1,
+                               const vadx_marblenet_ragged *rt, void *stream, const vadx_marblenet_cfg *cfg);
+
 /* enc [B][C][T] -> softmax(Linear(C->2)) split into score0 / score1 [B][T]. */
 int vadx_frame_classifier(const float *enc, const float *dec_w, const float *dec_b, int batch, int channels,
                           int frames, float *score0, float *score1, void *stream);

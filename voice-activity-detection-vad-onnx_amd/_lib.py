@@ -48,6 +48,12 @@ class MarbleNetCfg(C.Structure):
     _fields_ = [("arithmetic", C.c_int32), ("reserved", C.c_int32), ("range_flag", C.c_void_p)]
 
 
+class MarbleNetRagged(C.Structure):
+    """vadx_marblenet_ragged (include/vadx.h): the encoder's tables of a ragged batch (device pointers) and their counts"""
+    _fields_ = [("tile_first", C.c_void_p), ("tile_clip", C.c_void_p), ("frame_first", C.c_void_p), ("src_first", C.c_void_p),
+                ("clips", C.c_int32), ("n_tiles", C.c_int32), ("frames_total", C.c_int32), ("src_total", C.c_int32)]
+
+
 class SileroCfg(C.Structure):
     """vadx_silero_cfg (include/vadx.h): per-call configuration of the Silero launches"""
     _fields_ = [("arithmetic", C.c_int32), ("sample_rate", C.c_int32), ("reserved", C.c_int32 * 2)]
@@ -205,6 +211,10 @@ SIGNATURES = {
     "vadx_frag_h2_floats": (C.c_size_t, [_I, _I]),
     "vadx_frag_h2_host": (_I, [_P, _I, _I, _I, _P, _P]),
     "vadx_marblenet_tail": (_I, [_P] * 10 + [_I, _I, _P, C.POINTER(MarbleNetCfg)]),
+    "vadx_frontend_logmel_ragged": (_I, [C.POINTER(FrontendCfg), _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "vadx_sepconv_block_ragged": (_I, [C.POINTER(SepConvCfg), _P, _P, _P, _P, _L, _P, C.POINTER(MarbleNetRagged), _P, C.POINTER(MarbleNetCfg)]),
+    "vadx_marblenet_block2_ragged": (_I, [_I, _I] + [_P] * 10 + [C.POINTER(MarbleNetRagged), _P, C.POINTER(MarbleNetCfg)]),
+    "vadx_marblenet_tail_ragged": (_I, [_P] * 10 + [C.POINTER(MarbleNetRagged), _P, C.POINTER(MarbleNetCfg)]),
     "vadx_frame_classifier": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "vadx_dfsmn_frame_stats": (_I, [C.POINTER(FtView), C.POINTER(FtView), _I, _I, _P, _P]),
     "vadx_dfsmn_stats_merge": (_I, [_P, _P, _I, _P, _P]),

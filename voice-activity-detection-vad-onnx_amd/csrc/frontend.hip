@@ -1273,6 +1273,42 @@ __global__ __launch_bounds__(SQ_THREADS, 2) void frontend_split_kernel(
     FE_TILE64_LADDER(d, k.tile, split_tile<SC, MT>(d, P, k.win, mean, f0, k.out_win, fsmem));
 }
 
+// The split kernel over a RAGGED batch (include/vadx.h: vadx_frontend_logmel_ragged): one workgroup per 64-frame tile of ANY clip, one
+// window = one whole clip.  tile_clip[blockIdx.x] names the clip and tile_first[b] its first tile (two uniform loads; a search of the
+// prefix would save a table of one int per 64 frames = 10 240 samples); the clip's samples are pcm[clip_off[b] .. + clip_len[b]), its
+// frames = clip_len / hop + 1 rows of `out` from row mel_first[b].  split_tile's sample loads are scalar int16 loads from clamped
+// indices, so a clip may start at any sample.  A workgroup whose entries do not describe a tile inside pcm and out returns before its
+// first read or write of them.
+struct FeRagged {
+    const int *tile_first, *tile_clip, *clip_len, *mel_first;
+    const long long *clip_off;
+    long long pcm_len;
+    int clips, n_tiles, mel_total;
+};
+template <typename SC>
+__global__ __launch_bounds__(SQ_THREADS, 2) void frontend_split_ragged_kernel(
+    Dev d, const float *__restrict__ P, const int16_t *__restrict__ pcm, FeRagged r, float *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char fsmem[];
+    const int tile = blockIdx.x;
+    if (tile >= r.n_tiles) return;
+    const int b = r.tile_clip[tile];
+    if (b < 0 || b >= r.clips) return;
+    const int first = r.tile_first[b], next = r.tile_first[b + 1], m0 = r.mel_first[b], m1 = r.mel_first[b + 1], len = r.clip_len[b];
+    const long long off = r.clip_off[b];
+    if (first < 0 || tile < first || tile >= next || m0 < 0 || m1 <= m0 || m1 > r.mel_total) return;
+    if (len < 1 || off < 0 || off > r.pcm_len - len) return;
+    const int frames = len / d.hop + 1;
+    if (frames != m1 - m0 || next - first != (frames + TF_FOLD - 1) / TF_FOLD) return;      // the tables disagree about this clip
+    Dev dc = d;                     // this clip's geometry in the uniform fields split_tile and mel_phase read
+    dc.window_len = len; dc.frames = frames;
+    dc.tiles64 = frames / TF_FOLD;
+    dc.tail_mt = (frames - dc.tiles64 * TF_FOLD + 15) / 16;
+    if (dc.tail_mt == 4) { dc.tiles64 += 1; dc.tail_mt = 0; }
+    const int16_t *win = pcm + off;
+    float *out_win = out + (size_t)m0 * d.out_stride;
+    FE_TILE64_LADDER(dc, tile - first, split_tile<SC, MT>(dc, P, win, 0.f, f0, out_win, fsmem));
+}
+
 __global__ __launch_bounds__(THREADS, 4) void frontend_logmel_kernel(
     Dev d, const float *__restrict__ P, const int16_t *__restrict__ audio, long long row_stride,
     long long win_stride, int windows_per_clip, const float *__restrict__ means, float *__restrict__ out,
@@ -1607,6 +1643,42 @@ extern "C" int vadx_frontend_logmel_means(const vadx_frontend_cfg *cfg, const fl
                                           int windows_per_clip, const float *means, float *out, void *stream) {
     VADX_REQUIRE(means, "vadx_frontend_logmel_means: NULL means");
     return logmel_impl(cfg, packed, mel_kb_host, audio, row_stride, win_stride, batch, windows_per_clip, const_cast<float *>(means), true, out, stream);
+}
+
+// The split kernel over clips of any lengths (one window = one clip, frames = clip_len / hop + 1: the centre-padded two-tap preset of
+// the MarbleNet export); cfg->frames and cfg->window_len are not read by the launch -- the tables say them per clip
+extern "C" int vadx_frontend_logmel_ragged(const vadx_frontend_cfg *cfg, const float *packed, const int32_t *mel_kb_host, const int16_t *pcm,
+                                           int64_t pcm_len, const int64_t *clip_off, const int32_t *clip_len, const int32_t *mel_first,
+                                           const int32_t *tile_first, const int32_t *tile_clip, int clips, int n_tiles, int mel_total,
+                                           float *out, void *stream) {
+    static const char who[] = "vadx_frontend_logmel_ragged";
+    VADX_REQUIRE(cfg && packed && mel_kb_host && pcm && clip_off && clip_len && mel_first && tile_first && tile_clip && out, "%s: NULL argument", who);
+    VADX_REQUIRE(is_split(cfg->fold), "%s: DFT product kind %d is not built for ragged batches (VADX_FE_KIND_SPLIT_H2 = %d or VADX_FE_KIND_SPLIT_B3 = %d)",
+                 who, cfg->fold, (int)K_SPLIT_H2, (int)K_SPLIT_B3);
+    VADX_REQUIRE(cfg->prep == 1 && cfg->center_pad > 0, "%s: prep %d (centre pad %d) is not built for ragged batches: the two-tap prep 1 of a "
+                 "centre-padded preset only (no in-graph resampling)", who, cfg->prep, cfg->center_pad);
+    VADX_REQUIRE(clips >= 1 && n_tiles >= 1 && mel_total >= 1 && pcm_len >= 1, "%s: clips=%d n_tiles=%d mel_total=%d pcm_len=%lld must be positive", who,
+                 clips, n_tiles, mel_total, (long long)pcm_len);
+    // every clip has at least one frame and every tile at least one of its <= 64 frames
+    VADX_REQUIRE(clips <= n_tiles && n_tiles <= mel_total && (long long)mel_total <= (long long)n_tiles * TF_FOLD,
+                 "%s: clips=%d, n_tiles=%d and mel_total=%d do not fit each other (clips <= n_tiles <= mel_total <= %d * n_tiles)", who, clips, n_tiles,
+                 mel_total, TF_FOLD);
+    Dev d;
+    VADX_REQUIRE(derive(cfg, &d) == 0, "%s: unsupported geometry", who);
+    for (int mt = 0; mt < d.nmt; ++mt) { d.mel_kb_lo[mt] = mel_kb_host[2 * mt]; d.mel_kb_hi[mt] = mel_kb_host[2 * mt + 1]; }
+    const size_t slds = split_lds_bytes(&d);
+    VADX_REQUIRE(slds <= 160 * 1024, "%s: geometry needs %zu B of LDS", who, slds);
+    const FeRagged r{tile_first, tile_clip, clip_len, mel_first, reinterpret_cast<const long long *>(clip_off), (long long)pcm_len, clips, n_tiles, mel_total};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (d.fold == K_SPLIT_B3) {
+        VADX_DYN_LDS(frontend_split_ragged_kernel<vadx::SchemeB3>, 160 * 1024);
+        hipLaunchKernelGGL(frontend_split_ragged_kernel<vadx::SchemeB3>, dim3((unsigned)n_tiles), dim3(SQ_THREADS), slds, st, d, packed, pcm, r, out);
+    } else {
+        VADX_DYN_LDS(frontend_split_ragged_kernel<vadx::SchemeH2>, 160 * 1024);
+        hipLaunchKernelGGL(frontend_split_ragged_kernel<vadx::SchemeH2>, dim3((unsigned)n_tiles), dim3(SQ_THREADS), slds, st, d, packed, pcm, r, out);
+    }
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
 }
 
 // DFSMN feature streams: same fused kernel, sources = int16 near window (+ its scaled mean) and/or the float AEC

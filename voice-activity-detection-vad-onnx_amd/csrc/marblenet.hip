@@ -101,22 +101,71 @@ __device__ __forceinline__ void gemm8_h2(const vadx::QLayerArgs &a, float &amax)
     for (int mt = 0; mt < 2; ++mt) vadx::qlayer_store<SC, 2, OUT_PLANES>(a, wave, mt, SC::join(hi[0][mt], lo[0][mt]), lane, amax);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Ragged launches (include/vadx.h: vadx_marblenet_ragged).  The three kernels below take a compile-time flag RG.  RG = false is the
+// rectangular launch: blockIdx.x -> (clip, tile) with a uniform tile count, every clip T frames of a [B][C][T] buffer; its trailing
+// argument is an empty struct and nothing about it reaches the code.  RG = true: one workgroup per 32-frame tile of ANY clip;
+// tile_clip[blockIdx.x] names the clip and tile_first[b] its first tile -- two uniform loads instead of a search of the prefix (the
+// table is one int per 32 frames, 1 / 2048 of the smallest activation it describes).  Clip b's activations are [C][T_b] at float offset
+// C * dst_first[b]; the prologue reads the time-major log-mel rows src_first[b] .. of clip b.  A workgroup whose entries do not
+// describe a tile inside the buffers returns before its first read or write of them (ok = false).
+// ---------------------------------------------------------------------------------------------
+struct Ragged {
+    const int *tile_first, *tile_clip, *dst_first, *src_first;      // src_first: the prologue only (elsewhere = dst_first)
+    int clips, n_tiles, dst_total, src_total;
+};
+struct NoTables {};
+template <bool RG> struct TablesOf { typedef NoTables type; };
+template <> struct TablesOf<true> { typedef Ragged type; };
+struct RaggedTile { bool ok; int t0, T, T_src; long long first, src_row; };
+template <bool STRIDE2>
+__device__ __forceinline__ RaggedTile ragged_tile(const Ragged &r) {
+    RaggedTile k;
+    k.ok = false; k.t0 = 0; k.T = 0; k.T_src = 0; k.first = 0; k.src_row = 0;
+    const int tile = blockIdx.x;
+    if (tile >= r.n_tiles) return k;
+    const int b = r.tile_clip[tile];
+    if (b < 0 || b >= r.clips) return k;
+    const int first = r.tile_first[b], next = r.tile_first[b + 1], d0 = r.dst_first[b], d1 = r.dst_first[b + 1];
+    if (first < 0 || tile < first || tile >= next || d0 < 0 || d1 <= d0 || d1 > r.dst_total) return k;
+    const int T = d1 - d0;
+    if (next - first != (T + TILE - 1) / TILE) return k;            // the two tables disagree about this clip
+    int T_src = T;
+    long long src_row = d0;
+    if (STRIDE2) {
+        const int s0 = r.src_first[b], s1 = r.src_first[b + 1];
+        if (s0 < 0 || s1 <= s0 || s1 > r.src_total || T != (s1 - s0 - 1) / 2 + 1) return k;
+        T_src = s1 - s0; src_row = s0;
+    }
+    k.ok = true; k.t0 = (tile - first) * TILE; k.T = T; k.T_src = T_src; k.first = d0; k.src_row = src_row;
+    return k;
+}
+
 // AR = 2: the prologue form only (depthwise, no residual branch, 128 filters): filter -> split pass -> gemm8_h2 (fp16 x 2 split products)
-template <int KT, int DT, int ST, int AR = 0>
+// RG (instantiated for the prologue <11, 1, 2> only): T_in / T_out come from the tables, x is time-major with row stride xs_t
+template <int KT, int DT, int ST, int AR = 0, bool RG = false>
 __global__ __launch_bounds__(THREADS, 2) void sepconv_block_kernel(
     Cfg c, const float *__restrict__ dw_w, const float *__restrict__ pw_w, const float *__restrict__ pw_b,
     const float *__restrict__ res_w, const float *__restrict__ res_b, const float *__restrict__ x,
     long long xs_b, long long xs_c, long long xs_t, int T_in, const float *__restrict__ xres,
-    float *__restrict__ y, int T_out, int tiles, unsigned *__restrict__ range_flag) {
+    float *__restrict__ y, int T_out, int tiles, unsigned *__restrict__ range_flag, const typename TablesOf<RG>::type rg) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int IN_LD = c.in_ld;
     float *IN = lds, *D = IN + c.cinp * IN_LD, *OUT = c.out_alias ? IN : D + (c.has_dw ? c.cinp * A_LD : 0), *RIN = OUT + c.coutp * A_LD,
           *ROUT = RIN + c.cresp * A_LD;           // (out_alias implies no residual branch: RIN / ROUT are unused then)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.x / tiles, t0 = (blockIdx.x - b * tiles) * TILE;
+    int b, t0;
+    long long first = 0, src_off = 0;           // RG: the clip's first output frame in the packed buffers / first float in x
+    if constexpr (RG) {
+        const RaggedTile k = ragged_tile<true>(rg);
+        if (!k.ok) return;
+        b = 0; t0 = k.t0; T_in = k.T_src; T_out = k.T; first = k.first; src_off = k.src_row * xs_t;
+    } else {
+        b = blockIdx.x / tiles; t0 = (blockIdx.x - b * tiles) * TILE;
+    }
     const int K = KT ? KT : c.k, DIL = KT ? DT : c.dil, STR = KT ? ST : c.stride;
     const int width = (TILE - 1) * STR + (K - 1) * DIL + 1;
-    const float *xb = x + (long long)b * xs_b;
+    const float *xb = x + (RG ? src_off : (long long)b * xs_b);
     const int tin0 = t0 * STR - c.pad;
     if (xs_c == 1) {            // time-major source (front-end output): channel fastest -> lane = channel, wave = time
         for (int j0 = 0; j0 < width; j0 += 4 * (THREADS / 64)) {
@@ -233,7 +282,7 @@ __global__ __launch_bounds__(THREADS, 2) void sepconv_block_kernel(
         layer<2, false>(r);
     }
     __syncthreads();
-    float *yb = y + (long long)b * c.cout * T_out;
+    float *yb = y + (RG ? first * c.cout : (long long)b * c.cout * T_out);
     for (int e = tid; e < c.cout * TILE; e += THREADS) {
         const int ch = e / TILE, m = e - ch * TILE;
         if (t0 + m < T_out) {
@@ -463,13 +512,22 @@ __device__ __forceinline__ void kmul(const typename KPreOf<AR>::type &p, int kdi
     else kgemm<MT>(p, kdim, act, lda, acol0, dst, ldd, bias, relu);
 }
 
-template <int K, int AR>
+template <int K, int AR, bool RG = false>
 __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
     Blk2 c, const float *__restrict__ dw0, const float *__restrict__ pw0, const float *__restrict__ b0,
     const float *__restrict__ dw1, const float *__restrict__ pw1, const float *__restrict__ b1,
     const float *__restrict__ rw, const float *__restrict__ rb, const float *__restrict__ x, float *__restrict__ y, int tiles,
-    unsigned *__restrict__ range_flag) {
+    unsigned *__restrict__ range_flag, const typename TablesOf<RG>::type rg) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    int b, t0;
+    long long first = 0;                        // RG: the clip's first frame in the packed buffers; c.T becomes the clip's frame count
+    if constexpr (RG) {
+        const RaggedTile k = ragged_tile<false>(rg);
+        if (!k.ok) return;
+        b = 0; t0 = k.t0; c.T = k.T; first = k.first;
+    } else {
+        b = blockIdx.x / tiles; t0 = (blockIdx.x - b * tiles) * TILE;
+    }
     typedef typename KPreOf<AR>::type KP;
     float amax = 0.f;
     constexpr int PAD = (K - 1) / 2, WIN0 = W1 + K - 1;
@@ -478,8 +536,7 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
     float *D0 = IN, *D1 = IN, *OUT = H1;
     unsigned char *PL = reinterpret_cast<unsigned char *>(ROUT + c.c2 * A_LD);      // AR = 3: operand planes [8 k-groups][<= 48 columns][8] x 2
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.x / tiles, t0 = (blockIdx.x - b * tiles) * TILE;
-    const float *xb = x + (long long)b * c.cin * c.T;
+    const float *xb = x + (RG ? first * c.cin : (long long)b * c.cin * c.T);
     const int tin0 = t0 - 2 * PAD;
     const KP wres = kpre<AR>(rw, c.cinp);                    // in flight while the input tile is staged
     // ---- stage the block input (channel-first source: lane = time, wave = channel), unconditional clamped loads
@@ -582,7 +639,7 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
         kmul<AR, 2>(wpw1, c.c1, D1, A_LD, 0, OUT, A_LD, b1, false, amax);
     }
     __syncthreads();
-    float *yb = y + (long long)b * c.c2 * c.T;
+    float *yb = y + (RG ? first * c.c2 : (long long)b * c.c2 * c.T);
     for (int e = tid; e < c.c2 * TILE; e += THREADS) {
         const int ch = e / TILE, m = e - ch * TILE;
         if (t0 + m < c.T) yb[(long long)ch * c.T + t0 + m] = fmaxf(OUT[ch * A_LD + m] + ROUT[ch * A_LD + m], 0.f);
@@ -602,20 +659,29 @@ struct Tail { int cin, cmid, k, dil, in_ld, T; };
 // needs a transposing split pass (item = (8 channels, frame): eight conflict-free reads, 24 VALU, one 16-byte store per plane into the dead
 // input tile's place); block 5's conv takes the weights as its A operand and stores its ReLU output straight into block 6's B planes
 // [channel / 8][frame][8] (8-byte stores, in H's place), block 6 takes the activations as A and stores float32 rows for the decoder.
-template <int AR>
+template <int AR, bool RG = false>
 __global__ __launch_bounds__(THREADS, 6) void marblenet_tail_kernel(
     Tail c, const float *__restrict__ dw, const float *__restrict__ pw, const float *__restrict__ pb,
     const float *__restrict__ w6, const float *__restrict__ b6, const float *__restrict__ dec_w, const float *__restrict__ dec_b,
-    const float *__restrict__ x, float *__restrict__ s0, float *__restrict__ s1, int tiles, unsigned *__restrict__ range_flag) {
+    const float *__restrict__ x, float *__restrict__ s0, float *__restrict__ s1, int tiles, unsigned *__restrict__ range_flag,
+    const typename TablesOf<RG>::type rg) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    int b, t0;
+    long long first = 0;                        // RG: the clip's first frame in the packed buffers; c.T becomes the clip's frame count
+    if constexpr (RG) {
+        const RaggedTile k = ragged_tile<false>(rg);
+        if (!k.ok) return;
+        b = 0; t0 = k.t0; c.T = k.T; first = k.first;
+    } else {
+        b = blockIdx.x / tiles; t0 = (blockIdx.x - b * tiles) * TILE;
+    }
     constexpr int K = 29, DIL = 2, PAD = 28, WIN0 = TILE + 2 * PAD;
     const int IN_LD = c.in_ld;
     float amax = 0.f;
     float *IN = lds, *D = IN + c.cin * IN_LD, *H = D + c.cin * A_LD, *OUT = IN;
     float *red = D;                                 // [16 parts][32 frames][2] once D is dead
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.x / tiles, t0 = (blockIdx.x - b * tiles) * TILE;
-    const float *xb = x + (long long)b * c.cin * c.T;
+    const float *xb = x + (RG ? first * c.cin : (long long)b * c.cin * c.T);
     const int tin0 = t0 - PAD;
     for (int ch0 = 0; ch0 < c.cin; ch0 += 4 * (THREADS / 64)) {
         float v[4][2];
@@ -693,8 +759,8 @@ __global__ __launch_bounds__(THREADS, 6) void marblenet_tail_kernel(
 #pragma unroll
         for (int part = 0; part < THREADS / 32; ++part) { z0 += red[(part * TILE + tid) * 2]; z1 += red[(part * TILE + tid) * 2 + 1]; }
         const float mx = fmaxf(z0, z1), e0 = expf(z0 - mx), e1 = expf(z1 - mx), inv = 1.0f / (e0 + e1);
-        s0[(long long)b * c.T + t0 + tid] = e0 * inv;
-        s1[(long long)b * c.T + t0 + tid] = e1 * inv;
+        s0[(RG ? first : (long long)b * c.T) + t0 + tid] = e0 * inv;
+        s1[(RG ? first : (long long)b * c.T) + t0 + tid] = e1 * inv;
     }
     if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(range_flag, amax);
 }
@@ -723,6 +789,33 @@ __global__ void frame_classifier_kernel(const float *__restrict__ enc, const flo
 
 using namespace vadx::marblenet;
 
+// the derived fields of a Cfg whose shape fields are set and checked: the halo tile's row stride and whether the output overwrites it
+static void finish_cfg(Cfg *c) {
+    const int width = (TILE - 1) * c->stride + (c->k - 1) * c->dil + 1;
+    c->in_ld = c->has_dw ? (((width + 7) & ~7) + 4) : A_LD;      // % 8 == 4; a plain 1x1 block feeds IN straight to the GEMM
+    c->out_alias = out_aliases_in(c->cinp, c->coutp, c->cresp, c->in_ld, c->has_dw) ? 1 : 0;
+}
+// bytes of the fp16 x 2 prologue's operand planes behind D
+static size_t prologue_plane_bytes(const Cfg &c) { return (size_t)((c.cinp + 31) / 32) * 4 * TILE * 16 * 2; }
+// the fused block's / the tail's geometry and LDS (the rectangular and the ragged entry points launch the same tiles)
+static Blk2 make_blk2(int cin, int kernel, int frames) {
+    Blk2 c;
+    c.cin = cin; c.cinp = (cin + 15) & ~15; c.c1 = 64; c.c2 = 64; c.T = frames;
+    const int width = W1 + kernel - 1;
+    c.in_ld = width + ((4 - width % 8) + 8) % 8;             // smallest row stride >= width with stride % 8 == 4
+    return c;
+}
+static size_t blk2_lds(const Blk2 &c, bool planes) {
+    return ((size_t)c.cinp * c.in_ld + (size_t)c.c1 * H_LD + (size_t)c.c2 * A_LD) * sizeof(float) + (planes ? 2 * 8 * W1 * 16 : 0);
+}
+static Tail make_tail(int frames) {
+    Tail c;
+    c.cin = 64; c.cmid = 128; c.k = 29; c.dil = 2; c.T = frames;
+    c.in_ld = ((TILE + 56 + 7) & ~7) + 4;
+    return c;
+}
+static size_t tail_lds(const Tail &c) { return ((size_t)c.cin * c.in_ld + (size_t)c.cin * A_LD + (size_t)c.cmid * A_LD) * sizeof(float); }
+
 extern "C" int vadx_sepconv_block(const vadx_sepconv_cfg *cfg, const float *dw_w, const float *pw_w, const float *pw_b,
                                   const float *res_w, const float *res_b, const float *x, int64_t xs_b, int64_t xs_c,
                                   int64_t xs_t, int t_in, const float *xres, float *y, int batch, int t_out, void *stream,
@@ -740,15 +833,13 @@ extern "C" int vadx_sepconv_block(const vadx_sepconv_cfg *cfg, const float *dw_w
                  "vadx_sepconv_block: channels must be in [1,128]");
     VADX_REQUIRE(c.k >= 1 && c.stride >= 1 && c.dil >= 1 && (TILE - 1) * c.stride + (c.k - 1) * c.dil + 1 <= IN_LD_MAX,
                  "vadx_sepconv_block: receptive field of a 32-frame tile exceeds %d samples", IN_LD_MAX);
-    {   const int width = (TILE - 1) * c.stride + (c.k - 1) * c.dil + 1;
-        c.in_ld = c.has_dw ? (((width + 7) & ~7) + 4) : A_LD; }      // % 8 == 4; a plain 1x1 block feeds IN straight to the GEMM
-    c.out_alias = out_aliases_in(c.cinp, c.coutp, c.cresp, c.in_ld, c.has_dw) ? 1 : 0;
+    finish_cfg(&c);
     size_t lds_bytes = lds_floats(c.cinp, c.coutp, c.cresp, c.in_ld, c.has_dw) * sizeof(float);
     if (ar == vadx::VADX_AR_H2) {
         VADX_REQUIRE(flag && c.has_dw && !c.cres && c.out_alias && c.coutp == 128 && c.k == 11 && c.dil == 1 && c.stride == 2,
                      "vadx_sepconv_block: F16X2 is built for the MarbleNet prologue (depthwise k 11 stride 2, 128 filters, no residual; pw_w from "
                      "vadx_frag_h2_host VADX_H2_K_PLAIN) and needs mcfg->range_flag");
-        lds_bytes += (size_t)((c.cinp + 31) / 32) * 4 * TILE * 16 * 2;      // the operand planes behind D
+        lds_bytes += prologue_plane_bytes(c);
     }
     VADX_REQUIRE(c.has_dw ? dw_w != nullptr : (c.k == 1 && c.stride == 1), "vadx_sepconv_block: plain conv must be k=1, stride 1");
     VADX_REQUIRE(!c.cres || (res_w && res_b && xres), "vadx_sepconv_block: residual branch needs res_w/res_b/xres");
@@ -765,7 +856,7 @@ extern "C" int vadx_sepconv_block(const vadx_sepconv_cfg *cfg, const float *dw_w
         VADX_DYN_LDS((sepconv_block_kernel<__VA_ARGS__>), 128 * 1024);                                                          \
         hipLaunchKernelGGL((sepconv_block_kernel<__VA_ARGS__>), dim3((unsigned)(batch * tiles)), dim3(THREADS),                 \
                            lds_bytes, static_cast<hipStream_t>(stream), c, dw_w, pw_w, pw_b, res_w, res_b, x,                   \
-                           (long long)xs_b, (long long)xs_c, (long long)xs_t, t_in, xres, y, t_out, tiles, flag);                \
+                           (long long)xs_b, (long long)xs_c, (long long)xs_t, t_in, xres, y, t_out, tiles, flag, NoTables{});    \
     } while (0)
     // the depthwise shapes of the published MarbleNet 3x2x64 get compile-time FIRs; anything else runs the generic kernel
     if (ar == vadx::VADX_AR_H2) SEPCONV_LAUNCH(11, 1, 2, 2);
@@ -792,20 +883,18 @@ extern "C" int vadx_marblenet_block2(int cin, int kernel, const float *dw0, cons
     unsigned *flag = cfg ? static_cast<unsigned *>(cfg->range_flag) : nullptr;
     VADX_REQUIRE((cin == 64 || cin == 128) && (kernel == 13 || kernel == 15 || kernel == 17) && batch > 0 && frames > 0,
                  "vadx_marblenet_block2: built for the published MarbleNet 3x2x64 residual blocks (cin 64/128, 64 filters, kernel 13/15/17)");
-    Blk2 c;
-    c.cin = cin; c.cinp = (cin + 15) & ~15; c.c1 = 64; c.c2 = 64; c.T = frames;
-    const int width = W1 + kernel - 1;
-    c.in_ld = width + ((4 - width % 8) + 8) % 8;             // smallest row stride >= width with stride % 8 == 4
+    const Blk2 c = make_blk2(cin, kernel, frames);
     const int tiles = (frames + TILE - 1) / TILE;
     VADX_REQUIRE((long long)batch * tiles < (1LL << 31), "vadx_marblenet_block2: too many tiles");
     const bool planes = ar == vadx::VADX_AR_H2 && cin == 64;      // the plane form (AR = 3): 12 KB more, still three workgroups per CU
-    const size_t lds = ((size_t)c.cinp * c.in_ld + (size_t)c.c1 * H_LD + (size_t)c.c2 * A_LD) * sizeof(float) + (planes ? 2 * 8 * W1 * 16 : 0);
+    const size_t lds = blk2_lds(c, planes);
     VADX_REQUIRE(c.cinp * c.in_ld >= c.c1 * A_LD, "vadx_marblenet_block2: the depthwise-1 output does not fit the input region");
 #define BLK2_LAUNCH(KK, AR)                                                                                                    \
     do {                                                                                                                       \
         VADX_DYN_LDS((jasper_block2_kernel<KK, AR>), 128 * 1024);                                                              \
         hipLaunchKernelGGL((jasper_block2_kernel<KK, AR>), dim3((unsigned)(batch * tiles)), dim3(THREADS), lds,                \
-                           static_cast<hipStream_t>(stream), c, dw0, pw0, b0, dw1, pw1, b1, res_w, res_b, x, y, tiles, flag);   \
+                           static_cast<hipStream_t>(stream), c, dw0, pw0, b0, dw1, pw1, b1, res_w, res_b, x, y, tiles, flag,    \
+                           NoTables{});                                                                                        \
     } while (0)
     if (planes) {
         if (kernel == 13) BLK2_LAUNCH(13, 3);
@@ -835,20 +924,145 @@ extern "C" int vadx_marblenet_tail(const float *dw, const float *pw, const float
     VADX_REQUIRE(ar != vadx::VADX_AR_H2 || cfg->range_flag, "vadx_marblenet_tail: F16X2 needs cfg->range_flag (two device words)");
     unsigned *flag = cfg ? static_cast<unsigned *>(cfg->range_flag) : nullptr;
     VADX_REQUIRE(batch > 0 && frames > 0, "vadx_marblenet_tail: bad shape");
-    Tail c;
-    c.cin = 64; c.cmid = 128; c.k = 29; c.dil = 2; c.T = frames;
-    c.in_ld = ((TILE + 56 + 7) & ~7) + 4;
+    const Tail c = make_tail(frames);
     const int tiles = (frames + TILE - 1) / TILE;
     VADX_REQUIRE((long long)batch * tiles < (1LL << 31), "vadx_marblenet_tail: too many tiles");
-    const size_t lds = ((size_t)c.cin * c.in_ld + (size_t)c.cin * A_LD + (size_t)c.cmid * A_LD) * sizeof(float);
+    const size_t lds = tail_lds(c);
     if (ar == vadx::VADX_AR_H2) {
         VADX_DYN_LDS(marblenet_tail_kernel<2>, 128 * 1024);
         hipLaunchKernelGGL(marblenet_tail_kernel<2>, dim3((unsigned)(batch * tiles)), dim3(THREADS), lds, static_cast<hipStream_t>(stream),
-                           c, dw, pw, pb, w6, b6, dec_w, dec_b, x, score0, score1, tiles, flag);
+                           c, dw, pw, pb, w6, b6, dec_w, dec_b, x, score0, score1, tiles, flag, NoTables{});
     } else {
         VADX_DYN_LDS(marblenet_tail_kernel<0>, 128 * 1024);
         hipLaunchKernelGGL(marblenet_tail_kernel<0>, dim3((unsigned)(batch * tiles)), dim3(THREADS), lds, static_cast<hipStream_t>(stream),
-                           c, dw, pw, pb, w6, b6, dec_w, dec_b, x, score0, score1, tiles, flag);
+                           c, dw, pw, pb, w6, b6, dec_w, dec_b, x, score0, score1, tiles, flag, NoTables{});
+    }
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+// ---- ragged launches: the same tiles, (clip, tile) from the tables of a vadx_marblenet_ragged
+// Host-side checks shared by the three entry points (`who` names the caller in the message); fills the device-side table struct
+static int ragged_tables(const char *who, const vadx_marblenet_ragged *rt, bool with_src, Ragged *r) {
+    VADX_REQUIRE(rt && rt->tile_first && rt->tile_clip && rt->frame_first && (!with_src || rt->src_first), "%s: NULL table", who);
+    VADX_REQUIRE(rt->clips >= 1 && rt->n_tiles >= 1 && rt->frames_total >= 1, "%s: clips=%d n_tiles=%d frames_total=%d must be positive", who,
+                 rt->clips, rt->n_tiles, rt->frames_total);
+    // every clip has at least one frame and every tile at least one of its <= 32 frames
+    VADX_REQUIRE(rt->clips <= rt->n_tiles && rt->n_tiles <= rt->frames_total && (long long)rt->frames_total <= (long long)rt->n_tiles * TILE,
+                 "%s: clips=%d, n_tiles=%d and frames_total=%d do not fit each other (clips <= n_tiles <= frames_total <= %d * n_tiles)", who,
+                 rt->clips, rt->n_tiles, rt->frames_total, TILE);
+    // T1 = (F - 1) / 2 + 1 per clip, so sum T1 <= sum F <= 2 * sum T1
+    VADX_REQUIRE(!with_src || (rt->src_total >= rt->frames_total && (long long)rt->src_total <= 2LL * rt->frames_total),
+                 "%s: src_total=%d does not fit frames_total=%d (the stride-2 prologue: frames_total <= src_total <= 2 * frames_total)", who,
+                 rt->src_total, rt->frames_total);
+    r->tile_first = rt->tile_first; r->tile_clip = rt->tile_clip; r->dst_first = rt->frame_first;
+    r->src_first = with_src ? rt->src_first : rt->frame_first;
+    r->clips = rt->clips; r->n_tiles = rt->n_tiles; r->dst_total = rt->frames_total; r->src_total = with_src ? rt->src_total : rt->frames_total;
+    return VADX_OK;
+}
+// AUTO / F32 -> VADX_AR_F32, F16X2 (with a flag) -> VADX_AR_H2, anything else refused by name
+static int ragged_arith(const char *who, const vadx_marblenet_cfg *cfg, int *ar, unsigned **flag) {
+    *ar = vadx::arith_internal(cfg ? cfg->arithmetic : VADX_ARITH_AUTO, vadx::VADX_AR_F32);
+    VADX_REQUIRE(*ar == vadx::VADX_AR_F32 || *ar == vadx::VADX_AR_H2, "%s: arithmetic %d is not built: AUTO / F32 (fragment-major weights) or F16X2 "
+                 "(vadx_frag_h2_host weights)", who, cfg ? cfg->arithmetic : VADX_ARITH_AUTO);
+    *flag = cfg ? static_cast<unsigned *>(cfg->range_flag) : nullptr;
+    VADX_REQUIRE(*ar != vadx::VADX_AR_H2 || *flag, "%s: F16X2 needs cfg->range_flag (two device words)", who);
+    return VADX_OK;
+}
+
+extern "C" int vadx_sepconv_block_ragged(const vadx_sepconv_cfg *cfg, const float *dw_w, const float *pw_w, const float *pw_b, const float *x,
+                                         int64_t xs_t, float *y, const vadx_marblenet_ragged *rt, void *stream, const vadx_marblenet_cfg *mcfg) {
+    static const char who[] = "vadx_sepconv_block_ragged";
+    VADX_REQUIRE(cfg && dw_w && pw_w && pw_b && x && y, "%s: NULL argument", who);
+    int ar;
+    unsigned *flag;
+    Ragged r;
+    if (int rc = ragged_arith(who, mcfg, &ar, &flag)) return rc;
+    if (int rc = ragged_tables(who, rt, true, &r)) return rc;
+    VADX_REQUIRE(cfg->depthwise && cfg->kernel == 11 && cfg->stride == 2 && cfg->dilation == 1 && cfg->residual_cin == 0 && cfg->cin > 0 &&
+                 cfg->cin <= MAXC && cfg->cout > 0 && cfg->cout <= MAXC && xs_t >= cfg->cin,
+                 "%s: built for the MarbleNet prologue (depthwise k 11 stride 2, no residual, <= 128 channels) on time-major rows of xs_t >= cin floats", who);
+    Cfg c;
+    c.cin = cfg->cin; c.cout = cfg->cout; c.k = 11; c.stride = 2; c.dil = 1; c.has_dw = 1; c.cres = 0; c.relu = cfg->relu ? 1 : 0;
+    c.pad = 5;
+    c.cinp = (c.cin + 15) & ~15; c.coutp = (c.cout + 15) & ~15; c.cresp = 0;
+    finish_cfg(&c);
+    size_t lds_bytes = lds_floats(c.cinp, c.coutp, c.cresp, c.in_ld, c.has_dw) * sizeof(float);
+    if (ar == vadx::VADX_AR_H2) {
+        VADX_REQUIRE(c.out_alias && c.coutp == 128, "%s: F16X2 needs 128 filters (pw_w from vadx_frag_h2_host VADX_H2_K_PLAIN)", who);
+        lds_bytes += prologue_plane_bytes(c);
+        VADX_DYN_LDS((sepconv_block_kernel<11, 1, 2, 2, true>), 128 * 1024);
+        hipLaunchKernelGGL((sepconv_block_kernel<11, 1, 2, 2, true>), dim3((unsigned)r.n_tiles), dim3(THREADS), lds_bytes, static_cast<hipStream_t>(stream),
+                           c, dw_w, pw_w, pw_b, nullptr, nullptr, x, 0LL, 1LL, (long long)xs_t, 0, nullptr, y, 0, 0, flag, r);
+    } else {
+        VADX_DYN_LDS((sepconv_block_kernel<11, 1, 2, 0, true>), 128 * 1024);
+        hipLaunchKernelGGL((sepconv_block_kernel<11, 1, 2, 0, true>), dim3((unsigned)r.n_tiles), dim3(THREADS), lds_bytes, static_cast<hipStream_t>(stream),
+                           c, dw_w, pw_w, pw_b, nullptr, nullptr, x, 0LL, 1LL, (long long)xs_t, 0, nullptr, y, 0, 0, flag, r);
+    }
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+extern "C" int vadx_marblenet_block2_ragged(int cin, int kernel, const float *dw0, const float *pw0, const float *b0, const float *dw1,
+                                            const float *pw1, const float *b1, const float *res_w, const float *res_b, const float *x, float *y,
+                                            const vadx_marblenet_ragged *rt, void *stream, const vadx_marblenet_cfg *cfg) {
+    static const char who[] = "vadx_marblenet_block2_ragged";
+    VADX_REQUIRE(dw0 && pw0 && b0 && dw1 && pw1 && b1 && res_w && res_b && x && y, "%s: NULL argument", who);
+    int ar;
+    unsigned *flag;
+    Ragged r;
+    if (int rc = ragged_arith(who, cfg, &ar, &flag)) return rc;
+    if (int rc = ragged_tables(who, rt, false, &r)) return rc;
+    VADX_REQUIRE((cin == 64 || cin == 128) && (kernel == 13 || kernel == 15 || kernel == 17),
+                 "%s: built for the published MarbleNet 3x2x64 residual blocks (cin 64/128, 64 filters, kernel 13/15/17)", who);
+    const Blk2 c = make_blk2(cin, kernel, 0);                // (T comes from the tables)
+    VADX_REQUIRE(c.cinp * c.in_ld >= c.c1 * A_LD, "%s: the depthwise-1 output does not fit the input region", who);
+    const bool planes = ar == vadx::VADX_AR_H2 && cin == 64;
+    const size_t lds = blk2_lds(c, planes);
+#define BLK2_RAGGED(KK, AR)                                                                                                    \
+    do {                                                                                                                       \
+        VADX_DYN_LDS((jasper_block2_kernel<KK, AR, true>), 128 * 1024);                                                        \
+        hipLaunchKernelGGL((jasper_block2_kernel<KK, AR, true>), dim3((unsigned)r.n_tiles), dim3(THREADS), lds,                \
+                           static_cast<hipStream_t>(stream), c, dw0, pw0, b0, dw1, pw1, b1, res_w, res_b, x, y, 0, flag, r);    \
+    } while (0)
+    if (planes) {
+        if (kernel == 13) BLK2_RAGGED(13, 3);
+        else if (kernel == 15) BLK2_RAGGED(15, 3);
+        else BLK2_RAGGED(17, 3);
+    } else if (ar == vadx::VADX_AR_H2) {
+        if (kernel == 13) BLK2_RAGGED(13, 2);
+        else if (kernel == 15) BLK2_RAGGED(15, 2);
+        else BLK2_RAGGED(17, 2);
+    } else {
+        if (kernel == 13) BLK2_RAGGED(13, 0);
+        else if (kernel == 15) BLK2_RAGGED(15, 0);
+        else BLK2_RAGGED(17, 0);
+    }
+#undef BLK2_RAGGED
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+extern "C" int vadx_marblenet_tail_ragged(const float *dw, const float *pw, const float *pb, const float *w6, const float *b6,
+                                          const float *dec_w, const float *dec_b, const float *x, float *score0, float *score1,
+                                          const vadx_marblenet_ragged *rt, void *stream, const vadx_marblenet_cfg *cfg) {
+    static const char who[] = "vadx_marblenet_tail_ragged";
+    VADX_REQUIRE(dw && pw && pb && w6 && b6 && dec_w && dec_b && x && score0 && score1, "%s: NULL argument", who);
+    int ar;
+    unsigned *flag;
+    Ragged r;
+    if (int rc = ragged_arith(who, cfg, &ar, &flag)) return rc;
+    if (int rc = ragged_tables(who, rt, false, &r)) return rc;
+    const Tail c = make_tail(0);                             // (T comes from the tables)
+    const size_t lds = tail_lds(c);
+    if (ar == vadx::VADX_AR_H2) {
+        VADX_DYN_LDS((marblenet_tail_kernel<2, true>), 128 * 1024);
+        hipLaunchKernelGGL((marblenet_tail_kernel<2, true>), dim3((unsigned)r.n_tiles), dim3(THREADS), lds, static_cast<hipStream_t>(stream),
+                           c, dw, pw, pb, w6, b6, dec_w, dec_b, x, score0, score1, 0, flag, r);
+    } else {
+        VADX_DYN_LDS((marblenet_tail_kernel<0, true>), 128 * 1024);
+        hipLaunchKernelGGL((marblenet_tail_kernel<0, true>), dim3((unsigned)r.n_tiles), dim3(THREADS), lds, static_cast<hipStream_t>(stream),
+                           c, dw, pw, pb, w6, b6, dec_w, dec_b, x, score0, score1, 0, flag, r);
     }
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;

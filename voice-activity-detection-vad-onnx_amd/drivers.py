@@ -1,8 +1,10 @@
 """Script-level drop-ins for the reference's `Inference_*_VAD_ONNX.py` programs: raw audio file(s) in,
 `timestamps_second.txt` / `timestamps_indices.txt` out, same constants (as keyword arguments instead
 of module-level globals), same stdout summary.  Each function also accepts a LIST of files: FSMN, FireRed and FireRed-AED hand
-the list to their engine as ONE ragged batch (vadx.ragged: clips of any lengths, work proportional to the audio); MarbleNet and DFSMN
-run equal-length files as one device batch per length group (`_grouped`); the Silero driver pads ragged clips into one batch.  The
+the list to their engine as ONE ragged batch (vadx.ragged: clips of any lengths, work proportional to the audio), and so does MarbleNet
+in both window modes (dynamic axis: vadx.ragged.RaggedFrames, one window per clip; INPUT_AUDIO_LENGTH: each clip on its own window
+grid); DFSMN runs equal-length files as one device batch per length group (`_grouped`); the Silero driver pads ragged clips into one
+batch.  The
 printed RTF is over the total audio duration.  `engine` / `model` may be an engine object, a weight dict, a checkpoint path, or the explicit
 opt-in "synthetic:<seed>" (vadx.checkpoints.resolve) -- never an implicit default."""
 from __future__ import annotations
@@ -198,7 +200,10 @@ def inference_marblenet(test_vad_audio="./vad_sample.wav", engine=None, save_tim
     t0 = time.time()
     post = (SMOOTH_WINDOW_SIZE, SPEAKING_SCORE, MIN_SPEECH_FRAME, MAX_SPEECH_FRAME, MIN_SILENCE_FRAME,
             MERGE_SILENCE_FRAME, EXTEND_SPEECH_FRAME)
-    all_ts = _grouped(clips, pad_noise, lambda batch, nz: engine.detect(batch, window_len=INPUT_AUDIO_LENGTH, pad_noise=nz, post=post))
+    if isinstance(test_vad_audio, (list, tuple)):          # files of any lengths: one ragged batch
+        all_ts = engine.detect(clips, window_len=INPUT_AUDIO_LENGTH, pad_noise=pad_noise, post=post)
+    else:
+        all_ts = _grouped(clips, pad_noise, lambda batch, nz: engine.detect(batch, window_len=INPUT_AUDIO_LENGTH, pad_noise=nz, post=post))
     elapsed = time.time() - t0
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
 

@@ -175,3 +175,28 @@ class Frontend:
                                                        None if means is None else means.data_ptr(), out.data_ptr(),
                                                        _lib.stream_ptr()))
         return out
+
+    RAGGED_KINDS = (KIND_SPLIT_H2, KIND_SPLIT_B3)
+
+    def logmel_ragged(self, rf):
+        """vadx.ragged.RaggedFrames (clips of any lengths, one window = one clip) -> log-mel f32 [sum F_b, n_mels] on the device, clip
+        b's rows from rf.mel_first[b]: one launch (vadx_frontend_logmel_ragged).  Nothing in the packed tables depends on a window
+        length, so ONE Frontend serves every length.  A host-only batch is uploaded first, in place.  Built for the split-product kinds
+        and the centre-padded two-tap preset at 16 kHz; anything else is a ValueError -- never another product behind the caller's back."""
+        t = self.torch
+        if self.fold not in self.RAGGED_KINDS:
+            raise ValueError(f"the ragged front-end is built for the split-product kinds {self.RAGGED_KINDS} (KIND_SPLIT_H2 / KIND_SPLIT_B3); this "
+                             f"Frontend was packed as kind {self.fold} (fold argument or VADX_FRONTEND_FOLD): no ragged form of that product")
+        if self.cfg.prep != 1 or self.cfg.center_pad <= 0 or self.cfg.hop != 160:
+            raise ValueError(f"the ragged front-end is built for the centre-padded two-tap preset at 16 kHz (prep 1, hop 160); this Frontend has "
+                             f"prep {self.cfg.prep}, centre pad {self.cfg.center_pad}, hop {self.cfg.hop}")
+        if rf.device is None:
+            rf.to(self.device)
+        out = t.empty((rf.n_mel, self.n_mels), dtype=t.float32, device=self.device)
+        with t.cuda.device(self.device):
+            _lib.check(_lib.lib().vadx_frontend_logmel_ragged(C.byref(self.cfg), self.packed.data_ptr(), self.mel_kb.ctypes.data,
+                                                              rf.pcm.data_ptr(), int(rf.pcm.numel()), rf.clip_off.data_ptr(),
+                                                              rf.clip_len.data_ptr(), rf.mel_first.data_ptr(), rf.fe_tile_first.data_ptr(),
+                                                              rf.fe_tile_clip.data_ptr(), len(rf), rf.n_fe_tiles, rf.n_mel, out.data_ptr(),
+                                                              _lib.stream_ptr()))
+        return out

@@ -87,6 +87,7 @@ class MarbleNetEngine:
         self.cout = cin
         self.dec_w, self.dec_b = dev(w["dec_w"]), dev(w["dec_b"])
         self._fe = {}
+        self._fe_ragged = None
         # the published 3x2x64 layout runs on the fused kernels: one launch per residual block, one for blocks 5 + 6 + decoder
         self.fused = tuple(tuple(b) for b in blocks) == tuple(tuple(b) for b in _weights.MARBLENET_BLOCKS)
         # fp16 x 2 split products for the 1x1 convs of the fused residual blocks (csrc/split2.h; include/vadx.h: vadx_marblenet_cfg)
@@ -125,6 +126,62 @@ class MarbleNetEngine:
         if L not in self._fe:
             self._fe[L] = _frontend.Frontend("marblenet", L, device=self.device, in_sample_rate=self.in_sample_rate)
         return self._fe[L]
+
+    def frontend_ragged(self):
+        """The one Frontend behind `logmel_ragged`: its tables do not depend on a window length (the length it is built with is only
+        a valid placeholder), so clips of every length share it."""
+        if self.in_sample_rate != SAMPLE_RATE:
+            raise ValueError(f"the ragged path has no in-graph resampling: in_sample_rate is {self.in_sample_rate}, not {SAMPLE_RATE}")
+        if self._fe_ragged is None:
+            self._fe_ragged = _frontend.Frontend("marblenet", SAMPLE_RATE, device=self.device)
+        return self._fe_ragged
+
+    def ragged(self, clips, device=True):
+        """The packed batch of `clips` (list of 1-D int16 arrays of any lengths; vadx.ragged.RaggedFrames).  device=None keeps it on the host."""
+        from . import ragged as _ragged
+        return _ragged.RaggedFrames.from_clips(clips, self.device if device is True else device)
+
+    def run_ragged(self, rf):
+        """RaggedFrames -> (score_silence, score_active f32 [sum T1_b] packed, enc_first int32 [B+1] on the host): clip b's scores are
+        [enc_first[b], enc_first[b+1]), bit for bit what `run(clip_b[None])` gives.  One front-end launch and five encoder launches for
+        the whole batch, whatever the lengths; the fp16 x 2 range protocol covers the whole batch (a raised flag recomputes all of it on
+        float32 and counts once in range_fallbacks).  The published 3x2x64 layout only."""
+        if not self.fused:
+            raise ValueError("MarbleNetEngine.run_ragged: ragged batches are built for the published MarbleNet 3x2x64 layout (the fused "
+                             "kernels); this engine was constructed with another `blocks` layout -- run its clips one length at a time")
+        if rf.device is None:
+            rf.to(self.device)
+        x = self.frontend_ragged().logmel_ragged(rf)
+        s0, s1 = _lib.range_guarded(self, self.mode(), lambda m: self._run_fused_ragged(x, rf, m), lambda: _lib.take_flag(self._flag), "f32")
+        return s0, s1, rf.enc_first_host
+
+    def _run_fused_ragged(self, x, rf, mode):
+        """`_run_fused` over packed clips: the same five launches, (clip, tile) from rf's tables; the activation between two launches
+        is clip b's [C][T1_b] block at float offset C * enc_first[b]."""
+        t, lib, st = self.torch, _lib.lib(), self.stages
+        p = lambda a: None if a is None else a.data_ptr()        # noqa: E731
+        n = rf.n_enc
+        with t.cuda.device(self.device):
+            rt = rf.encoder_tables()
+            mc = _lib.MarbleNetCfg(_lib.ARITH[mode], 0, self._flag.data_ptr())
+            sfx = "_h" if mode == "h2" else ""
+            s0 = st[0]
+            cur = t.empty((n * s0["cfg"].cout,), dtype=t.float32, device=self.device)
+            _lib.check(lib.vadx_sepconv_block_ragged(C.byref(s0["cfg"]), p(s0["dw"]), p(s0["pw" + sfx]), p(s0["pb"]), x.data_ptr(), x.shape[1],
+                                                     cur.data_ptr(), C.byref(rt), _lib.stream_ptr(), C.byref(mc)))
+            for k in (1, 3, 5):
+                a, b = st[k], st[k + 1]
+                y = t.empty((n * 64,), dtype=t.float32, device=self.device)
+                _lib.check(lib.vadx_marblenet_block2_ragged(a["cfg"].cin, a["cfg"].kernel, p(a["dw"]), p(a["pw" + sfx]), p(a["pb"]), p(b["dw"]),
+                                                            p(b["pw" + sfx]), p(b["pb"]), p(b["rw" + sfx]), p(b["rb"]), cur.data_ptr(),
+                                                            y.data_ptr(), C.byref(rt), _lib.stream_ptr(), C.byref(mc)))
+                cur = y
+            s0o = t.empty((n,), dtype=t.float32, device=self.device)
+            s1o = t.empty((n,), dtype=t.float32, device=self.device)
+            _lib.check(lib.vadx_marblenet_tail_ragged(p(st[7]["dw"]), p(st[7]["pw" + sfx]), p(st[7]["pb"]), p(st[8]["pw" + sfx]), p(st[8]["pb"]),
+                                                      self.dec_w.data_ptr(), self.dec_b.data_ptr(), cur.data_ptr(), s0o.data_ptr(),
+                                                      s1o.data_ptr(), C.byref(rt), _lib.stream_ptr(), C.byref(mc)))
+        return s0o, s1o
 
     def run(self, audio_i16, windows_per_clip=1, window_len=None):
         """audio int16 [B, W*L] -> (score_silence, score_active f32 [B*W, T'], signal_len = T' - 1)."""
@@ -212,7 +269,11 @@ class MarbleNetEngine:
 
     def detect(self, clips_i16, window_len=None, pad_noise=None, post=(3, 0.5, 10, 1000, 10, 3, 0), return_probs=False):
         """Equal-length clips int16 [B,N] (host) -> per clip [(start_s, end_s)].  window_len None = the
-        dynamic-axis mode (one window = the whole clip, up to 3600 s, :130-135)."""
+        dynamic-axis mode (one window = the whole clip, up to 3600 s, :130-135).
+        A LIST (or tuple) of 1-D clips of any lengths runs as one ragged batch in either mode (`_detect_ragged`); clip b's result is
+        that of the [1, N] call on it alone, and return_probs then gives (segments, tracks f32 [B, max n_frames], decisions, n_frames)."""
+        if isinstance(clips_i16, (list, tuple)):
+            return self._detect_ragged(clips_i16, window_len, pad_noise, post, return_probs)
         clips = np.asarray(clips_i16)
         B, n = clips.shape
         L = min(self.in_sample_rate * 3600, n) if window_len is None else int(window_len)
@@ -227,6 +288,75 @@ class MarbleNetEngine:
         segs, counts = segs.cpu().numpy(), counts.cpu().numpy()
         out = [pp.segments_to_seconds(segs[b, :counts[b]].tolist(), track.shape[1], n / self.in_sample_rate) for b in range(B)]
         return (out, track, dec) if return_probs else out
+
+    def _tracks(self, probs, win_floats, frames_per_window, win_first, n_frames):
+        """tracks f32 [B, max n_frames] (vadx_tracks_gather): row b = the first n_frames[b] scores of clip b's windows, zeros after them."""
+        t = self.torch
+        stride = max(int(n_frames.max()), 1)
+        tracks = t.empty((len(n_frames), stride), dtype=t.float32, device=self.device)
+        nfd = t.from_numpy(np.ascontiguousarray(n_frames, dtype=np.int32)).to(self.device)
+        with t.cuda.device(self.device):
+            _lib.check(_lib.lib().vadx_tracks_gather(probs.data_ptr(), win_floats, 0, frames_per_window, win_first.data_ptr(), nfd.data_ptr(),
+                                                     len(n_frames), tracks.data_ptr(), stride, _lib.stream_ptr()))
+        return tracks
+
+    def _detect_ragged(self, clips, window_len, pad_noise, post, return_probs):
+        """`detect` for a list of 1-D int16 clips of any lengths.  Dynamic axis: RaggedFrames -> logmel_ragged -> run_ragged, one
+        score per encoder frame; clips the ragged kernels do not take (longer than 3600 s: they are cut into windows; every clip when
+        the graph resamples) keep the one-call-per-length path and are spliced back in input order.  window_len = L (the static
+        export): the clips padded to their own window grids (vadx.ragged.RaggedBatch), every window through the unchanged front-end
+        and `run_features`.  Either way one vadx_tracks_gather + one vadx_vadpost launch for the batch."""
+        from . import ragged as _ragged
+        if not self.fused:
+            raise ValueError("MarbleNetEngine.detect: a list of clips (a ragged batch) is built for the published MarbleNet 3x2x64 layout; this "
+                             "engine was constructed with another `blocks` layout -- pass equal-length clips as a [B, N] array")
+        clips = [np.asarray(c) for c in clips]
+        B = len(clips)
+        if B == 0:
+            raise ValueError("a ragged batch needs at least one clip")
+        pp = _vadpost.VadPostprocessor(*post, frame_shift_s=OUTPUT_FRAME_SHIFT_S, frame_length_s=None, device=self.device)
+        if window_len is None:
+            cap = self.in_sample_rate * 3600
+            rag = [b for b in range(B) if self.in_sample_rate == SAMPLE_RATE and clips[b].reshape(-1).shape[0] <= cap]
+            out, tracks, decs, nfs = [None] * B, [None] * B, [None] * B, np.zeros(B, dtype=np.int32)
+            for b in set(range(B)) - set(rag):          # today's path, one call per clip
+                o, tr, de = self.detect(clips[b].reshape(1, -1), None, None if pad_noise is None else np.asarray(pad_noise[b])[None, :], post, True)
+                out[b], tracks[b], decs[b], nfs[b] = o[0], tr[0], de[0], tr.shape[1]
+            if rag:
+                rf = self.ragged([clips[b] for b in rag])
+                _, s1, enc_first = self.run_ragged(rf)
+                nf = (rf.enc_frames - 1).astype(np.int32)           # valid_b = min(signal_len, T1_b) = T1_b - 1
+                track = self._tracks(s1, 1, 1, rf.enc_first, nf)
+                dec, segs, counts = pp.process_batch(track, n_frames=nf)
+                segs, counts = segs.cpu().numpy(), counts.cpu().numpy()
+                for k, b in enumerate(rag):
+                    out[b] = pp.segments_to_seconds(segs[k, :counts[k]].tolist(), int(nf[k]), int(rf.lengths[k]) / self.in_sample_rate) if nf[k] else []
+                    tracks[b], decs[b], nfs[b] = track[k, :nf[k]], dec[k, :nf[k]], nf[k]
+            if not return_probs:
+                return out
+            if len(rag) == B:
+                return out, track, dec, nfs
+            return out, self._pad_rows(tracks, self.torch.float32), self._pad_rows(decs, self.torch.int8), nfs
+        L = int(window_len)
+        rb = _ragged.RaggedBatch.from_clips(clips, L, L, pad_noise, None, self.device)
+        s0, s1, slen = self.run_features(self.frontend(L).logmel(rb.gather(), 1, L))
+        T1 = int(s1.shape[1])
+        valid = min(slen, T1)
+        nf = (rb.windows.astype(np.int64) * valid).astype(np.int32)
+        track = self._tracks(s1, T1, valid, rb.win_first, nf) if valid else self.torch.zeros((B, 0), dtype=self.torch.float32, device=self.device)
+        dec, segs, counts = pp.process_batch(track, n_frames=nf)
+        segs, counts = segs.cpu().numpy(), counts.cpu().numpy()
+        out = [pp.segments_to_seconds(segs[b, :counts[b]].tolist(), int(nf[b]), int(rb.lengths[b]) / self.in_sample_rate) if nf[b] else []
+               for b in range(B)]
+        return (out, track, dec, nf) if return_probs else out
+
+    def _pad_rows(self, rows, dtype):
+        """1-D device rows of different lengths -> one zero-filled matrix [B, max len]."""
+        t = self.torch
+        m = t.zeros((len(rows), max(max(int(r.shape[0]) for r in rows), 1)), dtype=dtype, device=self.device)
+        for b, r in enumerate(rows):
+            m[b, :r.shape[0]] = r.to(self.device)
+        return m
 
 
 class MarbleNetSession:

@@ -10,6 +10,9 @@ Tables (include/vadx.h, "Ragged batches"):
     win_first [B+1]  prefix sum of the windows per clip: clip b owns windows win_first[b] .. win_first[b+1]-1 of every per-window buffer
     win_src   [sum W] sample offset of every window in `pcm`: clip_off[b] + k * stride
     order     [B]    clips by window count, longest first (stable): the launch order of one-workgroup-per-clip kernels
+
+`RaggedFrames` (below) is the batch of the model whose window is the whole clip (MarbleNet, dynamic axis): no window grid, no padding --
+the clips as they are, with per-clip frame prefixes and tile tables.
 """
 from __future__ import annotations
 
@@ -101,3 +104,85 @@ class RaggedBatch:
             _lib.check(_lib.lib().vadx_windows_gather(self.pcm.data_ptr(), int(self.pcm.numel()), self.win_src.data_ptr(), self.n_windows,
                                                       self.window, wbuf.data_ptr(), _lib.stream_ptr()))
         return wbuf
+
+
+FE_TILE, ENC_TILE = 64, 32   # frames per front-end / encoder tile (csrc/frontend.hip: TF_FOLD, csrc/marblenet.hip: TILE)
+HOP = 160                    # the MarbleNet preset's hop: a clip of n samples has n // HOP + 1 log-mel frames (centre-padded)
+
+
+def _prefix(counts, what):
+    """int32 prefix sum [B+1] of per-clip counts, refused when the total leaves the int32 range."""
+    total = int(np.sum(counts, dtype=np.int64))
+    if total >= 2 ** 31:
+        raise ValueError(f"{total} {what} do not fit the int32 tables of a ragged batch")
+    return np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32)
+
+
+class RaggedFrames:
+    """MarbleNet's ragged batch (dynamic-axis mode: one window = one whole clip, so every clip has its own frame count; include/vadx.h,
+    "MarbleNet over a RAGGED batch").  The clips lie end to end in `pcm` with NO padding and no alignment filler: the front-end's sample
+    loads are single int16 loads from clamped indices (csrc/frontend.hip: split_tile), so a clip may start at any sample.
+    Fields: pcm int16 [sum n_b]; clip_off int64 [B], clip_len int32 [B]; mel_first int32 [B+1] = prefix of F_b = n_b // 160 + 1 log-mel
+    frames; enc_first int32 [B+1] = prefix of T1_b = (F_b - 1) // 2 + 1 encoder frames (the stride-2, k 11 prologue); per tiling
+    (front-end 64 frames, encoder 32) a prefix `*_tile_first` int32 [B+1] and the clip of every tile `*_tile_clip` int32 [n_tiles]: a
+    workgroup finds (clip, tile) with two uniform loads, no search -- the tables cost one int per tile, and a search would put a
+    dependent chain of log2(B) loads in front of every tile's first useful load.
+    With a device every field is a tensor there and the `*_host` attributes keep the numpy tables; device=None keeps numpy only."""
+
+    TABLES = ("pcm", "clip_off", "clip_len", "mel_first", "enc_first", "fe_tile_first", "fe_tile_clip", "enc_tile_first", "enc_tile_clip")
+
+    @classmethod
+    def from_clips(cls, clips, device="cuda:0"):
+        if len(clips) == 0:
+            raise ValueError("a ragged batch needs at least one clip")
+        rows = []
+        for b, c in enumerate(clips):
+            a = np.asarray(c)
+            if a.dtype != np.int16:
+                raise ValueError(f"clip {b} must be int16, got {a.dtype}")
+            a = a.reshape(-1)
+            if a.shape[0] == 0:
+                raise ValueError(f"clip {b} is empty")
+            rows.append(a)
+        self = cls()
+        self.lengths = np.asarray([len(r) for r in rows], dtype=np.int64)
+        if int(self.lengths.max()) >= 2 ** 31:
+            raise ValueError("a clip of 2^31 samples or more does not fit the int32 clip_len table")
+        self.clip_len_host = self.lengths.astype(np.int32)
+        self.clip_off_host = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64)
+        self.mel_frames = (self.lengths // HOP + 1).astype(np.int64)
+        self.enc_frames = (self.mel_frames - 1) // 2 + 1
+        self.mel_first_host, self.enc_first_host = _prefix(self.mel_frames, "log-mel frames"), _prefix(self.enc_frames, "encoder frames")
+        fe_tiles, enc_tiles = (self.mel_frames + FE_TILE - 1) // FE_TILE, (self.enc_frames + ENC_TILE - 1) // ENC_TILE
+        self.fe_tile_first_host, self.enc_tile_first_host = _prefix(fe_tiles, "front-end tiles"), _prefix(enc_tiles, "encoder tiles")
+        ids = np.arange(len(rows), dtype=np.int32)
+        self.fe_tile_clip_host, self.enc_tile_clip_host = np.repeat(ids, fe_tiles), np.repeat(ids, enc_tiles)
+        self.pcm_host = np.concatenate(rows)
+        self.n_mel, self.n_enc = int(self.mel_first_host[-1]), int(self.enc_first_host[-1])
+        self.n_fe_tiles, self.n_enc_tiles = int(self.fe_tile_first_host[-1]), int(self.enc_tile_first_host[-1])
+        self.device = None
+        for name in self.TABLES:
+            setattr(self, name, getattr(self, name + "_host"))
+        if device is not None:
+            self.to(device)
+        return self
+
+    def to(self, device):
+        """Upload the packed PCM (once) and the tables."""
+        from . import _lib
+        t = _lib.require_gpu()
+        self.device = t.device(device)
+        for name in self.TABLES:
+            setattr(self, name, t.from_numpy(getattr(self, name + "_host")).to(self.device))
+        return self
+
+    def __len__(self):
+        return int(self.lengths.shape[0])
+
+    def encoder_tables(self):
+        """The vadx_marblenet_ragged struct of this batch (device pointers: the batch must be on a device)."""
+        from . import _lib
+        if self.device is None:
+            raise ValueError("this batch is host-only: call .to(device) first")
+        return _lib.MarbleNetRagged(self.enc_tile_first.data_ptr(), self.enc_tile_clip.data_ptr(), self.enc_first.data_ptr(),
+                                    self.mel_first.data_ptr(), len(self), self.n_enc_tiles, self.n_enc, self.n_mel)
