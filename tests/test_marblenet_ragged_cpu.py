@@ -178,4 +178,4 @@ def test_a_list_is_refused_on_another_layout_by_name():
     with pytest.raises(ValueError, match="published MarbleNet 3x2x64"):
         marblenet.MarbleNetEngine.run_ragged(_Stub(), None)
     with pytest.raises(ValueError, match="published MarbleNet 3x2x64"):
-        marblenet.MarbleNetEngine._detect_ragged(_Stub(), [np.zeros(8, np.int16)], None, None, (3, 0.5, 10, 1000, 10, 3, 0), False)
+        marblenet.MarbleNetEngine.detect(_Stub(), [np.zeros(8, np.int16)])

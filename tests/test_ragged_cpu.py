@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import vadx  # noqa: F401
-from vadx import _lib, build, fsmn, ragged, timestamps, weights
+from vadx import _lib, build, clips, fsmn, ragged, timestamps, weights
 
 L, T = 16000, 101
 NAMES = ("vadx_windows_gather", "vadx_fsmn_clips_ragged", "vadx_tracks_gather")
@@ -147,3 +147,103 @@ def test_packing_takes_noise_rows_as_a_list_and_refuses_bad_input():
         ragged.RaggedBatch.from_clips(clips, L, L, rows[:2], device=None)
     with pytest.raises(ValueError, match="host-only"):
         rb.gather()
+
+
+# ------------------------------------------------------------------------------------------------------- the whole-clip host pipeline
+@pytest.mark.parametrize("window,stride,prep", [(L, 11040, True), (L, 11040, False), (L, L, False), (8000, 8000, False)])
+@pytest.mark.parametrize("n", [9000, 16000, 27040, 30000])
+def test_pad_batch_is_the_stack_of_padded_rows(window, stride, prep, n):
+    """A clip shorter than the window, of exactly one window, exactly on the FSMN grid (16000 + 11040) and with a remainder; the FSMN
+    grid with and without its peak normalisation, an L, L grid; a given noise matrix."""
+    batch = weights.burst_clips(3, n, seed=900 + n % 7)
+    noise = np.random.default_rng(12).standard_normal((3, 20000))
+    fn = (lambda a: timestamps.normalize_to_int16(a.astype(np.float32))) if prep else None
+    padded, W = clips.pad_batch(batch, window, stride, noise, fn)
+    want = np.stack([fsmn.pad_to_window_grid(fn(batch[b]) if fn else batch[b], window, stride, noise[b]) for b in range(3)])
+    assert padded.dtype == np.int16 and np.array_equal(padded, want)
+    assert W == (padded.shape[1] - window) // stride + 1 == max(0, -(-(n - window) // stride)) + 1
+    assert (W - 1) * stride + window == padded.shape[1]                  # the last window ends with the padded clip
+    assert np.array_equal(padded[:, :n], np.stack([fn(batch[b]) for b in range(3)]) if fn else batch)
+    with pytest.raises(ValueError):
+        clips.pad_batch(batch[0], window, stride, noise)                 # one 1-D clip is not a batch
+
+
+def test_pad_batch_without_noise_draws_like_the_reference():
+    batch = weights.burst_clips(2, 9000, seed=3)
+    np.random.seed(5)
+    padded, W = clips.pad_batch(batch, L, L)
+    np.random.seed(5)
+    assert W == 1 and np.array_equal(padded, np.stack([fsmn.pad_to_window_grid(batch[b], L, L) for b in range(2)]))
+
+
+def test_the_moved_names_still_resolve():
+    from vadx import session
+    assert fsmn.pad_to_window_grid is clips.pad_to_window_grid and ragged.pad_to_window_grid is clips.pad_to_window_grid
+    assert fsmn._Meta is session._Meta
+    assert not hasattr(ragged, "fsmn")
+    assert session.io_types("float16") == (np.float16, "tensor(float16)") and session.io_types("float32") == (np.float32, "tensor(float)")
+    with pytest.raises(ValueError, match="io_dtype must be 'float32' or 'float16'"):
+        session.io_types("bfloat16")
+
+
+class _StubEngine:
+    """Stands where an engine stands in a driver call: records what `detect` receives; a clip's result names its first sample and the
+    first value of the noise row it was given, so a result that lost its clip or its noise row shows."""
+
+    def __init__(self):
+        self.seen = []
+
+    def detect(self, audio, pad_noise=None, **kw):
+        self.seen.append((audio, pad_noise, kw))
+        return [[(float(abs(int(c[0]))), float(abs(int(c[0]))) + abs(float(pad_noise[b][0])))] for b, c in enumerate(audio)]
+
+
+def _wavs(tmp_path, lengths):
+    import wave
+    paths = []
+    for k, n in enumerate(lengths):
+        pth = str(tmp_path / f"c{k}.wav")
+        a = weights.burst_clips(1, n, seed=600 + k)[0]
+        a[0] = 100 + k                                                    # the first sample names the clip
+        with wave.open(pth, "wb") as w:
+            w.setnchannels(1); w.setsampwidth(2); w.setframerate(16000); w.writeframes(a.tobytes())         # noqa: E702
+        paths.append(pth)
+    return paths
+
+
+@pytest.mark.parametrize("driver,kw", [("inference_fsmn", {}), ("inference_firered", {}), ("inference_marblenet", {}),
+                                       ("inference_marblenet", {"INPUT_AUDIO_LENGTH": 8000})])
+def test_driver_skeleton_with_a_stub_engine(tmp_path, driver, kw):
+    from vadx import drivers
+    run = getattr(drivers, driver)
+    lengths = [4000, 2500, 4000]
+    paths = _wavs(tmp_path, lengths)
+    noise = np.random.default_rng(13).standard_normal((3, 50))
+    files = (str(tmp_path / "s.txt"), str(tmp_path / "i.txt"))
+    quiet = lambda *_: None                                                                                               # noqa: E731
+    # a list of three files of different lengths reaches detect once, as a list
+    eng = _StubEngine()
+    many = run(paths, eng, *files, pad_noise=noise, echo=quiet, **kw)
+    assert len(eng.seen) == 1
+    audio, nz, passed = eng.seen[0]
+    assert isinstance(audio, list) and [a.shape for a in audio] == [(n,) for n in lengths] and nz is noise
+    assert [int(a[0]) for a in audio] == [100, 101, 102]
+    assert passed.get("window_len", None) == kw.get("INPUT_AUDIO_LENGTH")
+    assert [m[0][0] for m in many] == [100.0, 101.0, 102.0]
+    assert [m[0][1] - m[0][0] for m in many] == pytest.approx(np.abs(noise[:, 0]))
+    # a single path reaches detect as a [1, N] array, its noise as one row; the result is the clip's, not a list of one
+    for k, pth in enumerate(paths):
+        eng = _StubEngine()
+        one = run(pth, eng, *files, pad_noise=noise[k:k + 1], echo=quiet, **kw)
+        audio, nz, _ = eng.seen[0]
+        assert len(eng.seen) == 1 and isinstance(audio, np.ndarray) and audio.shape == (1, lengths[k]) and nz.shape == (1, 50)
+        assert one == many[k]                                             # two equal-length files one at a time: the same, in input order
+    # the length groups of `_grouped`: clips 0 and 2 share one [2, N] batch, their noise rows follow them; results in input order
+    eng = _StubEngine()
+    loaded = drivers._load(paths)
+    got = drivers._detect_files(lambda c, z: eng.detect(c, pad_noise=z), loaded, False, [noise[0], noise[1][:30], noise[2][:40]])
+    assert got == many and [s[0].shape for s in eng.seen] == [(2, 4000), (1, 2500)]
+    assert [s[1].shape for s in eng.seen] == [(2, 40), (1, 30)]           # ragged rows are trimmed to the group's shortest
+    assert np.array_equal(eng.seen[0][1], np.stack([noise[0][:40], noise[2][:40]]))
+    assert drivers._detect_files(lambda c, z: eng.detect(c, pad_noise=z), loaded, True, noise) == many
+    assert drivers._engine_of(dict, eng) is eng and drivers._engine_of(dict, {"a": 1}) == {"a": 1}

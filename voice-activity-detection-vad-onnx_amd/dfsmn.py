@@ -11,6 +11,8 @@ import os
 import numpy as np
 
 from . import _lib
+from .clips import flag_timestamps, pad_batch
+from .session import Session, _Meta, io_types
 
 F_BINS, CEPS_F, CH = 160, 81, 20
 
@@ -595,33 +597,25 @@ class DfsmnEngine:
         """Equal-length clip pairs (host, any numeric dtype) [B,N] -> per clip [(start_s, end_s)]
         (Inference_DFSMN_VAD_ONNX.py:124-163 prep, :221-278 loop)."""
         from . import timestamps as ts
-        from .fsmn import pad_to_window_grid
         t = self.torch
         near_clips = np.asarray(near_clips)
         far_clips = None if far_clips is None else np.asarray(far_clips)      # None: the near-end-only model
         B = near_clips.shape[0]
         n = near_clips.shape[1] if far_clips is None else min(near_clips.shape[1], far_clips.shape[1])
         lb, stride = self.grid()
-        rows_n, rows_f = [], []
-        for b in range(B):
-            a = ts.normalize_to_int16(near_clips[b, :n].astype(np.float32))
-            rows_n.append(pad_to_window_grid(a, self.L, stride, None if pad_noise_near is None else pad_noise_near[b]))
-            if far_clips is not None:
-                f = ts.normalize_to_int16(far_clips[b, :n].astype(np.float32))
-                rows_f.append(pad_to_window_grid(f, self.L, stride, None if pad_noise_far is None else pad_noise_far[b]))
-        near, far = np.stack(rows_n), (np.stack(rows_f) if far_clips is not None else None)
-        W = (near.shape[1] - self.L) // stride + 1
+        prep = lambda a: ts.normalize_to_int16(a.astype(np.float32))      # noqa: E731
+        near, W = pad_batch(near_clips[:, :n], self.L, stride, pad_noise_near, prep)
+        far = None if far_clips is None else pad_batch(far_clips[:B, :n], self.L, stride, pad_noise_far, prep)[0]
         vad = self.run(near, far, W, stride)
         flags = t.empty((B, W * (self.T_A - lb) + lb), dtype=t.uint8, device=self.device)
         with t.cuda.device(self.device):
             _lib.check(self.lib.vadx_dfsmn_vote(vad.data_ptr(), B, W, self.T_A, lb, float(speaking_score), float(silence_score),
                                                 flags.data_ptr(), _lib.stream_ptr()))
-        fl = flags.cpu().numpy().astype(bool)
-        return [ts.process_timestamps(ts.vad_to_timestamps(fl[b], self.FRAME / 16000), fusion_threshold, min_speech_duration)
-                for b in range(B)]
+        fl = flags.cpu().numpy()
+        return [flag_timestamps(fl[b], self.FRAME / 16000, fusion_threshold, min_speech_duration) for b in range(B)]
 
 
-class DfsmnSession:
+class DfsmnSession(Session):
     """{'near_end_audio','far_end_audio': int16 [1,1,16001]} -> [vad_results f32 [51]]
     (DFSMN/near_and_far_end_audio/Export_DFSMN_VAD.py:377-393).  near_only = (pow_far, far_comp): the near-end-only export
     instead -- {'audio': int16 [1,1,16001]} (DFSMN/only_near_end_audio/Export_DFSMN_VAD.py:373-392)."""
@@ -629,10 +623,7 @@ class DfsmnSession:
     def __init__(self, weights=None, device="cuda:0", near_only=None, io_dtype="float32"):
         """io_dtype="float16": I/O-compatible with the reference's fp16 conversion (Optimize_ONNX.py:40-44, keep_io_types=False: vad_results
         leaves as float16); the arithmetic here stays float32, the scores are rounded once on the way out."""
-        from .fsmn import _Meta
-        if io_dtype not in ("float32", "float16"):
-            raise ValueError("io_dtype must be 'float32' or 'float16'")
-        self.io_dtype = np.float16 if io_dtype == "float16" else np.float32
+        self.io_dtype, ftype = io_types(io_dtype)
         self.engine = DfsmnEngine(weights, device)
         self.near_only = near_only is not None
         if self.near_only:
@@ -640,16 +631,7 @@ class DfsmnSession:
             self._inputs_meta = [_Meta("audio", [1, 1, 16001], "tensor(int16)")]
         else:
             self._inputs_meta = [_Meta("near_end_audio", [1, 1, 16001], "tensor(int16)"), _Meta("far_end_audio", [1, 1, 16001], "tensor(int16)")]
-        self._outputs_meta = [_Meta("vad_results", [51], "tensor(float16)" if io_dtype == "float16" else "tensor(float)")]
-
-    def get_inputs(self):
-        return list(self._inputs_meta)
-
-    def get_outputs(self):
-        return list(self._outputs_meta)
-
-    def get_providers(self):
-        return ["VadxMI355XExecutionProvider"]
+        self._outputs_meta = [_Meta("vad_results", [51], ftype)]
 
     def run(self, output_names, feeds):
         arrs = [np.asarray(feeds[m.name]) for m in self._inputs_meta]

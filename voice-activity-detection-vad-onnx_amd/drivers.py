@@ -20,15 +20,35 @@ def _as_list(x):
     return list(x) if isinstance(x, (list, tuple)) else [x]
 
 
+def _engine_of(cls, spec, *args):
+    """`spec` itself when it is an engine object; `cls(spec, *args)` when it is something to build one from: a checkpoint path, a
+    weight dict, "synthetic:<seed>" -- or None, which raises there (vadx.checkpoints.resolve: no implicit default)."""
+    return cls(spec, *args) if (spec is None or isinstance(spec, (str, dict))) else spec
+
+
+def _load(files, normalise=False):
+    """The files as int16 clips at 16 kHz, through the reference's optional NORMALIZE_AUDIO."""
+    clips = [audio_io.load_wav(f, 16000) for f in files]
+    return [timestamps.normalise_audio(c) for c in clips] if normalise else clips
+
+
+def _detect_files(detect, clips, as_list, pad_noise):
+    """`detect(clips, pad_noise) -> one result per clip` over the clips of a driver call: a list of files goes to the engine as it is,
+    ONE ragged batch of clips of any lengths; a single file goes the way it always went, as a [1, N] array (`_grouped`)."""
+    return detect(clips, pad_noise) if as_list else _grouped(clips, pad_noise, detect)
+
+
 def _grouped(clips, noises, run):
     """Run `run(stacked_clips [G, n], stacked_noise or None) -> list of G results` once per group of equal-length clips
-    (one device batch each) and hand the results back in input order."""
+    (one device batch each) and hand the results back in input order.  A clip may be a [channels, n] array (DFSMN's near / far
+    pairs: stacked to [G, 2, n]); `noises` is then a tuple with one entry per channel, and `run` gets one stacked noise per entry."""
     by_len = {}
     for k, c in enumerate(clips):
-        by_len.setdefault(len(c), []).append(k)
+        by_len.setdefault(c.shape[-1], []).append(k)
     out = [None] * len(clips)
     for idx in by_len.values():
-        for k, r in zip(idx, run(np.stack([clips[k] for k in idx]), _stack_noise(noises, idx))):
+        stacked = [_stack_noise(nz, idx) for nz in (noises if isinstance(noises, tuple) else (noises,))]
+        for k, r in zip(idx, run(np.stack([clips[k] for k in idx]), *stacked)):
             out[k] = r
     return out
 
@@ -88,18 +108,15 @@ def inference_fsmn(test_vad_audio="./vad_sample.wav", engine=None, save_timestam
                    BACKGROUND_NOISE_dB_INIT=30.0, ONE_MINUS_SPEECH_THRESHOLD=1.0, pad_noise=None, echo=print):
     """FSMN/Inference_FSMN_VAD_ONNX.py:66-260."""
     from . import fsmn
-    files = _as_list(test_vad_audio)
-    engine = fsmn.FsmnEngine(engine) if (engine is None or isinstance(engine, (str, dict))) else engine
-    clips = [audio_io.load_wav(f, 16000) for f in files]
+    engine = _engine_of(fsmn.FsmnEngine, engine)
+    clips = _load(_as_list(test_vad_audio))
     echo("\nRunning the FSMN_VAD by ONNX Runtime.")
     t0 = time.time()
     kw = dict(fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION, look_backward_s=LOOK_BACKWARD,
               speaking_score=SPEAKING_SCORE, silence_score=SILENCE_SCORE, snr_threshold=SNR_THRESHOLD,
               noise_init_dB=BACKGROUND_NOISE_dB_INIT, one_minus_speech_threshold=ONE_MINUS_SPEECH_THRESHOLD)
-    if isinstance(test_vad_audio, (list, tuple)):          # files of any lengths: one ragged batch
-        all_ts = engine.detect([c.astype(np.float32) for c in clips], pad_noise=pad_noise, **kw)
-    else:
-        all_ts = _grouped(clips, pad_noise, lambda batch, nz: engine.detect(batch.astype(np.float32), pad_noise=nz, **kw))
+    # (the int16 clips as they are: `detect` widens each to float32 itself before its peak normalisation)
+    all_ts = _detect_files(lambda c, nz: engine.detect(c, pad_noise=nz, **kw), clips, isinstance(test_vad_audio, (list, tuple)), pad_noise)
     elapsed = time.time() - t0
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
 
@@ -110,19 +127,13 @@ def inference_firered(test_vad_audio="./vad_sample.wav", engine=None, save_times
                       MERGE_SILENCE_FRAME=5, EXTEND_SPEECH_FRAME=0, pad_noise=None, echo=print):
     """FireRedVAD/Inference_FireRed_ONNX.py:523-613 (RUN_VAD)."""
     from . import firered
-    files = _as_list(test_vad_audio)
-    engine = firered.FireRedEngine(engine) if (engine is None or isinstance(engine, (str, dict))) else engine
-    clips = [audio_io.load_wav(f, 16000) for f in files]
-    if NORMALIZE_AUDIO:
-        clips = [timestamps.normalise_audio(c) for c in clips]
+    engine = _engine_of(firered.FireRedEngine, engine)
+    clips = _load(_as_list(test_vad_audio), NORMALIZE_AUDIO)
     echo("\nRunning the FireRedVAD by ONNX Runtime.")
     t0 = time.time()
     post = (SMOOTH_WINDOW_SIZE, SPEAKING_SCORE, MIN_SPEECH_FRAME, MAX_SPEECH_FRAME, MIN_SILENCE_FRAME,
             MERGE_SILENCE_FRAME, EXTEND_SPEECH_FRAME)
-    if isinstance(test_vad_audio, (list, tuple)):          # files of any lengths: one ragged batch
-        all_ts = engine.detect(clips, pad_noise=pad_noise, post=post)
-    else:
-        all_ts = _grouped(clips, pad_noise, lambda batch, nz: engine.detect(batch, pad_noise=nz, post=post))
+    all_ts = _detect_files(lambda c, nz: engine.detect(c, pad_noise=nz, post=post), clips, isinstance(test_vad_audio, (list, tuple)), pad_noise)
     elapsed = time.time() - t0
     echo(f"RTF: {elapsed / (sum(len(c) for c in clips) / 16000):.4f}")
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
@@ -134,11 +145,8 @@ def inference_firered_aed(test_aed_audio="./vad_sample.wav", engine=None, NORMAL
                           pad_noise=None, echo=print):
     """FireRedVAD/Inference_FireRed_ONNX.py:620-742 (RUN_AED): -> (event2timestamps, event2ratio) per file."""
     from . import firered
-    files = _as_list(test_aed_audio)
-    engine = firered.FireRedEngine(engine) if (engine is None or isinstance(engine, (str, dict))) else engine      # None raises (checkpoints.resolve)
-    clips = [audio_io.load_wav(f, 16000) for f in files]
-    if NORMALIZE_AUDIO:
-        clips = [timestamps.normalise_audio(c) for c in clips]
+    engine = _engine_of(firered.FireRedEngine, engine)
+    clips = _load(_as_list(test_aed_audio), NORMALIZE_AUDIO)
     echo("\nRunning the FireRedAED by ONNX Runtime.")
     t0 = time.time()
     post = (SMOOTH_WINDOW_SIZE, MIN_EVENT_FRAME, MAX_EVENT_FRAME, MIN_SILENCE_FRAME, MERGE_SILENCE_FRAME, EXTEND_SPEECH_FRAME)
@@ -164,11 +172,8 @@ def inference_firered_stream(test_vad_audio="./vad_sample.wav", engine=None, NOR
                              MAX_SPEECH_FRAME_STREAM=2000, MIN_SILENCE_FRAME_STREAM=20, STREAM_CHUNK_SAMPLES=2560, echo=print):
     """FireRedVAD/Inference_FireRed_ONNX.py:744-840 (RUN_STREAM_VAD): -> [(start_s, end_s)] per file."""
     from . import firered
-    files = _as_list(test_vad_audio)
-    engine = firered.FireRedEngine(engine, STREAM_CHUNK_SAMPLES) if (engine is None or isinstance(engine, (str, dict))) else engine
-    clips = [audio_io.load_wav(f, 16000) for f in files]
-    if NORMALIZE_AUDIO:
-        clips = [timestamps.normalise_audio(c) for c in clips]
+    engine = _engine_of(firered.FireRedEngine, engine, STREAM_CHUNK_SAMPLES)
+    clips = _load(_as_list(test_vad_audio), NORMALIZE_AUDIO)
     echo("\nRunning the FireRedStreamVAD by ONNX Runtime.")
     t0 = time.time()
     post = (SMOOTH_WINDOW_SIZE, STREAM_VAD_THRESHOLD, PAD_START_FRAME, MIN_SPEECH_FRAME_STREAM, MAX_SPEECH_FRAME_STREAM,
@@ -191,19 +196,14 @@ def inference_marblenet(test_vad_audio="./vad_sample.wav", engine=None, save_tim
                         MERGE_SILENCE_FRAME=3, EXTEND_SPEECH_FRAME=0, INPUT_AUDIO_LENGTH=None, pad_noise=None, echo=print):
     """NVIDIA_.../Inference_NVIDIA_MarbleNet_VAD_ONNX.py:120-422 (dynamic axis: one window per clip)."""
     from . import marblenet
-    files = _as_list(test_vad_audio)
-    engine = marblenet.MarbleNetEngine(engine) if (engine is None or isinstance(engine, (str, dict))) else engine
-    clips = [audio_io.load_wav(f, 16000) for f in files]
-    if NORMALIZE_AUDIO:
-        clips = [timestamps.normalise_audio(c) for c in clips]
+    engine = _engine_of(marblenet.MarbleNetEngine, engine)
+    clips = _load(_as_list(test_vad_audio), NORMALIZE_AUDIO)
     echo("\nRunning the NVIDIA_VAD by ONNX Runtime.")
     t0 = time.time()
     post = (SMOOTH_WINDOW_SIZE, SPEAKING_SCORE, MIN_SPEECH_FRAME, MAX_SPEECH_FRAME, MIN_SILENCE_FRAME,
             MERGE_SILENCE_FRAME, EXTEND_SPEECH_FRAME)
-    if isinstance(test_vad_audio, (list, tuple)):          # files of any lengths: one ragged batch
-        all_ts = engine.detect(clips, window_len=INPUT_AUDIO_LENGTH, pad_noise=pad_noise, post=post)
-    else:
-        all_ts = _grouped(clips, pad_noise, lambda batch, nz: engine.detect(batch, window_len=INPUT_AUDIO_LENGTH, pad_noise=nz, post=post))
+    all_ts = _detect_files(lambda c, nz: engine.detect(c, window_len=INPUT_AUDIO_LENGTH, pad_noise=nz, post=post), clips,
+                           isinstance(test_vad_audio, (list, tuple)), pad_noise)
     elapsed = time.time() - t0
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
 
@@ -216,7 +216,7 @@ def inference_dfsmn(test_near_end_audio="./examples/nearend_mic.wav", test_far_e
     mask-net VAD -> look-ahead vote -> timestamps (both text files).  Lists of paths run as a batch of clip pairs."""
     from . import dfsmn
     nears, fars = _as_list(test_near_end_audio), _as_list(test_far_end_audio)
-    engine = dfsmn.DfsmnEngine(engine) if (engine is None or isinstance(engine, (str, dict))) else engine
+    engine = _engine_of(dfsmn.DfsmnEngine, engine)
     echo(f"\nTest Input Near_End Audio: {test_near_end_audio}\nTest Input Far_End Audio: {test_far_end_audio}")
     pairs = []
     for pn, pf in zip(nears, fars):                 # files are read before the clock starts, like the reference script
@@ -224,17 +224,10 @@ def inference_dfsmn(test_near_end_audio="./examples/nearend_mic.wav", test_far_e
         n = min(len(a), len(f))
         pairs.append(np.stack([a[:n], f[:n]]))
     t0 = time.time()
-    by_len = {}
-    for k, pr in enumerate(pairs):
-        by_len.setdefault(pr.shape[1], []).append(k)
-    all_ts = [None] * len(pairs)
-    for idx in by_len.values():                     # one device batch per group of equal-length pairs
-        near, far = np.stack([pairs[k][0] for k in idx]), np.stack([pairs[k][1] for k in idx])
-        nzn, nzf = _stack_noise(pad_noise_near, idx), _stack_noise(pad_noise_far, idx)      # each side independently, either may be None
-        res = engine.detect(near, far, nzn, nzf, fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION,
-                            speaking_score=SPEAKING_SCORE, silence_score=SILENCE_SCORE)
-        for k, r in zip(idx, res):
-            all_ts[k] = r
+    # one device batch per group of equal-length pairs; the noise of each side independently, either may be None
+    all_ts = _grouped(pairs, (pad_noise_near, pad_noise_far), lambda pr, nzn, nzf: engine.detect(
+        pr[:, 0], pr[:, 1], nzn, nzf, fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION,
+        speaking_score=SPEAKING_SCORE, silence_score=SILENCE_SCORE))
     elapsed = time.time() - t0
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_near_end_audio, (list, tuple)), elapsed, echo)
 

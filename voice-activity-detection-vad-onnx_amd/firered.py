@@ -10,9 +10,11 @@ import numpy as np
 from . import _lib
 from . import checkpoints as _checkpoints
 from . import frontend as _frontend
+from . import ragged as _ragged
 from . import vadpost as _vadpost
 from . import weights as _weights
-from .fsmn import _Meta, pad_to_window_grid
+from .clips import gather_tracks, pad_batch, track_segments
+from .session import Session, _Meta, require_int16
 
 SAMPLE_RATE, WINDOW_LENGTH, HOP_LENGTH = 16000, 400, 160
 STREAM_CHUNK_SAMPLES = 2560          # 160 ms (Export_FireRedVAD.py:52-53)
@@ -117,7 +119,6 @@ class FireRedEngine:
     def ragged(self, clips, pad_noise=None, device=True):
         """The packed batch of `clips` (list of 1-D int16 arrays of any lengths) on this engine's non-overlapping window grid
         (vadx.ragged.RaggedBatch), each padded with pad_noise row b.  device=None keeps it on the host."""
-        from . import ragged as _ragged
         return _ragged.RaggedBatch.from_clips(clips, self.L, self.L, pad_noise, None, self.device if device is True else device)
 
     def run_ragged(self, rb):
@@ -130,32 +131,24 @@ class FireRedEngine:
             rb.to(self.device)
         return self._run_logmel(self.fe.logmel(rb.gather(), 1, self.L))
 
-    def _ragged_tracks(self, rb, probs, n_frames, channel):
-        """One output channel of `probs` as tracks f32 [B, max n_frames] (vadx_tracks_gather): row b = the first n_frames[b] frames of
-        clip b's windows laid end to end, zeros after them -- the input of one vadx_vadpost launch."""
-        t = self.torch
-        stride = max(int(n_frames.max()), 1)
-        tracks = t.empty((len(rb), stride), dtype=t.float32, device=self.device)
-        nfd = t.from_numpy(np.ascontiguousarray(n_frames, dtype=np.int32)).to(self.device)
-        with t.cuda.device(self.device):
-            _lib.check(_lib.lib().vadx_tracks_gather(probs.data_ptr(), self.odim * self.T, channel * self.T, self.T, rb.win_first.data_ptr(),
-                                                     nfd.data_ptr(), len(rb), tracks.data_ptr(), stride, _lib.stream_ptr()))
-        return tracks
-
-    def _detect_ragged(self, clips, pad_noise, post, return_probs):
-        rb = self.ragged(clips, pad_noise)
-        probs = self.run_ragged(rb)
-        B = len(rb)
-        nf = np.minimum([valid_frame_count(int(n), self.in_sample_rate) for n in rb.lengths], rb.windows.astype(np.int64) * self.T)
-        pp = _vadpost.VadPostprocessor(*post, device=self.device)
-        track = self._ragged_tracks(rb, probs, nf, 0)
-        dec, segs, counts = pp.process_batch(track, n_frames=nf)
-        segs, counts = segs.cpu().numpy(), counts.cpu().numpy()
-        out = [pp.segments_to_seconds(segs[b, :counts[b]].tolist(), int(nf[b]), int(rb.lengths[b]) / self.in_sample_rate) if nf[b] else []
-               for b in range(B)]
-        if return_probs:
-            return out, [track[b, :nf[b]] for b in range(B)], [dec[b, :nf[b]] for b in range(B)]
-        return out
+    def _track_source(self, clips, pad_noise, sample_rate):
+        """Run the net over whole clips -> (channel, n_frames int64 [B] (host), durations in seconds [B]): `channel(k)` is output k as
+        tracks f32 [B, frames] on the device, row b valid up to n_frames[b] = min(clip b's snip-edge frames, its windows' frames).
+        A list (or tuple) of 1-D clips takes the ragged route (`run_ragged`, one vadx_tracks_gather per channel: [B, max(n_frames, 1)],
+        zeros past n_frames[b]); an array [B, N] the rectangular one (`run`: [B, n_frames], cut from the windows laid end to end).
+        sample_rate: what a sample count means in frames and in seconds -- `detect` passes in_sample_rate, the AED driver 16 kHz."""
+        if isinstance(clips, (list, tuple)):
+            rb = self.ragged(clips, pad_noise)
+            probs = self.run_ragged(rb)
+            nf = np.minimum([valid_frame_count(int(n), sample_rate) for n in rb.lengths], rb.windows.astype(np.int64) * self.T)
+            return (lambda k: gather_tracks(self.device, probs, self.odim * self.T, k * self.T, self.T, rb.win_first, nf),
+                    nf, [int(n) / sample_rate for n in rb.lengths])
+        B, n = np.asarray(clips).shape
+        padded, W = pad_batch(clips, self.L, self.L, pad_noise)
+        probs = self.run(padded, W).view(B, W, self.odim, self.T)
+        nvalid = min(valid_frame_count(n, sample_rate), W * self.T)     # 10 s clips give 980 of the 998 snip-edge frames
+        return (lambda k: probs[:, :, k, :].reshape(B, W * self.T)[:, :nvalid].contiguous(),
+                np.full(B, nvalid, dtype=np.int64), [n / sample_rate] * B)
 
     def run_from_host(self, host_i16, windows_per_clip=1, chunk_clips=256, feed=None):
         """`run` fed from HOST memory (int16 [B, W*L], ideally pinned: vadx.feed.pin), uploads overlapped with compute
@@ -239,25 +232,14 @@ class FireRedEngine:
         A LIST (or tuple) of 1-D clips of any lengths runs as one ragged batch (`run_ragged`, one vadx_vadpost launch); clip b's
         result is that of `detect(clip_b[None, :], pad_noise=row_b[None, :])[0]`, its seconds computed with its own duration;
         return_probs then gives per-clip LISTS of tracks and decisions, each cut to its clip's frame count."""
+        channel, nf, durations = self._track_source(clips_i16, pad_noise, self.in_sample_rate)
+        track = channel(0)
+        out, dec = track_segments(_vadpost.VadPostprocessor(*post, device=self.device), track, nf, durations)
+        if not return_probs:
+            return out
         if isinstance(clips_i16, (list, tuple)):
-            return self._detect_ragged(clips_i16, pad_noise, post, return_probs)
-        clips = np.asarray(clips_i16)
-        B, n = clips.shape
-        rows = [pad_to_window_grid(clips[b], self.L, self.L, None if pad_noise is None else pad_noise[b]) for b in range(B)]
-        padded = np.stack(rows)
-        W = padded.shape[1] // self.L
-        probs = self.run(padded, W).view(B, W, self.odim, self.T)
-        nvalid = valid_frame_count(n, self.in_sample_rate)
-        track = probs[:, :, 0, :].reshape(B, W * self.T)[:, :nvalid].contiguous()
-        pp = _vadpost.VadPostprocessor(*post, device=self.device)
-        if nvalid == 0:
-            out = [[] for _ in range(B)]
-            return (out, track) if return_probs else out
-        dec, segs, counts = pp.process_batch(track)
-        segs, counts = segs.cpu().numpy(), counts.cpu().numpy()
-        nfr = track.shape[1]     # min(valid frames, W*T): 10 s clips give 980 of the 998 snip-edge frames
-        out = [pp.segments_to_seconds(segs[b, :counts[b]].tolist(), nfr, n / self.in_sample_rate) for b in range(B)]
-        return (out, track, dec) if return_probs else out
+            return out, [track[b, :nf[b]] for b in range(len(nf))], [dec[b, :nf[b]] for b in range(len(nf))]
+        return (out, track, dec) if track.shape[1] else (out, track)      # an array without a valid frame: no decisions are returned
 
 
 IDX2EVENT = {0: "speech", 1: "singing", 2: "music"}      # Inference_FireRed_ONNX.py:632
@@ -267,74 +249,44 @@ def _detect_events(self, clips_i16, pad_noise=None, thresholds=(0.4, 0.5, 0.5), 
                    return_probs=False):
     """FireRedAED driver (Inference_FireRed_ONNX.py:620-742): equal-length clips int16 [B,N] through an
     odim == 3 model -> per clip (event2timestamps, event2ratio).  `post` = (smooth, min_event, max_event,
-    min_silence, merge_silence, extend); `thresholds` per event in IDX2EVENT order."""
+    min_silence, merge_silence, extend); `thresholds` per event in IDX2EVENT order.
+    A LIST (or tuple) of 1-D clips of any lengths runs as one ragged batch, per event one vadx_tracks_gather + one vadx_vadpost launch;
+    clip b's result is that of the [1, N] call on it alone.  return_probs adds the tracks: f32 [B, odim, n_frames] for an array, per
+    clip f32 [odim, n_frames[b]] for a list.  Frames and seconds are counted at 16 kHz here, whatever in_sample_rate is."""
     if self.odim != len(IDX2EVENT):
         raise ValueError(f"the AED driver needs a {len(IDX2EVENT)}-output model, this one has odim = {self.odim}")
-    if isinstance(clips_i16, (list, tuple)):
-        return _detect_events_ragged(self, clips_i16, pad_noise, thresholds, post, return_probs)
-    clips = np.asarray(clips_i16)
-    B, n = clips.shape
-    rows = [pad_to_window_grid(clips[b], self.L, self.L, None if pad_noise is None else pad_noise[b]) for b in range(B)]
-    padded = np.stack(rows)
-    W = padded.shape[1] // self.L
-    probs = self.run(padded, W).view(B, W, self.odim, self.T)
-    nvalid = valid_frame_count(n)
-    tracks = probs.permute(0, 2, 1, 3).reshape(B, self.odim, W * self.T)[:, :, :nvalid].contiguous()
-    nfr = tracks.shape[2]
-    out = [({}, {}) for _ in range(B)]
-    for idx, event in IDX2EVENT.items():
-        thr = thresholds[idx]
-        pp = _vadpost.VadPostprocessor(post[0], thr, *post[1:], device=self.device)
-        track = tracks[:, idx, :].contiguous()
-        if nfr == 0:
-            for b in range(B):
-                out[b][0][event], out[b][1][event] = [], 0.0
-            continue
-        _, segs, counts = pp.process_batch(track)
-        segs, counts = segs.cpu().numpy(), counts.cpu().numpy()
-        ratio = (track >= np.float32(thr)).float().mean(dim=1).cpu().numpy()
-        for b in range(B):
-            out[b][0][event] = pp.segments_to_seconds(segs[b, :counts[b]].tolist(), nfr, n / SAMPLE_RATE)
-            out[b][1][event] = round(float(ratio[b]), 3)
-    return (out, tracks) if return_probs else out
-
-
-def _detect_events_ragged(self, clips, pad_noise, thresholds, post, return_probs):
-    """`_detect_events` for a LIST of 1-D clips of any lengths: one ragged batch, per event one vadx_tracks_gather + one vadx_vadpost
-    launch; clip b's result is that of the [1, N] call on it alone.  return_probs adds per clip the tracks f32 [odim, n_frames[b]]."""
     t = self.torch
-    rb = self.ragged(clips, pad_noise)
-    probs = self.run_ragged(rb)
-    B = len(rb)
-    nf = np.minimum([valid_frame_count(int(n)) for n in rb.lengths], rb.windows.astype(np.int64) * self.T)
+    channel, nf, durations = self._track_source(clips_i16, pad_noise, SAMPLE_RATE)
+    B = len(nf)
     out = [({}, {}) for _ in range(B)]
-    tracks = []
-    live = t.arange(max(int(nf.max()), 1), device=self.device)[None, :] < t.from_numpy(nf).to(self.device)[:, None]
+    tracks, live = [], None
     for idx, event in IDX2EVENT.items():
         thr = thresholds[idx]
-        pp = _vadpost.VadPostprocessor(post[0], thr, *post[1:], device=self.device)
-        track = self._ragged_tracks(rb, probs, nf, idx)
+        track = channel(idx)
         tracks.append(track)
-        _, segs, counts = pp.process_batch(track, n_frames=nf)
-        segs, counts = segs.cpu().numpy(), counts.cpu().numpy()
-        # frames over threshold per clip: the rows are zero-filled past n_frames[b], so the columns are masked, not the values (one
-        # launch sequence, one read-back).  The [1, N] path takes torch's device mean of the 0 / 1 values, which is the exact count
-        # times the float32 reciprocal of N (not count / N: an ulp apart for some pairs); the same product here keeps the ratios
-        # bitwise those of the one-clip call (tests/test_gpu_ragged.py checks the product against torch.mean for every count)
+        segments, _ = track_segments(_vadpost.VadPostprocessor(post[0], thr, *post[1:], device=self.device), track, nf, durations)
+        # frames over threshold per clip: a ragged batch's rows are zero-filled past n_frames[b], so the columns are masked, not the
+        # values (one launch sequence, one read-back).  The ratio is the exact count times the float32 reciprocal of the frame count
+        # (not count / N: an ulp apart for some pairs), which is bitwise torch's device mean of the 0 / 1 values
+        # (tests/test_gpu_ragged.py checks the product against torch.mean for every count)
+        if live is None:
+            live = t.arange(track.shape[1], device=self.device)[None, :] < t.from_numpy(nf).to(self.device)[:, None]
         counts_over = ((track >= np.float32(thr)) & live).sum(dim=1).cpu().numpy()
         ratio = counts_over.astype(np.float32) * (np.float32(1.0) / np.maximum(nf, 1).astype(np.float32))
         for b in range(B):
-            out[b][0][event] = pp.segments_to_seconds(segs[b, :counts[b]].tolist(), int(nf[b]), int(rb.lengths[b]) / SAMPLE_RATE) if nf[b] else []
+            out[b][0][event] = segments[b]
             out[b][1][event] = round(float(ratio[b]), 3) if nf[b] else 0.0
-    if return_probs:
+    if not return_probs:
+        return out
+    if isinstance(clips_i16, (list, tuple)):
         return out, [t.stack([tr[b, :nf[b]] for tr in tracks]) for b in range(B)]
-    return out
+    return out, t.stack(tracks, dim=1)
 
 
 FireRedEngine.detect_events = _detect_events
 
 
-class FireRedSession:
+class FireRedSession(Session):
     """onnxruntime.InferenceSession look-alike: {'audio': int16 [1,1,L]} -> [probs f32 [1,odim,T]]
     (FireRedVAD/Export_FireRedVAD.py:785-807); a leading batch of windows is accepted."""
 
@@ -343,26 +295,16 @@ class FireRedSession:
         self._inputs_meta = [_Meta("audio", [1, 1, self.engine.L], "tensor(int16)")]
         self._outputs_meta = [_Meta("probs", [1, self.engine.odim, self.engine.T], "tensor(float)")]
 
-    def get_inputs(self):
-        return list(self._inputs_meta)
-
-    def get_outputs(self):
-        return list(self._outputs_meta)
-
-    def get_providers(self):
-        return ["VadxMI355XExecutionProvider"]
-
     def run(self, output_names, feeds):
         audio = np.asarray(feeds["audio"])
-        if audio.dtype != np.int16:
-            raise ValueError("Unexpected input data type. Actual: (%s) , expected: (tensor(int16))" % audio.dtype)
+        require_int16(audio)
         if audio.shape[-1] != self.engine.L:
             raise ValueError(f"Got invalid dimensions for input: audio, expected last dim {self.engine.L}")
         probs = self.engine.run(audio.reshape(-1, audio.shape[-1])).cpu().numpy()
         return [probs]
 
 
-class FireRedStreamSession:
+class FireRedStreamSession(Session):
     """Stream-VAD session look-alike: {'audio': int16 [1,1,n], 'caches_in': f32 [R,1,P,pad]} ->
     [probs f32 [1,odim,T], caches_out] (FireRedVAD/Export_FireRedVAD.py:848-872; 'audio' axis 2 is dynamic).
     The weights must have no look-ahead filter (cfg N2 == 0)."""
@@ -375,19 +317,9 @@ class FireRedStreamSession:
         self._outputs_meta = [_Meta("probs", [1, e.odim, "signal_len"], "tensor(float)"),
                               _Meta("caches_out", list(e.cache_shape), "tensor(float)")]
 
-    def get_inputs(self):
-        return list(self._inputs_meta)
-
-    def get_outputs(self):
-        return list(self._outputs_meta)
-
-    def get_providers(self):
-        return ["VadxMI355XExecutionProvider"]
-
     def run(self, output_names, feeds):
         audio, caches = np.asarray(feeds["audio"]), np.asarray(feeds["caches_in"])
-        if audio.dtype != np.int16:
-            raise ValueError("Unexpected input data type. Actual: (%s) , expected: (tensor(int16))" % audio.dtype)
+        require_int16(audio)
         if caches.dtype != np.float32 or caches.shape != self.engine.cache_shape:
             raise ValueError(f"Got invalid dimensions for input: caches_in, expected {list(self.engine.cache_shape)}")
         t = self.engine.torch

@@ -14,8 +14,11 @@ import numpy as np
 from . import _lib
 from . import checkpoints as _checkpoints
 from . import frontend as _frontend
+from . import ragged as _ragged
 from . import timestamps as _ts
 from . import weights as _weights
+from .clips import flag_timestamps, pad_batch, pad_to_window_grid  # noqa: F401  (`vadx.fsmn.pad_to_window_grid` is the name callers use)
+from .session import Session, _Meta, io_types, require_int16
 
 SAMPLE_RATE = 16000
 OUTPUT_FRAME_LENGTH = 160
@@ -37,15 +40,9 @@ def _loop_params(lb, speaking_score=0.5, silence_score=0.5, snr_threshold=10.0, 
     return lp
 
 
-def _timestamps(flags, fusion_threshold, min_speech_duration):
-    """One clip's or stream's silence flags (1-D) -> [(start_s, end_s)]: the reference's vad_to_timestamps + process_timestamps over its `saved` list."""
-    ts = _ts.vad_to_timestamps(np.asarray(flags).astype(bool), OUTPUT_FRAME_LENGTH / SAMPLE_RATE)
-    return _ts.process_timestamps(ts, fusion_threshold, min_speech_duration)
-
-
-class _Meta:
-    def __init__(self, name, shape, type_):
-        self.name, self.shape, self.type = name, shape, type_
+def _prep(normalize):
+    """The reference's peak normalisation of one clip (any numeric dtype -> int16), or None."""
+    return (lambda a: _ts.normalize_to_int16(a.astype(np.float32))) if normalize else None
 
 
 class FsmnEngine:
@@ -196,9 +193,7 @@ class FsmnEngine:
     def ragged(self, clips, pad_noise=None, normalize=True, look_backward_s=0.3, device=True):
         """The packed batch of `clips` (list of 1-D arrays of any lengths) on this engine's window grid (vadx.ragged.RaggedBatch):
         peak-normalised like the reference (normalize) and padded per clip with pad_noise row b.  device=None keeps it on the host."""
-        from . import ragged as _ragged
-        prep = (lambda a: _ts.normalize_to_int16(a.astype(np.float32))) if normalize else None
-        return _ragged.RaggedBatch.from_clips(clips, self.L, self.grid(look_backward_s)[1], pad_noise, prep,
+        return _ragged.RaggedBatch.from_clips(clips, self.L, self.grid(look_backward_s)[1], pad_noise, _prep(normalize),
                                               self.device if device is True else device)
 
     def flags_ragged(self, rb, *, order=None, return_noise=False, look_backward_s=0.3, speaking_score=0.5, silence_score=0.5,
@@ -250,47 +245,19 @@ class FsmnEngine:
         reference's unseeded np.random.normal tail padding (explicit so results are reproducible).
         A LIST (or tuple) of 1-D clips of any lengths runs as one ragged batch (`flags_ragged`); clip b's result is that of
         `detect(clip_b[None, :], pad_noise=row_b[None, :])[0]`."""
+        look_backward_s = loop_kw.get("look_backward_s", 0.3)
         if isinstance(clips_i16, (list, tuple)):
-            rb = self.ragged(clips_i16, pad_noise, normalize, loop_kw.get("look_backward_s", 0.3))
-            flags, nflags = self.flags_ragged(rb, **loop_kw)
-            flags = flags.cpu().numpy()
-            return [_timestamps(flags[b, :nflags[b]], fusion_threshold, min_speech_duration) for b in range(len(rb))]
-        clips = np.asarray(clips_i16)
-        B, n = clips.shape
-        lb, stride = self.grid(loop_kw.get("look_backward_s", 0.3))
-        rows = []
-        for b in range(B):
-            a = _ts.normalize_to_int16(clips[b].astype(np.float32)) if normalize else clips[b]
-            rows.append(pad_to_window_grid(a, self.L, stride, None if pad_noise is None else pad_noise[b]))
-        padded = np.stack(rows)
-        W = (padded.shape[1] - self.L) // stride + 1
-        flags = self.flags(self.torch.from_numpy(padded), W, **loop_kw).cpu().numpy()
-        return [_timestamps(flags[b], fusion_threshold, min_speech_duration) for b in range(B)]
+            flags, nflags = self.flags_ragged(self.ragged(clips_i16, pad_noise, normalize, look_backward_s), **loop_kw)
+        else:
+            padded, W = pad_batch(clips_i16, self.L, self.grid(look_backward_s)[1], pad_noise, _prep(normalize))
+            flags = self.flags(self.torch.from_numpy(padded), W, **loop_kw)
+            nflags = [flags.shape[1]] * flags.shape[0]
+        flags = flags.cpu().numpy()
+        return [flag_timestamps(flags[b, :nflags[b]], OUTPUT_FRAME_LENGTH / SAMPLE_RATE, fusion_threshold, min_speech_duration)
+                for b in range(flags.shape[0])]
 
 
-def pad_to_window_grid(audio_i16, window, stride, noise=None):
-    """Tail padding to the sliding-window grid with white noise at the RMS of the tail
-    (FSMN/Inference_FSMN_VAD_ONNX.py:88-99).  `noise` = standard-normal samples (seeded by the
-    caller); None draws from numpy's global RNG like the reference does."""
-    a = np.asarray(audio_i16).reshape(-1)
-    n = a.shape[0]
-    if n > window:
-        num_windows = int(np.ceil((n - window) / stride)) + 1
-        pad = (num_windows - 1) * stride + window - n
-        if pad == 0:
-            return a.copy()
-        ref = a[-pad:].astype(np.float32)
-    elif n < window:
-        pad = window - n
-        ref = a.astype(np.float32)
-    else:
-        return a.copy()
-    z = np.random.normal(loc=0.0, scale=1.0, size=pad) if noise is None else np.asarray(noise[:pad], dtype=np.float64)
-    fill = (np.sqrt(np.mean(ref * ref)) * z).astype(a.dtype)
-    return np.concatenate((a, fill))
-
-
-class FsmnSession:
+class FsmnSession(Session):
     """onnxruntime.InferenceSession look-alike for the FSMN graph (names/dtypes/shapes of
     FSMN/Export_FSMN_VAD.py:115-134); feeds may carry a leading batch of independent streams.
 
@@ -302,10 +269,7 @@ class FsmnSession:
     is identical and caches / noisy_dB differ by that single rounding (<= 2^-11 relative)."""
 
     def __init__(self, weights=None, input_audio_length=16000, device="cuda:0", io_dtype="float32", speech_2_noise_ratio=1.0):
-        if io_dtype not in ("float32", "float16"):
-            raise ValueError("io_dtype must be 'float32' or 'float16'")
-        self.io_dtype = np.float16 if io_dtype == "float16" else np.float32
-        ftype = "tensor(float16)" if io_dtype == "float16" else "tensor(float)"
+        self.io_dtype, ftype = io_types(io_dtype)
         self.engine = FsmnEngine(weights, input_audio_length, device, speech_2_noise_ratio)
         L, T = self.engine.L, self.engine.T
         cache = [1, PROJ, HIST, 1]
@@ -315,20 +279,10 @@ class FsmnSession:
         self._outputs_meta = [_Meta("score", [T], "tensor(uint8)")] + \
             [_Meta(f"cache_{i}", cache, ftype) for i in range(4)] + [_Meta("noisy_dB", [], ftype)]
 
-    def get_inputs(self):
-        return list(self._inputs_meta)
-
-    def get_outputs(self):
-        return list(self._outputs_meta)
-
-    def get_providers(self):
-        return ["VadxMI355XExecutionProvider"]
-
     def run(self, output_names, feeds):
         t = self.engine.torch
         audio = np.asarray(feeds["audio"])
-        if audio.dtype != np.int16:
-            raise ValueError("Unexpected input data type. Actual: (%s) , expected: (tensor(int16))" % audio.dtype)
+        require_int16(audio)
         for name in [f"cache_{i}" for i in range(4)] + ["one_minus_speech_threshold", "noise_average_dB"]:
             got = np.asarray(feeds[name]).dtype
             if got != self.io_dtype:       # onnxruntime refuses a feed of the wrong element type; so does this session
@@ -504,4 +458,4 @@ class FsmnStreamBatch:
         """One stream's accumulated flags (1-D, every tick so far) + the last tick's tail -> [(start_s, end_s)], the reference's
         vad_to_timestamps + process_timestamps over its `saved` list."""
         f = np.concatenate([np.asarray(a.cpu() if hasattr(a, "cpu") else a).reshape(-1) for a in (flags_so_far, tail)])
-        return _timestamps(f, fusion_threshold, min_speech_duration)
+        return flag_timestamps(f, OUTPUT_FRAME_LENGTH / SAMPLE_RATE, fusion_threshold, min_speech_duration)

@@ -13,9 +13,11 @@ import numpy as np
 from . import _lib
 from . import checkpoints as _checkpoints
 from . import frontend as _frontend
+from . import ragged as _ragged
 from . import vadpost as _vadpost
 from . import weights as _weights
-from .fsmn import _Meta, pad_to_window_grid
+from .clips import gather_tracks, pad_batch, track_segments
+from .session import Session, _Meta, io_types, require_int16
 
 SAMPLE_RATE = 16000
 OUTPUT_FRAME_SHIFT_S = 320 / 16000
@@ -138,7 +140,6 @@ class MarbleNetEngine:
 
     def ragged(self, clips, device=True):
         """The packed batch of `clips` (list of 1-D int16 arrays of any lengths; vadx.ragged.RaggedFrames).  device=None keeps it on the host."""
-        from . import ragged as _ragged
         return _ragged.RaggedFrames.from_clips(clips, self.device if device is True else device)
 
     def run_ragged(self, rf):
@@ -270,85 +271,68 @@ class MarbleNetEngine:
     def detect(self, clips_i16, window_len=None, pad_noise=None, post=(3, 0.5, 10, 1000, 10, 3, 0), return_probs=False):
         """Equal-length clips int16 [B,N] (host) -> per clip [(start_s, end_s)].  window_len None = the
         dynamic-axis mode (one window = the whole clip, up to 3600 s, :130-135).
-        A LIST (or tuple) of 1-D clips of any lengths runs as one ragged batch in either mode (`_detect_ragged`); clip b's result is
-        that of the [1, N] call on it alone, and return_probs then gives (segments, tracks f32 [B, max n_frames], decisions, n_frames)."""
-        if isinstance(clips_i16, (list, tuple)):
-            return self._detect_ragged(clips_i16, window_len, pad_noise, post, return_probs)
-        clips = np.asarray(clips_i16)
-        B, n = clips.shape
-        L = min(self.in_sample_rate * 3600, n) if window_len is None else int(window_len)
-        rows = [pad_to_window_grid(clips[b], L, L, None if pad_noise is None else pad_noise[b]) for b in range(B)]
-        padded = np.stack(rows)
-        W = padded.shape[1] // L
-        s0, s1, slen = self.run(padded, W, L)
-        valid = min(slen, s1.shape[1])
-        track = s1.view(B, W, -1)[:, :, :valid].reshape(B, W * valid).contiguous()
-        pp = _vadpost.VadPostprocessor(*post, frame_shift_s=OUTPUT_FRAME_SHIFT_S, frame_length_s=None, device=self.device)
-        dec, segs, counts = pp.process_batch(track)
-        segs, counts = segs.cpu().numpy(), counts.cpu().numpy()
-        out = [pp.segments_to_seconds(segs[b, :counts[b]].tolist(), track.shape[1], n / self.in_sample_rate) for b in range(B)]
-        return (out, track, dec) if return_probs else out
-
-    def _tracks(self, probs, win_floats, frames_per_window, win_first, n_frames):
-        """tracks f32 [B, max n_frames] (vadx_tracks_gather): row b = the first n_frames[b] scores of clip b's windows, zeros after them."""
-        t = self.torch
-        stride = max(int(n_frames.max()), 1)
-        tracks = t.empty((len(n_frames), stride), dtype=t.float32, device=self.device)
-        nfd = t.from_numpy(np.ascontiguousarray(n_frames, dtype=np.int32)).to(self.device)
-        with t.cuda.device(self.device):
-            _lib.check(_lib.lib().vadx_tracks_gather(probs.data_ptr(), win_floats, 0, frames_per_window, win_first.data_ptr(), nfd.data_ptr(),
-                                                     len(n_frames), tracks.data_ptr(), stride, _lib.stream_ptr()))
-        return tracks
-
-    def _detect_ragged(self, clips, window_len, pad_noise, post, return_probs):
-        """`detect` for a list of 1-D int16 clips of any lengths.  Dynamic axis: RaggedFrames -> logmel_ragged -> run_ragged, one
-        score per encoder frame; clips the ragged kernels do not take (longer than 3600 s: they are cut into windows; every clip when
-        the graph resamples) keep the one-call-per-length path and are spliced back in input order.  window_len = L (the static
-        export): the clips padded to their own window grids (vadx.ragged.RaggedBatch), every window through the unchanged front-end
-        and `run_features`.  Either way one vadx_tracks_gather + one vadx_vadpost launch for the batch."""
-        from . import ragged as _ragged
-        if not self.fused:
+        A LIST (or tuple) of 1-D clips of any lengths runs as one ragged batch in either mode (`_list_track`); clip b's result is
+        that of the [1, N] call on it alone, and return_probs then gives (segments, tracks f32 [B, max n_frames], decisions, n_frames).
+        Dynamic-axis clips the ragged kernels do not take (longer than 3600 s: they are cut into windows; every clip when the graph
+        resamples) keep the one-call-per-clip path and are spliced back in input order."""
+        as_list = isinstance(clips_i16, (list, tuple))
+        if as_list and not self.fused:
             raise ValueError("MarbleNetEngine.detect: a list of clips (a ragged batch) is built for the published MarbleNet 3x2x64 layout; this "
                              "engine was constructed with another `blocks` layout -- pass equal-length clips as a [B, N] array")
-        clips = [np.asarray(c) for c in clips]
-        B = len(clips)
-        if B == 0:
-            raise ValueError("a ragged batch needs at least one clip")
+        rate = self.in_sample_rate
         pp = _vadpost.VadPostprocessor(*post, frame_shift_s=OUTPUT_FRAME_SHIFT_S, frame_length_s=None, device=self.device)
+        if not as_list:
+            B, n = np.asarray(clips_i16).shape
+            L = min(rate * 3600, n) if window_len is None else int(window_len)
+            padded, W = pad_batch(clips_i16, L, L, pad_noise)
+            s0, s1, slen = self.run(padded, W, L)
+            valid = min(slen, s1.shape[1])
+            track = s1.view(B, W, -1)[:, :, :valid].reshape(B, W * valid).contiguous()
+            out, dec = track_segments(pp, track, None, [n / rate] * B)
+            return (out, track, dec) if return_probs else out
+        clips = [np.asarray(c) for c in clips_i16]
+        if len(clips) == 0:
+            raise ValueError("a ragged batch needs at least one clip")
+        odd = [b for b, c in enumerate(clips) if window_len is None and (rate != SAMPLE_RATE or c.size > rate * 3600)]
+        if not odd:
+            track, nf, lengths = self._list_track(clips, window_len, pad_noise)
+            out, dec = track_segments(pp, track, nf, [int(n) / rate for n in lengths])
+            return (out, track, dec, nf) if return_probs else out
+        rows = [None] * len(clips)                  # per clip (segments, track [n_frames[b]], decisions [n_frames[b]])
+        for b in odd:                               # today's path, one call per clip
+            o, tr, de = self.detect(clips[b].reshape(1, -1), None, None if pad_noise is None else np.asarray(pad_noise[b])[None, :], post, True)
+            rows[b] = (o[0], tr[0], de[0])
+        rag = [b for b in range(len(clips)) if b not in odd]
+        if rag:
+            track, nf, lengths = self._list_track([clips[b] for b in rag], None, None)
+            out, dec = track_segments(pp, track, nf, [int(n) / rate for n in lengths])
+            for k, b in enumerate(rag):
+                rows[b] = (out[k], track[k, :nf[k]], dec[k, :nf[k]])
+        out = [r[0] for r in rows]
+        if not return_probs:
+            return out
+        nfs = np.array([r[1].shape[0] for r in rows], dtype=np.int32)
+        return out, self._pad_rows([r[1] for r in rows], self.torch.float32), self._pad_rows([r[2] for r in rows], self.torch.int8), nfs
+
+    def _list_track(self, clips, window_len, pad_noise):
+        """A list of 1-D int16 clips of any lengths -> (track f32 [B, max n_frames] on the device, n_frames int32 [B], lengths [B]).
+        Dynamic axis: RaggedFrames -> logmel_ragged -> run_ragged, one score per encoder frame.  window_len = L (the static export):
+        the clips padded to their own window grids (vadx.ragged.RaggedBatch), every window through the unchanged front-end and
+        `run_features`.  Either way one vadx_tracks_gather, and the track is the input of one vadx_vadpost launch."""
         if window_len is None:
-            cap = self.in_sample_rate * 3600
-            rag = [b for b in range(B) if self.in_sample_rate == SAMPLE_RATE and clips[b].reshape(-1).shape[0] <= cap]
-            out, tracks, decs, nfs = [None] * B, [None] * B, [None] * B, np.zeros(B, dtype=np.int32)
-            for b in set(range(B)) - set(rag):          # today's path, one call per clip
-                o, tr, de = self.detect(clips[b].reshape(1, -1), None, None if pad_noise is None else np.asarray(pad_noise[b])[None, :], post, True)
-                out[b], tracks[b], decs[b], nfs[b] = o[0], tr[0], de[0], tr.shape[1]
-            if rag:
-                rf = self.ragged([clips[b] for b in rag])
-                _, s1, enc_first = self.run_ragged(rf)
-                nf = (rf.enc_frames - 1).astype(np.int32)           # valid_b = min(signal_len, T1_b) = T1_b - 1
-                track = self._tracks(s1, 1, 1, rf.enc_first, nf)
-                dec, segs, counts = pp.process_batch(track, n_frames=nf)
-                segs, counts = segs.cpu().numpy(), counts.cpu().numpy()
-                for k, b in enumerate(rag):
-                    out[b] = pp.segments_to_seconds(segs[k, :counts[k]].tolist(), int(nf[k]), int(rf.lengths[k]) / self.in_sample_rate) if nf[k] else []
-                    tracks[b], decs[b], nfs[b] = track[k, :nf[k]], dec[k, :nf[k]], nf[k]
-            if not return_probs:
-                return out
-            if len(rag) == B:
-                return out, track, dec, nfs
-            return out, self._pad_rows(tracks, self.torch.float32), self._pad_rows(decs, self.torch.int8), nfs
+            rf = self.ragged(clips)
+            _, s1, _ = self.run_ragged(rf)
+            nf = (rf.enc_frames - 1).astype(np.int32)           # valid_b = min(signal_len, T1_b) = T1_b - 1
+            return gather_tracks(self.device, s1, 1, 0, 1, rf.enc_first, nf), nf, rf.lengths
         L = int(window_len)
         rb = _ragged.RaggedBatch.from_clips(clips, L, L, pad_noise, None, self.device)
         s0, s1, slen = self.run_features(self.frontend(L).logmel(rb.gather(), 1, L))
         T1 = int(s1.shape[1])
         valid = min(slen, T1)
         nf = (rb.windows.astype(np.int64) * valid).astype(np.int32)
-        track = self._tracks(s1, T1, valid, rb.win_first, nf) if valid else self.torch.zeros((B, 0), dtype=self.torch.float32, device=self.device)
-        dec, segs, counts = pp.process_batch(track, n_frames=nf)
-        segs, counts = segs.cpu().numpy(), counts.cpu().numpy()
-        out = [pp.segments_to_seconds(segs[b, :counts[b]].tolist(), int(nf[b]), int(rb.lengths[b]) / self.in_sample_rate) if nf[b] else []
-               for b in range(B)]
-        return (out, track, dec, nf) if return_probs else out
+        if not valid:
+            return self.torch.zeros((len(rb), 0), dtype=self.torch.float32, device=self.device), nf, rb.lengths
+        return gather_tracks(self.device, s1, T1, 0, valid, rb.win_first, nf), nf, rb.lengths
 
     def _pad_rows(self, rows, dtype):
         """1-D device rows of different lengths -> one zero-filled matrix [B, max len]."""
@@ -359,36 +343,23 @@ class MarbleNetEngine:
         return m
 
 
-class MarbleNetSession:
+class MarbleNetSession(Session):
     """{'audio': int16 [1,1,L]} -> [score_silence [1,T,1], score_active [1,T,1], signal_len int32 [1]]
     (Export_NVIDIA_MarbleNet_VAD.py:436-457; dynamic audio length).  io_dtype="float16": I/O-compatible with the reference's
     fp16-optimised model (Optimize_ONNX.py:37-44 converts with keep_io_types=False, so the two scores leave as float16) -- the
     arithmetic here stays float32 and the scores are rounded once on the way out."""
 
     def __init__(self, weights=None, device="cuda:0", in_sample_rate=16000, io_dtype="float32"):
-        if io_dtype not in ("float32", "float16"):
-            raise ValueError("io_dtype must be 'float32' or 'float16'")
-        self.io_dtype = np.float16 if io_dtype == "float16" else np.float32
-        ftype = "tensor(float16)" if io_dtype == "float16" else "tensor(float)"
+        self.io_dtype, ftype = io_types(io_dtype)
         self.engine = MarbleNetEngine(weights, device, in_sample_rate=in_sample_rate)
         self._inputs_meta = [_Meta("audio", [1, 1, "audio_len"], "tensor(int16)")]
         self._outputs_meta = [_Meta("score_silence", [1, "signal_len", 1], ftype),
                               _Meta("score_active", [1, "signal_len", 1], ftype),
                               _Meta("signal_len", [1], "tensor(int32)")]
 
-    def get_inputs(self):
-        return list(self._inputs_meta)
-
-    def get_outputs(self):
-        return list(self._outputs_meta)
-
-    def get_providers(self):
-        return ["VadxMI355XExecutionProvider"]
-
     def run(self, output_names, feeds):
         audio = np.asarray(feeds["audio"])
-        if audio.dtype != np.int16:
-            raise ValueError("Unexpected input data type. Actual: (%s) , expected: (tensor(int16))" % audio.dtype)
+        require_int16(audio)
         s0, s1, slen = self.engine.run(audio.reshape(-1, audio.shape[-1]))
         res = {"score_silence": s0.cpu().numpy()[:, :, None].astype(self.io_dtype), "score_active": s1.cpu().numpy()[:, :, None].astype(self.io_dtype),
                "signal_len": np.array([slen], dtype=np.int32)}

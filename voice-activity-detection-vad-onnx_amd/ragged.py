@@ -1,6 +1,6 @@
 """A RAGGED batch: clips of any lengths packed into one int16 vector, with the tables the device needs to walk it.
 
-Every clip is padded to its own window grid on the host (`fsmn.pad_to_window_grid`: the reference's tail-noise arithmetic, bit-pinned
+Every clip is padded to its own window grid on the host (`clips.pad_to_window_grid`: the reference's tail-noise arithmetic, bit-pinned
 there), the padded clips are laid end to end -- each starting on a multiple of 8 samples, so that every analysis window is a whole
 number of 16-byte runs -- and uploaded ONCE.  Overlapping windows (FSMN: 16000 samples every 11040) exist only on the device, after
 vadx_windows_gather; the padding a rectangular [B, max N] batch would add to short clips is neither uploaded nor computed: the work
@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .fsmn import pad_to_window_grid
+from .clips import pad_to_window_grid
 
 ALIGN = 8            # samples: window and stride are multiples of it, so every clip starts on a 16-byte boundary of the packed vector
 
