@@ -52,7 +52,8 @@ extern "C" {
  *     Later additions under the SAME number (additive again: nothing an ABI-10 caller links against moved, and the suite's pin of this
  *     number, tests/test_fsmn_stream_cpu.py, stays as it is): the ragged-batch entry points vadx_windows_gather, vadx_fsmn_clips_ragged,
  *     vadx_tracks_gather; then MarbleNet over ragged batches: vadx_marblenet_ragged, vadx_frontend_logmel_ragged, vadx_sepconv_block_ragged,
- *     vadx_marblenet_block2_ragged, vadx_marblenet_tail_ragged.  A caller that needs them checks for the symbols (dlsym), not for a number. */
+ *     vadx_marblenet_block2_ragged, vadx_marblenet_tail_ragged; then FireRed Stream-VAD over live streams: vadx_firered_stream_state_bytes,
+ *     vadx_firered_stream_group_max, vadx_firered_stream_tick.  A caller that needs them checks for the symbols (dlsym), not for a number. */
 #define VADX_ABI_VERSION 10
 
 /* Arithmetic of the products whose one operand is a constant (every weight matrix, every DFT table) -- float32 RESULTS in all of them:
@@ -580,6 +581,50 @@ size_t vadx_stream_vadpost_state_bytes(int streams);
  * Replaces StreamVadPostprocessor.process_batch, FireRedVAD/Export_FireRedVAD.py:1161-1339 (driver Inference_FireRed_ONNX.py:788-822). */
 int vadx_stream_vadpost(const vadx_stream_vadpost_params *prm, const float *probs, int64_t probs_stride, int frames, int streams,
                         void *state, int reset, int flush, int32_t *segments, int32_t *counts, int cap, void *stream);
+
+/* Streaming FireRed (Stream-VAD for S live streams): every tick advances each stream by `chunks` chunks of cfg->frames frames,
+ * F = chunks * frames <= 112 frames in all.  What the reference's chunk loop carries -- the FIR caches it feeds back and the
+ * StreamVadPostprocessor object -- lives in a device RECORD of vadx_firered_stream_state_bytes(cfg, S) bytes.  The record is opaque
+ * except that
+ *   - its first S*R*P*pad floats are the caches [S][R][P][pad], pad = (N1 - 1) * S1: per stream the caches_in / caches_out of
+ *     vadx_firered_stream_run (there [R][streams][P][pad]);
+ *   - behind them, on the next multiple of 16 bytes, come 128 bytes per stream: the decision machine (ring buffer, sum, counters,
+ *     state) and, at byte 112 of those, a 64-bit count of the frames the stream has done since its reset;
+ *   - a record of all zero bytes is S streams in their reset state (no init call);
+ *   - its size is a multiple of 16 bytes; records are 16-byte aligned.
+ * After the front-end a tick is ONE call.  logmel f32 [S * chunks][frames][80] is the unchanged vadx_frontend_logmel over S rows of
+ * `chunks` chunks of n samples each (batch = S, windows_per_clip = chunks): every chunk's features are computed on its own, no sample is
+ * carried between chunks, as in the reference.  The `chunks` chunks of a stream are F consecutive frames to the net, which carries its
+ * caches across them: a look-back-only net over concatenated frames IS the chunked net.  cfg->N2 must be 0.
+ * state_in is never written (a tick can be recomputed from it, which the range protocol needs); state_out must not overlap it.
+ * reset (NULL or uint8 [S]): != 0 = back to the reset state before this tick.  active (NULL or uint8 [S]): 0 = no audio for this stream
+ * this tick -- its record in state_out is a bitwise copy of state_in's, a reset request is ignored, its probs are NaN, its count 0 and
+ * its open_start -1 (its logmel rows are not read).
+ * Outputs: probs f32 [S][odim][F]; segments int32 [S][cap][2] + counts [S]: the segments of channel 0 that END in this tick as 0-based
+ * (start_frame, end_frame) pairs counted from the stream's reset, exactly what vadx_stream_vadpost reports with flush = 0 (same float32
+ * operations in the same order; a count above cap = truncated, the state still advances); open_start int32 [S]: the 0-based start frame
+ * of the segment still open after the tick, or -1 -- with the frames done, (open_start, frames_done - 1) is what the reference's
+ * end-of-input rule appends, and nothing is closed by reporting it.  post->smooth_window_size <= 16.
+ * group: streams per workgroup, 1 <= group <= vadx_firered_stream_group_max(F) = 112 / F, or 0 = the library's choice.  The streams of a
+ * workgroup lie side by side in its LDS rows behind one load of the weights; every output of a stream and its bytes of state_out are
+ * bitwise independent of group, of S, of the other streams and of their masks.
+ * All three arithmetics, with the blob vadx_firered_pack_host wrote for cfg->arithmetic (a split arithmetic on widths the split
+ * kernels do not take is refused); on F32 the probabilities and caches are bitwise those of vadx_firered_stream_run.  Range protocol per
+ * tick: with an F16X2 cfg read vadx_firered_range_flag after the call and, when it is raised, call vadx_firered_stream_tick again with
+ * the BF16X3 cfg and blob on the same arguments: every byte the first call wrote is written again.
+ * Returns VADX_EINVAL, before any HIP call, for a NULL pointer (reset and active may be NULL), streams / chunks / cap < 1, F > 112, a
+ * group outside [0, 112 / F], N2 != 0, smooth_window_size > 16, or overlapping records.
+ * Replaces the body of the chunk loop, FireRedVAD/Inference_FireRed_ONNX.py:788-822 (ort_session_C.run :798-801 with its caches fed back,
+ * StreamVadPostprocessor.process_batch, FireRedVAD/Export_FireRedVAD.py:1205-1339), for S streams that arrive in pieces. */
+
+/* Bytes of the record of `streams` streams (0 for streams <= 0 or a cfg outside the limits; cfg->frames is not looked at). */
+size_t vadx_firered_stream_state_bytes(const vadx_firered_cfg *cfg, int streams);
+/* The most streams one workgroup serves at F = frames_per_tick frames per stream: 112 / F, 0 for F outside 1 .. 112. */
+int vadx_firered_stream_group_max(int frames_per_tick);
+int vadx_firered_stream_tick(const vadx_firered_cfg *cfg, const float *packed, const float *logmel, int streams, int chunks, int group,
+                             const vadx_stream_vadpost_params *post, const uint8_t *reset, const uint8_t *active,
+                             const void *state_in, void *state_out, float *probs, int32_t *segments, int32_t *counts, int cap,
+                             int32_t *open_start, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * MarbleNet building blocks: one fused launch per Jasper sub-block

@@ -928,3 +928,301 @@ extern "C" int vadx_firered_stream_run(const vadx_firered_cfg *cfg, const float 
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
+
+
+// ---- FireRed Stream-VAD for S live streams (FireRedVAD/Inference_FireRed_ONNX.py:744-822): one tick = `chunks` chunks of cfg->frames
+// frames per stream, the FIR caches and the StreamVadPostprocessor state carried in a device record.  A workgroup serves `group` streams:
+// their F = chunks * frames columns lie side by side in the LDS rows ([channel][stream slot * F + frame]), so one load of the weight
+// fragments (resident or streamed) serves all of them.  The point-wise layers are per column; the FIR of a stream reads its own cache for
+// the frames before its own first column, never a neighbour's columns; the decisions run one lane per stream once the probabilities are in
+// LDS.  Nothing a stream receives depends on `group`, on S, on its neighbours or on their masks.
+namespace vadx {
+namespace firered {
+constexpr int TK_HDR = 32;               // header words per stream: [0,26) as the stream_vadpost record, with last_start / last_end stored + 1 (so that
+                                         // zero bytes are the reset state); 28..29 frames done (int64); the rest zero
+constexpr int TK_DONE = 28;
+constexpr int TK_LDS_FLOATS = LDS_FLOATS + 2 * MAX_T;        // + slot status [MAX_T] (int) + channel-0 probabilities [MAX_T]
+
+struct TickArgs {
+    const float *logmel;
+    const unsigned char *reset, *active;
+    const unsigned *cin, *hin;           // record sections of state_in: caches [S][R][P][pad], headers [S][TK_HDR]
+    unsigned *cout, *hout;
+    float *probs;
+    int *segs, *counts, *open_start;
+    int S, F, group, cap, NC;            // NC = R * P * pad floats of cache per stream
+    StreamPostDev q;
+};
+
+// fsmn_memory_stream for the columns of `group` streams: same operations in the same order per (channel, frame); slot status 0 = no audio
+// (the columns stay zero), 1 = live, 2 = live from the reset state (zero cache)
+__device__ __forceinline__ void fsmn_memory_tick(const Dev &d, const float *__restrict__ Pk, int r, bool skip, const float *p, float *mem,
+                                                 const TickArgs &a, int g0, const int *slot) {
+    const int pad = (d.N1 - 1) * d.S1, C = d.T, F = a.F;
+    const float *cin = reinterpret_cast<const float *>(a.cin);
+    float *cout = reinterpret_cast<float *>(a.cout);
+    for (int e = threadIdx.x; e < d.P * C; e += THREADS) {
+        const int ch = e / C, c = e - ch * C, j = c / F, t = c - j * F, st = slot[j];
+        if (st == 0) continue;
+        const float *row = p + ch * M_LD + j * F, *crow = cin + (size_t)(g0 + j) * a.NC + ((size_t)r * d.P + ch) * pad, *w = Pk + d.off_lb[r] + ch * d.N1;
+        float lb = 0.f;
+        for (int k = 0; k < d.N1; ++k) {
+            const int i = t + k * d.S1;                       // index into cache ++ p
+            lb = fmaf(w[k], i < pad ? (st == 2 ? 0.f : crow[i]) : row[i - pad], lb);
+        }
+        float s2 = row[t] + lb;
+        if (skip) s2 += mem[ch * M_LD + c];
+        mem[ch * M_LD + c] = s2;
+    }
+    const int per = d.P * pad;
+    for (int e = threadIdx.x; e < a.group * per; e += THREADS) {      // new cache = last `pad` entries of cache ++ p
+        const int j = e / per, x = e - j * per, ch = x / pad, i = x - ch * pad, src = F + i, st = slot[j];
+        if (st == 0) continue;
+        const size_t at = (size_t)(g0 + j) * a.NC + (size_t)r * per + x;
+        cout[at] = src < pad ? (st == 2 ? 0.f : cin[at - i + src]) : p[ch * M_LD + j * F + src - pad];
+    }
+}
+
+// One stream's decisions over its F new probabilities: stream_vadpost_kernel's per-frame loop (flush = 0), operation for operation, on the
+// tick record's header.
+__device__ __forceinline__ void tick_decide(const TickArgs &a, int s, bool fresh, const float *pr) {
+    const StreamPostDev &q = a.q;
+    const unsigned *hi = a.hin + (size_t)s * TK_HDR;
+    unsigned *ho = a.hout + (size_t)s * TK_HDR;
+    float buf[SP_MAXWS];
+    float sum = 0.f;
+    int pos = 0, cnt = 0, fc = 0, st = 0, sp = 0, si = 0, hit = 0, last_start = -1, last_end = -1;
+    long long done = 0;
+#pragma unroll
+    for (int k = 0; k < SP_MAXWS; ++k) buf[k] = fresh ? 0.f : __uint_as_float(hi[k]);
+    if (!fresh) {
+        sum = __uint_as_float(hi[16]); pos = (int)hi[17]; cnt = (int)hi[18]; fc = (int)hi[19]; st = (int)hi[20]; sp = (int)hi[21]; si = (int)hi[22];
+        hit = (int)hi[23]; last_start = (int)hi[24] - 1; last_end = (int)hi[25] - 1;
+        done = (long long)(((unsigned long long)hi[TK_DONE + 1] << 32) | hi[TK_DONE]);
+    }
+    int *out = a.segs + (size_t)s * a.cap * 2, n = 0;
+    auto emit = [&](int x, int y) { if (n < a.cap) { out[2 * n] = x; out[2 * n + 1] = y; } ++n; };
+    for (int t = 0; t < a.F; ++t) {
+        const float p = pr[t];
+        ++fc;
+        float sm = p;
+        if (q.ws > 1) {
+            float old = 0.f;
+#pragma unroll
+            for (int k = 0; k < SP_MAXWS; ++k) if (k == pos) { old = buf[k]; buf[k] = p; }      // (register array: no dynamic indexing)
+            sum = __fadd_rn(sum, __fsub_rn(p, old));
+            pos = pos + 1 == q.ws ? 0 : pos + 1;
+            if (cnt < q.ws) ++cnt;
+            sm = __fdiv_rn(sum, (float)cnt);
+        }
+        const bool speech = sm >= q.thr;
+        int e0 = 0, e1 = 0;
+        bool ended = false;
+        if (hit) { last_start = fc; hit = 0; }           // a forced split re-opens a segment on the next frame
+        auto close = [&]() { e0 = last_start; e1 = fc; ended = true; last_start = -1; last_end = fc; };
+        if (st == 0) {
+            if (speech) { st = 1; sp = 1; } else { ++si; sp = 0; }
+        } else if (st == 1) {
+            if (speech) {
+                ++sp;
+                if (sp >= q.min_sp) {
+                    st = 2;
+                    int b = fc - sp + 1 - q.pad_start;
+                    b = b < 1 ? 1 : b;
+                    last_start = b > last_end + 1 ? b : last_end + 1;
+                    si = 0;
+                }
+            } else { st = 0; si = 1; sp = 0; }
+        } else {
+            ++sp;
+            if (speech) {
+                st = 2; si = 0;
+                if (sp >= q.max_sp) { hit = 1; sp = 0; close(); }
+            } else if (st == 2) { st = 3; si = 1; }
+            else {
+                ++si;
+                if (si >= q.min_si) { st = 0; sp = 0; close(); }
+            }
+        }
+        if (ended && e0 > 0) emit(e0 - 1 > 0 ? e0 - 1 : 0, e1 - 1 > 0 ? e1 - 1 : 0);
+    }
+    done += a.F;
+    a.counts[s] = n;
+    a.open_start[s] = last_start > 0 ? last_start - 1 : -1;      // what the end-of-input rule would report, without closing it
+#pragma unroll
+    for (int k = 0; k < SP_MAXWS; ++k) ho[k] = __float_as_uint(buf[k]);
+    ho[16] = __float_as_uint(sum); ho[17] = pos; ho[18] = cnt; ho[19] = fc; ho[20] = st; ho[21] = sp; ho[22] = si; ho[23] = hit;
+    ho[24] = last_start + 1; ho[25] = last_end + 1; ho[26] = 0; ho[27] = 0;
+    ho[TK_DONE] = (unsigned)((unsigned long long)done & 0xffffffffull); ho[TK_DONE + 1] = (unsigned)((unsigned long long)done >> 32);
+    ho[30] = 0; ho[31] = 0;
+}
+
+template <int AR>
+__global__ __launch_bounds__(THREADS, 2) void firered_stream_tick_kernel(Dev d, const float *__restrict__ Pk, TickArgs a) {
+    constexpr bool SPLIT = AR != vadx::VADX_AR_F32;
+    typedef typename vadx::SchemeFor<AR>::type SC;
+    float amax = 0.f;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *mem = lds, *p = lds + MEM_F, *h = p + P_F, *pr0 = h + H_F + MAX_T;
+    int *slot = reinterpret_cast<int *>(h + H_F);
+    const int tid = threadIdx.x, g0 = blockIdx.x * a.group, C = d.T, F = a.F;      // d.T = group * F columns
+    if (tid < a.group) {
+        const int s = g0 + tid;
+        const bool live = s < a.S && (!a.active || a.active[s]);
+        slot[tid] = !live ? 0 : (a.reset && a.reset[s]) ? 2 : 1;
+    }
+    __syncthreads();
+    // streams without audio: the record bit for bit, NaN probabilities, no segment
+    bool any = false;
+    for (int j = 0; j < a.group; ++j) any |= slot[j] != 0;
+    for (int e = tid; e < a.group * a.NC; e += THREADS) {
+        const int j = e / a.NC;
+        if (g0 + j < a.S && slot[j] == 0) { const size_t at = (size_t)g0 * a.NC + e; a.cout[at] = a.cin[at]; }
+    }
+    for (int e = tid; e < a.group * d.odim * F; e += THREADS) {
+        const int j = e / (d.odim * F);
+        if (g0 + j < a.S && slot[j] == 0) a.probs[(size_t)g0 * d.odim * F + e] = __uint_as_float(0x7fc00000u);
+    }
+    if (tid < a.group && g0 + tid < a.S && slot[tid] == 0) {
+        const size_t at = (size_t)(g0 + tid) * TK_HDR;
+        for (int k = 0; k < TK_HDR; ++k) a.hout[at + k] = a.hin[at + k];
+        a.counts[g0 + tid] = 0;
+        a.open_start[g0 + tid] = -1;
+    }
+    if (!any) return;
+    // stage log-mel channel-first into `mem` rows 0..79, the streams' chunks side by side; columns without audio and >= C are zero
+    const float *lm = a.logmel + (size_t)g0 * F * NMEL;
+    for (int e = tid; e < MAX_T * NMEL; e += THREADS) {
+        const int c = e / NMEL, mel = e - c * NMEL;
+        float v = 0.f;
+        if (c < C && slot[c / F] != 0) v = lm[(size_t)c * NMEL + mel];
+        mem[mel * M_LD + c] = v;
+    }
+    for (int e = tid; e < MAXP * M_LD; e += THREADS) p[e] = 0.f;
+    __syncthreads();
+    if (SPLIT) pointwise_pair_split<SC, 3>(d, Pk + d.q_fc1, Pk + d.off_fc1b, NMEL, mem, Pk + d.q_fc2, Pk + d.off_fc2b, true, p, h, amax);
+    else pointwise_pair(d, Pk + d.off_fc1, Pk + d.off_fc1b, NMEL / 16, mem, Pk + d.off_fc2, Pk + d.off_fc2b, 1, p, h);
+    for (int e = tid; e < MAXP * M_LD; e += THREADS) mem[e] = 0.f;
+    __syncthreads();
+    fsmn_memory_tick(d, Pk, 0, false, p, mem, a, g0, slot);
+    __syncthreads();
+    for (int r = 1; r < d.R; ++r) {
+        if (SPLIT) pointwise_pair_split<SC, 4>(d, Pk + d.q_bfc1[r], Pk + d.off_bfc1b[r], d.Pp, mem, Pk + d.q_bfc2[r], nullptr, false, p, h, amax);
+        else pointwise_pair(d, Pk + d.off_bfc1[r], Pk + d.off_bfc1b[r], d.Pp / 16, mem, Pk + d.off_bfc2[r], nullptr, 0, p, h);
+        fsmn_memory_tick(d, Pk, r, true, p, mem, a, g0, slot);
+        __syncthreads();
+    }
+    auto put = [&](int o, int c, float z) {        // logit of output o at column c -> probs [S][odim][F], channel 0 also to the decision lanes
+        const int j = c / F;
+        if (slot[j] == 0) return;
+        const float v = sigmoidf_(z);
+        a.probs[((size_t)(g0 + j) * d.odim + o) * F + c - j * F] = v;
+        if (o == 0) pr0[c] = v;
+    };
+    if (SPLIT && d.M == 1) {          // as firered_kernel: dnn + output head as one more point-wise pair, logits in p[o][c]
+        pointwise_pair_split<SC, 4>(d, Pk + d.q_dnn0, Pk + d.off_dnnb[0], d.Pp, mem, Pk + d.q_head, Pk + d.off_headb, false, p, h, amax);
+        __syncthreads();
+        for (int e = tid; e < d.odim * C; e += THREADS) {
+            const int o = e / C, c = e - o * C;
+            put(o, c, p[o * M_LD + c]);
+        }
+    } else {                          // as firered_stream_kernel, tile by tile
+        float *h2 = p;
+        for (int f0 = 0; f0 < C; f0 += 32) {
+            const bool half = (C - f0) <= 16;
+            LayerArgs l0{Pk + d.off_dnn[0], d.Pp, d.Hp / 16, 1, d.Pp / 16, 0, 0, Pk + d.off_dnnb[0], 1, mem, M_LD, f0, h, H_LD, 0, nullptr, nullptr};
+            if (half) layer<1, false>(l0); else layer<2, false>(l0);
+            __syncthreads();
+            float *cur = h, *nxt = h2;
+            for (int m = 1; m < d.M; ++m) {
+                LayerArgs lm_{Pk + d.off_dnn[m], d.Hp, d.Hp / 16, 1, d.Hp / 16, 0, 0, Pk + d.off_dnnb[m], 1, cur, H_LD, 0, nxt, H_LD, 0, nullptr, nullptr};
+                if (half) layer<1, false>(lm_); else layer<2, false>(lm_);
+                __syncthreads();
+                float *tmp = cur; cur = nxt; nxt = tmp;
+            }
+            float *lg = p + MAXH * H_LD;            // behind h2
+            {   LayerArgs o{Pk + d.off_out, d.Hp, 1, 1, d.Hp / 16, 0, 0, Pk + d.off_outb, 0, cur, H_LD, 0, lg, H_LD, 0, nullptr, nullptr};
+                if (half) layer<1, false>(o); else layer<2, false>(o); }
+            __syncthreads();
+            if (tid < 32 * d.odim) {
+                const int t = tid & 31, o = tid >> 5;
+                if (f0 + t < C) put(o, f0 + t, lg[o * H_LD + t]);
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    if (tid < a.group && slot[tid] != 0) tick_decide(a, g0 + tid, slot[tid] == 2, pr0 + tid * F);
+    if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
+}
+}  // namespace firered
+}  // namespace vadx
+
+static size_t tick_cache_words(const Dev &d, int streams) {      // the cache section, rounded to 16 bytes
+    return ((size_t)streams * d.R * d.P * (d.N1 - 1) * d.S1 + 3) & ~(size_t)3;
+}
+
+extern "C" size_t vadx_firered_stream_state_bytes(const vadx_firered_cfg *cfg, int streams) {
+    Dev d;
+    if (!cfg || streams <= 0) return 0;
+    vadx_firered_cfg c = *cfg;
+    c.frames = 1;                            // the record does not depend on the chunk length
+    if (derive(&c, &d)) return 0;
+    return (tick_cache_words(d, streams) + (size_t)streams * TK_HDR) * 4;
+}
+
+extern "C" int vadx_firered_stream_group_max(int frames_per_tick) {
+    return frames_per_tick >= 1 && frames_per_tick <= MAX_T ? MAX_T / frames_per_tick : 0;
+}
+
+// group = 0: the most streams per workgroup that still leave every compute unit a workgroup (256 CUs, one workgroup each: the LDS rows
+// take a whole CU) -- fewer workgroups than that idle part of the device, and the weight stream is cheap next to an idle CU
+static int tick_group_auto(int streams, int gmax) {
+    int g = streams / 256;
+    return g < 1 ? 1 : (g > gmax ? gmax : g);
+}
+
+extern "C" int vadx_firered_stream_tick(const vadx_firered_cfg *cfg, const float *packed, const float *logmel, int streams, int chunks,
+                                        int group, const vadx_stream_vadpost_params *post, const uint8_t *reset, const uint8_t *active,
+                                        const void *state_in, void *state_out, float *probs, int32_t *segments, int32_t *counts, int cap,
+                                        int32_t *open_start, void *stream) {
+    Dev d;
+    VADX_REQUIRE(cfg && packed && logmel && post && state_in && state_out && probs && segments && counts && open_start,
+                 "vadx_firered_stream_tick: NULL argument");
+    VADX_REQUIRE(streams >= 1 && chunks >= 1 && cap >= 1, "vadx_firered_stream_tick: streams=%d chunks=%d cap=%d must be at least 1", streams, chunks, cap);
+    VADX_REQUIRE(derive(cfg, &d) == 0, "vadx_firered_stream_tick: unsupported config (or a split arithmetic on widths the split kernels do not take)");
+    VADX_REQUIRE(cfg->N2 == 0, "vadx_firered_stream_tick: the streaming model has no look-ahead filter (N2 must be 0)");
+    const long long F = (long long)chunks * d.T;
+    VADX_REQUIRE(F <= MAX_T, "vadx_firered_stream_tick: chunks * frames = %lld exceeds the %d frames of a tick", F, MAX_T);
+    const int gmax = MAX_T / (int)F;
+    VADX_REQUIRE(group >= 0 && group <= gmax, "vadx_firered_stream_tick: group=%d outside [0, %d] (0 = the library's choice)", group, gmax);
+    const int ws = post->smooth_window_size < 1 ? 1 : post->smooth_window_size;
+    VADX_REQUIRE(ws <= SP_MAXWS, "vadx_firered_stream_tick: smooth_window_size %d > %d", ws, SP_MAXWS);
+    const size_t cache_words = tick_cache_words(d, streams), bytes = (cache_words + (size_t)streams * TK_HDR) * 4;
+    {   const uintptr_t x = reinterpret_cast<uintptr_t>(state_in), y = reinterpret_cast<uintptr_t>(state_out);
+        VADX_REQUIRE(x + bytes <= y || y + bytes <= x, "vadx_firered_stream_tick: state_in and state_out overlap");
+        VADX_REQUIRE(((x | y) & 15) == 0, "vadx_firered_stream_tick: records must be 16-byte aligned"); }
+    TickArgs a;
+    a.logmel = logmel; a.reset = reset; a.active = active;
+    a.cin = static_cast<const unsigned *>(state_in); a.hin = a.cin + cache_words;
+    a.cout = static_cast<unsigned *>(state_out); a.hout = a.cout + cache_words;
+    a.probs = probs; a.segs = segments; a.counts = counts; a.open_start = open_start;
+    a.S = streams; a.F = (int)F; a.group = group ? group : tick_group_auto(streams, gmax); a.cap = cap;
+    a.NC = d.R * d.P * (d.N1 - 1) * d.S1;
+    a.q.ws = ws; a.q.thr = post->speech_threshold; a.q.pad_start = post->pad_start_frame > ws ? post->pad_start_frame : ws;
+    a.q.min_sp = post->min_speech_frame; a.q.max_sp = post->max_speech_frame; a.q.min_si = post->min_silence_frame;
+    d.T = a.group * a.F;                     // the kernel's columns: the group's streams side by side
+    const unsigned grid = (unsigned)((streams + a.group - 1) / a.group);
+    const size_t lds = TK_LDS_FLOATS * sizeof(float);
+    VADX_DYN_LDS(firered_stream_tick_kernel<0>, lds);
+    VADX_DYN_LDS(firered_stream_tick_kernel<1>, lds);
+    VADX_DYN_LDS(firered_stream_tick_kernel<2>, lds);
+    if (d.arith == vadx::VADX_AR_H2)
+        hipLaunchKernelGGL(firered_stream_tick_kernel<2>, dim3(grid), dim3(THREADS), lds, static_cast<hipStream_t>(stream), d, packed, a);
+    else if (d.arith == vadx::VADX_AR_B3)
+        hipLaunchKernelGGL(firered_stream_tick_kernel<1>, dim3(grid), dim3(THREADS), lds, static_cast<hipStream_t>(stream), d, packed, a);
+    else
+        hipLaunchKernelGGL(firered_stream_tick_kernel<0>, dim3(grid), dim3(THREADS), lds, static_cast<hipStream_t>(stream), d, packed, a);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}

@@ -169,8 +169,11 @@ def inference_firered_aed(test_aed_audio="./vad_sample.wav", engine=None, NORMAL
 
 def inference_firered_stream(test_vad_audio="./vad_sample.wav", engine=None, NORMALIZE_AUDIO=False, SMOOTH_WINDOW_SIZE=5,
                              STREAM_VAD_THRESHOLD=0.4, PAD_START_FRAME=5, MIN_SPEECH_FRAME_STREAM=8,
-                             MAX_SPEECH_FRAME_STREAM=2000, MIN_SILENCE_FRAME_STREAM=20, STREAM_CHUNK_SAMPLES=2560, echo=print):
-    """FireRedVAD/Inference_FireRed_ONNX.py:744-840 (RUN_STREAM_VAD): -> [(start_s, end_s)] per file."""
+                             MAX_SPEECH_FRAME_STREAM=2000, MIN_SILENCE_FRAME_STREAM=20, STREAM_CHUNK_SAMPLES=2560, echo=print,
+                             batched=False):
+    """FireRedVAD/Inference_FireRed_ONNX.py:744-840 (RUN_STREAM_VAD): -> [(start_s, end_s)] per file.
+    batched=True with a list of files runs them as the streams of one batch (FireRedEngine.stream_detect over the list: all files tick
+    together on the chunk grid) instead of one file after the other."""
     from . import firered
     engine = _engine_of(firered.FireRedEngine, engine, STREAM_CHUNK_SAMPLES)
     clips = _load(_as_list(test_vad_audio), NORMALIZE_AUDIO)
@@ -179,8 +182,11 @@ def inference_firered_stream(test_vad_audio="./vad_sample.wav", engine=None, NOR
     post = (SMOOTH_WINDOW_SIZE, STREAM_VAD_THRESHOLD, PAD_START_FRAME, MIN_SPEECH_FRAME_STREAM, MAX_SPEECH_FRAME_STREAM,
             MIN_SILENCE_FRAME_STREAM)
     results = []
-    for c in clips:
-        results += engine.stream_detect(c[None, :], chunk=STREAM_CHUNK_SAMPLES, post=post)
+    if batched and isinstance(test_vad_audio, (list, tuple)):
+        results = engine.stream_detect(list(clips), chunk=STREAM_CHUNK_SAMPLES, post=post)
+    else:
+        for c in clips:
+            results += engine.stream_detect(c[None, :], chunk=STREAM_CHUNK_SAMPLES, post=post)
     elapsed = time.time() - t0
     for seg, c in zip(results, clips):
         echo(f"\nStream-VAD Results:\n  Audio duration: {len(c) / 16000:.3f}s\n  Segments detected: {len(seg)}\n\n  Timestamps in Second:")

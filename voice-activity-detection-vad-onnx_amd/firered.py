@@ -201,7 +201,11 @@ class FireRedEngine:
 
     def stream_detect(self, clips_i16, chunk=STREAM_CHUNK_SAMPLES, post=(5, 0.4, 5, 8, 2000, 20), return_probs=False):
         """Equal-length clips int16 [B,N] (host): every clip is one stream, all streams advance one chunk per
-        launch (Inference_FireRed_ONNX.py:788-822) -> per clip [(start_s, end_s)]."""
+        launch (Inference_FireRed_ONNX.py:788-822) -> per clip [(start_s, end_s)].
+        A LIST (or tuple) of 1-D clips of any lengths runs as the streams of one `FireRedStreamBatch` on the chunk grid until the longest
+        is done (`_stream_detect_list`); return_probs then gives a per-clip LIST of tracks."""
+        if isinstance(clips_i16, (list, tuple)):
+            return self._stream_detect_list(clips_i16, chunk, post, return_probs)
         t = self.torch
         clips = np.asarray(clips_i16)
         B, n = clips.shape
@@ -225,6 +229,54 @@ class FireRedEngine:
         out = _vadpost.StreamVadPostprocessorBatch(*post, streams=B, device=self.device).process_batch(track_dev)
         track = track_dev.cpu().numpy()
         return (out, track) if return_probs else out
+
+    def _stream_detect_list(self, clips, chunk, post, return_probs):
+        """`stream_detect` over clips of any lengths: clip b is stream b of one FireRedStreamBatch.  At every position of the chunk grid the
+        streams that still have a whole chunk tick together; a stream's short last chunk runs in a tick of its own length (zero-padded to
+        400 samples if shorter), streams elsewhere inactive.  A padded last chunk adds one frame; where that frame lies beyond
+        valid_frame_count(len) -- a clip of whole chunks plus fewer than 80 samples, or one under 400 samples -- the reference cuts it off
+        the track again, so the tick is skipped.  Per clip: the events of all ticks, then the segment still open at its end."""
+        t = self.torch
+        clips = [np.ascontiguousarray(np.asarray(c).reshape(-1), dtype=np.int16) for c in clips]
+        S, chunk = len(clips), int(chunk)
+        if S == 0:
+            return ([], []) if return_probs else []
+        if chunk < WINDOW_LENGTH:
+            raise ValueError(f"a stream chunk needs at least {WINDOW_LENGTH} samples, got {chunk}")
+        lens = np.array([len(c) for c in clips], dtype=np.int64)
+        grid = -(-int(lens.max()) // chunk) if lens.max() else 0
+        host = np.zeros((S, grid * chunk + WINDOW_LENGTH), dtype=np.int16)        # zeros behind every clip: the padding of a short last chunk
+        for b, c in enumerate(clips):
+            host[b, :len(c)] = c
+        dev = t.from_numpy(host).to(self.device)
+        it = FireRedStreamBatch(self, S, post)
+        out, tracks = [[] for _ in range(S)], [[] for _ in range(S)]
+        done = np.zeros(S, dtype=np.int64)                                        # frames each stream has run
+        valid = np.array([valid_frame_count(int(n), self.in_sample_rate) for n in lens], dtype=np.int64)
+        for g in range(grid):
+            pos = g * chunk
+            left = lens - pos
+            ticks = [(chunk, left >= chunk)] + [(int(n), left == n) for n in sorted(set(left[(left > 0) & (left < chunk)].tolist()))]
+            for n, act in ticks:
+                width = max(n, WINDOW_LENGTH)
+                frames = valid_frame_count(width, self.in_sample_rate)
+                if n < WINDOW_LENGTH:
+                    act = act & (done + frames <= valid)
+                if not act.any():
+                    continue
+                probs, events = it.step(dev[:, pos:pos + width].contiguous(), active=None if act.all() else act)
+                done[act] += frames
+                track = probs[:, 0, :].cpu().numpy() if return_probs else None
+                for b in np.flatnonzero(act):
+                    out[b] += events[b]
+                    if return_probs:
+                        tracks[b].append(track[b])
+        for b, seg in enumerate(it.open_segments()):
+            if seg is not None:
+                out[b].append(seg)
+        if not return_probs:
+            return out
+        return out, [np.concatenate(tr) if tr else np.zeros(0, np.float32) for tr in tracks]
 
     def detect(self, clips_i16, pad_noise=None, post=(5, 0.4, 20, 2000, 20, 5, 0), return_probs=False):
         """Equal-length clips int16 [B,N] (host) -> per clip [(start_s, end_s)] for output channel 0
@@ -284,6 +336,165 @@ def _detect_events(self, clips_i16, pad_noise=None, thresholds=(0.4, 0.5, 0.5), 
 
 
 FireRedEngine.detect_events = _detect_events
+
+HDR_WORDS, H_COUNT, H_LAST_START, H_DONE = 32, 19, 24, 28      # the record's per-stream header (csrc/firered.hip: TK_HDR, TK_DONE), in 32-bit words
+
+
+class FireRedStreamBatch:
+    """`streams` live FireRed Stream-VAD streams on the device (vadx_firered_stream_tick): every `step` advances each stream by `chunks`
+    chunks of audio.  What the reference's chunk loop carries (FireRedVAD/Inference_FireRed_ONNX.py:775-822) -- the FIR caches it feeds
+    back and the StreamVadPostprocessor object -- stays in a device record (two, ping-ponged); per tick the front-end and ONE net launch
+    run, and only the events come back.  `post` = the reference class's constructor arguments (smooth window, threshold, pad_start,
+    min_speech, max_speech, min_silence, in frames); cap = segments a stream may end in one tick (None: one per frame, the most there
+    can be).  On "h2" every tick reads the range flag and, when it is raised, recomputes the tick on "split" from the same record into
+    the same record."""
+
+    def __init__(self, engine, streams, post=(5, 0.4, 5, 8, 2000, 20), cap=None):
+        if not isinstance(engine, FireRedEngine):
+            raise TypeError("FireRedStreamBatch needs a vadx.firered.FireRedEngine")
+        self.engine, self.streams, self.cap = engine, int(streams), cap
+        if self.streams <= 0:
+            raise ValueError(f"streams={streams} must be positive")
+        if engine.cfg.N2 != 0:
+            raise ValueError(f"the streaming model has no look-ahead filter, these weights have N2 = {engine.cfg.N2}")
+        if max(1, int(post[0])) > 16:
+            raise ValueError(f"smooth_window_size {post[0]} > 16: the device record's ring buffer holds 16 frames")
+        self._prm = _lib.StreamVadPostParams(int(post[0]), float(np.float32(post[1])), *(int(v) for v in post[2:6]))
+        self.frames_per_second = 100
+        t = engine.torch
+        R, _, P, pad = engine.cache_shape
+        self._cache_floats = self.streams * R * P * pad
+        self._hdr_at = (self._cache_floats + 3) // 4 * 16             # the headers start on the next multiple of 16 bytes
+        nb = _lib.lib().vadx_firered_stream_state_bytes(C.byref(engine.cfg), self.streams)
+        if nb != self._hdr_at + self.streams * HDR_WORDS * 4:
+            raise _lib.VadxError(f"vadx_firered_stream_state_bytes = {nb}: not the record this binding was written for")
+        self._rec = [t.zeros(nb, dtype=t.uint8, device=engine.device) for _ in range(2)]
+        self._cur = 0
+        self._pending = np.zeros(self.streams, dtype=bool)       # reset_states() requests not yet applied to an active tick
+        self.open_start = None                                   # int32 [S] (device) of the last tick: 0-based start frame of the open segment, -1 = none
+
+    @property
+    def record(self):
+        """The current device record (uint8); its first S*R*P*pad floats are the FIR caches [S, R, P, pad]."""
+        return self._rec[self._cur]
+
+    @property
+    def caches(self):
+        R, _, P, pad = self.engine.cache_shape
+        return self.record[:self._cache_floats * 4].view(self.engine.torch.float32).view(self.streams, R, P, pad)
+
+    def headers(self, record=None):
+        """int32 view [S, 32] of the per-stream headers of `record` (default: the current one): the decision machine and frames done."""
+        record = self.record if record is None else record
+        return record[self._hdr_at:].view(self.engine.torch.int32).view(self.streams, HDR_WORDS)
+
+    def stream_bytes(self, record, s):
+        """Every byte of `record` that belongs to stream s (caches, header), as one uint8 tensor."""
+        n = self._cache_floats // self.streams * 4
+        return self.engine.torch.cat([record[s * n:(s + 1) * n], record[self._hdr_at + s * HDR_WORDS * 4:self._hdr_at + (s + 1) * HDR_WORDS * 4]])
+
+    @property
+    def frames_done(self):
+        """int64 [S] (host): frames each stream has done since its reset, read from the device record.  Frame i of a stream's next
+        tick is frame frames_done + i of its audio, 10 ms per frame."""
+        return self.headers()[:, H_DONE:H_DONE + 2].contiguous().view(self.engine.torch.int64)[:, 0].cpu().numpy()
+
+    def load_record(self, record):
+        """Continue from a saved copy of `record` (uint8, same streams and weights): the bytes are copied into the current record."""
+        r = record if self.engine.torch.is_tensor(record) else self.engine.torch.from_numpy(np.ascontiguousarray(record))
+        if r.dtype != self.engine.torch.uint8 or r.numel() != self.record.numel():
+            raise ValueError(f"record must be uint8 [{self.record.numel()}], got {r.dtype} [{r.numel()}]")
+        self.record.copy_(r.reshape(-1))
+        self._pending[:] = False
+
+    def reset_states(self, streams=None):
+        """None = every stream; else stream indices or a bool mask [S].  Applies at the next tick in which the stream is active."""
+        if streams is None:
+            self._pending[:] = True
+            return
+        idx = np.asarray(streams.cpu() if hasattr(streams, "cpu") else streams)
+        if idx.dtype == bool:
+            self._pending |= self._mask(idx, "reset mask")
+        else:
+            self._pending[idx.astype(np.int64).reshape(-1)] = True
+
+    def _mask(self, m, name):
+        a = np.asarray(m.cpu() if hasattr(m, "cpu") else m).astype(bool).reshape(-1)
+        if a.shape != (self.streams,):
+            raise ValueError(f"{name} must have shape ({self.streams},), got {a.shape}")
+        return a
+
+    def open_segments(self):
+        """Per stream the (start_s, end_s) of the segment still open after its last frame, or None: what the reference's process_batch
+        appends at the end of its input (Export_FireRedVAD.py:1336-1338).  Read from the record; nothing is closed."""
+        h = self.headers().cpu().numpy()
+        inv_fps = 1.0 / self.frames_per_second
+        start, count = h[:, H_LAST_START].astype(np.int64) - 1, h[:, H_COUNT].astype(np.int64)
+        return [(max(0, int(a) - 1) * inv_fps, (int(n) - 1) * inv_fps) if a > 0 else None for a, n in zip(start, count)]
+
+    def step(self, samples_i16, chunks=1, reset=None, active=None, group=0):
+        """samples_i16 int16 [S, chunks * n] (host or device, numpy or torch): each row holds that stream's next `chunks` chunks of n
+        samples (400 <= n; the call's width sets n) -> (probs f32 [S, odim, chunks * frames] on the device, events): per stream the
+        [(start_s, end_s)] of the segments that ended in this tick, at 100 frames per second.  Every chunk's features are computed on
+        its own, as the reference computes them; the net carries its caches across the chunks.  reset / active: bool [S] or None; an
+        inactive stream keeps its record bit for bit, ignores a reset, has NaN probabilities and no events.  group: streams per
+        workgroup (0 = the library's choice); no result depends on it."""
+        eng, t = self.engine, self.engine.torch
+        k, S = int(chunks), self.streams
+        x = samples_i16 if t.is_tensor(samples_i16) else t.from_numpy(np.ascontiguousarray(samples_i16))
+        if x.dtype != t.int16:
+            raise ValueError(f"samples must be int16, got {x.dtype}")
+        if k < 1:
+            raise ValueError(f"chunks={chunks} must be at least 1")
+        if x.dim() != 2 or x.shape[0] != S or x.shape[1] % k:
+            raise ValueError(f"samples must be [{S}, chunks * n], got {tuple(x.shape)} at chunks={k}")
+        n = x.shape[1] // k
+        if n < WINDOW_LENGTH:
+            raise ValueError(f"a stream chunk needs at least {WINDOW_LENGTH} samples, got {n}")
+        T = valid_frame_count(n, eng.in_sample_rate)
+        F = k * T
+        if F > MAX_FRAMES:
+            raise ValueError(f"a stream tick holds at most {MAX_FRAMES} frames, {k} chunks of {n} samples are {F}")
+        act = np.ones(S, dtype=bool) if active is None else self._mask(active, "active")
+        req = (self._pending | self._mask(reset, "reset") if reset is not None else self._pending) & act      # resets this tick applies
+        gmax = MAX_FRAMES // F                                    # vadx_firered_stream_group_max
+        if not 0 <= int(group) <= gmax:
+            raise ValueError(f"group={group} outside [0, {gmax}] at {F} frames per tick")
+        fe = eng._frontend_for(n)
+        logmel = fe.logmel(x.to(eng.device), k, n)
+        act_d = None if active is None else t.from_numpy(act.astype(np.uint8)).to(eng.device)
+        reset_d = t.from_numpy(req.astype(np.uint8)).to(eng.device) if req.any() else None
+        cap = int(self.cap) if self.cap else F                    # F: a forced split per frame is the most a tick can end
+        probs = t.empty((S, eng.odim, F), dtype=t.float32, device=eng.device)
+        segs = t.empty((S, cap, 2), dtype=t.int32, device=eng.device)
+        counts = t.empty((S,), dtype=t.int32, device=eng.device)
+        opened = t.empty((S,), dtype=t.int32, device=eng.device)
+        src, dst = self._rec[self._cur], self._rec[1 - self._cur]
+        Lb = _lib.lib()
+
+        def launch(mode, cfg, packed):
+            c = _lib.FireRedCfg.from_buffer_copy(cfg)
+            c.frames = T
+            with t.cuda.device(eng.device):
+                _lib.check(Lb.vadx_firered_stream_tick(C.byref(c), packed.data_ptr(), logmel.data_ptr(), S, k, int(group), C.byref(self._prm),
+                                                       None if reset_d is None else reset_d.data_ptr(),
+                                                       None if act_d is None else act_d.data_ptr(), src.data_ptr(), dst.data_ptr(),
+                                                       probs.data_ptr(), segs.data_ptr(), counts.data_ptr(), cap, opened.data_ptr(),
+                                                       _lib.stream_ptr()))
+        eng.blobs.guarded(launch)
+        self._cur = 1 - self._cur
+        self._pending &= ~act
+        self.open_start = opened
+        cn = counts.cpu().numpy()
+        used = int(cn.max())
+        if used > cap:
+            raise _lib.VadxError(f"FireRedStreamBatch: {used} segments ended in one tick, cap={cap} (the record has advanced)")
+        sg = segs[:, :used].cpu().numpy() if used else np.zeros((S, 0, 2), np.int32)      # only the used prefix of the table travels
+        inv_fps = 1.0 / self.frames_per_second
+        events = [[] for _ in range(S)]
+        for s in np.flatnonzero(cn).tolist():                     # most streams end nothing in most ticks
+            events[s] = [(int(a) * inv_fps, int(b) * inv_fps) for a, b in sg[s, :cn[s]].tolist()]
+        return probs, events
 
 
 class FireRedSession(Session):
