@@ -53,7 +53,9 @@ extern "C" {
  *     number, tests/test_fsmn_stream_cpu.py, stays as it is): the ragged-batch entry points vadx_windows_gather, vadx_fsmn_clips_ragged,
  *     vadx_tracks_gather; then MarbleNet over ragged batches: vadx_marblenet_ragged, vadx_frontend_logmel_ragged, vadx_sepconv_block_ragged,
  *     vadx_marblenet_block2_ragged, vadx_marblenet_tail_ragged; then FireRed Stream-VAD over live streams: vadx_firered_stream_state_bytes,
- *     vadx_firered_stream_group_max, vadx_firered_stream_tick.  A caller that needs them checks for the symbols (dlsym), not for a number. */
+ *     vadx_firered_stream_group_max, vadx_firered_stream_tick; then FSMN windows of any length: vadx_fsmn_long_workspace_bytes,
+ *     vadx_fsmn_window_stats_long, vadx_fsmn_run_long, vadx_fsmn_clips_long.  A caller that needs them checks for the symbols (dlsym), not
+ *     for a number. */
 #define VADX_ABI_VERSION 10
 
 /* Arithmetic of the products whose one operand is a constant (every weight matrix, every DFT table) -- float32 RESULTS in all of them:
@@ -337,7 +339,8 @@ int vadx_frontend_stft_ft(const vadx_frontend_cfg *cfg, const float *packed, con
 typedef struct vadx_fsmn_dims {          /* FunASR FSMN(input 400, proj 128, lorder 20, 4 layers pinned in-tree) */
     int   input_affine_dim, linear_dim, output_affine_dim, output_dim;   /* external config: 140/250/140/248 */
     int   frames;                         /* T = window_len // 160 + 1 (101); vadx_fsmn_run takes T <= 128 (window_len <= 20479), the clips, ragged
-                                           * and stream entry points T <= 112 (window_len <= 17919); more is VADX_EINVAL */
+                                           * and stream entry points T <= 112 (window_len <= 17919); more is VADX_EINVAL there.  The *_long
+                                           * entry points take T <= VADX_FSMN_LONG_MAX_FRAMES */
     float speech_2_noise_ratio;           /* FSMN/Export_FSMN_VAD.py:34,87-92 */
     int   arithmetic;                     /* VADX_ARITH_* of the dense layers (0 = AUTO = BF16X3: float32's exponent range, nothing to check; F16X2
                                            * is for callers that read vadx_fsmn_range_flag with the results and recompute a flagged batch on
@@ -496,6 +499,46 @@ int vadx_fsmn_clips_ragged(const vadx_fsmn_dims *dims, const float *packed, cons
                            int n_windows, int max_windows, const int32_t *win_first, const int32_t *order,
                            const vadx_fsmn_loop_params *lp, float *cache_ws, uint8_t *flags, int64_t flag_stride, float *noise_trace,
                            void *stream);
+
+/* Long windows (FSMN, opt-in): INPUT_AUDIO_LENGTH is a plain constant of FSMN/Export_FSMN_VAD.py which the driver reads back from the
+ * session (FSMN/Inference_FSMN_VAD_ONNX.py:73-80); an export at 160 000 scores a 10 s clip as ONE window of 1 001 frames.  The entry
+ * points above keep a window's scores in LDS and stop at 128 / 112 frames; the three below take any 1 <= frames <=
+ * VADX_FSMN_LONG_MAX_FRAMES (a 10-minute window, window_len <= 9 600 000; longer audio goes on the window grid).  One workgroup still
+ * walks a window tile by tile with the FIR caches carried from tile to tile; the window's P(silence) and gate bits live in `workspace`
+ * rows (8 bytes per frame, read back by the workgroup that wrote them).  At frames <= 112 the results are bit for bit those of the
+ * entry points above.  Same dims, blob, arithmetics and range protocol.  Each returns VADX_EINVAL with a message that names the
+ * argument, before any HIP call, for a NULL pointer or workspace, frames out of range, or counts that do not fit each other.
+ * Plain-C sequence for B padded clips of W windows: vadx_fsmn_window_stats_long, vadx_frontend_logmel_means (unchanged),
+ * vadx_fsmn_clips_long with win_first = NULL. */
+#define VADX_FSMN_LONG_MAX_FRAMES 60001
+/* Bytes of `workspace` for vadx_fsmn_run_long (rows = batch) and vadx_fsmn_clips_long (rows = clips); 0 for rows < 1 or frames outside
+ * [1, VADX_FSMN_LONG_MAX_FRAMES].  Contents need no initialisation and carry nothing between calls. */
+size_t vadx_fsmn_long_workspace_bytes(int rows, int frames);
+/* vadx_fsmn_window_stats for windows of any length >= 512 and any alignment, with a grid of (window, block of frames) so that a single
+ * long window fills the chip (vadx_fsmn_window_stats gives a window above 16 384 samples to one workgroup, twice).  means: the exact
+ * 64-bit integer sum, one float32 rounding -- bit for bit vadx_frontend_window_means; db: vadx_fsmn_energy's per-sample expression in
+ * another summation order (float32 rounding apart).  workspace: 8 bytes per window, 8-byte aligned (vadx_fsmn_long_workspace_bytes(
+ * batch * windows_per_clip, frames) is more than enough).  VADX_EINVAL also for a row_stride that does not hold the windows.
+ * Replaces what vadx_fsmn_window_stats does, FSMN/Export_FSMN_VAD.py:76-79, 93-97, for the window of a long export. */
+int vadx_fsmn_window_stats_long(const int16_t *audio, int64_t row_stride, int64_t win_stride, int batch, int windows_per_clip,
+                                int window_len, int frames, float *means, float *db, void *workspace, void *stream);
+/* vadx_fsmn_run for dims->frames up to VADX_FSMN_LONG_MAX_FRAMES: same feeds and fetches; with psil the window's P(silence) is written
+ * straight to it.  workspace: vadx_fsmn_long_workspace_bytes(batch, dims->frames) bytes, 4-byte aligned.
+ * Replaces ort_session_A.run(...), FSMN/Inference_FSMN_VAD_ONNX.py:177-187, for a long export. */
+int vadx_fsmn_run_long(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db,
+                       const float *const cache_in[4], float *const cache_out[4], const float *thr, const float *noise_db, int batch,
+                       uint8_t *score, float *noisy_db, float *psil, void *workspace, void *stream);
+/* vadx_fsmn_clips_ragged for dims->frames up to VADX_FSMN_LONG_MAX_FRAMES, and vadx_fsmn_clips too: win_first == NULL is the rectangular
+ * batch, max_windows windows for every clip (n_windows = batch * max_windows, logmel / db / noise_trace [batch][max_windows], flags
+ * [batch][flag_stride] with flag_stride >= max_windows * (T - look_backward) + look_backward).  With win_first the tables, the 255
+ * fill and the guard are vadx_fsmn_clips_ragged's: a lying entry leaves its row of 255s and touches nothing; batch <= n_windows <=
+ * batch * max_windows.  look_backward in [0, frames - 1): the windows of a grid must advance.  workspace:
+ * vadx_fsmn_long_workspace_bytes(batch, dims->frames) bytes, 4-byte aligned.
+ * Replaces the while-loop + tail, FSMN/Inference_FSMN_VAD_ONNX.py:176-234, for a long export. */
+int vadx_fsmn_clips_long(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db, int batch,
+                         int n_windows, int max_windows, const int32_t *win_first, const int32_t *order,
+                         const vadx_fsmn_loop_params *lp, float *cache_ws, uint8_t *flags, int64_t flag_stride, float *noise_trace,
+                         void *workspace, void *stream);
 
 /* Per-window scores -> one track per clip.  probs f32 [n_windows][win_floats]; a window's `frames_per_window` scores of interest start
  * at float `chan_offset` of its row (FireRed: probs [n_windows][odim][T], win_floats = odim * T, channel c = chan_offset / T).  Row b

@@ -192,6 +192,11 @@ SIGNATURES = {
     "vadx_fsmn_stream_run": (_I, [C.POINTER(FsmnDims), _P, _P, _P, _I, _I, C.POINTER(FsmnLoopParams), _P, _P, _P, _P, _P, _P, _P, _P]),
     "vadx_windows_gather": (_I, [_P, _L, _P, _I, _I, _P, _P]),
     "vadx_fsmn_clips_ragged": (_I, [C.POINTER(FsmnDims), _P, _P, _P, _I, _I, _I, _P, _P, C.POINTER(FsmnLoopParams), _P, _P, _L, _P, _P]),
+    "vadx_fsmn_long_workspace_bytes": (_Z, [_I, _I]),
+    "vadx_fsmn_window_stats_long": (_I, [_P, _L, _L, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "vadx_fsmn_run_long": (_I, [C.POINTER(FsmnDims), _P, _P, _P, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_void_p * 4),
+                                _P, _P, _I, _P, _P, _P, _P, _P]),
+    "vadx_fsmn_clips_long": (_I, [C.POINTER(FsmnDims), _P, _P, _P, _I, _I, _I, _P, _P, C.POINTER(FsmnLoopParams), _P, _P, _L, _P, _P, _P]),
     "vadx_tracks_gather": (_I, [_P, _L, _I, _I, _P, _P, _I, _P, _I, _P]),
     "vadx_firered_packed_floats": (_Z, [C.POINTER(FireRedCfg)]),
     "vadx_firered_range_flag": (_I, [C.POINTER(FireRedCfg), _P, _I, _P, _P, _P]),

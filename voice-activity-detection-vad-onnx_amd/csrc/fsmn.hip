@@ -469,15 +469,15 @@ __device__ __forceinline__ float gate(const Dev &d, const float *ps, const float
     return tot / cnt;                      // 0/0 -> NaN like torch's mean of an empty tensor
 }
 
-// One window: its tiles in order, P(silence) of its T frames into Small<AR>::ps
+// One window: its tiles in order, P(silence) of its T frames into ps[0 .. T): Small<AR>::ps (T <= MAX_T), or global memory (a long window)
 template <int AR>
-__device__ __forceinline__ void run_chunk(const Dev &d, const float *Pk, const float *lm, const float *const *cin,
-                                          float *const *cout, float *lds, float &amax) {
+__device__ __forceinline__ void run_chunk_to(const Dev &d, const float *Pk, const float *lm, const float *const *cin,
+                                             float *const *cout, float *lds, float *ps, float &amax) {
     constexpr bool SPLIT = AR != vadx::VADX_AR_F32;
     typedef typename vadx::SchemeFor<AR>::type SC;
     float *bufA = lds, *bufB = lds + BUFA, *bufP = bufB + BUFB;
     const Small<AR> sm(lds);
-    float *ps = sm.ps, *red = sm.red;
+    float *red = sm.red;
     unsigned char *smem = reinterpret_cast<unsigned char *>(lds);
     int f0 = 0;
     bool first = true;
@@ -497,6 +497,12 @@ __device__ __forceinline__ void run_chunk(const Dev &d, const float *Pk, const f
         }
         first = false;
     }
+}
+
+template <int AR>
+__device__ __forceinline__ void run_chunk(const Dev &d, const float *Pk, const float *lm, const float *const *cin,
+                                          float *const *cout, float *lds, float &amax) {
+    run_chunk_to<AR>(d, Pk, lm, cin, cout, lds, Small<AR>(lds).ps, amax);
 }
 
 struct RunArgs {
@@ -624,6 +630,133 @@ __global__ __launch_bounds__(THREADS, 2) void fsmn_clips_ragged_kernel(Dev d, co
     if (first < 0 || last <= first || last - first > c.max_windows || last > c.n_windows) return;
     clip_loop<AR>(d, Pk, c.lp, c.logmel + (size_t)first * d.T * NMEL, c.db + (size_t)first * d.T, c.cache + (size_t)b * CACHE_FLOATS,
                   last - first, c.flags + (size_t)b * c.flag_stride, c.noise_trace ? c.noise_trace + first : nullptr, lds, amax);
+    if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
+}
+
+// ---- long windows: any T up to MAX_T_LONG frames (opt-in entry points; the kernels above are untouched) ---------------------------------
+// What bounds T above is Small's ps / sc / cnt, a whole window's P(silence), gate bits and vote counts in LDS.  Here a window's ps and sc
+// are rows of a global workspace (L2-resident: 8 bytes per frame), written and read back by the SAME workgroup around a barrier; the tile
+// walk, the caches carried from tile to tile and the gate are the code above, given other pointers.  The vote needs no count per frame:
+// one running count of the gate bits in [i, i + lb) moves along the window.
+constexpr int MAX_T_LONG = VADX_FSMN_LONG_MAX_FRAMES;
+constexpr int VOTE_CH = 256;             // frames per step of the vote: their gate bits are staged in `red`, their flags in `cnt`
+static_assert(2 * VOTE_CH <= SM_SC - SM_RED && VOTE_CH <= (SMALL - SM_CNT) * 4 && NW <= SM_RED - SM_PS, "the long vote's staging in the small block");
+static int long_row(int T) { return (T + 63) & ~63; }                   // floats of one ps or sc row
+struct LongWs { float *base; int row; };                                 // [rows][2][row]: ps, sc
+
+struct RunLongArgs { RunArgs r; LongWs ws; };
+
+// fsmn_run_kernel for a window of any length: P(silence) goes straight to the caller's psil rows when they are asked for
+template <int AR>
+__global__ __launch_bounds__(THREADS, 2) void fsmn_run_long_kernel(Dev d, const float *__restrict__ Pk, RunLongArgs a) {
+    float amax = 0.f;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int b = blockIdx.x;
+    const RunArgs &r = a.r;
+    const float *cin[NLAYER]; float *cout[NLAYER];
+#pragma unroll
+    for (int l = 0; l < NLAYER; ++l) { cin[l] = r.cin[l] + (size_t)b * PROJ * HIST; cout[l] = r.cout[l] + (size_t)b * PROJ * HIST; }
+    float *row = a.ws.base + (size_t)b * 2 * a.ws.row;
+    float *ps = r.psil ? r.psil + (size_t)b * d.T : row;
+    run_chunk_to<AR>(d, Pk, r.logmel + (size_t)b * d.T * NMEL, cin, cout, lds, ps, amax);
+    if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
+    __threadfence_block();                 // ps was written by other threads of this workgroup
+    __syncthreads();
+    const Small<AR> sm(lds);
+    const float noisy = gate(d, ps, r.db + (size_t)b * d.T, r.thr[b], r.noise_db[b], r.score + (size_t)b * d.T, nullptr, row + a.ws.row, sm.red);
+    if (threadIdx.x == 0) r.noisy_db[b] = noisy;
+}
+
+// clip_loop for windows of any length: ps and sc are this clip's workspace rows.  The vote's count of window frame i is
+// #{ j in [1, lb) : sc[i+j] != 0 } = run - sc[i], run = the gate bits in [i, i + lb): exact small integers, the same value clip_loop sums.
+// Thread 0 walks VOTE_CH frames at a time over bits staged in LDS (cur = sc[i], ent = sc[i + lb], the bit that enters the count).
+template <int AR>
+__device__ __forceinline__ void clip_loop_long(const Dev &d, const float *__restrict__ Pk, const LoopArgs &c, const float *logmel, const float *db,
+                                               float *cbase, int W, unsigned char *fl, float *noise_trace, float *lds, float *ps, float *sc,
+                                               float &amax) {
+    const int tid = threadIdx.x;
+    const Small<AR> sm(lds);
+    float *red = sm.red, *cur = sm.red, *ent = sm.red + VOTE_CH, *wsum = sm.ps;
+    unsigned char *out = reinterpret_cast<unsigned char *>(sm.cnt);
+    for (int e = tid; e < CACHE_FLOATS; e += THREADS) cbase[e] = 0.f;
+    __syncthreads();
+    const float *cin[NLAYER]; float *cout[NLAYER];
+#pragma unroll
+    for (int l = 0; l < NLAYER; ++l) { cin[l] = cbase + l * PROJ * HIST; cout[l] = cbase + l * PROJ * HIST; }
+    float noise = c.noise0;
+    int silence = 1;                       // carried by thread 0
+    for (int k = 0; k < W; ++k) {
+        run_chunk_to<AR>(d, Pk, logmel + (size_t)k * d.T * NMEL, cin, cout, lds, ps, amax);
+        __threadfence_block();             // ps, then sc: written by some threads of this workgroup, read by others
+        __syncthreads();
+        const float noisy = gate(d, ps, db + (size_t)k * d.T, c.thr, noise, nullptr, nullptr, sc, red);
+        __threadfence_block();
+        __syncthreads();
+        {   // the count's first value: the gate bits of frames [0, lb)   (lb <= T - 1)
+            float part = 0.f;
+            for (int j = tid; j < c.lb; j += THREADS) part += sc[j];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+            if ((tid & 63) == 0) wsum[tid >> 6] = part;
+        }
+        float run = 0.f;                   // thread 0's
+        const int nfl = k == W - 1 ? d.T : c.slide;          // the final window's tail follows the plain rule (:223-234)
+        for (int i0 = 0; i0 < nfl; i0 += VOTE_CH) {
+            const int n = min(VOTE_CH, nfl - i0);
+            if (tid < n) {
+                const int i = i0 + tid;
+                cur[tid] = sc[i];
+                ent[tid] = i + c.lb < d.T ? sc[i + c.lb] : 0.f;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                if (i0 == 0)
+                    for (int w = 0; w < NW; ++w) run += wsum[w];
+                const double inv_lb = 1.0 / (double)c.lb;
+                for (int u = 0; u < n; ++u) {
+                    const float s = cur[u];
+                    if (i0 + u < c.slide) {
+                        const float cnt = run - s;
+                        if (silence) {
+                            if (s != 0.f) silence = !((1.0 + (double)cnt) * inv_lb >= c.speaking);
+                            else silence = 1;
+                        } else {
+                            if (s != 1.f) silence = !((1.0 + (double)((c.lb - 1) - cnt)) * inv_lb <= c.silence_score);
+                            else silence = 0;
+                        }
+                        run = cnt + ent[u];
+                    } else {
+                        silence = silence ? !(s != 0.f) : (s != 1.f);
+                    }
+                    out[u] = (unsigned char)silence;
+                }
+            }
+            __syncthreads();
+            if (tid < n) fl[(size_t)k * c.slide + i0 + tid] = out[tid];
+        }
+        if (noisy > 0.0f) noise = 0.5f * ((noise + noisy) + c.snr);
+        if (noise_trace && tid == 0) noise_trace[k] = noise;
+        __syncthreads();
+    }
+}
+
+struct ClipLongArgs { RaggedArgs r; LongWs ws; };
+
+// Whole clips of long windows, rectangular (win_first == NULL: max_windows windows for every clip) or ragged, one workgroup per clip.
+// The table guard is fsmn_clips_ragged_kernel's.
+template <int AR>
+__global__ __launch_bounds__(THREADS, 2) void fsmn_clips_long_kernel(Dev d, const float *__restrict__ Pk, ClipLongArgs a) {
+    float amax = 0.f;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const RaggedArgs &c = a.r;
+    const int b = c.order ? c.order[blockIdx.x] : (int)blockIdx.x;
+    if (b < 0 || b >= c.batch) return;
+    const int first = c.win_first ? c.win_first[b] : b * c.max_windows, last = c.win_first ? c.win_first[b + 1] : first + c.max_windows;
+    if (first < 0 || last <= first || last - first > c.max_windows || last > c.n_windows) return;
+    float *row = a.ws.base + (size_t)b * 2 * a.ws.row;
+    clip_loop_long<AR>(d, Pk, c.lp, c.logmel + (size_t)first * d.T * NMEL, c.db + (size_t)first * d.T, c.cache + (size_t)b * CACHE_FLOATS,
+                       last - first, c.flags + (size_t)b * c.flag_stride, c.noise_trace ? c.noise_trace + first : nullptr, lds, row,
+                       row + a.ws.row, amax);
     if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
 }
 
@@ -886,6 +1019,71 @@ __global__ __launch_bounds__(ST_THREADS) void fsmn_stats_kernel(const int16_t *_
     }
 }
 
+// Means and energies of LONG windows: above ST_MAXGRAN granules vadx_fsmn_window_stats falls back to one workgroup per window twice
+// (window_mean_kernel: one wave; fsmn_energy_kernel: four waves, every sample 3.2 times), which leaves a single 10-minute window on one CU.
+// Here the grid is (window, block): a sum kernel adds each block's samples into the window's 64-bit integer sum (integer atomics: exact,
+// any order), then an energy kernel takes SL_FRAMES frames per workgroup.  The mean is window_mean_kernel's value bit for bit (exact sum,
+// one rounding); a sample's y is fsmn_energy_kernel's expression; y^2 is summed per 32-sample granule by 32 lanes and a frame is sixteen
+// granules, as in fsmn_stats_kernel.  Any alignment and any window_len >= 512: only granules inside a frame are formed.
+constexpr int SL_THREADS = 256, SL_SUM = 16384, SL_FRAMES = 48, SL_GRAN = 5 * (SL_FRAMES - 1) + 16;
+__global__ __launch_bounds__(SL_THREADS) void fsmn_long_sum_kernel(const int16_t *__restrict__ audio, long long row_stride, long long win_stride,
+                                                                   int windows_per_clip, int window_len, unsigned long long *__restrict__ sums) {
+    __shared__ long long wsum[SL_THREADS / 64];
+    const int widx = blockIdx.x, tid = threadIdx.x;
+    const int b = widx / windows_per_clip, w = widx - b * windows_per_clip;
+    const int16_t *win = audio + (long long)b * row_stride + (long long)w * win_stride;
+    const int n0 = blockIdx.y * SL_SUM, n1 = min(n0 + SL_SUM, window_len);
+    long long s = 0;                       // 9.6 M samples x 32 767 does not fit 32 bits
+    for (int n = n0 + tid; n < n1; n += SL_THREADS) s += win[n];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((tid & 63) == 0) wsum[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) {
+        long long tot = 0;
+#pragma unroll
+        for (int k = 0; k < SL_THREADS / 64; ++k) tot += wsum[k];
+        atomicAdd(sums + widx, (unsigned long long)tot);      // two's complement: the wrapped sum of the blocks is the window's signed sum
+    }
+}
+
+__global__ __launch_bounds__(SL_THREADS) void fsmn_long_energy_kernel(const int16_t *__restrict__ audio, long long row_stride, long long win_stride,
+                                                                      int windows_per_clip, int window_len, int T, float inv_ref,
+                                                                      const unsigned long long *__restrict__ sums, float *__restrict__ means,
+                                                                      float *__restrict__ db) {
+    __shared__ float gran[SL_GRAN];
+    const int widx = blockIdx.x, tid = threadIdx.x, l = tid & 31, hw = tid >> 5;
+    const int b = widx / windows_per_clip, w = widx - b * windows_per_clip;
+    const int16_t *win = audio + (long long)b * row_stride + (long long)w * win_stride;
+    const float mean = (float)((double)(long long)sums[widx] / (double)window_len);
+    if (blockIdx.y == 0 && tid == 0) means[widx] = mean;
+    const int nfr = (window_len - 512) / 160 + 1;
+    const int f0 = blockIdx.y * SL_FRAMES, f1 = min(f0 + SL_FRAMES, T) - 1;          // this block's frames, f0 <= f1 < T
+    const int ff0 = min(f0, nfr - 1), ff1 = min(f1, nfr - 1);                         // last value repeated up to T frames
+    const int g0 = 5 * ff0, ng = 5 * (ff1 - ff0) + 16;                                // granules g0 .. g0 + ng - 1, ng <= SL_GRAN
+    for (int gb = 0; gb < ng; gb += SL_THREADS / 32) {
+        const int g = min(gb + hw, ng - 1), n = 32 * (g0 + g) + l;                   // n <= 160 (nfr - 1) + 511 < window_len
+        const float xa = (float)win[n], xb = (float)win[n > 0 ? n - 1 : 0];
+        const float a = __fsub_rn(xa, mean);
+        float y = a;
+        if (n > 0) y = __fsub_rn(a, __fmul_rn(0.97f, __fsub_rn(xb, mean)));
+        y = __fmul_rn(y, inv_ref);
+        float acc = __fmul_rn(y, y);
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        if (l == 0 && gb + hw < ng) gran[g] = acc;
+    }
+    __syncthreads();
+    float *out = db + (size_t)widx * T;
+    for (int f = f0 + tid; f <= f1; f += SL_THREADS) {
+        const int ff = min(f, nfr - 1);
+        float e = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) e += gran[5 * (ff - ff0) + j];
+        out[f] = log10f(e + 0.00002f);
+    }
+}
+
 }  // namespace fsmn
 }  // namespace vadx
 
@@ -1108,6 +1306,106 @@ extern "C" int vadx_fsmn_clips_ragged(const vadx_fsmn_dims *dims, const float *p
     c.win_first = win_first; c.order = order;
     c.flags = flags; c.flag_stride = (long long)flag_stride; c.noise_trace = noise_trace;
     FSMN_LAUNCH(fsmn_clips_ragged_kernel, d.arith, batch, stream, d, packed, c);
+    return VADX_OK;
+}
+
+// ---- long windows (opt-in): every refusal names its argument and comes before any HIP call -----------------------------------------------
+#define FSMN_NONNULL(who, p) VADX_REQUIRE((p) != nullptr, who ": NULL " #p)
+
+extern "C" size_t vadx_fsmn_long_workspace_bytes(int rows, int frames) {
+    if (rows < 1 || frames < 1 || frames > MAX_T_LONG) return 0;
+    return (size_t)rows * 2 * long_row(frames) * sizeof(float);
+}
+
+extern "C" int vadx_fsmn_window_stats_long(const int16_t *audio, int64_t row_stride, int64_t win_stride, int batch, int windows_per_clip,
+                                           int window_len, int frames, float *means, float *db, void *workspace, void *stream) {
+    FSMN_NONNULL("vadx_fsmn_window_stats_long", audio); FSMN_NONNULL("vadx_fsmn_window_stats_long", means);
+    FSMN_NONNULL("vadx_fsmn_window_stats_long", db); FSMN_NONNULL("vadx_fsmn_window_stats_long", workspace);
+    VADX_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "vadx_fsmn_window_stats_long: workspace must be 8-byte aligned");
+    VADX_REQUIRE(batch > 0 && windows_per_clip > 0 && (long long)batch * windows_per_clip < (1ll << 31),
+                 "vadx_fsmn_window_stats_long: batch=%d windows_per_clip=%d must be positive", batch, windows_per_clip);
+    VADX_REQUIRE(window_len >= 512 && window_len <= (MAX_T_LONG - 1) * 160, "vadx_fsmn_window_stats_long: window_len=%d outside [512, %d]",
+                 window_len, (MAX_T_LONG - 1) * 160);
+    VADX_REQUIRE(frames >= 1 && frames <= MAX_T_LONG, "vadx_fsmn_window_stats_long: frames=%d outside [1, %d]", frames, MAX_T_LONG);
+    VADX_REQUIRE(row_stride >= 0 && win_stride >= 0 && (windows_per_clip - 1) * win_stride + window_len <= row_stride,
+                 "vadx_fsmn_window_stats_long: row_stride=%lld holds fewer than (windows_per_clip - 1) * win_stride + window_len = %lld samples",
+                 (long long)row_stride, (long long)((windows_per_clip - 1) * win_stride + window_len));
+    const float inv_ref = (float)(1.0 / (sqrt((double)window_len) * 2e-5));
+    const unsigned nwin = (unsigned)(batch * windows_per_clip);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned long long *sums = static_cast<unsigned long long *>(workspace);
+    VADX_HIP_TRY(hipMemsetAsync(sums, 0, (size_t)nwin * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(fsmn_long_sum_kernel, dim3(nwin, (unsigned)((window_len + SL_SUM - 1) / SL_SUM)), dim3(SL_THREADS), 0, st, audio,
+                       (long long)row_stride, (long long)win_stride, windows_per_clip, window_len, sums);
+    VADX_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(fsmn_long_energy_kernel, dim3(nwin, (unsigned)((frames + SL_FRAMES - 1) / SL_FRAMES)), dim3(SL_THREADS), 0, st, audio,
+                       (long long)row_stride, (long long)win_stride, windows_per_clip, window_len, frames, inv_ref, sums, means, db);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+extern "C" int vadx_fsmn_run_long(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db,
+                                  const float *const cache_in[4], float *const cache_out[4], const float *thr, const float *noise_db,
+                                  int batch, uint8_t *score, float *noisy_db, float *psil, void *workspace, void *stream) {
+    Dev d;
+    FSMN_NONNULL("vadx_fsmn_run_long", dims); FSMN_NONNULL("vadx_fsmn_run_long", packed); FSMN_NONNULL("vadx_fsmn_run_long", logmel);
+    FSMN_NONNULL("vadx_fsmn_run_long", db); FSMN_NONNULL("vadx_fsmn_run_long", cache_in); FSMN_NONNULL("vadx_fsmn_run_long", cache_out);
+    FSMN_NONNULL("vadx_fsmn_run_long", thr); FSMN_NONNULL("vadx_fsmn_run_long", noise_db); FSMN_NONNULL("vadx_fsmn_run_long", score);
+    FSMN_NONNULL("vadx_fsmn_run_long", noisy_db); FSMN_NONNULL("vadx_fsmn_run_long", workspace);
+    VADX_REQUIRE(dims->frames >= 1 && dims->frames <= MAX_T_LONG, "vadx_fsmn_run_long: frames=%d outside [1, %d] (window_len <= %d)", dims->frames,
+                 MAX_T_LONG, (MAX_T_LONG - 1) * 160);
+    VADX_REQUIRE(derive(dims, &d) == 0, "vadx_fsmn_run_long: unsupported dims");
+    VADX_REQUIRE(batch > 0, "vadx_fsmn_run_long: batch=%d must be positive", batch);
+    VADX_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "vadx_fsmn_run_long: workspace must be 4-byte aligned");
+    RunLongArgs a;
+    RunArgs &r = a.r;
+    r.logmel = logmel; r.db = db; r.thr = thr; r.noise_db = noise_db; r.score = score; r.noisy_db = noisy_db; r.psil = psil;
+    for (int l = 0; l < NLAYER; ++l) {
+        VADX_REQUIRE(cache_in[l] && cache_out[l], "vadx_fsmn_run_long: NULL cache_in / cache_out %d", l);
+        r.cin[l] = cache_in[l]; r.cout[l] = cache_out[l];
+    }
+    a.ws.base = static_cast<float *>(workspace); a.ws.row = long_row(d.T);
+    FSMN_LAUNCH(fsmn_run_long_kernel, d.arith, batch, stream, d, packed, a);
+    return VADX_OK;
+}
+
+extern "C" int vadx_fsmn_clips_long(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db, int batch,
+                                    int n_windows, int max_windows, const int32_t *win_first, const int32_t *order,
+                                    const vadx_fsmn_loop_params *lp, float *cache_ws, uint8_t *flags, int64_t flag_stride, float *noise_trace,
+                                    void *workspace, void *stream) {
+    Dev d;
+    FSMN_NONNULL("vadx_fsmn_clips_long", dims); FSMN_NONNULL("vadx_fsmn_clips_long", packed); FSMN_NONNULL("vadx_fsmn_clips_long", logmel);
+    FSMN_NONNULL("vadx_fsmn_clips_long", db); FSMN_NONNULL("vadx_fsmn_clips_long", lp); FSMN_NONNULL("vadx_fsmn_clips_long", cache_ws);
+    FSMN_NONNULL("vadx_fsmn_clips_long", flags); FSMN_NONNULL("vadx_fsmn_clips_long", workspace);
+    VADX_REQUIRE(dims->frames >= 1 && dims->frames <= MAX_T_LONG, "vadx_fsmn_clips_long: frames=%d outside [1, %d] (window_len <= %d)", dims->frames,
+                 MAX_T_LONG, (MAX_T_LONG - 1) * 160);
+    VADX_REQUIRE(derive(dims, &d) == 0, "vadx_fsmn_clips_long: unsupported dims");
+    VADX_REQUIRE(batch >= 1 && n_windows >= 1 && max_windows >= 1, "vadx_fsmn_clips_long: batch=%d n_windows=%d max_windows=%d must be positive",
+                 batch, n_windows, max_windows);
+    // the counts fit each other: a rectangular batch is batch * max_windows windows; a ragged one gives every clip 1 .. max_windows
+    VADX_REQUIRE(win_first ? n_windows >= batch && (long long)n_windows <= (long long)batch * max_windows
+                           : (long long)n_windows == (long long)batch * max_windows,
+                 "vadx_fsmn_clips_long: n_windows=%d does not fit batch=%d clips of %s max_windows=%d", n_windows, batch,
+                 win_first ? "1 .." : "exactly", max_windows);
+    // the windows of a grid must advance: (look_backward + 1) * 160 < window_len, as the stream path asks
+    VADX_REQUIRE(lp->look_backward >= 0 && lp->look_backward < d.T - 1, "vadx_fsmn_clips_long: look_backward=%d outside [0, frames - 1 = %d)",
+                 lp->look_backward, d.T - 1);
+    ClipLongArgs a;
+    RaggedArgs &c = a.r;
+    c.lp.lb = lp->look_backward > 0 ? lp->look_backward : 1;       // as loop_args: slide_range is taken before a zero look_backward becomes 1
+    c.lp.slide = d.T - lp->look_backward; c.lp.thr = lp->one_minus_speech_threshold; c.lp.noise0 = lp->noise_db_init;
+    c.lp.snr = lp->snr_threshold; c.lp.speaking = lp->speaking_score; c.lp.silence_score = lp->silence_score;
+    const long long need = (long long)max_windows * c.lp.slide + lp->look_backward;
+    VADX_REQUIRE(flag_stride >= need, "vadx_fsmn_clips_long: flag_stride=%lld holds fewer than max_windows * slide + look_backward = %lld flags",
+                 (long long)flag_stride, need);
+    VADX_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "vadx_fsmn_clips_long: workspace must be 4-byte aligned");
+    // every row starts as "no flag", as in vadx_fsmn_clips_ragged
+    VADX_HIP_TRY(hipMemsetAsync(flags, 255, (size_t)batch * (size_t)flag_stride, static_cast<hipStream_t>(stream)));
+    c.logmel = logmel; c.db = db; c.cache = cache_ws; c.batch = batch; c.n_windows = n_windows; c.max_windows = max_windows;
+    c.win_first = win_first; c.order = order;
+    c.flags = flags; c.flag_stride = (long long)flag_stride; c.noise_trace = noise_trace;
+    a.ws.base = static_cast<float *>(workspace); a.ws.row = long_row(d.T);
+    FSMN_LAUNCH(fsmn_clips_long_kernel, d.arith, batch, stream, d, packed, a);
     return VADX_OK;
 }
 

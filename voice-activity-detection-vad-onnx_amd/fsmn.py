@@ -24,6 +24,8 @@ SAMPLE_RATE = 16000
 OUTPUT_FRAME_LENGTH = 160
 PROJ, HIST = 128, 19
 MAX_FRAMES = 128             # frames per window the kernel's score scratch holds (vadx_fsmn_run); `flags`, ragged batches and streams take 112
+LOOP_MAX_FRAMES = 112
+LONG_MAX_LENGTH = 9_600_000  # long_windows=True: a 10-minute window, VADX_FSMN_LONG_MAX_FRAMES = 60 001 frames (include/vadx.h)
 # The stream record of S streams, mirroring the contract in include/vadx.h, as three sections in this order:
 CACHES, HEADER, CARRY = 0, 1, 2      # f32 [S][4][128][19] | u32 [S][8]: word H_PRIMED = has a carry, H_DONE and the next = windows done (u64) | int16 [S][(lb + 1) * 160]
 CACHE_BYTES, HDR_BYTES, H_PRIMED, H_DONE = 4 * PROJ * HIST * 4, 8 * 4, 2, 4
@@ -46,17 +48,27 @@ def _prep(normalize):
 
 
 class FsmnEngine:
-    def __init__(self, weights=None, input_audio_length=16000, device="cuda:0", speech_2_noise_ratio=1.0):
+    def __init__(self, weights=None, input_audio_length=16000, device="cuda:0", speech_2_noise_ratio=1.0, long_windows=False):
+        """long_windows=True: the model of an export with a long INPUT_AUDIO_LENGTH (FSMN/Export_FSMN_VAD.py; the driver reads it back from
+        the session, FSMN/Inference_FSMN_VAD_ONNX.py:73-80): any 512 <= input_audio_length <= 9 600 000.  Such an engine runs the long
+        entry points (vadx_fsmn_window_stats_long, vadx_fsmn_run_long, vadx_fsmn_clips_long: a window's scores in a global workspace instead
+        of LDS) at EVERY length; up to 112 frames its results are bit for bit the default engine's."""
         torch = _lib.require_gpu()
         self.torch = torch
         self.device = torch.device(device)
         w = _checkpoints.resolve("fsmn", weights)
         w = {k: np.ascontiguousarray(np.asarray(v), dtype=np.float32) for k, v in w.items()}
         self.L = int(input_audio_length)
-        if self.L // OUTPUT_FRAME_LENGTH + 1 > MAX_FRAMES:
+        self.long_windows = bool(long_windows)
+        if self.long_windows:
+            if not 512 <= self.L <= LONG_MAX_LENGTH:
+                raise ValueError(f"input_audio_length={self.L} is outside [512, {LONG_MAX_LENGTH}]: a long window holds at most "
+                                 f"{LONG_MAX_LENGTH // OUTPUT_FRAME_LENGTH + 1} frames (10 minutes); longer audio goes on the window grid")
+        elif self.L // OUTPUT_FRAME_LENGTH + 1 > MAX_FRAMES:
             raise ValueError(f"input_audio_length={self.L} gives {self.L // OUTPUT_FRAME_LENGTH + 1} frames per window: the FSMN kernel takes at most "
                              f"{MAX_FRAMES} (input_audio_length <= {MAX_FRAMES * OUTPUT_FRAME_LENGTH - 1}); `flags`, ragged batches and streams "
-                             f"need at most 112 (input_audio_length <= {112 * OUTPUT_FRAME_LENGTH - 1})")
+                             f"need at most 112 (input_audio_length <= {112 * OUTPUT_FRAME_LENGTH - 1}).  long_windows=True takes windows of any "
+                             f"length up to {LONG_MAX_LENGTH} samples")
         self.fe = _frontend.Frontend("fsmn", self.L, device=device)
         self.T = self.fe.frames
         dims = _lib.FsmnDims()
@@ -105,6 +117,18 @@ class FsmnEngine:
     def packed(self):
         return self.blobs.get()[1]
 
+    def _workspace(self, rows):
+        """The long entry points' scratch for `rows` windows walked at a time (vadx_fsmn_long_workspace_bytes): a window's P(silence) and gate bits."""
+        t = self.torch
+        return t.empty(_lib.lib().vadx_fsmn_long_workspace_bytes(int(rows), self.T), dtype=t.uint8, device=self.device)
+
+    def _long_grid(self, look_backward_s):
+        """`grid` for the long clip loop, whose windows must advance: refused here by name, before anything is padded or launched."""
+        lb, stride = self.grid(look_backward_s)
+        if lb < 0 or lb >= self.T - 1 or stride <= 0:
+            raise ValueError(f"look_backward_s={look_backward_s}: {lb} frames leave no window stride at input_audio_length={self.L}")
+        return lb, stride
+
     # ---- front-end + energy for a [B, N] int16 batch cut into W windows at `stride`
     def features(self, audio_i16, windows_per_clip, stride):
         t = self.torch
@@ -118,8 +142,13 @@ class FsmnEngine:
         L = _lib.lib()
         with t.cuda.device(self.device):
             # window means + frame energies in one pass over the PCM, then the log-mel front-end with those means
-            _lib.check(L.vadx_fsmn_window_stats(a.data_ptr(), _lib.row_stride(a), int(stride), B, W, self.L, self.T, means.data_ptr(),
-                                                db.data_ptr(), _lib.stream_ptr()))
+            if self.long_windows:             # a grid of (window, block of frames); the windows' 64-bit sums are its workspace
+                sums = t.empty((B * W,), dtype=t.int64, device=self.device)
+                _lib.check(L.vadx_fsmn_window_stats_long(a.data_ptr(), _lib.row_stride(a), int(stride), B, W, self.L, self.T, means.data_ptr(),
+                                                         db.data_ptr(), sums.data_ptr(), _lib.stream_ptr()))
+            else:
+                _lib.check(L.vadx_fsmn_window_stats(a.data_ptr(), _lib.row_stride(a), int(stride), B, W, self.L, self.T, means.data_ptr(),
+                                                    db.data_ptr(), _lib.stream_ptr()))
             _lib.check(L.vadx_frontend_logmel_means(C.byref(fe.cfg), fe.packed.data_ptr(), fe.mel_kb.ctypes.data, a.data_ptr(),
                                                     _lib.row_stride(a), int(stride), B, W, means.data_ptr(), logmel.data_ptr(),
                                                     _lib.stream_ptr()))
@@ -145,13 +174,16 @@ class FsmnEngine:
         psil = t.empty((B, self.T), dtype=t.float32, device=self.device) if return_psil else None
         pin = (C.c_void_p * 4)(*[c.data_ptr() for c in cin])
         pout = (C.c_void_p * 4)(*[c.data_ptr() for c in cout])
+        ws = self._workspace(B) if self.long_windows else None
 
         def launch(mode, dims, packed):
             with t.cuda.device(self.device):
-                _lib.check(_lib.lib().vadx_fsmn_run(C.byref(dims), packed.data_ptr(), logmel.data_ptr(), db.data_ptr(),
-                                                    C.byref(pin), C.byref(pout), thr.data_ptr(), nz.data_ptr(), B,
-                                                    score.data_ptr(), noisy.data_ptr(),
-                                                    None if psil is None else psil.data_ptr(), _lib.stream_ptr()))
+                args = (C.byref(dims), packed.data_ptr(), logmel.data_ptr(), db.data_ptr(), C.byref(pin), C.byref(pout), thr.data_ptr(),
+                        nz.data_ptr(), B, score.data_ptr(), noisy.data_ptr(), None if psil is None else psil.data_ptr())
+                if ws is None:
+                    _lib.check(_lib.lib().vadx_fsmn_run(*args, _lib.stream_ptr()))
+                else:
+                    _lib.check(_lib.lib().vadx_fsmn_run_long(*args, ws.data_ptr(), _lib.stream_ptr()))
             return (score, cout, noisy, psil) if return_psil else (score, cout, noisy)
         return self.blobs.guarded(launch)
 
@@ -165,7 +197,8 @@ class FsmnEngine:
               snr_threshold=10.0, noise_init_dB=30.0, one_minus_speech_threshold=1.0, return_noise=False):
         """padded_i16 [B, (W-1)*stride + L] int16 on the window grid -> silence flags u8 [B, W*(T-lb)+lb]."""
         t = self.torch
-        lb, stride = self.grid(look_backward_s)        # lb may be 0: W*T flags, no tail (Inference_FSMN_VAD_ONNX.py:79-86)
+        # lb may be 0: W*T flags, no tail (Inference_FSMN_VAD_ONNX.py:79-86)
+        lb, stride = self._long_grid(look_backward_s) if self.long_windows else self.grid(look_backward_s)
         a = padded_i16.to(self.device).contiguous()
         B, W = a.shape[0], int(windows_per_clip)
         logmel, db = self.features(a, W, stride)
@@ -174,12 +207,18 @@ class FsmnEngine:
         flags = t.empty((B, nflags), dtype=t.uint8, device=self.device)
         cache = t.empty((B, 4, PROJ, HIST), dtype=t.float32, device=self.device)
         trace = t.empty((B, W), dtype=t.float32, device=self.device) if return_noise else None
+        ws = self._workspace(B) if self.long_windows else None
 
         def launch(mode, dims, packed):
             with t.cuda.device(self.device):
-                _lib.check(_lib.lib().vadx_fsmn_clips(C.byref(dims), packed.data_ptr(), logmel.data_ptr(),
-                                                      db.data_ptr(), B, W, C.byref(lp), cache.data_ptr(), flags.data_ptr(),
-                                                      None if trace is None else trace.data_ptr(), _lib.stream_ptr()))
+                if ws is None:
+                    _lib.check(_lib.lib().vadx_fsmn_clips(C.byref(dims), packed.data_ptr(), logmel.data_ptr(),
+                                                          db.data_ptr(), B, W, C.byref(lp), cache.data_ptr(), flags.data_ptr(),
+                                                          None if trace is None else trace.data_ptr(), _lib.stream_ptr()))
+                else:                         # the rectangular batch of the long loop: no window table, W windows for every clip
+                    _lib.check(_lib.lib().vadx_fsmn_clips_long(C.byref(dims), packed.data_ptr(), logmel.data_ptr(), db.data_ptr(), B, B * W, W,
+                                                               None, None, C.byref(lp), cache.data_ptr(), flags.data_ptr(), nflags,
+                                                               None if trace is None else trace.data_ptr(), ws.data_ptr(), _lib.stream_ptr()))
             return (flags, trace) if return_noise else flags
         return self.blobs.guarded(launch)
 
@@ -193,7 +232,10 @@ class FsmnEngine:
     def ragged(self, clips, pad_noise=None, normalize=True, look_backward_s=0.3, device=True):
         """The packed batch of `clips` (list of 1-D arrays of any lengths) on this engine's window grid (vadx.ragged.RaggedBatch):
         peak-normalised like the reference (normalize) and padded per clip with pad_noise row b.  device=None keeps it on the host."""
-        return _ragged.RaggedBatch.from_clips(clips, self.L, self.grid(look_backward_s)[1], pad_noise, _prep(normalize),
+        if self.long_windows and self.L % 8:
+            raise ValueError(f"input_audio_length={self.L} must be a multiple of 8 for a ragged batch: the window gather moves 16-byte runs")
+        stride = (self._long_grid(look_backward_s) if self.long_windows else self.grid(look_backward_s))[1]
+        return _ragged.RaggedBatch.from_clips(clips, self.L, stride, pad_noise, _prep(normalize),
                                               self.device if device is True else device)
 
     def flags_ragged(self, rb, *, order=None, return_noise=False, look_backward_s=0.3, speaking_score=0.5, silence_score=0.5,
@@ -204,7 +246,7 @@ class FsmnEngine:
         order: None = rb.order (longest clip first), "identity" = clip b on workgroup b, or an int32 permutation of the clips.
         A host-only batch (device=None) is uploaded first, in place: `rb.to(self.device)` turns its pcm and tables into device tensors."""
         t = self.torch
-        lb, stride = self.grid(look_backward_s)
+        lb, stride = self._long_grid(look_backward_s) if self.long_windows else self.grid(look_backward_s)
         if rb.window != self.L or rb.stride != stride:
             raise ValueError(f"the batch was packed for windows of {rb.window} every {rb.stride} samples, this call needs {self.L} every {stride}")
         if rb.device is None:
@@ -229,13 +271,17 @@ class FsmnEngine:
         flags = t.empty((B, stride_f), dtype=t.uint8, device=self.device)
         cache = t.empty((B, 4, PROJ, HIST), dtype=t.float32, device=self.device)
         trace = t.empty((nwin,), dtype=t.float32, device=self.device) if return_noise else None
+        ws = self._workspace(B) if self.long_windows else None
 
         def launch(mode, dims, packed):
             with t.cuda.device(self.device):
-                _lib.check(_lib.lib().vadx_fsmn_clips_ragged(C.byref(dims), packed.data_ptr(), logmel.data_ptr(), db.data_ptr(), B, nwin,
-                                                             maxw, rb.win_first.data_ptr(), None if order_d is None else order_d.data_ptr(),
-                                                             C.byref(lp), cache.data_ptr(), flags.data_ptr(), stride_f,
-                                                             None if trace is None else trace.data_ptr(), _lib.stream_ptr()))
+                args = (C.byref(dims), packed.data_ptr(), logmel.data_ptr(), db.data_ptr(), B, nwin, maxw, rb.win_first.data_ptr(),
+                        None if order_d is None else order_d.data_ptr(), C.byref(lp), cache.data_ptr(), flags.data_ptr(), stride_f,
+                        None if trace is None else trace.data_ptr())
+                if ws is None:
+                    _lib.check(_lib.lib().vadx_fsmn_clips_ragged(*args, _lib.stream_ptr()))
+                else:
+                    _lib.check(_lib.lib().vadx_fsmn_clips_long(*args, ws.data_ptr(), _lib.stream_ptr()))
             return (flags, nflags, trace) if return_noise else (flags, nflags)
         return self.blobs.guarded(launch)
 
@@ -249,7 +295,8 @@ class FsmnEngine:
         if isinstance(clips_i16, (list, tuple)):
             flags, nflags = self.flags_ragged(self.ragged(clips_i16, pad_noise, normalize, look_backward_s), **loop_kw)
         else:
-            padded, W = pad_batch(clips_i16, self.L, self.grid(look_backward_s)[1], pad_noise, _prep(normalize))
+            stride = (self._long_grid(look_backward_s) if self.long_windows else self.grid(look_backward_s))[1]
+            padded, W = pad_batch(clips_i16, self.L, stride, pad_noise, _prep(normalize))
             flags = self.flags(self.torch.from_numpy(padded), W, **loop_kw)
             nflags = [flags.shape[1]] * flags.shape[0]
         flags = flags.cpu().numpy()
@@ -268,9 +315,10 @@ class FsmnSession(Session):
     rounded to float16 once.  Against the float32 session fed the same (float16-representable) values the uint8 score
     is identical and caches / noisy_dB differ by that single rounding (<= 2^-11 relative)."""
 
-    def __init__(self, weights=None, input_audio_length=16000, device="cuda:0", io_dtype="float32", speech_2_noise_ratio=1.0):
+    def __init__(self, weights=None, input_audio_length=16000, device="cuda:0", io_dtype="float32", speech_2_noise_ratio=1.0, long_windows=False):
+        """long_windows=True: any 512 <= input_audio_length <= 9 600 000 (FsmnEngine), reported as `[1,1,L]` and `[T]` like any other."""
         self.io_dtype, ftype = io_types(io_dtype)
-        self.engine = FsmnEngine(weights, input_audio_length, device, speech_2_noise_ratio)
+        self.engine = FsmnEngine(weights, input_audio_length, device, speech_2_noise_ratio, long_windows=long_windows)
         L, T = self.engine.L, self.engine.T
         cache = [1, PROJ, HIST, 1]
         self._inputs_meta = [_Meta("audio", [1, 1, L], "tensor(int16)")] + \
@@ -322,6 +370,10 @@ class FsmnStreamBatch:
         if not isinstance(engine, FsmnEngine):
             raise TypeError("FsmnStreamBatch needs a vadx.fsmn.FsmnEngine")
         self.engine, self.streams = engine, int(streams)
+        if engine.long_windows and engine.T > LOOP_MAX_FRAMES:        # live streams want short windows
+            raise ValueError(f"FsmnStreamBatch: the engine's input_audio_length={engine.L} gives {engine.T} frames per window; the stream "
+                             f"kernel takes at most {LOOP_MAX_FRAMES} (input_audio_length <= {LOOP_MAX_FRAMES * OUTPUT_FRAME_LENGTH - 1}): "
+                             f"long windows are not served as live streams")
         if self.streams <= 0:
             raise ValueError(f"streams={streams} must be positive")
         self.lb, self.stride = engine.grid(look_backward_s)
