@@ -54,7 +54,8 @@ extern "C" {
  *     vadx_tracks_gather; then MarbleNet over ragged batches: vadx_marblenet_ragged, vadx_frontend_logmel_ragged, vadx_sepconv_block_ragged,
  *     vadx_marblenet_block2_ragged, vadx_marblenet_tail_ragged; then FireRed Stream-VAD over live streams: vadx_firered_stream_state_bytes,
  *     vadx_firered_stream_group_max, vadx_firered_stream_tick; then FSMN windows of any length: vadx_fsmn_long_workspace_bytes,
- *     vadx_fsmn_window_stats_long, vadx_fsmn_run_long, vadx_fsmn_clips_long.  A caller that needs them checks for the symbols (dlsym), not
+ *     vadx_fsmn_window_stats_long, vadx_fsmn_run_long, vadx_fsmn_clips_long; then DFSMN over ragged batches and live streams:
+ *     vadx_windows_gather_any, vadx_dfsmn_vote_ragged, vadx_dfsmn_stream_state_bytes, vadx_dfsmn_stream_windows, vadx_dfsmn_stream_vote.  A caller that needs them checks for the symbols (dlsym), not
  *     for a number. */
 #define VADX_ABI_VERSION 10
 
@@ -911,6 +912,87 @@ int vadx_dfsmn_mask_net(const vadx_dfsmn_mask_weights *w, const float *feat, int
  * -> flags u8 [B][W*(frames-lb) + lb] (1 = silence). */
 int vadx_dfsmn_vote(const float *vad, int batch, int windows, int frames, int look_backward, double speaking_score,
                     double silence_score, uint8_t *flags, void *stream);
+
+/* DFSMN over a RAGGED batch (ABI 10): B clip pairs of ANY lengths, work proportional to the sum of their windows.  The caller cuts each
+ * pair to its shorter side, pads each side to the window grid on the host (Inference_DFSMN_VAD_ONNX.py:124-163) and lays the padded clips
+ * end to end, with no filler, in two int16 vectors that share the tables win_first int32 [B+1] and win_src int64 [n_windows] of "Ragged
+ * batches" above (vadx.ragged.RaggedPairs builds all of this).  DFSMN's grid -- 16 001 samples every 10 881 -- is not made of 16-byte
+ * runs, so the sequence on one HIP stream is
+ *   vadx_windows_gather_any    once per channel: pcm, win_src -> int16 [n_windows][window_len]
+ *   the network                unchanged (windows are stateless): vadx_frontend_stft_ft .. vadx_dfsmn_mask_net with batch = n_windows,
+ *                              windows_per_clip = 1, row_stride = win_stride = window_len -> vad f32 [n_windows][frames]
+ *   vadx_dfsmn_vote_ragged     -> flags u8 [B][flag_stride] */
+
+/* vadx_windows_gather for any grid: row w of window_buf int16 [n_windows][window_len] = pcm[win_src[w], win_src[w] + window_len), for any
+ * window_len >= 1 and any offset >= 0; pcm and window_buf 2-byte aligned.  A window whose source range leaves [0, pcm_len) is written as
+ * ZEROS; nothing outside pcm is ever read.  A pure copy, one int16 per access (64 KB per window pair ahead of a network pass that moves
+ * orders of magnitude more).  Returns VADX_EINVAL, before any HIP call, for a NULL pointer, n_windows < 1, pcm_len < 1 or window_len < 1.
+ * Replaces the slicing `near_end_audio[:, :, slice_start:slice_end]` of DFSMN/near_and_far_end_audio/Inference_DFSMN_VAD_ONNX.py:221-229,
+ * 259-260 for every window of every clip at once. */
+int vadx_windows_gather_any(const int16_t *pcm, int64_t pcm_len, const int64_t *win_src, int n_windows, int window_len,
+                            int16_t *window_buf, void *stream);
+
+/* vadx_dfsmn_vote over a ragged batch (one device function votes a window in both): vad f32 [n_windows][frames], clip b owns the rows
+ * win_first[b] .. win_first[b+1]-1.  Row b of flags u8 [batch][flag_stride]: its first W_b * (frames - look_backward) + look_backward
+ * entries are the reference's `saved` list of clip b (1 = silence), bit for bit what vadx_dfsmn_vote gives for that clip's rows alone
+ * (the same float32 threshold comparison); every other entry is 255 (the call fills flags with 255 first, on `stream`).  max_windows: the
+ * largest W_b the caller sized flag_stride for.  A table entry that does not describe rows inside vad -- W_b <= 0, W_b > max_windows,
+ * win_first[b] < 0, win_first[b+1] > n_windows -- leaves that row all 255 and indexes nothing out of bounds.  Returns VADX_EINVAL, before
+ * any HIP call, for a NULL pointer, batch / n_windows / max_windows / frames < 1, flag_stride < max_windows * (frames - look_backward) +
+ * look_backward, or a look_backward outside [1, frames).
+ * Replaces the while-loop + tail, Inference_DFSMN_VAD_ONNX.py:231-273, for B file pairs of different lengths. */
+int vadx_dfsmn_vote_ragged(const float *vad, int batch, int n_windows, int max_windows, const int32_t *win_first, int frames,
+                           int look_backward, double speaking_score, double silence_score, uint8_t *flags, int64_t flag_stride,
+                           void *stream);
+
+/* Live DFSMN streams (ABI 10): S calls (microphone + loudspeaker reference, or the microphone alone) advance by `windows` analysis windows
+ * per tick.  What the reference loop carries from window to window -- the vote's `silence` and the (look_backward + 1) * 320 samples two
+ * consecutive windows share, per channel -- lives, with a "has a carry" word and a 64-bit count of the windows done since the reset, in a
+ * device RECORD of vadx_dfsmn_stream_state_bytes bytes.  The record is opaque except that a record of all zero bytes is S streams in
+ * their reset state (no init call) and that its size is a multiple of 16 bytes; records are 16-byte aligned.
+ * One tick on one HIP stream:
+ *   vadx_dfsmn_stream_windows  new samples + carry -> near_buf / far_buf int16 [n_slots*windows][window_len], the new carry
+ *   the network                unchanged, with batch = n_slots * windows, windows_per_clip = 1 -> vad f32 [n_slots*windows][frames]
+ *   vadx_dfsmn_stream_vote     -> flags, tail, the rest of the record
+ * Both stream calls of a tick take the SAME state_in, state_out, slot and reset.  state_in is never written (a tick can be repeated from
+ * it); state_in and state_out must not overlap.  vadx_dfsmn_stream_windows writes only the carry and the "has a carry" word of state_out,
+ * vadx_dfsmn_stream_vote everything else.
+ * slot (NULL or int32 [S]) is the active mask AND the row map, because a stream without audio must cost no network time: slot[s] = -1 =
+ * no audio for stream s this tick; slot[s] = a in [0, n_slots) = stream s owns the rows a*windows .. a*windows + windows - 1 of near_buf /
+ * far_buf / vad.  NULL = the identity (a stream s >= n_slots is then inactive); a value outside [-1, n_slots) is treated as -1.  Two
+ * streams naming one slot is the caller's error -- documented, not checked, like `order` of vadx_fsmn_clips_ragged: their window rows
+ * race.  Rows of a slot no stream names are not written.  An inactive stream's record in state_out is a bitwise copy of state_in's (a
+ * reset request on it is ignored), its flags and tail are 255.
+ * reset (NULL or uint8 [S]): != 0 = back to the reset state before this tick.
+ * The fp16 x 2 range protocol needs nothing here: it concerns the network calls, which read only the window buffers.
+ * The flags of successive ticks followed by the last tick's tail are bit for bit vadx_dfsmn_vote over the concatenated windows. */
+
+/* Bytes of the record of `streams` streams of `channels` channels (1 = near-end only, 2 = near + far): a multiple of 16, linear in
+ * streams.  0 for streams < 1, channels outside {1, 2}, look_backward < 1 or (look_backward + 1) * 320 >= window_len (no stride left). */
+size_t vadx_dfsmn_stream_state_bytes(int streams, int window_len, int look_backward, int channels);
+
+/* Window assembly, per channel (far and far_buf both NULL = one channel).  stride = window_len - (look_backward + 1) * 320.  near / far
+ * int16 [S][row_stride] hold each stream's NEW samples from column 0: windows * stride of them for a stream that has a carry, window_len +
+ * (windows - 1) * stride for one that has none (zero record, or reset this tick); row_stride >= windows * stride is all this call can
+ * check, and a sample past row_stride reads as zero.  Window j of a stream is [j * stride, j * stride + window_len) of (carry ++ new
+ * samples); the last (look_backward + 1) * 320 samples become the carry in state_out.  Any window_len: buffers 2-byte aligned, records
+ * 16-byte.  Returns VADX_EINVAL, before any HIP call, for a NULL pointer (near, state_in, state_out, near_buf; far without far_buf or the
+ * reverse), streams / n_slots / windows < 1, look_backward < 1 or leaving no stride, a row_stride below windows * stride, or overlapping
+ * records.
+ * Replaces the slicing and `slice_start += stride_step` of Inference_DFSMN_VAD_ONNX.py:221-229, 259-260 for audio that arrives in pieces. */
+int vadx_dfsmn_stream_windows(const int16_t *near, const int16_t *far, int64_t row_stride, int streams, int n_slots, int windows,
+                              int window_len, int look_backward, const int32_t *slot, const uint8_t *reset, const void *state_in,
+                              void *state_out, int16_t *near_buf, int16_t *far_buf, void *stream);
+
+/* The vote of one tick, with the carried `silence`: flags u8 [S][windows * (frames - look_backward)] are the next entries of the
+ * reference's `saved` list (1 = silence); tail u8 [S][look_backward] is what the plain rule appends if the stream ENDS with this tick -- it
+ * does not touch the carried state, so the stream can go on.  channels: that of the record (it sizes the overlap check).  Returns
+ * VADX_EINVAL, before any HIP call, for a NULL pointer, streams / n_slots / windows / frames < 1, look_backward outside [1, frames),
+ * channels outside {1, 2}, or overlapping records.
+ * Replaces the while-loop body + tail, Inference_DFSMN_VAD_ONNX.py:231-273, for S calls that arrive in pieces. */
+int vadx_dfsmn_stream_vote(const float *vad, int streams, int n_slots, int windows, int frames, int look_backward, int channels,
+                           double speaking_score, double silence_score, const int32_t *slot, const uint8_t *reset,
+                           const void *state_in, void *state_out, uint8_t *flags, uint8_t *tail, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Test hooks (used by tests/ only)

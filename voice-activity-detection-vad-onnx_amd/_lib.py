@@ -244,6 +244,11 @@ SIGNATURES = {
     "vadx_dfsmn_ft_repack": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "vadx_dfsmn_istft": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
     "vadx_dfsmn_vote": (_I, [_P, _I, _I, _I, _I, C.c_double, C.c_double, _P, _P]),
+    "vadx_windows_gather_any": (_I, [_P, _L, _P, _I, _I, _P, _P]),
+    "vadx_dfsmn_vote_ragged": (_I, [_P, _I, _I, _I, _P, _I, _I, C.c_double, C.c_double, _P, _L, _P]),
+    "vadx_dfsmn_stream_state_bytes": (_Z, [_I, _I, _I, _I]),
+    "vadx_dfsmn_stream_windows": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "vadx_dfsmn_stream_vote": (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
     "vadx_frontend_logmel_ex": (_I, [C.POINTER(FrontendCfg), _P, _P, _P, _L, _L, _I, _I, _P, _P, _I, _I, _P, _P]),
     "vadx_frontend_stft_ft": (_I, [C.POINTER(FrontendCfg), _P, _P, _L, _L, _I, _I, _P, _P, _I, _I, _P]),
     "vadx_dfsmn_mask_net": (_I, [C.POINTER(DfsmnMaskWeights), _P, _I, _I, _P, _P]),

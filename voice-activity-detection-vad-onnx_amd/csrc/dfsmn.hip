@@ -1699,21 +1699,19 @@ __global__ void istft_ola_kernel(const float *__restrict__ Z, const float *__res
 // ---------------------------------------------------------------------------------------------
 // look-ahead vote of the DFSMN driver on float scores (Inference_DFSMN_VAD_ONNX.py:231-273), one clip/thread
 // ---------------------------------------------------------------------------------------------
-__global__ void dfsmn_vote_kernel(const float *__restrict__ vad, int B, int W, int Tn, int lb, double speaking,
-                                  double silence_score, unsigned char *__restrict__ flags) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const int slide = Tn - lb, nflags = W * slide + lb;
-    const double inv_lb = 1.0 / (double)lb;
+struct Vote {
+    int Tn, lb, slide;
+    double speaking, silence_score, inv_lb;
     // A float32 score against the Python-float constant: NumPy 2 (NEP 50) compares in float32, i.e. against the constant rounded to
     // float32 -- a score of exactly float32(0.7) IS >= 0.7 there (tests/golden/hostloop_thresholds.npz, produced by the
     // reference loop under NumPy 2.2).  The vote ratio (int * float) against the constant stays a float64 comparison.
-    const float hi = (float)speaking, lo = (float)silence_score;
-    int silence = 1;
-    unsigned char *fl = flags + (size_t)b * nflags;
-    const float *sc = nullptr;
-    for (int k = 0; k < W; ++k) {
-        sc = vad + ((size_t)b * W + k) * Tn;
+    float hi, lo;
+    __device__ Vote(int Tn_, int lb_, double speaking_, double silence_score_)
+        : Tn(Tn_), lb(lb_), slide(Tn_ - lb_), speaking(speaking_), silence_score(silence_score_), inv_lb(1.0 / (double)lb_),
+          hi((float)speaking_), lo((float)silence_score_) {}
+
+    // one window (:231-258): `slide` voted flags from its scores sc[0, Tn); returns the vote's `silence` after it
+    __device__ int window(const float *__restrict__ sc, int silence, unsigned char *__restrict__ fl) const {
         for (int i2 = 0; i2 < slide; ++i2) {
             if (silence) {
                 if (sc[i2] >= hi) {
@@ -1728,14 +1726,155 @@ __global__ void dfsmn_vote_kernel(const float *__restrict__ vad, int B, int W, i
                     silence = !((double)act * inv_lb <= silence_score);
                 } else silence = 0;
             }
-            fl[k * slide + i2] = (unsigned char)silence;
+            fl[i2] = (unsigned char)silence;
+        }
+        return silence;
+    }
+
+    // the plain rule over the last window's last lb scores (:262-273): lb flags
+    __device__ void tail(const float *__restrict__ sc, int silence, unsigned char *__restrict__ fl) const {
+        for (int i2 = slide; i2 < Tn; ++i2) {
+            if (silence) silence = !(sc[i2] >= hi);
+            else silence = (sc[i2] <= lo) ? 1 : 0;
+            fl[i2 - slide] = (unsigned char)silence;
         }
     }
-    for (int i2 = slide; i2 < Tn; ++i2) {
-        if (silence) silence = !(sc[i2] >= hi);
-        else silence = (sc[i2] <= lo) ? 1 : 0;
-        fl[W * slide + (i2 - slide)] = (unsigned char)silence;
+};
+
+__global__ void dfsmn_vote_kernel(const float *__restrict__ vad, int B, int W, int Tn, int lb, double speaking,
+                                  double silence_score, unsigned char *__restrict__ flags) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const Vote v(Tn, lb, speaking, silence_score);
+    int silence = 1;
+    unsigned char *fl = flags + (size_t)b * (W * v.slide + lb);
+    const float *sc = nullptr;
+    for (int k = 0; k < W; ++k) {
+        sc = vad + ((size_t)b * W + k) * Tn;
+        silence = v.window(sc, silence, fl + k * v.slide);
     }
+    v.tail(sc, silence, fl + W * v.slide);
+}
+
+// The same vote over a RAGGED batch: clip b owns the score rows win_first[b] .. win_first[b+1]-1 and row b of flags (filled with 255 by the
+// caller of the kernel).  A table entry that does not describe rows inside `vad` leaves the thread without a store.
+__global__ void dfsmn_vote_ragged_kernel(const float *__restrict__ vad, int B, int n_windows, int max_windows, const int *__restrict__ win_first,
+                                         int Tn, int lb, double speaking, double silence_score, unsigned char *__restrict__ flags,
+                                         long long flag_stride) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int first = win_first[b], last = win_first[b + 1];
+    if (first < 0 || last > n_windows || last <= first || last - first > max_windows) return;
+    const int W = last - first;
+    const Vote v(Tn, lb, speaking, silence_score);
+    int silence = 1;
+    unsigned char *fl = flags + (size_t)b * flag_stride;
+    const float *sc = nullptr;
+    for (int k = 0; k < W; ++k) {
+        sc = vad + ((size_t)first + k) * Tn;
+        silence = v.window(sc, silence, fl + (size_t)k * v.slide);
+    }
+    v.tail(sc, silence, fl + (size_t)W * v.slide);
+}
+
+// ---- live near + far streams ------------------------------------------------------------------------------------------------------------
+// The record of S streams with `ch` channels (include/vadx.h states the contract): header u32 [S][4] | carry int16 [ch][S][C],
+// C = (look_backward + 1) * 320 = the samples two consecutive windows share.  Header words: 0 silence (the vote's), 1 primed (the stream
+// has a carry), 2-3 windows done (u64).  The window kernel owns word 1 and the carry, the vote kernel the other words; zero bytes =
+// un-primed = the reset state (silence takes its initial value, true, when an un-primed stream starts).
+constexpr int SHDR_WORDS = 4, SH_SIL = 0, SH_PRIMED = 1, SH_DONE = 2, SFRAME = 320;
+__host__ __device__ static size_t srec_carry(int S) { return (size_t)S * SHDR_WORDS * 4; }
+static size_t srec_bytes(int S, int C, int ch) { return srec_carry(S) + (size_t)ch * S * C * sizeof(int16_t); }
+
+// slot of stream s this tick: -1 = no audio (also for an entry outside [-1, n_slots))
+__device__ __forceinline__ int stream_slot(const int *__restrict__ slot, int s, int n_slots) {
+    const int a = slot ? slot[s] : s;
+    return a >= 0 && a < n_slots ? a : -1;
+}
+
+struct StreamWinArgs {
+    const int16_t *samples[2]; long long row_stride;   // per channel [S][row_stride]: each stream's new samples from column 0
+    int S, n_slots, k, L, C, ch;                       // streams, slots, windows per tick, window length, carry length, channels
+    const int *slot; const unsigned char *reset;       // optional [S]
+    const unsigned char *sin; unsigned char *sout;     // records
+    int16_t *wbuf[2];                                  // per channel [n_slots * k][L]
+};
+
+// Window assembly (the slicing of Inference_DFSMN_VAD_ONNX.py:221-229, 259-260 for a stream that arrives in pieces): a stream's timeline of
+// this tick is its carry followed by its new samples (no carry before the first tick); window j = timeline[j * stride, j * stride + L), the
+// new carry = the timeline's last C samples.  One workgroup per (channel, stream, window) plus one per (channel, stream) for the carry; one
+// int16 per access (L and the stride are odd).  A sample past row_stride reads as zero.  An inactive stream keeps its carry and owns no row.
+__global__ __launch_bounds__(256) void dfsmn_stream_windows_kernel(StreamWinArgs a) {
+    const int per = a.k + 1, c = blockIdx.x / (a.S * per), r = blockIdx.x - c * (a.S * per), s = r / per, j = r - s * per, tid = threadIdx.x;
+    const unsigned *hin = reinterpret_cast<const unsigned *>(a.sin) + (size_t)s * SHDR_WORDS;
+    unsigned *hout = reinterpret_cast<unsigned *>(a.sout) + (size_t)s * SHDR_WORDS;
+    const size_t coff = srec_carry(a.S) + ((size_t)c * a.S + s) * a.C * sizeof(int16_t);
+    const int16_t *cin = reinterpret_cast<const int16_t *>(a.sin + coff);
+    int16_t *cout = reinterpret_cast<int16_t *>(a.sout + coff);
+    const int slot = stream_slot(a.slot, s, a.n_slots);
+    if (slot < 0) {
+        if (j == a.k) {
+            for (int i = tid; i < a.C; i += 256) cout[i] = cin[i];
+            if (c == 0 && tid == 0) hout[SH_PRIMED] = hin[SH_PRIMED];
+        }
+        return;
+    }
+    const bool primed = hin[SH_PRIMED] != 0 && !(a.reset && a.reset[s]);
+    const int16_t *smp = a.samples[c] + (long long)s * a.row_stride;
+    const int stride = a.L - a.C;
+    auto timeline = [&](long long i) -> int16_t {
+        if (primed) {
+            if (i < a.C) return cin[i];
+            i -= a.C;
+        }
+        return i < a.row_stride ? smp[i] : (int16_t)0;
+    };
+    if (j < a.k) {
+        int16_t *win = a.wbuf[c] + ((size_t)slot * a.k + j) * a.L;
+        for (int i = tid; i < a.L; i += 256) win[i] = timeline((long long)j * stride + i);
+    } else {
+        for (int i = tid; i < a.C; i += 256) cout[i] = timeline((long long)a.k * stride + i);      // the timeline holds k * stride + C samples
+        if (c == 0 && tid == 0) hout[SH_PRIMED] = 1u;
+    }
+}
+
+struct StreamVoteArgs {
+    const float *vad;                                  // [n_slots * k][Tn]
+    int S, n_slots, k, Tn, lb;
+    double speaking, silence_score;
+    const int *slot; const unsigned char *reset;       // optional [S]
+    const unsigned char *sin; unsigned char *sout;     // records
+    unsigned char *flags, *tail;                       // [S][k * (Tn - lb)], [S][lb]
+};
+
+// One tick of the vote, one stream per thread: `silence` comes from state_in (true for an un-primed or reset stream), the tick's windows are
+// voted as dfsmn_vote_kernel votes a clip's, the tail is what the plain rule would append if the stream ended here -- it starts from a copy
+// of `silence`, the carried value is the one the next tick continues from.
+__global__ void dfsmn_stream_vote_kernel(StreamVoteArgs a) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= a.S) return;
+    const Vote v(a.Tn, a.lb, a.speaking, a.silence_score);
+    const unsigned *hin = reinterpret_cast<const unsigned *>(a.sin) + (size_t)s * SHDR_WORDS;
+    unsigned *hout = reinterpret_cast<unsigned *>(a.sout) + (size_t)s * SHDR_WORDS;
+    unsigned char *fl = a.flags + (size_t)s * a.k * v.slide, *tl = a.tail + (size_t)s * a.lb;
+    const int slot = stream_slot(a.slot, s, a.n_slots);
+    if (slot < 0) {                        // no audio this tick: the record passes through bit for bit, a reset request is ignored
+        hout[SH_SIL] = hin[SH_SIL]; hout[SH_DONE] = hin[SH_DONE]; hout[SH_DONE + 1] = hin[SH_DONE + 1];
+        for (int i = 0; i < a.k * v.slide; ++i) fl[i] = 255;
+        for (int i = 0; i < a.lb; ++i) tl[i] = 255;
+        return;
+    }
+    const bool fresh = hin[SH_PRIMED] == 0 || (a.reset && a.reset[s]);
+    int silence = fresh ? 1 : (int)hin[SH_SIL];
+    const float *sc = nullptr;
+    for (int k = 0; k < a.k; ++k) {
+        sc = a.vad + ((size_t)slot * a.k + k) * a.Tn;
+        silence = v.window(sc, silence, fl + (size_t)k * v.slide);
+    }
+    v.tail(sc, silence, tl);
+    const unsigned long long done = (fresh ? 0ull : ((unsigned long long)hin[SH_DONE + 1] << 32 | hin[SH_DONE])) + (unsigned long long)a.k;
+    hout[SH_SIL] = (unsigned)silence;
+    hout[SH_DONE] = (unsigned)done; hout[SH_DONE + 1] = (unsigned)(done >> 32);
 }
 
 
@@ -2008,6 +2147,92 @@ extern "C" int vadx_dfsmn_vote(const float *vad, int batch, int windows, int fra
     VADX_REQUIRE(vad && flags && batch > 0 && windows > 0 && look_backward >= 1 && look_backward < frames, "vadx_dfsmn_vote: bad argument");
     hipLaunchKernelGGL(dfsmn_vote_kernel, dim3((batch + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), vad, batch,
                        windows, frames, look_backward, speaking_score, silence_score, flags);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+extern "C" int vadx_dfsmn_vote_ragged(const float *vad, int batch, int n_windows, int max_windows, const int32_t *win_first, int frames,
+                                      int look_backward, double speaking_score, double silence_score, uint8_t *flags, int64_t flag_stride,
+                                      void *stream) {
+    VADX_REQUIRE(vad && win_first && flags, "vadx_dfsmn_vote_ragged: NULL argument (vad, win_first, flags)");
+    VADX_REQUIRE(batch >= 1 && n_windows >= 1 && max_windows >= 1 && frames >= 1,
+                 "vadx_dfsmn_vote_ragged: batch=%d n_windows=%d max_windows=%d frames=%d must be positive", batch, n_windows, max_windows, frames);
+    VADX_REQUIRE(look_backward >= 1 && look_backward < frames, "vadx_dfsmn_vote_ragged: look_backward=%d outside [1, %d)", look_backward, frames);
+    const int64_t need = (int64_t)max_windows * (frames - look_backward) + look_backward;
+    VADX_REQUIRE(flag_stride >= need, "vadx_dfsmn_vote_ragged: flag_stride=%lld is below max_windows * (frames - look_backward) + look_backward = %lld",
+                 (long long)flag_stride, (long long)need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    VADX_HIP_TRY(hipMemsetAsync(flags, 255, (size_t)batch * (size_t)flag_stride, st));
+    hipLaunchKernelGGL(dfsmn_vote_ragged_kernel, dim3((batch + 63) / 64), dim3(64), 0, st, vad, batch, n_windows, max_windows, win_first, frames,
+                       look_backward, speaking_score, silence_score, flags, (long long)flag_stride);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+// carry length of a stream record, or 0 when the arguments describe no window grid
+static int stream_carry(int window_len, int look_backward) {
+    if (window_len < 1 || look_backward < 1 || look_backward >= (1 << 20)) return 0;
+    const long long C = (long long)(look_backward + 1) * SFRAME;
+    return C < window_len ? (int)C : 0;
+}
+
+extern "C" size_t vadx_dfsmn_stream_state_bytes(int streams, int window_len, int look_backward, int channels) {
+    const int C = stream_carry(window_len, look_backward);
+    return streams > 0 && C > 0 && (channels == 1 || channels == 2) ? srec_bytes(streams, C, channels) : 0;
+}
+
+// true when two records of `bytes` bytes share a byte
+static bool records_overlap(const void *a, const void *b, size_t bytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return !(x + bytes <= y || y + bytes <= x);
+}
+
+extern "C" int vadx_dfsmn_stream_windows(const int16_t *near, const int16_t *far, int64_t row_stride, int streams, int n_slots, int windows,
+                                         int window_len, int look_backward, const int32_t *slot, const uint8_t *reset, const void *state_in,
+                                         void *state_out, int16_t *near_buf, int16_t *far_buf, void *stream) {
+    VADX_REQUIRE(near && state_in && state_out && near_buf, "vadx_dfsmn_stream_windows: NULL argument (near, state_in, state_out, near_buf)");
+    VADX_REQUIRE((far == nullptr) == (far_buf == nullptr), "vadx_dfsmn_stream_windows: far and far_buf must both be given or both be NULL");
+    const int ch = far ? 2 : 1;
+    VADX_REQUIRE(streams >= 1 && n_slots >= 1 && windows >= 1 && (long long)ch * streams * ((long long)windows + 1) < (1ll << 31),
+                 "vadx_dfsmn_stream_windows: streams=%d n_slots=%d windows=%d must be positive", streams, n_slots, windows);
+    const int C = stream_carry(window_len, look_backward);
+    VADX_REQUIRE(C > 0, "vadx_dfsmn_stream_windows: window_len=%d look_backward=%d: look_backward must be at least 1 and leave a stride "
+                        "(window_len - (look_backward + 1) * 320 > 0)", window_len, look_backward);
+    VADX_REQUIRE(row_stride >= (int64_t)windows * (window_len - C), "vadx_dfsmn_stream_windows: row_stride=%lld must hold windows * stride = %lld samples",
+                 (long long)row_stride, (long long)windows * (window_len - C));
+    VADX_REQUIRE(!records_overlap(state_in, state_out, srec_bytes(streams, C, ch)), "vadx_dfsmn_stream_windows: state_in and state_out overlap");
+    VADX_REQUIRE(((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 15) == 0 &&
+                 ((reinterpret_cast<uintptr_t>(near) | reinterpret_cast<uintptr_t>(far) | reinterpret_cast<uintptr_t>(near_buf) |
+                   reinterpret_cast<uintptr_t>(far_buf)) & 1) == 0 && (reinterpret_cast<uintptr_t>(slot) & 3) == 0,
+                 "vadx_dfsmn_stream_windows: the records must be 16-byte aligned, slot 4-byte, the sample and window buffers 2-byte");
+    StreamWinArgs a;
+    a.samples[0] = near; a.samples[1] = far; a.row_stride = (long long)row_stride;
+    a.S = streams; a.n_slots = n_slots; a.k = windows; a.L = window_len; a.C = C; a.ch = ch; a.slot = slot; a.reset = reset;
+    a.sin = static_cast<const unsigned char *>(state_in); a.sout = static_cast<unsigned char *>(state_out);
+    a.wbuf[0] = near_buf; a.wbuf[1] = far_buf;
+    hipLaunchKernelGGL(dfsmn_stream_windows_kernel, dim3((unsigned)(ch * streams * (windows + 1))), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+extern "C" int vadx_dfsmn_stream_vote(const float *vad, int streams, int n_slots, int windows, int frames, int look_backward, int channels,
+                                      double speaking_score, double silence_score, const int32_t *slot, const uint8_t *reset,
+                                      const void *state_in, void *state_out, uint8_t *flags, uint8_t *tail, void *stream) {
+    VADX_REQUIRE(vad && state_in && state_out && flags && tail, "vadx_dfsmn_stream_vote: NULL argument (vad, state_in, state_out, flags, tail)");
+    VADX_REQUIRE(streams >= 1 && n_slots >= 1 && windows >= 1 && frames >= 1,
+                 "vadx_dfsmn_stream_vote: streams=%d n_slots=%d windows=%d frames=%d must be positive", streams, n_slots, windows, frames);
+    VADX_REQUIRE(look_backward >= 1 && look_backward < frames, "vadx_dfsmn_stream_vote: look_backward=%d outside [1, %d)", look_backward, frames);
+    VADX_REQUIRE(channels == 1 || channels == 2, "vadx_dfsmn_stream_vote: channels=%d must be 1 or 2", channels);
+    VADX_REQUIRE(!records_overlap(state_in, state_out, srec_bytes(streams, (look_backward + 1) * SFRAME, channels)),
+                 "vadx_dfsmn_stream_vote: state_in and state_out overlap");
+    VADX_REQUIRE(((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 15) == 0 && (reinterpret_cast<uintptr_t>(slot) & 3) == 0,
+                 "vadx_dfsmn_stream_vote: the records must be 16-byte aligned, slot 4-byte");
+    StreamVoteArgs a;
+    a.vad = vad; a.S = streams; a.n_slots = n_slots; a.k = windows; a.Tn = frames; a.lb = look_backward;
+    a.speaking = speaking_score; a.silence_score = silence_score; a.slot = slot; a.reset = reset;
+    a.sin = static_cast<const unsigned char *>(state_in); a.sout = static_cast<unsigned char *>(state_out);
+    a.flags = flags; a.tail = tail;
+    hipLaunchKernelGGL(dfsmn_stream_vote_kernel, dim3((streams + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), a);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }

@@ -1,10 +1,12 @@
-// ragged.hip -- the two copies around a RAGGED batch (clips of any lengths packed into one int16 vector, include/vadx.h "Ragged batches"):
+// ragged.hip -- the copies around a RAGGED batch (clips of any lengths packed into one int16 vector, include/vadx.h "Ragged batches"):
 //   vadx_windows_gather   packed PCM + one source offset per analysis window -> window_buf int16 [n_windows][window_len], the layout the
 //                         front-end entry points take with batch = n_windows, windows_per_clip = 1 (the slicing of
 //                         FSMN/Inference_FSMN_VAD_ONNX.py:162-167 and FireRedVAD/Inference_FireRed_ONNX.py:560-566 for every clip at once);
+//   vadx_windows_gather_any  the same rows for a window / stride that is no multiple of 8 samples (DFSMN, Inference_DFSMN_VAD_ONNX.py:221-229),
+//                         once per channel;
 //   vadx_tracks_gather    per-window scores [n_windows][win_floats] -> one zero-filled track row per clip, what vadx_vadpost takes
 //                         (the np.concatenate + [:num_valid_frames] of Inference_FireRed_ONNX.py:574-579).
-// Both are pure copies: HBM-bound, no arithmetic.
+// All are pure copies: HBM-bound, no arithmetic.
 #include "common.h"
 
 namespace vadx {
@@ -26,6 +28,17 @@ __global__ __launch_bounds__(256) void windows_gather_kernel(const int16_t *__re
     }
     const s16x8 *from = reinterpret_cast<const s16x8 *>(pcm + src);
     for (int v = tid; v < nl; v += 256) win[v] = from[v];
+}
+
+// The same copy for a grid that is not made of 16-byte runs (DFSMN: 16 001 samples every 10 881): one workgroup per window, one int16 per
+// access, any offset >= 0 and any window_len >= 1.  A window whose source range leaves [0, pcm_len) reads nothing: it is zeros.
+__global__ __launch_bounds__(256) void windows_gather_any_kernel(const int16_t *__restrict__ pcm, long long pcm_len, const long long *__restrict__ win_src,
+                                                                 int window_len, int16_t *__restrict__ wbuf) {
+    const long long w = blockIdx.x, src = win_src[w];
+    int16_t *win = wbuf + w * window_len;
+    const bool inside = src >= 0 && pcm_len >= window_len && src <= pcm_len - window_len;
+    const int16_t *from = pcm + (inside ? src : 0);
+    for (int i = threadIdx.x; i < window_len; i += 256) win[i] = inside ? from[i] : (int16_t)0;
 }
 
 // tracks[b][j] = probs[win_first[b] + j / fpw][chan_offset + j % fpw] for j < min(n_frames[b], W_b * fpw), 0 up to track_stride
@@ -59,6 +72,20 @@ extern "C" int vadx_windows_gather(const int16_t *pcm, int64_t pcm_len, const in
     VADX_REQUIRE(((reinterpret_cast<uintptr_t>(pcm) | reinterpret_cast<uintptr_t>(window_buf)) & 15) == 0 && (reinterpret_cast<uintptr_t>(win_src) & 7) == 0,
                  "vadx_windows_gather: pcm and window_buf must be 16-byte aligned, win_src 8-byte aligned");
     hipLaunchKernelGGL(windows_gather_kernel, dim3((unsigned)n_windows), dim3(256), 0, static_cast<hipStream_t>(stream), pcm, (long long)pcm_len,
+                       reinterpret_cast<const long long *>(win_src), window_len, window_buf);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+extern "C" int vadx_windows_gather_any(const int16_t *pcm, int64_t pcm_len, const int64_t *win_src, int n_windows, int window_len,
+                                       int16_t *window_buf, void *stream) {
+    VADX_REQUIRE(pcm && win_src && window_buf, "vadx_windows_gather_any: NULL argument (pcm, win_src, window_buf)");
+    VADX_REQUIRE(n_windows >= 1, "vadx_windows_gather_any: n_windows=%d must be positive", n_windows);
+    VADX_REQUIRE(pcm_len >= 1, "vadx_windows_gather_any: pcm_len=%lld must be positive", (long long)pcm_len);
+    VADX_REQUIRE(window_len >= 1, "vadx_windows_gather_any: window_len=%d must be positive", window_len);
+    VADX_REQUIRE(((reinterpret_cast<uintptr_t>(pcm) | reinterpret_cast<uintptr_t>(window_buf)) & 1) == 0 && (reinterpret_cast<uintptr_t>(win_src) & 7) == 0,
+                 "vadx_windows_gather_any: pcm and window_buf must be 2-byte aligned, win_src 8-byte aligned");
+    hipLaunchKernelGGL(windows_gather_any_kernel, dim3((unsigned)n_windows), dim3(256), 0, static_cast<hipStream_t>(stream), pcm, (long long)pcm_len,
                        reinterpret_cast<const long long *>(win_src), window_len, window_buf);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;

@@ -595,9 +595,15 @@ class DfsmnEngine:
     def detect(self, near_clips, far_clips, pad_noise_near=None, pad_noise_far=None, fusion_threshold=0.3,
                min_speech_duration=0.2, speaking_score=0.5, silence_score=0.5):
         """Equal-length clip pairs (host, any numeric dtype) [B,N] -> per clip [(start_s, end_s)]
-        (Inference_DFSMN_VAD_ONNX.py:124-163 prep, :221-278 loop)."""
+        (Inference_DFSMN_VAD_ONNX.py:124-163 prep, :221-278 loop).  A LIST or tuple of clips (far_clips a list too, or None) is taken as
+        clips of any lengths: ONE ragged batch (`ragged`, `flags_ragged`), work proportional to the audio."""
         from . import timestamps as ts
         t = self.torch
+        if isinstance(near_clips, (list, tuple)):
+            rp = self.ragged(near_clips, far_clips, pad_noise_near, pad_noise_far)
+            flags, nflags = self.flags_ragged(rp, speaking_score, silence_score)
+            fl = flags.cpu().numpy()
+            return [flag_timestamps(fl[b, :nflags[b]], self.FRAME / 16000, fusion_threshold, min_speech_duration) for b in range(len(rp))]
         near_clips = np.asarray(near_clips)
         far_clips = None if far_clips is None else np.asarray(far_clips)      # None: the near-end-only model
         B = near_clips.shape[0]
@@ -613,6 +619,230 @@ class DfsmnEngine:
                                                 flags.data_ptr(), _lib.stream_ptr()))
         fl = flags.cpu().numpy()
         return [flag_timestamps(fl[b], self.FRAME / 16000, fusion_threshold, min_speech_duration) for b in range(B)]
+
+    # ---- ragged batches: clip pairs of any lengths, one launch sequence (include/vadx.h, "DFSMN over a RAGGED batch") -----------------
+    def ragged(self, near_clips, far_clips, pad_noise_near=None, pad_noise_far=None, device=True):
+        """Clip pairs of any lengths (host, any numeric dtype; far_clips None = the near-end-only model) -> vadx.ragged.RaggedPairs on
+        this engine's window grid, each side peak-normalised and padded as `detect` does per clip.  device: True = the engine's, None =
+        keep the batch on the host."""
+        from . import timestamps as ts
+        from .ragged import RaggedPairs
+        _, stride = self.grid()
+        return RaggedPairs.from_clips(near_clips, far_clips, self.L, stride, pad_noise_near, pad_noise_far,
+                                      prep=lambda a: ts.normalize_to_int16(np.asarray(a).astype(np.float32)),
+                                      device=self.device if device is True else device)
+
+    def scores_ragged(self, rp):
+        """vad f32 [sum W, 51] of a RaggedPairs batch: rows win_first[b] .. win_first[b+1]-1 are clip b's windows.  Two gathers, then `run`
+        on the window rows (windows are stateless), which cuts its sub-batches by rows."""
+        near_buf, far_buf = rp.gather()
+        return self.run(near_buf, far_buf, 1)
+
+    def flags_ragged(self, rp, speaking_score=0.5, silence_score=0.5, vad=None):
+        """-> (flags u8 [B, max W * (51 - lb) + lb] on the device, nflags int64 [B] on the host): the first nflags[b] entries of row b are
+        clip b's `saved` list (1 = silence), the rest 255 (vadx_dfsmn_vote_ragged).  vad: `scores_ragged(rp)` when the caller has it."""
+        t = self.torch
+        vad = self.scores_ragged(rp) if vad is None else vad
+        lb, _ = self.grid()
+        slide = self.T_A - lb
+        flag_stride = rp.max_windows * slide + lb
+        flags = t.empty((len(rp), flag_stride), dtype=t.uint8, device=self.device)
+        with t.cuda.device(self.device):
+            _lib.check(self.lib.vadx_dfsmn_vote_ragged(vad.data_ptr(), len(rp), rp.n_windows, rp.max_windows, rp.win_first.data_ptr(), self.T_A,
+                                                       lb, float(speaking_score), float(silence_score), flags.data_ptr(), flag_stride,
+                                                       _lib.stream_ptr()))
+        return flags, rp.windows.astype(np.int64) * slide + lb
+
+    # ---- live streams ------------------------------------------------------------------------------------------------------------
+    def stream_flags(self, rp, windows_per_tick=1, speaking_score=0.5, silence_score=0.5):
+        """The clips of a RaggedPairs batch (host tables are enough: `ragged(..., device=None)`) run as live streams to completion through
+        a DfsmnStreamBatch: every tick advances each unfinished stream by min(windows_per_tick, fewest windows left among them), finished
+        streams go inactive.  -> per clip the uint8 flags of its ticks followed by its last tick's tail: its `saved` list."""
+        S, k_max = len(rp), int(windows_per_tick)
+        if k_max < 1:
+            raise ValueError(f"windows_per_tick={windows_per_tick} must be at least 1")
+        sb = DfsmnStreamBatch(self, S, speaking_score, silence_score, near_only=rp.far_host is None)
+        left, pos = rp.windows.astype(np.int64).copy(), np.zeros(S, dtype=np.int64)
+        saved = [[] for _ in range(S)]
+        while (left > 0).any():
+            act = left > 0
+            k = int(min(k_max, left[act].min()))
+            need = sb.samples_needed(k)
+            rows = [np.zeros((S, int(need[act].max())), dtype=np.int16) for _ in range(sb.channels)]
+            for s in np.flatnonzero(act):
+                for row, side in zip(rows, rp.padded(s)):
+                    row[s, :need[s]] = side[pos[s]:pos[s] + need[s]]
+                pos[s] += need[s]
+            flags, tail = sb.step(rows[0], rows[1] if sb.channels == 2 else None, k, active=act)
+            fl, tl = flags.cpu().numpy(), tail.cpu().numpy()
+            left[act] -= k
+            for s in np.flatnonzero(act):
+                saved[s].append(fl[s])
+                if left[s] == 0:
+                    saved[s].append(tl[s])
+        return [np.concatenate(x) for x in saved]
+
+    def stream_detect(self, near_list, far_list, pad_noise_near=None, pad_noise_far=None, windows_per_tick=1, fusion_threshold=0.3,
+                      min_speech_duration=0.2, speaking_score=0.5, silence_score=0.5):
+        """A list of clip pairs (far_list None = near-end only) run as live streams to completion (`stream_flags`) -> what `detect` returns
+        for the list.  The clips are whole here, so they are peak-normalised and padded as `detect` does; a caller with truly live audio
+        drives DfsmnStreamBatch itself."""
+        rp = self.ragged(near_list, far_list, pad_noise_near, pad_noise_far, device=None)
+        return [flag_timestamps(f, self.FRAME / 16000, fusion_threshold, min_speech_duration)
+                for f in self.stream_flags(rp, windows_per_tick, speaking_score, silence_score)]
+
+
+SHDR_WORDS, SH_SIL, SH_PRIMED, SH_DONE = 4, 0, 1, 2      # header words of a stream record (csrc/dfsmn.hip)
+
+
+class DfsmnStreamBatch:
+    """`streams` live DFSMN streams on the device (vadx_dfsmn_stream_windows + the network + vadx_dfsmn_stream_vote): every `step` advances
+    each active stream by k analysis windows.  What the reference loop carries (Inference_DFSMN_VAD_ONNX.py:221-273) -- the vote's `silence`
+    and the (look_backward + 1) * 320 samples two windows share, per channel -- stays in a device record (two, ping-ponged).  Per stream, the
+    flags of successive ticks followed by the last tick's tail are bit for bit `vadx_dfsmn_vote` over the concatenated audio's windows.  An
+    inactive stream costs no network time: only the active streams' windows are assembled and run.
+
+    The samples are taken as the int16 they arrive as.  The reference driver normalises a WHOLE clip to its peak before anything else and
+    pads its end with noise to the window grid; neither can be done on audio that is still arriving, so both are the caller's job: scale
+    with a gain of its own, and end a stream on the window grid (`pad_to_window_grid`).  near_only=True: one channel, on an engine that
+    carries the export's constants (`set_near_only_constants`)."""
+
+    def __init__(self, engine, streams, speaking_score=0.5, silence_score=0.5, near_only=False):
+        if not isinstance(engine, DfsmnEngine):
+            raise TypeError("DfsmnStreamBatch needs a vadx.dfsmn.DfsmnEngine")
+        self.engine, self.streams = engine, int(streams)
+        if self.streams <= 0:
+            raise ValueError(f"streams={streams} must be positive")
+        if near_only and getattr(engine, "pow_far", None) is None:
+            raise ValueError("near-only streams: call engine.set_near_only_constants(pow_far, far_comp) first")
+        self.channels = 1 if near_only else 2
+        self.speaking_score, self.silence_score = float(speaking_score), float(silence_score)
+        self.lb, self.stride = engine.grid()
+        self.slide = engine.T_A - self.lb
+        self.carry = engine.L - self.stride               # (lb + 1) * 320 samples
+        t = engine.torch
+        nb = _lib.lib().vadx_dfsmn_stream_state_bytes(self.streams, engine.L, self.lb, self.channels)
+        if nb == 0:
+            raise ValueError(f"no stream record for window {engine.L}, look-back {self.lb}")
+        self._rec = [t.zeros(nb, dtype=t.uint8, device=engine.device) for _ in range(2)]
+        self._cur = 0
+        self._primed = np.zeros(self.streams, dtype=bool)        # host mirror of "the stream has a carry"
+        self._pending = np.zeros(self.streams, dtype=bool)       # reset_states() requests not yet applied to an active tick
+
+    @property
+    def record(self):
+        """The current device record (uint8): header u32 [S, 4] = {silence, has a carry, windows done (u64)}, then the carry int16
+        [channels, S, (lb + 1) * 320]."""
+        return self._rec[self._cur]
+
+    def _header(self, record):
+        return record[:self.streams * SHDR_WORDS * 4].view(self.engine.torch.int32).view(self.streams, SHDR_WORDS)
+
+    def carries(self, record=None):
+        """int16 view [channels, S, carry] of a record's (default: the current one's) carried samples."""
+        r = self.record if record is None else record
+        return r[self.streams * SHDR_WORDS * 4:].view(self.engine.torch.int16).view(self.channels, self.streams, self.carry)
+
+    def stream_bytes(self, record, s):
+        """Every byte of `record` that belongs to stream s (header, carry of each channel), as one uint8 tensor."""
+        t = self.engine.torch
+        return t.cat([self._header(record)[s].view(t.uint8)] + [self.carries(record)[c, s].view(t.uint8) for c in range(self.channels)])
+
+    @property
+    def windows_done(self):
+        """int64 [S] (host): windows each stream has done since its reset, read from the device record.  Flag i of a stream's next tick
+        is frame windows_done * (51 - look_backward) + i of its audio, 20 ms per frame."""
+        return self._header(self.record).view(self.engine.torch.int64)[:, SH_DONE // 2].cpu().numpy()
+
+    def load_record(self, record):
+        """Continue from a saved copy of `record` (uint8, same streams and channels): the bytes are copied into the current record."""
+        t = self.engine.torch
+        r = record if t.is_tensor(record) else t.from_numpy(np.ascontiguousarray(record))
+        if r.dtype != t.uint8 or r.numel() != self.record.numel():
+            raise ValueError(f"record must be uint8 [{self.record.numel()}], got {r.dtype} [{r.numel()}]")
+        self.record.copy_(r.reshape(-1))
+        self._primed = self._header(self.record)[:, SH_PRIMED].cpu().numpy() != 0
+        self._pending[:] = False
+
+    def reset_states(self, streams=None):
+        """None = every stream; else stream indices or a bool mask [S].  Applies at the next tick in which the stream is active."""
+        if streams is None:
+            self._pending[:] = True
+            return
+        idx = np.asarray(streams.cpu() if hasattr(streams, "cpu") else streams)
+        if idx.dtype == bool:
+            self._pending |= self._mask(idx, "reset mask")
+        else:
+            self._pending[idx.astype(np.int64).reshape(-1)] = True
+
+    def _mask(self, m, name):
+        a = np.asarray(m.cpu() if hasattr(m, "cpu") else m).astype(bool).reshape(-1)
+        if a.shape != (self.streams,):
+            raise ValueError(f"{name} must have shape ({self.streams},), got {a.shape}")
+        return a
+
+    def samples_needed(self, windows, reset=None):
+        """int64 [S]: new samples (per channel) each stream consumes in the next tick of `windows` windows: windows * stride with a
+        carry, L + (windows - 1) * stride without one (first tick, or reset -- requested here or pending from reset_states)."""
+        k = int(windows)
+        if k < 1:
+            raise ValueError(f"windows={windows} must be at least 1")
+        fresh = ~self._primed | self._pending | (False if reset is None else self._mask(reset, "reset"))
+        return np.where(fresh, self.engine.L + (k - 1) * self.stride, k * self.stride).astype(np.int64)
+
+    def step(self, near_i16, far_i16=None, windows=1, reset=None, active=None):
+        """near_i16 / far_i16 int16 [S, >= samples_needed(windows, reset).max() over the active streams] (host or device, numpy or torch;
+        far_i16 None for near-only streams), each row holding that stream's NEW samples from column 0 -> device tensors (flags u8
+        [S, windows*(51-lb)], tail u8 [S, lb]): the voted silence flags of this tick's windows, and what the reference's plain rule would
+        append if the stream ended here.  reset / active: bool [S] or None; an inactive stream keeps its record bit for bit, ignores a
+        reset, reads 255 and is not run through the network."""
+        eng, t = self.engine, self.engine.torch
+        k, S, L = int(windows), self.streams, self.engine.L
+        if (far_i16 is None) != (self.channels == 1):
+            raise ValueError(f"this batch has {self.channels} channel(s): far_i16 must {'not ' if self.channels == 1 else ''}be given")
+        xs = []
+        for x in (near_i16, far_i16)[:self.channels]:
+            x = x if t.is_tensor(x) else t.from_numpy(np.ascontiguousarray(x))
+            if x.dtype != t.int16:
+                raise ValueError(f"samples must be int16, got {x.dtype}")
+            if x.dim() != 2 or x.shape[0] != S or (xs and x.shape != xs[0].shape):
+                raise ValueError(f"samples must be [{S}, n], the same n for both channels, got {tuple(x.shape)}")
+            xs.append(x)
+        act = np.ones(S, dtype=bool) if active is None else self._mask(active, "active")
+        req = (self._pending | self._mask(reset, "reset") if reset is not None else self._pending) & act      # resets this tick applies
+        need = int(self.samples_needed(k, reset)[act].max(initial=0))
+        if xs[0].shape[1] < need:
+            raise ValueError(f"samples rows hold {xs[0].shape[1]} samples, this tick needs {need} (samples_needed)")
+        flags = t.full((S, k * self.slide), 255, dtype=t.uint8, device=eng.device)
+        tail = t.full((S, self.lb), 255, dtype=t.uint8, device=eng.device)
+        n_slots = int(act.sum())
+        if n_slots == 0:                                   # nobody has audio: the record stays where it is
+            return flags, tail
+        xs = [x.to(eng.device).contiguous() for x in xs]
+        slot_d = None if active is None else t.from_numpy(np.where(act, np.cumsum(act) - 1, -1).astype(np.int32)).to(eng.device)
+        reset_d = t.from_numpy(req.astype(np.uint8)).to(eng.device) if req.any() else None
+        bufs = [t.empty((n_slots * k, L), dtype=t.int16, device=eng.device) for _ in xs]
+        src, dst = self._rec[self._cur], self._rec[1 - self._cur]
+        two = self.channels == 2
+        common = (None if slot_d is None else slot_d.data_ptr(), None if reset_d is None else reset_d.data_ptr(), src.data_ptr(), dst.data_ptr())
+        with t.cuda.device(eng.device):
+            _lib.check(_lib.lib().vadx_dfsmn_stream_windows(xs[0].data_ptr(), xs[1].data_ptr() if two else None, int(xs[0].shape[1]), S, n_slots,
+                                                            k, L, self.lb, *common, bufs[0].data_ptr(), bufs[1].data_ptr() if two else None,
+                                                            _lib.stream_ptr()))
+        vad = eng.run(bufs[0], bufs[1] if two else None, 1)
+        with t.cuda.device(eng.device):
+            _lib.check(_lib.lib().vadx_dfsmn_stream_vote(vad.data_ptr(), S, n_slots, k, eng.T_A, self.lb, self.channels, self.speaking_score,
+                                                         self.silence_score, *common, flags.data_ptr(), tail.data_ptr(), _lib.stream_ptr()))
+        self._cur = 1 - self._cur
+        self._primed |= act
+        self._pending &= ~act
+        return flags, tail
+
+    def timestamps(self, flags_so_far, tail, fusion_threshold=0.3, min_speech_duration=0.2):
+        """One stream's accumulated flags (1-D, every tick so far) + the last tick's tail -> [(start_s, end_s)], the reference's
+        vad_to_timestamps + process_timestamps over its `saved` list."""
+        f = np.concatenate([np.asarray(a.cpu() if hasattr(a, "cpu") else a).reshape(-1) for a in (flags_so_far, tail)])
+        return flag_timestamps(f, DfsmnEngine.FRAME / 16000, fusion_threshold, min_speech_duration)
 
 
 class DfsmnSession(Session):

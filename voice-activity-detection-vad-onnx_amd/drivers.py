@@ -3,8 +3,8 @@
 of module-level globals), same stdout summary.  Each function also accepts a LIST of files: FSMN, FireRed and FireRed-AED hand
 the list to their engine as ONE ragged batch (vadx.ragged: clips of any lengths, work proportional to the audio), and so does MarbleNet
 in both window modes (dynamic axis: vadx.ragged.RaggedFrames, one window per clip; INPUT_AUDIO_LENGTH: each clip on its own window
-grid); DFSMN runs equal-length files as one device batch per length group (`_grouped`); the Silero driver pads ragged clips into one
-batch.  The
+grid) and both DFSMN drivers (vadx.ragged.RaggedPairs: near / far pairs on a grid of odd window and stride); the Silero driver pads
+ragged clips into one batch.  The
 printed RTF is over the total audio duration.  `engine` / `model` may be an engine object, a weight dict, a checkpoint path, or the explicit
 opt-in "synthetic:<seed>" (vadx.checkpoints.resolve) -- never an implicit default."""
 from __future__ import annotations
@@ -219,7 +219,7 @@ def inference_dfsmn(test_near_end_audio="./examples/nearend_mic.wav", test_far_e
                     SPEAKING_SCORE=0.5, SILENCE_SCORE=0.5, FUSION_THRESHOLD=0.3, MIN_SPEECH_DURATION=0.2,
                     pad_noise_near=None, pad_noise_far=None, echo=print):
     """DFSMN/near_and_far_end_audio/Inference_DFSMN_VAD_ONNX.py:121-300: near-end mic + far-end reference -> AEC ->
-    mask-net VAD -> look-ahead vote -> timestamps (both text files).  Lists of paths run as a batch of clip pairs."""
+    mask-net VAD -> look-ahead vote -> timestamps (both text files).  Lists of paths run as ONE ragged batch of clip pairs of any lengths."""
     from . import dfsmn
     nears, fars = _as_list(test_near_end_audio), _as_list(test_far_end_audio)
     engine = _engine_of(dfsmn.DfsmnEngine, engine)
@@ -230,10 +230,15 @@ def inference_dfsmn(test_near_end_audio="./examples/nearend_mic.wav", test_far_e
         n = min(len(a), len(f))
         pairs.append(np.stack([a[:n], f[:n]]))
     t0 = time.time()
-    # one device batch per group of equal-length pairs; the noise of each side independently, either may be None
-    all_ts = _grouped(pairs, (pad_noise_near, pad_noise_far), lambda pr, nzn, nzf: engine.detect(
-        pr[:, 0], pr[:, 1], nzn, nzf, fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION,
-        speaking_score=SPEAKING_SCORE, silence_score=SILENCE_SCORE))
+    kw = dict(fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION, speaking_score=SPEAKING_SCORE, silence_score=SILENCE_SCORE)
+
+    def detect(pr, *nz):
+        """a list of [2, n] pairs with the (near, far) noise tuple (_detect_files), or a stacked [1, 2, n] with one noise per side (_grouped);
+        the noise of each side independently, either may be None"""
+        if isinstance(pr, list):
+            return engine.detect([p[0] for p in pr], [p[1] for p in pr], *nz[0], **kw)
+        return engine.detect(pr[:, 0], pr[:, 1], *nz, **kw)
+    all_ts = _detect_files(detect, pairs, isinstance(test_near_end_audio, (list, tuple)), (pad_noise_near, pad_noise_far))
     elapsed = time.time() - t0
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_near_end_audio, (list, tuple)), elapsed, echo)
 
@@ -241,7 +246,8 @@ def inference_dfsmn(test_near_end_audio="./examples/nearend_mic.wav", test_far_e
 def inference_dfsmn_near_only(test_vad_audio="./vad_sample.wav", engine=None, save_timestamps_second="./timestamps_second.txt",
                               save_timestamps_indices="./timestamps_indices.txt", SPEAKING_SCORE=0.5, SILENCE_SCORE=0.5,
                               FUSION_THRESHOLD=0.3, MIN_SPEECH_DURATION=0.2, pad_noise=None, echo=print):
-    """DFSMN/only_near_end_audio/Inference_DFSMN_VAD_ONNX.py: one microphone file in, timestamps out.  `engine` must
+    """DFSMN/only_near_end_audio/Inference_DFSMN_VAD_ONNX.py: one microphone file in, timestamps out (a list of files:
+    one ragged batch).  `engine` must
     carry the export's baked white-noise constants (DfsmnEngine.set_near_only_constants)."""
     from . import dfsmn, weights
     files = _as_list(test_vad_audio)
@@ -249,12 +255,10 @@ def inference_dfsmn_near_only(test_vad_audio="./vad_sample.wav", engine=None, sa
         raise ValueError("inference_dfsmn_near_only needs a DfsmnEngine carrying the export's baked white-noise constants "
                          "(DfsmnEngine.set_near_only_constants); weights.dfsmn_near_only_constants(seed) gives a stand-in")
     echo(f"\nTest Input Audio: {test_vad_audio}")
-    all_ts = []
+    clips = [audio_io.load_wav(pth, 16000).astype(np.float32) for pth in files]
     t0 = time.time()
-    for k, pth in enumerate(files):
-        a = audio_io.load_wav(pth, 16000).astype(np.float32)
-        nz = None if pad_noise is None else np.asarray(pad_noise)[k][None, :]
-        all_ts += engine.detect(a[None, :], None, nz, None, fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION,
-                                speaking_score=SPEAKING_SCORE, silence_score=SILENCE_SCORE)
+    all_ts = _detect_files(lambda c, nz: engine.detect(c, None, nz, None, fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION,
+                                                       speaking_score=SPEAKING_SCORE, silence_score=SILENCE_SCORE),
+                           clips, isinstance(test_vad_audio, (list, tuple)), pad_noise)
     elapsed = time.time() - t0
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)

@@ -11,6 +11,9 @@ Tables (include/vadx.h, "Ragged batches"):
     win_src   [sum W] sample offset of every window in `pcm`: clip_off[b] + k * stride
     order     [B]    clips by window count, longest first (stable): the launch order of one-workgroup-per-clip kernels
 
+`RaggedPairs` is the batch of DFSMN's near / far pairs: two packed vectors on one grid of odd window and stride (no 16-byte runs:
+vadx_windows_gather_any), sharing win_first and win_src.
+
 `RaggedFrames` (below) is the batch of the model whose window is the whole clip (MarbleNet, dynamic axis): no window grid, no padding --
 the clips as they are, with per-clip frame prefixes and tile tables.
 """
@@ -104,6 +107,102 @@ class RaggedBatch:
             _lib.check(_lib.lib().vadx_windows_gather(self.pcm.data_ptr(), int(self.pcm.numel()), self.win_src.data_ptr(), self.n_windows,
                                                       self.window, wbuf.data_ptr(), _lib.stream_ptr()))
         return wbuf
+
+
+class RaggedPairs:
+    """DFSMN's ragged batch: near / far clip pairs of any lengths (far None = the near-end-only model) on ONE window grid that need not be
+    made of 16-byte runs (16 001 samples every 10 881).  Per pair both sides are cut to the shorter one, go through `prep` and through
+    `pad_to_window_grid`, each side with its own noise row (DFSMN/near_and_far_end_audio/Inference_DFSMN_VAD_ONNX.py:124-163); the padded
+    clips lie end to end with NO alignment filler in two int16 vectors, `near` and `far`, which share every table: lengths [B] (samples
+    after the cut), padded_lengths [B], windows int32 [B], clip_off int64 [B], win_first int32 [B+1], win_src int64 [sum W].
+    With a device near / far / win_first / win_src are tensors there and the `*_host` attributes keep numpy; device=None keeps numpy."""
+
+    @classmethod
+    def from_clips(cls, near_clips, far_clips, window, stride, pad_noise_near=None, pad_noise_far=None, prep=None, device="cuda:0"):
+        """near_clips / far_clips: lists of 1-D arrays (int16, or whatever `prep` turns into int16); pad_noise_*: None (numpy's global RNG,
+        as the reference) or standard-normal rows -- pair b uses the first pad_b samples of row b of its side."""
+        window, stride = int(window), int(stride)
+        if window < 1 or stride < 1:
+            raise ValueError(f"window={window} and stride={stride} must be positive")
+        B = len(near_clips)
+        if B == 0:
+            raise ValueError("a ragged batch needs at least one clip")
+        if far_clips is not None and len(far_clips) != B:
+            raise ValueError(f"{B} near clips but {len(far_clips)} far clips")
+        for name, nz in (("pad_noise_near", pad_noise_near), ("pad_noise_far", pad_noise_far)):
+            if nz is not None and len(nz) < B:
+                raise ValueError(f"{name} has {len(nz)} rows for {B} clips")
+
+        def side(clips, noise, lengths):
+            rows = []
+            for b, n in enumerate(lengths):
+                a = np.asarray(clips[b]).reshape(-1)[:n]
+                a = np.asarray(prep(a) if prep is not None else a)
+                if a.dtype != np.int16:
+                    raise ValueError(f"clip {b} must be int16 (after prep), got {a.dtype}")
+                rows.append(pad_to_window_grid(a, window, stride, None if noise is None else np.asarray(noise[b]).reshape(-1)))
+            return rows
+
+        lengths = [np.asarray(c).reshape(-1).shape[0] for c in near_clips]
+        if far_clips is not None:
+            lengths = [min(n, np.asarray(c).reshape(-1).shape[0]) for n, c in zip(lengths, far_clips)]
+        if min(lengths) == 0:
+            raise ValueError(f"clip {int(np.argmin(lengths))} is empty")
+        near = side(near_clips, pad_noise_near, lengths)
+        far = None if far_clips is None else side(far_clips, pad_noise_far, lengths)
+        self = cls()
+        self.window, self.stride = window, stride
+        self.lengths = np.asarray(lengths, dtype=np.int64)
+        self.padded_lengths = np.asarray([len(r) for r in near], dtype=np.int64)       # both sides: the same length, so the same grid
+        self.windows = ((self.padded_lengths - window) // stride + 1).astype(np.int32)
+        self.clip_off = np.concatenate([[0], np.cumsum(self.padded_lengths)[:-1]]).astype(np.int64)
+        self.win_first_host = _prefix(self.windows, "windows")
+        self.n_windows, self.max_windows = int(self.win_first_host[-1]), int(self.windows.max())
+        k = np.arange(self.n_windows, dtype=np.int64) - np.repeat(self.win_first_host[:-1].astype(np.int64), self.windows)
+        self.win_src_host = np.repeat(self.clip_off, self.windows) + k * stride
+        self.near_host, self.far_host = np.concatenate(near), None if far is None else np.concatenate(far)
+        self.device = None
+        self.near, self.far, self.win_first, self.win_src = self.near_host, self.far_host, self.win_first_host, self.win_src_host
+        if device is not None:
+            self.to(device)
+        return self
+
+    def to(self, device):
+        """Upload the two packed vectors (once) and the two tables."""
+        from . import _lib
+        t = _lib.require_gpu()
+        self.device = t.device(device)
+        up = lambda a: None if a is None else t.from_numpy(a).to(self.device)      # noqa: E731
+        self.near, self.far, self.win_first, self.win_src = up(self.near_host), up(self.far_host), up(self.win_first_host), up(self.win_src_host)
+        return self
+
+    def __len__(self):
+        return int(self.lengths.shape[0])
+
+    def padded(self, b):
+        """Pair b as it was packed: (near, far) host int16 [padded_lengths[b]] each (far None for a near-only batch) =
+        pad_to_window_grid of the cut, prepped clip with that side's noise row."""
+        at = slice(int(self.clip_off[b]), int(self.clip_off[b] + self.padded_lengths[b]))
+        return self.near_host[at], None if self.far_host is None else self.far_host[at]
+
+    def gather(self):
+        """(near_buf, far_buf) int16 [n_windows, window] on the device (vadx_windows_gather_any, once per channel; far_buf None for a
+        near-only batch): row win_first[b] + k is window k of pair b."""
+        from . import _lib
+        if self.device is None:
+            raise ValueError("this batch is host-only: call .to(device) first")
+        t = _lib.require_gpu()
+        out = []
+        for pcm in (self.near, self.far):
+            if pcm is None:
+                out.append(None)
+                continue
+            wbuf = t.empty((self.n_windows, self.window), dtype=t.int16, device=self.device)
+            with t.cuda.device(self.device):
+                _lib.check(_lib.lib().vadx_windows_gather_any(pcm.data_ptr(), int(pcm.numel()), self.win_src.data_ptr(), self.n_windows,
+                                                              self.window, wbuf.data_ptr(), _lib.stream_ptr()))
+            out.append(wbuf)
+        return tuple(out)
 
 
 FE_TILE, ENC_TILE = 64, 32   # frames per front-end / encoder tile (csrc/frontend.hip: TF_FOLD, csrc/marblenet.hip: TILE)
