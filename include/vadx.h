@@ -55,8 +55,10 @@ extern "C" {
  *     vadx_marblenet_block2_ragged, vadx_marblenet_tail_ragged; then FireRed Stream-VAD over live streams: vadx_firered_stream_state_bytes,
  *     vadx_firered_stream_group_max, vadx_firered_stream_tick; then FSMN windows of any length: vadx_fsmn_long_workspace_bytes,
  *     vadx_fsmn_window_stats_long, vadx_fsmn_run_long, vadx_fsmn_clips_long; then DFSMN over ragged batches and live streams:
- *     vadx_windows_gather_any, vadx_dfsmn_vote_ragged, vadx_dfsmn_stream_state_bytes, vadx_dfsmn_stream_windows, vadx_dfsmn_stream_vote.  A caller that needs them checks for the symbols (dlsym), not
- *     for a number. */
+ *     vadx_windows_gather_any, vadx_dfsmn_vote_ragged, vadx_dfsmn_stream_state_bytes, vadx_dfsmn_stream_windows, vadx_dfsmn_stream_vote; then
+ *     MarbleNet over live streams: vadx_marblenet_stream_weights, vadx_marblenet_stream_max_frames, vadx_marblenet_stream_cap,
+ *     vadx_marblenet_stream_state_bytes, vadx_marblenet_stream_workspace_bytes, vadx_marblenet_stream_tick, vadx_frontend_logmel_stream.
+ *     A caller that needs them checks for the symbols (dlsym), not for a number. */
 #define VADX_ABI_VERSION 10
 
 /* Arithmetic of the products whose one operand is a constant (every weight matrix, every DFT table) -- float32 RESULTS in all of them:
@@ -779,6 +781,71 @@ int vadx_marblenet_block2_ragged(int cin, int kernel, const float *dw0, const fl
 int vadx_marblenet_tail_ragged(const float *dw, const float *pw, const float *pb, const float *w6, const float *b6,
                                const float *dec_w, const float *dec_b, const float *x, float *score0, float *score1,
                                const vadx_marblenet_ragged *rt, void *stream, const vadx_marblenet_cfg *cfg);
+
+/* ---- MarbleNet over LIVE STREAMS: S streams, each the audio of one virtual clip arriving in pieces.  After a stream's last piece its
+ * emitted scores, in order, are what the dynamic-axis call gives for the whole clip (n / 320 frames of n samples: the session's
+ * signal_len - 1) -- bit for bit in every frame that reads none of the log-mel frames the whole-clip front-end computes in a TAIL tile (its
+ * last F mod 64 frames when that is 1 .. 48, F = n / 160 + 1: that tile variant rounds |X|^2 with an FMA, the full tile does not, so the
+ * whole-clip call's own bits depend on where the clip ends; a stream computes every frame in the full-tile form), and within one float32
+ * ulp of the log-mel behind that.  Replaces, for a growing stream, re-running the session over a sliding buffer -- the seam is the window loop
+ * and the dynamic-axis call of NVIDIA_.../Inference_NVIDIA_MarbleNet_VAD_ONNX.py:130-135, 369-388.
+ * Geometry (published 3x2x64 layout, masks off): score frame j reads encoder frames j - 70 .. j + 70 = log-mel frames 2j - 145 .. 2j +
+ * 145 = samples up to 320 j + 23 456, so a stream emits every frame once, 73 frames (1.46 s) behind the audio it has been fed:
+ *   after N = 320 J samples and no final tick   log-mel frames 0 .. 2J - 2 are complete, max(0, J - 73) score frames are out;
+ *   a final tick at a total of n samples         brings the total to n / 320 and resets the stream.
+ * RECORD: vadx_marblenet_stream_state_bytes(S) = S * 46 048 bytes on the device, 16-byte aligned, stream s at byte 46 048 s.  Per stream,
+ * in 4-byte words (activations float32 on both arithmetics; J = samples fed / 320):
+ *       0 ..   800  log-mel history [10 frames][80], frames 2J - 11 .. 2J - 2      800 ..  3872  prologue output [128][24], frames J - 27 .. J - 4
+ *    3872 ..  5664  block 2 output [64][28], frames J - 43 .. J - 16              5664 ..  7712  block 3 output [64][32], frames J - 61 .. J - 30
+ *    7712 .. 11296  block 4 output [64][56], frames J - 101 .. J - 46            11296 .. 11508  audio carry: 417 int16 (416 samples + the
+ *   11508 .. 11510  samples fed since the reset (int64)                                           pre-emphasis tap in front), zero-padded
+ *   11510 .. 11512  score frames emitted since the reset (int64)
+ *   A frame index below 0 is a layer's zero padding and is held as zeros, so ALL-ZERO BYTES ARE A FRESH STREAM (no init call).
+ * A TICK is one call: vadx_marblenet_stream_tick runs, on `stream`, an opening kernel (checks, plan, `carry || new` rows, histories into
+ * the row buffers of the workspace), vadx_frontend_logmel_stream, the prologue, blocks 2 - 4 and the tail as stream instantiations of the
+ * whole-clip kernels (a workgroup's tile is a tile of the virtual clip; its halo comes from the history columns; frames < 0, or >= the
+ * clip's end on a final tick, are masked where the rectangular kernels mask them), and a closing kernel that writes state_out.
+ * Inputs per tick: samples int16 [S][sample_stride >= 320 k]; n_samples int32 [S]: 0 = no audio this tick, a non-final stream a positive
+ * multiple of 320 up to 320 k, a final stream anything in 0 .. 320 k; reset / final: NULL or uint8 [S] (reset applies before the audio;
+ * final runs every stage out against zeros BEHIND THE CLIP'S LAST FRAME, stage by stage -- not "feed silence" -- emits the remaining
+ * look-ahead and leaves the stream reset).  1 <= k <= vadx_marblenet_stream_max_frames() = 256 frames (5.12 s) per tick.
+ * Outputs: score0 / score1 f32 [S][cap], cap = vadx_marblenet_stream_cap(k) = k + 73, the first n_out[s] entries = the stream's next
+ * score frames, the rest NaN; n_out int32 [S].  state_in is never written and state_out is a second record (ping-pong): a tick whose
+ * F16X2 range flag was raised is repeated on VADX_ARITH_F32 from the same state_in.  A stream with n_samples = 0 and not final costs no
+ * tile, emits nothing and has its record copied bit for bit (zeroed when reset is set).  No result depends on k, on a stream's
+ * neighbours or on the order of streams.
+ * Device-side guard: a stream whose n_samples is negative, above 320 k, or no multiple of 320 while not final -- or whose record's
+ * counters no tick could have written -- is skipped: its record in state_out, its score rows and its n_out keep what they held, and
+ * nothing is indexed with its values.
+ * VADX_EINVAL, before any HIP call: a NULL pointer (reset / final may be NULL), streams < 1, k outside [1, 256], sample_stride < 320 k,
+ * state_out == state_in, an unaligned or short workspace, an arithmetic other than AUTO / F32 / F16X2 (named), F16X2 without range_flag,
+ * a front-end cfg other than the MarbleNet preset at 16 kHz on VADX_FE_KIND_SPLIT_H2 / SPLIT_B3 (named: kind, prep, hop, in-graph
+ * resampling).  Weights: those of vadx_sepconv_block / vadx_marblenet_block2 / vadx_marblenet_tail for the same arithmetic. */
+typedef struct vadx_marblenet_stream_weights {
+    const float *p_dw, *p_pw, *p_pb;                                   /* prologue (block 1) */
+    const float *b_dw0[3], *b_pw0[3], *b_b0[3], *b_dw1[3], *b_pw1[3], *b_b1[3], *b_rw[3], *b_rb[3];   /* blocks 2, 3, 4 */
+    const float *t_dw, *t_pw, *t_pb, *t_w6, *t_b6, *dec_w, *dec_b;     /* blocks 5 + 6 + decoder */
+} vadx_marblenet_stream_weights;
+int vadx_marblenet_stream_max_frames(void);
+int vadx_marblenet_stream_cap(int k);                       /* k + 73; 0 for a k outside [1, 256] */
+size_t vadx_marblenet_stream_state_bytes(int streams);
+size_t vadx_marblenet_stream_workspace_bytes(int streams, int k);   /* scratch of one tick (nothing is carried in it); 0 = bad arguments */
+int vadx_marblenet_stream_tick(const vadx_frontend_cfg *fe, const float *fe_packed, const int32_t *mel_kb_host,
+                               const vadx_marblenet_stream_weights *w, const int16_t *samples, int64_t sample_stride,
+                               const int32_t *n_samples, const uint8_t *reset, const uint8_t *final, int streams, int k,
+                               const void *state_in, void *state_out, float *score0, float *score1, int32_t *n_out,
+                               void *workspace, size_t workspace_bytes, void *stream, const vadx_marblenet_cfg *cfg);
+/* The stream front-end on its own: stream s's row = rows + s * row_stride holds `carry || new` int16 samples with NO centre padding --
+ * sample 0 is the pre-emphasis tap, frame i starts at row sample 1 + 160 i; samples at and behind row_len[s] read as zeros.  n_frames[s]
+ * frames go to rows out_row0 .. of the stream's out_rows rows of out f32 [S][out_rows][n_mels]; row_len / n_frames are device int32 [S].
+ * A frame is computed by the device functions of vadx_frontend_logmel in their full-tile (64-frame) form whatever n_frames is, so its bits
+ * are those of the whole-clip call's full tiles and depend on no neighbour frame.  Device-side guard:
+ * row_len outside [1, row_stride] or n_frames outside [1, max_frames] skips the stream.  VADX_EINVAL, before any HIP call: a NULL
+ * pointer, a kind other than VADX_FE_KIND_SPLIT_H2 / SPLIT_B3, a prep other than 1, a hop other than 160 or in-graph resampling (each
+ * named), streams / max_frames / row_stride < 1, or out_row0 + max_frames > out_rows. */
+int vadx_frontend_logmel_stream(const vadx_frontend_cfg *cfg, const float *packed, const int32_t *mel_kb_host, const int16_t *rows,
+                                int64_t row_stride, const int32_t *row_len, const int32_t *n_frames, int streams, int max_frames,
+                                float *out, int out_rows, int out_row0, void *stream);
 
 /* enc [B][C][T] -> softmax(Linear(C->2)) split into score0 / score1 [B][T]. */
 int vadx_frame_classifier(const float *enc, const float *dec_w, const float *dec_b, int batch, int channels,

@@ -54,6 +54,13 @@ class MarbleNetRagged(C.Structure):
                 ("clips", C.c_int32), ("n_tiles", C.c_int32), ("frames_total", C.c_int32), ("src_total", C.c_int32)]
 
 
+class MarbleNetStreamWeights(C.Structure):
+    """vadx_marblenet_stream_weights (include/vadx.h): device pointers of the prologue, blocks 2 - 4 and the tail + decoder"""
+    _fields_ = [("p_dw", C.c_void_p), ("p_pw", C.c_void_p), ("p_pb", C.c_void_p)] + \
+               [(k, C.c_void_p * 3) for k in ("b_dw0", "b_pw0", "b_b0", "b_dw1", "b_pw1", "b_b1", "b_rw", "b_rb")] + \
+               [(k, C.c_void_p) for k in ("t_dw", "t_pw", "t_pb", "t_w6", "t_b6", "dec_w", "dec_b")]
+
+
 class SileroCfg(C.Structure):
     """vadx_silero_cfg (include/vadx.h): per-call configuration of the Silero launches"""
     _fields_ = [("arithmetic", C.c_int32), ("sample_rate", C.c_int32), ("reserved", C.c_int32 * 2)]
@@ -224,6 +231,13 @@ SIGNATURES = {
     "vadx_sepconv_block_ragged": (_I, [C.POINTER(SepConvCfg), _P, _P, _P, _P, _L, _P, C.POINTER(MarbleNetRagged), _P, C.POINTER(MarbleNetCfg)]),
     "vadx_marblenet_block2_ragged": (_I, [_I, _I] + [_P] * 10 + [C.POINTER(MarbleNetRagged), _P, C.POINTER(MarbleNetCfg)]),
     "vadx_marblenet_tail_ragged": (_I, [_P] * 10 + [C.POINTER(MarbleNetRagged), _P, C.POINTER(MarbleNetCfg)]),
+    "vadx_marblenet_stream_max_frames": (_I, []),
+    "vadx_marblenet_stream_cap": (_I, [_I]),
+    "vadx_marblenet_stream_state_bytes": (_Z, [_I]),
+    "vadx_marblenet_stream_workspace_bytes": (_Z, [_I, _I]),
+    "vadx_marblenet_stream_tick": (_I, [C.POINTER(FrontendCfg), _P, _P, C.POINTER(MarbleNetStreamWeights), _P, _L, _P, _P, _P, _I, _I, _P, _P, _P, _P,
+                                        _P, _P, _Z, _P, C.POINTER(MarbleNetCfg)]),
+    "vadx_frontend_logmel_stream": (_I, [C.POINTER(FrontendCfg), _P, _P, _P, _L, _P, _P, _I, _I, _P, _I, _I, _P]),
     "vadx_frame_classifier": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "vadx_dfsmn_frame_stats": (_I, [C.POINTER(FtView), C.POINTER(FtView), _I, _I, _P, _P]),
     "vadx_dfsmn_stats_merge": (_I, [_P, _P, _I, _P, _P]),

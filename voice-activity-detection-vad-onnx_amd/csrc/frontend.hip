@@ -1309,6 +1309,37 @@ __global__ __launch_bounds__(SQ_THREADS, 2) void frontend_split_ragged_kernel(
     FE_TILE64_LADDER(dc, tile - first, split_tile<SC, MT>(dc, P, win, 0.f, f0, out_win, fsmem));
 }
 
+// The split kernel over LIVE STREAMS (include/vadx.h: vadx_frontend_logmel_stream): one workgroup per (stream, 64-frame tile).  Stream
+// s's row = rows + s * row_stride holds `carry || new` samples with NO centre padding: sample 0 is the pre-emphasis tap of sample 1, and
+// frame i starts at row sample 1 + hop * i -- split_tile's window geometry with a centre pad of -1 (n0 = f0 * hop + tap0 + 1), so a frame
+// is computed by the very instructions of the whole-clip kernels; samples at and behind row_len[s] read as zeros (the STFT's right pad
+// on a stream's last tick).  n_frames[s] rows are written from row out_row0 of the stream's out_rows rows of `out`.  A workgroup whose
+// entries do not fit the buffers returns before its first read or write of them.
+struct FeStream {
+    const int *row_len, *n_frames;
+    long long row_stride;
+    int streams, tiles, max_frames, out_rows, out_row0;
+};
+template <typename SC>
+__global__ __launch_bounds__(SQ_THREADS, 2) void frontend_split_stream_kernel(
+    Dev d, const float *__restrict__ P, const int16_t *__restrict__ rows, FeStream r, float *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char fsmem[];
+    const int s = blockIdx.x / r.tiles, tile = blockIdx.x - s * r.tiles;
+    if (s >= r.streams) return;
+    const int len = r.row_len[s], frames = r.n_frames[s];
+    if (len < 1 || len > r.row_stride || frames < 1 || frames > r.max_frames || tile * TF_FOLD >= frames) return;
+    Dev dc = d;                     // this stream's geometry in the uniform fields split_tile and mel_phase read
+    dc.center_pad = -1; dc.window_len = len; dc.frames = frames;
+    // FULL tiles only (four m-tiles, rows at and behind `frames` not stored): split_tile's four tile variants do not round alike -- the
+    // compiler contracts re * re + im * im into an FMA in the tail variants and not in the full tile -- and a stream's frame must not
+    // depend on how many frames share its tick.  The full tile is the variant every frame of a whole clip but its last < 49 is computed by.
+    dc.tiles64 = (frames + TF_FOLD - 1) / TF_FOLD;
+    dc.tail_mt = 0;
+    const int16_t *win = rows + (long long)s * r.row_stride;
+    float *out_win = out + ((size_t)s * r.out_rows + r.out_row0) * d.out_stride;
+    FE_TILE64_LADDER(dc, tile, split_tile<SC, MT>(dc, P, win, 0.f, f0, out_win, fsmem));
+}
+
 __global__ __launch_bounds__(THREADS, 4) void frontend_logmel_kernel(
     Dev d, const float *__restrict__ P, const int16_t *__restrict__ audio, long long row_stride,
     long long win_stride, int windows_per_clip, const float *__restrict__ means, float *__restrict__ out,
@@ -1676,6 +1707,40 @@ extern "C" int vadx_frontend_logmel_ragged(const vadx_frontend_cfg *cfg, const f
     } else {
         VADX_DYN_LDS(frontend_split_ragged_kernel<vadx::SchemeH2>, 160 * 1024);
         hipLaunchKernelGGL(frontend_split_ragged_kernel<vadx::SchemeH2>, dim3((unsigned)n_tiles), dim3(SQ_THREADS), slds, st, d, packed, pcm, r, out);
+    }
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+// The split kernel over live streams: rows of `carry || new` samples, no centre padding (frontend_split_stream_kernel above);
+// cfg->frames and cfg->window_len are not read by the launch -- row_len / n_frames say them per stream
+extern "C" int vadx_frontend_logmel_stream(const vadx_frontend_cfg *cfg, const float *packed, const int32_t *mel_kb_host, const int16_t *rows,
+                                           int64_t row_stride, const int32_t *row_len, const int32_t *n_frames, int streams, int max_frames,
+                                           float *out, int out_rows, int out_row0, void *stream) {
+    static const char who[] = "vadx_frontend_logmel_stream";
+    VADX_REQUIRE(cfg && packed && mel_kb_host && rows && row_len && n_frames && out, "%s: NULL argument", who);
+    VADX_REQUIRE(is_split(cfg->fold), "%s: DFT product kind %d is not built for streams (VADX_FE_KIND_SPLIT_H2 = %d or VADX_FE_KIND_SPLIT_B3 = %d)",
+                 who, cfg->fold, (int)K_SPLIT_H2, (int)K_SPLIT_B3);
+    VADX_REQUIRE(cfg->prep == 1 && cfg->hop == 160 && cfg->in_window_len <= 0, "%s: prep %d (hop %d, in_window_len %d) is not built for streams: "
+                 "the two-tap prep 1 at 16 kHz only (hop 160, no in-graph resampling)", who, cfg->prep, cfg->hop, cfg->in_window_len);
+    VADX_REQUIRE(streams >= 1 && max_frames >= 1 && row_stride >= 1 && out_row0 >= 0 && (long long)out_row0 + max_frames <= out_rows,
+                 "%s: streams=%d max_frames=%d row_stride=%lld out_row0=%d out_rows=%d do not fit (rows out_row0 .. out_row0 + max_frames of out_rows)",
+                 who, streams, max_frames, (long long)row_stride, out_row0, out_rows);
+    Dev d;
+    VADX_REQUIRE(derive(cfg, &d) == 0, "%s: unsupported geometry", who);
+    for (int mt = 0; mt < d.nmt; ++mt) { d.mel_kb_lo[mt] = mel_kb_host[2 * mt]; d.mel_kb_hi[mt] = mel_kb_host[2 * mt + 1]; }
+    const size_t slds = split_lds_bytes(&d);
+    VADX_REQUIRE(slds <= 160 * 1024, "%s: geometry needs %zu B of LDS", who, slds);
+    const int tiles = (max_frames + TF_FOLD - 1) / TF_FOLD;
+    VADX_REQUIRE((long long)streams * tiles < (1LL << 31), "%s: too many tiles", who);
+    const FeStream r{row_len, n_frames, (long long)row_stride, streams, tiles, max_frames, out_rows, out_row0};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (d.fold == K_SPLIT_B3) {
+        VADX_DYN_LDS(frontend_split_stream_kernel<vadx::SchemeB3>, 160 * 1024);
+        hipLaunchKernelGGL(frontend_split_stream_kernel<vadx::SchemeB3>, dim3((unsigned)(streams * tiles)), dim3(SQ_THREADS), slds, st, d, packed, rows, r, out);
+    } else {
+        VADX_DYN_LDS(frontend_split_stream_kernel<vadx::SchemeH2>, 160 * 1024);
+        hipLaunchKernelGGL(frontend_split_stream_kernel<vadx::SchemeH2>, dim3((unsigned)(streams * tiles)), dim3(SQ_THREADS), slds, st, d, packed, rows, r, out);
     }
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;

@@ -115,8 +115,42 @@ struct Ragged {
     int clips, n_tiles, dst_total, src_total;
 };
 struct NoTables {};
-template <bool RG> struct TablesOf { typedef NoTables type; };
-template <> struct TablesOf<true> { typedef Ragged type; };
+// Live streams (include/vadx.h: vadx_marblenet_stream_tick), RG = 2: a workgroup's tile is a tile of the stream's VIRTUAL CLIP.  Frame
+// indices are global (frame 0 = the stream's first encoder frame since its reset); the launch's input is the stream's row buffer whose
+// column 0 holds global frame g0 (history columns first, then what the launch in front wrote this tick), frames outside [0, T_in) read
+// as zeros exactly where the rectangular kernels mask them, and frame t of the output goes to column t + ocol of the next row buffer.
+// plan[s] = what stream_open_kernel derived from the record and the tick's inputs; a stream it refused or found idle costs no tile.
+constexpr int PLAN_WORDS = 16;
+enum PlanWord { PL_ACTIVE = 0, PL_J = 1, PL_N = 2, PL_FINAL = 3, PL_KF = 4, PL_NOUT = 5, PL_MEL_END = 6, PL_END = 7 };      // PL_END + stage: o1 of stage 0 .. 4
+struct Stream {
+    const int *plan;
+    int stage, off_out, off_in, in_h, out_h, in_w, out_w, tiles, streams;      // off_*: position of a stage behind the fed frame count J
+};
+template <int RG> struct TablesOf { typedef NoTables type; };
+template <> struct TablesOf<1> { typedef Ragged type; };
+template <> struct TablesOf<2> { typedef Stream type; };
+struct StreamTile { bool ok; int s, t0, T_in, t_end, g0, ocol; };
+__device__ __forceinline__ StreamTile stream_tile(const Stream &r) {
+    StreamTile k;
+    k.ok = false; k.s = 0; k.t0 = 0; k.T_in = 0; k.t_end = 0; k.g0 = 0; k.ocol = 0;
+    const int s = blockIdx.x / r.tiles, tile = blockIdx.x - s * r.tiles;
+    if (s >= r.streams) return k;
+    const int *p = r.plan + (size_t)s * PLAN_WORDS;
+    if (p[PL_ACTIVE] != 1) return k;
+    const int J = p[PL_J], o0 = J - r.off_out, o1 = p[PL_END + r.stage];
+    const int t0 = o0 + tile * TILE;
+    if (o1 <= 0 || t0 >= o1 || t0 + TILE <= 0) return k;             // nothing of this tile is a frame of the clip
+    k.ok = true; k.s = s; k.t0 = t0; k.t_end = o1;
+    k.T_in = r.stage == 0 ? p[PL_MEL_END] : p[PL_END + r.stage - 1];
+    k.g0 = (r.stage == 0 ? 2 * J - 1 : J - r.off_in) - r.in_h;
+    k.ocol = r.out_h - o0;
+    return k;
+}
+// column of global frame tc in a row buffer of width w whose column 0 is frame g0 (clamped: an index is never outside the buffer)
+__device__ __forceinline__ int stream_col(int tc, int g0, int w) {
+    const int c = tc - g0;
+    return c < 0 ? 0 : (c >= w ? w - 1 : c);
+}
 struct RaggedTile { bool ok; int t0, T, T_src; long long first, src_row; };
 template <bool STRIDE2>
 __device__ __forceinline__ RaggedTile ragged_tile(const Ragged &r) {
@@ -143,7 +177,7 @@ __device__ __forceinline__ RaggedTile ragged_tile(const Ragged &r) {
 
 // AR = 2: the prologue form only (depthwise, no residual branch, 128 filters): filter -> split pass -> gemm8_h2 (fp16 x 2 split products)
 // RG (instantiated for the prologue <11, 1, 2> only): T_in / T_out come from the tables, x is time-major with row stride xs_t
-template <int KT, int DT, int ST, int AR = 0, bool RG = false>
+template <int KT, int DT, int ST, int AR = 0, int RG = 0>
 __global__ __launch_bounds__(THREADS, 2) void sepconv_block_kernel(
     Cfg c, const float *__restrict__ dw_w, const float *__restrict__ pw_w, const float *__restrict__ pw_b,
     const float *__restrict__ res_w, const float *__restrict__ res_b, const float *__restrict__ x,
@@ -156,10 +190,16 @@ __global__ __launch_bounds__(THREADS, 2) void sepconv_block_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int b, t0;
     long long first = 0, src_off = 0;           // RG: the clip's first output frame in the packed buffers / first float in x
-    if constexpr (RG) {
+    int g0 = 0, ocol = 0, in_w = 0, out_w = 0;  // RG = 2: the stream's row buffers (see Stream)
+    if constexpr (RG == 1) {
         const RaggedTile k = ragged_tile<true>(rg);
         if (!k.ok) return;
         b = 0; t0 = k.t0; T_in = k.T_src; T_out = k.T; first = k.first; src_off = k.src_row * xs_t;
+    } else if constexpr (RG == 2) {
+        const StreamTile k = stream_tile(rg);
+        if (!k.ok) return;
+        b = k.s; t0 = k.t0; T_in = k.T_in; T_out = k.t_end; g0 = k.g0; ocol = k.ocol; in_w = rg.in_w; out_w = rg.out_w;
+        src_off = (long long)b * in_w * xs_t;
     } else {
         b = blockIdx.x / tiles; t0 = (blockIdx.x - b * tiles) * TILE;
     }
@@ -176,7 +216,7 @@ __global__ __launch_bounds__(THREADS, 2) void sepconv_block_kernel(
                 for (int h = 0; h < 2; ++h) {
                     const int j = j0 + u * (THREADS / 64) + wave, ch = lane + 64 * h, ti = tin0 + j;
                     const int tc = ti < 0 ? 0 : (ti >= T_in ? T_in - 1 : ti), cc = ch < c.cin ? ch : c.cin - 1;
-                    v[u][h] = xb[(long long)tc * xs_t + cc];
+                    v[u][h] = xb[(long long)(RG == 2 ? stream_col(tc, g0, in_w) : tc) * xs_t + cc];
                 }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
@@ -282,13 +322,18 @@ __global__ __launch_bounds__(THREADS, 2) void sepconv_block_kernel(
         layer<2, false>(r);
     }
     __syncthreads();
-    float *yb = y + (RG ? first * c.cout : (long long)b * c.cout * T_out);
+    float *yb = y + (RG == 2 ? (long long)b * c.cout * out_w : RG ? first * c.cout : (long long)b * c.cout * T_out);
     for (int e = tid; e < c.cout * TILE; e += THREADS) {
         const int ch = e / TILE, m = e - ch * TILE;
         if (t0 + m < T_out) {
             float v = OUT[ch * A_LD + m];
             if (c.cres) { v += ROUT[ch * A_LD + m]; if (c.relu) v = fmaxf(v, 0.f); }
-            yb[(long long)ch * T_out + t0 + m] = v;
+            if constexpr (RG == 2) {
+                const int col = t0 + m + ocol;
+                if (t0 + m >= 0 && col >= 0 && col < out_w) yb[(long long)ch * out_w + col] = v;
+            } else {
+                yb[(long long)ch * T_out + t0 + m] = v;
+            }
         }
     }
 }
@@ -512,7 +557,7 @@ __device__ __forceinline__ void kmul(const typename KPreOf<AR>::type &p, int kdi
     else kgemm<MT>(p, kdim, act, lda, acol0, dst, ldd, bias, relu);
 }
 
-template <int K, int AR, bool RG = false>
+template <int K, int AR, int RG = 0>
 __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
     Blk2 c, const float *__restrict__ dw0, const float *__restrict__ pw0, const float *__restrict__ b0,
     const float *__restrict__ dw1, const float *__restrict__ pw1, const float *__restrict__ b1,
@@ -521,10 +566,15 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int b, t0;
     long long first = 0;                        // RG: the clip's first frame in the packed buffers; c.T becomes the clip's frame count
-    if constexpr (RG) {
+    int g0 = 0, ocol = 0, in_w = 0, out_w = 0, t_end = 0;      // RG = 2: the stream's row buffers (see Stream); c.T becomes the input's end
+    if constexpr (RG == 1) {
         const RaggedTile k = ragged_tile<false>(rg);
         if (!k.ok) return;
         b = 0; t0 = k.t0; c.T = k.T; first = k.first;
+    } else if constexpr (RG == 2) {
+        const StreamTile k = stream_tile(rg);
+        if (!k.ok) return;
+        b = k.s; t0 = k.t0; c.T = k.T_in; t_end = k.t_end; g0 = k.g0; ocol = k.ocol; in_w = rg.in_w; out_w = rg.out_w;
     } else {
         b = blockIdx.x / tiles; t0 = (blockIdx.x - b * tiles) * TILE;
     }
@@ -536,7 +586,7 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
     float *D0 = IN, *D1 = IN, *OUT = H1;
     unsigned char *PL = reinterpret_cast<unsigned char *>(ROUT + c.c2 * A_LD);      // AR = 3: operand planes [8 k-groups][<= 48 columns][8] x 2
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *xb = x + (RG ? first * c.cin : (long long)b * c.cin * c.T);
+    const float *xb = x + (RG == 2 ? (long long)b * c.cin * in_w : RG ? first * c.cin : (long long)b * c.cin * c.T);
     const int tin0 = t0 - 2 * PAD;
     const KP wres = kpre<AR>(rw, c.cinp);                    // in flight while the input tile is staged
     // ---- stage the block input (channel-first source: lane = time, wave = channel), unconditional clamped loads
@@ -546,7 +596,7 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
         for (int u = 0; u < 8; ++u) {
             const int ch = ch0 + u * (THREADS / 64) + wave, ti = tin0 + lane;
             const int tc = ti < 0 ? 0 : (ti >= c.T ? c.T - 1 : ti), cc = ch < c.cin ? ch : c.cin - 1;
-            v[u] = xb[(long long)cc * c.T + tc];
+            v[u] = RG == 2 ? xb[(long long)cc * in_w + stream_col(tc, g0, in_w)] : xb[(long long)cc * c.T + tc];
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -639,10 +689,15 @@ __global__ __launch_bounds__(THREADS, 6) void jasper_block2_kernel(
         kmul<AR, 2>(wpw1, c.c1, D1, A_LD, 0, OUT, A_LD, b1, false, amax);
     }
     __syncthreads();
-    float *yb = y + (RG ? first * c.c2 : (long long)b * c.c2 * c.T);
+    float *yb = y + (RG == 2 ? (long long)b * c.c2 * out_w : RG ? first * c.c2 : (long long)b * c.c2 * c.T);
     for (int e = tid; e < c.c2 * TILE; e += THREADS) {
         const int ch = e / TILE, m = e - ch * TILE;
-        if (t0 + m < c.T) yb[(long long)ch * c.T + t0 + m] = fmaxf(OUT[ch * A_LD + m] + ROUT[ch * A_LD + m], 0.f);
+        if constexpr (RG == 2) {
+            const int col = t0 + m + ocol;
+            if (t0 + m >= 0 && t0 + m < t_end && col >= 0 && col < out_w) yb[(long long)ch * out_w + col] = fmaxf(OUT[ch * A_LD + m] + ROUT[ch * A_LD + m], 0.f);
+        } else {
+            if (t0 + m < c.T) yb[(long long)ch * c.T + t0 + m] = fmaxf(OUT[ch * A_LD + m] + ROUT[ch * A_LD + m], 0.f);
+        }
     }
     if (AR >= vadx::VADX_AR_H2) vadx::range_flag_raise(range_flag, amax);          // an operand left the fp16 range: the host recomputes this batch on float32
 }
@@ -659,7 +714,7 @@ struct Tail { int cin, cmid, k, dil, in_ld, T; };
 // needs a transposing split pass (item = (8 channels, frame): eight conflict-free reads, 24 VALU, one 16-byte store per plane into the dead
 // input tile's place); block 5's conv takes the weights as its A operand and stores its ReLU output straight into block 6's B planes
 // [channel / 8][frame][8] (8-byte stores, in H's place), block 6 takes the activations as A and stores float32 rows for the decoder.
-template <int AR, bool RG = false>
+template <int AR, int RG = 0>
 __global__ __launch_bounds__(THREADS, 6) void marblenet_tail_kernel(
     Tail c, const float *__restrict__ dw, const float *__restrict__ pw, const float *__restrict__ pb,
     const float *__restrict__ w6, const float *__restrict__ b6, const float *__restrict__ dec_w, const float *__restrict__ dec_b,
@@ -668,10 +723,16 @@ __global__ __launch_bounds__(THREADS, 6) void marblenet_tail_kernel(
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int b, t0;
     long long first = 0;                        // RG: the clip's first frame in the packed buffers; c.T becomes the clip's frame count
-    if constexpr (RG) {
+    int g0 = 0, ocol = 0, in_w = 0, out_w = 0, t_end = 0;      // RG = 2: the stream's row buffer (see Stream); out_w = the score rows' cap
+    if constexpr (RG == 1) {
         const RaggedTile k = ragged_tile<false>(rg);
         if (!k.ok) return;
         b = 0; t0 = k.t0; c.T = k.T; first = k.first;
+    } else if constexpr (RG == 2) {
+        const StreamTile k = stream_tile(rg);
+        if (!k.ok) return;
+        b = k.s; t0 = k.t0; c.T = k.T_in; t_end = k.t_end; g0 = k.g0; in_w = rg.in_w; out_w = rg.out_w;
+        ocol = k.ocol < 0 ? k.ocol : 0;         // (out_h = 0: ocol = -o0) a score row starts at the stream's first REAL frame this tick, max(o0, 0)
     } else {
         b = blockIdx.x / tiles; t0 = (blockIdx.x - b * tiles) * TILE;
     }
@@ -681,7 +742,7 @@ __global__ __launch_bounds__(THREADS, 6) void marblenet_tail_kernel(
     float *IN = lds, *D = IN + c.cin * IN_LD, *H = D + c.cin * A_LD, *OUT = IN;
     float *red = D;                                 // [16 parts][32 frames][2] once D is dead
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *xb = x + (RG ? first * c.cin : (long long)b * c.cin * c.T);
+    const float *xb = x + (RG == 2 ? (long long)b * c.cin * in_w : RG ? first * c.cin : (long long)b * c.cin * c.T);
     const int tin0 = t0 - PAD;
     for (int ch0 = 0; ch0 < c.cin; ch0 += 4 * (THREADS / 64)) {
         float v[4][2];
@@ -691,7 +752,7 @@ __global__ __launch_bounds__(THREADS, 6) void marblenet_tail_kernel(
             for (int h = 0; h < 2; ++h) {
                 const int ch = ch0 + u * (THREADS / 64) + wave, ti = tin0 + lane + 64 * h;
                 const int tc = ti < 0 ? 0 : (ti >= c.T ? c.T - 1 : ti), cc = ch < c.cin ? ch : c.cin - 1;
-                v[u][h] = xb[(long long)cc * c.T + tc];
+                v[u][h] = RG == 2 ? xb[(long long)cc * in_w + stream_col(tc, g0, in_w)] : xb[(long long)cc * c.T + tc];
             }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -754,7 +815,17 @@ __global__ __launch_bounds__(THREADS, 6) void marblenet_tail_kernel(
         red[(part * TILE + m) * 2 + 1] = z1;
     }
     __syncthreads();
-    if (tid < TILE && t0 + tid < c.T) {
+    if constexpr (RG == 2) {                        // the frame's place in the stream's score row
+        const int col = t0 + tid + ocol;
+        if (tid < TILE && t0 + tid >= 0 && t0 + tid < t_end && col >= 0 && col < out_w) {
+            float z0 = dec_b[0], z1 = dec_b[1];
+#pragma unroll
+            for (int part = 0; part < THREADS / 32; ++part) { z0 += red[(part * TILE + tid) * 2]; z1 += red[(part * TILE + tid) * 2 + 1]; }
+            const float mx = fmaxf(z0, z1), e0 = expf(z0 - mx), e1 = expf(z1 - mx), inv = 1.0f / (e0 + e1);
+            s0[(long long)b * out_w + col] = e0 * inv;
+            s1[(long long)b * out_w + col] = e1 * inv;
+        }
+    } else if (tid < TILE && t0 + tid < c.T) {
         float z0 = dec_b[0], z1 = dec_b[1];
 #pragma unroll
         for (int part = 0; part < THREADS / 32; ++part) { z0 += red[(part * TILE + tid) * 2]; z1 += red[(part * TILE + tid) * 2 + 1]; }
@@ -782,6 +853,169 @@ __global__ void frame_classifier_kernel(const float *__restrict__ enc, const flo
     const float m = fmaxf(z0, z1), e0 = expf(z0 - m), e1 = expf(z1 - m), inv = 1.0f / (e0 + e1);
     s0[idx] = e0 * inv;
     s1[idx] = e1 * inv;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Live streams: the device record and the two kernels around a tick's launches (include/vadx.h: vadx_marblenet_stream_tick).
+// A stream that has been fed 320 J samples stands, stage by stage, a fixed distance behind J: log-mel frames 0 .. 2J - 2 are complete,
+// the prologue has written encoder frames < J - 3, blocks 2 / 3 / 4 frames < J - 15 / J - 29 / J - 45, and score frames < J - 73 are out
+// (negative = none yet).  The record keeps, per launch boundary, the frames in front of that position the next launch's filter reaches
+// back to; an index below 0 is the layers' zero padding, which is what an all-zero record holds: zero bytes = a fresh stream.
+//   words (4 bytes)   0 ..   800  log-mel history   [10 frames][80]  (time-major)      frames 2J - 11 .. 2J - 2
+//                   800 ..  3872  prologue output   [128][24]                           frames  J - 27 ..  J - 4
+//                  3872 ..  5664  block 2 output    [64][28]                            frames  J - 43 ..  J - 16
+//                  5664 ..  7712  block 3 output    [64][32]                            frames  J - 61 ..  J - 30
+//                  7712 .. 11296  block 4 output    [64][56]                            frames  J - 101 .. J - 46
+//                 11296 .. 11508  audio carry       417 int16 (the last 416 samples + the pre-emphasis tap in front), zero-padded
+//                 11508, 11509    samples fed since the reset (int64);   11510, 11511   score frames emitted since the reset (int64)
+// ---------------------------------------------------------------------------------------------
+constexpr int R_MEL = 0, R_P = 800, R_B2 = 3872, R_B3 = 5664, R_B4 = 7712, R_PCM = 11296, R_FED = 11508, R_EMIT = 11510, R_WORDS = 11512;
+constexpr int CARRY = 417, HOP2 = 320, LOOKAHEAD = 73, K_MAX = 256, J_CLAMP = 1 << 24;
+constexpr int ST_OFF[5] = {3, 15, 29, 45, 73};       // position of the prologue, blocks 2 - 4 and the scores behind J
+// INVARIANT the row buffers rest on: they are scratch that nobody initialises, so every column a launch may read must have been written
+// this tick -- by stream_open_kernel (the history columns) or by the launch in front (the new ones).  That holds because the history
+// width of a boundary EQUALS the reach of the stage behind it: 2 * pad of the prologue (k 11: 10 log-mel frames) and of the tail (k 29,
+// dilation 2: 56), 4 * pad of a fused block (two sub-blocks of k 13 / 15 / 17: 24 / 28 / 32), and because ST_OFF[i] - ST_OFF[i - 1] is
+// half of that, so a tile's first input column is column 0.  Columns below frame 0 may hold anything (an early-out tile wrote nothing):
+// every load masks them by index and stream_close_kernel writes zeros for them.  Change a kernel size and all three tables change with it;
+// a width short of the reach reads unwritten memory (possibly NaN, which raises the range flag), a longer one carries dead columns.
+constexpr int ST_HIST[5] = {10, 24, 28, 32, 56};     // history frames IN FRONT of stage i (its input's): log-mel, prologue, blocks 2 - 4
+constexpr int ST_EXTRA[5] = {4, 16, 30, 46, 73};     // frames beyond k a stage can write on a stream's final tick
+constexpr int ST_CH[4] = {128, 64, 64, 64};          // channels of the prologue's and the blocks' outputs
+constexpr int ST_REC[5] = {R_MEL, R_P, R_B2, R_B3, R_B4};
+
+// the workspace of one tick: plan, the front-end's two tables, the sample rows, then one row buffer per launch boundary
+struct StreamWs {
+    int *plan, *fe_len, *fe_frames;
+    int16_t *pcm;
+    float *rows[5];          // log-mel [S][w[0]][80]; prologue [S][128][w[1]]; blocks 2 - 4 [S][64][w[2 .. 4]]
+    int pcm_w, w[5];
+};
+static size_t stream_ws_layout(int streams, int k, StreamWs *ws, char *base) {
+    size_t at = 0;
+    auto take = [&](size_t bytes) { char *p = base ? base + at : nullptr; at += (bytes + 255) & ~(size_t)255; return p; };
+    ws->pcm_w = (CARRY + HOP2 * k + 7) & ~7;
+    ws->w[0] = ST_HIST[0] + 2 * k + 2;
+    for (int i = 1; i < 5; ++i) ws->w[i] = ST_HIST[i] + k + ST_EXTRA[i - 1];
+    ws->plan = reinterpret_cast<int *>(take((size_t)streams * PLAN_WORDS * 4));
+    ws->fe_len = reinterpret_cast<int *>(take((size_t)streams * 4));
+    ws->fe_frames = reinterpret_cast<int *>(take((size_t)streams * 4));
+    ws->pcm = reinterpret_cast<int16_t *>(take((size_t)streams * ws->pcm_w * 2));
+    ws->rows[0] = reinterpret_cast<float *>(take((size_t)streams * ws->w[0] * 80 * 4));
+    for (int i = 1; i < 5; ++i) ws->rows[i] = reinterpret_cast<float *>(take((size_t)streams * ST_CH[i - 1] * ws->w[i] * 4));
+    return at;
+}
+
+struct StreamIO {
+    const int16_t *samples;
+    long long sample_stride;
+    const int *n_samples;
+    const unsigned char *reset, *final;
+    const unsigned *state_in;
+    unsigned *state_out;
+    float *score0, *score1;
+    int *n_out;
+    int k, cap;
+};
+
+// One workgroup per stream, before the tick's launches: checks the stream's inputs, writes its plan, and for a stream that runs lays
+// out `carry || new` samples and the histories in the row buffers.  A refused stream (n_samples outside its range, a record whose
+// counter no tick could have written) touches nothing but its plan; an idle one (no samples, not final) copies its record.
+__global__ __launch_bounds__(256) void stream_open_kernel(StreamIO io, StreamWs ws) {
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const unsigned *rin = io.state_in + (size_t)s * R_WORDS;
+    unsigned *rout = io.state_out + (size_t)s * R_WORDS;
+    int *plan = ws.plan + (size_t)s * PLAN_WORDS;
+    const int n = io.n_samples[s];
+    const bool rs = io.reset && io.reset[s], fin = io.final && io.final[s];
+    const long long fed0 = rs ? 0 : *reinterpret_cast<const long long *>(rin + R_FED);
+    const long long emit0 = rs ? 0 : *reinterpret_cast<const long long *>(rin + R_EMIT);
+    const bool ok = n >= 0 && n <= io.k * HOP2 && (fin || n % HOP2 == 0) && fed0 >= 0 && fed0 % HOP2 == 0 && emit0 >= 0;
+    if (!ok) {
+        if (tid == 0) { plan[PL_ACTIVE] = -1; ws.fe_len[s] = 0; ws.fe_frames[s] = 0; }
+        return;
+    }
+    float *sc0 = io.score0 + (size_t)s * io.cap, *sc1 = io.score1 + (size_t)s * io.cap;
+    for (int e = tid; e < io.cap; e += 256) { sc0[e] = __builtin_nanf(""); sc1[e] = __builtin_nanf(""); }
+    if (n == 0 && !fin) {
+        if (tid == 0) { plan[PL_ACTIVE] = 0; ws.fe_len[s] = 0; ws.fe_frames[s] = 0; io.n_out[s] = 0; }
+        for (int e = tid; e < R_WORDS; e += 256) rout[e] = rs ? 0u : rin[e];
+        return;
+    }
+    const long long J64 = fed0 / HOP2;
+    const int J = J64 > J_CLAMP ? J_CLAMP : (int)J64;         // only the distance to frame 0 matters, and only while it is below the look-ahead
+    const int kf = n / HOP2;
+    const int T1 = J + kf + 1, F = 2 * J + n / 160 + 1;       // final: the virtual clip's encoder / log-mel frame counts
+    const int mel_end = fin ? F : 2 * (J + kf) - 1;
+    const int sc_end = fin ? T1 - 1 : J + kf - LOOKAHEAD;
+    const int o0 = J - LOOKAHEAD;
+    const int nout = (sc_end > 0 ? sc_end : 0) - (o0 > 0 ? o0 : 0);
+    if (tid == 0) {
+        plan[PL_ACTIVE] = 1; plan[PL_J] = J; plan[PL_N] = n; plan[PL_FINAL] = fin ? 1 : 0; plan[PL_KF] = kf;
+        plan[PL_NOUT] = nout > 0 ? nout : 0; plan[PL_MEL_END] = mel_end;
+        for (int i = 0; i < 4; ++i) plan[PL_END + i] = fin ? T1 : J + kf - ST_OFF[i];
+        plan[PL_END + 4] = sc_end;
+        ws.fe_len[s] = CARRY + n;
+        ws.fe_frames[s] = mel_end - (2 * J - 1);
+        io.n_out[s] = nout > 0 ? nout : 0;
+    }
+    const int16_t *carry = reinterpret_cast<const int16_t *>(rin + R_PCM);
+    const int16_t *src = io.samples + (long long)s * io.sample_stride;
+    int16_t *row = ws.pcm + (size_t)s * ws.pcm_w;
+    for (int e = tid; e < ws.pcm_w; e += 256) row[e] = e < CARRY ? (rs ? (int16_t)0 : carry[e]) : (e - CARRY < n ? src[e - CARRY] : (int16_t)0);
+    float *mel = ws.rows[0] + (size_t)s * ws.w[0] * 80;
+    for (int e = tid; e < ST_HIST[0] * 80; e += 256) mel[e] = rs ? 0.f : __uint_as_float(rin[R_MEL + e]);
+#pragma unroll
+    for (int i = 1; i < 5; ++i) {
+        const int H = ST_HIST[i], Cn = ST_CH[i - 1], W = ws.w[i];
+        float *dst = ws.rows[i] + (size_t)s * Cn * W;
+        for (int e = tid; e < Cn * H; e += 256) {
+            const int ch = e / H, col = e - ch * H;
+            dst[(size_t)ch * W + col] = rs ? 0.f : __uint_as_float(rin[ST_REC[i] + e]);
+        }
+    }
+}
+
+// One workgroup per stream, behind the tick's launches: the record a stream that ran leaves -- all zeros after its final tick, else the
+// last frames of every row buffer (a frame below 0 is padding and stays zero), the last 417 samples and the two counters.
+__global__ __launch_bounds__(256) void stream_close_kernel(StreamIO io, StreamWs ws) {
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int *plan = ws.plan + (size_t)s * PLAN_WORDS;
+    if (plan[PL_ACTIVE] != 1) return;
+    const unsigned *rin = io.state_in + (size_t)s * R_WORDS;
+    unsigned *rout = io.state_out + (size_t)s * R_WORDS;
+    if (plan[PL_FINAL]) {
+        for (int e = tid; e < R_WORDS; e += 256) rout[e] = 0u;
+        return;
+    }
+    const int J = plan[PL_J], kf = plan[PL_KF], n = plan[PL_N];
+    const bool rs = io.reset && io.reset[s];
+    const float *mel = ws.rows[0] + (size_t)s * ws.w[0] * 80;
+    for (int e = tid; e < ST_HIST[0] * 80; e += 256) {
+        const int r = e / 80 + 2 * kf;                          // row r of the buffer = log-mel frame 2J - 11 + r
+        rout[R_MEL + e] = 2 * J - 11 + r >= 0 ? __float_as_uint(mel[(size_t)r * 80 + (e % 80)]) : 0u;
+    }
+#pragma unroll
+    for (int i = 1; i < 5; ++i) {
+        const int H = ST_HIST[i], Cn = ST_CH[i - 1], W = ws.w[i], g0 = J - ST_OFF[i - 1] - H;
+        const float *src = ws.rows[i] + (size_t)s * Cn * W;
+        for (int e = tid; e < Cn * H; e += 256) {
+            const int ch = e / H, col = e - ch * H + kf;
+            rout[ST_REC[i] + e] = g0 + col >= 0 ? __float_as_uint(src[(size_t)ch * W + col]) : 0u;
+        }
+    }
+    const int16_t *row = ws.pcm + (size_t)s * ws.pcm_w;
+    for (int e = tid; e < (R_FED - R_PCM); e += 256) {           // two samples per word
+        const int a = 2 * e, b = 2 * e + 1;
+        const unsigned lo = a < CARRY ? (unsigned short)row[n + a] : 0u, hi = b < CARRY ? (unsigned short)row[n + b] : 0u;
+        rout[R_PCM + e] = lo | (hi << 16);
+    }
+    if (tid == 0) {
+        const long long fed0 = rs ? 0 : *reinterpret_cast<const long long *>(rin + R_FED);
+        const long long emit0 = rs ? 0 : *reinterpret_cast<const long long *>(rin + R_EMIT);
+        *reinterpret_cast<long long *>(rout + R_FED) = fed0 + n;
+        *reinterpret_cast<long long *>(rout + R_EMIT) = emit0 + plan[PL_NOUT];
+    }
 }
 
 }  // namespace marblenet
@@ -1064,6 +1298,131 @@ extern "C" int vadx_marblenet_tail_ragged(const float *dw, const float *pw, cons
         hipLaunchKernelGGL((marblenet_tail_kernel<0, true>), dim3((unsigned)r.n_tiles), dim3(THREADS), lds, static_cast<hipStream_t>(stream),
                            c, dw, pw, pb, w6, b6, dec_w, dec_b, x, score0, score1, 0, flag, r);
     }
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+// ---- live streams: one tick = open, the stream front-end, the five encoder launches on the streams' row buffers, close
+extern "C" int vadx_marblenet_stream_max_frames(void) { return K_MAX; }
+extern "C" int vadx_marblenet_stream_cap(int k) { return k >= 1 && k <= K_MAX ? k + LOOKAHEAD : 0; }
+extern "C" size_t vadx_marblenet_stream_state_bytes(int streams) { return streams >= 1 ? (size_t)streams * R_WORDS * 4 : 0; }
+extern "C" size_t vadx_marblenet_stream_workspace_bytes(int streams, int k) {
+    if (streams < 1 || k < 1 || k > K_MAX) return 0;
+    StreamWs ws;
+    return stream_ws_layout(streams, k, &ws, nullptr);
+}
+
+extern "C" int vadx_marblenet_stream_tick(const vadx_frontend_cfg *fe, const float *fe_packed, const int32_t *mel_kb_host,
+                                          const vadx_marblenet_stream_weights *w, const int16_t *samples, int64_t sample_stride,
+                                          const int32_t *n_samples, const uint8_t *reset, const uint8_t *final, int streams, int k,
+                                          const void *state_in, void *state_out, float *score0, float *score1, int32_t *n_out,
+                                          void *workspace, size_t workspace_bytes, void *stream, const vadx_marblenet_cfg *cfg) {
+    static const char who[] = "vadx_marblenet_stream_tick";
+    VADX_REQUIRE(fe && fe_packed && mel_kb_host && w && samples && n_samples && state_in && state_out && score0 && score1 && n_out && workspace,
+                 "%s: NULL argument", who);
+    VADX_REQUIRE(w->p_dw && w->p_pw && w->p_pb && w->t_dw && w->t_pw && w->t_pb && w->t_w6 && w->t_b6 && w->dec_w && w->dec_b, "%s: NULL weight", who);
+    for (int i = 0; i < 3; ++i)
+        VADX_REQUIRE(w->b_dw0[i] && w->b_pw0[i] && w->b_b0[i] && w->b_dw1[i] && w->b_pw1[i] && w->b_b1[i] && w->b_rw[i] && w->b_rb[i],
+                     "%s: NULL weight of block %d", who, i + 2);
+    VADX_REQUIRE(streams >= 1, "%s: streams=%d must be at least 1", who, streams);
+    VADX_REQUIRE(k >= 1 && k <= K_MAX, "%s: k=%d frames per tick is outside [1, %d]", who, k, K_MAX);
+    VADX_REQUIRE(sample_stride >= (int64_t)k * HOP2, "%s: sample_stride=%lld is shorter than a row of k * 320 = %d samples", who,
+                 (long long)sample_stride, k * HOP2);
+    VADX_REQUIRE(state_in != state_out, "%s: state_out must be a second record (state_in is never written)", who);
+    int ar;
+    unsigned *flag;
+    if (int rc = ragged_arith(who, cfg, &ar, &flag)) return rc;
+    // the front-end's own refusals, by name and before any HIP call (vadx_frontend_logmel_stream repeats them)
+    VADX_REQUIRE(fe->fold == VADX_FE_KIND_SPLIT_H2 || fe->fold == VADX_FE_KIND_SPLIT_B3, "%s: DFT product kind %d is not built for streams "
+                 "(VADX_FE_KIND_SPLIT_H2 = %d or VADX_FE_KIND_SPLIT_B3 = %d)", who, fe->fold, (int)VADX_FE_KIND_SPLIT_H2, (int)VADX_FE_KIND_SPLIT_B3);
+    VADX_REQUIRE(fe->prep == 1 && fe->hop == 160 && fe->in_window_len <= 0 && fe->n_mels == 80 && fe->center_pad == 256,
+                 "%s: front-end prep %d, hop %d, in_window_len %d, n_mels %d, centre pad %d is not the MarbleNet preset at 16 kHz (prep 1, hop 160, "
+                 "no in-graph resampling, 80 mels, centre pad 256)", who, fe->prep, fe->hop, fe->in_window_len, fe->n_mels, fe->center_pad);
+    StreamWs ws;
+    const size_t need = stream_ws_layout(streams, k, &ws, static_cast<char *>(workspace));
+    VADX_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, vadx_marblenet_stream_workspace_bytes(%d, %d) = %zu", who, workspace_bytes,
+                 streams, k, need);
+    VADX_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(state_in) & 15) == 0 &&
+                 (reinterpret_cast<uintptr_t>(state_out) & 15) == 0, "%s: workspace and records must be 16-byte aligned", who);
+    const int cap = k + LOOKAHEAD;
+    int tiles[5];
+    for (int i = 0; i < 5; ++i) tiles[i] = (k + ST_EXTRA[i] + TILE - 1) / TILE;
+    VADX_REQUIRE((long long)streams * tiles[4] < (1LL << 31), "%s: too many tiles", who);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const StreamIO io{samples, (long long)sample_stride, n_samples, reset, final, static_cast<const unsigned *>(state_in),
+                      static_cast<unsigned *>(state_out), score0, score1, n_out, k, cap};
+    hipLaunchKernelGGL(stream_open_kernel, dim3((unsigned)streams), dim3(256), 0, st, io, ws);
+    VADX_HIP_TRY(hipGetLastError());
+    if (int rc = vadx_frontend_logmel_stream(fe, fe_packed, mel_kb_host, ws.pcm, ws.pcm_w, ws.fe_len, ws.fe_frames, streams, 2 * k + 2, ws.rows[0],
+                                             ws.w[0], ST_HIST[0], stream))
+        return rc;
+    auto tables = [&](int stage) {
+        return Stream{ws.plan, stage, ST_OFF[stage], stage ? ST_OFF[stage - 1] : 0, ST_HIST[stage], stage < 4 ? ST_HIST[stage + 1] : 0,
+                      ws.w[stage], stage < 4 ? ws.w[stage + 1] : cap, tiles[stage], streams};
+    };
+    {   // the prologue on the time-major log-mel rows
+        Cfg c;
+        c.cin = 80; c.cout = 128; c.k = 11; c.stride = 2; c.dil = 1; c.has_dw = 1; c.cres = 0; c.relu = 1; c.pad = 5;
+        c.cinp = 80; c.coutp = 128; c.cresp = 0;
+        finish_cfg(&c);
+        size_t lds_bytes = lds_floats(c.cinp, c.coutp, c.cresp, c.in_ld, c.has_dw) * sizeof(float);
+        const Stream r = tables(0);
+        if (ar == vadx::VADX_AR_H2) {
+            VADX_REQUIRE(c.out_alias, "%s: the fp16 x 2 prologue needs its output in the input tile's place", who);
+            lds_bytes += prologue_plane_bytes(c);
+            VADX_DYN_LDS((sepconv_block_kernel<11, 1, 2, 2, 2>), 128 * 1024);
+            hipLaunchKernelGGL((sepconv_block_kernel<11, 1, 2, 2, 2>), dim3((unsigned)(streams * r.tiles)), dim3(THREADS), lds_bytes, st, c, w->p_dw,
+                               w->p_pw, w->p_pb, nullptr, nullptr, ws.rows[0], 0LL, 1LL, 80LL, 0, nullptr, ws.rows[1], 0, 0, flag, r);
+        } else {
+            VADX_DYN_LDS((sepconv_block_kernel<11, 1, 2, 0, 2>), 128 * 1024);
+            hipLaunchKernelGGL((sepconv_block_kernel<11, 1, 2, 0, 2>), dim3((unsigned)(streams * r.tiles)), dim3(THREADS), lds_bytes, st, c, w->p_dw,
+                               w->p_pw, w->p_pb, nullptr, nullptr, ws.rows[0], 0LL, 1LL, 80LL, 0, nullptr, ws.rows[1], 0, 0, flag, r);
+        }
+        VADX_HIP_TRY(hipGetLastError());
+    }
+    for (int i = 0; i < 3; ++i) {
+        const int cin = i == 0 ? 128 : 64, kernel = 13 + 2 * i;
+        const Blk2 c = make_blk2(cin, kernel, 0);                // (T comes from the plan)
+        VADX_REQUIRE(c.cinp * c.in_ld >= c.c1 * A_LD, "%s: the depthwise-1 output does not fit the input region", who);
+        const bool planes = ar == vadx::VADX_AR_H2 && cin == 64;
+        const size_t lds = blk2_lds(c, planes);
+        const Stream r = tables(1 + i);
+#define BLK2_STREAM(KK, AR)                                                                                                        \
+    do {                                                                                                                           \
+        VADX_DYN_LDS((jasper_block2_kernel<KK, AR, 2>), 128 * 1024);                                                               \
+        hipLaunchKernelGGL((jasper_block2_kernel<KK, AR, 2>), dim3((unsigned)(streams * r.tiles)), dim3(THREADS), lds, st, c,      \
+                           w->b_dw0[i], w->b_pw0[i], w->b_b0[i], w->b_dw1[i], w->b_pw1[i], w->b_b1[i], w->b_rw[i], w->b_rb[i],      \
+                           ws.rows[1 + i], ws.rows[2 + i], 0, flag, r);                                                            \
+    } while (0)
+        // the arithmetics of the whole-clip launches: block 2 (128 channels in) splits in the GEMM waves, blocks 3 / 4 read operand planes
+        if (ar != vadx::VADX_AR_H2) {
+            if (i == 0) BLK2_STREAM(13, 0);
+            else if (i == 1) BLK2_STREAM(15, 0);
+            else BLK2_STREAM(17, 0);
+        } else {
+            if (i == 0) BLK2_STREAM(13, 2);
+            else if (i == 1) BLK2_STREAM(15, 3);
+            else BLK2_STREAM(17, 3);
+        }
+#undef BLK2_STREAM
+        VADX_HIP_TRY(hipGetLastError());
+    }
+    {
+        const Tail c = make_tail(0);
+        const size_t lds = tail_lds(c);
+        const Stream r = tables(4);
+        if (ar == vadx::VADX_AR_H2) {
+            VADX_DYN_LDS((marblenet_tail_kernel<2, 2>), 128 * 1024);
+            hipLaunchKernelGGL((marblenet_tail_kernel<2, 2>), dim3((unsigned)(streams * r.tiles)), dim3(THREADS), lds, st, c, w->t_dw, w->t_pw, w->t_pb,
+                               w->t_w6, w->t_b6, w->dec_w, w->dec_b, ws.rows[4], score0, score1, 0, flag, r);
+        } else {
+            VADX_DYN_LDS((marblenet_tail_kernel<0, 2>), 128 * 1024);
+            hipLaunchKernelGGL((marblenet_tail_kernel<0, 2>), dim3((unsigned)(streams * r.tiles)), dim3(THREADS), lds, st, c, w->t_dw, w->t_pw, w->t_pb,
+                               w->t_w6, w->t_b6, w->dec_w, w->dec_b, ws.rows[4], score0, score1, 0, flag, r);
+        }
+        VADX_HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(stream_close_kernel, dim3((unsigned)streams), dim3(256), 0, st, io, ws);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }

@@ -196,6 +196,29 @@ def inference_firered_stream(test_vad_audio="./vad_sample.wav", engine=None, NOR
     return results[0] if not isinstance(test_vad_audio, (list, tuple)) else results
 
 
+def inference_marblenet_stream(test_vad_audio="./vad_sample.wav", engine=None, chunk_frames=16, NORMALIZE_AUDIO=False, SMOOTH_WINDOW_SIZE=3,
+                               SPEAKING_SCORE=0.5, MIN_SPEECH_FRAME=10, MAX_SPEECH_FRAME=1000, MIN_SILENCE_FRAME=10,
+                               MERGE_SILENCE_FRAME=3, EXTEND_SPEECH_FRAME=0, echo=print):
+    """NVIDIA_.../Inference_NVIDIA_MarbleNet_VAD_ONNX.py:130-135, 369-388 (the dynamic-axis call) with every file fed as a LIVE STREAM:
+    the files of a list are the streams of one batch (MarbleNetEngine.stream_detect: all files tick together, `chunk_frames` frames of
+    20 ms per tick, each file with its own final tick) -> [(start_s, end_s)] per file, the segments `inference_marblenet` gives."""
+    from . import marblenet
+    engine = _engine_of(marblenet.MarbleNetEngine, engine)
+    clips = _load(_as_list(test_vad_audio), NORMALIZE_AUDIO)
+    echo("\nRunning the NVIDIA_VAD by ONNX Runtime (streamed).")
+    t0 = time.time()
+    post = (SMOOTH_WINDOW_SIZE, SPEAKING_SCORE, MIN_SPEECH_FRAME, MAX_SPEECH_FRAME, MIN_SILENCE_FRAME, MERGE_SILENCE_FRAME, EXTEND_SPEECH_FRAME)
+    results = engine.stream_detect(list(clips), chunk_frames=chunk_frames, post=post)
+    elapsed = time.time() - t0
+    for seg, c in zip(results, clips):
+        echo(f"\nStream Results:\n  Audio duration: {len(c) / 16000:.3f}s\n  Segments detected: {len(seg)}\n\n  Timestamps in Second:")
+        for a, b in seg:
+            echo(f"    {timestamps.format_time(a)} --> {timestamps.format_time(b)}")
+    # the files tick together as one batch: the wall time is set against the longest of them
+    echo(f"\nStream Process Complete.\n\nTime Cost: {elapsed:.3f} Seconds\nRTF: {elapsed / (max(len(c) for c in clips) / 16000):.4f}")
+    return results[0] if not isinstance(test_vad_audio, (list, tuple)) else results
+
+
 def inference_marblenet(test_vad_audio="./vad_sample.wav", engine=None, save_timestamps_second="./timestamps_second.txt",
                         save_timestamps_indices="./timestamps_indices.txt", NORMALIZE_AUDIO=False, SMOOTH_WINDOW_SIZE=3,
                         SPEAKING_SCORE=0.5, MIN_SPEECH_FRAME=10, MAX_SPEECH_FRAME=1000, MIN_SILENCE_FRAME=10,

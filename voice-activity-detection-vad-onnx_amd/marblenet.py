@@ -334,6 +334,52 @@ class MarbleNetEngine:
             return self.torch.zeros((len(rb), 0), dtype=self.torch.float32, device=self.device), nf, rb.lengths
         return gather_tracks(self.device, s1, T1, 0, valid, rb.win_first, nf), nf, rb.lengths
 
+    def stream_detect(self, clips, chunk_frames=16, post=(3, 0.5, 10, 1000, 10, 3, 0), return_probs=False):
+        """A list of 1-D int16 clips of any lengths, every clip one live stream (MarbleNetStreamBatch): all streams advance `chunk_frames`
+        frames per tick until the longest is done, each with its own final tick; the collected tracks go through the whole-clip
+        VadPostprocessor path of `detect(list)`.  -> per clip [(start_s, end_s)], equal to `detect(clips)` (dynamic-axis mode);
+        return_probs adds (tracks f32 [B, max n_frames], decisions, n_frames), the tracks `detect`'s (bit for bit up to the frames that
+        read `detect`'s tail-tile log-mel, see MarbleNetStreamBatch).  The host knows every stream's sample count, so `stream_counts` says
+        how many frames each tick's rows hold: no tick waits for a read-back, and the device's n_out of all ticks is checked against the
+        counts once, at the end."""
+        t = self.torch
+        clips = [np.ascontiguousarray(np.asarray(c).reshape(-1)) for c in clips]
+        if len(clips) == 0:
+            raise ValueError("stream_detect needs at least one clip")
+        for c in clips:
+            if c.dtype != np.int16:
+                raise ValueError(f"clips must be int16, got {c.dtype}")
+        k = int(chunk_frames)
+        check_stream_step(k, [0], [False])
+        S, row = len(clips), k * STREAM_HOP
+        sb = MarbleNetStreamBatch(self, S)
+        last = np.array([c.size // row for c in clips])              # the tick that is the stream's final one
+        fed = np.zeros(S, dtype=np.int64)
+        parts, counts, n_outs = [[] for _ in range(S)], [], []
+        for i in range(int(last.max()) + 1):
+            host = np.zeros((S, row), dtype=np.int16)
+            n = np.zeros(S, dtype=np.int64)
+            for s, c in enumerate(clips):
+                if i <= last[s]:
+                    piece = c[i * row:(i + 1) * row]
+                    host[s, :piece.size], n[s] = piece, piece.size
+            fin = last == i
+            cnt = stream_counts(fed, n, fin)[2]
+            fed = np.where(fin, 0, fed + n)
+            _, s1, n_out = sb.step(host, n, final=fin)
+            counts.append(cnt); n_outs.append(n_out)
+            for s in np.flatnonzero(cnt).tolist():
+                parts[s].append(s1[s, :cnt[s]])
+        if not np.array_equal(t.stack(n_outs).cpu().numpy(), np.stack(counts)):
+            raise _lib.VadxError("stream_detect: the device emitted other frame counts than stream_counts gives for the samples it was fed")
+        empty = t.zeros((0,), dtype=t.float32, device=self.device)
+        rows = [t.cat(p) if p else empty for p in parts]
+        nf = np.array([int(r.shape[0]) for r in rows], dtype=np.int32)
+        track = self._pad_rows(rows, t.float32)
+        pp = _vadpost.VadPostprocessor(*post, frame_shift_s=OUTPUT_FRAME_SHIFT_S, frame_length_s=None, device=self.device)
+        out, dec = track_segments(pp, track, nf, [c.size / SAMPLE_RATE for c in clips])
+        return (out, track, dec, nf) if return_probs else out
+
     def _pad_rows(self, rows, dtype):
         """1-D device rows of different lengths -> one zero-filled matrix [B, max len]."""
         t = self.torch
@@ -341,6 +387,207 @@ class MarbleNetEngine:
         for b, r in enumerate(rows):
             m[b, :r.shape[0]] = r.to(self.device)
         return m
+
+
+# ---- live streams (include/vadx.h: vadx_marblenet_stream_tick)
+STREAM_HOP = 320                  # samples per score frame
+STREAM_LOOKAHEAD = 73             # score frames a stream stands behind the audio it has been fed (70 encoder frames + the prologue's 3)
+STREAM_MAX_FRAMES = 256           # frames per tick the entry point takes (vadx_marblenet_stream_max_frames)
+STREAM_RECORD_WORDS, STREAM_FED_WORD, STREAM_EMITTED_WORD = 11512, 11508, 11510      # per stream, in 4-byte words (the counters are int64)
+_STAGE_BEHIND = (3, 15, 29, 45, 73)      # prologue, blocks 2 - 4, scores: frames behind J = samples fed / 320
+
+
+def stream_counts(fed_before, n_samples, final):
+    """What one tick produces for each stream, from its sample counts alone (numpy, no GPU): -> (mel, enc, score) int64 arrays, the
+    log-mel frames, encoder frames (the prologue's output) and score frames that become final in this tick.  fed_before: samples fed
+    since the stream's reset (a multiple of 320); n_samples: this tick's; final: the stream's last tick.  After N = 320 J samples and no
+    final tick log-mel frames 0 .. 2J - 2 are complete (frame i reads samples up to 160 i + 255), the prologue has written frames
+    < J - 3 (frame p reads log-mel frames up to 2p + 5) and max(0, J - 73) scores are out; a final tick at n samples in all completes
+    n // 160 + 1 log-mel frames, n // 320 + 1 encoder frames and brings the scores to n // 320 (the last encoder frame is dropped, as
+    the session's signal_len - 1 drops it)."""
+    fed = np.asarray(fed_before, dtype=np.int64)
+    n = np.asarray(n_samples, dtype=np.int64)
+    fin = np.asarray(final, dtype=bool)
+    fed, n, fin = np.broadcast_arrays(fed, n, fin)
+    if np.any(fed < 0) or np.any(fed % STREAM_HOP):
+        raise ValueError("fed_before must be a non-negative multiple of 320 (a stream is fed whole frames until its final tick)")
+    if np.any(n < 0) or np.any((n % STREAM_HOP != 0) & ~fin):
+        raise ValueError("n_samples must be a non-negative multiple of 320 on a stream that is not final")
+    J0, J1, total = fed // STREAM_HOP, (fed + n) // STREAM_HOP, fed + n
+    pos = lambda J, behind: np.maximum(J - behind, 0)           # noqa: E731
+    mel0, enc0, sc0 = np.maximum(2 * J0 - 1, 0), pos(J0, _STAGE_BEHIND[0]), pos(J0, STREAM_LOOKAHEAD)
+    mel1 = np.where(fin, total // 160 + 1, np.maximum(2 * J1 - 1, 0))
+    enc1 = np.where(fin, total // STREAM_HOP + 1, pos(J1, _STAGE_BEHIND[0]))
+    sc1 = np.where(fin, total // STREAM_HOP, pos(J1, STREAM_LOOKAHEAD))
+    return mel1 - mel0, enc1 - enc0, sc1 - sc0
+
+
+def check_stream_step(k, n_samples, final):
+    """The per-tick arguments MarbleNetStreamBatch.step takes, checked on the host before anything is uploaded: k frames per row,
+    n_samples int [S], final bool [S].  Raises ValueError naming the offending value."""
+    k = int(k)
+    if not 1 <= k <= STREAM_MAX_FRAMES:
+        raise ValueError(f"k={k} frames per tick is outside [1, {STREAM_MAX_FRAMES}] (vadx_marblenet_stream_max_frames)")
+    n = np.asarray(n_samples, dtype=np.int64).reshape(-1)
+    fin = np.asarray(final, dtype=bool).reshape(-1)
+    if n.shape != fin.shape:
+        raise ValueError(f"n_samples {n.shape} and final {fin.shape} must have one entry per stream")
+    if np.any(n < 0) or np.any(n > k * STREAM_HOP):
+        bad = int(n[(n < 0) | (n > k * STREAM_HOP)][0])
+        raise ValueError(f"n_samples={bad} is outside [0, k * 320 = {k * STREAM_HOP}]")
+    odd = (n % STREAM_HOP != 0) & ~fin
+    if np.any(odd):
+        raise ValueError(f"n_samples={int(n[odd][0])} is not a multiple of 320 on a stream that is not final: a stream is fed whole "
+                         "score frames until its final tick")
+
+
+class MarbleNetStreamBatch:
+    """`streams` live Frame-VAD MarbleNet streams on the device (vadx_marblenet_stream_tick).  A stream is the audio of one virtual clip
+    arriving in pieces; every `step` feeds each stream up to k frames (k * 320 samples) and returns the score frames that became final:
+    a stream stands 73 frames (1.46 s) behind its audio, and its last tick (`final`) emits the remaining look-ahead against the zero
+    padding behind the clip's last frame.  The concatenated scores are what `MarbleNetEngine.run(clip[None])` gives for the whole
+    clip (n // 320 frames): bit for bit wherever a frame reads none of the log-mel frames `run` computes in its front-end's tail tile
+    (the clip's last F mod 64 <= 48 frames, F = n // 160 + 1), one float32 ulp of the log-mel apart behind that (DESIGN.md 4s).  Per stream only the left context of every launch boundary is carried, in a device record (two,
+    ping-ponged; all-zero bytes = a fresh stream).  On "h2" every tick reads the range flag and, when it is raised, is recomputed on
+    float32 from the same record; that counts once in engine.range_fallbacks."""
+
+    def __init__(self, engine, streams):
+        if int(getattr(engine, "in_sample_rate", SAMPLE_RATE)) != SAMPLE_RATE:
+            raise ValueError(f"MarbleNetStreamBatch has no in-graph resampling: in_sample_rate is {engine.in_sample_rate}, not {SAMPLE_RATE}")
+        if not getattr(engine, "fused", False):
+            raise ValueError("MarbleNetStreamBatch is built for the published MarbleNet 3x2x64 layout (the fused kernels); this engine was "
+                             "constructed with another `blocks` layout")
+        self.engine, self.streams = engine, int(streams)
+        if self.streams < 1:
+            raise ValueError(f"streams={streams} must be at least 1")
+        t, lib = engine.torch, _lib.lib()
+        nb = lib.vadx_marblenet_stream_state_bytes(self.streams)
+        if nb != self.streams * STREAM_RECORD_WORDS * 4:
+            raise _lib.VadxError(f"vadx_marblenet_stream_state_bytes = {nb}: not the record this binding was written for")
+        self._rec = [t.zeros(nb, dtype=t.uint8, device=engine.device) for _ in range(2)]
+        self._cur = 0
+        self._pending = np.zeros(self.streams, dtype=bool)
+        self._ws = {}                  # k -> workspace (uint8)
+        self._weights = {}             # mode -> vadx_marblenet_stream_weights
+        self._fe = engine.frontend_ragged()
+        if self._fe.fold not in self._fe.RAGGED_KINDS:
+            raise ValueError(f"the stream front-end is built for the split-product kinds {self._fe.RAGGED_KINDS} (KIND_SPLIT_H2 / KIND_SPLIT_B3); "
+                             f"this engine's Frontend was packed as kind {self._fe.fold} (VADX_FRONTEND_FOLD)")
+
+    @property
+    def record(self):
+        """The current device record (uint8, streams * 46 048 bytes; layout in include/vadx.h)."""
+        return self._rec[self._cur]
+
+    def stream_bytes(self, s, record=None):
+        """Every byte of `record` (default: the current one) that belongs to stream s, as one uint8 tensor."""
+        r = self.record if record is None else record
+        return r[s * STREAM_RECORD_WORDS * 4:(s + 1) * STREAM_RECORD_WORDS * 4]
+
+    def _counter(self, word):
+        r = self.record.view(self.engine.torch.int32).view(self.streams, STREAM_RECORD_WORDS)
+        return r[:, word:word + 2].contiguous().view(self.engine.torch.int64)[:, 0].cpu().numpy()
+
+    @property
+    def fed(self):
+        """int64 [S] (host): samples each stream has been fed since its reset, read from the device record."""
+        return self._counter(STREAM_FED_WORD)
+
+    @property
+    def emitted(self):
+        """int64 [S] (host): score frames each stream has emitted since its reset, read from the device record."""
+        return self._counter(STREAM_EMITTED_WORD)
+
+    def reset_states(self, streams=None):
+        """None = every stream; else stream indices or a bool mask [S].  Applies at the next tick, before that tick's audio."""
+        if streams is None:
+            self._pending[:] = True
+            return
+        idx = np.asarray(streams.cpu() if hasattr(streams, "cpu") else streams)
+        if idx.dtype == bool:
+            self._pending |= self._mask(idx, "reset mask")
+        else:
+            self._pending[idx.astype(np.int64).reshape(-1)] = True
+
+    def _mask(self, m, name):
+        a = np.asarray(m.cpu() if hasattr(m, "cpu") else m).astype(bool).reshape(-1)
+        if a.shape != (self.streams,):
+            raise ValueError(f"{name} must have shape ({self.streams},), got {a.shape}")
+        return a
+
+    def _weights_for(self, mode):
+        if mode not in self._weights:
+            st, sfx = self.engine.stages, "_h" if mode == "h2" else ""
+            p = lambda a: a.data_ptr()        # noqa: E731
+            w = _lib.MarbleNetStreamWeights()
+            w.p_dw, w.p_pw, w.p_pb = p(st[0]["dw"]), p(st[0]["pw" + sfx]), p(st[0]["pb"])
+            for i, k in enumerate((1, 3, 5)):
+                a, b = st[k], st[k + 1]
+                w.b_dw0[i], w.b_pw0[i], w.b_b0[i] = p(a["dw"]), p(a["pw" + sfx]), p(a["pb"])
+                w.b_dw1[i], w.b_pw1[i], w.b_b1[i] = p(b["dw"]), p(b["pw" + sfx]), p(b["pb"])
+                w.b_rw[i], w.b_rb[i] = p(b["rw" + sfx]), p(b["rb"])
+            w.t_dw, w.t_pw, w.t_pb = p(st[7]["dw"]), p(st[7]["pw" + sfx]), p(st[7]["pb"])
+            w.t_w6, w.t_b6 = p(st[8]["pw" + sfx]), p(st[8]["pb"])
+            w.dec_w, w.dec_b = p(self.engine.dec_w), p(self.engine.dec_b)
+            self._weights[mode] = w
+        return self._weights[mode]
+
+    def _workspace(self, k):
+        if k not in self._ws:
+            t = self.engine.torch
+            nb = _lib.lib().vadx_marblenet_stream_workspace_bytes(self.streams, k)
+            if not nb:
+                raise ValueError(f"k={k} frames per tick is outside [1, {STREAM_MAX_FRAMES}] (vadx_marblenet_stream_max_frames)")
+            self._ws = {k: t.empty(nb, dtype=t.uint8, device=self.engine.device)}        # one tick size at a time: a stream keeps nothing in it
+        return self._ws[k]
+
+    def tick_raw(self, x, n_dev, reset_dev, final_dev, k, src, dst, s0, s1, n_out, mode):
+        """One vadx_marblenet_stream_tick on device tensors, no host-side checks (the tests reach the device-side guards through it)."""
+        eng, t = self.engine, self.engine.torch
+        ws = self._workspace(k)
+        mc = _lib.MarbleNetCfg(_lib.ARITH[mode], 0, eng._flag.data_ptr())
+        with t.cuda.device(eng.device):
+            _lib.check(_lib.lib().vadx_marblenet_stream_tick(
+                C.byref(self._fe.cfg), self._fe.packed.data_ptr(), self._fe.mel_kb.ctypes.data, C.byref(self._weights_for(mode)),
+                x.data_ptr(), int(x.stride(0)) if x.shape[0] > 1 else int(x.shape[1]), n_dev.data_ptr(),
+                None if reset_dev is None else reset_dev.data_ptr(), None if final_dev is None else final_dev.data_ptr(), self.streams, k,
+                src.data_ptr(), dst.data_ptr(), s0.data_ptr(), s1.data_ptr(), n_out.data_ptr(), ws.data_ptr(), int(ws.numel()),
+                _lib.stream_ptr(), C.byref(mc)))
+
+    def step(self, samples_i16, n_samples=None, reset=None, final=None):
+        """samples_i16 int16 [S, k * 320] (host or device): each row holds that stream's next samples; n_samples int [S] (None: every
+        stream gets the full row): 0 = no audio this tick, a positive multiple of 320 on a stream that goes on, anything in 0 .. k * 320
+        on a `final` stream.  reset / final: bool [S] or None; reset applies before the audio, final emits the stream's remaining
+        look-ahead and leaves it reset.  -> (score_silence, score_active f32 [S, k + 73], n_out int32 [S]) on the device: row s holds
+        n_out[s] new score frames, NaN behind them.  A stream with no samples that is not final keeps its record bit for bit."""
+        eng, t, S = self.engine, self.engine.torch, self.streams
+        x = samples_i16 if t.is_tensor(samples_i16) else t.from_numpy(np.ascontiguousarray(samples_i16))
+        if x.dtype != t.int16:
+            raise ValueError(f"samples must be int16, got {x.dtype}")
+        if x.dim() != 2 or x.shape[0] != S or x.shape[1] % STREAM_HOP or x.shape[1] == 0:
+            raise ValueError(f"samples must be [{S}, k * 320], got {tuple(x.shape)}")
+        k = x.shape[1] // STREAM_HOP
+        fin = np.zeros(S, dtype=bool) if final is None else self._mask(final, "final")
+        n = np.full(S, k * STREAM_HOP, dtype=np.int64) if n_samples is None else \
+            np.asarray(n_samples.cpu() if hasattr(n_samples, "cpu") else n_samples, dtype=np.int64).reshape(-1)
+        if n.shape != (S,):
+            raise ValueError(f"n_samples must have shape ({S},), got {n.shape}")
+        check_stream_step(k, n, fin)
+        req = self._pending | self._mask(reset, "reset") if reset is not None else self._pending.copy()
+        x = x.to(eng.device).contiguous()
+        n_dev = t.from_numpy(n.astype(np.int32)).to(eng.device)
+        reset_dev = t.from_numpy(req.astype(np.uint8)).to(eng.device) if req.any() else None
+        final_dev = t.from_numpy(fin.astype(np.uint8)).to(eng.device) if fin.any() else None
+        cap = k + STREAM_LOOKAHEAD                                    # the most stream_counts gives a tick of k frames: a final tick's whole look-ahead
+        s0 = t.empty((S, cap), dtype=t.float32, device=eng.device)
+        s1 = t.empty((S, cap), dtype=t.float32, device=eng.device)
+        n_out = t.empty((S,), dtype=t.int32, device=eng.device)
+        src, dst = self._rec[self._cur], self._rec[1 - self._cur]
+        _lib.range_guarded(eng, eng.mode(), lambda m: self.tick_raw(x, n_dev, reset_dev, final_dev, k, src, dst, s0, s1, n_out, m),
+                           lambda: _lib.take_flag(eng._flag), "f32")
+        self._cur = 1 - self._cur
+        self._pending[:] = False
+        return s0, s1, n_out
 
 
 class MarbleNetSession(Session):
