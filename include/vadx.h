@@ -57,7 +57,8 @@ extern "C" {
  *     vadx_fsmn_window_stats_long, vadx_fsmn_run_long, vadx_fsmn_clips_long; then DFSMN over ragged batches and live streams:
  *     vadx_windows_gather_any, vadx_dfsmn_vote_ragged, vadx_dfsmn_stream_state_bytes, vadx_dfsmn_stream_windows, vadx_dfsmn_stream_vote; then
  *     MarbleNet over live streams: vadx_marblenet_stream_weights, vadx_marblenet_stream_max_frames, vadx_marblenet_stream_cap,
- *     vadx_marblenet_stream_state_bytes, vadx_marblenet_stream_workspace_bytes, vadx_marblenet_stream_tick, vadx_frontend_logmel_stream.
+ *     vadx_marblenet_stream_state_bytes, vadx_marblenet_stream_workspace_bytes, vadx_marblenet_stream_tick, vadx_frontend_logmel_stream; then
+ *     cutting the speech out on the device: vadx_chunks_plan_bytes, vadx_chunks_plan, vadx_chunks_copy.
  *     A caller that needs them checks for the symbols (dlsym), not for a number. */
 #define VADX_ABI_VERSION 10
 
@@ -1060,6 +1061,54 @@ int vadx_dfsmn_stream_windows(const int16_t *near, const int16_t *far, int64_t r
 int vadx_dfsmn_stream_vote(const float *vad, int streams, int n_slots, int windows, int frames, int look_backward, int channels,
                            double speaking_score, double silence_score, const int32_t *slot, const uint8_t *reset,
                            const void *state_in, void *state_out, uint8_t *flags, uint8_t *tail, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Chunks: cut the speech out of a resident batch (or drop it), every clip in one launch sequence -- the batched form of the reference's
+ * collect_chunks / drop_chunks (Silero/modeling_modified/utils_vad.py:588-631 / 634-682).  Input is the table vadx_silero_segments
+ * writes (or any table of that shape): segments int64 [batch][cap][2] = (start, end) in elements of the clip, counts int32 [batch].
+ *
+ * A PIECE is a half-open source interval of one clip, resolved by exactly Python's slice rule (what `wav[start:end]` does there): an
+ * index i < 0 becomes i + len, it is then clamped to [0, len], and lo >= hi is empty.  Rows may overlap, be unsorted, reversed or out
+ * of range; they give what the reference's slicing gives (overlaps duplicate samples in COLLECT, give empty pieces in DROP).
+ *   VADX_CHUNKS_COLLECT  (utils_vad.py:588-631)  n = counts[b] pieces:  piece k = [start_k, end_k)
+ *   VADX_CHUNKS_DROP     (utils_vad.py:634-682)  n + 1 pieces:          piece k = [cur_k, start_k), cur_0 = 0, cur_k = end_{k-1}; the last
+ *                                                                       piece is [cur_n, len)
+ * The output is a PACKED vector: clip after clip, each clip's start rounded up to `align` elements (align = 8 int16 gives the 16-byte
+ * clip starts of the ragged batches above), the filler between clips -- and after the last one, up to the total -- written as zeros.
+ *
+ * The PLAN record (device memory, vadx_chunks_plan_bytes(batch, cap) bytes, 16-byte aligned; byte offsets):
+ *   0    int64 total                      = clip_dst[batch]: at a fixed offset, so that a host reads 8 bytes and knows what to allocate
+ *   8    int32 status                     VADX_CHUNKS_ST_* bits (vadx_chunks_plan resets the word, vadx_chunks_copy only adds bits); 12: int32 0
+ *   16   int64 clip_dst  [batch+1]        exclusive prefix of the clips' output lengths, each rounded up to `align`
+ *   then int64 piece_dst [batch][cap+2]   exclusive prefix of the piece lengths inside the clip; entry n_pieces -- and every later entry --
+ *                                         is the clip's output length
+ *   then int64 piece_src [batch][cap+1][2]  the resolved intervals (lo, hi), hi >= lo; (0, 0) beyond n_pieces
+ *   then int32 n_pieces  [batch]
+ * A clip with counts[b] < 0, counts[b] > cap or clip_len[b] < 0 is a BAD clip: n_pieces = -1, output length 0, VADX_CHUNKS_ST_BAD_CLIP
+ * set; its table rows are never read and it copies nothing.  All offsets are 64-bit; batch may be 2^20 and more. */
+#define VADX_CHUNKS_COLLECT 0   /* utils_vad.py:588-631 */
+#define VADX_CHUNKS_DROP    1   /* utils_vad.py:634-682 */
+#define VADX_CHUNKS_ST_BAD_CLIP  1   /* vadx_chunks_plan: some clip's count or length was refused */
+#define VADX_CHUNKS_ST_OVERFLOW  2   /* vadx_chunks_copy: total > dst_elems -- NOTHING was written */
+#define VADX_CHUNKS_ST_SRC_RANGE 4   /* vadx_chunks_copy: a piece lay outside [0, src_elems) (clip_src / clip_len do not describe src); those
+                                        elements were written as zeros, nothing outside src was read */
+/* Bytes of the plan record of (batch, cap) that vadx_chunks_plan writes for collect_chunks / drop_chunks (utils_vad.py:588-631 / 634-682);
+ * 0 when either is < 1. */
+size_t vadx_chunks_plan_bytes(int batch, int cap);
+/* The plan of collect_chunks (utils_vad.py:588-631) / drop_chunks (utils_vad.py:634-682) for every clip: two launches on `stream`, no
+ * synchronisation.  clip_len int64 [batch] = every clip's length in elements; align: a power of two in [1, 4096].  VADX_EINVAL (before any
+ * HIP call) for a NULL pointer, batch / cap < 1, another mode, another align, a misaligned pointer, plan_bytes < vadx_chunks_plan_bytes. */
+int vadx_chunks_plan(const int64_t *segments, const int32_t *counts, const int64_t *clip_len, int batch, int cap, int mode, int align,
+                     void *plan, size_t plan_bytes, void *stream);
+/* The copy of collect_chunks / drop_chunks (utils_vad.py:588-631 / 634-682: the slices and the torch.cat) for every clip: fills
+ * dst[0, total) from src by the plan; one launch over 16 KB tiles of the DESTINATION.  elem_bytes 2 (int16 PCM) or 4 (float32); a pure
+ * copy.  Clip b's elements start at src[clip_src[b]] (int64 element offsets: b * N for a rectangle [batch][N], the clip offsets of a
+ * packed ragged vector otherwise).  src and dst 16-byte aligned, holding src_elems / dst_elems elements: no byte outside
+ * [src, src + src_elems) is read, none outside [dst, dst + min(total, dst_elems)) written.  total > dst_elems sets
+ * VADX_CHUNKS_ST_OVERFLOW and writes nothing.  VADX_EINVAL (before any HIP call) for a NULL pointer, batch / cap < 1, elem_bytes not 2 or 4,
+ * a negative element count, src / dst not 16-byte aligned, plan_bytes < vadx_chunks_plan_bytes, ceil(dst_elems / tile) >= 2^31. */
+int vadx_chunks_copy(const void *src, int64_t src_elems, const int64_t *clip_src, int elem_bytes, void *plan, size_t plan_bytes, int batch, int cap,
+                     void *dst, int64_t dst_elems, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Test hooks (used by tests/ only)

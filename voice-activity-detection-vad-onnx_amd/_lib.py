@@ -266,6 +266,9 @@ SIGNATURES = {
     "vadx_frontend_logmel_ex": (_I, [C.POINTER(FrontendCfg), _P, _P, _P, _L, _L, _I, _I, _P, _P, _I, _I, _P, _P]),
     "vadx_frontend_stft_ft": (_I, [C.POINTER(FrontendCfg), _P, _P, _L, _L, _I, _I, _P, _P, _I, _I, _P]),
     "vadx_dfsmn_mask_net": (_I, [C.POINTER(DfsmnMaskWeights), _P, _I, _I, _P, _P]),
+    "vadx_chunks_plan_bytes": (_Z, [_I, _I]),
+    "vadx_chunks_plan": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "vadx_chunks_copy": (_I, [_P, _L, _P, _I, _P, _Z, _I, _I, _P, _L, _P]),
 }
 
 _lib = None

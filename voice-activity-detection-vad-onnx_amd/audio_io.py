@@ -86,6 +86,18 @@ def load_wav(path, sample_rate=16000, channels=1):
     return np.ascontiguousarray(x, dtype=np.int16)
 
 
+def save_wav(path, samples, sample_rate=16000):
+    """int16 mono samples [n] -> a 16-bit PCM wav file (what `load_wav` reads back bit for bit at the same rate)."""
+    x = np.asarray(samples)
+    if x.dtype != np.int16 or x.ndim != 1:
+        raise ValueError(f"save_wav takes int16 [n] samples, got {x.dtype} {x.shape}")
+    with wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(sample_rate))
+        w.writeframes(np.ascontiguousarray(x).astype("<i2").tobytes())
+
+
 def read_wav_raw(path):
     """-> (int16 numpy [frames * channels] interleaved, channels, rate) without any conversion (16-bit PCM only)."""
     with wave.open(path, "rb") as w:

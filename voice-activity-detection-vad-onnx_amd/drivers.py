@@ -76,9 +76,11 @@ def _finish(all_ts, sample_rate, save_second, save_indices, single, elapsed, ech
 def inference_silero(test_vad_audio="./vad_sample.wav", model=None, save_timestamps_second="./timestamps_second.txt",
                      save_timestamps_indices="./timestamps_indices.txt", ACTIVATE_THRESHOLD=0.5, FUSION_THRESHOLD=0.3,
                      MIN_SPEECH_DURATION=0.25, MAX_SPEECH_DURATION=20, MIN_SILENCE_DURATION=250, SAMPLE_RATE=16000,
-                     use_fp16=False, echo=print):
+                     use_fp16=False, echo=print, save_speech_audio=None):
     """Silero/Inference_Silero_VAD_ONNX.py:80-120.  use_fp16 (:16, :83): the samples are quantised to float16 and scaled there, as
-    the reference feeds its fp16-optimised model -- I/O-compatible: the network arithmetic here stays float32."""
+    the reference feeds its fp16-optimised model -- I/O-compatible: the network arithmetic here stays float32.
+    save_speech_audio (off by default, not in the reference script): a wav path -- for a list of files `<path>.<k>`, as the timestamp
+    files -- that receives the file's int16 samples inside the written timestamps, cut out on the device (vadx.chunks)."""
     from . import silero
     files = _as_list(test_vad_audio)
     model = silero.load_silero_vad(onnx=True, use_cpu=True, path=model) if (model is None or isinstance(model, (str, dict))) else model
@@ -99,7 +101,27 @@ def inference_silero(test_vad_audio="./vad_sample.wav", model=None, save_timesta
     elapsed = time.time() - t0
     echo(f"\nVAD Complete. Time Cost: {elapsed:.3f} seconds.")
     all_ts = [timestamps.process_timestamps([(d["start"], d["end"]) for d in r], FUSION_THRESHOLD, MIN_SPEECH_DURATION) for r in res]
+    if save_speech_audio is not None:
+        _save_speech(files, all_ts, SAMPLE_RATE, save_speech_audio, not isinstance(test_vad_audio, (list, tuple)), getattr(model, "engine", model).device)
     return _finish(all_ts, SAMPLE_RATE, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
+
+
+def _save_speech(files, all_ts, sample_rate, path, single, device):
+    """Every file's int16 samples inside its (start_s, end_s) timestamps as a wav: the clips go up once as a packed vector, ONE
+    collect_chunks_batch cuts them all, the packed speech comes back once."""
+    import torch
+    from . import chunks
+    pcm = [audio_io.load_wav(f, sample_rate) for f in files]
+    lens = np.asarray([len(c) for c in pcm], dtype=np.int64)
+    starts = np.concatenate([[0], np.cumsum((lens + 7) // 8 * 8)]).astype(np.int64)       # every clip on a 16-byte boundary
+    flat = np.zeros(int(starts[-1]), np.int16)
+    for k, c in enumerate(pcm):
+        flat[starts[k]:starts[k] + len(c)] = c
+    packed, offsets, plan = chunks.collect_chunks_batch(chunks.from_seconds(all_ts, sample_rate), torch.from_numpy(flat).to(device), lengths=lens,
+                                                        clip_offsets=starts[:-1], return_plan=True)
+    packed, offsets, n = packed.cpu().numpy(), offsets.cpu().numpy(), plan.lengths.cpu().numpy()
+    for k in range(len(files)):
+        audio_io.save_wav(path if single else f"{path}.{k}", packed[offsets[k]:offsets[k] + n[k]], sample_rate)
 
 
 def inference_fsmn(test_vad_audio="./vad_sample.wav", engine=None, save_timestamps_second="./timestamps_second.txt",

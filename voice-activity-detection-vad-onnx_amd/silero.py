@@ -19,6 +19,7 @@ import numpy as np
 
 from . import _lib
 from . import weights as _weights
+from .chunks import collect_chunks, drop_chunks            # noqa: F401  (the reference keeps them beside get_speech_timestamps)
 
 CONTEXT_SIZE = 64
 NUM_SAMPLES = 512
@@ -798,19 +799,16 @@ def _finish(segs, counts, lengths, sampling_rate, return_seconds, time_resolutio
     return out
 
 
-def get_speech_timestamps_batch(audio, model, lengths=None, threshold: float = 0.5, sampling_rate: int = 16000,
-                                min_speech_duration_ms: int = 250, max_speech_duration_s: float = float("inf"),
-                                min_silence_duration_ms: int = 100, speech_pad_ms: int = 30,
-                                return_seconds: bool = False, time_resolution: int = 1,
-                                neg_threshold: float = None, min_silence_at_max_speech: int = 98,
-                                use_max_poss_sil_at_max_speech: bool = True, return_probs: bool = False):
-    """Batched get_speech_timestamps: audio f32 [B,N] (equal length, or `lengths` per clip with
-    zero padding beyond) -> list (per clip) of lists of {'start','end'} dicts."""
+def _segments_on_device(audio, model, lengths, sampling_rate, **seg_kw):
+    """The device half of get_speech_timestamps_batch: -> (engine, audio f32 [B, N] as given (before decimation and masking), lens
+    int64 [B] host (in samples of the network's rate), sampling_rate the network runs at, step, probs, segs, counts); probs / segs /
+    counts are None for empty audio."""
     engine = model.engine if isinstance(model, OnnxWrapper) else model
     t = engine.torch
     audio = engine._dev_f32(audio)
     if audio.dim() == 1:
         audio = audio.unsqueeze(0)
+    given = audio
     step = 1
     if sampling_rate > 16000 and sampling_rate % 16000 == 0:
         step = sampling_rate // 16000
@@ -824,8 +822,7 @@ def get_speech_timestamps_batch(audio, model, lengths=None, threshold: float = 0
                          "8 kHz weights); window probabilities from elsewhere can be segmented with segments_from_probs(..., sampling_rate=8000)")
     B, N = audio.shape
     if N == 0:           # empty audio: the reference's chunk loop never runs and it returns [] (utils_vad.py:330-344)
-        res = [[] for _ in range(B)]
-        return (res, t.empty((B, 0), dtype=t.float32, device=engine.device)) if return_probs else res
+        return engine, given, np.zeros((B,), np.int64), sampling_rate, step, None, None, None
     if lengths is None:
         lens = np.full((B,), N, dtype=np.int64)
     else:
@@ -838,14 +835,49 @@ def get_speech_timestamps_batch(audio, model, lengths=None, threshold: float = 0
             mask = t.arange(N, device=engine.device).unsqueeze(0) < t.as_tensor(lens, device=engine.device).unsqueeze(1)
             audio = audio * mask
     probs = engine.clips(audio, n_samples=int(lens.max()), sampling_rate=sampling_rate)
-    segs, counts = engine.segments(probs, lens, threshold=threshold, sampling_rate=sampling_rate,
-                                   min_speech_duration_ms=min_speech_duration_ms,
-                                   max_speech_duration_s=max_speech_duration_s,
-                                   min_silence_duration_ms=min_silence_duration_ms, speech_pad_ms=speech_pad_ms,
-                                   neg_threshold=neg_threshold, min_silence_at_max_speech=min_silence_at_max_speech,
-                                   use_max_poss_sil_at_max_speech=use_max_poss_sil_at_max_speech)
+    segs, counts = engine.segments(probs, lens, sampling_rate=sampling_rate, **seg_kw)
+    return engine, given, lens, sampling_rate, step, probs, segs, counts
+
+
+def get_speech_timestamps_batch(audio, model, lengths=None, threshold: float = 0.5, sampling_rate: int = 16000,
+                                min_speech_duration_ms: int = 250, max_speech_duration_s: float = float("inf"),
+                                min_silence_duration_ms: int = 100, speech_pad_ms: int = 30,
+                                return_seconds: bool = False, time_resolution: int = 1,
+                                neg_threshold: float = None, min_silence_at_max_speech: int = 98,
+                                use_max_poss_sil_at_max_speech: bool = True, return_probs: bool = False):
+    """Batched get_speech_timestamps: audio f32 [B,N] (equal length, or `lengths` per clip with
+    zero padding beyond) -> list (per clip) of lists of {'start','end'} dicts."""
+    engine, given, lens, sampling_rate, step, probs, segs, counts = _segments_on_device(
+        audio, model, lengths, sampling_rate, threshold=threshold, min_speech_duration_ms=min_speech_duration_ms,
+        max_speech_duration_s=max_speech_duration_s, min_silence_duration_ms=min_silence_duration_ms, speech_pad_ms=speech_pad_ms,
+        neg_threshold=neg_threshold, min_silence_at_max_speech=min_silence_at_max_speech,
+        use_max_poss_sil_at_max_speech=use_max_poss_sil_at_max_speech)
+    if probs is None:
+        t = engine.torch
+        res = [[] for _ in range(given.shape[0])]
+        return (res, t.empty((given.shape[0], 0), dtype=t.float32, device=engine.device)) if return_probs else res
     res = _finish(segs, counts, lens, sampling_rate, return_seconds, time_resolution, step)
     return (res, probs) if return_probs else res
+
+
+def get_speech_audio_batch(audio, model, lengths=None, drop=False, align=1, return_seconds: bool = False, time_resolution: int = 1,
+                           sampling_rate: int = 16000, **kw):
+    """Timestamps AND the audio they select, without the table leaving the device: clips -> segments -> chunks plan -> chunks copy, with
+    one 16-byte read (the size of the packed result) in between.  audio f32 [B, N] and `lengths` as get_speech_timestamps_batch, **kw its
+    segmenter arguments (threshold, min_speech_duration_ms, ...); drop=True keeps what is NOT speech (drop_chunks), align as
+    vadx.chunks.collect_chunks_batch.  -> (packed float32, offsets int64 [B+1], timestamps): clip b's samples are
+    packed[offsets[b] : offsets[b+1]] (up to alignment filler); `timestamps` is what get_speech_timestamps_batch returns.  With a
+    sampling rate that is a multiple of 16000 the network sees every step-th sample and the cut is made in the audio as given."""
+    from . import chunks
+    engine, given, lens, sampling_rate, step, probs, segs, counts = _segments_on_device(audio, model, lengths, sampling_rate, **kw)
+    t = engine.torch
+    B = given.shape[0]
+    if probs is None:
+        return t.empty(0, dtype=t.float32, device=engine.device), t.zeros(B + 1, dtype=t.int64, device=engine.device), [[] for _ in range(B)]
+    full = np.full((B,), given.shape[1], np.int64) if lengths is None else np.asarray(lengths, dtype=np.int64)
+    run = chunks.drop_chunks_batch if drop else chunks.collect_chunks_batch
+    packed, offsets = run((segs * step if step > 1 else segs, counts), given, lengths=full, align=align)
+    return packed, offsets, _finish(segs, counts, lens, sampling_rate, return_seconds, time_resolution, step)
 
 
 def get_speech_timestamps(audio, model, threshold: float = 0.5, sampling_rate: int = 16000,
