@@ -196,7 +196,8 @@ typedef struct vadx_silero_seg_params {
  * index pairs int64 [B][cap][2] + counts int32 [B] (count > cap => truncated, VADX_ENOSPACE is NOT
  * raised on device; the host checks counts).  n_samples int64 [B] = true clip lengths.
  * Replaces: the state machine + padding of get_speech_timestamps, utils_vad.py:374-476
- * (the seconds rounding :478-482 stays on the host: it is Python round()). */
+ * (the seconds rounding :478-482 stays on the host: it is Python round()).  On the device, from this call's table:
+ * vadx_timestamps_samples, section "Timestamps". */
 int vadx_silero_segments(const float *probs, int batch, int steps, const int64_t *n_samples,
                          const vadx_silero_seg_params *params, int64_t *segments, int32_t *counts,
                          int cap, void *stream);
@@ -606,7 +607,8 @@ size_t vadx_vadpost_workspace_bytes(int batch, int stride);
  * int32 pairs [B][cap][2] + counts [B]; one clip per thread.
  * Replaces VadPostprocessor.process + the edge extraction of decision_to_segment
  * (Inference_FireRed_ONNX.py:122-168, 181-304; MarbleNet copy Inference_NVIDIA_...:160-353);
- * the float32 seconds arithmetic + round(,3) of decision_to_segment :169-179 stays on the host. */
+ * the float32 seconds arithmetic + round(,3) of decision_to_segment :169-179 stays on the host.  On the device, from this call's
+ * table: vadx_timestamps_frames, section "Timestamps". */
 int vadx_vadpost(const vadx_vadpost_params *prm, const float *probs, int stride, const int32_t *n_frames,
                  int batch, int8_t *decisions, int32_t *segments, int32_t *counts, int cap,
                  void *workspace, size_t workspace_bytes, void *stream);
@@ -1109,6 +1111,65 @@ int vadx_chunks_plan(const int64_t *segments, const int32_t *counts, const int64
  * a negative element count, src / dst not 16-byte aligned, plan_bytes < vadx_chunks_plan_bytes, ceil(dst_elems / tile) >= 2^31. */
 int vadx_chunks_copy(const void *src, int64_t src_elems, const int64_t *clip_src, int elem_bytes, void *plan, size_t plan_bytes, int batch, int cap,
                      void *dst, int64_t dst_elems, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Timestamps: per-frame decisions or a segment table -> timestamps in seconds AND in samples, for every clip of a resident batch, in
+ * one launch (one wave per clip) -- the step between a model's device output and vadx_chunks_plan, which the drivers otherwise do on
+ * the host, one clip at a time.  Every number is bit for bit what the reference's Python computes (csrc/timestamps.hip states each rule).
+ * Three inputs, one entry point each; all share the second half, process_timestamps (FSMN/Inference_FSMN_VAD_ONNX.py:123-141): rows with
+ * (end - start) >= min_duration are kept, a kept row opens a new segment when start - (the previous kept row's end) > fusion_threshold
+ * and extends the open one otherwise.  (The reference runs the fuse twice; its second pass compares the same numbers and changes nothing.)
+ *
+ * Outputs of every call (device memory):
+ *   seconds f64   [batch][cap][2]   (start_s, end_s)
+ *   samples int64 [batch][cap][2]   the same rows in samples, by params.sample_rule:
+ *                                   VADX_TS_NEAREST int(round(s * sampling_rate)), VADX_TS_TRUNC int(s * sampling_rate)
+ *                                   -- the table vadx_chunks_plan takes as it is
+ *   counts  int32 [batch]           the TRUE number of segments; rows beyond cap are not written (nothing is indexed past cap)
+ *   head    16 bytes                int32 status (VADX_TS_ST_* bits), int32 the largest count, 8 bytes of zeros: one small read answers
+ *                                   both "did it fit" and "was anything refused"
+ * A REFUSED clip (its n_flags / counts_in / n_frames / clip_len outside its table, as listed per call) gets count 0 and sets
+ * VADX_TS_ST_BAD_CLIP; none of its input rows is read, none of its output rows written.  VADX_EINVAL, before any HIP call, for a NULL
+ * or misaligned pointer, batch < 1, cap outside [1, 2^30], sampling_rate < 1, another sample_rule, process not 0 / 1, a NaN threshold
+ * with process = 1, and what each call adds. */
+#define VADX_TS_NEAREST 0           /* int(round(s * sr)): vadx.chunks.from_seconds */
+#define VADX_TS_TRUNC   1           /* int(s * sr): timestamps_indices.txt, FSMN/Inference_FSMN_VAD_ONNX.py:252-258 */
+#define VADX_TS_ST_BAD_CLIP 1       /* some clip was refused (its count is 0) */
+#define VADX_TS_ST_OVERFLOW 2       /* some clip has more segments than cap: call again with cap = the head's largest count */
+typedef struct vadx_ts_params {
+    double frame_s;                 /* FLAGS: seconds per flag (> 0) */
+    double fusion_threshold;        /* process_timestamps, used when process = 1 */
+    double min_duration;
+    float  frame_shift;             /* FRAMES: seconds per frame, float32 as VadPostprocessor holds it (> 0) */
+    float  frame_length;            /* FRAMES: added to an end at the end of the audio when use_frame_length = 1 (FireRed 0.025; MarbleNet none) */
+    int    use_frame_length;
+    int    sampling_rate;           /* the rate of `samples`; SAMPLES: also the divisor, 16000 or 8000 */
+    int    process;                 /* 1: process_timestamps after the conversion; 0: the rows go through as they are */
+    int    sample_rule;             /* VADX_TS_NEAREST / VADX_TS_TRUNC */
+} vadx_ts_params;
+/* FLAGS: silence flags uint8 [batch][stride], n_flags int32 [batch] valid per row (what vadx_fsmn_clips* and vadx_dfsmn_vote write;
+ * speech = flag 0 at a position < n_flags[b], so the 255 filler of a ragged row is silence).  A run [a, b) of speech gives
+ * (a * frame_s, b == n ? n * frame_s : b * frame_s + frame_s), then process_timestamps when process = 1.
+ * Replaces vad_to_timestamps + process_timestamps, FSMN/Inference_FSMN_VAD_ONNX.py:102-141 (the DFSMN drivers carry the same code).
+ * Refused: n_flags[b] < 0 or > stride.  Also VADX_EINVAL: stride < 0, frame_s not positive and finite. */
+int vadx_timestamps_flags(const vadx_ts_params *prm, const uint8_t *flags, int64_t stride, const int32_t *n_flags, int batch,
+                          double *seconds, int64_t *samples, int32_t *counts, int cap, void *head, void *stream);
+/* FRAMES: the table vadx_vadpost writes, segments int32 [batch][cap_in][2] + counts_in int32 [batch], with n_frames int32 [batch] and
+ * wav_dur f64 [batch] (seconds; NaN = none).  float32 frame * frame_shift; when the clip's last row ends at n_frames[b] its end is
+ * n_frames[b] * frame_shift (+ frame_length), capped by wav_dur[b], as float32; then Python's round(, 3).  n_frames[b] = 0: no segment.
+ * Replaces the tail of decision_to_segment, FireRedVAD/Inference_FireRed_ONNX.py:169-179 (and MarbleNet's copy).
+ * Refused: counts_in[b] < 0 or > cap_in, n_frames[b] < 0.  Also VADX_EINVAL: cap_in < 1, frame_shift not positive and finite,
+ * use_frame_length not 0 / 1. */
+int vadx_timestamps_frames(const vadx_ts_params *prm, const int32_t *segments, const int32_t *counts_in, int cap_in, const int32_t *n_frames,
+                           const double *wav_dur, int batch, double *seconds, int64_t *samples, int32_t *counts, int cap, void *head,
+                           void *stream);
+/* SAMPLES: the table vadx_silero_segments writes, segments int64 [batch][cap_in][2] + counts_in int32 [batch], with clip_len int64
+ * [batch]: start = max(round(s / sr, 1), 0), end = min(round(e / sr, 1), clip_len / sr), Python's round (time_resolution = 1 only;
+ * |s|, |e|, clip_len < 2^53).  Replaces the return_seconds branch of get_speech_timestamps, Silero/modeling_modified/utils_vad.py:478-482,
+ * and with process = 1 the process_timestamps pass of Silero/Inference_Silero_VAD_ONNX.py over its result.
+ * Refused: counts_in[b] < 0 or > cap_in, clip_len[b] < 0.  Also VADX_EINVAL: cap_in < 1, sampling_rate not 16000 or 8000. */
+int vadx_timestamps_samples(const vadx_ts_params *prm, const int64_t *segments, const int32_t *counts_in, int cap_in, const int64_t *clip_len,
+                            int batch, double *seconds, int64_t *samples, int32_t *counts, int cap, void *head, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Test hooks (used by tests/ only)

@@ -130,6 +130,13 @@ class StreamVadPostParams(C.Structure):
                 ("min_speech_frame", C.c_int), ("max_speech_frame", C.c_int), ("min_silence_frame", C.c_int)]
 
 
+class TsParams(C.Structure):
+    """vadx_ts_params (include/vadx.h, "Timestamps")"""
+    _fields_ = [("frame_s", C.c_double), ("fusion_threshold", C.c_double), ("min_duration", C.c_double), ("frame_shift", C.c_float),
+                ("frame_length", C.c_float), ("use_frame_length", C.c_int), ("sampling_rate", C.c_int), ("process", C.c_int),
+                ("sample_rule", C.c_int)]
+
+
 class SepConvCfg(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("cin", "cout", "kernel", "stride", "dilation", "depthwise", "residual_cin", "relu")]
 
@@ -269,6 +276,9 @@ SIGNATURES = {
     "vadx_chunks_plan_bytes": (_Z, [_I, _I]),
     "vadx_chunks_plan": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
     "vadx_chunks_copy": (_I, [_P, _L, _P, _I, _P, _Z, _I, _I, _P, _L, _P]),
+    "vadx_timestamps_flags": (_I, [C.POINTER(TsParams), _P, _L, _P, _I, _P, _P, _P, _I, _P, _P]),
+    "vadx_timestamps_frames": (_I, [C.POINTER(TsParams), _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
+    "vadx_timestamps_samples": (_I, [C.POINTER(TsParams), _P, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P]),
 }
 
 _lib = None
@@ -306,7 +316,7 @@ class _TracingLib:
 
     def __getattr__(self, name):
         fn = getattr(_load(), name)
-        if name.endswith(("_host", "_floats", "_bytes", "_version", "_error", "_frames")):
+        if name.endswith(("_host", "_floats", "_bytes", "_version", "_error", "_out_frames", "_max_frames")):
             return fn
         import torch
 

@@ -72,6 +72,20 @@ def track_segments(pp, track, n_frames, durations_s):
             for b in range(track.shape[0])], dec
 
 
+def track_table(pp, track, n_frames, durations_s, sampling_rate, sample_rule=0, cap=64):
+    """`track_segments` without the frame table leaving the device -> (vadx.tstable.TimestampTable, decisions i8 [B, S] on the device):
+    one process_batch launch, one vadx_timestamps_frames launch, one 16-byte read of the table's head.  Only when that head reports a
+    clip with more than `cap` segments (refused) is the frame table made again as wide as it must be, the way `process_batch` does."""
+    from . import tstable
+    nf = [track.shape[1]] * track.shape[0] if n_frames is None else n_frames
+    dec, segs, counts = pp.process_batch(track, n_frames=n_frames, cap=cap, check=False)
+    table = tstable.from_frames(pp, segs, counts, nf, durations_s, sampling_rate, sample_rule)
+    if table.head()[0] & tstable.ST_BAD_CLIP:
+        dec, segs, counts = pp.process_batch(track, n_frames=n_frames, cap=cap)
+        table = tstable.from_frames(pp, segs, counts, nf, durations_s, sampling_rate, sample_rule)
+    return table, dec
+
+
 def flag_timestamps(flags, frame_s, fusion_threshold, min_speech_duration):
     """One clip's or stream's silence flags (1-D, one per `frame_s` seconds) -> [(start_s, end_s)]: the reference's vad_to_timestamps +
     process_timestamps over its `saved` list."""

@@ -620,6 +620,31 @@ class DfsmnEngine:
         fl = flags.cpu().numpy()
         return [flag_timestamps(fl[b], self.FRAME / 16000, fusion_threshold, min_speech_duration) for b in range(B)]
 
+    def detect_table(self, near_clips, far_clips, pad_noise_near=None, pad_noise_far=None, fusion_threshold=0.3,
+                     min_speech_duration=0.2, speaking_score=0.5, silence_score=0.5, sample_rule="nearest"):
+        """`detect` with the flags staying on the device: the same launches, then one vadx_timestamps_flags launch -> a
+        vadx.tstable.TimestampTable whose `lists()` is what `detect` returns and whose `chunks_table()` goes straight to
+        vadx.chunks.collect_chunks_batch (sample rows at 16 kHz, by `sample_rule`)."""
+        from . import timestamps as ts, tstable
+        t = self.torch
+        if isinstance(near_clips, (list, tuple)):
+            flags, nflags = self.flags_ragged(self.ragged(near_clips, far_clips, pad_noise_near, pad_noise_far), speaking_score, silence_score)
+        else:
+            near_clips = np.asarray(near_clips)
+            far_clips = None if far_clips is None else np.asarray(far_clips)
+            B = near_clips.shape[0]
+            n = near_clips.shape[1] if far_clips is None else min(near_clips.shape[1], far_clips.shape[1])
+            lb, stride = self.grid()
+            prep = lambda a: ts.normalize_to_int16(a.astype(np.float32))      # noqa: E731
+            near, W = pad_batch(near_clips[:, :n], self.L, stride, pad_noise_near, prep)
+            far = None if far_clips is None else pad_batch(far_clips[:B, :n], self.L, stride, pad_noise_far, prep)[0]
+            vad = self.run(near, far, W, stride)
+            flags, nflags = t.empty((B, W * (self.T_A - lb) + lb), dtype=t.uint8, device=self.device), None
+            with t.cuda.device(self.device):
+                _lib.check(self.lib.vadx_dfsmn_vote(vad.data_ptr(), B, W, self.T_A, lb, float(speaking_score), float(silence_score),
+                                                    flags.data_ptr(), _lib.stream_ptr()))
+        return tstable.from_flags(flags, nflags, self.FRAME / 16000, fusion_threshold, min_speech_duration, 16000, sample_rule)
+
     # ---- ragged batches: clip pairs of any lengths, one launch sequence (include/vadx.h, "DFSMN over a RAGGED batch") -----------------
     def ragged(self, near_clips, far_clips, pad_noise_near=None, pad_noise_far=None, device=True):
         """Clip pairs of any lengths (host, any numeric dtype; far_clips None = the near-end-only model) -> vadx.ragged.RaggedPairs on

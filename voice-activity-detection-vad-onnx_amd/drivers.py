@@ -63,6 +63,23 @@ def _stack_noise(noises, idx):
     return np.stack([r[:n] for r in rows])
 
 
+def _table_files(detect_table, clips, as_list, pad_noise):
+    """`_detect_files` for the `detect_table` calls (save_speech_audio): a list of files is one ragged batch, a single file a [1, N]
+    array with its noise row -> the vadx.tstable.TimestampTable of the call."""
+    if as_list:
+        return detect_table(clips, pad_noise)
+    return detect_table(clips[0][None, :], _stack_noise(pad_noise, [0]))
+
+
+def _finish_speech(files, table, save_speech_audio, device, save_second, save_indices, single, elapsed, echo):
+    """The end of a driver call that was given save_speech_audio (a wav path; for a list of files `<path>.<k>`, as the timestamp files):
+    the call ran its engine's `detect_table`, so the timestamps are a device table (vadx.tstable).  The files' int16 samples inside
+    them are cut from that table (vadx.chunks) -- no timestamp crosses to the host in between -- and the timestamp files are written
+    from the table's one read-back."""
+    _save_speech(files, table, 16000, save_speech_audio, single, device)
+    return _finish(table.lists(), 16000, save_second, save_indices, single, elapsed, echo)
+
+
 def _finish(all_ts, sample_rate, save_second, save_indices, single, elapsed, echo):
     if single:
         timestamps.write_timestamp_files(all_ts[0], sample_rate, save_second, save_indices, echo)
@@ -108,7 +125,8 @@ def inference_silero(test_vad_audio="./vad_sample.wav", model=None, save_timesta
 
 def _save_speech(files, all_ts, sample_rate, path, single, device):
     """Every file's int16 samples inside its (start_s, end_s) timestamps as a wav: the clips go up once as a packed vector, ONE
-    collect_chunks_batch cuts them all, the packed speech comes back once."""
+    collect_chunks_batch cuts them all, the packed speech comes back once.  all_ts: the host lists, uploaded as a table -- or a
+    vadx.tstable.TimestampTable, whose sample rows are on the device already (no timestamp crosses to the host for the cut)."""
     import torch
     from . import chunks
     pcm = [audio_io.load_wav(f, sample_rate) for f in files]
@@ -117,8 +135,8 @@ def _save_speech(files, all_ts, sample_rate, path, single, device):
     flat = np.zeros(int(starts[-1]), np.int16)
     for k, c in enumerate(pcm):
         flat[starts[k]:starts[k] + len(c)] = c
-    packed, offsets, plan = chunks.collect_chunks_batch(chunks.from_seconds(all_ts, sample_rate), torch.from_numpy(flat).to(device), lengths=lens,
-                                                        clip_offsets=starts[:-1], return_plan=True)
+    table = all_ts.chunks_table() if hasattr(all_ts, "chunks_table") else chunks.from_seconds(all_ts, sample_rate)
+    packed, offsets, plan = chunks.collect_chunks_batch(table, torch.from_numpy(flat).to(device), lengths=lens, clip_offsets=starts[:-1], return_plan=True)
     packed, offsets, n = packed.cpu().numpy(), offsets.cpu().numpy(), plan.lengths.cpu().numpy()
     for k in range(len(files)):
         audio_io.save_wav(path if single else f"{path}.{k}", packed[offsets[k]:offsets[k] + n[k]], sample_rate)
@@ -127,17 +145,22 @@ def _save_speech(files, all_ts, sample_rate, path, single, device):
 def inference_fsmn(test_vad_audio="./vad_sample.wav", engine=None, save_timestamps_second="./timestamps_second.txt",
                    save_timestamps_indices="./timestamps_indices.txt", FUSION_THRESHOLD=0.3, MIN_SPEECH_DURATION=0.2,
                    SPEAKING_SCORE=0.5, SILENCE_SCORE=0.5, LOOK_BACKWARD=0.3, SNR_THRESHOLD=10.0,
-                   BACKGROUND_NOISE_dB_INIT=30.0, ONE_MINUS_SPEECH_THRESHOLD=1.0, pad_noise=None, echo=print):
-    """FSMN/Inference_FSMN_VAD_ONNX.py:66-260."""
+                   BACKGROUND_NOISE_dB_INIT=30.0, ONE_MINUS_SPEECH_THRESHOLD=1.0, pad_noise=None, echo=print, save_speech_audio=None):
+    """FSMN/Inference_FSMN_VAD_ONNX.py:66-260.  save_speech_audio: `_finish_speech`."""
     from . import fsmn
     engine = _engine_of(fsmn.FsmnEngine, engine)
-    clips = _load(_as_list(test_vad_audio))
+    files, single = _as_list(test_vad_audio), not isinstance(test_vad_audio, (list, tuple))
+    clips = _load(files)
     echo("\nRunning the FSMN_VAD by ONNX Runtime.")
     t0 = time.time()
     kw = dict(fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION, look_backward_s=LOOK_BACKWARD,
               speaking_score=SPEAKING_SCORE, silence_score=SILENCE_SCORE, snr_threshold=SNR_THRESHOLD,
               noise_init_dB=BACKGROUND_NOISE_dB_INIT, one_minus_speech_threshold=ONE_MINUS_SPEECH_THRESHOLD)
     # (the int16 clips as they are: `detect` widens each to float32 itself before its peak normalisation)
+    if save_speech_audio is not None:
+        table = _table_files(lambda c, nz: engine.detect_table(c, pad_noise=nz, **kw), clips, not single, pad_noise)
+        return _finish_speech(files, table, save_speech_audio, engine.device, save_timestamps_second, save_timestamps_indices, single,
+                              time.time() - t0, echo)
     all_ts = _detect_files(lambda c, nz: engine.detect(c, pad_noise=nz, **kw), clips, isinstance(test_vad_audio, (list, tuple)), pad_noise)
     elapsed = time.time() - t0
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
@@ -146,18 +169,25 @@ def inference_fsmn(test_vad_audio="./vad_sample.wav", engine=None, save_timestam
 def inference_firered(test_vad_audio="./vad_sample.wav", engine=None, save_timestamps_second="./timestamps_second.txt",
                       save_timestamps_indices="./timestamps_indices.txt", NORMALIZE_AUDIO=False, SMOOTH_WINDOW_SIZE=5,
                       SPEAKING_SCORE=0.4, MIN_SPEECH_FRAME=20, MAX_SPEECH_FRAME=2000, MIN_SILENCE_FRAME=20,
-                      MERGE_SILENCE_FRAME=5, EXTEND_SPEECH_FRAME=0, pad_noise=None, echo=print):
-    """FireRedVAD/Inference_FireRed_ONNX.py:523-613 (RUN_VAD)."""
+                      MERGE_SILENCE_FRAME=5, EXTEND_SPEECH_FRAME=0, pad_noise=None, echo=print, save_speech_audio=None):
+    """FireRedVAD/Inference_FireRed_ONNX.py:523-613 (RUN_VAD).  save_speech_audio: `_finish_speech`."""
     from . import firered
     engine = _engine_of(firered.FireRedEngine, engine)
-    clips = _load(_as_list(test_vad_audio), NORMALIZE_AUDIO)
+    files, single = _as_list(test_vad_audio), not isinstance(test_vad_audio, (list, tuple))
+    clips = _load(files, NORMALIZE_AUDIO)
     echo("\nRunning the FireRedVAD by ONNX Runtime.")
     t0 = time.time()
     post = (SMOOTH_WINDOW_SIZE, SPEAKING_SCORE, MIN_SPEECH_FRAME, MAX_SPEECH_FRAME, MIN_SILENCE_FRAME,
             MERGE_SILENCE_FRAME, EXTEND_SPEECH_FRAME)
-    all_ts = _detect_files(lambda c, nz: engine.detect(c, pad_noise=nz, post=post), clips, isinstance(test_vad_audio, (list, tuple)), pad_noise)
+    table = None
+    if save_speech_audio is not None:
+        table = _table_files(lambda c, nz: engine.detect_table(c, pad_noise=nz, post=post), clips, not single, pad_noise)
+    else:
+        all_ts = _detect_files(lambda c, nz: engine.detect(c, pad_noise=nz, post=post), clips, isinstance(test_vad_audio, (list, tuple)), pad_noise)
     elapsed = time.time() - t0
     echo(f"RTF: {elapsed / (sum(len(c) for c in clips) / 16000):.4f}")
+    if table is not None:
+        return _finish_speech(files, table, save_speech_audio, engine.device, save_timestamps_second, save_timestamps_indices, single, elapsed, echo)
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
 
 
@@ -244,15 +274,21 @@ def inference_marblenet_stream(test_vad_audio="./vad_sample.wav", engine=None, c
 def inference_marblenet(test_vad_audio="./vad_sample.wav", engine=None, save_timestamps_second="./timestamps_second.txt",
                         save_timestamps_indices="./timestamps_indices.txt", NORMALIZE_AUDIO=False, SMOOTH_WINDOW_SIZE=3,
                         SPEAKING_SCORE=0.5, MIN_SPEECH_FRAME=10, MAX_SPEECH_FRAME=1000, MIN_SILENCE_FRAME=10,
-                        MERGE_SILENCE_FRAME=3, EXTEND_SPEECH_FRAME=0, INPUT_AUDIO_LENGTH=None, pad_noise=None, echo=print):
-    """NVIDIA_.../Inference_NVIDIA_MarbleNet_VAD_ONNX.py:120-422 (dynamic axis: one window per clip)."""
+                        MERGE_SILENCE_FRAME=3, EXTEND_SPEECH_FRAME=0, INPUT_AUDIO_LENGTH=None, pad_noise=None, echo=print,
+                        save_speech_audio=None):
+    """NVIDIA_.../Inference_NVIDIA_MarbleNet_VAD_ONNX.py:120-422 (dynamic axis: one window per clip).  save_speech_audio: `_finish_speech`."""
     from . import marblenet
     engine = _engine_of(marblenet.MarbleNetEngine, engine)
-    clips = _load(_as_list(test_vad_audio), NORMALIZE_AUDIO)
+    files, single = _as_list(test_vad_audio), not isinstance(test_vad_audio, (list, tuple))
+    clips = _load(files, NORMALIZE_AUDIO)
     echo("\nRunning the NVIDIA_VAD by ONNX Runtime.")
     t0 = time.time()
     post = (SMOOTH_WINDOW_SIZE, SPEAKING_SCORE, MIN_SPEECH_FRAME, MAX_SPEECH_FRAME, MIN_SILENCE_FRAME,
             MERGE_SILENCE_FRAME, EXTEND_SPEECH_FRAME)
+    if save_speech_audio is not None:
+        table = _table_files(lambda c, nz: engine.detect_table(c, window_len=INPUT_AUDIO_LENGTH, pad_noise=nz, post=post), clips, not single, pad_noise)
+        return _finish_speech(files, table, save_speech_audio, engine.device, save_timestamps_second, save_timestamps_indices, single,
+                              time.time() - t0, echo)
     all_ts = _detect_files(lambda c, nz: engine.detect(c, window_len=INPUT_AUDIO_LENGTH, pad_noise=nz, post=post), clips,
                            isinstance(test_vad_audio, (list, tuple)), pad_noise)
     elapsed = time.time() - t0
@@ -262,9 +298,10 @@ def inference_marblenet(test_vad_audio="./vad_sample.wav", engine=None, save_tim
 def inference_dfsmn(test_near_end_audio="./examples/nearend_mic.wav", test_far_end_audio="./examples/farend_speech.wav", engine=None,
                     save_timestamps_second="./timestamps_second.txt", save_timestamps_indices="./timestamps_indices.txt",
                     SPEAKING_SCORE=0.5, SILENCE_SCORE=0.5, FUSION_THRESHOLD=0.3, MIN_SPEECH_DURATION=0.2,
-                    pad_noise_near=None, pad_noise_far=None, echo=print):
+                    pad_noise_near=None, pad_noise_far=None, echo=print, save_speech_audio=None):
     """DFSMN/near_and_far_end_audio/Inference_DFSMN_VAD_ONNX.py:121-300: near-end mic + far-end reference -> AEC ->
-    mask-net VAD -> look-ahead vote -> timestamps (both text files).  Lists of paths run as ONE ragged batch of clip pairs of any lengths."""
+    mask-net VAD -> look-ahead vote -> timestamps (both text files).  Lists of paths run as ONE ragged batch of clip pairs of any lengths.
+    save_speech_audio: `_finish_speech`, cut from the near-end file."""
     from . import dfsmn
     nears, fars = _as_list(test_near_end_audio), _as_list(test_far_end_audio)
     engine = _engine_of(dfsmn.DfsmnEngine, engine)
@@ -283,6 +320,14 @@ def inference_dfsmn(test_near_end_audio="./examples/nearend_mic.wav", test_far_e
         if isinstance(pr, list):
             return engine.detect([p[0] for p in pr], [p[1] for p in pr], *nz[0], **kw)
         return engine.detect(pr[:, 0], pr[:, 1], *nz, **kw)
+    if save_speech_audio is not None:
+        single = not isinstance(test_near_end_audio, (list, tuple))
+        if single:
+            table = engine.detect_table(pairs[0][None, 0], pairs[0][None, 1], _stack_noise(pad_noise_near, [0]), _stack_noise(pad_noise_far, [0]), **kw)
+        else:
+            table = engine.detect_table([p[0] for p in pairs], [p[1] for p in pairs], pad_noise_near, pad_noise_far, **kw)
+        return _finish_speech(nears, table, save_speech_audio, engine.device, save_timestamps_second, save_timestamps_indices, single,
+                              time.time() - t0, echo)
     all_ts = _detect_files(detect, pairs, isinstance(test_near_end_audio, (list, tuple)), (pad_noise_near, pad_noise_far))
     elapsed = time.time() - t0
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_near_end_audio, (list, tuple)), elapsed, echo)
@@ -290,10 +335,10 @@ def inference_dfsmn(test_near_end_audio="./examples/nearend_mic.wav", test_far_e
 
 def inference_dfsmn_near_only(test_vad_audio="./vad_sample.wav", engine=None, save_timestamps_second="./timestamps_second.txt",
                               save_timestamps_indices="./timestamps_indices.txt", SPEAKING_SCORE=0.5, SILENCE_SCORE=0.5,
-                              FUSION_THRESHOLD=0.3, MIN_SPEECH_DURATION=0.2, pad_noise=None, echo=print):
+                              FUSION_THRESHOLD=0.3, MIN_SPEECH_DURATION=0.2, pad_noise=None, echo=print, save_speech_audio=None):
     """DFSMN/only_near_end_audio/Inference_DFSMN_VAD_ONNX.py: one microphone file in, timestamps out (a list of files:
     one ragged batch).  `engine` must
-    carry the export's baked white-noise constants (DfsmnEngine.set_near_only_constants)."""
+    carry the export's baked white-noise constants (DfsmnEngine.set_near_only_constants).  save_speech_audio: `_finish_speech`."""
     from . import dfsmn, weights
     files = _as_list(test_vad_audio)
     if engine is None or isinstance(engine, (str, dict)):
@@ -302,6 +347,12 @@ def inference_dfsmn_near_only(test_vad_audio="./vad_sample.wav", engine=None, sa
     echo(f"\nTest Input Audio: {test_vad_audio}")
     clips = [audio_io.load_wav(pth, 16000).astype(np.float32) for pth in files]
     t0 = time.time()
+    if save_speech_audio is not None:
+        single = not isinstance(test_vad_audio, (list, tuple))
+        table = _table_files(lambda c, nz: engine.detect_table(c, None, nz, None, fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION,
+                                                               speaking_score=SPEAKING_SCORE, silence_score=SILENCE_SCORE), clips, not single, pad_noise)
+        return _finish_speech(files, table, save_speech_audio, engine.device, save_timestamps_second, save_timestamps_indices, single,
+                              time.time() - t0, echo)
     all_ts = _detect_files(lambda c, nz: engine.detect(c, None, nz, None, fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION,
                                                        speaking_score=SPEAKING_SCORE, silence_score=SILENCE_SCORE),
                            clips, isinstance(test_vad_audio, (list, tuple)), pad_noise)

@@ -13,7 +13,7 @@ from . import frontend as _frontend
 from . import ragged as _ragged
 from . import vadpost as _vadpost
 from . import weights as _weights
-from .clips import gather_tracks, pad_batch, track_segments
+from .clips import gather_tracks, pad_batch, track_segments, track_table
 from .session import Session, _Meta, require_int16
 
 SAMPLE_RATE, WINDOW_LENGTH, HOP_LENGTH = 16000, 400, 160
@@ -292,6 +292,13 @@ class FireRedEngine:
         if isinstance(clips_i16, (list, tuple)):
             return out, [track[b, :nf[b]] for b in range(len(nf))], [dec[b, :nf[b]] for b in range(len(nf))]
         return (out, track, dec) if track.shape[1] else (out, track)      # an array without a valid frame: no decisions are returned
+
+    def detect_table(self, clips_i16, pad_noise=None, post=(5, 0.4, 20, 2000, 20, 5, 0), sample_rule="nearest"):
+        """`detect` with the tracks and the frame table staying on the device (`clips.track_table`: one vadx_vadpost launch, one
+        vadx_timestamps_frames launch) -> a vadx.tstable.TimestampTable whose `lists()` is what `detect` returns and whose
+        `chunks_table()` goes straight to vadx.chunks.collect_chunks_batch (sample rows at in_sample_rate, by `sample_rule`)."""
+        channel, nf, durations = self._track_source(clips_i16, pad_noise, self.in_sample_rate)
+        return track_table(_vadpost.VadPostprocessor(*post, device=self.device), channel(0), nf, durations, self.in_sample_rate, sample_rule)[0]
 
 
 IDX2EVENT = {0: "speech", 1: "singing", 2: "music"}      # Inference_FireRed_ONNX.py:632

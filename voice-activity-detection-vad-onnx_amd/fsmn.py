@@ -303,6 +303,21 @@ class FsmnEngine:
         return [flag_timestamps(flags[b, :nflags[b]], OUTPUT_FRAME_LENGTH / SAMPLE_RATE, fusion_threshold, min_speech_duration)
                 for b in range(flags.shape[0])]
 
+    def detect_table(self, clips_i16, pad_noise=None, fusion_threshold=0.3, min_speech_duration=0.2, normalize=True, sample_rule="nearest",
+                     **loop_kw):
+        """`detect` with the flags staying on the device: the same launches, then one vadx_timestamps_flags launch -> a
+        vadx.tstable.TimestampTable whose `lists()` is what `detect` returns and whose `chunks_table()` goes straight to
+        vadx.chunks.collect_chunks_batch (sample rows at 16 kHz, by `sample_rule`)."""
+        from . import tstable
+        look_backward_s = loop_kw.get("look_backward_s", 0.3)
+        if isinstance(clips_i16, (list, tuple)):
+            flags, nflags = self.flags_ragged(self.ragged(clips_i16, pad_noise, normalize, look_backward_s), **loop_kw)
+        else:
+            stride = (self._long_grid(look_backward_s) if self.long_windows else self.grid(look_backward_s))[1]
+            padded, W = pad_batch(clips_i16, self.L, stride, pad_noise, _prep(normalize))
+            flags, nflags = self.flags(self.torch.from_numpy(padded), W, **loop_kw), None
+        return tstable.from_flags(flags, nflags, OUTPUT_FRAME_LENGTH / SAMPLE_RATE, fusion_threshold, min_speech_duration, SAMPLE_RATE, sample_rule)
+
 
 class FsmnSession(Session):
     """onnxruntime.InferenceSession look-alike for the FSMN graph (names/dtypes/shapes of

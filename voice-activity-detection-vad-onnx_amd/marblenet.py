@@ -16,7 +16,7 @@ from . import frontend as _frontend
 from . import ragged as _ragged
 from . import vadpost as _vadpost
 from . import weights as _weights
-from .clips import gather_tracks, pad_batch, track_segments
+from .clips import gather_tracks, pad_batch, track_segments, track_table
 from .session import Session, _Meta, io_types, require_int16
 
 SAMPLE_RATE = 16000
@@ -313,6 +313,35 @@ class MarbleNetEngine:
             return out
         nfs = np.array([r[1].shape[0] for r in rows], dtype=np.int32)
         return out, self._pad_rows([r[1] for r in rows], self.torch.float32), self._pad_rows([r[2] for r in rows], self.torch.int8), nfs
+
+    def detect_table(self, clips_i16, window_len=None, pad_noise=None, post=(3, 0.5, 10, 1000, 10, 3, 0), sample_rule="nearest"):
+        """`detect` with the tracks and the frame table staying on the device (`clips.track_table`: one vadx_vadpost launch, one
+        vadx_timestamps_frames launch) -> a vadx.tstable.TimestampTable whose `lists()` is what `detect` returns and whose
+        `chunks_table()` goes straight to vadx.chunks.collect_chunks_batch (sample rows at in_sample_rate, by `sample_rule`).
+        A list holding a clip that `detect` would run on its own (dynamic axis: longer than 3600 s, or a graph that resamples) is
+        refused: one table is one launch sequence."""
+        as_list = isinstance(clips_i16, (list, tuple))
+        if as_list and not self.fused:
+            raise ValueError("MarbleNetEngine.detect_table: a list of clips (a ragged batch) is built for the published MarbleNet 3x2x64 layout; "
+                             "this engine was constructed with another `blocks` layout -- pass equal-length clips as a [B, N] array")
+        rate = self.in_sample_rate
+        pp = _vadpost.VadPostprocessor(*post, frame_shift_s=OUTPUT_FRAME_SHIFT_S, frame_length_s=None, device=self.device)
+        if not as_list:
+            B, n = np.asarray(clips_i16).shape
+            L = min(rate * 3600, n) if window_len is None else int(window_len)
+            padded, W = pad_batch(clips_i16, L, L, pad_noise)
+            s0, s1, slen = self.run(padded, W, L)
+            valid = min(slen, s1.shape[1])
+            track = s1.view(B, W, -1)[:, :, :valid].reshape(B, W * valid).contiguous()
+            return track_table(pp, track, None, [n / rate] * B, rate, sample_rule)[0]
+        clips = [np.asarray(c) for c in clips_i16]
+        if len(clips) == 0:
+            raise ValueError("a ragged batch needs at least one clip")
+        if window_len is None and (rate != SAMPLE_RATE or any(c.size > rate * 3600 for c in clips)):
+            raise ValueError("MarbleNetEngine.detect_table: a dynamic-axis clip longer than 3600 s, or a graph that resamples, runs one call per "
+                             "clip in `detect`; build the table from clips the ragged kernels take, or pass window_len")
+        track, nf, lengths = self._list_track(clips, window_len, pad_noise)
+        return track_table(pp, track, nf, [int(n) / rate for n in lengths], rate, sample_rule)[0]
 
     def _list_track(self, clips, window_len, pad_noise):
         """A list of 1-D int16 clips of any lengths -> (track f32 [B, max n_frames] on the device, n_frames int32 [B], lengths [B]).

@@ -860,6 +860,22 @@ def get_speech_timestamps_batch(audio, model, lengths=None, threshold: float = 0
     return (res, probs) if return_probs else res
 
 
+def get_speech_timestamps_table(audio, model, lengths=None, sampling_rate: int = 16000, time_resolution: int = 1, fusion_threshold=None,
+                                min_duration=None, sample_rule="nearest", **kw):
+    """The device half of get_speech_timestamps_batch(return_seconds=True): the same launches, then one vadx_timestamps_samples launch
+    instead of the per-row round() on the host -> a vadx.tstable.TimestampTable whose `lists()` are those dicts.  With fusion_threshold
+    and min_duration the table also carries the process_timestamps pass that `drivers.inference_silero` runs over them.  **kw: the
+    segmenter arguments (threshold, min_speech_duration_ms, ...).  Only time_resolution = 1.  `chunks_table()` holds the seconds as
+    sample rows of the rate the network ran at (16000 for a multiple of it)."""
+    from . import tstable
+    if time_resolution != 1:
+        raise ValueError(f"time_resolution={time_resolution}: the device table rounds to one decimal (time_resolution=1) only")
+    engine, given, lens, sampling_rate, step, probs, segs, counts = _segments_on_device(audio, model, lengths, sampling_rate, **kw)
+    if probs is None:
+        return tstable.empty(given.shape[0], engine.device, sampling_rate, dicts=True)
+    return tstable.from_samples(segs, counts, lens, sampling_rate, fusion_threshold, min_duration, sample_rule=sample_rule)
+
+
 def get_speech_audio_batch(audio, model, lengths=None, drop=False, align=1, return_seconds: bool = False, time_resolution: int = 1,
                            sampling_rate: int = 16000, **kw):
     """Timestamps AND the audio they select, without the table leaving the device: clips -> segments -> chunks plan -> chunks copy, with

@@ -30,8 +30,10 @@ class VadPostprocessor:
         self.frame_shift = np.float32(frame_shift_s)
         self.frame_length = None if frame_length_s is None else np.float32(frame_length_s)
 
-    def process_batch(self, probs, n_frames=None, cap=64):
-        """probs f32 [B, S] (device or host), n_frames [B] -> (decisions i8 [B,S], segs i32 [B,cap,2], counts)."""
+    def process_batch(self, probs, n_frames=None, cap=64, check=True):
+        """probs f32 [B, S] (device or host), n_frames [B] -> (decisions i8 [B,S], segs i32 [B,cap,2], counts).
+        check=False: one launch and no read-back -- a clip with more than `cap` segments is then the caller's to find (its count says so;
+        vadx.tstable.from_frames refuses such a clip and sets a status bit)."""
         t = self.torch
         if not t.is_tensor(probs):
             probs = t.from_numpy(np.ascontiguousarray(probs, dtype=np.float32))
@@ -53,6 +55,8 @@ class VadPostprocessor:
                 _lib.check(L.vadx_vadpost(C.byref(self.params), probs.data_ptr(), S, nfd.data_ptr(), B, dec.data_ptr(),
                                           segs.data_ptr(), counts.data_ptr(), cap, ws.data_ptr(), ws.numel(),
                                           _lib.stream_ptr()))
+            if not check:
+                return dec, segs, counts
             worst = int(counts.max().item())
             if worst <= cap:
                 return dec, segs, counts
