@@ -58,7 +58,9 @@ extern "C" {
  *     vadx_windows_gather_any, vadx_dfsmn_vote_ragged, vadx_dfsmn_stream_state_bytes, vadx_dfsmn_stream_windows, vadx_dfsmn_stream_vote; then
  *     MarbleNet over live streams: vadx_marblenet_stream_weights, vadx_marblenet_stream_max_frames, vadx_marblenet_stream_cap,
  *     vadx_marblenet_stream_state_bytes, vadx_marblenet_stream_workspace_bytes, vadx_marblenet_stream_tick, vadx_frontend_logmel_stream; then
- *     cutting the speech out on the device: vadx_chunks_plan_bytes, vadx_chunks_plan, vadx_chunks_copy.
+ *     cutting the speech out on the device: vadx_chunks_plan_bytes, vadx_chunks_plan, vadx_chunks_copy; then timestamps on the device:
+ *     vadx_timestamps_flags, vadx_timestamps_frames, vadx_timestamps_samples; then preparing a ragged batch on the device:
+ *     vadx_ingest_pcm16_ragged, vadx_prepare_workspace_bytes, vadx_prepare_stats, vadx_prepare_scale, vadx_prepare_write.
  *     A caller that needs them checks for the symbols (dlsym), not for a number. */
 #define VADX_ABI_VERSION 10
 
@@ -1183,6 +1185,61 @@ int vadx_timestamps_samples(const vadx_ts_params *prm, const int64_t *segments, 
 int64_t vadx_ingest_out_frames(int64_t frames_in, int in_rate, int out_rate);
 int vadx_ingest_pcm16(const int16_t *src, int64_t src_stride, int channels, int64_t frames_in, int in_rate,
                       int out_rate, int16_t *dst, int64_t dst_stride, int batch, void *stream);
+/* The same arithmetic over a RAGGED batch: the raw interleaved clips lie in one int16 vector `src`, clip b = frames_in[b] frames of
+ * channels[b] (1 or 2) channels at in_rate[b] from element src_off[b]; its vadx_ingest_out_frames(frames_in[b], in_rate[b], out_rate)
+ * mono samples go to dst from element dst_off[b].  One launch over tiles of 1024 output samples: tile_first int32 [batch + 1] is the prefix
+ * of max(1, ceil(out frames / 1024)) tiles per clip (every clip has a tile: its first writes the status), tile_clip int32 [tiles] the clip of
+ * every tile.  status int32 [batch] receives VADX_INGEST_ST_* bits per clip: what vadx_ingest_pcm16 refuses for its whole batch (channels not
+ * 1 or 2, a rate or frame count that is not positive, frames_in >= 2^31, reduced output rate >= 65536) is refused per clip, and so is a
+ * clip whose source range leaves [0, src_elems): its samples are written as zeros, nothing outside src is read.  A clip whose output
+ * range leaves [0, dst_elems) writes nothing.  VADX_EINVAL (before any HIP call) for a NULL or misaligned pointer, batch / tiles < 1,
+ * out_rate < 1, a negative element count. */
+#define VADX_INGEST_ST_BAD_CLIP  1
+#define VADX_INGEST_ST_SRC_RANGE 2
+#define VADX_INGEST_ST_DST_RANGE 4
+int vadx_ingest_pcm16_ragged(const int16_t *src, int64_t src_elems, const int64_t *src_off, const int64_t *frames_in, const int32_t *channels,
+                             const int32_t *in_rate, int out_rate, const int64_t *dst_off, const int32_t *tile_first, const int32_t *tile_clip,
+                             int batch, int tiles, int16_t *dst, int64_t dst_elems, int32_t *status, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Prepare: a resident packed vector of clips -> the packed, normalised, grid-padded vector of a ragged batch (vadx.ragged), bit for bit
+ * what the host loop builds per clip: normalize_to_int16 (PEAK, FSMN/Inference_FSMN_VAD_ONNX.py:60-63) or normalise_audio (RMS,
+ * Inference_NVIDIA_MarbleNet_VAD_ONNX.py:110-118) or nothing (NONE), then pad_to_window_grid's noise at the RMS of the normalised
+ * tail (FSMN/Inference_FSMN_VAD_ONNX.py:88-99).  csrc/prepare.hip states the arithmetic: float32, one rounding per operation, and the mean
+ * of squares in numpy's own order -- consecutive chunks of 8192 elements added in order, numpy's pairwise tree inside a chunk.
+ *
+ * Tables (device memory): clip b is lengths[b] samples of src from element src_off[b] (any residue) and owns elements
+ * dst_off[b] .. dst_off[b+1]-1 of dst (dst_off int64 [batch + 1], non-decreasing): first its samples, then dst_off[b+1] - dst_off[b] -
+ * lengths[b] samples of fill -- the caller lays dst out, by pad_to_window_grid's count for a window grid or end to end for none.  The fill's
+ * reference region is the clip's last `fill` samples when lengths[b] > window and the whole clip otherwise.  tile_first int32 [batch + 1] is
+ * the prefix of ceil(lengths[b] / 8192) chunks per clip, tile_clip int32 [tiles] the clip of every chunk.
+ * The workspace (vadx_prepare_workspace_bytes, 16-byte aligned) starts with one 16-byte record per clip, which the caller may read:
+ *   float scale (s or g; 1 when the clip stays as it is), float tail_rms, int32 status (VADX_PREPARE_ST_* bits), int32 0.
+ * Three launches on `stream`, in this order, whatever the batch: vadx_prepare_stats (per chunk: peak / sum of squares; not needed for NONE),
+ * vadx_prepare_scale (per clip: the record), vadx_prepare_write (per 16 KB of dst: the samples, then fill_k = int16(tail_rms * noise[noise_off[b]
+ * + k]) with the product in float64 and the cast as numpy's: toward zero, low 16 bits).  A clip whose source range leaves [0, src_elems), or
+ * whose length is < 1, sets VADX_PREPARE_ST_SRC_RANGE: nothing of src is read for it, its elements of dst are zeros.  A fill index outside
+ * [0, noise_elems) sets VADX_PREPARE_ST_NOISE_RANGE and writes zero.  A fill count that is neither 0 nor pad_to_window_grid's for (lengths[b],
+ * window, stride) sets VADX_PREPARE_ST_GRID (and is honoured).  Elements of dst that no clip owns are written as zeros; nothing outside
+ * [dst, dst + dst_elems) is written.
+ * VADX_EINVAL (before any HIP call) for a NULL or misaligned pointer (src, dst, workspace: 16 bytes), batch / tiles < 1, a negative
+ * element count, window or stride that is not a positive multiple of 8, another mode, target_rms not positive and finite,
+ * workspace_bytes < vadx_prepare_workspace_bytes(batch, tiles). */
+#define VADX_PREPARE_NONE 0
+#define VADX_PREPARE_PEAK 1
+#define VADX_PREPARE_RMS  2
+#define VADX_PREPARE_ST_SRC_RANGE   1
+#define VADX_PREPARE_ST_NOISE_RANGE 2
+#define VADX_PREPARE_ST_GRID        4
+size_t vadx_prepare_workspace_bytes(int batch, int tiles);
+int vadx_prepare_stats(const int16_t *src, int64_t src_elems, const int64_t *src_off, const int64_t *lengths, const int32_t *tile_first,
+                       const int32_t *tile_clip, int batch, int tiles, int mode, void *workspace, size_t workspace_bytes, void *stream);
+int vadx_prepare_scale(const int16_t *src, int64_t src_elems, const int64_t *src_off, const int64_t *lengths, const int64_t *dst_off,
+                       const int32_t *tile_first, int batch, int tiles, int window, int stride, int mode, float target_rms, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int vadx_prepare_write(const int16_t *src, int64_t src_elems, const int64_t *src_off, const int64_t *lengths, const int64_t *dst_off,
+                       const double *noise, int64_t noise_elems, const int64_t *noise_off, int batch, int tiles, int mode, void *workspace,
+                       size_t workspace_bytes, int16_t *dst, int64_t dst_elems, void *stream);
 
 /* Weight layout of every GEMM operand the kernels stream from L2 ("fragment-major"): a row-major
  * [rows][cols] matrix, zero-padded to multiples of 16 both ways, stored as

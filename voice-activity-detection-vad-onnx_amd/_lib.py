@@ -279,6 +279,11 @@ SIGNATURES = {
     "vadx_timestamps_flags": (_I, [C.POINTER(TsParams), _P, _L, _P, _I, _P, _P, _P, _I, _P, _P]),
     "vadx_timestamps_frames": (_I, [C.POINTER(TsParams), _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "vadx_timestamps_samples": (_I, [C.POINTER(TsParams), _P, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P]),
+    "vadx_ingest_pcm16_ragged": (_I, [_P, _L, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _L, _P, _P]),
+    "vadx_prepare_workspace_bytes": (_Z, [_I, _I]),
+    "vadx_prepare_stats": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "vadx_prepare_scale": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_float, _P, _Z, _P]),
+    "vadx_prepare_write": (_I, [_P, _L, _P, _P, _P, _P, _L, _P, _I, _I, _I, _P, _Z, _P, _L, _P]),
 }
 
 _lib = None

@@ -106,6 +106,80 @@ def read_wav_raw(path):
     return _lin2lin16(data, width).copy(), nch, rate
 
 
+INGEST_TILE = 1024        # output samples per workgroup of vadx_ingest_pcm16_ragged
+INGEST_ALIGN = 8          # every clip of ingest_ragged's output starts on a 16-byte boundary
+
+
+def _ragged_plan(raws, channels, rates, sample_rate):
+    """Checks and layout shared by `ingest_ragged` and its host mirror: -> (raws as int16 vectors, channels, rates, frames, out frames,
+    where each clip starts in the packed output, its length).  Refuses what vadx_ingest_pcm16 refuses, per clip."""
+    raws = [np.ascontiguousarray(r, dtype=np.int16).reshape(-1) for r in raws]
+    B = len(raws)
+    if B == 0:
+        raise ValueError("a ragged batch needs at least one clip")
+    channels = [int(channels)] * B if np.isscalar(channels) else [int(c) for c in channels]
+    rates = [int(rates)] * B if np.isscalar(rates) else [int(r) for r in rates]
+    if len(channels) != B or len(rates) != B:
+        raise ValueError(f"{B} clips, {len(channels)} channel counts, {len(rates)} rates")
+    frames, outs = [], []
+    for b, (r, c, rate) in enumerate(zip(raws, channels, rates)):
+        if c not in (1, 2):
+            raise ValueError(f"clip {b}: 1 or 2 interleaved channels (got {c})")
+        if rate <= 0 or sample_rate <= 0:
+            raise ValueError(f"clip {b}: rates must be positive")
+        if r.shape[0] == 0 or r.shape[0] % c:
+            raise ValueError(f"clip {b}: {r.shape[0]} samples are not a positive whole number of {c}-channel frames")
+        g = math.gcd(rate, int(sample_rate))
+        if int(sample_rate) // g >= 65536 or r.shape[0] // c >= 2 ** 31:
+            raise ValueError(f"clip {b}: reduced rates {rate // g} -> {int(sample_rate) // g} or {r.shape[0] // c} frames out of range")
+        frames.append(r.shape[0] // c)
+        outs.append((frames[-1] - 1) * (int(sample_rate) // g) // (rate // g) + 1)
+    outs = np.asarray(outs, dtype=np.int64)
+    room = (outs + INGEST_ALIGN - 1) // INGEST_ALIGN * INGEST_ALIGN
+    return raws, channels, rates, np.asarray(frames, dtype=np.int64), np.concatenate([[0], np.cumsum(room)[:-1]]).astype(np.int64), outs
+
+
+def ingest_ragged_host(raws, channels, rates, sample_rate=16000):
+    """The host mirror of `ingest_ragged`: (pcm int16 numpy, clip_offsets, lengths) with the closed form csrc/prepare.hip evaluates per
+    output sample (`_tomono`, `_ratecv`: audioop's arithmetic); the gaps that align the clips are zeros."""
+    raws, channels, rates, _, offs, outs = _ragged_plan(raws, channels, rates, sample_rate)
+    pcm = np.zeros(int(offs[-1] + (outs[-1] + INGEST_ALIGN - 1) // INGEST_ALIGN * INGEST_ALIGN), dtype=np.int16)
+    for r, c, rate, o, n in zip(raws, channels, rates, offs, outs):
+        x = _tomono(r) if c == 2 else r
+        pcm[o:o + n] = _ratecv(x, rate, sample_rate)
+    return pcm, offs, outs
+
+
+def ingest_ragged(raws, channels, rates, sample_rate=16000, device="cuda:0", return_status=False):
+    """Raw clips of ANY lengths, channel counts (1 or 2) and rates -> (pcm, clip_offsets, lengths): device int16 [total] mono at
+    `sample_rate` with audioop's tomono + ratecv arithmetic (vadx_ingest_pcm16_ragged, one launch), clip b = lengths[b] samples from
+    element clip_offsets[b] (host int64 arrays; every clip starts on a 16-byte boundary, the gaps are zeros) -- what
+    `RaggedBatch.from_packed` takes.  raws: interleaved int16 vectors as `read_wav_raw` returns them; the upload is the file bytes, once.
+    return_status: also the kernel's per-clip status words (device int32 [B], VADX_INGEST_ST_* bits; all zero for what this accepted)."""
+    from . import _lib
+    t = _lib.require_gpu()
+    raws, channels, rates, frames, offs, outs = _ragged_plan(raws, channels, rates, sample_rate)
+    B = len(raws)
+    src_off = np.concatenate([[0], np.cumsum([r.shape[0] for r in raws])[:-1]]).astype(np.int64)
+    per = np.maximum((outs + INGEST_TILE - 1) // INGEST_TILE, 1)
+    tiles = int(per.sum())
+    if tiles >= 2 ** 31:
+        raise ValueError(f"{tiles} tiles of {INGEST_TILE} samples do not fit the int32 tile tables")
+    total = int(offs[-1] + (outs[-1] + INGEST_ALIGN - 1) // INGEST_ALIGN * INGEST_ALIGN)
+    src = t.from_numpy(np.concatenate(raws)).to(device)
+    i64 = t.from_numpy(np.concatenate([src_off, frames, offs])).to(device)
+    i32 = t.from_numpy(np.concatenate([np.asarray(channels), np.asarray(rates), np.concatenate([[0], np.cumsum(per)]),
+                                       np.repeat(np.arange(B), per)]).astype(np.int32)).to(device)
+    out = t.zeros(total, dtype=t.int16, device=src.device)
+    status = t.zeros(B, dtype=t.int32, device=src.device)
+    p64, p32 = i64.data_ptr(), i32.data_ptr()
+    with t.cuda.device(src.device):
+        _lib.check(_lib.lib().vadx_ingest_pcm16_ragged(src.data_ptr(), int(src.numel()), p64, p64 + 8 * B, p32, p32 + 4 * B, int(sample_rate),
+                                                       p64 + 16 * B, p32 + 8 * B, p32 + 4 * (3 * B + 1), B, tiles, out.data_ptr(), total,
+                                                       status.data_ptr(), _lib.stream_ptr()))
+    return (out, offs, outs, status) if return_status else (out, offs, outs)
+
+
 def ingest_device(raw_i16, channels, rate, sample_rate=16000, device="cuda:0"):
     """Batch of equal-length raw clips int16 [B, frames * channels] (interleaved) -> device int16 [B, n] mono at
     `sample_rate`, with audioop's tomono + ratecv arithmetic on the GPU (vadx_ingest_pcm16): the upload is the raw

@@ -17,7 +17,7 @@ OBJ = os.path.join(CSRC, ".obj")
 LIB = os.path.join(HERE, "libvadx.so")
 TEST_HOOKS_SRC = os.path.join(ROOT, "tests", "hip")
 TEST_HOOKS_LIB = os.path.join(TEST_HOOKS_SRC, "libvadx_testhooks.so")
-SOURCES = ["capi.hip", "silero.hip", "silero_split.hip", "silero_h2.hip", "silero_stream.hip", "silero8k.hip", "silero_pack.hip", "frontend.hip", "fsmn.hip", "firered.hip", "marblenet.hip", "dfsmn.hip", "dfsmn_cfb.hip", "ingest.hip", "ragged.hip", "chunks.hip", "timestamps.hip"]
+SOURCES = ["capi.hip", "silero.hip", "silero_split.hip", "silero_h2.hip", "silero_stream.hip", "silero8k.hip", "silero_pack.hip", "frontend.hip", "fsmn.hip", "firered.hip", "marblenet.hip", "dfsmn.hip", "dfsmn_cfb.hip", "ingest.hip", "ragged.hip", "chunks.hip", "timestamps.hip", "prepare.hip"]
 # -fno-slp-vectorize: the SLP vectoriser is what turns pairs of scalar float adds / multiplies into v_pk_*_f32 with swizzled sources; the
 # CROSS-swizzled form gives wrong sums inside silero_encode_h2_kernel (profiles/r06_pk_hazard.txt) and is banned from
 # the product (tests/test_cabi_cpu.py::test_no_cross_swizzled_packed_f32_in_product_kernels).  A/B over the five BASELINE configs on one box

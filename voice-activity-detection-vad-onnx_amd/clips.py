@@ -13,6 +13,14 @@ from . import _lib
 from . import timestamps as _ts
 
 
+def pad_count(n, window, stride):
+    """How many samples `pad_to_window_grid` appends to a clip of n samples: a function of the three numbers alone, so that the layout of
+    a batch is known from its lengths (vadx.prepare)."""
+    if n > window:
+        return int(np.ceil((n - window) / stride)) * stride + window - n
+    return window - n
+
+
 def pad_to_window_grid(audio_i16, window, stride, noise=None):
     """Tail padding to the sliding-window grid with white noise at the RMS of the tail
     (FSMN/Inference_FSMN_VAD_ONNX.py:88-99).  `noise` = standard-normal samples (seeded by the

@@ -32,6 +32,13 @@ def _load(files, normalise=False):
     return [timestamps.normalise_audio(c) for c in clips] if normalise else clips
 
 
+def _ingest(files, device):
+    """device_ingest=True: the files' raw frames go up once and are down-mixed and resampled to 16 kHz there (audio_io.ingest_ragged)
+    -> (pcm on the device, clip_offsets, lengths): what an engine's `ragged_packed` takes.  16-bit PCM wav only."""
+    raws = [audio_io.read_wav_raw(f) for f in files]
+    return audio_io.ingest_ragged([r[0] for r in raws], [r[1] for r in raws], [r[2] for r in raws], 16000, device)
+
+
 def _detect_files(detect, clips, as_list, pad_noise):
     """`detect(clips, pad_noise) -> one result per clip` over the clips of a driver call: a list of files goes to the engine as it is,
     ONE ragged batch of clips of any lengths; a single file goes the way it always went, as a [1, N] array (`_grouped`)."""
@@ -145,12 +152,19 @@ def _save_speech(files, all_ts, sample_rate, path, single, device):
 def inference_fsmn(test_vad_audio="./vad_sample.wav", engine=None, save_timestamps_second="./timestamps_second.txt",
                    save_timestamps_indices="./timestamps_indices.txt", FUSION_THRESHOLD=0.3, MIN_SPEECH_DURATION=0.2,
                    SPEAKING_SCORE=0.5, SILENCE_SCORE=0.5, LOOK_BACKWARD=0.3, SNR_THRESHOLD=10.0,
-                   BACKGROUND_NOISE_dB_INIT=30.0, ONE_MINUS_SPEECH_THRESHOLD=1.0, pad_noise=None, echo=print, save_speech_audio=None):
-    """FSMN/Inference_FSMN_VAD_ONNX.py:66-260.  save_speech_audio: `_finish_speech`."""
+                   BACKGROUND_NOISE_dB_INIT=30.0, ONE_MINUS_SPEECH_THRESHOLD=1.0, pad_noise=None, echo=print, save_speech_audio=None,
+                   device_ingest=False):
+    """FSMN/Inference_FSMN_VAD_ONNX.py:66-260.  save_speech_audio: `_finish_speech`.
+    device_ingest (off by default): the files' raw frames are uploaded once; down-mix, resampling, peak normalisation, padding and
+    packing run on the device (`_ingest`, FsmnEngine.ragged_packed) -- the same timestamps, no per-clip host loop."""
     from . import fsmn
     engine = _engine_of(fsmn.FsmnEngine, engine)
     files, single = _as_list(test_vad_audio), not isinstance(test_vad_audio, (list, tuple))
-    clips = _load(files)
+    if device_ingest:
+        clips = engine.ragged_packed(*_ingest(files, engine.device), pad_noise=pad_noise, look_backward_s=LOOK_BACKWARD)
+        single_clips, pad_noise = False, None                   # one packed batch, its noise already in it
+    else:
+        clips, single_clips = _load(files), single
     echo("\nRunning the FSMN_VAD by ONNX Runtime.")
     t0 = time.time()
     kw = dict(fusion_threshold=FUSION_THRESHOLD, min_speech_duration=MIN_SPEECH_DURATION, look_backward_s=LOOK_BACKWARD,
@@ -158,10 +172,10 @@ def inference_fsmn(test_vad_audio="./vad_sample.wav", engine=None, save_timestam
               noise_init_dB=BACKGROUND_NOISE_dB_INIT, one_minus_speech_threshold=ONE_MINUS_SPEECH_THRESHOLD)
     # (the int16 clips as they are: `detect` widens each to float32 itself before its peak normalisation)
     if save_speech_audio is not None:
-        table = _table_files(lambda c, nz: engine.detect_table(c, pad_noise=nz, **kw), clips, not single, pad_noise)
+        table = _table_files(lambda c, nz: engine.detect_table(c, pad_noise=nz, **kw), clips, not single_clips, pad_noise)
         return _finish_speech(files, table, save_speech_audio, engine.device, save_timestamps_second, save_timestamps_indices, single,
                               time.time() - t0, echo)
-    all_ts = _detect_files(lambda c, nz: engine.detect(c, pad_noise=nz, **kw), clips, isinstance(test_vad_audio, (list, tuple)), pad_noise)
+    all_ts = _detect_files(lambda c, nz: engine.detect(c, pad_noise=nz, **kw), clips, not single_clips, pad_noise)
     elapsed = time.time() - t0
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
 
@@ -169,23 +183,30 @@ def inference_fsmn(test_vad_audio="./vad_sample.wav", engine=None, save_timestam
 def inference_firered(test_vad_audio="./vad_sample.wav", engine=None, save_timestamps_second="./timestamps_second.txt",
                       save_timestamps_indices="./timestamps_indices.txt", NORMALIZE_AUDIO=False, SMOOTH_WINDOW_SIZE=5,
                       SPEAKING_SCORE=0.4, MIN_SPEECH_FRAME=20, MAX_SPEECH_FRAME=2000, MIN_SILENCE_FRAME=20,
-                      MERGE_SILENCE_FRAME=5, EXTEND_SPEECH_FRAME=0, pad_noise=None, echo=print, save_speech_audio=None):
-    """FireRedVAD/Inference_FireRed_ONNX.py:523-613 (RUN_VAD).  save_speech_audio: `_finish_speech`."""
+                      MERGE_SILENCE_FRAME=5, EXTEND_SPEECH_FRAME=0, pad_noise=None, echo=print, save_speech_audio=None,
+                      device_ingest=False):
+    """FireRedVAD/Inference_FireRed_ONNX.py:523-613 (RUN_VAD).  save_speech_audio: `_finish_speech`.
+    device_ingest (off by default): as inference_fsmn's; NORMALIZE_AUDIO then runs on the device too."""
     from . import firered
     engine = _engine_of(firered.FireRedEngine, engine)
     files, single = _as_list(test_vad_audio), not isinstance(test_vad_audio, (list, tuple))
-    clips = _load(files, NORMALIZE_AUDIO)
+    if device_ingest:
+        clips = engine.ragged_packed(*_ingest(files, engine.device), pad_noise=pad_noise, normalize="rms" if NORMALIZE_AUDIO else None)
+        single_clips, pad_noise, n_samples = False, None, int(clips.lengths.sum())
+    else:
+        clips, single_clips = _load(files, NORMALIZE_AUDIO), single
+        n_samples = sum(len(c) for c in clips)
     echo("\nRunning the FireRedVAD by ONNX Runtime.")
     t0 = time.time()
     post = (SMOOTH_WINDOW_SIZE, SPEAKING_SCORE, MIN_SPEECH_FRAME, MAX_SPEECH_FRAME, MIN_SILENCE_FRAME,
             MERGE_SILENCE_FRAME, EXTEND_SPEECH_FRAME)
     table = None
     if save_speech_audio is not None:
-        table = _table_files(lambda c, nz: engine.detect_table(c, pad_noise=nz, post=post), clips, not single, pad_noise)
+        table = _table_files(lambda c, nz: engine.detect_table(c, pad_noise=nz, post=post), clips, not single_clips, pad_noise)
     else:
-        all_ts = _detect_files(lambda c, nz: engine.detect(c, pad_noise=nz, post=post), clips, isinstance(test_vad_audio, (list, tuple)), pad_noise)
+        all_ts = _detect_files(lambda c, nz: engine.detect(c, pad_noise=nz, post=post), clips, not single_clips, pad_noise)
     elapsed = time.time() - t0
-    echo(f"RTF: {elapsed / (sum(len(c) for c in clips) / 16000):.4f}")
+    echo(f"RTF: {elapsed / (n_samples / 16000):.4f}")
     if table is not None:
         return _finish_speech(files, table, save_speech_audio, engine.device, save_timestamps_second, save_timestamps_indices, single, elapsed, echo)
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
@@ -275,22 +296,28 @@ def inference_marblenet(test_vad_audio="./vad_sample.wav", engine=None, save_tim
                         save_timestamps_indices="./timestamps_indices.txt", NORMALIZE_AUDIO=False, SMOOTH_WINDOW_SIZE=3,
                         SPEAKING_SCORE=0.5, MIN_SPEECH_FRAME=10, MAX_SPEECH_FRAME=1000, MIN_SILENCE_FRAME=10,
                         MERGE_SILENCE_FRAME=3, EXTEND_SPEECH_FRAME=0, INPUT_AUDIO_LENGTH=None, pad_noise=None, echo=print,
-                        save_speech_audio=None):
-    """NVIDIA_.../Inference_NVIDIA_MarbleNet_VAD_ONNX.py:120-422 (dynamic axis: one window per clip).  save_speech_audio: `_finish_speech`."""
+                        save_speech_audio=None, device_ingest=False):
+    """NVIDIA_.../Inference_NVIDIA_MarbleNet_VAD_ONNX.py:120-422 (dynamic axis: one window per clip).  save_speech_audio: `_finish_speech`.
+    device_ingest (off by default): as inference_fsmn's, in either window mode; NORMALIZE_AUDIO then runs on the device too."""
     from . import marblenet
     engine = _engine_of(marblenet.MarbleNetEngine, engine)
     files, single = _as_list(test_vad_audio), not isinstance(test_vad_audio, (list, tuple))
-    clips = _load(files, NORMALIZE_AUDIO)
+    if device_ingest:
+        clips = engine.ragged_packed(*_ingest(files, engine.device), window_len=INPUT_AUDIO_LENGTH, pad_noise=pad_noise,
+                                     normalize="rms" if NORMALIZE_AUDIO else None)
+        single_clips, pad_noise = False, None
+    else:
+        clips, single_clips = _load(files, NORMALIZE_AUDIO), single
     echo("\nRunning the NVIDIA_VAD by ONNX Runtime.")
     t0 = time.time()
     post = (SMOOTH_WINDOW_SIZE, SPEAKING_SCORE, MIN_SPEECH_FRAME, MAX_SPEECH_FRAME, MIN_SILENCE_FRAME,
             MERGE_SILENCE_FRAME, EXTEND_SPEECH_FRAME)
     if save_speech_audio is not None:
-        table = _table_files(lambda c, nz: engine.detect_table(c, window_len=INPUT_AUDIO_LENGTH, pad_noise=nz, post=post), clips, not single, pad_noise)
+        table = _table_files(lambda c, nz: engine.detect_table(c, window_len=INPUT_AUDIO_LENGTH, pad_noise=nz, post=post), clips, not single_clips,
+                             pad_noise)
         return _finish_speech(files, table, save_speech_audio, engine.device, save_timestamps_second, save_timestamps_indices, single,
                               time.time() - t0, echo)
-    all_ts = _detect_files(lambda c, nz: engine.detect(c, window_len=INPUT_AUDIO_LENGTH, pad_noise=nz, post=post), clips,
-                           isinstance(test_vad_audio, (list, tuple)), pad_noise)
+    all_ts = _detect_files(lambda c, nz: engine.detect(c, window_len=INPUT_AUDIO_LENGTH, pad_noise=nz, post=post), clips, not single_clips, pad_noise)
     elapsed = time.time() - t0
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
 

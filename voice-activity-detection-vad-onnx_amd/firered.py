@@ -121,6 +121,11 @@ class FireRedEngine:
         (vadx.ragged.RaggedBatch), each padded with pad_noise row b.  device=None keeps it on the host."""
         return _ragged.RaggedBatch.from_clips(clips, self.L, self.L, pad_noise, None, self.device if device is True else device)
 
+    def ragged_packed(self, pcm, clip_offsets, lengths, pad_noise=None, normalize=None):
+        """`ragged` for clips that already lie in device memory (RaggedBatch.from_packed: padded and packed on the device, bit for bit what
+        `ragged` builds from the same clips and noise; normalize="rms" applies timestamps.normalise_audio on the way)."""
+        return _ragged.RaggedBatch.from_packed(pcm, clip_offsets, lengths, self.L, self.L, pad_noise, normalize, device=self.device)
+
     def run_ragged(self, rb):
         """RaggedBatch on this engine's grid -> probs f32 [sum W, odim, T]: rows win_first[b] .. win_first[b+1]-1 are clip b's windows
         (vadx_windows_gather, then the unchanged front-end and vadx_firered_run over sum W windows).  A host-only batch
@@ -137,8 +142,9 @@ class FireRedEngine:
         A list (or tuple) of 1-D clips takes the ragged route (`run_ragged`, one vadx_tracks_gather per channel: [B, max(n_frames, 1)],
         zeros past n_frames[b]); an array [B, N] the rectangular one (`run`: [B, n_frames], cut from the windows laid end to end).
         sample_rate: what a sample count means in frames and in seconds -- `detect` passes in_sample_rate, the AED driver 16 kHz."""
-        if isinstance(clips, (list, tuple)):
-            rb = self.ragged(clips, pad_noise)
+        if isinstance(clips, (list, tuple, _ragged.RaggedBatch)):
+            # (a RaggedBatch is packed already: `ragged`, or RaggedBatch.from_packed on the device)
+            rb = clips if isinstance(clips, _ragged.RaggedBatch) else self.ragged(clips, pad_noise)
             probs = self.run_ragged(rb)
             nf = np.minimum([valid_frame_count(int(n), sample_rate) for n in rb.lengths], rb.windows.astype(np.int64) * self.T)
             return (lambda k: gather_tracks(self.device, probs, self.odim * self.T, k * self.T, self.T, rb.win_first, nf),
@@ -289,7 +295,7 @@ class FireRedEngine:
         out, dec = track_segments(_vadpost.VadPostprocessor(*post, device=self.device), track, nf, durations)
         if not return_probs:
             return out
-        if isinstance(clips_i16, (list, tuple)):
+        if isinstance(clips_i16, (list, tuple, _ragged.RaggedBatch)):
             return out, [track[b, :nf[b]] for b in range(len(nf))], [dec[b, :nf[b]] for b in range(len(nf))]
         return (out, track, dec) if track.shape[1] else (out, track)      # an array without a valid frame: no decisions are returned
 

@@ -238,6 +238,15 @@ class FsmnEngine:
         return _ragged.RaggedBatch.from_clips(clips, self.L, stride, pad_noise, _prep(normalize),
                                               self.device if device is True else device)
 
+    def ragged_packed(self, pcm, clip_offsets, lengths, pad_noise=None, normalize=True, look_backward_s=0.3):
+        """`ragged` for clips that already lie in device memory (RaggedBatch.from_packed: normalised, padded and packed on the device, bit
+        for bit what `ragged` builds from the same clips and noise)."""
+        if self.long_windows and self.L % 8:
+            raise ValueError(f"input_audio_length={self.L} must be a multiple of 8 for a ragged batch: the window gather moves 16-byte runs")
+        stride = (self._long_grid(look_backward_s) if self.long_windows else self.grid(look_backward_s))[1]
+        return _ragged.RaggedBatch.from_packed(pcm, clip_offsets, lengths, self.L, stride, pad_noise, "peak" if normalize else None,
+                                               device=self.device)
+
     def flags_ragged(self, rb, *, order=None, return_noise=False, look_backward_s=0.3, speaking_score=0.5, silence_score=0.5,
                      snr_threshold=10.0, noise_init_dB=30.0, one_minus_speech_threshold=1.0):
         """`flags` for a RaggedBatch on this engine's grid: one gather, the unchanged front-end over sum(W) windows, one
@@ -292,7 +301,9 @@ class FsmnEngine:
         A LIST (or tuple) of 1-D clips of any lengths runs as one ragged batch (`flags_ragged`); clip b's result is that of
         `detect(clip_b[None, :], pad_noise=row_b[None, :])[0]`."""
         look_backward_s = loop_kw.get("look_backward_s", 0.3)
-        if isinstance(clips_i16, (list, tuple)):
+        if isinstance(clips_i16, _ragged.RaggedBatch):          # packed already (`ragged`, or RaggedBatch.from_packed on the device)
+            flags, nflags = self.flags_ragged(clips_i16, **loop_kw)
+        elif isinstance(clips_i16, (list, tuple)):
             flags, nflags = self.flags_ragged(self.ragged(clips_i16, pad_noise, normalize, look_backward_s), **loop_kw)
         else:
             stride = (self._long_grid(look_backward_s) if self.long_windows else self.grid(look_backward_s))[1]
@@ -310,7 +321,9 @@ class FsmnEngine:
         vadx.chunks.collect_chunks_batch (sample rows at 16 kHz, by `sample_rule`)."""
         from . import tstable
         look_backward_s = loop_kw.get("look_backward_s", 0.3)
-        if isinstance(clips_i16, (list, tuple)):
+        if isinstance(clips_i16, _ragged.RaggedBatch):          # packed already (`ragged`, or RaggedBatch.from_packed on the device)
+            flags, nflags = self.flags_ragged(clips_i16, **loop_kw)
+        elif isinstance(clips_i16, (list, tuple)):
             flags, nflags = self.flags_ragged(self.ragged(clips_i16, pad_noise, normalize, look_backward_s), **loop_kw)
         else:
             stride = (self._long_grid(look_backward_s) if self.long_windows else self.grid(look_backward_s))[1]

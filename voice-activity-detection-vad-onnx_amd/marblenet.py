@@ -281,6 +281,10 @@ class MarbleNetEngine:
                              "engine was constructed with another `blocks` layout -- pass equal-length clips as a [B, N] array")
         rate = self.in_sample_rate
         pp = _vadpost.VadPostprocessor(*post, frame_shift_s=OUTPUT_FRAME_SHIFT_S, frame_length_s=None, device=self.device)
+        if isinstance(clips_i16, (_ragged.RaggedBatch, _ragged.RaggedFrames)):        # packed already (from_clips / from_packed): as a list
+            track, nf, lengths = self._batch_track(clips_i16)
+            out, dec = track_segments(pp, track, nf, [int(n) / rate for n in lengths])
+            return (out, track, dec, nf) if return_probs else out
         if not as_list:
             B, n = np.asarray(clips_i16).shape
             L = min(rate * 3600, n) if window_len is None else int(window_len)
@@ -326,6 +330,9 @@ class MarbleNetEngine:
                              "this engine was constructed with another `blocks` layout -- pass equal-length clips as a [B, N] array")
         rate = self.in_sample_rate
         pp = _vadpost.VadPostprocessor(*post, frame_shift_s=OUTPUT_FRAME_SHIFT_S, frame_length_s=None, device=self.device)
+        if isinstance(clips_i16, (_ragged.RaggedBatch, _ragged.RaggedFrames)):
+            track, nf, lengths = self._batch_track(clips_i16)
+            return track_table(pp, track, nf, [int(n) / rate for n in lengths], rate, sample_rule)[0]
         if not as_list:
             B, n = np.asarray(clips_i16).shape
             L = min(rate * 3600, n) if window_len is None else int(window_len)
@@ -349,12 +356,33 @@ class MarbleNetEngine:
         the clips padded to their own window grids (vadx.ragged.RaggedBatch), every window through the unchanged front-end and
         `run_features`.  Either way one vadx_tracks_gather, and the track is the input of one vadx_vadpost launch."""
         if window_len is None:
-            rf = self.ragged(clips)
+            return self._batch_track(self.ragged(clips))
+        L = int(window_len)
+        return self._batch_track(_ragged.RaggedBatch.from_clips(clips, L, L, pad_noise, None, self.device))
+
+    def ragged_packed(self, pcm, clip_offsets, lengths, window_len=None, pad_noise=None, normalize=None):
+        """The batch `detect` builds from a list of clips, for clips that already lie in device memory: a RaggedFrames (window_len None,
+        the dynamic axis) or a RaggedBatch on the grid window = stride = window_len, packed on the device (`from_packed`);
+        normalize="rms" applies timestamps.normalise_audio on the way.  `detect` / `detect_table` take the result as they take a list."""
+        if window_len is None:
+            return _ragged.RaggedFrames.from_packed(pcm, clip_offsets, lengths, normalize, device=self.device)
+        L = int(window_len)
+        return _ragged.RaggedBatch.from_packed(pcm, clip_offsets, lengths, L, L, pad_noise, normalize, device=self.device)
+
+    def _batch_track(self, batch):
+        """`_list_track` of a batch that is packed already: a RaggedFrames (dynamic axis) or a RaggedBatch on a grid of window = stride = L
+        (from_clips or from_packed: the PCM of a from_packed batch was never on the host)."""
+        if isinstance(batch, _ragged.RaggedFrames):
+            rf = batch
             _, s1, _ = self.run_ragged(rf)
             nf = (rf.enc_frames - 1).astype(np.int32)           # valid_b = min(signal_len, T1_b) = T1_b - 1
             return gather_tracks(self.device, s1, 1, 0, 1, rf.enc_first, nf), nf, rf.lengths
-        L = int(window_len)
-        rb = _ragged.RaggedBatch.from_clips(clips, L, L, pad_noise, None, self.device)
+        rb = batch
+        L = rb.window
+        if rb.stride != L:
+            raise ValueError(f"the batch was packed for windows of {rb.window} every {rb.stride} samples, MarbleNet cuts {L} every {L}")
+        if rb.device is None:
+            rb.to(self.device)
         s0, s1, slen = self.run_features(self.frontend(L).logmel(rb.gather(), 1, L))
         T1 = int(s1.shape[1])
         valid = min(slen, T1)

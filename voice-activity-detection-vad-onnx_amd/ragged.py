@@ -11,6 +11,10 @@ Tables (include/vadx.h, "Ragged batches"):
     win_src   [sum W] sample offset of every window in `pcm`: clip_off[b] + k * stride
     order     [B]    clips by window count, longest first (stable): the launch order of one-workgroup-per-clip kernels
 
+`RaggedBatch.from_packed` / `RaggedFrames.from_packed` build the same objects from clips that already lie in DEVICE memory (the output of
+vadx.chunks.collect_chunks_batch or audio_io.ingest_ragged): normalisation, padding and packing run there (vadx.prepare), bit for bit
+what `from_clips` does on the host, and the tables -- functions of the lengths alone -- come from the same code.
+
 `RaggedPairs` is the batch of DFSMN's near / far pairs: two packed vectors on one grid of odd window and stride (no 16-byte runs:
 vadx_windows_gather_any), sharing win_first and win_src.
 
@@ -26,6 +30,13 @@ from .clips import pad_to_window_grid
 ALIGN = 8            # samples: window and stride are multiples of it, so every clip starts on a 16-byte boundary of the packed vector
 
 
+def check_grid(window, stride):
+    window, stride = int(window), int(stride)
+    if window < ALIGN or window % ALIGN or stride < ALIGN or stride % ALIGN:
+        raise ValueError(f"window={window} and stride={stride} must be positive multiples of {ALIGN} samples")
+    return window, stride
+
+
 class RaggedBatch:
     """Fields: pcm int16 [total], lengths [B] (original sample counts, host), windows int32 [B] (host), win_first int32 [B+1],
     win_src int64 [sum W], order int32 [B]; clip_off int64 [B] (host) = where each padded clip starts in pcm, padded_lengths [B].
@@ -37,9 +48,7 @@ class RaggedBatch:
         """clips: list of 1-D int16 arrays (or whatever `prep` turns into one: FSMN passes timestamps.normalize_to_int16);
         pad_noise: None (numpy's global RNG, as the reference) or standard-normal rows, a list or a matrix -- clip b uses the first
         pad_b samples of row b."""
-        window, stride = int(window), int(stride)
-        if window < ALIGN or window % ALIGN or stride < ALIGN or stride % ALIGN:
-            raise ValueError(f"window={window} and stride={stride} must be positive multiples of {ALIGN} samples")
+        window, stride = check_grid(window, stride)
         if len(clips) == 0:
             raise ValueError("a ragged batch needs at least one clip")
         if pad_noise is not None and len(pad_noise) < len(clips):
@@ -55,14 +64,24 @@ class RaggedBatch:
                 raise ValueError(f"clip {b} must be int16 (after prep), got {a.dtype}")
             rows.append(pad_to_window_grid(a, window, stride, None if pad_noise is None else np.asarray(pad_noise[b]).reshape(-1)))
         self = cls()
+        self._set_grid(lengths, [len(r) for r in rows], window, stride)
+        pcm = np.concatenate(rows)
+        self.pcm_host = pcm
+        self.device = None
+        self.pcm, self.win_first, self.win_src, self.order = pcm, self.win_first_host, self.win_src_host, self.order_host
+        if device is not None:
+            self.to(device)
+        return self
+
+    def _set_grid(self, lengths, padded_lengths, window, stride):
+        """Every table of the batch: a function of the clips' lengths before and after padding, and of the grid."""
         self.window, self.stride = window, stride
         self.lengths = np.asarray(lengths, dtype=np.int64)
-        self.padded_lengths = np.asarray([len(r) for r in rows], dtype=np.int64)
+        self.padded_lengths = np.asarray(padded_lengths, dtype=np.int64)
         self.windows = ((self.padded_lengths - window) // stride + 1).astype(np.int32)
         # a padded clip is (W-1) * stride + window samples, a multiple of 8 like both terms: laid end to end, every clip (and so every
         # window) starts on a 16-byte boundary with no filler between clips
         self.clip_off = np.concatenate([[0], np.cumsum(self.padded_lengths)[:-1]]).astype(np.int64)
-        pcm = np.concatenate(rows)
         nwin = int(self.windows.sum())
         if nwin >= 2 ** 31:
             raise ValueError(f"{nwin} windows do not fit the int32 window tables")
@@ -71,11 +90,50 @@ class RaggedBatch:
         k = np.arange(nwin, dtype=np.int64) - np.repeat(self.win_first_host[:-1].astype(np.int64), self.windows)
         self.win_src_host = np.repeat(self.clip_off, self.windows) + k * stride
         self.order_host = np.argsort(-self.windows.astype(np.int64), kind="stable").astype(np.int32)
-        self.pcm_host = pcm
-        self.device = None
-        self.pcm, self.win_first, self.win_src, self.order = pcm, self.win_first_host, self.win_src_host, self.order_host
-        if device is not None:
-            self.to(device)
+
+    @classmethod
+    def from_packed(cls, pcm, clip_offsets, lengths, window, stride, pad_noise=None, normalize=None, target_rms=8192.0, device=None,
+                    out=None):
+        """The batch `from_clips` builds, from clips that already lie in device memory (vadx.prepare; include/vadx.h, "Prepare"): bit for
+        bit the same `pcm` and tables, and the PCM never visits the host.
+        pcm: 1-D int16 tensor on the device, clip b = lengths[b] samples from element clip_offsets[b] (any element: what
+        chunks.collect_chunks_batch or audio_io.ingest_ragged return); clip_offsets / lengths: host arrays or device tensors (device
+        tensors are read back once, 16 * B bytes -- the only synchronisation).  normalize: None, "peak" (timestamps.normalize_to_int16 of
+        the float32 clip: FSMN's prep) or "rms" (timestamps.normalise_audio with `target_rms`).  pad_noise: None (numpy's global RNG, one
+        draw of pad_b per clip in clip order, as the reference), standard-normal host rows (clip b uses the first pad_b samples of row b)
+        or a device float64 matrix [B or 1, >= the longest pad], used where it lies.  out: an int16 device tensor to write the packed
+        vector into (16-byte aligned, long enough).  `pcm_host` is None; `records` holds per clip (scale, tail RMS, status bits, 0) on the
+        device and `check()` reads the status bits (a clip whose offsets lie outside `pcm` is zeros and says so there)."""
+        from . import _lib, prepare
+        from .clips import pad_count
+        t = _lib.require_gpu()
+        window, stride = check_grid(window, stride)
+        src_off, lengths = prepare.read_tables(clip_offsets, lengths)
+        if lengths.shape[0] == 0:
+            raise ValueError("a ragged batch needs at least one clip")
+        if src_off.shape[0] != lengths.shape[0]:
+            raise ValueError(f"{src_off.shape[0]} clip_offsets for {lengths.shape[0]} lengths")
+        if int(lengths.min()) < 1:
+            raise ValueError(f"clip {int(np.argmin(lengths))} is empty")
+        pcm = pcm.to(device) if device is not None else pcm
+        pads = np.asarray([pad_count(int(n), window, stride) for n in lengths], dtype=np.int64)
+        self = cls()
+        self._set_grid(lengths, lengths + pads, window, stride)
+        self.device = pcm.device
+        noise, noise_off = prepare.device_noise(pads, pad_noise, self.device)
+        dst_off = np.concatenate([self.clip_off, [int(self.padded_lengths.sum())]])
+        self.prepared = prepare.prepare_device(pcm.contiguous(), src_off, lengths, dst_off, window, stride, normalize, target_rms, noise, noise_off,
+                                               out=out)
+        self.pcm, self.records, self.pcm_host = self.prepared.pcm, self.prepared.records, None
+        self.win_first = t.from_numpy(self.win_first_host).to(self.device)
+        self.win_src = t.from_numpy(self.win_src_host).to(self.device)
+        self.order = t.from_numpy(self.order_host).to(self.device)
+        return self
+
+    def check(self):
+        """Raise ValueError when the device refused a clip of a `from_packed` batch (one small read-back)."""
+        if getattr(self, "prepared", None) is not None:
+            self.prepared.check()
         return self
 
     def to(self, device):
@@ -93,7 +151,10 @@ class RaggedBatch:
         return int(self.lengths.shape[0])
 
     def padded(self, b):
-        """Clip b as it was packed (host int16 [padded_lengths[b]]) = pad_to_window_grid of the prepped clip."""
+        """Clip b as it was packed (host int16 [padded_lengths[b]]) = pad_to_window_grid of the prepped clip (a `from_packed` batch keeps
+        no host copy: its slice is downloaded)."""
+        if self.pcm_host is None:
+            return self.pcm[int(self.clip_off[b]):int(self.clip_off[b] + self.padded_lengths[b])].cpu().numpy()
         return self.pcm_host[self.clip_off[b]:self.clip_off[b] + self.padded_lengths[b]]
 
     def gather(self):
@@ -244,7 +305,18 @@ class RaggedFrames:
                 raise ValueError(f"clip {b} is empty")
             rows.append(a)
         self = cls()
-        self.lengths = np.asarray([len(r) for r in rows], dtype=np.int64)
+        self._set_tables([len(r) for r in rows])
+        self.pcm_host = np.concatenate(rows)
+        self.device = None
+        for name in self.TABLES:
+            setattr(self, name, getattr(self, name + "_host"))
+        if device is not None:
+            self.to(device)
+        return self
+
+    def _set_tables(self, lengths):
+        """Every table of the batch: a function of the clips' lengths."""
+        self.lengths = np.asarray(lengths, dtype=np.int64)
         if int(self.lengths.max()) >= 2 ** 31:
             raise ValueError("a clip of 2^31 samples or more does not fit the int32 clip_len table")
         self.clip_len_host = self.lengths.astype(np.int32)
@@ -254,16 +326,43 @@ class RaggedFrames:
         self.mel_first_host, self.enc_first_host = _prefix(self.mel_frames, "log-mel frames"), _prefix(self.enc_frames, "encoder frames")
         fe_tiles, enc_tiles = (self.mel_frames + FE_TILE - 1) // FE_TILE, (self.enc_frames + ENC_TILE - 1) // ENC_TILE
         self.fe_tile_first_host, self.enc_tile_first_host = _prefix(fe_tiles, "front-end tiles"), _prefix(enc_tiles, "encoder tiles")
-        ids = np.arange(len(rows), dtype=np.int32)
+        ids = np.arange(len(self.lengths), dtype=np.int32)
         self.fe_tile_clip_host, self.enc_tile_clip_host = np.repeat(ids, fe_tiles), np.repeat(ids, enc_tiles)
-        self.pcm_host = np.concatenate(rows)
         self.n_mel, self.n_enc = int(self.mel_first_host[-1]), int(self.enc_first_host[-1])
         self.n_fe_tiles, self.n_enc_tiles = int(self.fe_tile_first_host[-1]), int(self.enc_tile_first_host[-1])
-        self.device = None
-        for name in self.TABLES:
-            setattr(self, name, getattr(self, name + "_host"))
-        if device is not None:
-            self.to(device)
+
+    @classmethod
+    def from_packed(cls, pcm, clip_offsets, lengths, normalize=None, target_rms=8192.0, device=None, out=None):
+        """The batch `from_clips` builds, from clips that already lie in device memory (vadx.prepare): the PCM is repacked end to end on the
+        device -- RMS-normalised on the way with normalize="rms" (timestamps.normalise_audio, bit for bit) -- and never visits the host.
+        pcm, clip_offsets, lengths, out: as RaggedBatch.from_packed; `pcm_host` is None."""
+        from . import _lib, prepare
+        t = _lib.require_gpu()
+        if normalize not in (None, "rms"):
+            raise ValueError(f"normalize must be None or 'rms', got {normalize!r}")
+        src_off, lengths = prepare.read_tables(clip_offsets, lengths)
+        if lengths.shape[0] == 0:
+            raise ValueError("a ragged batch needs at least one clip")
+        if src_off.shape[0] != lengths.shape[0]:
+            raise ValueError(f"{src_off.shape[0]} clip_offsets for {lengths.shape[0]} lengths")
+        if int(lengths.min()) < 1:
+            raise ValueError(f"clip {int(np.argmin(lengths))} is empty")
+        pcm = pcm.to(device) if device is not None else pcm
+        self = cls()
+        self._set_tables(lengths)
+        self.device = pcm.device
+        dst_off = np.concatenate([self.clip_off_host, [int(self.lengths.sum())]])
+        # no grid: every clip's room is its own length, so nothing is filled and the grid arguments only have to be well formed
+        self.prepared = prepare.prepare_device(pcm.contiguous(), src_off, lengths, dst_off, ALIGN, ALIGN, normalize, target_rms, None, None, out=out)
+        self.pcm, self.records, self.pcm_host = self.prepared.pcm, self.prepared.records, None
+        for name in self.TABLES[1:]:
+            setattr(self, name, t.from_numpy(getattr(self, name + "_host")).to(self.device))
+        return self
+
+    def check(self):
+        """Raise ValueError when the device refused a clip of a `from_packed` batch (one small read-back)."""
+        if getattr(self, "prepared", None) is not None:
+            self.prepared.check()
         return self
 
     def to(self, device):
