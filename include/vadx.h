@@ -60,7 +60,9 @@ extern "C" {
  *     vadx_marblenet_stream_state_bytes, vadx_marblenet_stream_workspace_bytes, vadx_marblenet_stream_tick, vadx_frontend_logmel_stream; then
  *     cutting the speech out on the device: vadx_chunks_plan_bytes, vadx_chunks_plan, vadx_chunks_copy; then timestamps on the device:
  *     vadx_timestamps_flags, vadx_timestamps_frames, vadx_timestamps_samples; then preparing a ragged batch on the device:
- *     vadx_ingest_pcm16_ragged, vadx_prepare_workspace_bytes, vadx_prepare_stats, vadx_prepare_scale, vadx_prepare_write.
+ *     vadx_ingest_pcm16_ragged, vadx_prepare_workspace_bytes, vadx_prepare_stats, vadx_prepare_scale, vadx_prepare_write; then Silero over
+ *     ragged batches: vadx_silero_ragged, vadx_silero_ragged_workspace_bytes, vadx_silero_encode_ragged, vadx_silero_encode_ragged_pcm16,
+ *     vadx_silero_recur_ragged, vadx_silero_clips_ragged, vadx_silero_segments_ragged.
  *     A caller that needs them checks for the symbols (dlsym), not for a number. */
 #define VADX_ABI_VERSION 10
 
@@ -215,6 +217,54 @@ int vadx_silero_segments(const float *probs, int batch, int steps, const int64_t
  * The underflow side needs no protocol: pack_host rebalances layers whose weights sit outside [2^-10, 2^7) by exact powers of two
  * (csrc/rebalance.h) and marks a blob with a weight tensor wholly below 2^-14 as unusable for this arithmetic (flag bit 1 on a launch). */
 int vadx_silero_range_flag(const float *packed, int reset, uint32_t *flag_host, float *amax_host, void *stream);
+
+/* Silero over a RAGGED batch (16 kHz network): clips of any lengths in ONE packed source vector (float32 on the +-1 scale, or int16 PCM
+ * scaled while staging as vadx_silero_encode_pcm16 does), scored in one encoder and one recurrent launch whose work follows the clips'
+ * own window counts T_b = ceil(len_b / 512) instead of batch x the longest clip's.  The host sorts the clips by T_b (descending, stable)
+ * and takes sixteen at a time -- one MFMA column tile -- as a GROUP; slot s = 16 g + i is column i of group g.  A group runs T_g = the
+ * window count of its first slot; its gx tiles (32 KB each) lie CONSECUTIVELY in the workspace from tile gx_first[g] (the rectangular
+ * layout is window-major).  The encoder's workgroups find their work in wg_tab: one entry per (group, run of VADX_SILERO_RAGGED_RUN
+ * consecutive windows), ordered run-major over the groups that still have that run, read with uniform loads -- no search.
+ * Per slot the window is read as the rectangular kernel reads a clip of n_samples = slot_len: zero beyond the clip's own end, reflect
+ * pad over that; an empty slot (slot_clip = -1, behind the last clip of a partial group) stages zeros.  A slot may start at any element
+ * of the source; one that does not start on a multiple of four elements is loaded element by element, with the same result.
+ * Scores: one packed float32 vector [probs_first[clips]], clip b's T_b scores from probs_first[b] (the caller's clip order); a clip's
+ * LSTM state stops changing behind its own last window, so state_n [2][clips][128] holds every clip's state after its last window.
+ * The device trusts no slot: one whose [slot_off, slot_off + slot_len) leaves [0, n_src) is not read at all, its scores are NaN,
+ * bit 0 of *status is raised (the caller zeroes the word), and no other clip's result changes.  The remaining tables are functions of
+ * the lengths (vadx.ragged.RaggedClips._set_tables writes them) and are the caller's contract, as a rectangular call's batch and steps. */
+#define VADX_SILERO_RAGGED_RUN 4                /* windows per wg_tab entry = the fp16 x 2 encoder's tiles per workgroup (H2_NSUB) */
+typedef struct vadx_silero_ragged {             /* every pointer: device memory */
+    const int64_t *slot_off;                    /* [16 groups] first element of the slot's clip in the source vector (0: empty slot) */
+    const int32_t *slot_len;                    /* [16 groups] its samples (0: empty slot) */
+    const int32_t *slot_clip;                   /* [16 groups] the caller's clip index, -1: empty slot */
+    const int32_t *gx_first;                    /* [groups + 1] prefix of T_g, in gx tiles */
+    const int32_t *grp_min_len;                 /* [groups] the shortest slot_len of a full group, 0 for a partial one: windows that end below it
+                                                   are covered by every clip of the group (the encoder's vector staging; the device takes
+                                                   the smaller of this and what its own slot checks leave) */
+    const int32_t *wg_tab;                      /* [n_runs][2] (group, run) */
+    const int64_t *probs_first;                 /* [clips + 1] prefix of T_b in the caller's clip order */
+    uint32_t *status;                           /* [1] bit 0: a slot lay outside the source vector */
+    int32_t clips, groups, n_runs, tiles;       /* tiles = gx_first[groups] */
+} vadx_silero_ragged;
+size_t vadx_silero_ragged_workspace_bytes(int64_t tiles);          /* tiles x 32 KB */
+/* The halves of vadx_silero_clips_ragged (no range protocol of their own, as vadx_silero_encode / _recur).  n_src = elements of `src`.
+ * cfg->ext.sample_rate = 8000 is refused: the 8 kHz network has no ragged encoder.  A workspace below
+ * vadx_silero_ragged_workspace_bytes(rg->tiles) returns VADX_ENOSPACE. */
+int vadx_silero_encode_ragged(const float *packed, const float *src, int64_t n_src, const vadx_silero_ragged *rg,
+                              void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg);
+int vadx_silero_encode_ragged_pcm16(const float *packed, const int16_t *src, float scale, int64_t n_src, const vadx_silero_ragged *rg,
+                                    void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg);
+int vadx_silero_recur_ragged(const float *packed, const void *workspace, size_t workspace_bytes, int64_t n_src,
+                             const vadx_silero_ragged *rg, float *probs, float *state_n, void *stream, const vadx_silero_cfg *cfg);
+/* encode then recur; src_int16 != 0: `src` is int16 PCM scaled by `scale`, otherwise float32 (scale ignored).  state_n may be NULL. */
+int vadx_silero_clips_ragged(const float *packed, const void *src, int src_int16, float scale, int64_t n_src,
+                             const vadx_silero_ragged *rg, float *probs, float *state_n, void *workspace, size_t workspace_bytes,
+                             void *stream, const vadx_silero_cfg *cfg);
+/* vadx_silero_segments on the packed scores: clip b's row starts at probs_first[b] and has probs_first[b + 1] - probs_first[b] windows
+ * (of which ceil(n_samples[b] / window) are read at most).  Same tables out. */
+int vadx_silero_segments_ragged(const float *probs, const int64_t *probs_first, int batch, const int64_t *n_samples,
+                                const vadx_silero_seg_params *params, int64_t *segments, int32_t *counts, int cap, void *stream);
 
 /* Streaming Silero: S live streams advance by `windows` 512-sample windows per call (256 at 8 kHz), each stream's context, LSTM state and VADIterator
  * machine kept in a device RECORD (vadx_silero_stream_state_bytes(S) bytes).  The record is opaque except that

@@ -66,6 +66,12 @@ class SileroCfg(C.Structure):
     _fields_ = [("arithmetic", C.c_int32), ("sample_rate", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class SileroRagged(C.Structure):
+    """vadx_silero_ragged (include/vadx.h): the tables of a ragged Silero batch (device pointers) and their counts"""
+    _fields_ = [(k, C.c_void_p) for k in ("slot_off", "slot_len", "slot_clip", "gx_first", "grp_min_len", "wg_tab", "probs_first", "status")] + \
+               [(k, C.c_int32) for k in ("clips", "groups", "n_runs", "tiles")]
+
+
 ARITH = {"auto": 0, "f32": 1, "split": 2, "bf16x3": 2, "h2": 3, "f16x2": 3}       # VADX_ARITH_*
 
 
@@ -187,6 +193,12 @@ SIGNATURES = {
     "vadx_silero_stream_workspace_bytes": (_Z, [_I, _I]),
     "vadx_silero_stream_run": (_I, [_P, C.POINTER(SileroIterParams), _P, _I, C.c_float, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P,
                                     _P, _Z, _P, _P]),
+    "vadx_silero_ragged_workspace_bytes": (_Z, [_L]),
+    "vadx_silero_encode_ragged": (_I, [_P, _P, _L, C.POINTER(SileroRagged), _P, _Z, _P, _P]),
+    "vadx_silero_encode_ragged_pcm16": (_I, [_P, _P, C.c_float, _L, C.POINTER(SileroRagged), _P, _Z, _P, _P]),
+    "vadx_silero_recur_ragged": (_I, [_P, _P, _Z, _L, C.POINTER(SileroRagged), _P, _P, _P, _P]),
+    "vadx_silero_clips_ragged": (_I, [_P, _P, _I, C.c_float, _L, C.POINTER(SileroRagged), _P, _P, _P, _Z, _P, _P]),
+    "vadx_silero_segments_ragged": (_I, [_P, _P, _I, _P, C.POINTER(SileroSegParams), _P, _P, _I, _P]),
     "vadx_frontend_packed_floats": (_Z, [C.POINTER(FrontendCfg)]),
     "vadx_frontend_pack_host": (_I, [C.POINTER(FrontendCfg), _P, _P, _I, _P, _P, _P]),
     "vadx_frontend_fold_kind": (_I, [C.POINTER(FrontendCfg), _P, _P, _I]),

@@ -148,10 +148,13 @@ __device__ __forceinline__ f32x4 gemm_chain(const float *act, int lda, const flo
 }
 
 
-template <typename SampleT>
+// RG (a ragged batch, silero_common.h): the tile is (group, window) of the workgroup table -- RG_RUN workgroups per entry, one per window
+// of the run --, the sixteen slots are staged by stage_ragged and the group's gx tiles lie consecutively; everything behind phase 0 is the
+// rectangular kernel's code.
+template <typename SampleT, bool RG = false>
 __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
     const float *__restrict__ P, const SampleT *__restrict__ audio, float in_scale, long long n_samples,
-    long long row_stride, long long origin, int B, int G, int T, int Gws, int g0, float *__restrict__ gx) {
+    long long row_stride, long long origin, int B, int G, int T, int Gws, int g0, float *__restrict__ gx, const RgArg<RG> rg) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *X = lds, *V = lds, *A1 = lds;           // one region, one tenant per phase
     float *A3 = lds + A3_OFF, *A4 = lds + A4_OFF;
@@ -159,13 +162,22 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = lane >> 4, i = lane & 15;
-    const int grp = blockIdx.x % G, t = blockIdx.x / G;
+    int grp = blockIdx.x % G, t = blockIdx.x / G;
+    if constexpr (RG) {
+        const int ent = blockIdx.x / RG_RUN;
+        grp = rg.t.wg_tab[2 * ent];
+        t = rg.t.wg_tab[2 * ent + 1] * RG_RUN + blockIdx.x % RG_RUN;
+        if (t >= rg.t.gx_first[grp + 1] - rg.t.gx_first[grp]) return;      // (uniform) the group's last run is a partial one
+    }
 
     const bool fold = P[OFF_FOLD] != 0.f;      // uniform: the basis has the DFT symmetries -> folded STFT pass
     // ---------------- phase 0: copy the 16 windows (576 samples each) + right reflect pad of 64
     // (folded pass: even / odd samples go to separate planes of the clip row)
     auto xslot = [fold](int pp) { return fold ? (pp & 1) * X_ODD + (pp >> 1) : pp; };
-    {
+    if constexpr (RG) {
+        (void)xslot;
+        stage_ragged<SampleT, ENC_THREADS>(X, fold, audio, in_scale, rg, grp, (long long)t * 512 + origin, tid);
+    } else {
         const long long base = (long long)t * 512 + origin;
         const bool vec_ok = ((row_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(audio) & (SampleIO<SampleT>::VEC_ALIGN - 1)) == 0) && n_samples >= 4;
         // Work item e = (clip c, float4 p/4) of the 16 x 576-sample tile.  In the normal case every lane loads its
@@ -505,7 +517,9 @@ __global__ __launch_bounds__(ENC_THREADS, 6) void silero_encode_kernel(
                 for (int g = 0; g < 4; ++g) wcur[g] = wnxt[g];
             }
         }
-        float *dst = gx + ((size_t)t * Gws + g0 + grp) * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
+        size_t tile = (size_t)t * Gws + g0 + grp;
+        if constexpr (RG) tile = (size_t)rg.t.gx_first[grp] + t;
+        float *dst = gx + tile * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
 #pragma unroll
         for (int g = 0; g < 4; ++g)
             *reinterpret_cast<f32x4 *>(dst + g * 256) = acc[g][0];
@@ -517,10 +531,14 @@ constexpr int HS_LD = 136;                       // h [16 clips][128] (+8 pad: c
 constexpr int LSTM_LDS_FLOATS = 2 * 16 * HS_LD + 2 * 8 * 16;
 constexpr int LSTM_THREADS = 512;
 
+// RG (a ragged batch): the workgroup walks the T_g consecutive gx tiles of its group; column n is the clip of slot 16 grp + n (B = the
+// batch's clips, b = the caller's clip index), whose T_b scores go to its own row of the packed vector and whose h / c stop changing at
+// t = T_b.  A refused slot's row is NaN.
+template <bool RG = false>
 __global__ __launch_bounds__(LSTM_THREADS, 2) void silero_lstm_kernel(
     const float *__restrict__ P, const float *__restrict__ gx, const float *__restrict__ state0,
     int B, int G, int T, float *__restrict__ probs, long long probs_stride,
-    float *__restrict__ state_n) {
+    float *__restrict__ state_n, const RgArg<RG> rg) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *Hs = lds;                              // [2][16][HS_LD]
     float *part = lds + 2 * 16 * HS_LD;           // [2][8][16]
@@ -528,8 +546,26 @@ __global__ __launch_bounds__(LSTM_THREADS, 2) void silero_lstm_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = lane >> 4, n = lane & 15;
     const int grp = blockIdx.x;
-    const long long b = (long long)grp * 16 + n;
-    const bool bvalid = b < B;
+    long long b = (long long)grp * 16 + n;
+    bool bvalid = b < B;
+    int Tb = T;                                   // RG: the column's own window count
+    bool refused = false;
+    float *prow = nullptr;                        // RG: the clip's row of the packed scores
+    size_t gx0 = (size_t)grp, gstep_tiles = (size_t)G;
+    if constexpr (RG) {
+        const int clip = rg_clip(rg, grp * 16 + n);
+        long long o_;
+        int l_;
+        refused = !rg_slot(rg, grp * 16 + n, o_, l_);
+        T = rg.t.gx_first[grp + 1] - rg.t.gx_first[grp];
+        gx0 = (size_t)rg.t.gx_first[grp];
+        gstep_tiles = 1;
+        bvalid = clip >= 0;
+        b = bvalid ? clip : 0;
+        Tb = bvalid ? min((int)(rg.t.probs_first[b + 1] - rg.t.probs_first[b]), T) : 0;
+        prow = probs + rg.t.probs_first[b];
+        if (refused && wave == 0 && q == 0) atomicOr(rg.t.status, 1u);
+    }
     const int u0 = wave * 16 + 4 * q;             // this lane's 4 hidden units
 
     // W_hh rows of this wave's 4 gate tiles, resident for the whole clip: 128 VGPRs
@@ -554,8 +590,8 @@ __global__ __launch_bounds__(LSTM_THREADS, 2) void silero_lstm_kernel(
     *reinterpret_cast<f32x4 *>(&Hs[n * HS_LD + u0]) = h;
     __syncthreads();
 
-    const float *gsrc = gx + (size_t)grp * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
-    const size_t gstep = (size_t)G * GX_TILE_FLOATS;
+    const float *gsrc = gx + gx0 * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
+    const size_t gstep = gstep_tiles * GX_TILE_FLOATS;
     f32x4 gcur[4], gnxt[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) gcur[g] = *reinterpret_cast<const f32x4 *>(gsrc + g * 256);
@@ -565,6 +601,7 @@ __global__ __launch_bounds__(LSTM_THREADS, 2) void silero_lstm_kernel(
         const int tn = (t + 1 < T) ? t + 1 : t;
 #pragma unroll
         for (int g = 0; g < 4; ++g) gnxt[g] = *reinterpret_cast<const f32x4 *>(gsrc + tn * gstep + g * 256);
+        const f32x4 h_in = h, c_in = c;           // (RG) what a column behind its last window keeps
 
         // Gate-outer order: a gate's 32 MFMAs finish before the next gate's start, so its non-linearity (VALU +
         // transcendentals) runs in the shadow of the following gate's MFMAs instead of after all 128 of them; only
@@ -601,17 +638,21 @@ __global__ __launch_bounds__(LSTM_THREADS, 2) void silero_lstm_kernel(
             h[r] = gate_sigmoid(ao[r]) * gate_tanh(c[r]);
             dpart = fmaf(dw[r], fmaxf(h[r], 0.f), dpart);
         }
+        if constexpr (RG) {
+            if (t >= Tb) { h = h_in; c = c_in; }
+        }
         const int nxt = cur ^ 1;
         *reinterpret_cast<f32x4 *>(&Hs[nxt * 16 * HS_LD + n * HS_LD + u0]) = h;
         dpart += __shfl_xor(dpart, 16);
         dpart += __shfl_xor(dpart, 32);
         if (q == 0) part[(nxt * 8 + wave) * 16 + n] = dpart;
         __syncthreads();
-        if (wave == 0 && lane < 16 && bvalid) {
+        if (wave == 0 && lane < 16 && bvalid && (!RG || t < Tb)) {
             float s = db;
 #pragma unroll
             for (int w = 0; w < 8; ++w) s += part[(nxt * 8 + w) * 16 + lane];
-            probs[b * probs_stride + t] = sigmoidf_(s);
+            if constexpr (RG) prow[t] = refused ? __builtin_nanf("") : sigmoidf_(s);
+            else probs[b * probs_stride + t] = sigmoidf_(s);
         }
         cur = nxt;
 #pragma unroll
@@ -631,13 +672,23 @@ __global__ __launch_bounds__(LSTM_THREADS, 2) void silero_lstm_kernel(
 // Everywhere else step() provably falls through all four of its conditions.  A NaN score sets neither bit, as in the plain loop.
 // (One clip per lane walked all T windows on a divergent wave at ~1000 cycles each: 0.13 ms per 4096 x 313 for about four segments a clip.)
 constexpr int SEG_WAVES = 4;                     // clips (waves) per workgroup
+// RG: the scores are a packed vector, clip b's row starts at row_first[b] and has row_first[b + 1] - row_first[b] windows
+template <bool RG> struct SegRows {};
+template <> struct SegRows<true> { const long long *row_first; };
+template <bool RG = false>
 __global__ __launch_bounds__(64 * SEG_WAVES) void silero_segments_kernel(const float *__restrict__ probs, int B, int T,
                                        const long long *__restrict__ n_samples,
                                        vadx_silero_seg_params prm, long long *__restrict__ segs,
-                                       int *__restrict__ counts, int cap) {
+                                       int *__restrict__ counts, int cap, const SegRows<RG> rows) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * SEG_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (b >= B) return;
+    size_t row0 = (size_t)b * T;
+    if constexpr (RG) {
+        const long long nr = rows.row_first[b + 1] - rows.row_first[b];
+        row0 = (size_t)rows.row_first[b];
+        T = (int)(nr < T ? nr : T);
+    }
     const double sr = (double)prm.sampling_rate;
     const long long W = (prm.sampling_rate == 16000) ? 512 : 256;
     const double thr = prm.threshold;
@@ -675,7 +726,7 @@ __global__ __launch_bounds__(64 * SEG_WAVES) void silero_segments_kernel(const f
     int cur_start = 0, temp_end = 0, prev_end = 0, next_start = 0;      // window indices (0 doubles as "unset", like the reference)
     int best_end = 0, best_dur = 0;
     // 64 windows at a time, the next chunk's scores requested before the current one is walked
-    const float *pr = probs + (size_t)b * T;
+    const float *pr = probs + row0;
     const float qnan = __builtin_nanf("");
     float p = lane < nwin ? pr[lane] : qnan;
     for (int k0 = 0; k0 < nwin; k0 += 64) {      // (leaves through the break below: k0 + 64 may not be representable)
@@ -858,7 +909,7 @@ int vadx::silero::silero_encode_launch(const float *packed, const S *src, float 
     VADX_DYN_LDS(silero_encode_kernel<S>, ENC_LDS_FLOATS * sizeof(float));
     hipLaunchKernelGGL(silero_encode_kernel<S>, dim3((unsigned)nblk), dim3(ENC_THREADS), ENC_LDS_FLOATS * sizeof(float),
                        static_cast<hipStream_t>(stream), packed, src, in_scale, n_valid, row_stride, origin, batch, G, steps,
-                       Gws, first_group, static_cast<float *>(ws));
+                       Gws, first_group, static_cast<float *>(ws), RgArg<false>{});
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
@@ -880,9 +931,9 @@ int vadx::silero::silero_recur_launch(const float *packed, const void *ws, size_
         return silero_lstm_h2_launch(packed, static_cast<const float *>(ws), state0, batch, G, steps, probs, probs_stride, state_n, stream);
     if (arith == 1)
         return silero_lstm_split_launch(packed, static_cast<const float *>(ws), state0, batch, G, steps, probs, probs_stride, state_n, stream);
-    hipLaunchKernelGGL(silero_lstm_kernel, dim3(G), dim3(LSTM_THREADS), LSTM_LDS_FLOATS * sizeof(float),
+    hipLaunchKernelGGL(silero_lstm_kernel<false>, dim3(G), dim3(LSTM_THREADS), LSTM_LDS_FLOATS * sizeof(float),
                        static_cast<hipStream_t>(stream), packed, static_cast<const float *>(ws), state0, batch, G, steps,
-                       probs, probs_stride, state_n);
+                       probs, probs_stride, state_n, RgArg<false>{});
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
@@ -988,9 +1039,111 @@ extern "C" int vadx_silero_segments(const float *probs, int batch, int steps, co
     VADX_REQUIRE(batch > 0 && steps > 0 && cap > 0, "vadx_silero_segments: batch/steps/cap must be positive");
     VADX_REQUIRE(params->sampling_rate == 16000 || params->sampling_rate == 8000,
                  "Currently silero VAD models support 8000 and 16000 (or multiply of 16000) sample rates");
-    hipLaunchKernelGGL(silero_segments_kernel, dim3((batch + SEG_WAVES - 1) / SEG_WAVES), dim3(64 * SEG_WAVES), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(silero_segments_kernel<false>, dim3((batch + SEG_WAVES - 1) / SEG_WAVES), dim3(64 * SEG_WAVES), 0, static_cast<hipStream_t>(stream),
                        probs, batch, steps, reinterpret_cast<const long long *>(n_samples), *params,
-                       reinterpret_cast<long long *>(segments), counts, cap);
+                       reinterpret_cast<long long *>(segments), counts, cap, SegRows<false>{});
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+// ---- ragged batches (include/vadx.h: "Silero over a RAGGED batch") ----
+extern "C" size_t vadx_silero_ragged_workspace_bytes(int64_t tiles) {
+    return tiles <= 0 ? 0 : (size_t)tiles * GX_TILE_FLOATS * sizeof(float);
+}
+
+// what every ragged launch checks of its arguments on the host; -> the kernels' argument
+static int ragged_args(const char *who, const float *packed, const vadx_silero_ragged *rg, int64_t n_src, const void *ws, size_t ws_bytes,
+                       const vadx_silero_cfg *cfg, RgArg<true> &out) {
+    VADX_REQUIRE(!(cfg && cfg->ext.sample_rate == 8000),
+                 "%s: cfg->ext.sample_rate=8000: the ragged Silero path runs the 16 kHz network only (the 8 kHz encoder has no ragged form)", who);
+    VADX_REQUIRE(rate_of(cfg) == 16000, "%s: cfg->ext.sample_rate=%d is not 16000 (0 = 16000)", who, cfg ? cfg->ext.sample_rate : 0);
+    VADX_REQUIRE(packed && rg && ws, "%s: NULL pointer argument", who);
+    VADX_REQUIRE(rg->slot_off && rg->slot_len && rg->slot_clip && rg->gx_first && rg->grp_min_len && rg->wg_tab && rg->probs_first && rg->status,
+                 "%s: NULL table in vadx_silero_ragged", who);
+    VADX_REQUIRE(rg->clips > 0 && rg->groups == (rg->clips + 15) / 16 && rg->tiles >= rg->groups && rg->n_runs >= rg->groups &&
+                     (long long)rg->n_runs * RG_RUN < (1LL << 31) && (long long)rg->n_runs * RG_RUN >= rg->tiles,
+                 "%s: clips=%d groups=%d n_runs=%d tiles=%d are not the counts of one ragged batch", who, rg->clips, rg->groups, rg->n_runs,
+                 rg->tiles);
+    VADX_REQUIRE(n_src > 0, "%s: n_src=%lld must be positive", who, (long long)n_src);
+    VADX_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0,
+                 "%s: packed weights and workspace must be 16-byte aligned", who);
+    if (ws_bytes < vadx_silero_ragged_workspace_bytes(rg->tiles)) {
+        vadx::set_error("%s: workspace %zu B < required %zu B", who, ws_bytes, vadx_silero_ragged_workspace_bytes(rg->tiles));
+        return VADX_ENOSPACE;
+    }
+    out.t = *rg;
+    out.n_src = n_src;
+    return VADX_OK;
+}
+
+template <typename S>
+static int encode_ragged(const char *who, const float *packed, const S *src, float in_scale, int64_t n_src, const vadx_silero_ragged *rg,
+                         void *ws, size_t ws_bytes, void *stream, const vadx_silero_cfg *cfg) {
+    VADX_SILERO_ARITH(cfg, "silero (ragged)");
+    VADX_REQUIRE(src, "%s: NULL pointer argument", who);
+    RgArg<true> a;
+    const int rc = ragged_args(who, packed, rg, n_src, ws, ws_bytes, cfg, a);
+    if (rc != VADX_OK) return rc;
+    if (arith == 2) return silero_encode_h2_ragged_launch<S>(packed, src, in_scale, a, static_cast<float *>(ws), stream);
+    if (arith == 1) return silero_encode_split_ragged_launch<S>(packed, src, in_scale, a, static_cast<float *>(ws), stream);
+    VADX_DYN_LDS((silero_encode_kernel<S, true>), ENC_LDS_FLOATS * sizeof(float));
+    hipLaunchKernelGGL((silero_encode_kernel<S, true>), dim3((unsigned)(rg->n_runs * RG_RUN)), dim3(ENC_THREADS), ENC_LDS_FLOATS * sizeof(float),
+                       static_cast<hipStream_t>(stream), packed, src, in_scale, (long long)n_src, 0LL, -64LL, rg->clips, rg->groups, 0, 0, 0,
+                       static_cast<float *>(ws), a);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+extern "C" int vadx_silero_encode_ragged(const float *packed, const float *src, int64_t n_src, const vadx_silero_ragged *rg,
+                                         void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg) {
+    return encode_ragged("vadx_silero_encode_ragged", packed, src, 1.0f, n_src, rg, workspace, workspace_bytes, stream, cfg);
+}
+
+extern "C" int vadx_silero_encode_ragged_pcm16(const float *packed, const int16_t *src, float scale, int64_t n_src,
+                                               const vadx_silero_ragged *rg, void *workspace, size_t workspace_bytes, void *stream,
+                                               const vadx_silero_cfg *cfg) {
+    return encode_ragged("vadx_silero_encode_ragged_pcm16", packed, src, scale, n_src, rg, workspace, workspace_bytes, stream, cfg);
+}
+
+extern "C" int vadx_silero_recur_ragged(const float *packed, const void *workspace, size_t workspace_bytes, int64_t n_src,
+                                        const vadx_silero_ragged *rg, float *probs, float *state_n, void *stream,
+                                        const vadx_silero_cfg *cfg) {
+    VADX_SILERO_ARITH(cfg, "silero (ragged)");
+    VADX_REQUIRE(probs, "vadx_silero_recur_ragged: NULL pointer argument");
+    RgArg<true> a;
+    const int rc = ragged_args("vadx_silero_recur_ragged", packed, rg, n_src, workspace, workspace_bytes, cfg, a);
+    if (rc != VADX_OK) return rc;
+    const float *gx = static_cast<const float *>(workspace);
+    if (arith == 2) return silero_lstm_h2_ragged_launch(packed, gx, a, probs, state_n, stream);
+    if (arith == 1) return silero_lstm_split_ragged_launch(packed, gx, a, probs, state_n, stream);
+    hipLaunchKernelGGL(silero_lstm_kernel<true>, dim3(rg->groups), dim3(LSTM_THREADS), LSTM_LDS_FLOATS * sizeof(float),
+                       static_cast<hipStream_t>(stream), packed, gx, static_cast<const float *>(nullptr), rg->clips, rg->groups, 0, probs, 0LL,
+                       state_n, a);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+extern "C" int vadx_silero_clips_ragged(const float *packed, const void *src, int src_int16, float scale, int64_t n_src,
+                                        const vadx_silero_ragged *rg, float *probs, float *state_n, void *workspace,
+                                        size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg) {
+    const int rc = src_int16 ? encode_ragged("vadx_silero_clips_ragged", packed, static_cast<const int16_t *>(src), scale, n_src, rg, workspace,
+                                             workspace_bytes, stream, cfg)
+                             : encode_ragged("vadx_silero_clips_ragged", packed, static_cast<const float *>(src), 1.0f, n_src, rg, workspace,
+                                             workspace_bytes, stream, cfg);
+    if (rc != VADX_OK) return rc;
+    return vadx_silero_recur_ragged(packed, workspace, workspace_bytes, n_src, rg, probs, state_n, stream, cfg);
+}
+
+extern "C" int vadx_silero_segments_ragged(const float *probs, const int64_t *probs_first, int batch, const int64_t *n_samples,
+                                           const vadx_silero_seg_params *params, int64_t *segments, int32_t *counts, int cap,
+                                           void *stream) {
+    VADX_REQUIRE(probs && probs_first && n_samples && params && segments && counts, "vadx_silero_segments_ragged: NULL pointer argument");
+    VADX_REQUIRE(batch > 0 && cap > 0, "vadx_silero_segments_ragged: batch/cap must be positive");
+    VADX_REQUIRE(params->sampling_rate == 16000, "vadx_silero_segments_ragged: the ragged Silero path runs at 16000 Hz only (got %d)",
+                 params->sampling_rate);
+    hipLaunchKernelGGL(silero_segments_kernel<true>, dim3((batch + SEG_WAVES - 1) / SEG_WAVES), dim3(64 * SEG_WAVES), 0,
+                       static_cast<hipStream_t>(stream), probs, batch, 2147483647, reinterpret_cast<const long long *>(n_samples), *params,
+                       reinterpret_cast<long long *>(segments), counts, cap, SegRows<true>{reinterpret_cast<const long long *>(probs_first)});
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }

@@ -198,6 +198,91 @@ template <> struct SampleIO<int16_t> {
     static __device__ __forceinline__ float load1(const int16_t *p, float scale) { return (float)*p * scale; }
 };
 
+// ---- ragged batches (include/vadx.h: vadx_silero_ragged) -----------------------------------------
+// The ragged kernels are second instantiations of the rectangular ones under the compile-time flag RG: (group, window) comes from the
+// workgroup table, the staging base and length are per slot, a group's gx tiles lie consecutively.  The rectangular instantiation's last
+// kernel argument is an empty struct: nothing of the tables reaches its code.
+enum : int { RG_RUN = VADX_SILERO_RAGGED_RUN };      // windows per entry of the workgroup table
+template <bool RG> struct RgArg {};
+template <> struct RgArg<true> {
+    vadx_silero_ragged t;
+    long long n_src;          // elements of the source vector: every slot is checked against it before anything of it is read
+};
+
+// Slot `slot` as the device accepts it: (off, len) of a clip that lies inside the source vector, (0, 0) for an empty slot and for one
+// that does not (-> false: the slot is refused).  Nothing is read through a refused slot's offset.
+__device__ __forceinline__ bool rg_slot(const RgArg<true> &rg, int slot, long long &off, int &len) {
+    const bool used = rg.t.slot_clip[slot] >= 0;
+    const long long o = rg.t.slot_off[slot];
+    const int l = rg.t.slot_len[slot];
+    const bool ok = used && l >= 1 && o >= 0 && o <= rg.n_src - (long long)l;
+    off = ok ? o : 0;
+    len = ok ? l : 0;
+    return ok || !used;
+}
+// the caller's clip of a slot (-1: none) -- an index outside [0, clips) counts as none
+__device__ __forceinline__ int rg_clip(const RgArg<true> &rg, int slot) {
+    const int c = rg.t.slot_clip[slot];
+    return (unsigned)c < (unsigned)rg.t.clips ? c : -1;
+}
+
+// Phase 0 of a ragged tile: window `base` .. base + 575 (+ reflect pad) of the sixteen slots of group grp into X, laid out as the
+// rectangular kernels stage it.  Slot c reads its clip as those read a row with n_samples = its own length: zeros before the clip and
+// beyond its end, the pad mirrored over that.  A float4 that lies inside the clip is one vector load when the clip starts on a multiple of
+// four elements (base and p are multiples of four), single loads otherwise; `whole` (uniform: the window ends below the group's shortest
+// accepted length) spares the per-float4 range test.
+template <typename SampleT, int THREADS>
+__device__ __forceinline__ void stage_ragged(float *X, bool fold, const SampleT *__restrict__ audio, float in_scale,
+                                             const RgArg<true> &rg, int grp, long long base, int tid) {
+    auto xslot = [fold](int pp) { return fold ? (pp & 1) * X_ODD + (pp >> 1) : pp; };
+    const bool ptr_ok = (reinterpret_cast<uintptr_t>(audio) & (SampleIO<SampleT>::VEC_ALIGN - 1)) == 0;
+    int shortest;
+    {
+        long long o_;
+        rg_slot(rg, grp * 16 + (tid & 15), o_, shortest);
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) shortest = min(shortest, __shfl_xor(shortest, d));
+        shortest = min(shortest, rg.t.grp_min_len[grp]);
+    }
+    const bool whole = base >= 0 && base + 576 <= (long long)shortest;
+#pragma unroll 1
+    for (int it = 0; it < (16 * 144 + THREADS - 1) / THREADS; ++it) {
+        const int e = tid + THREADS * it;                // 16 clips x 144 float4
+        if (e < 16 * 144) {
+            const int c = e / 144, p = 4 * (e - c * 144);
+            long long off;
+            int len;
+            if (!rg_slot(rg, grp * 16 + c, off, len) && p == 0) atomicOr(rg.t.status, 1u);
+            const SampleT *src = audio + off;
+            const long long idx = base + p;
+            float v[4];
+            if (ptr_ok && (off & 3) == 0 && (whole || (idx >= 0 && idx + 3 < len))) {
+                const f32x4 x = SampleIO<SampleT>::load4(src + idx, in_scale);
+                v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
+            } else {
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+                    v[jj] = (idx + jj >= 0 && idx + jj < len) ? SampleIO<SampleT>::load1(src + idx + jj, in_scale) : 0.f;
+            }
+            float *row = X + c * X_LDM;
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                const int pp = p + jj;
+                row[xslot(pp)] = v[jj];
+                if (pp >= 511 && pp <= 574) row[xslot(1150 - pp)] = v[jj];       // reflect pad (0,64)
+            }
+        }
+    }
+}
+
+// host: the ragged launches of the three kernel sets (csrc/silero.hip picks by cfg)
+template <typename S>
+int silero_encode_split_ragged_launch(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream);
+template <typename S>
+int silero_encode_h2_ragged_launch(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream);
+int silero_lstm_split_ragged_launch(const float *packed, const float *gx, const RgArg<true> &rg, float *probs, float *state_n, void *stream);
+int silero_lstm_h2_ragged_launch(const float *packed, const float *gx, const RgArg<true> &rg, float *probs, float *state_n, void *stream);
+
 // host: launch of the split-product encoder (csrc/silero_split.hip); arguments as silero_encode_kernel's
 template <typename S>
 int silero_encode_split_launch(const float *packed, const S *src, float in_scale, long long n_valid, long long row_stride,

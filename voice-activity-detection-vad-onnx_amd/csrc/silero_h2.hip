@@ -93,10 +93,14 @@ __device__ __forceinline__ void load_a2(f16x8 (&a)[2], const float *frag2, int l
     a[1] = ldh(frag2 + HF, lane);
 }
 
-template <typename SampleT, int NSUB>
+// RG (a ragged batch, silero_common.h): workgroup blk takes entry blk of the workgroup table -- (group, run of NSUB = RG_RUN consecutive
+// windows) --, its valid slots are the windows the group still has, the sixteen clips are staged by stage_ragged and the group's gx tiles
+// lie consecutively.  The range protocol is the rectangular one: the workgroup's verdict poisons its own tiles.
+template <typename SampleT, int NSUB, bool RG = false>
 __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h2_kernel(
     const float *__restrict__ P, const SampleT *__restrict__ audio, float in_scale, long long n_samples,
-    long long row_stride, long long origin, int B, int G, int T, int Gws, int g0, float *__restrict__ gx) {
+    long long row_stride, long long origin, int B, int G, int T, int Gws, int g0, float *__restrict__ gx, const RgArg<RG> rg) {
+    static_assert(!RG || NSUB == RG_RUN, "the workgroup table has one entry per NSUB windows");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *X = reinterpret_cast<float *>(smem);
     float *scr = reinterpret_cast<float *>(smem + H2_SCR), *nyq = scr, *b64p = scr + 256;
@@ -113,7 +117,11 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
     // previous tile has just made -- instead of sixteen rows 10 MB away (adjacent groups of one window, the round-5 order).  The valid
     // slots are a prefix of the NSUB; nvalid depends on blockIdx alone (workgroup-uniform), so a slot past the last window skips its whole
     // tile, barriers included, and the tail multiplies only the nvalid column tiles.
-    const int nvalid = (int)min((long long)NSUB, (long long)T - (blk / G) * NSUB);
+    int nvalid = (int)min((long long)NSUB, (long long)T - (blk / G) * NSUB);
+    if constexpr (RG) {
+        const int g_ = rg.t.wg_tab[2 * blk], r_ = rg.t.wg_tab[2 * blk + 1];
+        nvalid = min(NSUB, rg.t.gx_first[g_ + 1] - rg.t.gx_first[g_] - r_ * NSUB);
+    }
     {
     // Cross-phase fragment prefetch: the first sets of the STFT's weight stream are requested BEFORE the barrier that ends the staging phase
     // (global loads stay in flight across s_barrier, which only waits for lgkmcnt), so the L2 round trip that used to open the STFT runs
@@ -121,12 +129,20 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
 #pragma unroll 1
     for (int sub = 0; sub < nvalid; ++sub) {
     // per tile: nothing derived from the thread index is hoisted out of the tile loop (see silero_split.hip)
-    const int grp = (int)(blk % G), t = (int)(blk / G) * NSUB + sub;
+    int grp = (int)(blk % G), t = (int)(blk / G) * NSUB + sub;
+    if constexpr (RG) {
+        grp = rg.t.wg_tab[2 * blk];
+        t = rg.t.wg_tab[2 * blk + 1] * NSUB + sub;
+    }
 
     // ---------------- phase 0: the 16 windows (576 samples each) + right reflect pad of 64, even / odd samples in separate planes of the
     // clip row (as silero_encode_kernel stages them for the folded pass)
     auto xslot = [](int pp) { return (pp & 1) * X_ODD + (pp >> 1); };
-    {
+    if constexpr (RG) {
+        H2_IDS();
+        (void)xslot;
+        stage_ragged<SampleT, H2_THREADS>(X, true, audio, in_scale, rg, grp, (long long)t * 512 + origin, tid);
+    } else {
         H2_IDS();
         const long long base = (long long)t * 512 + origin;
         const bool vec_ok = ((row_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(audio) & (SampleIO<SampleT>::VEC_ALIGN - 1)) == 0) && n_samples >= 4;
@@ -595,7 +611,9 @@ __global__ __launch_bounds__(H2_THREADS, H2_WAVES_PER_SIMD) void silero_encode_h
             for (int sb = 0; sb < NSUB; ++sb) {
                 if (sb >= nvalid) continue;
                 const int t_s = (int)(blk / G) * NSUB + sb, grp_s = (int)(blk % G);
-                float *dst = gx + ((size_t)t_s * Gws + g0 + grp_s) * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
+                size_t tile = (size_t)t_s * Gws + g0 + grp_s;
+                if constexpr (RG) tile = (size_t)rg.t.gx_first[rg.t.wg_tab[2 * blk]] + rg.t.wg_tab[2 * blk + 1] * NSUB + sb;
+                float *dst = gx + tile * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
                 if (!poison) {           // (workgroup-uniform: a branch, not 32 selects)
 #pragma unroll
                     for (int gg = 0; gg < 2; ++gg) *reinterpret_cast<f32x4 *>(dst + (2 * gh + gg) * 256) = join2(hi[sb][gg], mid[sb][gg]);
@@ -637,22 +655,45 @@ constexpr int LH_BYTES = LH_PART + 2 * LH_BLK * LH_SLOT * 4;
 // latency exceeds a step.
 constexpr int LH_GX_AHEAD = 3;
 
+// RG (a ragged batch): as silero_lstm_kernel's ragged instantiation (csrc/silero.hip) -- T_g steps over the group's consecutive gx tiles,
+// column n = the clip of slot 16 grp + n, frozen behind its own last window; a flush block stores a clip's scores for t < T_b only, into
+// its own row, and the NaN of a poisoned group stays inside its clips' rows.
+template <bool RG = false>
 __global__ __launch_bounds__(512, 2) void silero_lstm_h2_kernel(
     const float *__restrict__ P, const float *__restrict__ gx, const float *__restrict__ state0,
-    int B, int G, int T, float *__restrict__ probs, long long probs_stride, float *__restrict__ state_n) {
+    int B, int G, int T, float *__restrict__ probs, long long probs_stride, float *__restrict__ state_n, const RgArg<RG> rg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *part = reinterpret_cast<float *>(smem + LH_PART);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = lane >> 4, n = lane & 15;
     const int grp = blockIdx.x;
-    const long long b = (long long)grp * 16 + n;
-    const bool bvalid = b < B;
+    long long b = (long long)grp * 16 + n;
+    bool bvalid = b < B;
+    int Tb = T;                                   // RG: the column's own window count
+    float *prow = nullptr;                        // RG: the clip's row of the packed scores
+    size_t gx0 = (size_t)grp, gstep_tiles = (size_t)G;
+    if constexpr (RG) {
+        const int clip = rg_clip(rg, grp * 16 + n);
+        long long o_;
+        int l_;
+        const bool refused = !rg_slot(rg, grp * 16 + n, o_, l_);
+        T = rg.t.gx_first[grp + 1] - rg.t.gx_first[grp];
+        gx0 = (size_t)rg.t.gx_first[grp];
+        gstep_tiles = 1;
+        bvalid = clip >= 0;
+        b = bvalid ? clip : 0;
+        Tb = bvalid ? min((int)(rg.t.probs_first[b + 1] - rg.t.probs_first[b]), T) : 0;
+        prow = probs + rg.t.probs_first[b];
+        if (refused && wave == 0 && q == 0) atomicOr(rg.t.status, 1u);
+    }
     const int u0 = wave * 16 + 4 * q;             // this lane's 4 hidden units
     if (ldg1(P + OFF_HFLAG) == 0.f) {   // uniform: this blob cannot run on fp16 x 2 (a weight outside the fp16 range): as the encoder, flag bit 1,
         if (tid == 0 && grp == 0) atomicOr(reinterpret_cast<unsigned *>(const_cast<float *>(P)) + OFF_HFLAG + 1, 2u);      // and no plausible score
-        if (wave == 0 && lane < 16 && bvalid)
-            for (int t = 0; t < T; ++t) probs[b * probs_stride + t] = __builtin_nanf("");
+        if (wave == 0 && lane < 16 && bvalid) {
+            if constexpr (RG) for (int t = 0; t < Tb; ++t) prow[t] = __builtin_nanf("");
+            else for (int t = 0; t < T; ++t) probs[b * probs_stride + t] = __builtin_nanf("");
+        }
         return;
     }
 
@@ -678,8 +719,8 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_h2_kernel(
     store_h4(smem, LH_HPL, 4 * wave + q, n, h, amax);
     __syncthreads();
 
-    const float *gsrc = gx + (size_t)grp * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
-    const size_t gstep = (size_t)G * GX_TILE_FLOATS;
+    const float *gsrc = gx + gx0 * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
+    const size_t gstep = gstep_tiles * GX_TILE_FLOATS;
     // the gx ring (LH_GX_AHEAD steps) is indexed statically: the step loop is unrolled by its depth
 // (round 6, measured, removed: gate-major MFMA order -- a gate's twelve products finish before the next gate's start, so that its non-linearity
 //  runs under the next gate's MFMAs, all four B fragment pairs held in registers -- 0.590 -> 0.597 ms with gx two steps ahead, 0.65 with three
@@ -721,6 +762,7 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_h2_kernel(
 #pragma unroll
             for (int g = 0; g < 4; ++g) hi[g] = mfma_f16(a[g][kc][0], bb[0], hi[g]);
         }
+        const f32x4 h_in = h, c_in = c;           // (RG) what a column behind its last window keeps
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float ig = gate_sigmoid(fmaf(mid[0][r], H1_INV, hi[0][r])), fg = gate_sigmoid(fmaf(mid[1][r], H1_INV, hi[1][r]));
@@ -728,6 +770,9 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_h2_kernel(
             c[r] = fg * c[r] + ig * gg;
             h[r] = og * gate_tanh(c[r]);
             dpart = fmaf(dwh[r], h[r] + __builtin_fabsf(h[r]), dpart);
+        }
+        if constexpr (RG) {
+            if (t >= Tb) { h = h_in; c = c_in; }
         }
         const int nxt = cur ^ 1;
         store_h4(smem + nxt * LH_HBUF, LH_HPL, 4 * wave + q, n, h, amax);
@@ -738,6 +783,23 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_h2_kernel(
         if ((t & (LH_BLK - 1)) == LH_BLK - 1 || t == T - 1) {        // uniform: this block's scores leave
             const int fc = tid >> 4, fs = tid & (LH_BLK - 1), t_blk = t & ~(LH_BLK - 1);
             const long long fb = (long long)grp * 16 + fc;
+            if constexpr (RG) {      // clip fc's row and window count; a refused slot's scores are NaN
+                if (tid < 16 * LH_BLK) {
+                    const int fclip = rg_clip(rg, grp * 16 + fc);
+                    const long long r0 = fclip >= 0 ? rg.t.probs_first[fclip] : 0;
+                    const int ftb = fclip >= 0 ? min((int)(rg.t.probs_first[fclip + 1] - r0), T) : 0;
+                    long long o_;
+                    int l_;
+                    const bool fref = !rg_slot(rg, grp * 16 + fc, o_, l_);
+                    if (t_blk + fs <= t && t_blk + fs < ftb) {
+                        const float *pp = part + ((t_blk + fs) & (2 * LH_BLK - 1)) * LH_SLOT + fc;
+                        float s = db;
+#pragma unroll
+                        for (int w = 0; w < 8; ++w) s += pp[w * 16];
+                        probs[r0 + t_blk + fs] = fref ? __builtin_nanf("") : sigmoidf_(s);
+                    }
+                }
+            } else
             if (tid < 16 * LH_BLK && fb < B && t_blk + fs <= t) {
                 const float *pp = part + ((t_blk + fs) & (2 * LH_BLK - 1)) * LH_SLOT + fc;
                 float s = db;
@@ -767,15 +829,24 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_h2_kernel(
     __syncthreads();
     {
         const unsigned *bw = reinterpret_cast<const unsigned *>(part);
-        if ((bw[0] | bw[1] | bw[2] | bw[3] | bw[4] | bw[5] | bw[6] | bw[7]) != 0u && wave == 0 && lane < 16 && bvalid)
-            for (int t = 0; t < T; ++t) probs[b * probs_stride + t] = __builtin_nanf("");
+        if ((bw[0] | bw[1] | bw[2] | bw[3] | bw[4] | bw[5] | bw[6] | bw[7]) != 0u && wave == 0 && lane < 16 && bvalid) {
+            if constexpr (RG) for (int t = 0; t < Tb; ++t) prow[t] = __builtin_nanf("");
+            else for (int t = 0; t < T; ++t) probs[b * probs_stride + t] = __builtin_nanf("");
+        }
     }
 }
 
 int silero_lstm_h2_launch(const float *packed, const float *gx, const float *state0, int batch, int G, int steps, float *probs,
                           long long probs_stride, float *state_n, void *stream) {
-    hipLaunchKernelGGL(silero_lstm_h2_kernel, dim3(G), dim3(512), LH_BYTES, static_cast<hipStream_t>(stream), packed, gx, state0, batch, G,
-                       steps, probs, probs_stride, state_n);
+    hipLaunchKernelGGL(silero_lstm_h2_kernel<false>, dim3(G), dim3(512), LH_BYTES, static_cast<hipStream_t>(stream), packed, gx, state0, batch, G,
+                       steps, probs, probs_stride, state_n, RgArg<false>{});
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+int silero_lstm_h2_ragged_launch(const float *packed, const float *gx, const RgArg<true> &rg, float *probs, float *state_n, void *stream) {
+    hipLaunchKernelGGL(silero_lstm_h2_kernel<true>, dim3(rg.t.groups), dim3(512), LH_BYTES, static_cast<hipStream_t>(stream), packed, gx,
+                       static_cast<const float *>(nullptr), rg.t.clips, rg.t.groups, 0, probs, 0LL, state_n, rg);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
@@ -788,10 +859,22 @@ int silero_encode_h2_launch(const float *packed, const S *src, float in_scale, l
     VADX_DYN_LDS((silero_encode_h2_kernel<S, NS>), LDS);
     const long long nblk = (long long)G * ((steps + NS - 1) / NS);
     hipLaunchKernelGGL((silero_encode_h2_kernel<S, NS>), dim3((unsigned)nblk), dim3(H2_THREADS), LDS, static_cast<hipStream_t>(stream),
-                       packed, src, in_scale, n_valid, row_stride, origin, batch, G, steps, Gws, first_group, gx);
+                       packed, src, in_scale, n_valid, row_stride, origin, batch, G, steps, Gws, first_group, gx, RgArg<false>{});
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
+template <typename S>
+int silero_encode_h2_ragged_launch(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream) {
+    constexpr int NS = H2_NSUB;
+    constexpr int LDS = H2_LDS_BYTES;
+    VADX_DYN_LDS((silero_encode_h2_kernel<S, NS, true>), LDS);
+    hipLaunchKernelGGL((silero_encode_h2_kernel<S, NS, true>), dim3((unsigned)rg.t.n_runs), dim3(H2_THREADS), LDS, static_cast<hipStream_t>(stream),
+                       packed, src, in_scale, rg.n_src, 0LL, -64LL, rg.t.clips, rg.t.groups, 0, 0, 0, gx, rg);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+template int silero_encode_h2_ragged_launch<float>(const float *, const float *, float, const RgArg<true> &, float *, void *);
+template int silero_encode_h2_ragged_launch<int16_t>(const float *, const int16_t *, float, const RgArg<true> &, float *, void *);
 template int silero_encode_h2_launch<float>(const float *, const float *, float, long long, long long, long long, int, int, int, int, int, float *, void *);
 template int silero_encode_h2_launch<int16_t>(const float *, const int16_t *, float, long long, long long, long long, int, int, int, int, int, float *, void *);
 

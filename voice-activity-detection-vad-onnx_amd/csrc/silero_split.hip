@@ -77,10 +77,13 @@ __device__ __forceinline__ void load_a3(bf16x8 (&a)[3], const float *frag3, int 
 // 512-thread workgroups, but the halves stream the SAME weight fragments at the same moment, so the second request of every line is an
 // L1 hit instead of an L2 read (the weight stream out of L2 is the kernel's largest stall: a build that read "every fragment from
 // one address" 5.77 -> 4.51 ms).
-template <typename SampleT, int HALVES, int NSUB>
+// RG (a ragged batch, silero_common.h; one tile per workgroup): as silero_encode_kernel's -- RG_RUN workgroups per entry of the workgroup
+// table, slots staged by stage_ragged, the group's gx tiles consecutive.
+template <typename SampleT, int HALVES, int NSUB, bool RG = false>
 __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_kernel(
     const float *__restrict__ P, const SampleT *__restrict__ audio, float in_scale, long long n_samples,
-    long long row_stride, long long origin, int B, int G, int T, int Gws, int g0, float *__restrict__ gx) {
+    long long row_stride, long long origin, int B, int G, int T, int Gws, int g0, float *__restrict__ gx, const RgArg<RG> rg) {
+    static_assert(!RG || (HALVES == 1 && NSUB == 1), "the ragged instantiation encodes one tile per workgroup");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
     const int half = HALVES > 1 ? (int)(threadIdx.x >> 9) : 0;
     unsigned char *smem = smem_all + half * SP_LDS_BYTES;
@@ -88,7 +91,15 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
     float *scr = reinterpret_cast<float *>(smem + SP_SCR), *nyq = scr + 256;
 
     int tid0 = threadIdx.x & (SP_THREADS - 1);
-    const long long ntile = (long long)G * T;
+    long long ntile = (long long)G * T;
+    int rg_grp = 0, rg_t = 0;
+    if constexpr (RG) {
+        const int ent = blockIdx.x / RG_RUN;
+        rg_grp = rg.t.wg_tab[2 * ent];
+        rg_t = rg.t.wg_tab[2 * ent + 1] * RG_RUN + blockIdx.x % RG_RUN;
+        if (rg_t >= rg.t.gx_first[rg_grp + 1] - rg.t.gx_first[rg_grp]) return;      // (uniform) the group's last run is a partial one
+        ntile = (long long)blockIdx.x + 1;       // this workgroup's one tile is always stored
+    }
     const bool fold = P[OFF_FOLD] != 0.f;      // uniform: the basis has the DFT symmetries -> folded STFT pass
 #pragma unroll 1
     for (int sub = 0; sub < NSUB; ++sub) {
@@ -102,12 +113,15 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
     const long long tile_raw = ((long long)blockIdx.x * HALVES + half) * NSUB + sub;
     const bool tile_ok = tile_raw < ntile;
     const int tile_id = (int)(tile_ok ? tile_raw : ntile - 1);
-    const int grp = tile_id % G, t = tile_id / G;
+    const int grp = RG ? rg_grp : tile_id % G, t = RG ? rg_t : tile_id / G;
 
     // ---------------- phase 0: the 16 windows (576 samples each) + right reflect pad of 64 (as silero_encode_kernel stages them:
     // folded pass -> even / odd samples in separate planes of the clip row)
     auto xslot = [fold](int pp) { return fold ? (pp & 1) * X_ODD + (pp >> 1) : pp; };
-    {
+    if constexpr (RG) {
+        (void)xslot;
+        stage_ragged<SampleT, SP_THREADS>(X, fold, audio, in_scale, rg, grp, (long long)t * 512 + origin, tid);
+    } else {
         const long long base = (long long)t * 512 + origin;
         const bool vec_ok = ((row_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(audio) & (SampleIO<SampleT>::VEC_ALIGN - 1)) == 0) && n_samples >= 4;
         const int wv = __builtin_amdgcn_readfirstlane(wave);
@@ -506,7 +520,9 @@ __global__ __launch_bounds__(SP_THREADS * HALVES, 4) void silero_encode_split_ke
         for (int sb = 0; sb < NSUB; ++sb) {
             const long long tile_raw = ((long long)blockIdx.x * HALVES + half) * NSUB + sb;
             const int tile_id = (int)(tile_raw < ntile ? tile_raw : ntile - 1);
-            float *dst = gx + ((size_t)(tile_id / G) * Gws + g0 + tile_id % G) * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
+            size_t tile = (size_t)(tile_id / G) * Gws + g0 + tile_id % G;
+            if constexpr (RG) tile = (size_t)rg.t.gx_first[rg_grp] + rg_t;
+            float *dst = gx + tile * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
             if (tile_raw < ntile)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x4 *>(dst + g * 256) = hi[sb][g] + lo[sb][g];
@@ -528,17 +544,37 @@ constexpr int LS_W2 = LS_PART + 1024;            // W_hh plane 2: [8 waves][4 ga
 constexpr int LS_BYTES = LS_W2 + 131072;
 static_assert(LS_BYTES <= 160 * 1024, "split LSTM LDS map");
 
+// RG (a ragged batch): as silero_lstm_kernel's ragged instantiation (csrc/silero.hip)
+template <bool RG = false>
 __global__ __launch_bounds__(512, 2) void silero_lstm_split_kernel(
     const float *__restrict__ P, const float *__restrict__ gx, const float *__restrict__ state0,
-    int B, int G, int T, float *__restrict__ probs, long long probs_stride, float *__restrict__ state_n) {
+    int B, int G, int T, float *__restrict__ probs, long long probs_stride, float *__restrict__ state_n, const RgArg<RG> rg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *part = reinterpret_cast<float *>(smem + LS_PART);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = lane >> 4, n = lane & 15;
     const int grp = blockIdx.x;
-    const long long b = (long long)grp * 16 + n;
-    const bool bvalid = b < B;
+    long long b = (long long)grp * 16 + n;
+    bool bvalid = b < B;
+    int Tb = T;                                   // RG: the column's own window count
+    bool refused = false;
+    float *prow = nullptr;                        // RG: the clip's row of the packed scores
+    size_t gx0 = (size_t)grp, gstep_tiles = (size_t)G;
+    if constexpr (RG) {
+        const int clip = rg_clip(rg, grp * 16 + n);
+        long long o_;
+        int l_;
+        refused = !rg_slot(rg, grp * 16 + n, o_, l_);
+        T = rg.t.gx_first[grp + 1] - rg.t.gx_first[grp];
+        gx0 = (size_t)rg.t.gx_first[grp];
+        gstep_tiles = 1;
+        bvalid = clip >= 0;
+        b = bvalid ? clip : 0;
+        Tb = bvalid ? min((int)(rg.t.probs_first[b + 1] - rg.t.probs_first[b]), T) : 0;
+        prow = probs + rg.t.probs_first[b];
+        if (refused && wave == 0 && q == 0) atomicOr(rg.t.status, 1u);
+    }
     const int u0 = wave * 16 + 4 * q;             // this lane's 4 hidden units
 
     // W_hh fragments of this wave's 4 gate tiles: planes 0, 1 -> 128 VGPRs for the whole clip, plane 2 -> LDS
@@ -566,8 +602,8 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_split_kernel(
     store_split4(smem + LS_H, LS_HPL, 4 * wave + q, n, h);
     __syncthreads();
 
-    const float *gsrc = gx + (size_t)grp * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
-    const size_t gstep = (size_t)G * GX_TILE_FLOATS;
+    const float *gsrc = gx + gx0 * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
+    const size_t gstep = gstep_tiles * GX_TILE_FLOATS;
     f32x4 gcur[4], gnxt[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) gcur[g] = *reinterpret_cast<const f32x4 *>(gsrc + g * 256);
@@ -605,6 +641,7 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_split_kernel(
             for (int g = 0; g < 4; ++g) hi[g] = mfma_bf16(a[g][kc][0], bb[0], hi[g]);
         }
         float dpart = 0.f;
+        const f32x4 h_in = h, c_in = c;           // (RG) what a column behind its last window keeps
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float ig = gate_sigmoid(hi[0][r] + lo[0][r]), fg = gate_sigmoid(hi[1][r] + lo[1][r]);
@@ -613,17 +650,21 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_split_kernel(
             h[r] = og * gate_tanh(c[r]);
             dpart = fmaf(dw[r], fmaxf(h[r], 0.f), dpart);
         }
+        if constexpr (RG) {
+            if (t >= Tb) { h = h_in; c = c_in; }
+        }
         const int nxt = cur ^ 1;
         store_split4(smem + LS_H + nxt * LS_HBUF, LS_HPL, 4 * wave + q, n, h);
         dpart += __shfl_xor(dpart, 16);
         dpart += __shfl_xor(dpart, 32);
         if (q == 0) part[(nxt * 8 + wave) * 16 + n] = dpart;
         __syncthreads();
-        if (wave == 0 && lane < 16 && bvalid) {
+        if (wave == 0 && lane < 16 && bvalid && (!RG || t < Tb)) {
             float s = db;
 #pragma unroll
             for (int w = 0; w < 8; ++w) s += part[(nxt * 8 + w) * 16 + lane];
-            probs[b * probs_stride + t] = sigmoidf_(s);
+            if constexpr (RG) prow[t] = refused ? __builtin_nanf("") : sigmoidf_(s);
+            else probs[b * probs_stride + t] = sigmoidf_(s);
         }
         cur = nxt;
 #pragma unroll
@@ -637,9 +678,17 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_split_kernel(
 
 int silero_lstm_split_launch(const float *packed, const float *gx, const float *state0, int batch, int G, int steps, float *probs,
                              long long probs_stride, float *state_n, void *stream) {
-    VADX_DYN_LDS(silero_lstm_split_kernel, LS_BYTES);
-    hipLaunchKernelGGL(silero_lstm_split_kernel, dim3(G), dim3(512), LS_BYTES, static_cast<hipStream_t>(stream), packed, gx, state0, batch, G,
-                       steps, probs, probs_stride, state_n);
+    VADX_DYN_LDS(silero_lstm_split_kernel<false>, LS_BYTES);
+    hipLaunchKernelGGL(silero_lstm_split_kernel<false>, dim3(G), dim3(512), LS_BYTES, static_cast<hipStream_t>(stream), packed, gx, state0, batch, G,
+                       steps, probs, probs_stride, state_n, RgArg<false>{});
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+int silero_lstm_split_ragged_launch(const float *packed, const float *gx, const RgArg<true> &rg, float *probs, float *state_n, void *stream) {
+    VADX_DYN_LDS(silero_lstm_split_kernel<true>, LS_BYTES);
+    hipLaunchKernelGGL(silero_lstm_split_kernel<true>, dim3(rg.t.groups), dim3(512), LS_BYTES, static_cast<hipStream_t>(stream), packed, gx,
+                       static_cast<const float *>(nullptr), rg.t.clips, rg.t.groups, 0, probs, 0LL, state_n, rg);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
@@ -659,10 +708,20 @@ int silero_encode_split_launch(const float *packed, const S *src, float in_scale
     VADX_DYN_LDS((silero_encode_split_kernel<S, HV, NS>), SP_LDS_BYTES * HV);
     const long long nblk = ((long long)G * steps + HV * NS - 1) / (HV * NS);
     hipLaunchKernelGGL((silero_encode_split_kernel<S, HV, NS>), dim3((unsigned)nblk), dim3(SP_THREADS * HV), SP_LDS_BYTES * HV, static_cast<hipStream_t>(stream),
-                       packed, src, in_scale, n_valid, row_stride, origin, batch, G, steps, Gws, first_group, gx);
+                       packed, src, in_scale, n_valid, row_stride, origin, batch, G, steps, Gws, first_group, gx, RgArg<false>{});
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
+template <typename S>
+int silero_encode_split_ragged_launch(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream) {
+    VADX_DYN_LDS((silero_encode_split_kernel<S, 1, 1, true>), SP_LDS_BYTES);
+    hipLaunchKernelGGL((silero_encode_split_kernel<S, 1, 1, true>), dim3((unsigned)(rg.t.n_runs * RG_RUN)), dim3(SP_THREADS), SP_LDS_BYTES,
+                       static_cast<hipStream_t>(stream), packed, src, in_scale, rg.n_src, 0LL, -64LL, rg.t.clips, rg.t.groups, 0, 0, 0, gx, rg);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+template int silero_encode_split_ragged_launch<float>(const float *, const float *, float, const RgArg<true> &, float *, void *);
+template int silero_encode_split_ragged_launch<int16_t>(const float *, const int16_t *, float, const RgArg<true> &, float *, void *);
 template int silero_encode_split_launch<float>(const float *, const float *, float, long long, long long, long long, int, int, int, int, int, float *, void *);
 template int silero_encode_split_launch<int16_t>(const float *, const int16_t *, float, long long, long long, long long, int, int, int, int, int, float *, void *);
 

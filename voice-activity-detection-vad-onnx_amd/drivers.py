@@ -114,11 +114,14 @@ def inference_silero(test_vad_audio="./vad_sample.wav", model=None, save_timesta
         clips = [audio_io.load_wav(f, SAMPLE_RATE).astype(np.float32) * np.float32(0.000030517578) for f in files]
     echo("\nStart to run the VAD process.")
     t0 = time.time()
-    n = max(len(c) for c in clips)
-    batch = np.zeros((len(clips), n), np.float32)
-    for k, c in enumerate(clips):
-        batch[k, :len(c)] = c
-    res = silero.get_speech_timestamps_batch(batch, model, lengths=[len(c) for c in clips], threshold=ACTIVATE_THRESHOLD,
+    if len(clips) > 1 and SAMPLE_RATE == 16000:       # a list of files: one ragged batch (every file pays for its own windows)
+        batch, lengths = clips, None
+    else:
+        n = max(len(c) for c in clips)
+        batch, lengths = np.zeros((len(clips), n), np.float32), [len(c) for c in clips]
+        for k, c in enumerate(clips):
+            batch[k, :len(c)] = c
+    res = silero.get_speech_timestamps_batch(batch, model, lengths=lengths, threshold=ACTIVATE_THRESHOLD,
                                              max_speech_duration_s=MAX_SPEECH_DURATION,
                                              min_speech_duration_ms=int(MIN_SPEECH_DURATION * 1000),
                                              min_silence_duration_ms=MIN_SILENCE_DURATION, return_seconds=True)

@@ -20,6 +20,9 @@ vadx_windows_gather_any), sharing win_first and win_src.
 
 `RaggedFrames` (below) is the batch of the model whose window is the whole clip (MarbleNet, dynamic axis): no window grid, no padding --
 the clips as they are, with per-clip frame prefixes and tile tables.
+
+`RaggedClips` (at the end) is Silero's batch: float32 or int16 clips as they are, sorted into groups of sixteen by window count, with the
+slot, group and workgroup tables of include/vadx.h's vadx_silero_ragged.
 """
 from __future__ import annotations
 
@@ -384,3 +387,167 @@ class RaggedFrames:
             raise ValueError("this batch is host-only: call .to(device) first")
         return _lib.MarbleNetRagged(self.enc_tile_first.data_ptr(), self.enc_tile_clip.data_ptr(), self.enc_first.data_ptr(),
                                     self.mel_first.data_ptr(), len(self), self.n_enc_tiles, self.n_enc, self.n_mel)
+
+
+SILERO_WINDOW = 512          # samples per Silero window at 16 kHz
+SILERO_GROUP = 16            # clips per group = columns of one MFMA tile
+SILERO_RUN = 4               # windows per workgroup-table entry (include/vadx.h: VADX_SILERO_RAGGED_RUN)
+GX_TILE_BYTES = 32768        # one (group, window) tile of gate pre-activations
+
+
+class RaggedClips:
+    """Silero's ragged batch (16 kHz; include/vadx.h, "Silero over a RAGGED batch"): clips of any lengths in ONE packed vector, float32 on
+    the +-1 scale or int16 PCM (scaled by SileroEngine.PCM16_SCALE while staging), as they are -- Silero needs no normalisation and no
+    padding, so `from_packed` copies nothing.  The clips are sorted by window count T_b = ceil(len_b / 512), descending and stable, and
+    taken sixteen at a time as GROUPS; a group runs T_g = its first slot's window count, and the encoder's work is sum(T_g) tiles instead
+    of ceil(B / 16) * max(T_b).
+    Host fields (functions of the lengths and offsets alone, `_set_tables`): lengths int64 [B], clip_off int64 [B], windows int64 [B],
+    order [B], group_windows [G]; tables `<name>_host`: slot_off int64 [16 G], slot_len / slot_clip int32 [16 G] (slot_clip = -1 behind the
+    last clip of a partial group), gx_first int32 [G + 1], grp_min_len int32 [G], wg_tab int32 [n_runs, 2] = (group, run of four windows),
+    run-major over the groups that still have that run, probs_first int64 [B + 1]; n_windows = sum(T_b), tiles = sum(T_g), n_runs,
+    workspace_bytes = tiles * 32 KB.  With a device, `pcm`, the tables and the status word are tensors there.
+    Scores of a batch: one packed float32 vector [n_windows], clip b's at probs_first[b] .. probs_first[b + 1] (`rows`)."""
+
+    TABLES = ("slot_off", "slot_len", "slot_clip", "gx_first", "grp_min_len", "wg_tab", "probs_first")
+
+    @classmethod
+    def from_clips(cls, clips, device="cuda:0", align=ALIGN):
+        """clips: list of 1-D arrays, all float32 (+-1 scale) or all int16; packed on the host with every clip on a multiple of `align`
+        elements (zero filler) and uploaded once."""
+        if len(clips) == 0:
+            raise ValueError("a ragged batch needs at least one clip")
+        align = int(align)
+        if align < 1:
+            raise ValueError(f"align={align} must be positive")
+        rows = []
+        for b, c in enumerate(clips):
+            a = c.detach().cpu().numpy() if hasattr(c, "detach") else np.asarray(c)
+            if a.dtype not in (np.float32, np.int16):
+                raise ValueError(f"clip {b} must be float32 or int16, got dtype {a.dtype}")
+            if rows and a.dtype != rows[0].dtype:
+                raise ValueError(f"clip {b} has dtype {a.dtype}, clip 0 {rows[0].dtype}: one batch, one dtype")
+            a = a.reshape(-1)
+            if a.shape[0] == 0:
+                raise ValueError(f"clip {b} is empty")
+            rows.append(a)
+        lengths = np.asarray([len(r) for r in rows], dtype=np.int64)
+        starts = np.concatenate([[0], np.cumsum((lengths + align - 1) // align * align)]).astype(np.int64)
+        self = cls()
+        self._set_tables(lengths, starts[:-1])
+        pcm = np.zeros(int(starts[-1]), dtype=rows[0].dtype)
+        for k, r in enumerate(rows):
+            pcm[starts[k]:starts[k] + len(r)] = r
+        self.pcm_host, self.device = pcm, None
+        self.pcm = pcm
+        for name in self.TABLES:
+            setattr(self, name, getattr(self, name + "_host"))
+        self.status = None
+        if device is not None:
+            self.to(device)
+        return self
+
+    @classmethod
+    def from_packed(cls, pcm, clip_offsets, lengths):
+        """Tables only, over clips that already lie in DEVICE memory: pcm 1-D float32 or int16 tensor, clip b = lengths[b] samples from
+        element clip_offsets[b] (any element: what chunks.collect_chunks_batch / drop_chunks_batch return goes in as it is).  No copy;
+        clip_offsets / lengths are host arrays or device tensors (read back once, as prepare.read_tables does)."""
+        from . import _lib, prepare
+        t = _lib.require_gpu()
+        if not t.is_tensor(pcm) or not pcm.is_cuda or pcm.dim() != 1:
+            raise ValueError("pcm must be a 1-D device tensor")
+        if pcm.dtype not in (t.float32, t.int16):
+            raise ValueError(f"pcm must be float32 or int16, got dtype {pcm.dtype}")
+        off, lengths = prepare.read_tables(clip_offsets, lengths)
+        if lengths.shape[0] == 0:
+            raise ValueError("a ragged batch needs at least one clip")
+        if off.shape[0] != lengths.shape[0]:
+            raise ValueError(f"{off.shape[0]} clip_offsets for {lengths.shape[0]} lengths")
+        self = cls()
+        self._set_tables(lengths, off)
+        if int(off.min()) < 0 or int((off + self.lengths).max()) > int(pcm.numel()):
+            raise ValueError(f"a clip lies outside the packed vector of {int(pcm.numel())} elements")
+        self.pcm_host, self.device = None, pcm.device
+        self.pcm = pcm.contiguous()
+        self._upload_tables()
+        return self
+
+    def _set_tables(self, lengths, clip_off):
+        """Every table of the batch: a function of the clips' lengths and offsets.  Pure numpy."""
+        self.lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        self.clip_off = np.asarray(clip_off, dtype=np.int64).reshape(-1)
+        B = int(self.lengths.shape[0])
+        if B == 0:
+            raise ValueError("a ragged batch needs at least one clip")
+        if int(self.lengths.min()) < 1:
+            raise ValueError(f"clip {int(np.argmin(self.lengths))} is empty")
+        if int(self.lengths.max()) >= 2 ** 31:
+            raise ValueError("a clip of 2^31 samples or more does not fit the int32 slot_len table")
+        if B >= 2 ** 31 - SILERO_GROUP:
+            raise ValueError(f"{B} clips do not fit the int32 slot tables")
+        self.windows = (self.lengths + SILERO_WINDOW - 1) // SILERO_WINDOW
+        self.order = np.argsort(-self.windows, kind="stable").astype(np.int32)
+        G = (B + SILERO_GROUP - 1) // SILERO_GROUP
+        self.groups = G
+        self.slot_clip_host = np.full(G * SILERO_GROUP, -1, dtype=np.int32)
+        self.slot_clip_host[:B] = self.order
+        self.slot_off_host = np.zeros(G * SILERO_GROUP, dtype=np.int64)
+        self.slot_off_host[:B] = self.clip_off[self.order]
+        self.slot_len_host = np.zeros(G * SILERO_GROUP, dtype=np.int32)
+        self.slot_len_host[:B] = self.lengths[self.order]
+        self.group_windows = self.windows[self.order[::SILERO_GROUP]]                    # T_g: the group's first (longest) slot
+        self.tiles = int(self.group_windows.sum())
+        runs = (self.group_windows + SILERO_RUN - 1) // SILERO_RUN
+        self.n_runs = int(runs.sum())
+        if self.tiles >= 2 ** 31 or self.n_runs * SILERO_RUN >= 2 ** 31:
+            raise ValueError(f"{self.tiles} gx tiles do not fit the int32 tables of a ragged batch")
+        self.gx_first_host = np.concatenate([[0], np.cumsum(self.group_windows)]).astype(np.int32)
+        grp_min = self.slot_len_host.reshape(G, SILERO_GROUP).min(axis=1)                # 0 for a partial group (an empty slot)
+        self.grp_min_len_host = grp_min.astype(np.int32)
+        # run-major over the groups that still have that run: T_g never grows with g, so those are the first n_r groups
+        n_r = np.searchsorted(-runs, -np.arange(1, int(runs.max()) + 1), side="right")   # groups with runs >= r + 1
+        grp = np.concatenate([np.arange(n, dtype=np.int32) for n in n_r])
+        run = np.repeat(np.arange(len(n_r), dtype=np.int32), n_r)
+        self.wg_tab_host = np.ascontiguousarray(np.stack([grp, run], axis=1).astype(np.int32))
+        self.probs_first_host = np.concatenate([[0], np.cumsum(self.windows)]).astype(np.int64)
+        self.n_windows = int(self.probs_first_host[-1])
+        self.workspace_bytes = self.tiles * GX_TILE_BYTES
+
+    def _upload_tables(self):
+        from . import _lib
+        t = _lib.require_gpu()
+        for name in self.TABLES:
+            setattr(self, name, t.from_numpy(getattr(self, name + "_host")).to(self.device))
+        self.status = t.zeros(1, dtype=t.int32, device=self.device)
+
+    def to(self, device):
+        """Upload the packed vector (once), the tables and a cleared status word."""
+        from . import _lib
+        t = _lib.require_gpu()
+        self.device = t.device(device)
+        self.pcm = t.from_numpy(self.pcm_host).to(self.device)
+        self._upload_tables()
+        return self
+
+    def __len__(self):
+        return int(self.lengths.shape[0])
+
+    def tables(self):
+        """The vadx_silero_ragged struct of this batch (device pointers: the batch must be on a device)."""
+        from . import _lib
+        if self.device is None:
+            raise ValueError("this batch is host-only: call .to(device) first")
+        return _lib.SileroRagged(self.slot_off.data_ptr(), self.slot_len.data_ptr(), self.slot_clip.data_ptr(), self.gx_first.data_ptr(),
+                                 self.grp_min_len.data_ptr(), self.wg_tab.data_ptr(), self.probs_first.data_ptr(), self.status.data_ptr(),
+                                 len(self), self.groups, self.n_runs, self.tiles)
+
+    def rows(self, packed):
+        """per-clip views of a packed per-window vector (the scores): [packed[probs_first[b] : probs_first[b + 1]]]"""
+        f = self.probs_first_host
+        return [packed[int(f[b]):int(f[b + 1])] for b in range(len(self))]
+
+    def check(self):
+        """Raise ValueError when the device refused a slot (one 4-byte read-back; clears the word)."""
+        if self.status is not None and int(self.status.item()) != 0:
+            self.status.zero_()
+            raise ValueError("a clip of the ragged batch lies outside the packed vector: the device did not read it and its scores are NaN")
+        return self

@@ -5,8 +5,8 @@ Mirrors (same names / arguments / error behaviour):
   * `load_silero_vad`        -- Silero/modeling_modified/model.py:9-41
   * `get_speech_timestamps`  -- Silero/modeling_modified/utils_vad.py:248-491
   * `VADIterator`            -- Silero/modeling_modified/utils_vad.py:494-586 (host drop-in)
-plus the batched entry points the reference does not have (`SileroEngine.clips`,
-`get_speech_timestamps_batch`, `VADIteratorBatch`: many live streams on the device).  All arithmetic runs in libvadx.so (HIP, gfx950); this file is
+plus the batched entry points the reference does not have (`SileroEngine.clips`, `SileroEngine.clips_ragged`: clips of any lengths as one
+ragged batch, `get_speech_timestamps_batch`, `VADIteratorBatch`: many live streams on the device).  All arithmetic runs in libvadx.so (HIP, gfx950); this file is
 plumbing: tensors in, C-ABI call, tensors out.  No CPU fallback.
 """
 from __future__ import annotations
@@ -352,6 +352,105 @@ class SileroEngine:
             _lib.check(_lib.lib().vadx_silero_recur(self.blob(sampling_rate).data_ptr(), ws.data_ptr(), ws.numel(), batch, steps,
                                                     None, probs.data_ptr(), None, _lib.stream_ptr(), self.cfg(mode, sampling_rate)))
         return probs
+
+    # -- ragged batches (vadx.ragged.RaggedClips; include/vadx.h: "Silero over a RAGGED batch")
+    def _ragged_workspace(self, batch, who):
+        need = int(batch.workspace_bytes)
+        if need > WORKSPACE_CAP_BYTES:
+            raise ValueError(f"{who}: a ragged batch of {len(batch)} clips / {batch.tiles} gx tiles needs a {need / 2**30:.1f} GiB workspace "
+                             f"(cap {WORKSPACE_CAP_BYTES / 2**30:.0f} GiB, WORKSPACE_CAP_BYTES): split the list into smaller batches "
+                             "(the ragged path has no spanned form)")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = self.torch.empty(need, dtype=self.torch.uint8, device=self.device)
+        return self._ws
+
+    def _ragged_batch(self, batch, who):
+        from .ragged import RaggedClips
+        if not isinstance(batch, RaggedClips):
+            batch = RaggedClips.from_clips(batch, device=self.device)
+        if batch.device is None:
+            batch.to(self.device)
+        if batch.device != self.device:
+            raise ValueError(f"{who}: the batch lives on {batch.device}, the engine on {self.device}")
+        return batch
+
+    def encode_ragged(self, batch, mode=None):
+        """First half of `clips_ragged` as its own launch (fills the workspace; no range protocol, as `encode`)."""
+        t, L = self.torch, _lib.lib()
+        ws = self._ragged_workspace(batch, "encode_ragged")
+        tab = batch.tables()
+        with t.cuda.device(self.device):
+            if batch.pcm.dtype == t.int16:
+                _lib.check(L.vadx_silero_encode_ragged_pcm16(self.packed.data_ptr(), batch.pcm.data_ptr(), self.PCM16_SCALE, int(batch.pcm.numel()),
+                                                             C.byref(tab), ws.data_ptr(), ws.numel(), _lib.stream_ptr(), self.cfg(mode)))
+            else:
+                _lib.check(L.vadx_silero_encode_ragged(self.packed.data_ptr(), batch.pcm.data_ptr(), int(batch.pcm.numel()), C.byref(tab),
+                                                       ws.data_ptr(), ws.numel(), _lib.stream_ptr(), self.cfg(mode)))
+        return batch
+
+    def recur_ragged(self, batch, probs=None, state_n=None, mode=None):
+        """Second half of `clips_ragged`: workspace -> packed scores [batch.n_windows] (+ state_n [2, B, 128] when given)."""
+        t = self.torch
+        ws = self._ragged_workspace(batch, "recur_ragged")
+        if probs is None:
+            probs = t.empty(batch.n_windows, dtype=t.float32, device=self.device)
+        tab = batch.tables()
+        with t.cuda.device(self.device):
+            _lib.check(_lib.lib().vadx_silero_recur_ragged(self.packed.data_ptr(), ws.data_ptr(), ws.numel(), int(batch.pcm.numel()), C.byref(tab),
+                                                           probs.data_ptr(), None if state_n is None else state_n.data_ptr(),
+                                                           _lib.stream_ptr(), self.cfg(mode)))
+        return probs
+
+    def clips_ragged(self, batch, return_state=False):
+        """A ragged batch (vadx.ragged.RaggedClips, or a list of 1-D float32 / int16 clips) -> (probs_packed float32 [sum T_b],
+        probs_first int64 [B + 1]) on the device: clip b's T_b = ceil(len_b / 512) scores are probs_packed[probs_first[b] :
+        probs_first[b + 1]], bit for bit what `clips` gives for that clip alone; with return_state also state [2, B, 128], every clip's
+        LSTM state after its own last window, in the caller's clip order.  One encoder and one recurrent launch whose work follows the
+        clips' own window counts; the fp16 x 2 range protocol as `clips`."""
+        t = self.torch
+        batch = self._ragged_batch(batch, "clips_ragged")
+        ws = self._ragged_workspace(batch, "clips_ragged")
+        probs = t.empty(batch.n_windows, dtype=t.float32, device=self.device)
+        state_n = t.empty((2, len(batch), HIDDEN), dtype=t.float32, device=self.device) if return_state else None
+        pcm16 = batch.pcm.dtype == t.int16
+        tab = batch.tables()
+
+        def run(mode):
+            with t.cuda.device(self.device):
+                _lib.check(_lib.lib().vadx_silero_clips_ragged(self.packed.data_ptr(), batch.pcm.data_ptr(), 1 if pcm16 else 0, self.PCM16_SCALE,
+                                                               int(batch.pcm.numel()), C.byref(tab), probs.data_ptr(),
+                                                               None if state_n is None else state_n.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                               _lib.stream_ptr(), self.cfg(mode)))
+            return (probs, batch.probs_first, state_n) if return_state else (probs, batch.probs_first)
+        return self._guarded(run)
+
+    def segments_ragged(self, probs, probs_first, n_samples, cap=64, **kw):
+        """`segments` on packed scores: probs float32 [sum T_b], probs_first int64 [B + 1] (device; a RaggedClips goes in as it is) ->
+        (int64 [B, cap, 2] sample indices, int32 [B] counts), the tables `segments` gives for the per-clip rows."""
+        t = self.torch
+        if hasattr(probs_first, "probs_first"):
+            probs_first = probs_first.probs_first
+        first = probs_first.to(device=self.device, dtype=t.int64).contiguous()
+        B = int(first.shape[0]) - 1
+        if t.is_tensor(n_samples):
+            lens = n_samples.to(device=self.device, dtype=t.int64).reshape(-1).contiguous()
+        else:
+            lens = t.as_tensor(np.asarray(n_samples, dtype=np.int64).reshape(-1).copy(), device=self.device)
+        if lens.shape[0] != B:
+            raise ValueError(f"{lens.shape[0]} lengths for {B} clips")
+        if int(kw.get("sampling_rate", 16000)) != 16000:
+            raise ValueError(f"segments_ragged: sampling_rate={kw['sampling_rate']}: the ragged Silero path runs at 16000 Hz only")
+        prm = seg_params(**kw)
+        while True:
+            segs = t.empty((B, cap, 2), dtype=t.int64, device=self.device)
+            counts = t.empty((B,), dtype=t.int32, device=self.device)
+            with t.cuda.device(self.device):
+                _lib.check(_lib.lib().vadx_silero_segments_ragged(probs.data_ptr(), first.data_ptr(), B, lens.data_ptr(), C.byref(prm),
+                                                                  segs.data_ptr(), counts.data_ptr(), cap, _lib.stream_ptr()))
+            worst = int(counts.max().item())
+            if worst <= cap:
+                return segs, counts
+            cap = worst          # rare: a clip produced more segments than the table holds -> rerun
 
     def segments(self, probs, n_samples, cap=64, **kw):
         """Device segmenter: probs [B,T] -> (int64 [B,cap,2] sample indices, int32 [B] counts)."""
@@ -839,6 +938,31 @@ def _segments_on_device(audio, model, lengths, sampling_rate, **seg_kw):
     return engine, given, lens, sampling_rate, step, probs, segs, counts
 
 
+def _is_ragged(audio):
+    from .ragged import RaggedClips
+    return isinstance(audio, (list, tuple, RaggedClips))
+
+
+def _segments_ragged(audio, model, lengths, sampling_rate, **seg_kw):
+    """The device half of the batch entry points for a LIST of clips (or a vadx.ragged.RaggedClips): one ragged encoder + recurrent launch
+    and the ragged segmenter -> (engine, batch, lens int64 [B] host, probs_packed, segs, counts)."""
+    engine = model.engine if isinstance(model, OnnxWrapper) else model
+    if sampling_rate == 8000:
+        raise ValueError("sampling_rate=8000: a list of clips runs Silero's ragged path, which has the 16 kHz network only (the 8 kHz encoder "
+                         "has no ragged form); pass a [B, N] array with lengths=")
+    if sampling_rate != 16000 and sampling_rate % 16000 == 0:
+        raise ValueError(f"sampling_rate={sampling_rate}: a list of clips runs Silero's ragged path at 16000 Hz only (a multiple of 16000 is "
+                         "decimated only in the [B, N] array form); pass the array with lengths=, or decimate the clips")
+    if sampling_rate != 16000:
+        raise ValueError("Currently silero VAD models support 8000 and 16000 (or multiply of 16000) sample rates")
+    if lengths is not None:
+        raise ValueError("lengths= goes with a [B, N] array: a list's clips carry their own lengths")
+    batch = engine._ragged_batch(audio, "get_speech_timestamps_batch")
+    probs, first = engine.clips_ragged(batch)
+    segs, counts = engine.segments_ragged(probs, first, batch.lengths, sampling_rate=16000, **seg_kw)
+    return engine, batch, batch.lengths, probs, segs, counts
+
+
 def get_speech_timestamps_batch(audio, model, lengths=None, threshold: float = 0.5, sampling_rate: int = 16000,
                                 min_speech_duration_ms: int = 250, max_speech_duration_s: float = float("inf"),
                                 min_silence_duration_ms: int = 100, speech_pad_ms: int = 30,
@@ -846,7 +970,18 @@ def get_speech_timestamps_batch(audio, model, lengths=None, threshold: float = 0
                                 neg_threshold: float = None, min_silence_at_max_speech: int = 98,
                                 use_max_poss_sil_at_max_speech: bool = True, return_probs: bool = False):
     """Batched get_speech_timestamps: audio f32 [B,N] (equal length, or `lengths` per clip with
-    zero padding beyond) -> list (per clip) of lists of {'start','end'} dicts."""
+    zero padding beyond) -> list (per clip) of lists of {'start','end'} dicts.
+    audio may also be a LIST of 1-D clips (float32 on the +-1 scale, or int16) of any lengths, or a vadx.ragged.RaggedClips: the clips
+    then run as one ragged batch (16000 Hz only) -- every clip pays for its own windows, not for the longest clip's -- with the same
+    lists; return_probs gives the list of per-clip score vectors (views of one packed vector)."""
+    if _is_ragged(audio):
+        engine, batch, lens, probs, segs, counts = _segments_ragged(
+            audio, model, lengths, sampling_rate, threshold=threshold, min_speech_duration_ms=min_speech_duration_ms,
+            max_speech_duration_s=max_speech_duration_s, min_silence_duration_ms=min_silence_duration_ms, speech_pad_ms=speech_pad_ms,
+            neg_threshold=neg_threshold, min_silence_at_max_speech=min_silence_at_max_speech,
+            use_max_poss_sil_at_max_speech=use_max_poss_sil_at_max_speech)
+        res = _finish(segs, counts, lens, 16000, return_seconds, time_resolution, 1)
+        return (res, batch.rows(probs)) if return_probs else res
     engine, given, lens, sampling_rate, step, probs, segs, counts = _segments_on_device(
         audio, model, lengths, sampling_rate, threshold=threshold, min_speech_duration_ms=min_speech_duration_ms,
         max_speech_duration_s=max_speech_duration_s, min_silence_duration_ms=min_silence_duration_ms, speech_pad_ms=speech_pad_ms,
@@ -870,6 +1005,9 @@ def get_speech_timestamps_table(audio, model, lengths=None, sampling_rate: int =
     from . import tstable
     if time_resolution != 1:
         raise ValueError(f"time_resolution={time_resolution}: the device table rounds to one decimal (time_resolution=1) only")
+    if _is_ragged(audio):        # a list of clips / a RaggedClips: the ragged launches, the same table
+        engine, batch, lens, probs, segs, counts = _segments_ragged(audio, model, lengths, sampling_rate, **kw)
+        return tstable.from_samples(segs, counts, lens, 16000, fusion_threshold, min_duration, sample_rule=sample_rule)
     engine, given, lens, sampling_rate, step, probs, segs, counts = _segments_on_device(audio, model, lengths, sampling_rate, **kw)
     if probs is None:
         return tstable.empty(given.shape[0], engine.device, sampling_rate, dicts=True)
@@ -885,6 +1023,11 @@ def get_speech_audio_batch(audio, model, lengths=None, drop=False, align=1, retu
     packed[offsets[b] : offsets[b+1]] (up to alignment filler); `timestamps` is what get_speech_timestamps_batch returns.  With a
     sampling rate that is a multiple of 16000 the network sees every step-th sample and the cut is made in the audio as given."""
     from . import chunks
+    if _is_ragged(audio):        # a list of clips / a RaggedClips: the cut is made in the batch's own packed vector
+        engine, batch, lens, probs, segs, counts = _segments_ragged(audio, model, lengths, sampling_rate, **kw)
+        run = chunks.drop_chunks_batch if drop else chunks.collect_chunks_batch
+        packed, offsets = run((segs, counts), batch.pcm, lengths=lens, clip_offsets=batch.clip_off, align=align)
+        return packed, offsets, _finish(segs, counts, lens, 16000, return_seconds, time_resolution, 1)
     engine, given, lens, sampling_rate, step, probs, segs, counts = _segments_on_device(audio, model, lengths, sampling_rate, **kw)
     t = engine.torch
     B = given.shape[0]
