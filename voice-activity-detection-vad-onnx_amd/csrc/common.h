@@ -32,6 +32,12 @@ void set_error(const char *fmt, ...);
         }                                  \
     } while (0)
 
+// true when two records of `bytes` bytes share a byte (a stream tick reads one record and writes the other)
+inline bool records_overlap(const void *a, const void *b, size_t bytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return !(x + bytes <= y || y + bytes <= x);
+}
+
 // Raise a kernel's dynamic-LDS limit once PER DEVICE (the attribute is per device; engines accept device="cuda:N", so a
 // process-wide flag would leave the kernel at the 64 KB default on the second GPU) and thread-safely.
 #define VADX_DYN_LDS(kernel_expr, bytes)                                                                              \

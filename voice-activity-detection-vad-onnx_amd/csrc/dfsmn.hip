@@ -2181,12 +2181,6 @@ extern "C" size_t vadx_dfsmn_stream_state_bytes(int streams, int window_len, int
     return streams > 0 && C > 0 && (channels == 1 || channels == 2) ? srec_bytes(streams, C, channels) : 0;
 }
 
-// true when two records of `bytes` bytes share a byte
-static bool records_overlap(const void *a, const void *b, size_t bytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return !(x + bytes <= y || y + bytes <= x);
-}
-
 extern "C" int vadx_dfsmn_stream_windows(const int16_t *near, const int16_t *far, int64_t row_stride, int streams, int n_slots, int windows,
                                          int window_len, int look_backward, const int32_t *slot, const uint8_t *reset, const void *state_in,
                                          void *state_out, int16_t *near_buf, int16_t *far_buf, void *stream) {
@@ -2200,7 +2194,7 @@ extern "C" int vadx_dfsmn_stream_windows(const int16_t *near, const int16_t *far
                         "(window_len - (look_backward + 1) * 320 > 0)", window_len, look_backward);
     VADX_REQUIRE(row_stride >= (int64_t)windows * (window_len - C), "vadx_dfsmn_stream_windows: row_stride=%lld must hold windows * stride = %lld samples",
                  (long long)row_stride, (long long)windows * (window_len - C));
-    VADX_REQUIRE(!records_overlap(state_in, state_out, srec_bytes(streams, C, ch)), "vadx_dfsmn_stream_windows: state_in and state_out overlap");
+    VADX_REQUIRE(!vadx::records_overlap(state_in, state_out, srec_bytes(streams, C, ch)), "vadx_dfsmn_stream_windows: state_in and state_out overlap");
     VADX_REQUIRE(((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 15) == 0 &&
                  ((reinterpret_cast<uintptr_t>(near) | reinterpret_cast<uintptr_t>(far) | reinterpret_cast<uintptr_t>(near_buf) |
                    reinterpret_cast<uintptr_t>(far_buf)) & 1) == 0 && (reinterpret_cast<uintptr_t>(slot) & 3) == 0,
@@ -2223,7 +2217,7 @@ extern "C" int vadx_dfsmn_stream_vote(const float *vad, int streams, int n_slots
                  "vadx_dfsmn_stream_vote: streams=%d n_slots=%d windows=%d frames=%d must be positive", streams, n_slots, windows, frames);
     VADX_REQUIRE(look_backward >= 1 && look_backward < frames, "vadx_dfsmn_stream_vote: look_backward=%d outside [1, %d)", look_backward, frames);
     VADX_REQUIRE(channels == 1 || channels == 2, "vadx_dfsmn_stream_vote: channels=%d must be 1 or 2", channels);
-    VADX_REQUIRE(!records_overlap(state_in, state_out, srec_bytes(streams, (look_backward + 1) * SFRAME, channels)),
+    VADX_REQUIRE(!vadx::records_overlap(state_in, state_out, srec_bytes(streams, (look_backward + 1) * SFRAME, channels)),
                  "vadx_dfsmn_stream_vote: state_in and state_out overlap");
     VADX_REQUIRE(((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 15) == 0 && (reinterpret_cast<uintptr_t>(slot) & 3) == 0,
                  "vadx_dfsmn_stream_vote: the records must be 16-byte aligned, slot 4-byte");

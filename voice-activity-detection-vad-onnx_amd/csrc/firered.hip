@@ -1199,9 +1199,9 @@ extern "C" int vadx_firered_stream_tick(const vadx_firered_cfg *cfg, const float
     const int ws = post->smooth_window_size < 1 ? 1 : post->smooth_window_size;
     VADX_REQUIRE(ws <= SP_MAXWS, "vadx_firered_stream_tick: smooth_window_size %d > %d", ws, SP_MAXWS);
     const size_t cache_words = tick_cache_words(d, streams), bytes = (cache_words + (size_t)streams * TK_HDR) * 4;
-    {   const uintptr_t x = reinterpret_cast<uintptr_t>(state_in), y = reinterpret_cast<uintptr_t>(state_out);
-        VADX_REQUIRE(x + bytes <= y || y + bytes <= x, "vadx_firered_stream_tick: state_in and state_out overlap");
-        VADX_REQUIRE(((x | y) & 15) == 0, "vadx_firered_stream_tick: records must be 16-byte aligned"); }
+    VADX_REQUIRE(!vadx::records_overlap(state_in, state_out, bytes), "vadx_firered_stream_tick: state_in and state_out overlap");
+    VADX_REQUIRE(((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 15) == 0,
+                 "vadx_firered_stream_tick: records must be 16-byte aligned");
     TickArgs a;
     a.logmel = logmel; a.reset = reset; a.active = active;
     a.cin = static_cast<const unsigned *>(state_in); a.hin = a.cin + cache_words;

@@ -1413,12 +1413,6 @@ extern "C" size_t vadx_fsmn_stream_state_bytes(int streams, int look_backward) {
     return streams > 0 && look_backward >= 0 ? rec_bytes(streams, (look_backward + 1) * 160) : 0;
 }
 
-// true when two records of `bytes` bytes share a byte
-static bool records_overlap(const void *a, const void *b, size_t bytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return !(x + bytes <= y || y + bytes <= x);
-}
-
 extern "C" int vadx_fsmn_stream_windows(const int16_t *samples, int64_t row_stride, int streams, int windows, int window_len,
                                         int look_backward, const uint8_t *reset, const uint8_t *active, const void *state_in,
                                         void *state_out, int16_t *window_buf, void *stream) {
@@ -1433,7 +1427,7 @@ extern "C" int vadx_fsmn_stream_windows(const int16_t *samples, int64_t row_stri
     VADX_REQUIRE(row_stride >= (int64_t)windows * stride && row_stride % 8 == 0,
                  "vadx_fsmn_stream_windows: row_stride=%lld must be a multiple of 8 and hold windows * stride = %lld samples",
                  (long long)row_stride, (long long)windows * stride);
-    VADX_REQUIRE(!records_overlap(state_in, state_out, rec_bytes(streams, C)), "vadx_fsmn_stream_windows: state_in and state_out overlap");
+    VADX_REQUIRE(!vadx::records_overlap(state_in, state_out, rec_bytes(streams, C)), "vadx_fsmn_stream_windows: state_in and state_out overlap");
     VADX_REQUIRE(((reinterpret_cast<uintptr_t>(samples) | reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out) |
                    reinterpret_cast<uintptr_t>(window_buf)) & 15) == 0,
                  "vadx_fsmn_stream_windows: samples, records and window_buf must be 16-byte aligned");
@@ -1457,7 +1451,7 @@ extern "C" int vadx_fsmn_stream_run(const vadx_fsmn_dims *dims, const float *pac
     int rc = loop_args("vadx_fsmn_stream_run", d, lp, true, &a);
     if (rc) return rc;
     VADX_REQUIRE(tail || lp->look_backward == 0, "vadx_fsmn_stream_run: NULL tail with look_backward=%d", lp->look_backward);
-    VADX_REQUIRE(!records_overlap(state_in, state_out, rec_bytes(streams, (lp->look_backward + 1) * 160)),
+    VADX_REQUIRE(!vadx::records_overlap(state_in, state_out, rec_bytes(streams, (lp->look_backward + 1) * 160)),
                  "vadx_fsmn_stream_run: state_in and state_out overlap");
     VADX_REQUIRE(((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 15) == 0,
                  "vadx_fsmn_stream_run: records must be 16-byte aligned");

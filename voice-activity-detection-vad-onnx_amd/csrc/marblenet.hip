@@ -1328,7 +1328,6 @@ extern "C" int vadx_marblenet_stream_tick(const vadx_frontend_cfg *fe, const flo
     VADX_REQUIRE(k >= 1 && k <= K_MAX, "%s: k=%d frames per tick is outside [1, %d]", who, k, K_MAX);
     VADX_REQUIRE(sample_stride >= (int64_t)k * HOP2, "%s: sample_stride=%lld is shorter than a row of k * 320 = %d samples", who,
                  (long long)sample_stride, k * HOP2);
-    VADX_REQUIRE(state_in != state_out, "%s: state_out must be a second record (state_in is never written)", who);
     int ar;
     unsigned *flag;
     if (int rc = ragged_arith(who, cfg, &ar, &flag)) return rc;
@@ -1344,6 +1343,8 @@ extern "C" int vadx_marblenet_stream_tick(const vadx_frontend_cfg *fe, const flo
                  streams, k, need);
     VADX_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(state_in) & 15) == 0 &&
                  (reinterpret_cast<uintptr_t>(state_out) & 15) == 0, "%s: workspace and records must be 16-byte aligned", who);
+    VADX_REQUIRE(!vadx::records_overlap(state_in, state_out, vadx_marblenet_stream_state_bytes(streams)),
+                 "%s: state_out must be a second record (state_in is never written)", who);
     const int cap = k + LOOKAHEAD;
     int tiles[5];
     for (int i = 0; i < 5; ++i) tiles[i] = (k + ST_EXTRA[i] + TILE - 1) / TILE;

@@ -193,9 +193,7 @@ extern "C" int vadx_silero_stream_run(const float *packed, const vadx_silero_ite
                  (long long)row_stride, win, (long long)windows * win);
     const int a = cfg ? cfg->arithmetic : VADX_ARITH_AUTO;
     VADX_REQUIRE(a >= VADX_ARITH_AUTO && a <= VADX_ARITH_F16X2, "vadx_silero_stream_run: cfg->arithmetic=%d is not one of VADX_ARITH_*", a);
-    const size_t rb = record_bytes(streams);
-    const char *pin = static_cast<const char *>(state_in), *pout = static_cast<const char *>(state_out);
-    VADX_REQUIRE(pin + rb <= pout || pout + rb <= pin, "vadx_silero_stream_run: state_in and state_out overlap");
+    VADX_REQUIRE(!vadx::records_overlap(state_in, state_out, record_bytes(streams)), "vadx_silero_stream_run: state_in and state_out overlap");
     const size_t need = vadx_silero_stream_workspace_bytes(streams, windows);
     if (workspace_bytes < need) {
         vadx::set_error("vadx_silero_stream_run: workspace %zu B < required %zu B", workspace_bytes, need);

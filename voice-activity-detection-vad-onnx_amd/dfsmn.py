@@ -13,6 +13,7 @@ import numpy as np
 from . import _lib
 from .clips import flag_timestamps, pad_batch
 from .session import Session, _Meta, io_types
+from .stream import WindowStreamBatch
 
 F_BINS, CEPS_F, CH = 160, 81, 20
 
@@ -720,10 +721,11 @@ class DfsmnEngine:
 SHDR_WORDS, SH_SIL, SH_PRIMED, SH_DONE = 4, 0, 1, 2      # header words of a stream record (csrc/dfsmn.hip)
 
 
-class DfsmnStreamBatch:
+class DfsmnStreamBatch(WindowStreamBatch):
     """`streams` live DFSMN streams on the device (vadx_dfsmn_stream_windows + the network + vadx_dfsmn_stream_vote): every `step` advances
     each active stream by k analysis windows.  What the reference loop carries (Inference_DFSMN_VAD_ONNX.py:221-273) -- the vote's `silence`
-    and the (look_backward + 1) * 320 samples two windows share, per channel -- stays in a device record (two, ping-ponged).  Per stream, the
+    and the (look_backward + 1) * 320 samples two windows share, per channel -- stays in the device `record` (DESIGN.md "Stream batches"):
+    header u32 [S, 4] = {silence, has a carry, windows done (u64)}, then the carry int16 [channels, S, (lb + 1) * 320].  Per stream, the
     flags of successive ticks followed by the last tick's tail are bit for bit `vadx_dfsmn_vote` over the concatenated audio's windows.  An
     inactive stream costs no network time: only the active streams' windows are assembled and run.
 
@@ -732,36 +734,28 @@ class DfsmnStreamBatch:
     with a gain of its own, and end a stream on the window grid (`pad_to_window_grid`).  near_only=True: one channel, on an engine that
     carries the export's constants (`set_near_only_constants`)."""
 
+    frame_s = DfsmnEngine.FRAME / 16000
+
     def __init__(self, engine, streams, speaking_score=0.5, silence_score=0.5, near_only=False):
         if not isinstance(engine, DfsmnEngine):
             raise TypeError("DfsmnStreamBatch needs a vadx.dfsmn.DfsmnEngine")
-        self.engine, self.streams = engine, int(streams)
-        if self.streams <= 0:
-            raise ValueError(f"streams={streams} must be positive")
+        self.channels = 1 if near_only else 2
+        self.lb, self.stride = engine.grid()
+        nb = _lib.lib().vadx_dfsmn_stream_state_bytes(int(streams), engine.L, self.lb, self.channels)
+        super().__init__(engine, streams, nb)
         if near_only and getattr(engine, "pow_far", None) is None:
             raise ValueError("near-only streams: call engine.set_near_only_constants(pow_far, far_comp) first")
-        self.channels = 1 if near_only else 2
-        self.speaking_score, self.silence_score = float(speaking_score), float(silence_score)
-        self.lb, self.stride = engine.grid()
-        self.slide = engine.T_A - self.lb
-        self.carry = engine.L - self.stride               # (lb + 1) * 320 samples
-        t = engine.torch
-        nb = _lib.lib().vadx_dfsmn_stream_state_bytes(self.streams, engine.L, self.lb, self.channels)
         if nb == 0:
             raise ValueError(f"no stream record for window {engine.L}, look-back {self.lb}")
-        self._rec = [t.zeros(nb, dtype=t.uint8, device=engine.device) for _ in range(2)]
-        self._cur = 0
-        self._primed = np.zeros(self.streams, dtype=bool)        # host mirror of "the stream has a carry"
-        self._pending = np.zeros(self.streams, dtype=bool)       # reset_states() requests not yet applied to an active tick
-
-    @property
-    def record(self):
-        """The current device record (uint8): header u32 [S, 4] = {silence, has a carry, windows done (u64)}, then the carry int16
-        [channels, S, (lb + 1) * 320]."""
-        return self._rec[self._cur]
+        self.speaking_score, self.silence_score = float(speaking_score), float(silence_score)
+        self.slide = engine.T_A - self.lb
+        self.carry = engine.L - self.stride               # (lb + 1) * 320 samples
 
     def _header(self, record):
         return record[:self.streams * SHDR_WORDS * 4].view(self.engine.torch.int32).view(self.streams, SHDR_WORDS)
+
+    def _primed_words(self):
+        return self._header(self.record)[:, SH_PRIMED]
 
     def carries(self, record=None):
         """int16 view [channels, S, carry] of a record's (default: the current one's) carried samples."""
@@ -779,42 +773,6 @@ class DfsmnStreamBatch:
         is frame windows_done * (51 - look_backward) + i of its audio, 20 ms per frame."""
         return self._header(self.record).view(self.engine.torch.int64)[:, SH_DONE // 2].cpu().numpy()
 
-    def load_record(self, record):
-        """Continue from a saved copy of `record` (uint8, same streams and channels): the bytes are copied into the current record."""
-        t = self.engine.torch
-        r = record if t.is_tensor(record) else t.from_numpy(np.ascontiguousarray(record))
-        if r.dtype != t.uint8 or r.numel() != self.record.numel():
-            raise ValueError(f"record must be uint8 [{self.record.numel()}], got {r.dtype} [{r.numel()}]")
-        self.record.copy_(r.reshape(-1))
-        self._primed = self._header(self.record)[:, SH_PRIMED].cpu().numpy() != 0
-        self._pending[:] = False
-
-    def reset_states(self, streams=None):
-        """None = every stream; else stream indices or a bool mask [S].  Applies at the next tick in which the stream is active."""
-        if streams is None:
-            self._pending[:] = True
-            return
-        idx = np.asarray(streams.cpu() if hasattr(streams, "cpu") else streams)
-        if idx.dtype == bool:
-            self._pending |= self._mask(idx, "reset mask")
-        else:
-            self._pending[idx.astype(np.int64).reshape(-1)] = True
-
-    def _mask(self, m, name):
-        a = np.asarray(m.cpu() if hasattr(m, "cpu") else m).astype(bool).reshape(-1)
-        if a.shape != (self.streams,):
-            raise ValueError(f"{name} must have shape ({self.streams},), got {a.shape}")
-        return a
-
-    def samples_needed(self, windows, reset=None):
-        """int64 [S]: new samples (per channel) each stream consumes in the next tick of `windows` windows: windows * stride with a
-        carry, L + (windows - 1) * stride without one (first tick, or reset -- requested here or pending from reset_states)."""
-        k = int(windows)
-        if k < 1:
-            raise ValueError(f"windows={windows} must be at least 1")
-        fresh = ~self._primed | self._pending | (False if reset is None else self._mask(reset, "reset"))
-        return np.where(fresh, self.engine.L + (k - 1) * self.stride, k * self.stride).astype(np.int64)
-
     def step(self, near_i16, far_i16=None, windows=1, reset=None, active=None):
         """near_i16 / far_i16 int16 [S, >= samples_needed(windows, reset).max() over the active streams] (host or device, numpy or torch;
         far_i16 None for near-only streams), each row holding that stream's NEW samples from column 0 -> device tensors (flags u8
@@ -827,14 +785,8 @@ class DfsmnStreamBatch:
             raise ValueError(f"this batch has {self.channels} channel(s): far_i16 must {'not ' if self.channels == 1 else ''}be given")
         xs = []
         for x in (near_i16, far_i16)[:self.channels]:
-            x = x if t.is_tensor(x) else t.from_numpy(np.ascontiguousarray(x))
-            if x.dtype != t.int16:
-                raise ValueError(f"samples must be int16, got {x.dtype}")
-            if x.dim() != 2 or x.shape[0] != S or (xs and x.shape != xs[0].shape):
-                raise ValueError(f"samples must be [{S}, n], the same n for both channels, got {tuple(x.shape)}")
-            xs.append(x)
-        act = np.ones(S, dtype=bool) if active is None else self._mask(active, "active")
-        req = (self._pending | self._mask(reset, "reset") if reset is not None else self._pending) & act      # resets this tick applies
+            xs.append(self._samples(x, f"[{S}, n], the same n for both channels", lambda x: xs and x.shape != xs[0].shape))
+        act, _, reset_d, _, src, dst = self._begin(reset, active, upload_active=False)      # (the slot table below says who is active)
         need = int(self.samples_needed(k, reset)[act].max(initial=0))
         if xs[0].shape[1] < need:
             raise ValueError(f"samples rows hold {xs[0].shape[1]} samples, this tick needs {need} (samples_needed)")
@@ -845,9 +797,7 @@ class DfsmnStreamBatch:
             return flags, tail
         xs = [x.to(eng.device).contiguous() for x in xs]
         slot_d = None if active is None else t.from_numpy(np.where(act, np.cumsum(act) - 1, -1).astype(np.int32)).to(eng.device)
-        reset_d = t.from_numpy(req.astype(np.uint8)).to(eng.device) if req.any() else None
         bufs = [t.empty((n_slots * k, L), dtype=t.int16, device=eng.device) for _ in xs]
-        src, dst = self._rec[self._cur], self._rec[1 - self._cur]
         two = self.channels == 2
         common = (None if slot_d is None else slot_d.data_ptr(), None if reset_d is None else reset_d.data_ptr(), src.data_ptr(), dst.data_ptr())
         with t.cuda.device(eng.device):
@@ -858,16 +808,8 @@ class DfsmnStreamBatch:
         with t.cuda.device(eng.device):
             _lib.check(_lib.lib().vadx_dfsmn_stream_vote(vad.data_ptr(), S, n_slots, k, eng.T_A, self.lb, self.channels, self.speaking_score,
                                                          self.silence_score, *common, flags.data_ptr(), tail.data_ptr(), _lib.stream_ptr()))
-        self._cur = 1 - self._cur
-        self._primed |= act
-        self._pending &= ~act
+        self._end(act)
         return flags, tail
-
-    def timestamps(self, flags_so_far, tail, fusion_threshold=0.3, min_speech_duration=0.2):
-        """One stream's accumulated flags (1-D, every tick so far) + the last tick's tail -> [(start_s, end_s)], the reference's
-        vad_to_timestamps + process_timestamps over its `saved` list."""
-        f = np.concatenate([np.asarray(a.cpu() if hasattr(a, "cpu") else a).reshape(-1) for a in (flags_so_far, tail)])
-        return flag_timestamps(f, DfsmnEngine.FRAME / 16000, fusion_threshold, min_speech_duration)
 
 
 class DfsmnSession(Session):

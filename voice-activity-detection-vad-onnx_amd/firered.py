@@ -15,6 +15,7 @@ from . import vadpost as _vadpost
 from . import weights as _weights
 from .clips import gather_tracks, pad_batch, track_segments, track_table
 from .session import Session, _Meta, require_int16
+from .stream import StreamBatch
 
 SAMPLE_RATE, WINDOW_LENGTH, HOP_LENGTH = 16000, 400, 160
 STREAM_CHUNK_SAMPLES = 2560          # 160 ms (Export_FireRedVAD.py:52-53)
@@ -353,43 +354,33 @@ FireRedEngine.detect_events = _detect_events
 HDR_WORDS, H_COUNT, H_LAST_START, H_DONE = 32, 19, 24, 28      # the record's per-stream header (csrc/firered.hip: TK_HDR, TK_DONE), in 32-bit words
 
 
-class FireRedStreamBatch:
+class FireRedStreamBatch(StreamBatch):
     """`streams` live FireRed Stream-VAD streams on the device (vadx_firered_stream_tick): every `step` advances each stream by `chunks`
     chunks of audio.  What the reference's chunk loop carries (FireRedVAD/Inference_FireRed_ONNX.py:775-822) -- the FIR caches it feeds
-    back and the StreamVadPostprocessor object -- stays in a device record (two, ping-ponged); per tick the front-end and ONE net launch
-    run, and only the events come back.  `post` = the reference class's constructor arguments (smooth window, threshold, pad_start,
-    min_speech, max_speech, min_silence, in frames); cap = segments a stream may end in one tick (None: one per frame, the most there
-    can be).  On "h2" every tick reads the range flag and, when it is raised, recomputes the tick on "split" from the same record into
-    the same record."""
+    back and the StreamVadPostprocessor object -- stays in the device `record` (DESIGN.md "Stream batches"; its first S*R*P*pad floats are
+    the FIR caches [S, R, P, pad], the headers follow); per tick the front-end and ONE net launch run, and only the events come back.
+    `post` = the reference class's constructor arguments (smooth window, threshold, pad_start, min_speech, max_speech, min_silence, in
+    frames); cap = segments a stream may end in one tick (None: one per frame, the most there can be).  On "h2" every tick reads the
+    range flag and, when it is raised, recomputes the tick on "split" from the same record into the same record."""
 
     def __init__(self, engine, streams, post=(5, 0.4, 5, 8, 2000, 20), cap=None):
         if not isinstance(engine, FireRedEngine):
             raise TypeError("FireRedStreamBatch needs a vadx.firered.FireRedEngine")
-        self.engine, self.streams, self.cap = engine, int(streams), cap
-        if self.streams <= 0:
-            raise ValueError(f"streams={streams} must be positive")
+        nb = _lib.lib().vadx_firered_stream_state_bytes(C.byref(engine.cfg), int(streams))
+        super().__init__(engine, streams, nb)
+        self.cap = cap
         if engine.cfg.N2 != 0:
             raise ValueError(f"the streaming model has no look-ahead filter, these weights have N2 = {engine.cfg.N2}")
         if max(1, int(post[0])) > 16:
             raise ValueError(f"smooth_window_size {post[0]} > 16: the device record's ring buffer holds 16 frames")
         self._prm = _lib.StreamVadPostParams(int(post[0]), float(np.float32(post[1])), *(int(v) for v in post[2:6]))
         self.frames_per_second = 100
-        t = engine.torch
         R, _, P, pad = engine.cache_shape
         self._cache_floats = self.streams * R * P * pad
         self._hdr_at = (self._cache_floats + 3) // 4 * 16             # the headers start on the next multiple of 16 bytes
-        nb = _lib.lib().vadx_firered_stream_state_bytes(C.byref(engine.cfg), self.streams)
         if nb != self._hdr_at + self.streams * HDR_WORDS * 4:
             raise _lib.VadxError(f"vadx_firered_stream_state_bytes = {nb}: not the record this binding was written for")
-        self._rec = [t.zeros(nb, dtype=t.uint8, device=engine.device) for _ in range(2)]
-        self._cur = 0
-        self._pending = np.zeros(self.streams, dtype=bool)       # reset_states() requests not yet applied to an active tick
         self.open_start = None                                   # int32 [S] (device) of the last tick: 0-based start frame of the open segment, -1 = none
-
-    @property
-    def record(self):
-        """The current device record (uint8); its first S*R*P*pad floats are the FIR caches [S, R, P, pad]."""
-        return self._rec[self._cur]
 
     @property
     def caches(self):
@@ -412,31 +403,6 @@ class FireRedStreamBatch:
         tick is frame frames_done + i of its audio, 10 ms per frame."""
         return self.headers()[:, H_DONE:H_DONE + 2].contiguous().view(self.engine.torch.int64)[:, 0].cpu().numpy()
 
-    def load_record(self, record):
-        """Continue from a saved copy of `record` (uint8, same streams and weights): the bytes are copied into the current record."""
-        r = record if self.engine.torch.is_tensor(record) else self.engine.torch.from_numpy(np.ascontiguousarray(record))
-        if r.dtype != self.engine.torch.uint8 or r.numel() != self.record.numel():
-            raise ValueError(f"record must be uint8 [{self.record.numel()}], got {r.dtype} [{r.numel()}]")
-        self.record.copy_(r.reshape(-1))
-        self._pending[:] = False
-
-    def reset_states(self, streams=None):
-        """None = every stream; else stream indices or a bool mask [S].  Applies at the next tick in which the stream is active."""
-        if streams is None:
-            self._pending[:] = True
-            return
-        idx = np.asarray(streams.cpu() if hasattr(streams, "cpu") else streams)
-        if idx.dtype == bool:
-            self._pending |= self._mask(idx, "reset mask")
-        else:
-            self._pending[idx.astype(np.int64).reshape(-1)] = True
-
-    def _mask(self, m, name):
-        a = np.asarray(m.cpu() if hasattr(m, "cpu") else m).astype(bool).reshape(-1)
-        if a.shape != (self.streams,):
-            raise ValueError(f"{name} must have shape ({self.streams},), got {a.shape}")
-        return a
-
     def open_segments(self):
         """Per stream the (start_s, end_s) of the segment still open after its last frame, or None: what the reference's process_batch
         appends at the end of its input (Export_FireRedVAD.py:1336-1338).  Read from the record; nothing is closed."""
@@ -454,13 +420,9 @@ class FireRedStreamBatch:
         workgroup (0 = the library's choice); no result depends on it."""
         eng, t = self.engine, self.engine.torch
         k, S = int(chunks), self.streams
-        x = samples_i16 if t.is_tensor(samples_i16) else t.from_numpy(np.ascontiguousarray(samples_i16))
-        if x.dtype != t.int16:
-            raise ValueError(f"samples must be int16, got {x.dtype}")
         if k < 1:
             raise ValueError(f"chunks={chunks} must be at least 1")
-        if x.dim() != 2 or x.shape[0] != S or x.shape[1] % k:
-            raise ValueError(f"samples must be [{S}, chunks * n], got {tuple(x.shape)} at chunks={k}")
+        x = self._samples(samples_i16, f"[{S}, chunks * n]", lambda x: x.shape[1] % k, where=f" at chunks={k}")
         n = x.shape[1] // k
         if n < WINDOW_LENGTH:
             raise ValueError(f"a stream chunk needs at least {WINDOW_LENGTH} samples, got {n}")
@@ -468,21 +430,17 @@ class FireRedStreamBatch:
         F = k * T
         if F > MAX_FRAMES:
             raise ValueError(f"a stream tick holds at most {MAX_FRAMES} frames, {k} chunks of {n} samples are {F}")
-        act = np.ones(S, dtype=bool) if active is None else self._mask(active, "active")
-        req = (self._pending | self._mask(reset, "reset") if reset is not None else self._pending) & act      # resets this tick applies
         gmax = MAX_FRAMES // F                                    # vadx_firered_stream_group_max
         if not 0 <= int(group) <= gmax:
             raise ValueError(f"group={group} outside [0, {gmax}] at {F} frames per tick")
+        act, _, reset_d, act_d, src, dst = self._begin(reset, active)
         fe = eng._frontend_for(n)
         logmel = fe.logmel(x.to(eng.device), k, n)
-        act_d = None if active is None else t.from_numpy(act.astype(np.uint8)).to(eng.device)
-        reset_d = t.from_numpy(req.astype(np.uint8)).to(eng.device) if req.any() else None
         cap = int(self.cap) if self.cap else F                    # F: a forced split per frame is the most a tick can end
         probs = t.empty((S, eng.odim, F), dtype=t.float32, device=eng.device)
         segs = t.empty((S, cap, 2), dtype=t.int32, device=eng.device)
         counts = t.empty((S,), dtype=t.int32, device=eng.device)
         opened = t.empty((S,), dtype=t.int32, device=eng.device)
-        src, dst = self._rec[self._cur], self._rec[1 - self._cur]
         Lb = _lib.lib()
 
         def launch(mode, cfg, packed):
@@ -495,8 +453,7 @@ class FireRedStreamBatch:
                                                        probs.data_ptr(), segs.data_ptr(), counts.data_ptr(), cap, opened.data_ptr(),
                                                        _lib.stream_ptr()))
         eng.blobs.guarded(launch)
-        self._cur = 1 - self._cur
-        self._pending &= ~act
+        self._end(act)
         self.open_start = opened
         cn = counts.cpu().numpy()
         used = int(cn.max())

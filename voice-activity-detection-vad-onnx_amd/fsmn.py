@@ -19,6 +19,7 @@ from . import timestamps as _ts
 from . import weights as _weights
 from .clips import flag_timestamps, pad_batch, pad_to_window_grid  # noqa: F401  (`vadx.fsmn.pad_to_window_grid` is the name callers use)
 from .session import Session, _Meta, io_types, require_int16
+from .stream import WindowStreamBatch
 
 SAMPLE_RATE = 16000
 OUTPUT_FRAME_LENGTH = 160
@@ -382,47 +383,37 @@ class FsmnSession(Session):
         return [res[n] for n in names]
 
 
-class FsmnStreamBatch:
+class FsmnStreamBatch(WindowStreamBatch):
     """`streams` live FSMN streams on the device (vadx_fsmn_stream_windows + vadx_fsmn_stream_run): every `step` advances each stream by
     k analysis windows.  What the reference loop carries (FSMN/Inference_FSMN_VAD_ONNX.py:162-167, 176-234) -- the four FIR caches, the
-    noise floor, the vote's `silence` and the (look_backward + 1) * 160 samples two windows share -- stays in a device record (two,
-    ping-ponged); nothing crosses to the host per window.  Per stream, the flags of successive ticks followed by the last tick's tail are
-    bit for bit `FsmnEngine.flags` over the concatenated audio.  On "h2" every tick reads the range flag and, when it is raised,
-    recomputes the tick on "split" from the same record into the same record.
+    noise floor, the vote's `silence` and the (look_backward + 1) * 160 samples two windows share -- stays in the device `record`
+    (DESIGN.md "Stream batches"; its first S*4*128*19 floats are the FIR caches [S,4,128,19], then the headers, then the carries); nothing
+    crosses to the host per window.  Per stream, the flags of successive ticks followed by the last tick's tail are bit for bit
+    `FsmnEngine.flags` over the concatenated audio.  On "h2" every tick reads the range flag and, when it is raised, recomputes the tick
+    on "split" from the same record into the same record.
 
     A stream's audio must end on the window grid: padding the end of a stream with noise is the caller's job (`pad_to_window_grid`), as
     it is for `flags`."""
+
+    frame_s = OUTPUT_FRAME_LENGTH / SAMPLE_RATE
 
     def __init__(self, engine, streams, *, look_backward_s=0.3, speaking_score=0.5, silence_score=0.5, snr_threshold=10.0,
                  noise_init_dB=30.0, one_minus_speech_threshold=1.0):
         if not isinstance(engine, FsmnEngine):
             raise TypeError("FsmnStreamBatch needs a vadx.fsmn.FsmnEngine")
-        self.engine, self.streams = engine, int(streams)
         if engine.long_windows and engine.T > LOOP_MAX_FRAMES:        # live streams want short windows
             raise ValueError(f"FsmnStreamBatch: the engine's input_audio_length={engine.L} gives {engine.T} frames per window; the stream "
                              f"kernel takes at most {LOOP_MAX_FRAMES} (input_audio_length <= {LOOP_MAX_FRAMES * OUTPUT_FRAME_LENGTH - 1}): "
                              f"long windows are not served as live streams")
-        if self.streams <= 0:
-            raise ValueError(f"streams={streams} must be positive")
         self.lb, self.stride = engine.grid(look_backward_s)
-        self.slide = engine.T - self.lb
-        self.carry = engine.L - self.stride              # (lb + 1) * 160 samples
         if self.lb < 0 or self.stride <= 0 or self.lb >= engine.T - 2:
             raise ValueError(f"look_backward_s={look_backward_s}: {self.lb} frames leave no window stride")
+        super().__init__(engine, streams, _lib.lib().vadx_fsmn_stream_state_bytes(int(streams), self.lb))
+        self.slide = engine.T - self.lb
+        self.carry = engine.L - self.stride              # (lb + 1) * 160 samples
         self._lp = _loop_params(self.lb, speaking_score, silence_score, snr_threshold, noise_init_dB, one_minus_speech_threshold)
-        t = engine.torch
-        nb = _lib.lib().vadx_fsmn_stream_state_bytes(self.streams, self.lb)
-        self._rec = [t.zeros(nb, dtype=t.uint8, device=engine.device) for _ in range(2)]
-        self._cur = 0
         self._wbuf = None
-        self._primed = np.zeros(self.streams, dtype=bool)        # host mirror of "the stream has a carry"
-        self._pending = np.zeros(self.streams, dtype=bool)       # reset_states() requests not yet applied to an active tick
         self.noise_trace = None                                  # float32 [S, windows] of the last tick: noise floor after each window
-
-    @property
-    def record(self):
-        """The current device record (uint8); its first S*4*128*19 floats are the FIR caches [S,4,128,19]."""
-        return self._rec[self._cur]
 
     def _section(self, record, i):
         """Section i (CACHES, HEADER or CARRY) of `record` as a uint8 view [S, that section's bytes per stream]."""
@@ -444,42 +435,8 @@ class FsmnStreamBatch:
         is frame windows_done * (T - look_backward) + i of its audio, 10 ms per frame."""
         return self._section(self.record, HEADER).view(self.engine.torch.int64)[:, H_DONE // 2].cpu().numpy()
 
-    def load_record(self, record):
-        """Continue from a saved copy of `record` (uint8, same streams and look-back): the bytes are copied into the current record."""
-        r = record if self.engine.torch.is_tensor(record) else self.engine.torch.from_numpy(np.ascontiguousarray(record))
-        if r.dtype != self.engine.torch.uint8 or r.numel() != self.record.numel():
-            raise ValueError(f"record must be uint8 [{self.record.numel()}], got {r.dtype} [{r.numel()}]")
-        self.record.copy_(r.reshape(-1))
-        self._primed = self._section(self.record, HEADER).view(self.engine.torch.int32)[:, H_PRIMED].cpu().numpy() != 0
-        self._pending[:] = False
-
-    def reset_states(self, streams=None):
-        """None = every stream; else stream indices or a bool mask [S].  Applies at the next tick in which the stream is active."""
-        if streams is None:
-            self._pending[:] = True
-            return
-        idx = np.asarray(streams.cpu() if hasattr(streams, "cpu") else streams)
-        if idx.dtype == bool:
-            self._pending |= self._mask(idx, "reset mask")
-        else:
-            self._pending[idx.astype(np.int64).reshape(-1)] = True
-
-    def _mask(self, m, name):
-        a = np.asarray(m.cpu() if hasattr(m, "cpu") else m).astype(bool).reshape(-1)
-        if a.shape != (self.streams,):
-            raise ValueError(f"{name} must have shape ({self.streams},), got {a.shape}")
-        return a
-
-    def _fresh(self, reset):
-        return ~self._primed | self._pending | (False if reset is None else self._mask(reset, "reset"))
-
-    def samples_needed(self, windows, reset=None):
-        """int64 [S]: new samples each stream consumes in the next tick of `windows` windows: windows * stride with a carry,
-        L + (windows - 1) * stride without one (first tick, or reset -- requested here or pending from reset_states)."""
-        k = int(windows)
-        if k < 1:
-            raise ValueError(f"windows={windows} must be at least 1")
-        return np.where(self._fresh(reset), self.engine.L + (k - 1) * self.stride, k * self.stride).astype(np.int64)
+    def _primed_words(self):
+        return self._section(self.record, HEADER).view(self.engine.torch.int32)[:, H_PRIMED]
 
     def step(self, samples_i16, windows=1, reset=None, active=None):
         """samples_i16 int16 [S, >= samples_needed(windows, reset).max() over the active streams] (host or device, numpy or torch), each
@@ -488,13 +445,8 @@ class FsmnStreamBatch:
         reset / active: bool [S] or None; an inactive stream keeps its record bit for bit, ignores a reset, and reads 255."""
         eng, t = self.engine, self.engine.torch
         k, S, L = int(windows), self.streams, self.engine.L
-        x = samples_i16 if t.is_tensor(samples_i16) else t.from_numpy(np.ascontiguousarray(samples_i16))
-        if x.dtype != t.int16:
-            raise ValueError(f"samples must be int16, got {x.dtype}")
-        if x.dim() != 2 or x.shape[0] != S:
-            raise ValueError(f"samples must be [{S}, n], got {tuple(x.shape)}")
-        act = np.ones(S, dtype=bool) if active is None else self._mask(active, "active")
-        req = (self._pending | self._mask(reset, "reset") if reset is not None else self._pending) & act      # resets this tick applies
+        x = self._samples(samples_i16)
+        act, _, reset_d, act_d, src, dst = self._begin(reset, active)
         need = int(self.samples_needed(k, reset)[act].max(initial=0))       # refuses windows < 1; an active stream is fresh without a carry or with a reset
         if x.shape[1] < need:
             raise ValueError(f"samples rows hold {x.shape[1]} samples, this tick needs {need} (samples_needed)")
@@ -504,12 +456,9 @@ class FsmnStreamBatch:
             pad[:, :x.shape[1]] = x
             x = pad
         row = int(x.stride(0)) if S > 1 else int(x.shape[1]) // 8 * 8
-        act_d = None if active is None else t.from_numpy(act.astype(np.uint8)).to(eng.device)
-        reset_d = t.from_numpy(req.astype(np.uint8)).to(eng.device) if req.any() else None
         if self._wbuf is None or self._wbuf.numel() < S * k * L:
             self._wbuf = t.empty(S * k * L, dtype=t.int16, device=eng.device)
         wbuf = self._wbuf[:S * k * L].view(S, k * L)
-        src, dst = self._rec[self._cur], self._rec[1 - self._cur]
         Lb = _lib.lib()
         with t.cuda.device(eng.device):
             _lib.check(Lb.vadx_fsmn_stream_windows(x.data_ptr(), row, S, k, L, self.lb, None if reset_d is None else reset_d.data_ptr(),
@@ -528,14 +477,6 @@ class FsmnStreamBatch:
                                                    flags.data_ptr(), tail.data_ptr() if self.lb else None, trace.data_ptr(),
                                                    _lib.stream_ptr()))
         eng.blobs.guarded(launch)
-        self._cur = 1 - self._cur
-        self._primed |= act
-        self._pending &= ~act
+        self._end(act)
         self.noise_trace = trace
         return flags, tail
-
-    def timestamps(self, flags_so_far, tail, fusion_threshold=0.3, min_speech_duration=0.2):
-        """One stream's accumulated flags (1-D, every tick so far) + the last tick's tail -> [(start_s, end_s)], the reference's
-        vad_to_timestamps + process_timestamps over its `saved` list."""
-        f = np.concatenate([np.asarray(a.cpu() if hasattr(a, "cpu") else a).reshape(-1) for a in (flags_so_far, tail)])
-        return flag_timestamps(f, OUTPUT_FRAME_LENGTH / SAMPLE_RATE, fusion_threshold, min_speech_duration)

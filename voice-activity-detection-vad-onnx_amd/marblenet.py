@@ -18,6 +18,7 @@ from . import vadpost as _vadpost
 from . import weights as _weights
 from .clips import gather_tracks, pad_batch, track_segments, track_table
 from .session import Session, _Meta, io_types, require_int16
+from .stream import StreamBatch
 
 SAMPLE_RATE = 16000
 OUTPUT_FRAME_SHIFT_S = 320 / 16000
@@ -498,15 +499,17 @@ def check_stream_step(k, n_samples, final):
                          "score frames until its final tick")
 
 
-class MarbleNetStreamBatch:
+class MarbleNetStreamBatch(StreamBatch):
     """`streams` live Frame-VAD MarbleNet streams on the device (vadx_marblenet_stream_tick).  A stream is the audio of one virtual clip
     arriving in pieces; every `step` feeds each stream up to k frames (k * 320 samples) and returns the score frames that became final:
     a stream stands 73 frames (1.46 s) behind its audio, and its last tick (`final`) emits the remaining look-ahead against the zero
     padding behind the clip's last frame.  The concatenated scores are what `MarbleNetEngine.run(clip[None])` gives for the whole
     clip (n // 320 frames): bit for bit wherever a frame reads none of the log-mel frames `run` computes in its front-end's tail tile
-    (the clip's last F mod 64 <= 48 frames, F = n // 160 + 1), one float32 ulp of the log-mel apart behind that (DESIGN.md 4s).  Per stream only the left context of every launch boundary is carried, in a device record (two,
-    ping-ponged; all-zero bytes = a fresh stream).  On "h2" every tick reads the range flag and, when it is raised, is recomputed on
-    float32 from the same record; that counts once in engine.range_fallbacks."""
+    (the clip's last F mod 64 <= 48 frames, F = n // 160 + 1), one float32 ulp of the log-mel apart behind that (DESIGN.md 4s).  Per stream only the left context of every launch boundary is carried, in the device
+    `record` (DESIGN.md "Stream batches"; streams * 46 048 bytes, layout in include/vadx.h).  There is no `active` mask here -- a stream
+    without audio has n_samples = 0 -- and a reset request applies at the very next tick, before that tick's audio, whether or not the
+    stream gets any.  On "h2" every tick reads the range flag and, when it is raised, is recomputed on float32 from the same record; that
+    counts once in engine.range_fallbacks."""
 
     def __init__(self, engine, streams):
         if int(getattr(engine, "in_sample_rate", SAMPLE_RATE)) != SAMPLE_RATE:
@@ -514,27 +517,18 @@ class MarbleNetStreamBatch:
         if not getattr(engine, "fused", False):
             raise ValueError("MarbleNetStreamBatch is built for the published MarbleNet 3x2x64 layout (the fused kernels); this engine was "
                              "constructed with another `blocks` layout")
-        self.engine, self.streams = engine, int(streams)
-        if self.streams < 1:
+        if int(streams) < 1:                # (the wording of vadx_marblenet_stream_tick's own refusal)
             raise ValueError(f"streams={streams} must be at least 1")
-        t, lib = engine.torch, _lib.lib()
-        nb = lib.vadx_marblenet_stream_state_bytes(self.streams)
-        if nb != self.streams * STREAM_RECORD_WORDS * 4:
+        nb = _lib.lib().vadx_marblenet_stream_state_bytes(int(streams))
+        if nb != int(streams) * STREAM_RECORD_WORDS * 4:
             raise _lib.VadxError(f"vadx_marblenet_stream_state_bytes = {nb}: not the record this binding was written for")
-        self._rec = [t.zeros(nb, dtype=t.uint8, device=engine.device) for _ in range(2)]
-        self._cur = 0
-        self._pending = np.zeros(self.streams, dtype=bool)
-        self._ws = {}                  # k -> workspace (uint8)
+        super().__init__(engine, streams, nb)
+        self._ws = {}               # k -> workspace (uint8)
         self._weights = {}             # mode -> vadx_marblenet_stream_weights
         self._fe = engine.frontend_ragged()
         if self._fe.fold not in self._fe.RAGGED_KINDS:
             raise ValueError(f"the stream front-end is built for the split-product kinds {self._fe.RAGGED_KINDS} (KIND_SPLIT_H2 / KIND_SPLIT_B3); "
                              f"this engine's Frontend was packed as kind {self._fe.fold} (VADX_FRONTEND_FOLD)")
-
-    @property
-    def record(self):
-        """The current device record (uint8, streams * 46 048 bytes; layout in include/vadx.h)."""
-        return self._rec[self._cur]
 
     def stream_bytes(self, s, record=None):
         """Every byte of `record` (default: the current one) that belongs to stream s, as one uint8 tensor."""
@@ -554,23 +548,6 @@ class MarbleNetStreamBatch:
     def emitted(self):
         """int64 [S] (host): score frames each stream has emitted since its reset, read from the device record."""
         return self._counter(STREAM_EMITTED_WORD)
-
-    def reset_states(self, streams=None):
-        """None = every stream; else stream indices or a bool mask [S].  Applies at the next tick, before that tick's audio."""
-        if streams is None:
-            self._pending[:] = True
-            return
-        idx = np.asarray(streams.cpu() if hasattr(streams, "cpu") else streams)
-        if idx.dtype == bool:
-            self._pending |= self._mask(idx, "reset mask")
-        else:
-            self._pending[idx.astype(np.int64).reshape(-1)] = True
-
-    def _mask(self, m, name):
-        a = np.asarray(m.cpu() if hasattr(m, "cpu") else m).astype(bool).reshape(-1)
-        if a.shape != (self.streams,):
-            raise ValueError(f"{name} must have shape ({self.streams},), got {a.shape}")
-        return a
 
     def _weights_for(self, mode):
         if mode not in self._weights:
@@ -618,11 +595,7 @@ class MarbleNetStreamBatch:
         look-ahead and leaves it reset.  -> (score_silence, score_active f32 [S, k + 73], n_out int32 [S]) on the device: row s holds
         n_out[s] new score frames, NaN behind them.  A stream with no samples that is not final keeps its record bit for bit."""
         eng, t, S = self.engine, self.engine.torch, self.streams
-        x = samples_i16 if t.is_tensor(samples_i16) else t.from_numpy(np.ascontiguousarray(samples_i16))
-        if x.dtype != t.int16:
-            raise ValueError(f"samples must be int16, got {x.dtype}")
-        if x.dim() != 2 or x.shape[0] != S or x.shape[1] % STREAM_HOP or x.shape[1] == 0:
-            raise ValueError(f"samples must be [{S}, k * 320], got {tuple(x.shape)}")
+        x = self._samples(samples_i16, f"[{S}, k * 320]", lambda x: x.shape[1] % STREAM_HOP or x.shape[1] == 0)
         k = x.shape[1] // STREAM_HOP
         fin = np.zeros(S, dtype=bool) if final is None else self._mask(final, "final")
         n = np.full(S, k * STREAM_HOP, dtype=np.int64) if n_samples is None else \

@@ -20,6 +20,7 @@ import numpy as np
 from . import _lib
 from . import weights as _weights
 from .chunks import collect_chunks, drop_chunks            # noqa: F401  (the reference keeps them beside get_speech_timestamps)
+from .stream import StreamBatch
 
 CONTEXT_SIZE = 64
 NUM_SAMPLES = 512
@@ -728,93 +729,45 @@ class VADIterator:
         return _event(kind, value, self.sampling_rate, return_seconds, time_resolution)
 
 
-class VADIteratorBatch:
+class VADIteratorBatch(StreamBatch):
     """`streams` live Silero streams on the device (vadx_silero_stream_run): every call advances each stream by k windows of 512
-    samples (256 at 8 kHz); context, LSTM state and VADIterator machine of every stream stay in a device record (two, ping-ponged), and the start /
-    end events come back from the device.  Per stream, the scores are bit for bit what `SileroEngine.clips` gives for the concatenated
-    audio.  On "h2" every tick reads the range flag and, when it is raised, recomputes the tick on "split" from the same record."""
+    samples (256 at 8 kHz); context, LSTM state and VADIterator machine of every stream stay in the device `record` (DESIGN.md "Stream
+    batches"; its first 2*S*128 floats are the LSTM state [2,S,128]), and the start / end events come back from the device.  Per stream,
+    the scores are bit for bit what `SileroEngine.clips` gives for the concatenated audio.  On "h2" every tick reads the range flag and,
+    when it is raised, recomputes the tick on "split" from the same record."""
 
     def __init__(self, model, streams, threshold: float = 0.5, sampling_rate: int = 16000, min_silence_duration_ms: int = 100,
                  speech_pad_ms: int = 30):
-        self.engine = model.engine if isinstance(model, OnnxWrapper) else model
-        if not isinstance(self.engine, SileroEngine):
+        engine = model.engine if isinstance(model, OnnxWrapper) else model
+        if not isinstance(engine, SileroEngine):
             raise TypeError("VADIteratorBatch needs a vadx.silero.OnnxWrapper or SileroEngine")
         if sampling_rate not in [8000, 16000]:
             raise ValueError("VADIterator does not support sampling rates other than [8000, 16000]")
-        if sampling_rate != 16000 and not self.engine.has_8k:
+        if sampling_rate != 16000 and not engine.has_8k:
             raise ValueError(f"sr={sampling_rate}: only the 16 kHz sub-graph of the Silero network is loaded on the HIP path "
                              "(the engine has no 8 kHz weights: SileroEngine(..., weights_8k=...))")
-        self.streams = int(streams)
-        if self.streams <= 0:
-            raise ValueError(f"streams={streams} must be positive")
+        super().__init__(engine, streams, _lib.lib().vadx_silero_stream_state_bytes(int(streams)))
         self.sampling_rate = sampling_rate
         p = _lib.SileroIterParams()
         p.threshold, p.sampling_rate = float(threshold), int(sampling_rate)
         p.min_silence_duration_ms, p.speech_pad_ms = float(min_silence_duration_ms), float(speech_pad_ms)
         self._prm = p
-        t = self.engine.torch
-        nb = _lib.lib().vadx_silero_stream_state_bytes(self.streams)
-        self._rec = [t.zeros(nb, dtype=t.uint8, device=self.engine.device) for _ in range(2)]
-        self._cur = 0
         self._ws = None
-        self._pending = np.zeros(self.streams, dtype=bool)       # reset_states() requests not yet applied to an active tick
-
-    @property
-    def record(self):
-        """The current device record (uint8); its first 2*S*128 floats are the LSTM state [2,S,128]."""
-        return self._rec[self._cur]
 
     @property
     def state(self):
         return self.record[:2 * self.streams * HIDDEN * 4].view(self.engine.torch.float32).view(2, self.streams, HIDDEN)
-
-    def reset_states(self, streams=None):
-        """None = every stream; else stream indices or a bool mask [S].  Applies at the next tick in which the stream is active."""
-        if streams is None:
-            self._pending[:] = True
-            return
-        idx = np.asarray(streams.cpu() if hasattr(streams, "cpu") else streams)
-        if idx.dtype == bool:
-            if idx.shape != (self.streams,):
-                raise ValueError(f"reset mask must have shape ({self.streams},), got {idx.shape}")
-            self._pending |= idx
-        else:
-            self._pending[idx.astype(np.int64).reshape(-1)] = True
-
-    def _samples(self, x):
-        t = self.engine.torch
-        if not t.is_tensor(x):
-            x = t.from_numpy(np.ascontiguousarray(x))
-        if x.dtype != t.int16:
-            if not x.is_floating_point():
-                raise ValueError(f"samples must be float32 or int16, got {x.dtype}")
-            x = x.to(t.float32)
-        win, _ = _geom(self.sampling_rate)
-        if x.dim() != 2 or x.shape[0] != self.streams or x.shape[1] == 0 or x.shape[1] % win:
-            raise ValueError(f"samples must be [{self.streams}, k*{win}], got {tuple(x.shape)}")
-        return x.to(self.engine.device).contiguous()
-
-    def _mask(self, m, name):
-        a = np.asarray(m.cpu() if hasattr(m, "cpu") else m).astype(bool).reshape(-1)
-        if a.shape != (self.streams,):
-            raise ValueError(f"{name} must have shape ({self.streams},), got {a.shape}")
-        return a
-
-    def _dev_u8(self, a):
-        return self.engine.torch.from_numpy(a.astype(np.uint8)).to(self.engine.device)
 
     def step(self, x, active=None):
         """x [S, k*512] ([S, k*256] at 8 kHz; float32 on the +-1 scale, or int16 PCM; host or device, numpy or torch) -> device tensors
         (kind int8 [S,k], value float64 [S,k], probs float32 [S,k]); kind 0 none / 1 start / 2 end / -1 score not finite,
         value the sample position before int().  active (bool [S], None = all): False = no audio for that stream this tick."""
         eng, t = self.engine, self.engine.torch
-        x = self._samples(x)
         win, _ = _geom(self.sampling_rate)
-        S, k = self.streams, x.shape[1] // win
-        act_h = None if active is None else self._mask(active, "active")
-        act_d = None if act_h is None else self._dev_u8(act_h)
-        applied = self._pending if act_h is None else (self._pending & act_h)
-        reset_d = self._dev_u8(applied) if applied.any() else None
+        S = self.streams
+        x = self._samples(x, f"[{S}, k*{win}]", lambda x: x.shape[1] == 0 or x.shape[1] % win, floats=True).to(eng.device).contiguous()
+        k = x.shape[1] // win
+        act, _, reset_d, act_d, src, dst = self._begin(None, active)
         L = _lib.lib()
         need = L.vadx_silero_stream_workspace_bytes(S, k)
         if self._ws is None or self._ws.numel() < need:
@@ -822,7 +775,6 @@ class VADIteratorBatch:
         kind = t.empty((S, k), dtype=t.int8, device=eng.device)
         value = t.empty((S, k), dtype=t.float64, device=eng.device)
         probs = t.empty((S, k), dtype=t.float32, device=eng.device)
-        src, dst = self._rec[self._cur], self._rec[1 - self._cur]
         pcm = x.dtype == t.int16
 
         def run(mode):
@@ -834,8 +786,7 @@ class VADIteratorBatch:
                                                     probs.data_ptr(), kind.data_ptr(), value.data_ptr(), self._ws.data_ptr(),
                                                     self._ws.numel(), _lib.stream_ptr(), eng.cfg(mode, self.sampling_rate)))
         eng._guarded(run, self.sampling_rate)
-        self._cur = 1 - self._cur
-        self._pending &= ~applied
+        self._end(act)
         return kind, value, probs
 
     def __call__(self, x, active=None, return_seconds=False, time_resolution: int = 1):
