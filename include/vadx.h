@@ -62,7 +62,9 @@ extern "C" {
  *     vadx_timestamps_flags, vadx_timestamps_frames, vadx_timestamps_samples; then preparing a ragged batch on the device:
  *     vadx_ingest_pcm16_ragged, vadx_prepare_workspace_bytes, vadx_prepare_stats, vadx_prepare_scale, vadx_prepare_write; then Silero over
  *     ragged batches: vadx_silero_ragged, vadx_silero_ragged_workspace_bytes, vadx_silero_encode_ragged, vadx_silero_encode_ragged_pcm16,
- *     vadx_silero_recur_ragged, vadx_silero_clips_ragged, vadx_silero_segments_ragged.
+ *     vadx_silero_recur_ragged, vadx_silero_clips_ragged, vadx_silero_segments_ragged; then the 8 kHz network over ragged batches:
+ *     vadx_silero_encode_ragged_8k, vadx_silero_encode_ragged_8k_pcm16, vadx_silero_recur_ragged_8k, vadx_silero_clips_ragged_8k
+ *     (and two relaxations: vadx_silero_segments_ragged takes sampling_rate 8000, a vadx_silero_ragged may describe a run of groups).
  *     A caller that needs them checks for the symbols (dlsym), not for a number. */
 #define VADX_ABI_VERSION 10
 
@@ -218,9 +220,10 @@ int vadx_silero_segments(const float *probs, int batch, int steps, const int64_t
  * (csrc/rebalance.h) and marks a blob with a weight tensor wholly below 2^-14 as unusable for this arithmetic (flag bit 1 on a launch). */
 int vadx_silero_range_flag(const float *packed, int reset, uint32_t *flag_host, float *amax_host, void *stream);
 
-/* Silero over a RAGGED batch (16 kHz network): clips of any lengths in ONE packed source vector (float32 on the +-1 scale, or int16 PCM
+/* Silero over a RAGGED batch: clips of any lengths in ONE packed source vector (float32 on the +-1 scale, or int16 PCM
  * scaled while staging as vadx_silero_encode_pcm16 does), scored in one encoder and one recurrent launch whose work follows the clips'
- * own window counts T_b = ceil(len_b / 512) instead of batch x the longest clip's.  The host sorts the clips by T_b (descending, stable)
+ * own window counts T_b = ceil(len_b / 512) instead of batch x the longest clip's.  (The 16 kHz network is described; the 8 kHz one,
+ * windows of 256 samples, has the _8k entry points below and is otherwise the same.)  The host sorts the clips by T_b (descending, stable)
  * and takes sixteen at a time -- one MFMA column tile -- as a GROUP; slot s = 16 g + i is column i of group g.  A group runs T_g = the
  * window count of its first slot; its gx tiles (32 KB each) lie CONSECUTIVELY in the workspace from tile gx_first[g] (the rectangular
  * layout is window-major).  The encoder's workgroups find their work in wg_tab: one entry per (group, run of VADX_SILERO_RAGGED_RUN
@@ -232,7 +235,12 @@ int vadx_silero_range_flag(const float *packed, int reset, uint32_t *flag_host, 
  * LSTM state stops changing behind its own last window, so state_n [2][clips][128] holds every clip's state after its last window.
  * The device trusts no slot: one whose [slot_off, slot_off + slot_len) leaves [0, n_src) is not read at all, its scores are NaN,
  * bit 0 of *status is raised (the caller zeroes the word), and no other clip's result changes.  The remaining tables are functions of
- * the lengths (vadx.ragged.RaggedClips._set_tables writes them) and are the caller's contract, as a rectangular call's batch and steps. */
+ * the lengths (vadx.ragged.RaggedClips._set_tables writes them) and are the caller's contract, as a rectangular call's batch and steps.
+ * A table set may describe a RUN OF A BATCH'S GROUPS, 1 <= groups <= ceil(clips / 16): slot_*, grp_min_len start at the run's first group,
+ * gx_first is rebased to the run (gx_first[0] = 0, tiles = gx_first[groups]), wg_tab numbers the run's groups from 0, while clips,
+ * slot_clip, probs_first, probs and state_n stay the whole batch's -- the launch writes the scores and states of the run's clips to their
+ * places and nothing else.  Groups are independent workgroups, so a batch whose workspace would be too large runs as consecutive such
+ * launches on one smaller workspace, in stream order, with the results of the single launch (vadx.ragged.RaggedClips.parts). */
 #define VADX_SILERO_RAGGED_RUN 4                /* windows per wg_tab entry = the fp16 x 2 encoder's tiles per workgroup (H2_NSUB) */
 typedef struct vadx_silero_ragged {             /* every pointer: device memory */
     const int64_t *slot_off;                    /* [16 groups] first element of the slot's clip in the source vector (0: empty slot) */
@@ -249,7 +257,8 @@ typedef struct vadx_silero_ragged {             /* every pointer: device memory 
 } vadx_silero_ragged;
 size_t vadx_silero_ragged_workspace_bytes(int64_t tiles);          /* tiles x 32 KB */
 /* The halves of vadx_silero_clips_ragged (no range protocol of their own, as vadx_silero_encode / _recur).  n_src = elements of `src`.
- * cfg->ext.sample_rate = 8000 is refused: the 8 kHz network has no ragged encoder.  A workspace below
+ * cfg->ext.sample_rate = 8000 is refused by these four: a table set carries no window length, so the network comes with the entry point
+ * (the _8k calls below), not with a switch that tables built for the other rate would pass silently.  A workspace below
  * vadx_silero_ragged_workspace_bytes(rg->tiles) returns VADX_ENOSPACE. */
 int vadx_silero_encode_ragged(const float *packed, const float *src, int64_t n_src, const vadx_silero_ragged *rg,
                               void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg);
@@ -261,8 +270,21 @@ int vadx_silero_recur_ragged(const float *packed, const void *workspace, size_t 
 int vadx_silero_clips_ragged(const float *packed, const void *src, int src_int16, float scale, int64_t n_src,
                              const vadx_silero_ragged *rg, float *probs, float *state_n, void *workspace, size_t workspace_bytes,
                              void *stream, const vadx_silero_cfg *cfg);
+/* The 8 kHz network (the blob of vadx_silero_pack_host_sr(8000, ...)) over a ragged batch whose tables count windows of 256 samples,
+ * T_b = ceil(len_b / 256): arguments, layouts, device checks and results as the namesakes above; cfg must be given with
+ * ext.sample_rate = 8000 (anything else: VADX_EINVAL).  The encoder stages 32 samples of context + 256 + a reflect pad of 32 per slot and
+ * runs one tile per workgroup; the recurrent kernels are the 16 kHz calls' own.  A 16 kHz blob gives NaN scores and range-flag bit 2. */
+int vadx_silero_encode_ragged_8k(const float *packed, const float *src, int64_t n_src, const vadx_silero_ragged *rg,
+                                 void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg);
+int vadx_silero_encode_ragged_8k_pcm16(const float *packed, const int16_t *src, float scale, int64_t n_src, const vadx_silero_ragged *rg,
+                                       void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg);
+int vadx_silero_recur_ragged_8k(const float *packed, const void *workspace, size_t workspace_bytes, int64_t n_src,
+                                const vadx_silero_ragged *rg, float *probs, float *state_n, void *stream, const vadx_silero_cfg *cfg);
+int vadx_silero_clips_ragged_8k(const float *packed, const void *src, int src_int16, float scale, int64_t n_src,
+                                const vadx_silero_ragged *rg, float *probs, float *state_n, void *workspace, size_t workspace_bytes,
+                                void *stream, const vadx_silero_cfg *cfg);
 /* vadx_silero_segments on the packed scores: clip b's row starts at probs_first[b] and has probs_first[b + 1] - probs_first[b] windows
- * (of which ceil(n_samples[b] / window) are read at most).  Same tables out. */
+ * (of which ceil(n_samples[b] / window) are read at most; params->sampling_rate 16000 or 8000 gives the window).  Same tables out. */
 int vadx_silero_segments_ragged(const float *probs, const int64_t *probs_first, int batch, const int64_t *n_samples,
                                 const vadx_silero_seg_params *params, int64_t *segments, int32_t *counts, int cap, void *stream);
 

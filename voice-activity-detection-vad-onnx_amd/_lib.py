@@ -199,6 +199,10 @@ SIGNATURES = {
     "vadx_silero_recur_ragged": (_I, [_P, _P, _Z, _L, C.POINTER(SileroRagged), _P, _P, _P, _P]),
     "vadx_silero_clips_ragged": (_I, [_P, _P, _I, C.c_float, _L, C.POINTER(SileroRagged), _P, _P, _P, _Z, _P, _P]),
     "vadx_silero_segments_ragged": (_I, [_P, _P, _I, _P, C.POINTER(SileroSegParams), _P, _P, _I, _P]),
+    "vadx_silero_encode_ragged_8k": (_I, [_P, _P, _L, C.POINTER(SileroRagged), _P, _Z, _P, _P]),
+    "vadx_silero_encode_ragged_8k_pcm16": (_I, [_P, _P, C.c_float, _L, C.POINTER(SileroRagged), _P, _Z, _P, _P]),
+    "vadx_silero_recur_ragged_8k": (_I, [_P, _P, _Z, _L, C.POINTER(SileroRagged), _P, _P, _P, _P]),
+    "vadx_silero_clips_ragged_8k": (_I, [_P, _P, _I, C.c_float, _L, C.POINTER(SileroRagged), _P, _P, _P, _Z, _P, _P]),
     "vadx_frontend_packed_floats": (_Z, [C.POINTER(FrontendCfg)]),
     "vadx_frontend_pack_host": (_I, [C.POINTER(FrontendCfg), _P, _P, _I, _P, _P, _P]),
     "vadx_frontend_fold_kind": (_I, [C.POINTER(FrontendCfg), _P, _P, _I]),

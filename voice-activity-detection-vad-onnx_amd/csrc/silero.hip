@@ -636,7 +636,9 @@ __global__ __launch_bounds__(LSTM_THREADS, 2) void silero_lstm_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             h[r] = gate_sigmoid(ao[r]) * gate_tanh(c[r]);
-            dpart = fmaf(dw[r], fmaxf(h[r], 0.f), dpart);
+            float hr = fmaxf(h[r], 0.f);
+            if constexpr (RG) hr = h[r] != h[r] ? h[r] : hr;      // fmaxf drops a NaN: NaN gate pre-activations (a refused blob) stay NaN in the score
+            dpart = fmaf(dw[r], hr, dpart);
         }
         if constexpr (RG) {
             if (t >= Tb) { h = h_in; c = c_in; }
@@ -1051,16 +1053,26 @@ extern "C" size_t vadx_silero_ragged_workspace_bytes(int64_t tiles) {
     return tiles <= 0 ? 0 : (size_t)tiles * GX_TILE_FLOATS * sizeof(float);
 }
 
-// what every ragged launch checks of its arguments on the host; -> the kernels' argument
-static int ragged_args(const char *who, const float *packed, const vadx_silero_ragged *rg, int64_t n_src, const void *ws, size_t ws_bytes,
-                       const vadx_silero_cfg *cfg, RgArg<true> &out) {
-    VADX_REQUIRE(!(cfg && cfg->ext.sample_rate == 8000),
-                 "%s: cfg->ext.sample_rate=8000: the ragged Silero path runs the 16 kHz network only (the 8 kHz encoder has no ragged form)", who);
-    VADX_REQUIRE(rate_of(cfg) == 16000, "%s: cfg->ext.sample_rate=%d is not 16000 (0 = 16000)", who, cfg ? cfg->ext.sample_rate : 0);
+// what every ragged launch checks of its arguments on the host; -> the kernels' argument.  A table set carries no window length, so the
+// network comes with the ENTRY POINT (rate: 16000 for the plain names, 8000 for the _8k ones) and cfg must not contradict it: tables built
+// for one rate and run at the other would score misaligned windows without any error.  groups may be fewer than ceil(clips / 16): a table
+// set may describe a run of a batch's groups (include/vadx.h).
+static int ragged_args(const char *who, int rate, const float *packed, const vadx_silero_ragged *rg, int64_t n_src, const void *ws,
+                       size_t ws_bytes, const vadx_silero_cfg *cfg, RgArg<true> &out) {
+    if (rate == 16000) {
+        VADX_REQUIRE(!(cfg && cfg->ext.sample_rate == 8000),
+                     "%s: cfg->ext.sample_rate=8000: this entry point runs the 16 kHz network on tables of 512-sample windows; the 8 kHz network's "
+                     "ragged calls are vadx_silero_encode_ragged_8k, _encode_ragged_8k_pcm16, _recur_ragged_8k and _clips_ragged_8k", who);
+        VADX_REQUIRE(rate_of(cfg) == 16000, "%s: cfg->ext.sample_rate=%d is not 16000 (0 = 16000)", who, cfg ? cfg->ext.sample_rate : 0);
+    } else {
+        VADX_REQUIRE(cfg && cfg->ext.sample_rate == 8000,
+                     "%s: cfg->ext.sample_rate=%d must be 8000: this entry point runs the 8 kHz network on tables of 256-sample windows", who,
+                     cfg ? cfg->ext.sample_rate : 0);
+    }
     VADX_REQUIRE(packed && rg && ws, "%s: NULL pointer argument", who);
     VADX_REQUIRE(rg->slot_off && rg->slot_len && rg->slot_clip && rg->gx_first && rg->grp_min_len && rg->wg_tab && rg->probs_first && rg->status,
                  "%s: NULL table in vadx_silero_ragged", who);
-    VADX_REQUIRE(rg->clips > 0 && rg->groups == (rg->clips + 15) / 16 && rg->tiles >= rg->groups && rg->n_runs >= rg->groups &&
+    VADX_REQUIRE(rg->clips > 0 && rg->groups >= 1 && rg->groups <= (rg->clips + 15) / 16 && rg->tiles >= rg->groups && rg->n_runs >= rg->groups &&
                      (long long)rg->n_runs * RG_RUN < (1LL << 31) && (long long)rg->n_runs * RG_RUN >= rg->tiles,
                  "%s: clips=%d groups=%d n_runs=%d tiles=%d are not the counts of one ragged batch", who, rg->clips, rg->groups, rg->n_runs,
                  rg->tiles);
@@ -1077,13 +1089,14 @@ static int ragged_args(const char *who, const float *packed, const vadx_silero_r
 }
 
 template <typename S>
-static int encode_ragged(const char *who, const float *packed, const S *src, float in_scale, int64_t n_src, const vadx_silero_ragged *rg,
-                         void *ws, size_t ws_bytes, void *stream, const vadx_silero_cfg *cfg) {
+static int encode_ragged(const char *who, int rate, const float *packed, const S *src, float in_scale, int64_t n_src,
+                         const vadx_silero_ragged *rg, void *ws, size_t ws_bytes, void *stream, const vadx_silero_cfg *cfg) {
     VADX_SILERO_ARITH(cfg, "silero (ragged)");
     VADX_REQUIRE(src, "%s: NULL pointer argument", who);
     RgArg<true> a;
-    const int rc = ragged_args(who, packed, rg, n_src, ws, ws_bytes, cfg, a);
+    const int rc = ragged_args(who, rate, packed, rg, n_src, ws, ws_bytes, cfg, a);
     if (rc != VADX_OK) return rc;
+    if (rate == 8000) return silero8k_encode_ragged_launch<S>(arith, packed, src, in_scale, a, static_cast<float *>(ws), stream);
     if (arith == 2) return silero_encode_h2_ragged_launch<S>(packed, src, in_scale, a, static_cast<float *>(ws), stream);
     if (arith == 1) return silero_encode_split_ragged_launch<S>(packed, src, in_scale, a, static_cast<float *>(ws), stream);
     VADX_DYN_LDS((silero_encode_kernel<S, true>), ENC_LDS_FLOATS * sizeof(float));
@@ -1096,22 +1109,22 @@ static int encode_ragged(const char *who, const float *packed, const S *src, flo
 
 extern "C" int vadx_silero_encode_ragged(const float *packed, const float *src, int64_t n_src, const vadx_silero_ragged *rg,
                                          void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg) {
-    return encode_ragged("vadx_silero_encode_ragged", packed, src, 1.0f, n_src, rg, workspace, workspace_bytes, stream, cfg);
+    return encode_ragged("vadx_silero_encode_ragged", 16000, packed, src, 1.0f, n_src, rg, workspace, workspace_bytes, stream, cfg);
 }
 
 extern "C" int vadx_silero_encode_ragged_pcm16(const float *packed, const int16_t *src, float scale, int64_t n_src,
                                                const vadx_silero_ragged *rg, void *workspace, size_t workspace_bytes, void *stream,
                                                const vadx_silero_cfg *cfg) {
-    return encode_ragged("vadx_silero_encode_ragged_pcm16", packed, src, scale, n_src, rg, workspace, workspace_bytes, stream, cfg);
+    return encode_ragged("vadx_silero_encode_ragged_pcm16", 16000, packed, src, scale, n_src, rg, workspace, workspace_bytes, stream, cfg);
 }
 
-extern "C" int vadx_silero_recur_ragged(const float *packed, const void *workspace, size_t workspace_bytes, int64_t n_src,
-                                        const vadx_silero_ragged *rg, float *probs, float *state_n, void *stream,
-                                        const vadx_silero_cfg *cfg) {
+// the ragged recurrent kernels are the same at both rates (gx has one layout); only the blob and the tables differ
+static int recur_ragged(const char *who, int rate, const float *packed, const void *workspace, size_t workspace_bytes, int64_t n_src,
+                        const vadx_silero_ragged *rg, float *probs, float *state_n, void *stream, const vadx_silero_cfg *cfg) {
     VADX_SILERO_ARITH(cfg, "silero (ragged)");
-    VADX_REQUIRE(probs, "vadx_silero_recur_ragged: NULL pointer argument");
+    VADX_REQUIRE(probs, "%s: NULL pointer argument", who);
     RgArg<true> a;
-    const int rc = ragged_args("vadx_silero_recur_ragged", packed, rg, n_src, workspace, workspace_bytes, cfg, a);
+    const int rc = ragged_args(who, rate, packed, rg, n_src, workspace, workspace_bytes, cfg, a);
     if (rc != VADX_OK) return rc;
     const float *gx = static_cast<const float *>(workspace);
     if (arith == 2) return silero_lstm_h2_ragged_launch(packed, gx, a, probs, state_n, stream);
@@ -1123,15 +1136,53 @@ extern "C" int vadx_silero_recur_ragged(const float *packed, const void *workspa
     return VADX_OK;
 }
 
+static int clips_ragged(const char *who, int rate, const float *packed, const void *src, int src_int16, float scale, int64_t n_src,
+                        const vadx_silero_ragged *rg, float *probs, float *state_n, void *workspace, size_t workspace_bytes, void *stream,
+                        const vadx_silero_cfg *cfg) {
+    const int rc = src_int16 ? encode_ragged(who, rate, packed, static_cast<const int16_t *>(src), scale, n_src, rg, workspace,
+                                             workspace_bytes, stream, cfg)
+                             : encode_ragged(who, rate, packed, static_cast<const float *>(src), 1.0f, n_src, rg, workspace,
+                                             workspace_bytes, stream, cfg);
+    if (rc != VADX_OK) return rc;
+    return recur_ragged(who, rate, packed, workspace, workspace_bytes, n_src, rg, probs, state_n, stream, cfg);
+}
+
+extern "C" int vadx_silero_recur_ragged(const float *packed, const void *workspace, size_t workspace_bytes, int64_t n_src,
+                                        const vadx_silero_ragged *rg, float *probs, float *state_n, void *stream,
+                                        const vadx_silero_cfg *cfg) {
+    return recur_ragged("vadx_silero_recur_ragged", 16000, packed, workspace, workspace_bytes, n_src, rg, probs, state_n, stream, cfg);
+}
+
 extern "C" int vadx_silero_clips_ragged(const float *packed, const void *src, int src_int16, float scale, int64_t n_src,
                                         const vadx_silero_ragged *rg, float *probs, float *state_n, void *workspace,
                                         size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg) {
-    const int rc = src_int16 ? encode_ragged("vadx_silero_clips_ragged", packed, static_cast<const int16_t *>(src), scale, n_src, rg, workspace,
-                                             workspace_bytes, stream, cfg)
-                             : encode_ragged("vadx_silero_clips_ragged", packed, static_cast<const float *>(src), 1.0f, n_src, rg, workspace,
-                                             workspace_bytes, stream, cfg);
-    if (rc != VADX_OK) return rc;
-    return vadx_silero_recur_ragged(packed, workspace, workspace_bytes, n_src, rg, probs, state_n, stream, cfg);
+    return clips_ragged("vadx_silero_clips_ragged", 16000, packed, src, src_int16, scale, n_src, rg, probs, state_n, workspace,
+                        workspace_bytes, stream, cfg);
+}
+
+// ---- the 8 kHz network over a ragged batch: the same calls on tables of 256-sample windows and the 8 kHz blob (cfg->ext.sample_rate = 8000)
+extern "C" int vadx_silero_encode_ragged_8k(const float *packed, const float *src, int64_t n_src, const vadx_silero_ragged *rg,
+                                            void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg) {
+    return encode_ragged("vadx_silero_encode_ragged_8k", 8000, packed, src, 1.0f, n_src, rg, workspace, workspace_bytes, stream, cfg);
+}
+
+extern "C" int vadx_silero_encode_ragged_8k_pcm16(const float *packed, const int16_t *src, float scale, int64_t n_src,
+                                                  const vadx_silero_ragged *rg, void *workspace, size_t workspace_bytes, void *stream,
+                                                  const vadx_silero_cfg *cfg) {
+    return encode_ragged("vadx_silero_encode_ragged_8k_pcm16", 8000, packed, src, scale, n_src, rg, workspace, workspace_bytes, stream, cfg);
+}
+
+extern "C" int vadx_silero_recur_ragged_8k(const float *packed, const void *workspace, size_t workspace_bytes, int64_t n_src,
+                                           const vadx_silero_ragged *rg, float *probs, float *state_n, void *stream,
+                                           const vadx_silero_cfg *cfg) {
+    return recur_ragged("vadx_silero_recur_ragged_8k", 8000, packed, workspace, workspace_bytes, n_src, rg, probs, state_n, stream, cfg);
+}
+
+extern "C" int vadx_silero_clips_ragged_8k(const float *packed, const void *src, int src_int16, float scale, int64_t n_src,
+                                           const vadx_silero_ragged *rg, float *probs, float *state_n, void *workspace,
+                                           size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg) {
+    return clips_ragged("vadx_silero_clips_ragged_8k", 8000, packed, src, src_int16, scale, n_src, rg, probs, state_n, workspace,
+                        workspace_bytes, stream, cfg);
 }
 
 extern "C" int vadx_silero_segments_ragged(const float *probs, const int64_t *probs_first, int batch, const int64_t *n_samples,
@@ -1139,8 +1190,8 @@ extern "C" int vadx_silero_segments_ragged(const float *probs, const int64_t *pr
                                            void *stream) {
     VADX_REQUIRE(probs && probs_first && n_samples && params && segments && counts, "vadx_silero_segments_ragged: NULL pointer argument");
     VADX_REQUIRE(batch > 0 && cap > 0, "vadx_silero_segments_ragged: batch/cap must be positive");
-    VADX_REQUIRE(params->sampling_rate == 16000, "vadx_silero_segments_ragged: the ragged Silero path runs at 16000 Hz only (got %d)",
-                 params->sampling_rate);
+    VADX_REQUIRE(params->sampling_rate == 16000 || params->sampling_rate == 8000,
+                 "vadx_silero_segments_ragged: params->sampling_rate=%d is not 16000 or 8000", params->sampling_rate);
     hipLaunchKernelGGL(silero_segments_kernel<true>, dim3((batch + SEG_WAVES - 1) / SEG_WAVES), dim3(64 * SEG_WAVES), 0,
                        static_cast<hipStream_t>(stream), probs, batch, 2147483647, reinterpret_cast<const long long *>(n_samples), *params,
                        reinterpret_cast<long long *>(segments), counts, cap, SegRows<true>{reinterpret_cast<const long long *>(probs_first)});

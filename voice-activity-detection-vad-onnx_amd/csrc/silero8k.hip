@@ -118,14 +118,64 @@ template <class Sch> __device__ __forceinline__ const float *ih_w(const float *P
     return P + (Sch::ARITH == VADX_AR_B3 ? OFF_QIH : OFF_HIH) + ((ut * 4 + kc) * 4 + g) * Ops<Sch>::CHUNK;
 }
 
+// Phase 0 of a ragged tile (silero_common.h: "ragged batches"), the 8 kHz sibling of stage_ragged: window `base` .. base + 287 of the sixteen
+// slots of group grp into X, then the right reflect pad of 32, laid out as the rectangular phase 0 stages it.  Slot c reads its clip as that
+// reads a row with n_samples = the slot's own length: zeros before the clip and beyond its end, the pad mirrored over that.  A float4 inside
+// the clip is one vector load when the clip starts on a multiple of four elements (base and p are multiples of four), four single loads
+// otherwise; `whole` (uniform: the window ends below the group's shortest accepted length) spares the per-float4 range test.
+template <typename SampleT>
+__device__ __forceinline__ void stage_ragged8k(float *X, const SampleT *__restrict__ audio, float in_scale, const RgArg<true> &rg, int grp,
+                                               long long base, int tid) {
+    const bool ptr_ok = (reinterpret_cast<uintptr_t>(audio) & (SampleIO<SampleT>::VEC_ALIGN - 1)) == 0;
+    int shortest;
+    {
+        long long o_;
+        rg_slot(rg, grp * 16 + (tid & 15), o_, shortest);
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) shortest = min(shortest, __shfl_xor(shortest, d));
+        shortest = min(shortest, rg.t.grp_min_len[grp]);
+    }
+    const bool whole = base >= 0 && base + 288 <= (long long)shortest;
+#pragma unroll 1
+    for (int it = 0; it < 3; ++it) {
+        const int e = tid + K8_THREADS * it;                  // 16 clips x 72 groups of four samples
+        if (e < 16 * 72) {
+            const int c = e / 72, p = 4 * (e - c * 72);
+            long long off;
+            int len;
+            if (!rg_slot(rg, grp * 16 + c, off, len) && p == 0) atomicOr(rg.t.status, 1u);
+            const SampleT *src = audio + off;
+            const long long idx = base + p;
+            f32x4 v;
+            if (ptr_ok && (off & 3) == 0 && (whole || (idx >= 0 && idx + 3 < len))) {
+                v = SampleIO<SampleT>::load4(src + idx, in_scale);
+            } else {
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+                    v[jj] = (idx + jj >= 0 && idx + jj < len) ? SampleIO<SampleT>::load1(src + idx + jj, in_scale) : 0.f;
+            }
+            float *row = X + c * XLD;
+            *reinterpret_cast<f32x4 *>(row + p) = v;
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                const int pp = p + jj;
+                if (pp >= 255 && pp <= 286) row[574 - pp] = v[jj];
+            }
+        }
+    }
+}
+
 __device__ __forceinline__ f32x4 relu4(const f32x4 y, const f32x4 b) {
     return f32x4{fmaxf(y[0] + b[0], 0.f), fmaxf(y[1] + b[1], 0.f), fmaxf(y[2] + b[2], 0.f), fmaxf(y[3] + b[3], 0.f)};
 }
 
-template <class Sch, typename SampleT>
+// RG (a ragged batch, silero_common.h): the tile is (group, window) of the workgroup table -- RG_RUN workgroups per entry, one per window of
+// the run --, the sixteen slots are staged by stage_ragged8k and the group's gx tiles lie consecutively; everything behind phase 0 is the
+// rectangular kernel's code.
+template <class Sch, typename SampleT, bool RG = false>
 __global__ __launch_bounds__(K8_THREADS, 2) void silero8k_encode_kernel(
     const float *__restrict__ P, const SampleT *__restrict__ audio, float in_scale, long long n_samples,
-    long long row_stride, long long origin, int B, int G, int T, int Gws, int g0, float *__restrict__ gx) {
+    long long row_stride, long long origin, int B, int G, int T, int Gws, int g0, float *__restrict__ gx, const RgArg<RG> rg) {
     typedef Ops<Sch> O;
     extern __shared__ __attribute__((aligned(16))) float lds8[];
     float *X = lds8, *A1 = lds8, *A3 = lds8;                  // R0
@@ -134,8 +184,16 @@ __global__ __launch_bounds__(K8_THREADS, 2) void silero8k_encode_kernel(
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = lane >> 4, i = lane & 15;
-    const int grp = blockIdx.x % G, t = blockIdx.x / G;
-    float *dst = gx + ((size_t)t * Gws + g0 + grp) * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
+    int grp = blockIdx.x % G, t = blockIdx.x / G;
+    size_t tile = (size_t)t * Gws + g0 + grp;
+    if constexpr (RG) {
+        const int ent = blockIdx.x / RG_RUN;
+        grp = rg.t.wg_tab[2 * ent];
+        t = rg.t.wg_tab[2 * ent + 1] * RG_RUN + blockIdx.x % RG_RUN;
+        if (t >= rg.t.gx_first[grp + 1] - rg.t.gx_first[grp]) return;      // (uniform) the group's last run is a partial one
+        tile = (size_t)rg.t.gx_first[grp] + t;
+    }
+    float *dst = gx + tile * GX_TILE_FLOATS + (size_t)wave * 4 * 256 + lane * 4;
 
     // a blob without the 8 kHz tag (a 16 kHz blob), or one the fp16 x 2 kernels cannot run on: NaN gate pre-activations and a flag bit,
     // never plausible scores
@@ -153,7 +211,9 @@ __global__ __launch_bounds__(K8_THREADS, 2) void silero8k_encode_kernel(
     float amax = 0.f;           // running max |x| of everything this thread splits (fp16 x 2)
 
     // ---------------- phase 0: the 16 windows (288 samples each) + right reflect pad of 32: X[c][288 + m] = X[c][286 - m]
-    {
+    if constexpr (RG) {
+        stage_ragged8k<SampleT>(X, audio, in_scale, rg, grp, (long long)t * 256 + origin, tid);
+    } else {
         const long long base = (long long)t * 256 + origin;
         const bool vec_ok = ((row_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(audio) & (SampleIO<SampleT>::VEC_ALIGN - 1)) == 0) &&
                             n_samples >= 4;
@@ -368,10 +428,31 @@ static int launch8k(const float *packed, const S *src, float in_scale, long long
     const long long nblk = (long long)G * steps;
     hipLaunchKernelGGL((silero8k_encode_kernel<Sch, S>), dim3((unsigned)nblk), dim3(K8_THREADS), K8_LDS_BYTES,
                        static_cast<hipStream_t>(stream), packed, src, in_scale, n_valid, row_stride, origin, batch, G, steps, Gws,
-                       first_group, gx);
+                       first_group, gx, RgArg<false>{});
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
+
+// one workgroup per window of every run of the workgroup table (the caller has checked n_runs * RG_RUN < 2^31)
+template <class Sch, typename S>
+static int launch8k_ragged(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream) {
+    VADX_DYN_LDS((silero8k_encode_kernel<Sch, S, true>), K8_LDS_BYTES);
+    hipLaunchKernelGGL((silero8k_encode_kernel<Sch, S, true>), dim3((unsigned)(rg.t.n_runs * RG_RUN)), dim3(K8_THREADS), K8_LDS_BYTES,
+                       static_cast<hipStream_t>(stream), packed, src, in_scale, rg.n_src, 0LL, -32LL, rg.t.clips, rg.t.groups, 0, 0, 0, gx,
+                       rg);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+template <typename S>
+int silero8k_encode_ragged_launch(int arith, const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx,
+                                  void *stream) {
+    if (arith == VADX_AR_H2) return launch8k_ragged<SchemeH2, S>(packed, src, in_scale, rg, gx, stream);
+    if (arith == VADX_AR_B3) return launch8k_ragged<SchemeB3, S>(packed, src, in_scale, rg, gx, stream);
+    return launch8k_ragged<SchemeF32, S>(packed, src, in_scale, rg, gx, stream);
+}
+template int silero8k_encode_ragged_launch<float>(int, const float *, const float *, float, const RgArg<true> &, float *, void *);
+template int silero8k_encode_ragged_launch<int16_t>(int, const float *, const int16_t *, float, const RgArg<true> &, float *, void *);
 
 template <typename S>
 int silero8k_encode_launch(int arith, const float *packed, const S *src, float in_scale, long long n_valid, long long row_stride,

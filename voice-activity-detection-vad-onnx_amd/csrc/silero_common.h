@@ -309,6 +309,10 @@ int silero_recur_launch(const float *packed, const void *ws, size_t ws_bytes, in
 template <typename S>
 int silero8k_encode_launch(int arith, const float *packed, const S *src, float in_scale, long long n_valid, long long row_stride,
                            long long origin, int batch, int G, int steps, int Gws, int first_group, float *gx, void *stream);
+// ... and its ragged launch (the tables' windows are windows of 256)
+template <typename S>
+int silero8k_encode_ragged_launch(int arith, const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx,
+                                  void *stream);
 
 int silero_lstm_split_launch(const float *packed, const float *gx, const float *state0, int batch, int G, int steps, float *probs,
                              long long probs_stride, float *state_n, void *stream);

@@ -648,7 +648,9 @@ __global__ __launch_bounds__(512, 2) void silero_lstm_split_kernel(
             const float gg = gate_tanh(hi[2][r] + lo[2][r]), og = gate_sigmoid(hi[3][r] + lo[3][r]);
             c[r] = fg * c[r] + ig * gg;
             h[r] = og * gate_tanh(c[r]);
-            dpart = fmaf(dw[r], fmaxf(h[r], 0.f), dpart);
+            float hr = fmaxf(h[r], 0.f);
+            if constexpr (RG) hr = h[r] != h[r] ? h[r] : hr;      // fmaxf drops a NaN: NaN gate pre-activations (a refused blob) stay NaN in the score
+            dpart = fmaf(dw[r], hr, dpart);
         }
         if constexpr (RG) {
             if (t >= Tb) { h = h_in; c = c_in; }

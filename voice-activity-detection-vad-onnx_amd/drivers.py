@@ -3,8 +3,8 @@
 of module-level globals), same stdout summary.  Each function also accepts a LIST of files: FSMN, FireRed and FireRed-AED hand
 the list to their engine as ONE ragged batch (vadx.ragged: clips of any lengths, work proportional to the audio), and so does MarbleNet
 in both window modes (dynamic axis: vadx.ragged.RaggedFrames, one window per clip; INPUT_AUDIO_LENGTH: each clip on its own window
-grid) and both DFSMN drivers (vadx.ragged.RaggedPairs: near / far pairs on a grid of odd window and stride); the Silero driver pads
-ragged clips into one batch.  The
+grid) and both DFSMN drivers (vadx.ragged.RaggedPairs: near / far pairs on a grid of odd window and stride), and the Silero driver
+(vadx.ragged.RaggedClips, at 16000 Hz and -- with a model that holds the 8 kHz network -- at 8000).  The
 printed RTF is over the total audio duration.  `engine` / `model` may be an engine object, a weight dict, a checkpoint path, or the explicit
 opt-in "synthetic:<seed>" (vadx.checkpoints.resolve) -- never an implicit default."""
 from __future__ import annotations
@@ -114,14 +114,16 @@ def inference_silero(test_vad_audio="./vad_sample.wav", model=None, save_timesta
         clips = [audio_io.load_wav(f, SAMPLE_RATE).astype(np.float32) * np.float32(0.000030517578) for f in files]
     echo("\nStart to run the VAD process.")
     t0 = time.time()
-    if len(clips) > 1 and SAMPLE_RATE == 16000:       # a list of files: one ragged batch (every file pays for its own windows)
+    # the network follows SAMPLE_RATE where the model holds the 8 kHz one (otherwise, as the reference script, the 16 kHz default runs)
+    rate = 8000 if (SAMPLE_RATE == 8000 and getattr(getattr(model, "engine", model), "has_8k", False)) else 16000
+    if len(clips) > 1 and (SAMPLE_RATE == 16000 or rate == 8000):       # a list of files: one ragged batch (every file pays for its own windows)
         batch, lengths = clips, None
     else:
         n = max(len(c) for c in clips)
         batch, lengths = np.zeros((len(clips), n), np.float32), [len(c) for c in clips]
         for k, c in enumerate(clips):
             batch[k, :len(c)] = c
-    res = silero.get_speech_timestamps_batch(batch, model, lengths=lengths, threshold=ACTIVATE_THRESHOLD,
+    res = silero.get_speech_timestamps_batch(batch, model, lengths=lengths, threshold=ACTIVATE_THRESHOLD, sampling_rate=rate,
                                              max_speech_duration_s=MAX_SPEECH_DURATION,
                                              min_speech_duration_ms=int(MIN_SPEECH_DURATION * 1000),
                                              min_silence_duration_ms=MIN_SILENCE_DURATION, return_seconds=True)

@@ -390,15 +390,27 @@ class RaggedFrames:
 
 
 SILERO_WINDOW = 512          # samples per Silero window at 16 kHz
+SILERO_WINDOWS = {16000: 512, 8000: 256}     # samples per window of the network of each rate
 SILERO_GROUP = 16            # clips per group = columns of one MFMA tile
 SILERO_RUN = 4               # windows per workgroup-table entry (include/vadx.h: VADX_SILERO_RAGGED_RUN)
 GX_TILE_BYTES = 32768        # one (group, window) tile of gate pre-activations
 
 
+def _wg_tab(group_windows):
+    """The workgroup table int32 [n_runs, 2] = (group, run of SILERO_RUN windows) of groups with these window counts (which never grow
+    with the group index): run-major over the groups that still have that run, which are the first n_r groups."""
+    runs = (np.asarray(group_windows, dtype=np.int64) + SILERO_RUN - 1) // SILERO_RUN
+    n_r = np.searchsorted(-runs, -np.arange(1, int(runs.max()) + 1), side="right")   # groups with runs >= r + 1
+    grp = np.concatenate([np.arange(n, dtype=np.int32) for n in n_r])
+    run = np.repeat(np.arange(len(n_r), dtype=np.int32), n_r)
+    return np.ascontiguousarray(np.stack([grp, run], axis=1).astype(np.int32))
+
+
 class RaggedClips:
-    """Silero's ragged batch (16 kHz; include/vadx.h, "Silero over a RAGGED batch"): clips of any lengths in ONE packed vector, float32 on
+    """Silero's ragged batch (include/vadx.h, "Silero over a RAGGED batch"): clips of any lengths in ONE packed vector, float32 on
     the +-1 scale or int16 PCM (scaled by SileroEngine.PCM16_SCALE while staging), as they are -- Silero needs no normalisation and no
-    padding, so `from_packed` copies nothing.  The clips are sorted by window count T_b = ceil(len_b / 512), descending and stable, and
+    padding, so `from_packed` copies nothing.  The batch is built for ONE network: `sampling_rate` 16000 (`window` = 512 samples) or 8000
+    (256).  The clips are sorted by window count T_b = ceil(len_b / window), descending and stable, and
     taken sixteen at a time as GROUPS; a group runs T_g = its first slot's window count, and the encoder's work is sum(T_g) tiles instead
     of ceil(B / 16) * max(T_b).
     Host fields (functions of the lengths and offsets alone, `_set_tables`): lengths int64 [B], clip_off int64 [B], windows int64 [B],
@@ -406,14 +418,16 @@ class RaggedClips:
     last clip of a partial group), gx_first int32 [G + 1], grp_min_len int32 [G], wg_tab int32 [n_runs, 2] = (group, run of four windows),
     run-major over the groups that still have that run, probs_first int64 [B + 1]; n_windows = sum(T_b), tiles = sum(T_g), n_runs,
     workspace_bytes = tiles * 32 KB.  With a device, `pcm`, the tables and the status word are tensors there.
-    Scores of a batch: one packed float32 vector [n_windows], clip b's at probs_first[b] .. probs_first[b + 1] (`rows`)."""
+    Scores of a batch: one packed float32 vector [n_windows], clip b's at probs_first[b] .. probs_first[b + 1] (`rows`).
+    A batch whose workspace exceeds a cap runs in PARTS (`parts`, `part_tables`): runs of consecutive groups, each described by a table
+    set of its own -- gx_first rebased to the part, wg_tab over the part's groups -- that shares the batch's slot and score tables."""
 
     TABLES = ("slot_off", "slot_len", "slot_clip", "gx_first", "grp_min_len", "wg_tab", "probs_first")
 
     @classmethod
-    def from_clips(cls, clips, device="cuda:0", align=ALIGN):
+    def from_clips(cls, clips, device="cuda:0", align=ALIGN, *, sampling_rate=16000):
         """clips: list of 1-D arrays, all float32 (+-1 scale) or all int16; packed on the host with every clip on a multiple of `align`
-        elements (zero filler) and uploaded once."""
+        elements (zero filler) and uploaded once.  sampling_rate: 16000 or 8000, the network the batch is for."""
         if len(clips) == 0:
             raise ValueError("a ragged batch needs at least one clip")
         align = int(align)
@@ -433,7 +447,7 @@ class RaggedClips:
         lengths = np.asarray([len(r) for r in rows], dtype=np.int64)
         starts = np.concatenate([[0], np.cumsum((lengths + align - 1) // align * align)]).astype(np.int64)
         self = cls()
-        self._set_tables(lengths, starts[:-1])
+        self._set_tables(lengths, starts[:-1], sampling_rate)
         pcm = np.zeros(int(starts[-1]), dtype=rows[0].dtype)
         for k, r in enumerate(rows):
             pcm[starts[k]:starts[k] + len(r)] = r
@@ -447,10 +461,11 @@ class RaggedClips:
         return self
 
     @classmethod
-    def from_packed(cls, pcm, clip_offsets, lengths):
+    def from_packed(cls, pcm, clip_offsets, lengths, *, sampling_rate=16000):
         """Tables only, over clips that already lie in DEVICE memory: pcm 1-D float32 or int16 tensor, clip b = lengths[b] samples from
         element clip_offsets[b] (any element: what chunks.collect_chunks_batch / drop_chunks_batch return goes in as it is).  No copy;
-        clip_offsets / lengths are host arrays or device tensors (read back once, as prepare.read_tables does)."""
+        clip_offsets / lengths are host arrays or device tensors (read back once, as prepare.read_tables does).  sampling_rate: 16000 or
+        8000, the network the batch is for."""
         from . import _lib, prepare
         t = _lib.require_gpu()
         if not t.is_tensor(pcm) or not pcm.is_cuda or pcm.dim() != 1:
@@ -463,7 +478,7 @@ class RaggedClips:
         if off.shape[0] != lengths.shape[0]:
             raise ValueError(f"{off.shape[0]} clip_offsets for {lengths.shape[0]} lengths")
         self = cls()
-        self._set_tables(lengths, off)
+        self._set_tables(lengths, off, sampling_rate)
         if int(off.min()) < 0 or int((off + self.lengths).max()) > int(pcm.numel()):
             raise ValueError(f"a clip lies outside the packed vector of {int(pcm.numel())} elements")
         self.pcm_host, self.device = None, pcm.device
@@ -471,8 +486,13 @@ class RaggedClips:
         self._upload_tables()
         return self
 
-    def _set_tables(self, lengths, clip_off):
-        """Every table of the batch: a function of the clips' lengths and offsets.  Pure numpy."""
+    def _set_tables(self, lengths, clip_off, sampling_rate=16000):
+        """Every table of the batch: a function of the clips' lengths and offsets, and of the window length of the rate's network (the
+        only thing that depends on the rate: groups, runs and gx tiles are the same at both).  Pure numpy."""
+        if sampling_rate not in SILERO_WINDOWS:
+            raise ValueError(f"sampling_rate={sampling_rate}: a ragged Silero batch is built for 16000 or 8000 Hz")
+        self.sampling_rate = int(sampling_rate)
+        self.window = SILERO_WINDOWS[self.sampling_rate]
         self.lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
         self.clip_off = np.asarray(clip_off, dtype=np.int64).reshape(-1)
         B = int(self.lengths.shape[0])
@@ -484,7 +504,7 @@ class RaggedClips:
             raise ValueError("a clip of 2^31 samples or more does not fit the int32 slot_len table")
         if B >= 2 ** 31 - SILERO_GROUP:
             raise ValueError(f"{B} clips do not fit the int32 slot tables")
-        self.windows = (self.lengths + SILERO_WINDOW - 1) // SILERO_WINDOW
+        self.windows = (self.lengths + self.window - 1) // self.window
         self.order = np.argsort(-self.windows, kind="stable").astype(np.int32)
         G = (B + SILERO_GROUP - 1) // SILERO_GROUP
         self.groups = G
@@ -496,21 +516,69 @@ class RaggedClips:
         self.slot_len_host[:B] = self.lengths[self.order]
         self.group_windows = self.windows[self.order[::SILERO_GROUP]]                    # T_g: the group's first (longest) slot
         self.tiles = int(self.group_windows.sum())
-        runs = (self.group_windows + SILERO_RUN - 1) // SILERO_RUN
-        self.n_runs = int(runs.sum())
+        self.n_runs = int(((self.group_windows + SILERO_RUN - 1) // SILERO_RUN).sum())
         if self.tiles >= 2 ** 31 or self.n_runs * SILERO_RUN >= 2 ** 31:
             raise ValueError(f"{self.tiles} gx tiles do not fit the int32 tables of a ragged batch")
+        self.wg_tab_host = _wg_tab(self.group_windows)
         self.gx_first_host = np.concatenate([[0], np.cumsum(self.group_windows)]).astype(np.int32)
         grp_min = self.slot_len_host.reshape(G, SILERO_GROUP).min(axis=1)                # 0 for a partial group (an empty slot)
         self.grp_min_len_host = grp_min.astype(np.int32)
-        # run-major over the groups that still have that run: T_g never grows with g, so those are the first n_r groups
-        n_r = np.searchsorted(-runs, -np.arange(1, int(runs.max()) + 1), side="right")   # groups with runs >= r + 1
-        grp = np.concatenate([np.arange(n, dtype=np.int32) for n in n_r])
-        run = np.repeat(np.arange(len(n_r), dtype=np.int32), n_r)
-        self.wg_tab_host = np.ascontiguousarray(np.stack([grp, run], axis=1).astype(np.int32))
         self.probs_first_host = np.concatenate([[0], np.cumsum(self.windows)]).astype(np.int64)
         self.n_windows = int(self.probs_first_host[-1])
         self.workspace_bytes = self.tiles * GX_TILE_BYTES
+        self._parts = {}
+
+    def parts(self, cap_bytes):
+        """The batch as runs of consecutive groups [(g0, g1), ...] whose gx tiles fit a workspace of cap_bytes each: chosen greedily in
+        group order, [(0, groups)] when the whole batch fits.  A single group above the cap raises (its T_g * 32 KB is one clip's own
+        length: window spans with carried state are what the rectangular `clips` has and this path does not).  Pure numpy."""
+        cap_tiles = int(cap_bytes) // GX_TILE_BYTES
+        if int(self.group_windows[0]) > cap_tiles:
+            raise ValueError(f"a ragged batch's longest group has {int(self.group_windows[0])} windows: its {int(self.group_windows[0])} gx "
+                             f"tiles of 32 KB do not fit a workspace of {int(cap_bytes)} bytes (WORKSPACE_CAP_BYTES) -- a batch runs in "
+                             "parts of whole groups, a single group is not split; score that clip with clips(), which spans windows")
+        if self.tiles <= cap_tiles:
+            return [(0, self.groups)]
+        first = self.gx_first_host.astype(np.int64)
+        out, g0 = [], 0
+        while g0 < self.groups:
+            g1 = int(np.searchsorted(first, first[g0] + cap_tiles, side="right")) - 1     # the last g1 with first[g1] - first[g0] <= cap_tiles
+            out.append((g0, g1))
+            g0 = g1
+        return out
+
+    def part_tables(self, parts):
+        """One vadx_silero_ragged per part of `parts` (what `parts` returned): the part's gx_first rebased to its first tile and its wg_tab
+        over its own groups, numbered from 0 -- built on the host for all parts at once and uploaded once per distinct `parts` --, the
+        slot tables and grp_min_len as views of the batch's at the part's first group, and the batch's clips, probs_first and status
+        (slot_clip, the scores and the state index the caller's clips)."""
+        from . import _lib
+        if self.device is None:
+            raise ValueError("this batch is host-only: call .to(device) first")
+        parts = [(int(a), int(b)) for a, b in parts]
+        if parts == [(0, self.groups)]:
+            return [self.tables()]
+        key = tuple(parts)
+        if key not in self._parts:
+            t = _lib.require_gpu()
+            gx, wg, at = [], [], []
+            for g0, g1 in parts:
+                if not 0 <= g0 < g1 <= self.groups:
+                    raise ValueError(f"part [{g0}, {g1}) is not a run of the batch's {self.groups} groups")
+                first = self.gx_first_host[g0:g1 + 1] - self.gx_first_host[g0]
+                tab = _wg_tab(self.group_windows[g0:g1])
+                at.append((sum(len(a) for a in gx), sum(len(a) for a in wg), int(tab.shape[0]), int(first[-1])))
+                gx.append(first.astype(np.int32))
+                wg.append(tab)
+            self._parts[key] = (t.from_numpy(np.concatenate(gx)).to(self.device), t.from_numpy(np.concatenate(wg)).to(self.device), at)
+        gx_dev, wg_dev, at = self._parts[key]
+        out = []
+        for (g0, g1), (gx_at, wg_at, n_runs, tiles) in zip(parts, at):
+            out.append(_lib.SileroRagged(self.slot_off.data_ptr() + 8 * SILERO_GROUP * g0, self.slot_len.data_ptr() + 4 * SILERO_GROUP * g0,
+                                         self.slot_clip.data_ptr() + 4 * SILERO_GROUP * g0, gx_dev.data_ptr() + 4 * gx_at,
+                                         self.grp_min_len.data_ptr() + 4 * g0, wg_dev.data_ptr() + 8 * wg_at, self.probs_first.data_ptr(),
+                                         self.status.data_ptr(), len(self), g1 - g0, n_runs, tiles))
+        return out
 
     def _upload_tables(self):
         from . import _lib
@@ -518,6 +586,7 @@ class RaggedClips:
         for name in self.TABLES:
             setattr(self, name, t.from_numpy(getattr(self, name + "_host")).to(self.device))
         self.status = t.zeros(1, dtype=t.int32, device=self.device)
+        self._parts = {}         # part tables uploaded earlier belong to the tables they were views of
 
     def to(self, device):
         """Upload the packed vector (once), the tables and a cleared status word."""

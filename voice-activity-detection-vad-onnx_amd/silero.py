@@ -355,20 +355,31 @@ class SileroEngine:
         return probs
 
     # -- ragged batches (vadx.ragged.RaggedClips; include/vadx.h: "Silero over a RAGGED batch")
-    def _ragged_workspace(self, batch, who):
-        need = int(batch.workspace_bytes)
-        if need > WORKSPACE_CAP_BYTES:
-            raise ValueError(f"{who}: a ragged batch of {len(batch)} clips / {batch.tiles} gx tiles needs a {need / 2**30:.1f} GiB workspace "
-                             f"(cap {WORKSPACE_CAP_BYTES / 2**30:.0f} GiB, WORKSPACE_CAP_BYTES): split the list into smaller batches "
-                             "(the ragged path has no spanned form)")
+    def _ragged_workspace(self, batch, who, whole=False):
+        """The gx workspace of a ragged batch: its sum(T_g) tiles of 32 KB, or -- above WORKSPACE_CAP_BYTES -- the tiles of its largest
+        part (RaggedClips.parts: runs of whole groups under the cap; one group above it raises there).  whole: the caller cannot run
+        in parts."""
+        parts = batch.parts(WORKSPACE_CAP_BYTES)
+        if whole and len(parts) > 1:
+            raise ValueError(f"{who}: a ragged batch of {len(batch)} clips / {batch.tiles} gx tiles needs a {batch.workspace_bytes / 2**30:.1f} "
+                             f"GiB workspace (cap {WORKSPACE_CAP_BYTES / 2**30:.0f} GiB, WORKSPACE_CAP_BYTES): the separate halves keep the "
+                             "whole batch's gx; clips_ragged runs such a batch in parts")
+        first = batch.gx_first_host
+        need = max(int(first[g1]) - int(first[g0]) for g0, g1 in parts) * 32768
         if self._ws is None or self._ws.numel() < need:
             self._ws = self.torch.empty(need, dtype=self.torch.uint8, device=self.device)
         return self._ws
 
-    def _ragged_batch(self, batch, who):
+    def _ragged_batch(self, batch, who, sampling_rate=None):
+        """`batch` as a RaggedClips on this engine's device.  A list is packed for `sampling_rate` (None: 16000); a RaggedClips carries its
+        own rate, which an explicit `sampling_rate` must not contradict."""
         from .ragged import RaggedClips
         if not isinstance(batch, RaggedClips):
-            batch = RaggedClips.from_clips(batch, device=self.device)
+            self.blob(16000 if sampling_rate is None else sampling_rate)       # (an engine without that network: refused before any upload)
+            batch = RaggedClips.from_clips(batch, device=self.device, sampling_rate=16000 if sampling_rate is None else int(sampling_rate))
+        elif sampling_rate is not None and int(sampling_rate) != batch.sampling_rate:
+            raise ValueError(f"{who}: sampling_rate={sampling_rate}, but the RaggedClips was built for {batch.sampling_rate} Hz "
+                             f"(windows of {batch.window} samples)")
         if batch.device is None:
             batch.to(self.device)
         if batch.device != self.device:
@@ -376,54 +387,68 @@ class SileroEngine:
         return batch
 
     def encode_ragged(self, batch, mode=None):
-        """First half of `clips_ragged` as its own launch (fills the workspace; no range protocol, as `encode`)."""
+        """First half of `clips_ragged` as its own launch (fills the workspace; no range protocol, as `encode`).  The network is the one
+        of the batch's rate."""
         t, L = self.torch, _lib.lib()
-        ws = self._ragged_workspace(batch, "encode_ragged")
+        rate = batch.sampling_rate
+        blob = self.blob(rate)
+        ws = self._ragged_workspace(batch, "encode_ragged", whole=True)
         tab = batch.tables()
+        k8 = rate == 8000
         with t.cuda.device(self.device):
             if batch.pcm.dtype == t.int16:
-                _lib.check(L.vadx_silero_encode_ragged_pcm16(self.packed.data_ptr(), batch.pcm.data_ptr(), self.PCM16_SCALE, int(batch.pcm.numel()),
-                                                             C.byref(tab), ws.data_ptr(), ws.numel(), _lib.stream_ptr(), self.cfg(mode)))
+                call = L.vadx_silero_encode_ragged_8k_pcm16 if k8 else L.vadx_silero_encode_ragged_pcm16
+                _lib.check(call(blob.data_ptr(), batch.pcm.data_ptr(), self.PCM16_SCALE, int(batch.pcm.numel()), C.byref(tab), ws.data_ptr(),
+                                ws.numel(), _lib.stream_ptr(), self.cfg(mode, rate)))
             else:
-                _lib.check(L.vadx_silero_encode_ragged(self.packed.data_ptr(), batch.pcm.data_ptr(), int(batch.pcm.numel()), C.byref(tab),
-                                                       ws.data_ptr(), ws.numel(), _lib.stream_ptr(), self.cfg(mode)))
+                call = L.vadx_silero_encode_ragged_8k if k8 else L.vadx_silero_encode_ragged
+                _lib.check(call(blob.data_ptr(), batch.pcm.data_ptr(), int(batch.pcm.numel()), C.byref(tab), ws.data_ptr(), ws.numel(),
+                                _lib.stream_ptr(), self.cfg(mode, rate)))
         return batch
 
     def recur_ragged(self, batch, probs=None, state_n=None, mode=None):
         """Second half of `clips_ragged`: workspace -> packed scores [batch.n_windows] (+ state_n [2, B, 128] when given)."""
-        t = self.torch
-        ws = self._ragged_workspace(batch, "recur_ragged")
+        t, L = self.torch, _lib.lib()
+        rate = batch.sampling_rate
+        blob = self.blob(rate)
+        ws = self._ragged_workspace(batch, "recur_ragged", whole=True)
         if probs is None:
             probs = t.empty(batch.n_windows, dtype=t.float32, device=self.device)
         tab = batch.tables()
+        call = L.vadx_silero_recur_ragged_8k if rate == 8000 else L.vadx_silero_recur_ragged
         with t.cuda.device(self.device):
-            _lib.check(_lib.lib().vadx_silero_recur_ragged(self.packed.data_ptr(), ws.data_ptr(), ws.numel(), int(batch.pcm.numel()), C.byref(tab),
-                                                           probs.data_ptr(), None if state_n is None else state_n.data_ptr(),
-                                                           _lib.stream_ptr(), self.cfg(mode)))
+            _lib.check(call(blob.data_ptr(), ws.data_ptr(), ws.numel(), int(batch.pcm.numel()), C.byref(tab), probs.data_ptr(),
+                            None if state_n is None else state_n.data_ptr(), _lib.stream_ptr(), self.cfg(mode, rate)))
         return probs
 
-    def clips_ragged(self, batch, return_state=False):
+    def clips_ragged(self, batch, return_state=False, sampling_rate=None):
         """A ragged batch (vadx.ragged.RaggedClips, or a list of 1-D float32 / int16 clips) -> (probs_packed float32 [sum T_b],
-        probs_first int64 [B + 1]) on the device: clip b's T_b = ceil(len_b / 512) scores are probs_packed[probs_first[b] :
+        probs_first int64 [B + 1]) on the device: clip b's T_b = ceil(len_b / 512) scores (/ 256 at 8000) are probs_packed[probs_first[b] :
         probs_first[b + 1]], bit for bit what `clips` gives for that clip alone; with return_state also state [2, B, 128], every clip's
-        LSTM state after its own last window, in the caller's clip order.  One encoder and one recurrent launch whose work follows the
-        clips' own window counts; the fp16 x 2 range protocol as `clips`."""
-        t = self.torch
-        batch = self._ragged_batch(batch, "clips_ragged")
+        LSTM state after its own last window, in the caller's clip order.  sampling_rate (16000 | 8000; None = 16000 for a list, the
+        batch's own for a RaggedClips) selects the network.  One encoder and one recurrent launch whose work follows the clips' own
+        window counts; a batch whose gx workspace exceeds WORKSPACE_CAP_BYTES runs as PARTS of consecutive groups, one such launch pair
+        each, on one cap-sized workspace and this stream -- groups are independent, so the results are the single launch's.  The fp16 x 2
+        range protocol as `clips`: one flag read per call, the whole batch recomputed when it is raised."""
+        t, L = self.torch, _lib.lib()
+        batch = self._ragged_batch(batch, "clips_ragged", sampling_rate)
+        rate = batch.sampling_rate
+        blob = self.blob(rate)
         ws = self._ragged_workspace(batch, "clips_ragged")
         probs = t.empty(batch.n_windows, dtype=t.float32, device=self.device)
         state_n = t.empty((2, len(batch), HIDDEN), dtype=t.float32, device=self.device) if return_state else None
         pcm16 = batch.pcm.dtype == t.int16
-        tab = batch.tables()
+        tabs = batch.part_tables(batch.parts(WORKSPACE_CAP_BYTES))
+        call = L.vadx_silero_clips_ragged_8k if rate == 8000 else L.vadx_silero_clips_ragged
 
         def run(mode):
             with t.cuda.device(self.device):
-                _lib.check(_lib.lib().vadx_silero_clips_ragged(self.packed.data_ptr(), batch.pcm.data_ptr(), 1 if pcm16 else 0, self.PCM16_SCALE,
-                                                               int(batch.pcm.numel()), C.byref(tab), probs.data_ptr(),
-                                                               None if state_n is None else state_n.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                               _lib.stream_ptr(), self.cfg(mode)))
+                for tab in tabs:       # stream order keeps a part's encoder behind the recurrence of the part before it
+                    _lib.check(call(blob.data_ptr(), batch.pcm.data_ptr(), 1 if pcm16 else 0, self.PCM16_SCALE, int(batch.pcm.numel()),
+                                    C.byref(tab), probs.data_ptr(), None if state_n is None else state_n.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), _lib.stream_ptr(), self.cfg(mode, rate)))
             return (probs, batch.probs_first, state_n) if return_state else (probs, batch.probs_first)
-        return self._guarded(run)
+        return self._guarded(run, rate)
 
     def segments_ragged(self, probs, probs_first, n_samples, cap=64, **kw):
         """`segments` on packed scores: probs float32 [sum T_b], probs_first int64 [B + 1] (device; a RaggedClips goes in as it is) ->
@@ -439,8 +464,8 @@ class SileroEngine:
             lens = t.as_tensor(np.asarray(n_samples, dtype=np.int64).reshape(-1).copy(), device=self.device)
         if lens.shape[0] != B:
             raise ValueError(f"{lens.shape[0]} lengths for {B} clips")
-        if int(kw.get("sampling_rate", 16000)) != 16000:
-            raise ValueError(f"segments_ragged: sampling_rate={kw['sampling_rate']}: the ragged Silero path runs at 16000 Hz only")
+        if int(kw.get("sampling_rate", 16000)) not in (16000, 8000):
+            raise ValueError(f"segments_ragged: sampling_rate={kw['sampling_rate']} is not 16000 or 8000")
         prm = seg_params(**kw)
         while True:
             segs = t.empty((B, cap, 2), dtype=t.int64, device=self.device)
@@ -898,19 +923,19 @@ def _segments_ragged(audio, model, lengths, sampling_rate, **seg_kw):
     """The device half of the batch entry points for a LIST of clips (or a vadx.ragged.RaggedClips): one ragged encoder + recurrent launch
     and the ragged segmenter -> (engine, batch, lens int64 [B] host, probs_packed, segs, counts)."""
     engine = model.engine if isinstance(model, OnnxWrapper) else model
-    if sampling_rate == 8000:
-        raise ValueError("sampling_rate=8000: a list of clips runs Silero's ragged path, which has the 16 kHz network only (the 8 kHz encoder "
-                         "has no ragged form); pass a [B, N] array with lengths=")
-    if sampling_rate != 16000 and sampling_rate % 16000 == 0:
-        raise ValueError(f"sampling_rate={sampling_rate}: a list of clips runs Silero's ragged path at 16000 Hz only (a multiple of 16000 is "
-                         "decimated only in the [B, N] array form); pass the array with lengths=, or decimate the clips")
-    if sampling_rate != 16000:
+    if sampling_rate not in (8000, 16000) and sampling_rate % 16000 == 0:
+        raise ValueError(f"sampling_rate={sampling_rate}: a list of clips runs Silero's ragged path at 16000 or 8000 Hz only (a multiple of "
+                         "16000 is decimated only in the [B, N] array form); pass the array with lengths=, or decimate the clips")
+    if sampling_rate not in (8000, 16000):
         raise ValueError("Currently silero VAD models support 8000 and 16000 (or multiply of 16000) sample rates")
+    if sampling_rate == 8000 and not engine.has_8k:
+        raise ValueError("sampling_rate=8000: only the 16 kHz sub-graph of the Silero network is loaded on the HIP path (the engine has no "
+                         "8 kHz weights: SileroEngine(..., weights_8k=...))")
     if lengths is not None:
         raise ValueError("lengths= goes with a [B, N] array: a list's clips carry their own lengths")
-    batch = engine._ragged_batch(audio, "get_speech_timestamps_batch")
+    batch = engine._ragged_batch(audio, "get_speech_timestamps_batch", sampling_rate)
     probs, first = engine.clips_ragged(batch)
-    segs, counts = engine.segments_ragged(probs, first, batch.lengths, sampling_rate=16000, **seg_kw)
+    segs, counts = engine.segments_ragged(probs, first, batch.lengths, sampling_rate=batch.sampling_rate, **seg_kw)
     return engine, batch, batch.lengths, probs, segs, counts
 
 
@@ -923,7 +948,7 @@ def get_speech_timestamps_batch(audio, model, lengths=None, threshold: float = 0
     """Batched get_speech_timestamps: audio f32 [B,N] (equal length, or `lengths` per clip with
     zero padding beyond) -> list (per clip) of lists of {'start','end'} dicts.
     audio may also be a LIST of 1-D clips (float32 on the +-1 scale, or int16) of any lengths, or a vadx.ragged.RaggedClips: the clips
-    then run as one ragged batch (16000 Hz only) -- every clip pays for its own windows, not for the longest clip's -- with the same
+    then run as one ragged batch (16000 or 8000 Hz; a RaggedClips must have been built for `sampling_rate`) -- every clip pays for its own windows, not for the longest clip's -- with the same
     lists; return_probs gives the list of per-clip score vectors (views of one packed vector)."""
     if _is_ragged(audio):
         engine, batch, lens, probs, segs, counts = _segments_ragged(
@@ -931,7 +956,7 @@ def get_speech_timestamps_batch(audio, model, lengths=None, threshold: float = 0
             max_speech_duration_s=max_speech_duration_s, min_silence_duration_ms=min_silence_duration_ms, speech_pad_ms=speech_pad_ms,
             neg_threshold=neg_threshold, min_silence_at_max_speech=min_silence_at_max_speech,
             use_max_poss_sil_at_max_speech=use_max_poss_sil_at_max_speech)
-        res = _finish(segs, counts, lens, 16000, return_seconds, time_resolution, 1)
+        res = _finish(segs, counts, lens, batch.sampling_rate, return_seconds, time_resolution, 1)
         return (res, batch.rows(probs)) if return_probs else res
     engine, given, lens, sampling_rate, step, probs, segs, counts = _segments_on_device(
         audio, model, lengths, sampling_rate, threshold=threshold, min_speech_duration_ms=min_speech_duration_ms,
@@ -958,7 +983,7 @@ def get_speech_timestamps_table(audio, model, lengths=None, sampling_rate: int =
         raise ValueError(f"time_resolution={time_resolution}: the device table rounds to one decimal (time_resolution=1) only")
     if _is_ragged(audio):        # a list of clips / a RaggedClips: the ragged launches, the same table
         engine, batch, lens, probs, segs, counts = _segments_ragged(audio, model, lengths, sampling_rate, **kw)
-        return tstable.from_samples(segs, counts, lens, 16000, fusion_threshold, min_duration, sample_rule=sample_rule)
+        return tstable.from_samples(segs, counts, lens, batch.sampling_rate, fusion_threshold, min_duration, sample_rule=sample_rule)
     engine, given, lens, sampling_rate, step, probs, segs, counts = _segments_on_device(audio, model, lengths, sampling_rate, **kw)
     if probs is None:
         return tstable.empty(given.shape[0], engine.device, sampling_rate, dicts=True)
@@ -978,7 +1003,7 @@ def get_speech_audio_batch(audio, model, lengths=None, drop=False, align=1, retu
         engine, batch, lens, probs, segs, counts = _segments_ragged(audio, model, lengths, sampling_rate, **kw)
         run = chunks.drop_chunks_batch if drop else chunks.collect_chunks_batch
         packed, offsets = run((segs, counts), batch.pcm, lengths=lens, clip_offsets=batch.clip_off, align=align)
-        return packed, offsets, _finish(segs, counts, lens, 16000, return_seconds, time_resolution, 1)
+        return packed, offsets, _finish(segs, counts, lens, batch.sampling_rate, return_seconds, time_resolution, 1)
     engine, given, lens, sampling_rate, step, probs, segs, counts = _segments_on_device(audio, model, lengths, sampling_rate, **kw)
     t = engine.torch
     B = given.shape[0]
