@@ -64,7 +64,9 @@ extern "C" {
  *     ragged batches: vadx_silero_ragged, vadx_silero_ragged_workspace_bytes, vadx_silero_encode_ragged, vadx_silero_encode_ragged_pcm16,
  *     vadx_silero_recur_ragged, vadx_silero_clips_ragged, vadx_silero_segments_ragged; then the 8 kHz network over ragged batches:
  *     vadx_silero_encode_ragged_8k, vadx_silero_encode_ragged_8k_pcm16, vadx_silero_recur_ragged_8k, vadx_silero_clips_ragged_8k
- *     (and two relaxations: vadx_silero_segments_ragged takes sampling_rate 8000, a vadx_silero_ragged may describe a run of groups).
+ *     (and two relaxations: vadx_silero_segments_ragged takes sampling_rate 8000, a vadx_silero_ragged may describe a run of groups); then
+ *     ragged ticks of the Silero streams: vadx_silero_stream_ragged_max_windows, vadx_silero_stream_plan_bytes,
+ *     vadx_silero_stream_ragged_workspace_bytes, vadx_silero_stream_plan, vadx_silero_stream_run_ragged.
  *     A caller that needs them checks for the symbols (dlsym), not for a number. */
 #define VADX_ABI_VERSION 10
 
@@ -252,7 +254,7 @@ typedef struct vadx_silero_ragged {             /* every pointer: device memory 
                                                    the smaller of this and what its own slot checks leave) */
     const int32_t *wg_tab;                      /* [n_runs][2] (group, run) */
     const int64_t *probs_first;                 /* [clips + 1] prefix of T_b in the caller's clip order */
-    uint32_t *status;                           /* [1] bit 0: a slot lay outside the source vector */
+    uint32_t *status;                           /* [1] bit 0: a slot lay outside the source vector (bit 1: vadx_silero_stream_plan) */
     int32_t clips, groups, n_runs, tiles;       /* tiles = gx_first[groups] */
 } vadx_silero_ragged;
 size_t vadx_silero_ragged_workspace_bytes(int64_t tiles);          /* tiles x 32 KB */
@@ -321,6 +323,46 @@ int vadx_silero_stream_run(const float *packed, const vadx_silero_iter_params *p
                            const void *state_in, void *state_out,
                            float *probs, int8_t *event_kind, double *event_value,
                            void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg);
+
+/* RAGGED ticks: stream s delivers n_s windows this tick, 0 <= n_s <= max_windows <= vadx_silero_stream_ragged_max_windows() = 256 (longer
+ * catch-ups go through vadx_silero_stream_run); n_s = 0 is "no audio" and costs nothing.  A tick is a ragged Silero batch ("Silero over a
+ * RAGGED batch" above) over the staged rows [context | n_s windows] of the streams with n_s > 0, read from origin 0 with the record's h / c
+ * as the initial state: Sum T_g tiles of encoder and recurrent work instead of ceil(S / 16) * max n_s.  Its table set has clips = streams
+ * and two halves:
+ *   the group tables gx_first, grp_min_len (cw + window * the smallest count of a full group, 0 for a partial one; cw = window / 8),
+ *   wg_tab and the counts groups = ceil(active / 16), n_runs, tiles are functions of the HISTOGRAM of the counts and come from the host
+ *   (vadx.ragged.stream_plan: one bincount, no sort), as does bucket_first int32 [max_windows + 2], bucket_first[c] = the number of
+ *   streams with a count above c = the first sorted position of count c;
+ *   the per-stream tables are written on the device by vadx_silero_stream_plan from counts int32 [S] and bucket_first: probs_first
+ *   int64 [S + 1], the exclusive prefix of the counts in stream order, and over the 16 * groups slots slot_clip = the streams with n_s > 0
+ *   sorted by count, descending and stable -- exactly numpy's argsort(-counts, kind="stable") restricted to them; -1 in the empty slots --,
+ *   slot_off = stream * L with L = cw + max_windows * window (the staged row), slot_len = cw + n_s * window.  A counting sort (ranks of
+ *   equal keys from wave ballots, per-block key histograms, a prefix over the blocks) whose result does not depend on the order in which
+ *   anything executes: which stream sits in which slot decides who shares a poisoned fp16 x 2 workgroup.  A count outside
+ *   [0, max_windows] is taken as 0 and bit 1 of *status is raised; so is a slot position outside the tables, which is not written.
+ *   Scratch: vadx_silero_stream_plan_bytes(S, max_windows), the FIRST bytes of the tick workspace
+ *   (vadx_silero_stream_ragged_workspace_bytes(S, max_windows, tiles) = that + the staged rows + the initial states + tiles x 32 KB), so
+ *   the plan and the tick take the same workspace pointer; the plan alone needs only its own part.  window: 512 or 256.
+ * vadx_silero_stream_run_ragged: arguments as vadx_silero_stream_run, except samples [S][row_stride] with n_s * window valid per row
+ * (row_stride >= max_windows * window), max_windows and the table set in place of `windows`, no `active`.  probs, event_kind and
+ * event_value are PACKED vectors [probs_first[S]], stream s owns probs_first[s] .. probs_first[s + 1].  A reset applies to a stream with
+ * n_s > 0 only; an idle stream's state_out record is a bitwise copy of state_in and nothing else of it is touched or computed.  The new
+ * context is the last cw samples of the stream's own n_s windows.  Record format, NaN poisoning and the range protocol are
+ * vadx_silero_stream_run's: a record written by either call continues under the other, and per stream the scores are bit for bit those
+ * of vadx_silero_clips over the concatenated audio.  A workspace below vadx_silero_stream_ragged_workspace_bytes(S, max_windows,
+ * rg->tiles) returns VADX_ENOSPACE (a tick is not run in parts).  Stream-ordered after the plan: stage, encode, recur, events. */
+int    vadx_silero_stream_ragged_max_windows(void);                                   /* 256 */
+size_t vadx_silero_stream_plan_bytes(int streams, int max_windows);                  /* 0 for arguments out of range */
+size_t vadx_silero_stream_ragged_workspace_bytes(int streams, int max_windows, int64_t tiles);
+int vadx_silero_stream_plan(const int32_t *counts, const int32_t *bucket_first, int streams, int max_windows, int window, int groups,
+                            int64_t *probs_first, int64_t *slot_off, int32_t *slot_len, int32_t *slot_clip, uint32_t *status,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int vadx_silero_stream_run_ragged(const float *packed, const vadx_silero_iter_params *prm,
+                                  const void *samples, int samples_int16, float scale, int64_t row_stride,
+                                  int streams, int max_windows, const vadx_silero_ragged *rg, const uint8_t *reset,
+                                  const void *state_in, void *state_out,
+                                  float *probs, int8_t *event_kind, double *event_value,
+                                  void *workspace, size_t workspace_bytes, void *stream, const vadx_silero_cfg *cfg);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused signal front-end: int16 PCM -> prep -> framed windowed DFT against the

@@ -2,6 +2,8 @@
 
     python tools/time_stream.py [--out profiles/stream_tick.json] [--streams 1,64,...] [--windows 1,4,16]
     python tools/time_stream.py --profile S K TICKS         (a fixed run of step() ticks only, for rocprofv3 --kernel-trace --stats)
+    python tools/time_stream.py --ragged [--out profiles/stream_tick_ragged.json] [--streams 64,4096,65536] [--windows 4,16]
+                                                            (ragged ticks, step_ragged, against what a caller does today; see ragged_main)
 
 For every (S, k): warm-up, then >= --seconds of timed ticks, three repeats.  A tick is timed by a host clock around work that ends in a
 device synchronise (step() reads the range flag, which synchronises on "h2") and by HIP events around it.  Reported: ms per tick,
@@ -62,17 +64,99 @@ def best(reps, key):
     return min(r[key] for r in reps)
 
 
+def median_ms(fn, ticks=20):
+    """median host-clock ms of `ticks` calls, each ending in a device synchronise"""
+    out = []
+    for _ in range(ticks):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(out))
+
+
+def ragged_main(a, eng, dev):
+    """Ragged ticks against today's way, per (S, max k): median of 20 synchronised ticks, the two variants alternating A B A B on the same
+    box (both medians of each are kept).  (a) every count = k against step; (b) every other stream idle against step(active=); (c)
+    counts uniform in 0 .. k against the k masked one-window step ticks a caller issues today.  The host plan (stream_plan) and the device
+    planner (HIP events around vadx_silero_stream_plan, _lib.trace) are reported on their own."""
+    from vadx import _lib, ragged
+    rows = []
+    for S in [int(v) for v in a.streams.split(",")]:
+        for k in [int(v) for v in a.windows.split(",")]:
+            x = audio(S, k, dev)
+            rng = np.random.default_rng(S + k)
+            half = np.arange(S) % 2 == 0
+            cases = dict(all_equal=np.full(S, k), half_idle=np.where(half, k, 0), uniform_0_k=rng.integers(0, k + 1, S))
+            row = dict(S=S, k=k, mode=eng.mode())
+            for name, counts in cases.items():
+                its = [silero.VADIteratorBatch(eng, S) for _ in range(2)]
+                masks = [counts > j for j in range(k)]
+
+                def new():
+                    its[0].step_ragged(x, counts)
+
+                def old():
+                    if name == "all_equal":
+                        its[1].step(x)
+                    elif name == "half_idle":
+                        its[1].step(x, active=half)
+                    else:
+                        for j in range(k):
+                            if masks[j].any():
+                                its[1].step(x[:, j * 512:(j + 1) * 512], active=masks[j])
+                for f in (new, old, new, old):          # warm-up, both
+                    f()
+                torch.cuda.synchronize()
+                ms = [median_ms(f) for f in (new, old, new, old)]
+                plan_ms = []
+                for _ in range(20):
+                    t0 = time.perf_counter()
+                    ragged.stream_plan(counts, 512)
+                    plan_ms.append((time.perf_counter() - t0) * 1e3)
+                dev_plan, dev_tick = [], []
+                for _ in range(20):
+                    with _lib.trace() as tr:
+                        its[0].step_ragged(x, counts)
+                    dev_plan.append(tr.ms["vadx_silero_stream_plan"])
+                    dev_tick.append(tr.ms["vadx_silero_stream_run_ragged"])
+                row[name] = dict(ragged_ms=[ms[0], ms[2]], today_ms=[ms[1], ms[3]], windows=int(counts.sum()),
+                                 tiles=ragged.stream_plan(counts, 512).tiles, host_plan_ms=float(np.median(plan_ms)),
+                                 device_planner_ms=float(np.median(dev_plan)), device_tick_ms=float(np.median(dev_tick)),
+                                 fallbacks=eng.range_fallbacks)
+                print(json.dumps(dict(S=S, k=k, case=name, **row[name])), flush=True)
+                del its
+            rows.append(row)
+            del x
+            torch.cuda.empty_cache()
+    out = dict(device=torch.cuda.get_device_name(0), mode=eng.mode(),
+               note="median of 20 synchronised ticks (host clock, ms), variants alternating A B A B: [first, second] median of each; "
+                    "ragged = step_ragged (host plan + one upload + device planner + tick + flag read), today = step / step(active=) / "
+                    "k masked one-window step ticks; host_plan_ms = vadx.ragged.stream_plan alone; device_planner_ms / device_tick_ms = "
+                    "HIP events around vadx_silero_stream_plan / vadx_silero_stream_run_ragged", rows=rows)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+    print("wrote", a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/stream_tick.json")
-    ap.add_argument("--streams", default="1,64,1024,4096,16384,65536")
-    ap.add_argument("--windows", default="1,4,16")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--ragged", action="store_true")
+    ap.add_argument("--streams", default=None)
+    ap.add_argument("--windows", default=None)
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--call-max-streams", type=int, default=65536)
     ap.add_argument("--profile", nargs=3, type=int, metavar=("S", "K", "TICKS"))
     a = ap.parse_args()
+    a.out = a.out or ("profiles/stream_tick_ragged.json" if a.ragged else "profiles/stream_tick.json")
+    a.streams = a.streams or ("64,4096,65536" if a.ragged else "1,64,1024,4096,16384,65536")
+    a.windows = a.windows or ("4,16" if a.ragged else "1,4,16")
     dev = torch.device("cuda:0")
     eng = silero.SileroEngine(weights.silero_synthetic(1234), device=dev)
+    if a.ragged:
+        return ragged_main(a, eng, dev)
     if a.profile:
         S, k, n = a.profile
         it = silero.VADIteratorBatch(eng, S)

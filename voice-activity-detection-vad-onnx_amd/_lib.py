@@ -193,6 +193,12 @@ SIGNATURES = {
     "vadx_silero_stream_workspace_bytes": (_Z, [_I, _I]),
     "vadx_silero_stream_run": (_I, [_P, C.POINTER(SileroIterParams), _P, _I, C.c_float, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P,
                                     _P, _Z, _P, _P]),
+    "vadx_silero_stream_ragged_max_windows": (_I, []),
+    "vadx_silero_stream_plan_bytes": (_Z, [_I, _I]),
+    "vadx_silero_stream_ragged_workspace_bytes": (_Z, [_I, _I, _L]),
+    "vadx_silero_stream_plan": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "vadx_silero_stream_run_ragged": (_I, [_P, C.POINTER(SileroIterParams), _P, _I, C.c_float, _L, _I, _I, C.POINTER(SileroRagged), _P, _P, _P,
+                                           _P, _P, _P, _P, _Z, _P, _P]),
     "vadx_silero_ragged_workspace_bytes": (_Z, [_L]),
     "vadx_silero_encode_ragged": (_I, [_P, _P, _L, C.POINTER(SileroRagged), _P, _Z, _P, _P]),
     "vadx_silero_encode_ragged_pcm16": (_I, [_P, _P, C.c_float, _L, C.POINTER(SileroRagged), _P, _Z, _P, _P]),
@@ -337,7 +343,7 @@ class _TracingLib:
 
     def __getattr__(self, name):
         fn = getattr(_load(), name)
-        if name.endswith(("_host", "_floats", "_bytes", "_version", "_error", "_out_frames", "_max_frames")):
+        if name.endswith(("_host", "_floats", "_bytes", "_version", "_error", "_out_frames", "_max_frames", "_max_windows")):
             return fn
         import torch
 

@@ -1088,6 +1088,41 @@ static int ragged_args(const char *who, int rate, const float *packed, const vad
     return VADX_OK;
 }
 
+// the launches behind encode_ragged / recur_ragged, on a checked argument (arith = VADX_AR_*); the ragged stream tick (csrc/silero_stream.hip)
+// issues the same ones with origin 0 and the records' state
+namespace vadx {
+namespace silero {
+template <typename S>
+int silero_encode_ragged_launch(int rate, const vadx_silero_cfg *cfg, const float *packed, const S *src, float in_scale, const RgArg<true> &a,
+                                float *gx, void *stream, long long origin) {
+    VADX_SILERO_ARITH(cfg, "silero (ragged)");
+    if (rate == 8000) return silero8k_encode_ragged_launch<S>(arith, packed, src, in_scale, a, gx, stream, origin);
+    if (arith == 2) return silero_encode_h2_ragged_launch<S>(packed, src, in_scale, a, gx, stream, origin);
+    if (arith == 1) return silero_encode_split_ragged_launch<S>(packed, src, in_scale, a, gx, stream, origin);
+    VADX_DYN_LDS((silero_encode_kernel<S, true>), ENC_LDS_FLOATS * sizeof(float));
+    hipLaunchKernelGGL((silero_encode_kernel<S, true>), dim3((unsigned)(a.t.n_runs * RG_RUN)), dim3(ENC_THREADS), ENC_LDS_FLOATS * sizeof(float),
+                       static_cast<hipStream_t>(stream), packed, src, in_scale, a.n_src, 0LL, origin, a.t.clips, a.t.groups, 0, 0, 0, gx, a);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+template int silero_encode_ragged_launch<float>(int, const vadx_silero_cfg *, const float *, const float *, float, const RgArg<true> &, float *,
+                                                void *, long long);
+template int silero_encode_ragged_launch<int16_t>(int, const vadx_silero_cfg *, const float *, const int16_t *, float, const RgArg<true> &, float *,
+                                                  void *, long long);
+
+int silero_recur_ragged_launch(const vadx_silero_cfg *cfg, const float *packed, const float *gx, const RgArg<true> &a, float *probs,
+                               float *state_n, void *stream, const float *state0) {
+    VADX_SILERO_ARITH(cfg, "silero (ragged)");
+    if (arith == 2) return silero_lstm_h2_ragged_launch(packed, gx, a, probs, state_n, stream, state0);
+    if (arith == 1) return silero_lstm_split_ragged_launch(packed, gx, a, probs, state_n, stream, state0);
+    hipLaunchKernelGGL(silero_lstm_kernel<true>, dim3(a.t.groups), dim3(LSTM_THREADS), LSTM_LDS_FLOATS * sizeof(float),
+                       static_cast<hipStream_t>(stream), packed, gx, state0, a.t.clips, a.t.groups, 0, probs, 0LL, state_n, a);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+}  // namespace silero
+}  // namespace vadx
+
 template <typename S>
 static int encode_ragged(const char *who, int rate, const float *packed, const S *src, float in_scale, int64_t n_src,
                          const vadx_silero_ragged *rg, void *ws, size_t ws_bytes, void *stream, const vadx_silero_cfg *cfg) {
@@ -1096,15 +1131,7 @@ static int encode_ragged(const char *who, int rate, const float *packed, const S
     RgArg<true> a;
     const int rc = ragged_args(who, rate, packed, rg, n_src, ws, ws_bytes, cfg, a);
     if (rc != VADX_OK) return rc;
-    if (rate == 8000) return silero8k_encode_ragged_launch<S>(arith, packed, src, in_scale, a, static_cast<float *>(ws), stream);
-    if (arith == 2) return silero_encode_h2_ragged_launch<S>(packed, src, in_scale, a, static_cast<float *>(ws), stream);
-    if (arith == 1) return silero_encode_split_ragged_launch<S>(packed, src, in_scale, a, static_cast<float *>(ws), stream);
-    VADX_DYN_LDS((silero_encode_kernel<S, true>), ENC_LDS_FLOATS * sizeof(float));
-    hipLaunchKernelGGL((silero_encode_kernel<S, true>), dim3((unsigned)(rg->n_runs * RG_RUN)), dim3(ENC_THREADS), ENC_LDS_FLOATS * sizeof(float),
-                       static_cast<hipStream_t>(stream), packed, src, in_scale, (long long)n_src, 0LL, -64LL, rg->clips, rg->groups, 0, 0, 0,
-                       static_cast<float *>(ws), a);
-    VADX_HIP_TRY(hipGetLastError());
-    return VADX_OK;
+    return silero_encode_ragged_launch<S>(rate, cfg, packed, src, in_scale, a, static_cast<float *>(ws), stream, rate == 8000 ? -32LL : -64LL);
 }
 
 extern "C" int vadx_silero_encode_ragged(const float *packed, const float *src, int64_t n_src, const vadx_silero_ragged *rg,
@@ -1127,13 +1154,7 @@ static int recur_ragged(const char *who, int rate, const float *packed, const vo
     const int rc = ragged_args(who, rate, packed, rg, n_src, workspace, workspace_bytes, cfg, a);
     if (rc != VADX_OK) return rc;
     const float *gx = static_cast<const float *>(workspace);
-    if (arith == 2) return silero_lstm_h2_ragged_launch(packed, gx, a, probs, state_n, stream);
-    if (arith == 1) return silero_lstm_split_ragged_launch(packed, gx, a, probs, state_n, stream);
-    hipLaunchKernelGGL(silero_lstm_kernel<true>, dim3(rg->groups), dim3(LSTM_THREADS), LSTM_LDS_FLOATS * sizeof(float),
-                       static_cast<hipStream_t>(stream), packed, gx, static_cast<const float *>(nullptr), rg->clips, rg->groups, 0, probs, 0LL,
-                       state_n, a);
-    VADX_HIP_TRY(hipGetLastError());
-    return VADX_OK;
+    return silero_recur_ragged_launch(cfg, packed, gx, a, probs, state_n, stream, nullptr);
 }
 
 static int clips_ragged(const char *who, int rate, const float *packed, const void *src, int src_int16, float scale, int64_t n_src,

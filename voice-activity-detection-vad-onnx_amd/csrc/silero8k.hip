@@ -435,10 +435,10 @@ static int launch8k(const float *packed, const S *src, float in_scale, long long
 
 // one workgroup per window of every run of the workgroup table (the caller has checked n_runs * RG_RUN < 2^31)
 template <class Sch, typename S>
-static int launch8k_ragged(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream) {
+static int launch8k_ragged(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream, long long origin) {
     VADX_DYN_LDS((silero8k_encode_kernel<Sch, S, true>), K8_LDS_BYTES);
     hipLaunchKernelGGL((silero8k_encode_kernel<Sch, S, true>), dim3((unsigned)(rg.t.n_runs * RG_RUN)), dim3(K8_THREADS), K8_LDS_BYTES,
-                       static_cast<hipStream_t>(stream), packed, src, in_scale, rg.n_src, 0LL, -32LL, rg.t.clips, rg.t.groups, 0, 0, 0, gx,
+                       static_cast<hipStream_t>(stream), packed, src, in_scale, rg.n_src, 0LL, origin, rg.t.clips, rg.t.groups, 0, 0, 0, gx,
                        rg);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
@@ -446,13 +446,13 @@ static int launch8k_ragged(const float *packed, const S *src, float in_scale, co
 
 template <typename S>
 int silero8k_encode_ragged_launch(int arith, const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx,
-                                  void *stream) {
-    if (arith == VADX_AR_H2) return launch8k_ragged<SchemeH2, S>(packed, src, in_scale, rg, gx, stream);
-    if (arith == VADX_AR_B3) return launch8k_ragged<SchemeB3, S>(packed, src, in_scale, rg, gx, stream);
-    return launch8k_ragged<SchemeF32, S>(packed, src, in_scale, rg, gx, stream);
+                                  void *stream, long long origin) {
+    if (arith == VADX_AR_H2) return launch8k_ragged<SchemeH2, S>(packed, src, in_scale, rg, gx, stream, origin);
+    if (arith == VADX_AR_B3) return launch8k_ragged<SchemeB3, S>(packed, src, in_scale, rg, gx, stream, origin);
+    return launch8k_ragged<SchemeF32, S>(packed, src, in_scale, rg, gx, stream, origin);
 }
-template int silero8k_encode_ragged_launch<float>(int, const float *, const float *, float, const RgArg<true> &, float *, void *);
-template int silero8k_encode_ragged_launch<int16_t>(int, const float *, const int16_t *, float, const RgArg<true> &, float *, void *);
+template int silero8k_encode_ragged_launch<float>(int, const float *, const float *, float, const RgArg<true> &, float *, void *, long long);
+template int silero8k_encode_ragged_launch<int16_t>(int, const float *, const int16_t *, float, const RgArg<true> &, float *, void *, long long);
 
 template <typename S>
 int silero8k_encode_launch(int arith, const float *packed, const S *src, float in_scale, long long n_valid, long long row_stride,

@@ -275,13 +275,26 @@ __device__ __forceinline__ void stage_ragged(float *X, bool fold, const SampleT 
     }
 }
 
-// host: the ragged launches of the three kernel sets (csrc/silero.hip picks by cfg)
+// host: the ragged launches of the three kernel sets (csrc/silero.hip picks by cfg).  origin: the first window's first sample within a slot
+// (-64: a clip, whose context is zeros; 0: a staged stream row [context | windows], csrc/silero_stream.hip); state0: NULL = zeros, or
+// [2][clips][128] indexed by clip
 template <typename S>
-int silero_encode_split_ragged_launch(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream);
+int silero_encode_split_ragged_launch(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream,
+                                      long long origin = -64LL);
 template <typename S>
-int silero_encode_h2_ragged_launch(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream);
-int silero_lstm_split_ragged_launch(const float *packed, const float *gx, const RgArg<true> &rg, float *probs, float *state_n, void *stream);
-int silero_lstm_h2_ragged_launch(const float *packed, const float *gx, const RgArg<true> &rg, float *probs, float *state_n, void *stream);
+int silero_encode_h2_ragged_launch(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream,
+                                   long long origin = -64LL);
+int silero_lstm_split_ragged_launch(const float *packed, const float *gx, const RgArg<true> &rg, float *probs, float *state_n, void *stream,
+                                    const float *state0 = nullptr);
+int silero_lstm_h2_ragged_launch(const float *packed, const float *gx, const RgArg<true> &rg, float *probs, float *state_n, void *stream,
+                                 const float *state0 = nullptr);
+// csrc/silero.hip: the ragged encoder and recurrent launches on an argument the caller has checked, kernel set by cfg, network by rate --
+// what vadx_silero_encode_ragged / _recur_ragged issue, also called by the ragged stream tick
+template <typename S>
+int silero_encode_ragged_launch(int rate, const vadx_silero_cfg *cfg, const float *packed, const S *src, float in_scale, const RgArg<true> &rg,
+                                float *gx, void *stream, long long origin);
+int silero_recur_ragged_launch(const vadx_silero_cfg *cfg, const float *packed, const float *gx, const RgArg<true> &rg, float *probs,
+                               float *state_n, void *stream, const float *state0);
 
 // host: launch of the split-product encoder (csrc/silero_split.hip); arguments as silero_encode_kernel's
 template <typename S>
@@ -312,7 +325,7 @@ int silero8k_encode_launch(int arith, const float *packed, const S *src, float i
 // ... and its ragged launch (the tables' windows are windows of 256)
 template <typename S>
 int silero8k_encode_ragged_launch(int arith, const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx,
-                                  void *stream);
+                                  void *stream, long long origin = -32LL);
 
 int silero_lstm_split_launch(const float *packed, const float *gx, const float *state0, int batch, int G, int steps, float *probs,
                              long long probs_stride, float *state_n, void *stream);

@@ -844,9 +844,10 @@ int silero_lstm_h2_launch(const float *packed, const float *gx, const float *sta
     return VADX_OK;
 }
 
-int silero_lstm_h2_ragged_launch(const float *packed, const float *gx, const RgArg<true> &rg, float *probs, float *state_n, void *stream) {
+int silero_lstm_h2_ragged_launch(const float *packed, const float *gx, const RgArg<true> &rg, float *probs, float *state_n, void *stream,
+                                 const float *state0) {
     hipLaunchKernelGGL(silero_lstm_h2_kernel<true>, dim3(rg.t.groups), dim3(512), LH_BYTES, static_cast<hipStream_t>(stream), packed, gx,
-                       static_cast<const float *>(nullptr), rg.t.clips, rg.t.groups, 0, probs, 0LL, state_n, rg);
+                       state0, rg.t.clips, rg.t.groups, 0, probs, 0LL, state_n, rg);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
@@ -864,17 +865,18 @@ int silero_encode_h2_launch(const float *packed, const S *src, float in_scale, l
     return VADX_OK;
 }
 template <typename S>
-int silero_encode_h2_ragged_launch(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream) {
+int silero_encode_h2_ragged_launch(const float *packed, const S *src, float in_scale, const RgArg<true> &rg, float *gx, void *stream,
+                                   long long origin) {
     constexpr int NS = H2_NSUB;
     constexpr int LDS = H2_LDS_BYTES;
     VADX_DYN_LDS((silero_encode_h2_kernel<S, NS, true>), LDS);
     hipLaunchKernelGGL((silero_encode_h2_kernel<S, NS, true>), dim3((unsigned)rg.t.n_runs), dim3(H2_THREADS), LDS, static_cast<hipStream_t>(stream),
-                       packed, src, in_scale, rg.n_src, 0LL, -64LL, rg.t.clips, rg.t.groups, 0, 0, 0, gx, rg);
+                       packed, src, in_scale, rg.n_src, 0LL, origin, rg.t.clips, rg.t.groups, 0, 0, 0, gx, rg);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
-template int silero_encode_h2_ragged_launch<float>(const float *, const float *, float, const RgArg<true> &, float *, void *);
-template int silero_encode_h2_ragged_launch<int16_t>(const float *, const int16_t *, float, const RgArg<true> &, float *, void *);
+template int silero_encode_h2_ragged_launch<float>(const float *, const float *, float, const RgArg<true> &, float *, void *, long long);
+template int silero_encode_h2_ragged_launch<int16_t>(const float *, const int16_t *, float, const RgArg<true> &, float *, void *, long long);
 template int silero_encode_h2_launch<float>(const float *, const float *, float, long long, long long, long long, int, int, int, int, int, float *, void *);
 template int silero_encode_h2_launch<int16_t>(const float *, const int16_t *, float, long long, long long, long long, int, int, int, int, int, float *, void *);
 

@@ -620,3 +620,124 @@ class RaggedClips:
             self.status.zero_()
             raise ValueError("a clip of the ragged batch lies outside the packed vector: the device did not read it and its scores are NaN")
         return self
+
+
+# ---- ragged ticks of the Silero streams (include/vadx.h: vadx_silero_stream_plan, vadx_silero_stream_run_ragged) ----
+STREAM_MAX_WINDOWS = 256     # windows per stream and tick (vadx_silero_stream_ragged_max_windows)
+PLAN_BLOCK = 1024            # streams per workgroup of the device planner (csrc/silero_stream.hip: PLAN_THREADS)
+
+
+def stream_counts(counts, streams, max_windows=None):
+    """A tick's per-stream window counts as int32 [streams], or ValueError: wrong shape, not integers, negative, above max_windows, or
+    max_windows above the cap of 256 (None = the cap)."""
+    mw = STREAM_MAX_WINDOWS if max_windows is None else int(max_windows)
+    if not 1 <= mw <= STREAM_MAX_WINDOWS:
+        raise ValueError(f"max_windows={max_windows} must be in [1, {STREAM_MAX_WINDOWS}] (longer catch-ups go through step)")
+    c = np.asarray(counts.cpu() if hasattr(counts, "cpu") else counts)
+    if c.dtype.kind not in "iu":
+        raise ValueError(f"counts must be integers, got dtype {c.dtype}")
+    if c.shape != (int(streams),):
+        raise ValueError(f"counts must have shape ({int(streams)},), got {c.shape}")
+    if c.size and int(c.min()) < 0:
+        raise ValueError(f"counts[{int(np.argmin(c))}]={int(c.min())} is negative")
+    if c.size and int(c.max()) > mw:
+        raise ValueError(f"counts[{int(np.argmax(c))}]={int(c.max())} is above max_windows={mw}")
+    return c.astype(np.int32)
+
+
+class StreamPlan:
+    """The host half of a ragged tick's tables (see stream_plan)."""
+
+    def staging(self):
+        """counts | bucket_first | gx_first | grp_min_len | wg_tab as one int32 vector, and the element offset of each"""
+        parts = [("counts", self.counts), ("bucket_first", self.bucket_first), ("gx_first", self.gx_first),
+                 ("grp_min_len", self.grp_min_len), ("wg_tab", self.wg_tab.reshape(-1))]
+        at, n = {}, 0
+        for name, a in parts:
+            at[name] = n
+            n += int(a.shape[0])
+        return np.concatenate([a for _, a in parts]).astype(np.int32), at
+
+
+def stream_plan(counts, window, max_windows=None):
+    """The group-level plan of a ragged Silero stream tick: everything that is a function of the HISTOGRAM of the counts -- one
+    np.bincount, no sort.  counts: int [S] with 0 <= n_s <= max_windows (None = the largest count, at least 1); window 512 or 256.
+    -> StreamPlan with streams, window, cw = window // 8, max_windows, counts int32 [S], active = streams with n_s > 0, groups =
+    ceil(active / 16), group_windows [G] = the count at sorted position 16 g, gx_first int32 [G + 1], n_runs, tiles, wg_tab int32
+    [n_runs, 2] (_wg_tab), grp_min_len int32 [G] = cw + window * the smallest count of a full group (0 for a partial one), n_windows =
+    sum(n_s), bucket_first int32 [max_windows + 2] (bucket_first[c] = streams with a count above c = the first sorted position of count
+    c) and row = cw + max_windows * window, the staged row length.  `staging()` is the one int32 buffer that goes to the device.
+    All-zero counts give groups = 0 and no tables."""
+    if int(window) not in SILERO_WINDOWS.values():
+        raise ValueError(f"window={window} is not 512 (16 kHz) or 256 (8 kHz)")
+    c = np.asarray(counts)
+    c = stream_counts(c, c.shape[0] if c.ndim == 1 else -1, STREAM_MAX_WINDOWS)
+    if c.shape[0] == 0:
+        raise ValueError("a tick needs at least one stream")
+    top = int(c.max())
+    mw = max(top, 1) if max_windows is None else int(max_windows)
+    if not max(top, 1) <= mw <= STREAM_MAX_WINDOWS:
+        raise ValueError(f"max_windows={max_windows} must be in [{max(top, 1)}, {STREAM_MAX_WINDOWS}] for these counts")
+    p = StreamPlan()
+    p.streams, p.window, p.cw, p.max_windows, p.counts = int(c.shape[0]), int(window), int(window) // 8, mw, c
+    p.row = p.cw + mw * p.window
+    hist = np.bincount(c, minlength=mw + 1).astype(np.int64)
+    above = np.zeros(mw + 2, dtype=np.int64)                      # above[c] = streams with a count > c
+    above[:mw] = np.cumsum(hist[:0:-1])[::-1]
+    p.bucket_first = above.astype(np.int32)
+    p.active = int(above[0])
+    p.n_windows = int((hist * np.arange(mw + 1)).sum())
+    G = (p.active + SILERO_GROUP - 1) // SILERO_GROUP
+    p.groups = G
+    if G == 0:
+        return p
+
+    def count_at(pos):           # the count at sorted positions `pos` (descending): the number of c >= 1 with above[c - 1] > pos
+        return np.searchsorted(-above[:mw], -np.asarray(pos, dtype=np.int64), side="left")
+    first = np.arange(G, dtype=np.int64) * SILERO_GROUP
+    p.group_windows = count_at(first).astype(np.int64)
+    p.tiles = int(p.group_windows.sum())
+    p.n_runs = int(((p.group_windows + SILERO_RUN - 1) // SILERO_RUN).sum())
+    p.wg_tab = _wg_tab(p.group_windows)
+    p.gx_first = np.concatenate([[0], np.cumsum(p.group_windows)]).astype(np.int32)
+    last = first + SILERO_GROUP - 1
+    p.grp_min_len = np.where(last < p.active, p.cw + p.window * count_at(np.minimum(last, p.active - 1)), 0).astype(np.int32)
+    p.workspace_bytes = p.tiles * GX_TILE_BYTES
+    return p
+
+
+def stream_slots_mirror(counts, bucket_first, groups, window, max_windows):
+    """What vadx_silero_stream_plan writes, computed the way it computes it (numpy): per block of 1024 streams the key histogram, the
+    exclusive prefix of those over the blocks, and inside a block the rank of a stream among the earlier streams of its count; position =
+    bucket_first[n_s] + prefix + rank.  A count outside [0, max_windows] counts as 0 and raises status bit 1, as a position outside the
+    16 * groups slots does (it is not written).  -> (probs_first int64 [S + 1], slot_off int64, slot_len int32, slot_clip int32
+    [16 * groups], status).  Slots nobody writes hold slot_clip -2 here (the device leaves them as they were)."""
+    c = np.asarray(counts).astype(np.int64).reshape(-1)
+    S, mw, win = int(c.shape[0]), int(max_windows), int(window)
+    cw, K, slots = win // 8, mw + 1, SILERO_GROUP * int(groups)
+    bad = (c < 0) | (c > mw)
+    status = 2 if bad.any() else 0
+    key = np.where(bad, 0, c)
+    bucket_first = np.asarray(bucket_first).astype(np.int64)
+    slot_off, slot_len, slot_clip = np.zeros(slots, np.int64), np.zeros(slots, np.int32), np.full(slots, -2, np.int32)
+    base = np.zeros(K, dtype=np.int64)                           # streams of each key in the blocks before this one
+    for b0 in range(0, S, PLAN_BLOCK):
+        k = key[b0:b0 + PLAN_BLOCK]
+        onehot = k[:, None] == np.arange(K)[None, :]
+        before = np.cumsum(onehot, axis=0) - onehot               # earlier streams of the block, per key
+        rank = before[np.arange(len(k)), k]
+        pos = bucket_first[k] + base[k] + rank
+        s = b0 + np.arange(len(k))
+        act = k > 0
+        ok = act & (pos >= 0) & (pos < slots)
+        if (act & ~ok).any():
+            status |= 2
+        slot_clip[pos[ok]] = s[ok]
+        slot_off[pos[ok]] = s[ok] * (cw + mw * win)
+        slot_len[pos[ok]] = cw + k[ok] * win
+        base += onehot.sum(axis=0)
+    e = np.arange(max(0, int(bucket_first[0])), slots)
+    if int(bucket_first[0]) >= 0:
+        slot_clip[e], slot_off[e], slot_len[e] = -1, 0, 0
+    probs_first = np.concatenate([[0], np.cumsum(key)]).astype(np.int64)
+    return probs_first, slot_off, slot_len, slot_clip, status

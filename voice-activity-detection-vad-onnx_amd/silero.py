@@ -814,6 +814,102 @@ class VADIteratorBatch(StreamBatch):
         self._end(act)
         return kind, value, probs
 
+    # -- ragged ticks: every stream its own number of windows (vadx_silero_stream_plan + vadx_silero_stream_run_ragged)
+    def _ragged_samples(self, x, counts, max_windows, win):
+        """-> (samples tensor [S, n >= max(counts) * win] on the device, counts int32 [S]); a list of S 1-D host arrays of whole windows
+        (empty allowed) carries its own counts."""
+        from . import ragged
+        eng, t, S = self.engine, self.engine.torch, self.streams
+        if isinstance(x, (list, tuple)):
+            if counts is not None:
+                raise ValueError("counts= goes with a [S, n] array: a list's rows carry their own lengths")
+            if len(x) != S:
+                raise ValueError(f"a list of samples must have {S} rows, got {len(x)}")
+            rows = [np.asarray(r.cpu() if hasattr(r, "cpu") else r) for r in x]
+            kinds = {r.dtype for r in rows if r.size}
+            if any(r.ndim != 1 for r in rows) or len(kinds) > 1 or any(k != np.int16 and k.kind != "f" for k in kinds):
+                raise ValueError("a list of samples must hold 1-D arrays, all float or all int16")
+            if any(r.shape[0] % win for r in rows):
+                raise ValueError(f"every row of a list of samples must be whole windows of {win} samples")
+            counts = ragged.stream_counts(np.array([r.shape[0] // win for r in rows], dtype=np.int64), S, max_windows)
+            dt = np.int16 if kinds == {np.dtype(np.int16)} else np.float32
+            x = np.zeros((S, max(int(counts.max()), 1) * win), dtype=dt)
+            for s, r in enumerate(rows):
+                x[s, :r.shape[0]] = r
+        else:
+            if counts is None:
+                raise ValueError("step_ragged needs counts with a [S, n] array")
+            counts = ragged.stream_counts(counts, S, max_windows)
+        top = int(counts.max())
+        x = self._samples(x, f"[{S}, >= max(counts) * {win} = {top * win}]", lambda x: x.shape[1] < top * win, floats=True)
+        return x.to(eng.device).contiguous(), counts
+
+    def step_ragged(self, x, counts=None, max_windows=None):
+        """A tick in which stream s advances by counts[s] windows, 0 = no audio (which costs nothing; the record and a pending reset are
+        kept).  x [S, >= max(counts) * 512] (256 at 8 kHz), the first counts[s] windows of row s valid -- host or device, numpy or torch,
+        float or int16 -- or a list of S 1-D host arrays of whole windows (counts then come from the list).  max_windows (None = the cap
+        of 256 a ragged tick has) bounds the counts.  -> (kind int8, value float64, probs float32, first): packed device vectors
+        [sum(counts)] of which stream s owns first[s] .. first[s + 1] (first: host int64 [S + 1]); kinds and values as `step`.  Bad
+        counts raise ValueError before anything is launched.  `step` stays the path for uniform ticks (it is faster there)."""
+        from . import ragged
+        eng, t, S = self.engine, self.engine.torch, self.streams
+        win, _ = _geom(self.sampling_rate)
+        x, counts = self._ragged_samples(x, counts, max_windows, win)
+        plan = ragged.stream_plan(counts, win)
+        first = np.zeros(S + 1, dtype=np.int64)
+        np.cumsum(counts, out=first[1:])
+        n = plan.n_windows
+        kind = t.empty(n, dtype=t.int8, device=eng.device)
+        value = t.empty(n, dtype=t.float64, device=eng.device)
+        probs = t.empty(n, dtype=t.float32, device=eng.device)
+        if plan.groups == 0:         # nobody delivered audio: no launch, the record and the pending resets stay
+            return kind, value, probs, first
+        L = _lib.lib()
+        mw = plan.max_windows
+        need = L.vadx_silero_stream_ragged_workspace_bytes(S, mw, plan.tiles)
+        if need > WORKSPACE_CAP_BYTES:
+            raise ValueError(f"step_ragged: {S} streams x at most {mw} windows ({plan.tiles} gx tiles) need a {need / 2**30:.1f} GiB "
+                             f"workspace (cap {WORKSPACE_CAP_BYTES / 2**30:.0f} GiB, WORKSPACE_CAP_BYTES): a tick is not run in parts")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = t.empty(need, dtype=t.uint8, device=eng.device)
+        act = counts > 0
+        _, _, reset_d, _, src, dst = self._begin(None, act, upload_active=False)
+        # the host tables in one copy; the per-stream tables are written on the device
+        host, at = plan.staging()
+        dev = t.from_numpy(host).to(eng.device)
+        slots = 16 * plan.groups
+        out = t.empty(2 * (S + 1) + 2 * slots + 2 * slots + 2, dtype=t.int32, device=eng.device)     # probs_first | slot_off | len | clip | status
+        p_first, p_off = out.data_ptr(), out.data_ptr() + 8 * (S + 1)
+        p_len = p_off + 8 * slots
+        p_clip, p_status = p_len + 4 * slots, p_len + 8 * slots
+        out[-2:].zero_()
+        base = dev.data_ptr()
+        rg = _lib.SileroRagged(p_off, p_len, p_clip, base + 4 * at["gx_first"], base + 4 * at["grp_min_len"], base + 4 * at["wg_tab"],
+                               p_first, p_status, S, plan.groups, plan.n_runs, plan.tiles)
+        pcm = x.dtype == t.int16
+        with t.cuda.device(eng.device):
+            _lib.check(L.vadx_silero_stream_plan(base + 4 * at["counts"], base + 4 * at["bucket_first"], S, mw, win, plan.groups, p_first,
+                                                 p_off, p_len, p_clip, p_status, self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr()))
+
+        def run(mode):
+            with t.cuda.device(eng.device):
+                _lib.check(L.vadx_silero_stream_run_ragged(eng.blob(self.sampling_rate).data_ptr(), C.byref(self._prm), x.data_ptr(),
+                                                           1 if pcm else 0, eng.PCM16_SCALE, x.stride(0), S, mw, C.byref(rg),
+                                                           None if reset_d is None else reset_d.data_ptr(), src.data_ptr(), dst.data_ptr(),
+                                                           probs.data_ptr(), kind.data_ptr(), value.data_ptr(), self._ws.data_ptr(),
+                                                           self._ws.numel(), _lib.stream_ptr(), eng.cfg(mode, self.sampling_rate)))
+        eng._guarded(run, self.sampling_rate)
+        self._end(act)
+        return kind, value, probs, first
+
+    def call_ragged(self, x, counts=None, max_windows=None, return_seconds=False, time_resolution: int = 1):
+        """Per stream, the list of the counts[s] results that counts[s] calls of the reference's VADIterator give (dict or None); [] for
+        a stream without audio."""
+        kind, value, _, first = self.step_ragged(x, counts, max_windows)
+        kind, value = kind.cpu().numpy(), value.cpu().numpy()
+        return [[_event(int(kd), float(v), self.sampling_rate, return_seconds, time_resolution)
+                 for kd, v in zip(kind[first[s]:first[s + 1]], value[first[s]:first[s + 1]])] for s in range(self.streams)]
+
     def __call__(self, x, active=None, return_seconds=False, time_resolution: int = 1):
         """Per stream, what k calls of the reference's VADIterator would return: a list of k entries (dict or None); [] for an
         inactive stream."""
