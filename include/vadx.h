@@ -66,7 +66,8 @@ extern "C" {
  *     vadx_silero_encode_ragged_8k, vadx_silero_encode_ragged_8k_pcm16, vadx_silero_recur_ragged_8k, vadx_silero_clips_ragged_8k
  *     (and two relaxations: vadx_silero_segments_ragged takes sampling_rate 8000, a vadx_silero_ragged may describe a run of groups); then
  *     ragged ticks of the Silero streams: vadx_silero_stream_ragged_max_windows, vadx_silero_stream_plan_bytes,
- *     vadx_silero_stream_ragged_workspace_bytes, vadx_silero_stream_plan, vadx_silero_stream_run_ragged.
+ *     vadx_silero_stream_ragged_workspace_bytes, vadx_silero_stream_plan, vadx_silero_stream_run_ragged; then ragged ticks of the FSMN
+ *     streams: vadx_fsmn_stream_ragged_max_windows, vadx_fsmn_stream_windows_ragged, vadx_fsmn_stream_run_ragged.
  *     A caller that needs them checks for the symbols (dlsym), not for a number. */
 #define VADX_ABI_VERSION 10
 
@@ -575,6 +576,60 @@ int vadx_fsmn_stream_run(const vadx_fsmn_dims *dims, const float *packed, const 
                          int streams, int windows, const vadx_fsmn_loop_params *lp,
                          const uint8_t *reset, const uint8_t *active, const void *state_in, void *state_out,
                          uint8_t *flags, uint8_t *tail, float *noise_trace, void *stream);
+
+/* RAGGED ticks of the FSMN streams: stream s advances by counts[s] windows this tick, 0 <= counts[s] <= max_windows <=
+ * vadx_fsmn_stream_ragged_max_windows() = 256 (no kernel resource depends on a count, so the cap is the Silero ragged tick's; longer
+ * catch-ups go through vadx_fsmn_stream_run).  The work is sum(counts) windows, not S * k: a stream with count 0 owns no window row and
+ * costs no front-end and no network time.  The RECORD is the one above -- same layout, same size, zero bytes = reset, state_in never
+ * written, two records ping-ponged -- so the two tick forms interchange tick by tick.  The tick is the sequence above with two new ends:
+ *   vadx_fsmn_stream_windows_ragged   samples + carries -> window_buf int16 [n_windows][window_len], the new carries
+ *   vadx_fsmn_window_stats            batch = n_windows, windows_per_clip = 1, row_stride = win_stride = window_len
+ *   vadx_frontend_logmel_means        the same arguments
+ *   vadx_fsmn_stream_run_ragged       the window loop per stream -> flags, tails, the rest of the record
+ * Both new calls take the same tables, reset, state_in, state_out and status:
+ *   counts    int32 [S]       windows of each stream this tick; 0 = no audio (there is no `active` argument): the stream's record in
+ *                             state_out is a bitwise copy of state_in's, a reset request for it is ignored, its tail reads 255;
+ *   win_first int32 [S + 1]   prefix sum of counts; n_windows = win_first[S].  Window j of stream s is row win_first[s] + j of window_buf,
+ *                             logmel, db, flags and noise_trace;
+ *   status    uint32 [1]      zeroed by the caller.  The tables are device memory the library cannot read on the host: a stream whose
+ *                             count lies outside [0, max_windows], or whose win_first entries do not span exactly its count inside
+ *                             [0, n_windows], COUNTS AS 0 (record copied, no flags, tail 255) and raises bit 1 (value 2) of *status;
+ *                             nothing is indexed out of bounds and no other stream changes.
+ * Per-stream results depend on nothing but that stream's record and audio: not on `order`, S, its neighbours or where its rows lie.
+ * Range protocol as for the rectangular tick: with F16X2 dims read vadx_fsmn_range_flag after vadx_fsmn_stream_run_ragged and, when it is
+ * raised, call it again with the BF16X3 dims and blob on the same arguments; every byte the first call wrote is written again.
+ * Both return VADX_EINVAL, with a message that names the argument and before any HIP call, for a NULL pointer (reset, order and
+ * noise_trace may be NULL; tail when look_backward = 0), streams, n_windows or max_windows < 1, max_windows above the cap, a look_backward
+ * that leaves no stride, a row_stride below max_windows * stride, and misaligned or overlapping records. */
+int vadx_fsmn_stream_ragged_max_windows(void);                                          /* 256 */
+
+/* Window assembly of a ragged tick.  samples int16 [S][row_stride] holds each stream's NEW samples from column 0: n_s * stride for a
+ * stream with a carry, window_len + (n_s - 1) * stride for one without (zero record, or reset this tick) -- as for
+ * vadx_fsmn_stream_windows the caller sizes the rows for the streams it knows to be in that state; row_stride >= max_windows * stride
+ * is what this call can check.  A stream's timeline is its carry followed by its new samples; window j = timeline[j * stride, j * stride +
+ * window_len) goes to row win_first[s] + j, and the new carry is the last (look_backward + 1) * 160 samples of THAT stream's timeline of
+ * n_s windows.  A stream with count 0 keeps its carry and its "has a carry" word bit for bit.  win_stream int32 [n_windows] names the
+ * stream of each window row (the counts repeated; the caller uploads it with them); a row whose entry does not agree with win_first is
+ * left unwritten.  16-byte runs: samples, window_buf and the records 16-byte aligned, row_stride and window_len multiples of 8.
+ * Replaces the slicing of FSMN/Inference_FSMN_VAD_ONNX.py:162-167, 176-234 for streams that deliver different amounts of audio. */
+int vadx_fsmn_stream_windows_ragged(const int16_t *samples, int64_t row_stride, int streams, int n_windows, int max_windows,
+                                    int window_len, int look_backward, const int32_t *counts, const int32_t *win_first,
+                                    const int32_t *win_stream, const uint8_t *reset, const void *state_in, void *state_out,
+                                    int16_t *window_buf, uint32_t *status, void *stream);
+
+/* The window loop of a ragged tick, one workgroup per stream; workgroup i serves stream order[i] (int32 [S], optional: streams with
+ * audio by count descending, idle streams last; NULL = identity).  An order entry outside [0, S) makes its workgroup return at once
+ * (and raises bit 1 of *status); a stream no entry names is not served -- nothing of it is written by this call.  The workgroup of a
+ * stream with n_s > 0 runs n_s iterations of exactly the loop body of vadx_fsmn_stream_run (one __device__ function, shared).
+ * flags u8 [n_windows][T - look_backward]: stream s owns rows win_first[s] .. win_first[s+1] - 1.  tail u8 [S][look_backward] (may be
+ * NULL when look_backward = 0): written on the stream's OWN last window of this tick; 255 for a stream without audio.  noise_trace
+ * (optional) f32 [n_windows].  The windows-done word advances by n_s.
+ * Replaces the while-loop body + tail, FSMN/Inference_FSMN_VAD_ONNX.py:162-167, 176-234, for streams that advance by different amounts. */
+int vadx_fsmn_stream_run_ragged(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db,
+                                int streams, int n_windows, int max_windows, const vadx_fsmn_loop_params *lp,
+                                const int32_t *counts, const int32_t *win_first, const int32_t *order, const uint8_t *reset,
+                                const void *state_in, void *state_out, uint8_t *flags, uint8_t *tail, float *noise_trace,
+                                uint32_t *status, void *stream);
 
 /* Ragged batches (FSMN, FireRed): B clips of ANY lengths in one launch sequence, work proportional to the sum of their windows.
  * The caller pads every clip to its own window grid on the host (the reference's tail-noise rule, FSMN/Inference_FSMN_VAD_ONNX.py:88-99 /

@@ -226,6 +226,10 @@ SIGNATURES = {
     "vadx_fsmn_stream_state_bytes": (_Z, [_I, _I]),
     "vadx_fsmn_stream_windows": (_I, [_P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vadx_fsmn_stream_run": (_I, [C.POINTER(FsmnDims), _P, _P, _P, _I, _I, C.POINTER(FsmnLoopParams), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vadx_fsmn_stream_ragged_max_windows": (_I, []),
+    "vadx_fsmn_stream_windows_ragged": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vadx_fsmn_stream_run_ragged": (_I, [C.POINTER(FsmnDims), _P, _P, _P, _I, _I, _I, C.POINTER(FsmnLoopParams), _P, _P, _P, _P, _P, _P, _P, _P,
+                                         _P, _P, _P]),
     "vadx_windows_gather": (_I, [_P, _L, _P, _I, _I, _P, _P]),
     "vadx_fsmn_clips_ragged": (_I, [C.POINTER(FsmnDims), _P, _P, _P, _I, _I, _I, _P, _P, C.POINTER(FsmnLoopParams), _P, _P, _L, _P, _P]),
     "vadx_fsmn_long_workspace_bytes": (_Z, [_I, _I]),

@@ -825,17 +825,61 @@ struct StreamArgs {
     float *noise_trace;                   // optional [S][k]
 };
 
+// One window of a live stream -- the loop body both stream kernels run, written once: the network over the window (run_chunk), the score
+// gate, the look-ahead vote that continues `silence` and writes the window's `slide` flags to fl, the noise-floor update, the trace, and --
+// on the stream's LAST window of this tick -- the tail: the plain rule on a COPY of silence (the carried value is the one the next tick's
+// vote continues from).  noise and silence are the caller's carried values (silence is thread 0's); widx is the window's row in logmel /
+// db / noise_trace.
+template <int AR>
+__device__ __forceinline__ void stream_window(const Dev &d, const float *__restrict__ Pk, const float *logmel, const float *db, size_t widx,
+                                              const float *const *cin, float *const *cout, int slide, int lb, float thr, float snr,
+                                              double speaking, double silence_score, unsigned char *fl, unsigned char *tl, bool last,
+                                              float *noise_trace, float &noise, int &silence, float *lds, float &amax) {
+    const int tid = threadIdx.x;
+    const Small<AR> sm(lds);
+    float *ps = sm.ps, *red = sm.red, *sc = sm.sc, *cnt = sm.cnt;
+    run_chunk<AR>(d, Pk, logmel + widx * d.T * NMEL, cin, cout, lds, amax);
+    const float noisy = gate(d, ps, db + widx * d.T, thr, noise, nullptr, nullptr, sc, red);
+    // look-ahead vote: cnt[i] = #{ j in [1,lb) : sc[i+j] != 0 }
+    if (tid < slide) {
+        float v = 0.f;
+        for (int j = 1; j < lb; ++j) v += sc[tid + j];
+        cnt[tid] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double inv_lb = 1.0 / (double)lb;
+        for (int i = 0; i < slide; ++i) {
+            if (silence) {
+                if (sc[i] != 0.f) silence = !((1.0 + (double)cnt[i]) * inv_lb >= speaking);
+                else silence = 1;
+            } else {
+                if (sc[i] != 1.f) silence = !((1.0 + (double)((lb - 1) - cnt[i])) * inv_lb <= silence_score);
+                else silence = 0;
+            }
+            fl[i] = (unsigned char)silence;
+        }
+        if (last) {                        // what the tail would read if the stream ended here: plain rule (:223-234)
+            int st = silence;
+            for (int i = slide; i < d.T; ++i) {
+                st = st ? !(sc[i] != 0.f) : (sc[i] != 1.f);
+                tl[i - slide] = (unsigned char)st;
+            }
+        }
+    }
+    if (noisy > 0.0f) noise = 0.5f * ((noise + noisy) + snr);
+    if (noise_trace && tid == 0) noise_trace[widx] = noise;
+    __syncthreads();
+}
+
 // fsmn_clips_kernel's window loop with its state (four caches, noise floor, silence) loaded from state_in and stored to state_out; one
 // workgroup per stream.  state_in is only read: run_chunk reads the caches of a window's first tile from `cin` and everything later from
-// `cout`, so window 0 points cin at state_in and nothing is copied.  The tail of the tick's last window follows the plain rule on a COPY
-// of silence: the carried value is the one the next tick's vote continues from.
+// `cout`, so window 0 points cin at state_in and nothing is copied.
 template <int AR>
 __global__ __launch_bounds__(THREADS, 2) void fsmn_stream_kernel(Dev d, const float *__restrict__ Pk, StreamArgs c) {
     float amax = 0.f;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int s = blockIdx.x, tid = threadIdx.x;
-    const Small<AR> sm(lds);
-    float *ps = sm.ps, *red = sm.red, *sc = sm.sc, *cnt = sm.cnt;
     const float *cache_in = reinterpret_cast<const float *>(c.sin) + (size_t)s * CACHE_FLOATS;
     float *cache_out = reinterpret_cast<float *>(c.sout) + (size_t)s * CACHE_FLOATS;
     const unsigned *hin = reinterpret_cast<const unsigned *>(c.sin + c.hdr) + (size_t)s * HDR_WORDS;
@@ -862,48 +906,148 @@ __global__ __launch_bounds__(THREADS, 2) void fsmn_stream_kernel(Dev d, const fl
     float noise = fresh ? c.noise0 : __uint_as_float(hin[H_NOISE]);
     int silence = fresh ? 1 : (int)hin[H_SIL];                                    // carried by thread 0
     for (int k = 0; k < c.k; ++k) {
-        const size_t widx = (size_t)s * c.k + k;
         const float *cin[NLAYER];
 #pragma unroll
         for (int l = 0; l < NLAYER; ++l) cin[l] = (k == 0 && !fresh ? cache_in : cache_out) + l * PROJ * HIST;
-        run_chunk<AR>(d, Pk, c.logmel + widx * d.T * NMEL, cin, cout, lds, amax);
-        const float noisy = gate(d, ps, c.db + widx * d.T, c.thr, noise, nullptr, nullptr, sc, red);
-        // look-ahead vote: cnt[i] = #{ j in [1,lb) : sc[i+j] != 0 }
-        if (tid < c.slide) {
-            float v = 0.f;
-            for (int j = 1; j < c.lb; ++j) v += sc[tid + j];
-            cnt[tid] = v;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const double inv_lb = 1.0 / (double)c.lb;
-            for (int i = 0; i < c.slide; ++i) {
-                if (silence) {
-                    if (sc[i] != 0.f) silence = !((1.0 + (double)cnt[i]) * inv_lb >= c.speaking);
-                    else silence = 1;
-                } else {
-                    if (sc[i] != 1.f) silence = !((1.0 + (double)((c.lb - 1) - cnt[i])) * inv_lb <= c.silence_score);
-                    else silence = 0;
-                }
-                fl[k * c.slide + i] = (unsigned char)silence;
-            }
-            if (k == c.k - 1) {            // what the tail would read if the stream ended here: plain rule (:223-234)
-                int st = silence;
-                for (int i = c.slide; i < d.T; ++i) {
-                    st = st ? !(sc[i] != 0.f) : (sc[i] != 1.f);
-                    tl[i - c.slide] = (unsigned char)st;
-                }
-            }
-        }
-        if (noisy > 0.0f) noise = 0.5f * ((noise + noisy) + c.snr);
-        if (c.noise_trace && tid == 0) c.noise_trace[widx] = noise;
-        __syncthreads();
+        stream_window<AR>(d, Pk, c.logmel, c.db, (size_t)s * c.k + k, cin, cout, c.slide, c.lb, c.thr, c.snr, c.speaking, c.silence_score,
+                          fl + k * c.slide, tl, k == c.k - 1, c.noise_trace, noise, silence, lds, amax);
     }
     if (tid == 0) {
         hout[H_NOISE] = __float_as_uint(noise);
         hout[H_SIL] = (unsigned)silence;
         const unsigned long long done = fresh ? 0ull : *reinterpret_cast<const unsigned long long *>(hin + H_DONE);
         *reinterpret_cast<unsigned long long *>(hout + H_DONE) = done + (unsigned long long)c.k;
+        hout[H_DONE + 2] = 0u; hout[H_DONE + 3] = 0u;
+    }
+    if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
+}
+
+// ---- ragged ticks: stream s advances by counts[s] windows, 0 <= counts[s] <= max_windows; the work is sum(counts) windows ------------------
+// counts int32 [S] and win_first int32 [S + 1] (its prefix sum; n_windows = win_first[S]) describe the tick to both kernels; window j of
+// stream s is row win_first[s] + j of window_buf and of everything the front-end makes of it.  A stream with count 0 owns no row.  The
+// tables are the caller's: a stream whose entries do not describe rows inside the buffers counts as 0 and raises bit 1 of *status.
+constexpr int STREAM_RAGGED_MAX_WINDOWS = 256;       // no kernel resource depends on a count (a loop bound, a row index): the cap of the Silero tick
+constexpr unsigned STATUS_BAD_TABLE = 2u;
+
+// counts[s] when the tables of stream s describe rows inside [0, n_windows), else -1
+__device__ __forceinline__ int ragged_count(const int *counts, const int *win_first, int s, int n_windows, int max_windows) {
+    const int n = counts[s], first = win_first[s], last = win_first[s + 1];
+    return (n >= 0 && n <= max_windows && first >= 0 && last <= n_windows && last - first == n) ? n : -1;
+}
+
+struct WinRaggedArgs {
+    const int16_t *samples; long long row_stride;   // [S][row_stride]: n_s * stride new samples (L + (n_s - 1) * stride without a carry)
+    int S, n_windows, max_windows, L, C;
+    const int *counts, *win_first, *win_stream;     // [S], [S + 1], [n_windows]: the stream of each window row
+    const unsigned char *reset;                     // optional [S]
+    const unsigned char *sin; unsigned char *sout;
+    size_t hdr, carry;
+    int16_t *wbuf;                                  // [n_windows][L]
+    unsigned *status;
+};
+
+// fsmn_stream_windows_kernel's timeline rule with a count per stream: workgroup w < n_windows assembles window row w (stream win_stream[w],
+// its window w - win_first[s]); workgroup n_windows + s writes stream s's new carry -- the last C samples of ITS timeline of n_s windows --
+// or, for a stream without audio, copies the carry and the "has a carry" word bit for bit.  16-byte runs throughout.
+__global__ __launch_bounds__(256) void fsmn_stream_windows_ragged_kernel(WinRaggedArgs a) {
+    typedef short s16x8 __attribute__((ext_vector_type(8)));
+    const int w = blockIdx.x, tid = threadIdx.x;
+    const bool is_win = w < a.n_windows;
+    const int s = is_win ? a.win_stream[w] : w - a.n_windows;
+    if (s < 0 || s >= a.S) return;                  // a window row nobody owns stays unwritten
+    const int n = ragged_count(a.counts, a.win_first, s, a.n_windows, a.max_windows);
+    const unsigned *hin = reinterpret_cast<const unsigned *>(a.sin + a.hdr) + (size_t)s * HDR_WORDS;
+    unsigned *hout = reinterpret_cast<unsigned *>(a.sout + a.hdr) + (size_t)s * HDR_WORDS;
+    const s16x8 *cin = reinterpret_cast<const s16x8 *>(a.sin + a.carry + (size_t)s * a.C * sizeof(int16_t));
+    s16x8 *cout = reinterpret_cast<s16x8 *>(a.sout + a.carry + (size_t)s * a.C * sizeof(int16_t));
+    const int nc = a.C / 8, nl = a.L / 8, ns = (a.L - a.C) / 8;
+    if (n <= 0) {
+        if (!is_win) {
+            for (int v = tid; v < nc; v += 256) cout[v] = cin[v];
+            if (tid < 2) hout[H_PRIMED + tid] = hin[H_PRIMED + tid];
+            if (n < 0 && tid == 0) atomicOr(a.status, STATUS_BAD_TABLE);
+        }
+        return;
+    }
+    const bool primed = hin[H_PRIMED] != 0 && !(a.reset && a.reset[s]);
+    const s16x8 *smp = reinterpret_cast<const s16x8 *>(a.samples + (long long)s * a.row_stride);
+    auto timeline = [&](int v) { return primed ? (v < nc ? cin[v] : smp[v - nc]) : smp[v]; };       // 8-sample run v
+    if (is_win) {
+        const int j = w - a.win_first[s];
+        if (j < 0 || j >= n) return;                // the row table and win_first disagree: not this stream's row
+        s16x8 *win = reinterpret_cast<s16x8 *>(a.wbuf + (size_t)w * a.L);
+        for (int v = tid; v < nl; v += 256) win[v] = timeline(j * ns + v);
+    } else {
+        for (int v = tid; v < nc; v += 256) cout[v] = timeline(n * ns + v);          // the stream's timeline holds n * stride + C samples
+        if (tid < 2) hout[H_PRIMED + tid] = tid == 0 ? 1u : 0u;
+    }
+}
+
+struct StreamRaggedArgs {
+    const float *logmel, *db;             // [n_windows][T][80], [n_windows][T]
+    const unsigned char *sin; unsigned char *sout; size_t hdr;
+    const unsigned char *reset;           // optional [S]
+    const int *counts, *win_first, *order;          // [S], [S + 1], [S] launch order (optional)
+    int S, n_windows, max_windows, slide, lb, ntail;
+    float thr, noise0, snr;
+    double speaking, silence_score;
+    unsigned char *flags, *tail;          // [n_windows][slide], [S][ntail]
+    float *noise_trace;                   // optional [n_windows]
+    unsigned *status;
+};
+
+// fsmn_stream_kernel with a count per stream: workgroup i serves stream order[i] (most windows first, idle streams last) and runs
+// stream_window n_s times over its own rows.  A stream without audio (count 0, or tables that lie) copies its caches and header bit for bit
+// and reads 255 in its tail; it touches no flag or trace row.
+template <int AR>
+__global__ __launch_bounds__(THREADS, 2) void fsmn_stream_ragged_kernel(Dev d, const float *__restrict__ Pk, StreamRaggedArgs c) {
+    float amax = 0.f;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x;
+    const int s = c.order ? c.order[blockIdx.x] : (int)blockIdx.x;
+    if (s < 0 || s >= c.S) {
+        if (tid == 0) atomicOr(c.status, STATUS_BAD_TABLE);
+        return;
+    }
+    const int n = ragged_count(c.counts, c.win_first, s, c.n_windows, c.max_windows);
+    const float *cache_in = reinterpret_cast<const float *>(c.sin) + (size_t)s * CACHE_FLOATS;
+    float *cache_out = reinterpret_cast<float *>(c.sout) + (size_t)s * CACHE_FLOATS;
+    const unsigned *hin = reinterpret_cast<const unsigned *>(c.sin + c.hdr) + (size_t)s * HDR_WORDS;
+    unsigned *hout = reinterpret_cast<unsigned *>(c.sout + c.hdr) + (size_t)s * HDR_WORDS;
+    unsigned char *tl = c.tail + (size_t)s * c.ntail;
+    if (n <= 0) {
+        const unsigned *ci = reinterpret_cast<const unsigned *>(cache_in);
+        unsigned *co = reinterpret_cast<unsigned *>(cache_out);
+        for (int e = tid; e < CACHE_FLOATS; e += THREADS) co[e] = ci[e];
+        if (tid < HDR_WORDS && (tid < H_PRIMED || tid >= H_DONE)) hout[tid] = hin[tid];
+        for (int e = tid; e < c.ntail; e += THREADS) tl[e] = 255;
+        if (n < 0 && tid == 0) atomicOr(c.status, STATUS_BAD_TABLE);
+        return;
+    }
+    const size_t first = (size_t)c.win_first[s];
+    unsigned char *fl = c.flags + first * c.slide;
+    const bool fresh = hin[H_PRIMED] == 0 || (c.reset && c.reset[s]);
+    if (fresh) {
+        for (int e = tid; e < CACHE_FLOATS; e += THREADS) cache_out[e] = 0.f;
+        __syncthreads();
+    }
+    float *cout[NLAYER];
+#pragma unroll
+    for (int l = 0; l < NLAYER; ++l) cout[l] = cache_out + l * PROJ * HIST;
+    float noise = fresh ? c.noise0 : __uint_as_float(hin[H_NOISE]);
+    int silence = fresh ? 1 : (int)hin[H_SIL];                                    // carried by thread 0
+    for (int k = 0; k < n; ++k) {
+        const float *cin[NLAYER];
+#pragma unroll
+        for (int l = 0; l < NLAYER; ++l) cin[l] = (k == 0 && !fresh ? cache_in : cache_out) + l * PROJ * HIST;
+        stream_window<AR>(d, Pk, c.logmel, c.db, first + k, cin, cout, c.slide, c.lb, c.thr, c.snr, c.speaking, c.silence_score,
+                          fl + k * c.slide, tl, k == n - 1, c.noise_trace, noise, silence, lds, amax);
+    }
+    if (tid == 0) {
+        hout[H_NOISE] = __float_as_uint(noise);
+        hout[H_SIL] = (unsigned)silence;
+        const unsigned long long done = fresh ? 0ull : *reinterpret_cast<const unsigned long long *>(hin + H_DONE);
+        *reinterpret_cast<unsigned long long *>(hout + H_DONE) = done + (unsigned long long)n;
         hout[H_DONE + 2] = 0u; hout[H_DONE + 3] = 0u;
     }
     if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
@@ -1462,5 +1606,87 @@ extern "C" int vadx_fsmn_stream_run(const vadx_fsmn_dims *dims, const float *pac
     c.lb = a.lb; c.slide = a.slide; c.thr = a.thr; c.noise0 = a.noise0; c.snr = a.snr; c.speaking = a.speaking; c.silence_score = a.silence_score;
     c.flags = flags; c.tail = tail; c.noise_trace = noise_trace;
     FSMN_LAUNCH(fsmn_stream_kernel, d.arith, streams, stream, d, packed, c);
+    return VADX_OK;
+}
+
+// ---- ragged ticks: every refusal names its argument and comes before any HIP call ---------------------------------------------------------
+extern "C" int vadx_fsmn_stream_ragged_max_windows(void) { return STREAM_RAGGED_MAX_WINDOWS; }
+
+// what both ragged calls check alike: the sizes, the tables and the two records
+static int ragged_tick_args(const char *who, int streams, int n_windows, int max_windows, int look_backward, const int32_t *counts,
+                            const int32_t *win_first, const void *state_in, void *state_out, const uint32_t *status) {
+    VADX_REQUIRE(counts != nullptr, "%s: NULL counts", who);
+    VADX_REQUIRE(win_first != nullptr, "%s: NULL win_first", who);
+    VADX_REQUIRE(state_in != nullptr, "%s: NULL state_in", who);
+    VADX_REQUIRE(state_out != nullptr, "%s: NULL state_out", who);
+    VADX_REQUIRE(status != nullptr, "%s: NULL status", who);
+    VADX_REQUIRE(streams >= 1, "%s: streams=%d must be at least 1", who, streams);
+    VADX_REQUIRE(n_windows >= 1, "%s: n_windows=%d must be at least 1 (a tick without audio is not launched)", who, n_windows);
+    VADX_REQUIRE(max_windows >= 1 && max_windows <= STREAM_RAGGED_MAX_WINDOWS,
+                 "%s: max_windows=%d outside [1, %d] (vadx_fsmn_stream_ragged_max_windows; longer catch-ups go through vadx_fsmn_stream_run)",
+                 who, max_windows, STREAM_RAGGED_MAX_WINDOWS);
+    VADX_REQUIRE((long long)streams + (long long)n_windows < (1ll << 31), "%s: streams=%d + n_windows=%d workgroups", who, streams, n_windows);
+    VADX_REQUIRE(look_backward >= 0, "%s: look_backward=%d is negative", who, look_backward);
+    VADX_REQUIRE(((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 15) == 0,
+                 "%s: state_in and state_out must be 16-byte aligned", who);
+    VADX_REQUIRE(!vadx::records_overlap(state_in, state_out, rec_bytes(streams, (look_backward + 1) * 160)), "%s: state_in and state_out overlap", who);
+    return VADX_OK;
+}
+
+extern "C" int vadx_fsmn_stream_windows_ragged(const int16_t *samples, int64_t row_stride, int streams, int n_windows, int max_windows,
+                                               int window_len, int look_backward, const int32_t *counts, const int32_t *win_first,
+                                               const int32_t *win_stream, const uint8_t *reset, const void *state_in, void *state_out,
+                                               int16_t *window_buf, uint32_t *status, void *stream) {
+    const char *who = "vadx_fsmn_stream_windows_ragged";
+    VADX_REQUIRE(samples != nullptr, "%s: NULL samples", who);
+    VADX_REQUIRE(win_stream != nullptr, "%s: NULL win_stream", who);
+    VADX_REQUIRE(window_buf != nullptr, "%s: NULL window_buf", who);
+    VADX_REQUIRE(window_len >= 512 && window_len % 8 == 0, "%s: window_len=%d must be a multiple of 8, at least 512", who, window_len);
+    const int T = window_len / 160 + 1, C = (look_backward + 1) * 160, stride = window_len - C;
+    VADX_REQUIRE(look_backward >= 0 && look_backward < T && stride > 0,
+                 "%s: look_backward=%d outside [0, %d) or no stride left (window_len - (look_backward + 1) * 160 = %d)", who, look_backward, T, stride);
+    int rc = ragged_tick_args(who, streams, n_windows, max_windows, look_backward, counts, win_first, state_in, state_out, status);
+    if (rc) return rc;
+    VADX_REQUIRE(row_stride >= (int64_t)max_windows * stride && row_stride % 8 == 0,
+                 "%s: row_stride=%lld must be a multiple of 8 and hold max_windows * stride = %lld samples", who, (long long)row_stride,
+                 (long long)max_windows * stride);
+    VADX_REQUIRE(((reinterpret_cast<uintptr_t>(samples) | reinterpret_cast<uintptr_t>(window_buf)) & 15) == 0,
+                 "%s: samples and window_buf must be 16-byte aligned", who);
+    WinRaggedArgs a;
+    a.samples = samples; a.row_stride = (long long)row_stride; a.S = streams; a.n_windows = n_windows; a.max_windows = max_windows;
+    a.L = window_len; a.C = C; a.counts = counts; a.win_first = win_first; a.win_stream = win_stream; a.reset = reset;
+    a.sin = static_cast<const unsigned char *>(state_in); a.sout = static_cast<unsigned char *>(state_out);
+    a.hdr = rec_hdr(streams); a.carry = rec_carry(streams); a.wbuf = window_buf; a.status = status;
+    hipLaunchKernelGGL(fsmn_stream_windows_ragged_kernel, dim3((unsigned)(n_windows + streams)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+extern "C" int vadx_fsmn_stream_run_ragged(const vadx_fsmn_dims *dims, const float *packed, const float *logmel, const float *db, int streams,
+                                           int n_windows, int max_windows, const vadx_fsmn_loop_params *lp, const int32_t *counts,
+                                           const int32_t *win_first, const int32_t *order, const uint8_t *reset, const void *state_in,
+                                           void *state_out, uint8_t *flags, uint8_t *tail, float *noise_trace, uint32_t *status, void *stream) {
+    const char *who = "vadx_fsmn_stream_run_ragged";
+    Dev d;
+    VADX_REQUIRE(dims != nullptr, "%s: NULL dims", who);
+    VADX_REQUIRE(packed != nullptr, "%s: NULL packed", who);
+    VADX_REQUIRE(logmel != nullptr, "%s: NULL logmel", who);
+    VADX_REQUIRE(db != nullptr, "%s: NULL db", who);
+    VADX_REQUIRE(lp != nullptr, "%s: NULL lp", who);
+    VADX_REQUIRE(flags != nullptr, "%s: NULL flags", who);
+    VADX_REQUIRE(derive(dims, &d) == 0, "%s: unsupported dims", who);
+    LoopArgs a;
+    int rc = loop_args(who, d, lp, true, &a);
+    if (rc) return rc;
+    rc = ragged_tick_args(who, streams, n_windows, max_windows, lp->look_backward, counts, win_first, state_in, state_out, status);
+    if (rc) return rc;
+    VADX_REQUIRE(tail || lp->look_backward == 0, "%s: NULL tail with look_backward=%d", who, lp->look_backward);
+    StreamRaggedArgs c;
+    c.logmel = logmel; c.db = db; c.sin = static_cast<const unsigned char *>(state_in); c.sout = static_cast<unsigned char *>(state_out);
+    c.hdr = rec_hdr(streams); c.reset = reset; c.counts = counts; c.win_first = win_first; c.order = order;
+    c.S = streams; c.n_windows = n_windows; c.max_windows = max_windows; c.ntail = lp->look_backward;
+    c.lb = a.lb; c.slide = a.slide; c.thr = a.thr; c.noise0 = a.noise0; c.snr = a.snr; c.speaking = a.speaking; c.silence_score = a.silence_score;
+    c.flags = flags; c.tail = tail; c.noise_trace = noise_trace; c.status = status;
+    FSMN_LAUNCH(fsmn_stream_ragged_kernel, d.arith, streams, stream, d, packed, c);
     return VADX_OK;
 }

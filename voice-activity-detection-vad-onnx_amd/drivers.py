@@ -185,6 +185,27 @@ def inference_fsmn(test_vad_audio="./vad_sample.wav", engine=None, save_timestam
     return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, not isinstance(test_vad_audio, (list, tuple)), elapsed, echo)
 
 
+def inference_fsmn_stream(test_vad_audio="./vad_sample.wav", engine=None, save_timestamps_second="./timestamps_second.txt",
+                          save_timestamps_indices="./timestamps_indices.txt", FUSION_THRESHOLD=0.3, MIN_SPEECH_DURATION=0.2,
+                          SPEAKING_SCORE=0.5, SILENCE_SCORE=0.5, LOOK_BACKWARD=0.3, SNR_THRESHOLD=10.0,
+                          BACKGROUND_NOISE_dB_INIT=30.0, ONE_MINUS_SPEECH_THRESHOLD=1.0, pad_noise=None, echo=print, windows_per_tick=1):
+    """FSMN/Inference_FSMN_VAD_ONNX.py:66-260 with every file fed as a LIVE STREAM: the files of a list are the streams of one batch
+    (FsmnEngine.stream_detect: ragged ticks, every file advancing by up to `windows_per_tick` windows per tick until the longest is
+    done) -> the outputs `inference_fsmn` produces for the same files."""
+    from . import fsmn
+    engine = _engine_of(fsmn.FsmnEngine, engine)
+    files, single = _as_list(test_vad_audio), not isinstance(test_vad_audio, (list, tuple))
+    clips = _load(files)
+    echo("\nRunning the FSMN_VAD by ONNX Runtime (streamed).")
+    t0 = time.time()
+    all_ts = engine.stream_detect(clips, windows_per_tick=windows_per_tick, pad_noise=pad_noise, fusion_threshold=FUSION_THRESHOLD,
+                                  min_speech_duration=MIN_SPEECH_DURATION, look_backward_s=LOOK_BACKWARD, speaking_score=SPEAKING_SCORE,
+                                  silence_score=SILENCE_SCORE, snr_threshold=SNR_THRESHOLD, noise_init_dB=BACKGROUND_NOISE_dB_INIT,
+                                  one_minus_speech_threshold=ONE_MINUS_SPEECH_THRESHOLD)
+    elapsed = time.time() - t0
+    return _finish(all_ts, 16000, save_timestamps_second, save_timestamps_indices, single, elapsed, echo)
+
+
 def inference_firered(test_vad_audio="./vad_sample.wav", engine=None, save_timestamps_second="./timestamps_second.txt",
                       save_timestamps_indices="./timestamps_indices.txt", NORMALIZE_AUDIO=False, SMOOTH_WINDOW_SIZE=5,
                       SPEAKING_SCORE=0.4, MIN_SPEECH_FRAME=20, MAX_SPEECH_FRAME=2000, MIN_SILENCE_FRAME=20,

@@ -333,6 +333,37 @@ class FsmnEngine:
         return tstable.from_flags(flags, nflags, OUTPUT_FRAME_LENGTH / SAMPLE_RATE, fusion_threshold, min_speech_duration, SAMPLE_RATE, sample_rule)
 
 
+    def stream_detect(self, clips, windows_per_tick=1, pad_noise=None, normalize=True, fusion_threshold=0.3, min_speech_duration=0.2,
+                      **loop_kw):
+        """A list of 1-D int16 clips of any lengths run as the live streams of one FsmnStreamBatch with RAGGED ticks until the longest is
+        done: every clip is normalised and padded to its own window grid exactly as `detect(list)` does, and stream s advances by
+        min(windows_per_tick, windows left) windows per tick (0 once it is through) -> what `detect(list)` returns.  The clips are whole
+        here; a caller with truly live audio drives FsmnStreamBatch.step_ragged itself and pads a stream's end."""
+        k = int(windows_per_tick)
+        if k < 1:
+            raise ValueError(f"windows_per_tick={windows_per_tick} must be at least 1")
+        look_backward_s = loop_kw.pop("look_backward_s", 0.3)
+        rb = self.ragged(list(clips), pad_noise, normalize, look_backward_s, device=None)
+        S = len(rb)
+        sb = FsmnStreamBatch(self, S, look_backward_s=look_backward_s, **loop_kw)
+        left, pos = rb.windows.astype(np.int64), rb.clip_off.astype(np.int64)
+        parts, tails = [[] for _ in range(S)], [None] * S
+        while left.any():
+            counts = np.minimum(left, k)
+            need = sb.samples_needed_ragged(counts)
+            x = np.zeros((S, int(need.max())), dtype=np.int16)
+            for s in np.flatnonzero(counts).tolist():
+                x[s, :need[s]] = rb.pcm_host[pos[s]:pos[s] + need[s]]
+            pos, left = pos + need, left - counts
+            flags, tail, first = sb.step_ragged(x, counts, max_windows=k)
+            for s in np.flatnonzero(counts).tolist():
+                parts[s].append(flags[first[s]:first[s + 1]].reshape(-1))
+                if left[s] == 0:
+                    tails[s] = tail[s]
+        return [flag_timestamps(self.torch.cat(parts[s] + [tails[s]]).cpu().numpy(), OUTPUT_FRAME_LENGTH / SAMPLE_RATE, fusion_threshold,
+                                min_speech_duration) for s in range(S)]
+
+
 class FsmnSession(Session):
     """onnxruntime.InferenceSession look-alike for the FSMN graph (names/dtypes/shapes of
     FSMN/Export_FSMN_VAD.py:115-134); feeds may carry a leading batch of independent streams.
@@ -390,7 +421,9 @@ class FsmnStreamBatch(WindowStreamBatch):
     (DESIGN.md "Stream batches"; its first S*4*128*19 floats are the FIR caches [S,4,128,19], then the headers, then the carries); nothing
     crosses to the host per window.  Per stream, the flags of successive ticks followed by the last tick's tail are bit for bit
     `FsmnEngine.flags` over the concatenated audio.  On "h2" every tick reads the range flag and, when it is raised, recomputes the tick
-    on "split" from the same record into the same record.
+    on "split" from the same record into the same record.  `step_ragged` is the tick in which every stream advances by its own number of
+    windows (vadx_fsmn_stream_windows_ragged + vadx_fsmn_stream_run_ragged; 0 = no audio, which costs nothing); the record is the same, so
+    the two forms interchange tick by tick.
 
     A stream's audio must end on the window grid: padding the end of a stream with noise is the caller's job (`pad_to_window_grid`), as
     it is for `flags`."""
@@ -480,3 +513,89 @@ class FsmnStreamBatch(WindowStreamBatch):
         self._end(act)
         self.noise_trace = trace
         return flags, tail
+
+    def _ragged_samples(self, samples, counts, reset, max_windows):
+        """The samples and counts of a ragged tick -> (x int16 [S, n] tensor where it is, counts int32 [S]).  A list of S 1-D host arrays
+        gives its own counts: the lengths must be what samples_needed_ragged gives for some count."""
+        S = self.streams
+        if isinstance(samples, (list, tuple)):
+            if len(samples) != S:
+                raise ValueError(f"samples lists {len(samples)} arrays for {S} streams")
+            rows = [np.asarray(r).reshape(-1) for r in samples]
+            for s, r in enumerate(rows):
+                if r.dtype != np.int16:
+                    raise ValueError(f"samples[{s}] must be int16, got {r.dtype}")
+            got = self._counts_of_lengths([r.shape[0] for r in rows], reset)
+            if counts is not None and not np.array_equal(np.asarray(counts).reshape(-1), got):
+                raise ValueError("counts disagree with the lengths of the listed samples")
+            counts = _ragged.stream_counts(got, S, max_windows)
+            x = np.zeros((S, max(max(r.shape[0] for r in rows), 8)), dtype=np.int16)
+            for s, r in enumerate(rows):
+                x[s, :r.shape[0]] = r
+        else:
+            if counts is None:
+                raise ValueError("step_ragged needs counts with a [S, n] array")
+            counts = _ragged.stream_counts(counts, S, max_windows)
+            x = samples
+        return self._samples(x), counts
+
+    def step_ragged(self, samples, counts=None, reset=None, max_windows=None):
+        """A tick in which stream s advances by counts[s] windows, 0 <= counts[s] <= max_windows (None = the cap of 256 a ragged tick
+        has, vadx_fsmn_stream_ragged_max_windows): the work is sum(counts) windows.  samples: int16 [S, >=
+        samples_needed_ragged(counts, reset).max()] (host or device, numpy or torch), row s holding that stream's new samples from
+        column 0 -- or a list of S 1-D host arrays whose lengths ARE what samples_needed_ragged gives for some count (the counts then
+        come from the lengths).  -> (flags u8 [sum(counts), T - lb] on the device: stream s owns rows first[s] .. first[s + 1] - 1;
+        tail u8 [S, lb]: what the plain rule would append if the stream ended with ITS last window of this tick, 255 for a stream
+        without audio; first: host int64 [S + 1]).  self.noise_trace becomes float32 [sum(counts)].  A stream with count 0 costs
+        nothing: it keeps its record and its pending reset, and a reset request for it is ignored.  A tick whose counts are all 0
+        launches nothing and leaves the current record where it is.  Bad counts raise ValueError before anything is launched.  `step`
+        and `step_ragged` interchange tick by tick (one record); `step` stays the path for uniform ticks."""
+        eng, t = self.engine, self.engine.torch
+        S, L = self.streams, self.engine.L
+        x, counts = self._ragged_samples(samples, counts, reset, max_windows)
+        first, win_stream, order = _ragged.window_stream_plan(counts, max_windows)
+        n = int(first[-1])
+        if n == 0:                   # nobody delivered audio: no launch; the record, the pending resets and the trace's meaning stay
+            self.noise_trace = t.empty(0, dtype=t.float32, device=eng.device)
+            tail = t.from_numpy(np.full((S, self.lb), 255, dtype=np.uint8)).to(eng.device)
+            return t.empty((0, self.slide), dtype=t.uint8, device=eng.device), tail, first
+        need = int(self.samples_needed_ragged(counts, reset).max())
+        if x.shape[1] < need:
+            raise ValueError(f"samples rows hold {x.shape[1]} samples, this tick needs {need} (samples_needed_ragged)")
+        act = counts > 0
+        _, _, reset_d, _, src, dst = self._begin(reset, act, upload_active=False)
+        x = x.to(eng.device)
+        if x.shape[1] < 8 or x.stride(1) != 1 or (S > 1 and x.stride(0) % 8) or x.data_ptr() % 16:
+            pad = t.zeros((S, (x.shape[1] + 7) // 8 * 8 + 8), dtype=t.int16, device=eng.device)      # 16-byte rows for the window kernel
+            pad[:, :x.shape[1]] = x
+            x = pad
+        row = int(x.stride(0)) if S > 1 else int(x.shape[1]) // 8 * 8
+        mw = int(counts.max())
+        # the tick's tables in ONE copy: counts | win_first | order | win_stream | status (a zero the copy writes)
+        tab = t.from_numpy(np.concatenate([counts, first.astype(np.int32), order, win_stream, np.zeros(1, np.int32)]).astype(np.int32)).to(eng.device)
+        p_counts = tab.data_ptr()
+        p_first, p_order, p_wst = p_counts + 4 * S, p_counts + 4 * (2 * S + 1), p_counts + 4 * (3 * S + 1)
+        p_status = p_wst + 4 * n
+        if self._wbuf is None or self._wbuf.numel() < n * L:
+            self._wbuf = t.empty(max(n, S) * L, dtype=t.int16, device=eng.device)
+        wbuf = self._wbuf[:n * L].view(n, L)
+        Lb = _lib.lib()
+        rst = None if reset_d is None else reset_d.data_ptr()
+        with t.cuda.device(eng.device):
+            _lib.check(Lb.vadx_fsmn_stream_windows_ragged(x.data_ptr(), row, S, n, mw, L, self.lb, p_counts, p_first, p_wst, rst,
+                                                          src.data_ptr(), dst.data_ptr(), wbuf.data_ptr(), p_status, _lib.stream_ptr()))
+        logmel, db = eng.features(wbuf, 1, L)
+        flags = t.empty((n, self.slide), dtype=t.uint8, device=eng.device)
+        tail = t.empty((S, self.lb), dtype=t.uint8, device=eng.device)
+        trace = t.empty((n,), dtype=t.float32, device=eng.device)
+
+        def launch(mode, dims, packed):
+            with t.cuda.device(eng.device):
+                _lib.check(Lb.vadx_fsmn_stream_run_ragged(C.byref(dims), packed.data_ptr(), logmel.data_ptr(), db.data_ptr(), S, n, mw,
+                                                          C.byref(self._lp), p_counts, p_first, p_order, rst, src.data_ptr(), dst.data_ptr(),
+                                                          flags.data_ptr(), tail.data_ptr() if self.lb else None, trace.data_ptr(),
+                                                          p_status, _lib.stream_ptr()))
+        eng.blobs.guarded(launch)
+        self._end(act)
+        self.noise_trace = trace
+        return flags, tail, first

@@ -645,6 +645,27 @@ def stream_counts(counts, streams, max_windows=None):
     return c.astype(np.int32)
 
 
+def window_stream_plan(counts, max_windows=None):
+    """The host tables of a ragged tick of window streams (FSMN: vadx_fsmn_stream_windows_ragged / vadx_fsmn_stream_run_ragged), made
+    with a cumsum, a repeat and a counting sort over np.bincount of the counts -- no comparison sort.  counts: int [S], 0 <= n_s <=
+    max_windows (None = the cap).  -> (first int64 [S + 1] = prefix sum, win_stream int32 [sum n] = the stream of each window row,
+    order int32 [S] = np.argsort(-counts, kind="stable"): streams with audio by count descending, idle streams last in index order)."""
+    c = np.asarray(counts)
+    c = stream_counts(c, c.shape[0] if c.ndim == 1 else -1, max_windows)
+    S = int(c.shape[0])
+    first = np.zeros(S + 1, dtype=np.int64)
+    np.cumsum(c, out=first[1:])
+    idx = np.arange(S, dtype=np.int32)
+    win_stream = np.repeat(idx, c)
+    hist = np.bincount(c)
+    order = np.empty(S, dtype=np.int32)
+    at = 0
+    for v in np.flatnonzero(hist)[::-1].tolist():        # one bucket per count that occurs, largest first; a bucket keeps index order
+        order[at:at + int(hist[v])] = idx[c == v]
+        at += int(hist[v])
+    return first, win_stream, order
+
+
 class StreamPlan:
     """The host half of a ragged tick's tables (see stream_plan)."""
 

@@ -121,6 +121,29 @@ class WindowStreamBatch(StreamBatch):
         fresh = ~self._primed | self._pending | (False if reset is None else self._mask(reset, "reset"))
         return np.where(fresh, self.engine.L + (k - 1) * self.stride, k * self.stride).astype(np.int64)
 
+    def samples_needed_ragged(self, counts, reset=None):
+        """int64 [S]: new samples each stream consumes in the next RAGGED tick of counts[s] windows: 0 for a count of 0, n * stride with
+        a carry, L + (n - 1) * stride without one.  A pending or requested reset makes a stream one without a carry only when its count
+        is above 0 (a stream without audio keeps its record and its pending reset)."""
+        from . import ragged
+        c = ragged.stream_counts(counts, self.streams).astype(np.int64)
+        fresh = ~self._primed | self._pending | (False if reset is None else self._mask(reset, "reset"))
+        return np.where(c == 0, 0, np.where(fresh, self.engine.L + (c - 1) * self.stride, c * self.stride)).astype(np.int64)
+
+    def _counts_of_lengths(self, lengths, reset=None):
+        """The counts for which samples_needed_ragged gives `lengths` (new samples per stream), or ValueError naming the first stream
+        whose length is off its grid."""
+        n = np.asarray(lengths, dtype=np.int64)
+        fresh = ~self._primed | self._pending | (False if reset is None else self._mask(reset, "reset"))
+        L, st = self.engine.L, self.stride
+        c = np.where(n == 0, 0, np.where(fresh, (n - L) // st + 1, n // st))
+        ok = (n == 0) | np.where(fresh, (n >= L) & ((n - L) % st == 0), n % st == 0)
+        if not ok.all():
+            s = int(np.flatnonzero(~ok)[0])
+            want = f"{L} + m * {st} (no carry yet, or a reset)" if fresh[s] else f"a multiple of {st}"
+            raise ValueError(f"samples[{s}] holds {int(n[s])} samples: stream {s} takes 0 or {want} (samples_needed_ragged)")
+        return c.astype(np.int64)
+
     def _end(self, act):
         super()._end(act)
         self._primed |= act
