@@ -67,7 +67,8 @@ extern "C" {
  *     (and two relaxations: vadx_silero_segments_ragged takes sampling_rate 8000, a vadx_silero_ragged may describe a run of groups); then
  *     ragged ticks of the Silero streams: vadx_silero_stream_ragged_max_windows, vadx_silero_stream_plan_bytes,
  *     vadx_silero_stream_ragged_workspace_bytes, vadx_silero_stream_plan, vadx_silero_stream_run_ragged; then ragged ticks of the FSMN
- *     streams: vadx_fsmn_stream_ragged_max_windows, vadx_fsmn_stream_windows_ragged, vadx_fsmn_stream_run_ragged.
+ *     streams: vadx_fsmn_stream_ragged_max_windows, vadx_fsmn_stream_windows_ragged, vadx_fsmn_stream_run_ragged; then ragged ticks of the FireRed
+ *     streams: vadx_firered_stream_tick_ragged.
  *     A caller that needs them checks for the symbols (dlsym), not for a number. */
 #define VADX_ABI_VERSION 10
 
@@ -845,6 +846,38 @@ int vadx_firered_stream_tick(const vadx_firered_cfg *cfg, const float *packed, c
                              const vadx_stream_vadpost_params *post, const uint8_t *reset, const uint8_t *active,
                              const void *state_in, void *state_out, float *probs, int32_t *segments, int32_t *counts, int cap,
                              int32_t *open_start, void *stream);
+
+/* A RAGGED tick of the same streams on the same record: stream s advances by counts[s] chunks of cfg->frames frames, 0 <= counts[s] <=
+ * vadx_firered_stream_group_max(cfg->frames) = 112 / frames, and the work is sum(counts) chunks in ONE launch.  The record is the
+ * unchanged one of vadx_firered_stream_tick, so the two calls interchange tick by tick.  All tables are int32 on the device:
+ *   counts [S], row_first [S]: stream s owns the log-mel rows row_first[s] .. row_first[s] + counts[s] - 1 of
+ *     logmel f32 [n_rows][frames][80] (vadx_frontend_logmel over n_rows rows of ONE chunk each) and the columns
+ *     row_first[s] * frames .. (row_first[s] + counts[s]) * frames - 1 of every row of probs f32 [odim][n_rows * frames];
+ *   slot_stream [wg_first[n_wg]] (at most S entries) and wg_first [n_wg + 1]: workgroup w lays the streams
+ *     slot_stream[wg_first[w] .. wg_first[w + 1]) side by side, slot j with counts[s_j] * frames LDS columns behind those of the slots before
+ *     it; a workgroup holds at most 112 columns.  Every stream with a count above 0 must be named in exactly one slot: a stream named twice,
+ *     or one with audio named nowhere (its bytes of state_out are then not written), is the caller's fault and is not checked.
+ * segments [S][cap][2], counts_out [S] and open_start [S] are indexed by stream and mean what they mean in vadx_firered_stream_tick.
+ * A stream with count 0 owns no log-mel row and no probability column: its record in state_out is a bitwise copy of state_in's, a reset
+ * request for it is ignored, its counts_out is 0 and its open_start -1 (workgroups behind the n_wg compute ones do this).
+ * Tables that lie: a slot is SKIPPED -- no columns, no record write, no decision -- and bit 1 (value 2) of *status is raised when its
+ * stream index is outside [0, S), its count outside [0, 112 / frames], its rows outside [0, n_rows), or its columns would pass 112 (then
+ * every slot behind it in the workgroup is skipped too), and a workgroup whose wg_first entries are negative, decreasing, more than 112
+ * apart or above S is skipped whole.  A stream whose count or rows lie is treated as one without audio.  Nothing is indexed out of
+ * bounds.  *status (uint32, device) is only ever OR-ed into: the caller zeroes it.
+ * All three arithmetics and the range protocol of vadx_firered_stream_tick: after an F16X2 tick that raised vadx_firered_range_flag,
+ * call again with the BF16X3 cfg and blob, the same state_in and the same tables; every byte the first call wrote is written again.
+ * Every output of a stream and its bytes of state_out are bitwise what vadx_firered_stream_tick gives that stream with chunks =
+ * counts[s], whatever the plan.
+ * Returns VADX_EINVAL, before any HIP call and naming the argument, for a NULL pointer (reset may be NULL), streams / n_rows / n_wg /
+ * cap < 1, frames > 112, N2 != 0, smooth_window_size > 16, overlapping or misaligned records.
+ * Replaces the body of the chunk loop, FireRedVAD/Inference_FireRed_ONNX.py:788-822, for S streams that deliver different numbers of
+ * chunks per tick. */
+int vadx_firered_stream_tick_ragged(const vadx_firered_cfg *cfg, const float *packed, const float *logmel, int streams, int n_rows,
+                                    const int32_t *counts, const int32_t *row_first, const int32_t *slot_stream, const int32_t *wg_first,
+                                    int n_wg, const vadx_stream_vadpost_params *post, const uint8_t *reset, const void *state_in,
+                                    void *state_out, float *probs, int32_t *segments, int32_t *counts_out, int cap, int32_t *open_start,
+                                    uint32_t *status, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * MarbleNet building blocks: one fused launch per Jasper sub-block

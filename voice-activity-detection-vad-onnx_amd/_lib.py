@@ -253,6 +253,8 @@ SIGNATURES = {
     "vadx_firered_stream_group_max": (_I, [_I]),
     "vadx_firered_stream_tick": (_I, [C.POINTER(FireRedCfg), _P, _P, _I, _I, _I, C.POINTER(StreamVadPostParams), _P, _P, _P, _P, _P, _P, _P, _I,
                                       _P, _P]),
+    "vadx_firered_stream_tick_ragged": (_I, [C.POINTER(FireRedCfg), _P, _P, _I, _I, _P, _P, _P, _P, _I, C.POINTER(StreamVadPostParams), _P, _P, _P,
+                                             _P, _P, _P, _I, _P, _P, _P]),
     "vadx_vadpost_workspace_bytes": (_Z, [_I, _I]),
     "vadx_vadpost": (_I, [C.POINTER(VadPostParams), _P, _I, _P, _I, _P, _P, _P, _I, _P, _Z, _P]),
     "vadx_sepconv_block": (_I, [C.POINTER(SepConvCfg), _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _I, _I, _P, C.POINTER(MarbleNetCfg)]),

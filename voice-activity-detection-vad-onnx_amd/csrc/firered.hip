@@ -245,8 +245,9 @@ __device__ __forceinline__ void load_pair_resident(PairResident<KB1> &R, const f
     R.bias2 = (HAS2 && b2) ? ldg1(b2 + wave * 16 + i) : 0.f;
 }
 
-template <int KB1>
-__device__ __forceinline__ void pointwise_pair_resident(const Dev &d, const float *W1, const float *b1, const float *src,
+// (DV: a Dev, or the ragged tick's TickDims -- the point-wise pairs read T, Hp and Pp of it)
+template <int KB1, typename DV>
+__device__ __forceinline__ void pointwise_pair_resident(const DV &d, const float *W1, const float *b1, const float *src,
                                                         const float *W2, const float *b2, bool relu2, float *dst, float *h) {
     PairResident<KB1> R;
     load_pair_resident<KB1, true>(R, W1, b1, W2, b2);
@@ -288,8 +289,8 @@ __device__ __forceinline__ void load_pair_split(PairSplit<SC, KC1> &R, const flo
     R.bias2 = b2 ? ldg1(b2 + wave * 16 + i) : 0.f;
 }
 
-template <typename SC, int KC1>
-__device__ __forceinline__ void pointwise_pair_split(const Dev &d, const float *Q1, const float *b1, int ksrc, const float *src,
+template <typename SC, int KC1, typename DV>
+__device__ __forceinline__ void pointwise_pair_split(const DV &d, const float *Q1, const float *b1, int ksrc, const float *src,
                                                      const float *Q2, const float *b2, bool relu2, float *dst, float *hbuf, float &amax) {
     constexpr int NP = SC::NP;
     typedef typename SC::frag frag;
@@ -376,7 +377,8 @@ __device__ __forceinline__ void pointwise_pair_split(const Dev &d, const float *
     }
 }
 
-__device__ __forceinline__ void pointwise_pair(const Dev &d, const float *W1, const float *b1, int k1b, const float *src,
+template <typename DV>
+__device__ __forceinline__ void pointwise_pair(const DV &d, const float *W1, const float *b1, int k1b, const float *src,
                                                const float *W2, const float *b2, int relu2, float *dst, float *h) {
     if (W2 && d.Hp == 256 && d.Pp == 128 && blockDim.x == 512) {
         if (k1b == 8) { pointwise_pair_resident<8>(d, W1, b1, src, W2, b2, relu2 != 0, dst, h); return; }      // DFSMN block
@@ -943,6 +945,9 @@ constexpr int TK_HDR = 32;               // header words per stream: [0,26) as t
 constexpr int TK_DONE = 28;
 constexpr int TK_LDS_FLOATS = LDS_FLOATS + 2 * MAX_T;        // + slot status [MAX_T] (int) + channel-0 probabilities [MAX_T]
 
+constexpr int TKR_TABLES = 5;            // ragged tick, per slot: first column, columns, stream, (log-mel row = probability column) - column; per column: slot
+constexpr int TKR_LDS_FLOATS = TK_LDS_FLOATS + TKR_TABLES * MAX_T + 4;      // + the workgroup's column count
+
 struct TickArgs {
     const float *logmel;
     const unsigned char *reset, *active;
@@ -954,17 +959,55 @@ struct TickArgs {
     StreamPostDev q;
 };
 
+// The tables of a ragged tick (vadx_firered_stream_tick_ragged), all on the device; the rectangular instantiation takes the empty twin.
+struct TickNoTabs {};
+struct TickTabs {
+    const int *counts, *row_first, *slot_stream, *wg_first;
+    unsigned *status;
+    int n_wg, n_rows, frames;
+};
+template <bool RG> struct TickTabsFor { typedef TickNoTabs type; };
+template <> struct TickTabsFor<true> { typedef TickTabs type; };
+
+// the workgroup-local Dev of a ragged tick: what the point-wise pairs read of a Dev, T = this workgroup's columns (a whole modified copy
+// of the kernel's Dev would live in scratch, 656 bytes a lane: its offset tables are indexed by the block)
+struct TickDims { int T, Hp, Pp; };
+template <bool RG> struct TickDimsFor { typedef TickNoTabs type; };
+template <> struct TickDimsFor<true> { typedef TickDims type; };
+__device__ __forceinline__ const Dev &tick_dims(const Dev &d, const TickNoTabs &) { return d; }          // what the point-wise pairs of a tick read
+__device__ __forceinline__ const TickDims &tick_dims(const Dev &, const TickDims &dl) { return dl; }
+
+// A ragged workgroup's column map in LDS: slot j holds stream ss[j] in the fj[j] columns from c0[j]; column c belongs to slot cs[c] and is
+// log-mel row / probability column lm[slot] + c.  Empty in the rectangular instantiation, where slot j = columns [j * F, (j + 1) * F) of
+// stream g0 + j.
+struct TickNoMap {};
+struct TickMap { const int *c0, *fj, *ss, *lm, *cs; };
+template <bool RG> struct TickMapFor { typedef TickNoMap type; };
+template <> struct TickMapFor<true> { typedef TickMap type; };
+
+// a stream's count as the ragged tick takes it: -1 when the tables lie about it (count outside [0, 112 / frames], rows outside [0, n_rows))
+__device__ __forceinline__ int tick_ragged_count(const TickTabs &rt, int s) {
+    const int n = rt.counts[s];
+    const long long r0 = rt.row_first[s];
+    return n < 0 || n > MAX_T / rt.frames || r0 < 0 || r0 + n > rt.n_rows ? -1 : n;
+}
+
 // fsmn_memory_stream for the columns of `group` streams: same operations in the same order per (channel, frame); slot status 0 = no audio
 // (the columns stay zero), 1 = live, 2 = live from the reset state (zero cache)
-__device__ __forceinline__ void fsmn_memory_tick(const Dev &d, const float *__restrict__ Pk, int r, bool skip, const float *p, float *mem,
-                                                 const TickArgs &a, int g0, const int *slot) {
-    const int pad = (d.N1 - 1) * d.S1, C = d.T, F = a.F;
+template <bool RG>
+__device__ __forceinline__ void fsmn_memory_tick(const Dev &d, int C, const float *__restrict__ Pk, int r, bool skip, const float *p, float *mem,
+                                                 const TickArgs &a, int g0, const int *slot, const typename TickMapFor<RG>::type &m) {
+    const int pad = (d.N1 - 1) * d.S1;              // C = the workgroup's columns
     const float *cin = reinterpret_cast<const float *>(a.cin);
     float *cout = reinterpret_cast<float *>(a.cout);
     for (int e = threadIdx.x; e < d.P * C; e += THREADS) {
-        const int ch = e / C, c = e - ch * C, j = c / F, t = c - j * F, st = slot[j];
+        const int ch = e / C, c = e - ch * C;
+        int j, cb, s;                                      // the column's slot, that slot's first column and its stream
+        if constexpr (RG) { j = m.cs[c]; cb = m.c0[j]; s = m.ss[j]; }
+        else { j = c / a.F; cb = j * a.F; s = g0 + j; }
+        const int t = c - cb, st = slot[j];
         if (st == 0) continue;
-        const float *row = p + ch * M_LD + j * F, *crow = cin + (size_t)(g0 + j) * a.NC + ((size_t)r * d.P + ch) * pad, *w = Pk + d.off_lb[r] + ch * d.N1;
+        const float *row = p + ch * M_LD + cb, *crow = cin + (size_t)s * a.NC + ((size_t)r * d.P + ch) * pad, *w = Pk + d.off_lb[r] + ch * d.N1;
         float lb = 0.f;
         for (int k = 0; k < d.N1; ++k) {
             const int i = t + k * d.S1;                       // index into cache ++ p
@@ -976,16 +1019,20 @@ __device__ __forceinline__ void fsmn_memory_tick(const Dev &d, const float *__re
     }
     const int per = d.P * pad;
     for (int e = threadIdx.x; e < a.group * per; e += THREADS) {      // new cache = last `pad` entries of cache ++ p
-        const int j = e / per, x = e - j * per, ch = x / pad, i = x - ch * pad, src = F + i, st = slot[j];
+        const int j = e / per, x = e - j * per, ch = x / pad, i = x - ch * pad, st = slot[j];
         if (st == 0) continue;
-        const size_t at = (size_t)(g0 + j) * a.NC + (size_t)r * per + x;
-        cout[at] = src < pad ? (st == 2 ? 0.f : cin[at - i + src]) : p[ch * M_LD + j * F + src - pad];
+        int F, cb, s;
+        if constexpr (RG) { F = m.fj[j]; cb = m.c0[j]; s = m.ss[j]; }
+        else { F = a.F; cb = j * a.F; s = g0 + j; }
+        const int src = F + i;
+        const size_t at = (size_t)s * a.NC + (size_t)r * per + x;
+        cout[at] = src < pad ? (st == 2 ? 0.f : cin[at - i + src]) : p[ch * M_LD + cb + src - pad];
     }
 }
 
 // One stream's decisions over its F new probabilities: stream_vadpost_kernel's per-frame loop (flush = 0), operation for operation, on the
-// tick record's header.
-__device__ __forceinline__ void tick_decide(const TickArgs &a, int s, bool fresh, const float *pr) {
+// tick record's header.  F is the stream's own frame count this tick (a.F in a rectangular one).
+__device__ __forceinline__ void tick_decide(const TickArgs &a, int s, bool fresh, const float *pr, int F) {
     const StreamPostDev &q = a.q;
     const unsigned *hi = a.hin + (size_t)s * TK_HDR;
     unsigned *ho = a.hout + (size_t)s * TK_HDR;
@@ -1002,7 +1049,7 @@ __device__ __forceinline__ void tick_decide(const TickArgs &a, int s, bool fresh
     }
     int *out = a.segs + (size_t)s * a.cap * 2, n = 0;
     auto emit = [&](int x, int y) { if (n < a.cap) { out[2 * n] = x; out[2 * n + 1] = y; } ++n; };
-    for (int t = 0; t < a.F; ++t) {
+    for (int t = 0; t < F; ++t) {
         const float p = pr[t];
         ++fc;
         float sm = p;
@@ -1046,7 +1093,7 @@ __device__ __forceinline__ void tick_decide(const TickArgs &a, int s, bool fresh
         }
         if (ended && e0 > 0) emit(e0 - 1 > 0 ? e0 - 1 : 0, e1 - 1 > 0 ? e1 - 1 : 0);
     }
-    done += a.F;
+    done += F;
     a.counts[s] = n;
     a.open_start[s] = last_start > 0 ? last_start - 1 : -1;      // what the end-of-input rule would report, without closing it
 #pragma unroll
@@ -1057,70 +1104,138 @@ __device__ __forceinline__ void tick_decide(const TickArgs &a, int s, bool fresh
     ho[30] = 0; ho[31] = 0;
 }
 
-template <int AR>
-__global__ __launch_bounds__(THREADS, 2) void firered_stream_tick_kernel(Dev d, const float *__restrict__ Pk, TickArgs a) {
+// RG = a ragged tick: workgroup w < rt.n_wg serves the streams slot_stream[wg_first[w] .. wg_first[w + 1]), slot j with counts[s_j] *
+// frames columns behind those of the slots before it; workgroup rt.n_wg + s copies the record of stream s when it has no audio.
+template <int AR, bool RG>
+__global__ __launch_bounds__(THREADS, 2) void firered_stream_tick_kernel(Dev d, const float *__restrict__ Pk, TickArgs a,
+                                                                         typename TickTabsFor<RG>::type rt) {
     constexpr bool SPLIT = AR != vadx::VADX_AR_F32;
     typedef typename vadx::SchemeFor<AR>::type SC;
     float amax = 0.f;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *mem = lds, *p = lds + MEM_F, *h = p + P_F, *pr0 = h + H_F + MAX_T;
     int *slot = reinterpret_cast<int *>(h + H_F);
-    const int tid = threadIdx.x, g0 = blockIdx.x * a.group, C = d.T, F = a.F;      // d.T = group * F columns
-    if (tid < a.group) {
-        const int s = g0 + tid;
-        const bool live = s < a.S && (!a.active || a.active[s]);
-        slot[tid] = !live ? 0 : (a.reset && a.reset[s]) ? 2 : 1;
+    typename TickMapFor<RG>::type m;
+    typename TickDimsFor<RG>::type dl;           // RG: the point-wise helpers' Dev, with this workgroup's own column count
+    const int tid = threadIdx.x, F = a.F;
+    int g0 = blockIdx.x * a.group, C = d.T;      // d.T = group * F columns
+    if constexpr (RG) {
+        int *tab = reinterpret_cast<int *>(pr0 + MAX_T);
+        int *c0 = tab, *fj = tab + MAX_T, *ss = tab + 2 * MAX_T, *lmb = tab + 3 * MAX_T, *cs = tab + 4 * MAX_T, *cw = tab + TKR_TABLES * MAX_T;
+        m = TickMap{c0, fj, ss, lmb, cs};
+        const int w = blockIdx.x;
+        if (w >= rt.n_wg) {
+            // a stream without audio (count 0, or a count / rows the tables lie about): the record bit for bit, no segment
+            const int s = w - rt.n_wg, n = tick_ragged_count(rt, s);
+            if (n < 0 && tid == 0) atomicOr(rt.status, 2u);
+            if (n > 0) return;
+            for (int e = tid; e < a.NC; e += THREADS) { const size_t at = (size_t)s * a.NC + e; a.cout[at] = a.cin[at]; }
+            if (tid < TK_HDR) a.hout[(size_t)s * TK_HDR + tid] = a.hin[(size_t)s * TK_HDR + tid];
+            if (tid == 0) { a.counts[s] = 0; a.open_start[s] = -1; }
+            return;
+        }
+        const int j0 = rt.wg_first[w], j1 = rt.wg_first[w + 1], ns = j1 - j0;      // uniform loads
+        if (j0 < 0 || ns < 0 || ns > MAX_T || j1 > a.S) {                         // (slot_stream names a stream at most once: <= S entries)
+            if (tid == 0) atomicOr(rt.status, 2u);
+            return;
+        }
+        if (tid < MAX_T) {
+            int s = -1, n = 0;
+            if (tid < ns) {
+                s = rt.slot_stream[j0 + tid];
+                n = s < 0 || s >= a.S ? -1 : tick_ragged_count(rt, s);
+                if (n < 0) { atomicOr(rt.status, 2u); n = 0; }
+            }
+            fj[tid] = n * rt.frames;
+            ss[tid] = s;
+        }
+        if (tid == 0) *cw = 0;
+        __syncthreads();
+        if (tid < ns) {
+            int c = 0;
+            for (int i = 0; i < tid; ++i) c += fj[i];
+            const int f = fj[tid], s = ss[tid];
+            const bool live = f > 0 && c + f <= MAX_T;          // columns past 112: this slot is skipped, and so is every one behind it
+            if (f > 0 && !live) atomicOr(rt.status, 2u);
+            slot[tid] = !live ? 0 : (a.reset && a.reset[s]) ? 2 : 1;
+            c0[tid] = c;
+            if (live) {
+                lmb[tid] = rt.row_first[s] * rt.frames - c;
+                for (int i = 0; i < f; ++i) cs[c + i] = tid;
+                atomicMax(cw, c + f);
+            }
+        }
+        __syncthreads();
+        C = __builtin_amdgcn_readfirstlane(*cw);
+        if (C == 0) return;
+        dl.Hp = d.Hp; dl.Pp = d.Pp;
+        dl.T = C;                                                // the helpers' column count: this workgroup's own, wave-uniform
+        a.group = ns;                                            // its slots
+        g0 = 0;
+    } else {
+        if (tid < a.group) {
+            const int s = g0 + tid;
+            const bool live = s < a.S && (!a.active || a.active[s]);
+            slot[tid] = !live ? 0 : (a.reset && a.reset[s]) ? 2 : 1;
+        }
+        __syncthreads();
+        // streams without audio: the record bit for bit, NaN probabilities, no segment
+        bool any = false;
+        for (int j = 0; j < a.group; ++j) any |= slot[j] != 0;
+        for (int e = tid; e < a.group * a.NC; e += THREADS) {
+            const int j = e / a.NC;
+            if (g0 + j < a.S && slot[j] == 0) { const size_t at = (size_t)g0 * a.NC + e; a.cout[at] = a.cin[at]; }
+        }
+        for (int e = tid; e < a.group * d.odim * F; e += THREADS) {
+            const int j = e / (d.odim * F);
+            if (g0 + j < a.S && slot[j] == 0) a.probs[(size_t)g0 * d.odim * F + e] = __uint_as_float(0x7fc00000u);
+        }
+        if (tid < a.group && g0 + tid < a.S && slot[tid] == 0) {
+            const size_t at = (size_t)(g0 + tid) * TK_HDR;
+            for (int k = 0; k < TK_HDR; ++k) a.hout[at + k] = a.hin[at + k];
+            a.counts[g0 + tid] = 0;
+            a.open_start[g0 + tid] = -1;
+        }
+        if (!any) return;
     }
-    __syncthreads();
-    // streams without audio: the record bit for bit, NaN probabilities, no segment
-    bool any = false;
-    for (int j = 0; j < a.group; ++j) any |= slot[j] != 0;
-    for (int e = tid; e < a.group * a.NC; e += THREADS) {
-        const int j = e / a.NC;
-        if (g0 + j < a.S && slot[j] == 0) { const size_t at = (size_t)g0 * a.NC + e; a.cout[at] = a.cin[at]; }
-    }
-    for (int e = tid; e < a.group * d.odim * F; e += THREADS) {
-        const int j = e / (d.odim * F);
-        if (g0 + j < a.S && slot[j] == 0) a.probs[(size_t)g0 * d.odim * F + e] = __uint_as_float(0x7fc00000u);
-    }
-    if (tid < a.group && g0 + tid < a.S && slot[tid] == 0) {
-        const size_t at = (size_t)(g0 + tid) * TK_HDR;
-        for (int k = 0; k < TK_HDR; ++k) a.hout[at + k] = a.hin[at + k];
-        a.counts[g0 + tid] = 0;
-        a.open_start[g0 + tid] = -1;
-    }
-    if (!any) return;
+    const auto &dh = tick_dims(d, dl);
     // stage log-mel channel-first into `mem` rows 0..79, the streams' chunks side by side; columns without audio and >= C are zero
-    const float *lm = a.logmel + (size_t)g0 * F * NMEL;
     for (int e = tid; e < MAX_T * NMEL; e += THREADS) {
         const int c = e / NMEL, mel = e - c * NMEL;
         float v = 0.f;
-        if (c < C && slot[c / F] != 0) v = lm[(size_t)c * NMEL + mel];
+        if constexpr (RG) { if (c < C) v = a.logmel[(size_t)(m.lm[m.cs[c]] + c) * NMEL + mel]; }      // every column below C is a live slot's
+        else if (c < C && slot[c / F] != 0) v = a.logmel[((size_t)g0 * F + c) * NMEL + mel];
         mem[mel * M_LD + c] = v;
     }
     for (int e = tid; e < MAXP * M_LD; e += THREADS) p[e] = 0.f;
     __syncthreads();
-    if (SPLIT) pointwise_pair_split<SC, 3>(d, Pk + d.q_fc1, Pk + d.off_fc1b, NMEL, mem, Pk + d.q_fc2, Pk + d.off_fc2b, true, p, h, amax);
-    else pointwise_pair(d, Pk + d.off_fc1, Pk + d.off_fc1b, NMEL / 16, mem, Pk + d.off_fc2, Pk + d.off_fc2b, 1, p, h);
+    if (SPLIT) pointwise_pair_split<SC, 3>(dh, Pk + d.q_fc1, Pk + d.off_fc1b, NMEL, mem, Pk + d.q_fc2, Pk + d.off_fc2b, true, p, h, amax);
+    else pointwise_pair(dh, Pk + d.off_fc1, Pk + d.off_fc1b, NMEL / 16, mem, Pk + d.off_fc2, Pk + d.off_fc2b, 1, p, h);
     for (int e = tid; e < MAXP * M_LD; e += THREADS) mem[e] = 0.f;
     __syncthreads();
-    fsmn_memory_tick(d, Pk, 0, false, p, mem, a, g0, slot);
+    fsmn_memory_tick<RG>(d, C, Pk, 0, false, p, mem, a, g0, slot, m);
     __syncthreads();
     for (int r = 1; r < d.R; ++r) {
-        if (SPLIT) pointwise_pair_split<SC, 4>(d, Pk + d.q_bfc1[r], Pk + d.off_bfc1b[r], d.Pp, mem, Pk + d.q_bfc2[r], nullptr, false, p, h, amax);
-        else pointwise_pair(d, Pk + d.off_bfc1[r], Pk + d.off_bfc1b[r], d.Pp / 16, mem, Pk + d.off_bfc2[r], nullptr, 0, p, h);
-        fsmn_memory_tick(d, Pk, r, true, p, mem, a, g0, slot);
+        if (SPLIT) pointwise_pair_split<SC, 4>(dh, Pk + d.q_bfc1[r], Pk + d.off_bfc1b[r], d.Pp, mem, Pk + d.q_bfc2[r], nullptr, false, p, h, amax);
+        else pointwise_pair(dh, Pk + d.off_bfc1[r], Pk + d.off_bfc1b[r], d.Pp / 16, mem, Pk + d.off_bfc2[r], nullptr, 0, p, h);
+        fsmn_memory_tick<RG>(d, C, Pk, r, true, p, mem, a, g0, slot, m);
         __syncthreads();
     }
     auto put = [&](int o, int c, float z) {        // logit of output o at column c -> probs [S][odim][F], channel 0 also to the decision lanes
-        const int j = c / F;
-        if (slot[j] == 0) return;
-        const float v = sigmoidf_(z);
-        a.probs[((size_t)(g0 + j) * d.odim + o) * F + c - j * F] = v;
-        if (o == 0) pr0[c] = v;
+        if constexpr (RG) {                        // -> probs [odim][n_rows * frames]; every column below C is a live slot's
+            const float v = sigmoidf_(z);
+            a.probs[(size_t)o * rt.n_rows * rt.frames + m.lm[m.cs[c]] + c] = v;
+            if (o == 0) pr0[c] = v;
+        } else {
+            const int j = c / F;
+            if (slot[j] == 0) return;
+            const float v = sigmoidf_(z);
+            a.probs[((size_t)(g0 + j) * d.odim + o) * F + c - j * F] = v;
+            if (o == 0) pr0[c] = v;
+        }
     };
     if (SPLIT && d.M == 1) {          // as firered_kernel: dnn + output head as one more point-wise pair, logits in p[o][c]
-        pointwise_pair_split<SC, 4>(d, Pk + d.q_dnn0, Pk + d.off_dnnb[0], d.Pp, mem, Pk + d.q_head, Pk + d.off_headb, false, p, h, amax);
+        pointwise_pair_split<SC, 4>(dh, Pk + d.q_dnn0, Pk + d.off_dnnb[0], d.Pp, mem, Pk + d.q_head, Pk + d.off_headb, false, p, h, amax);
         __syncthreads();
         for (int e = tid; e < d.odim * C; e += THREADS) {
             const int o = e / C, c = e - o * C;
@@ -1152,7 +1267,10 @@ __global__ __launch_bounds__(THREADS, 2) void firered_stream_tick_kernel(Dev d, 
         }
     }
     __syncthreads();
-    if (tid < a.group && slot[tid] != 0) tick_decide(a, g0 + tid, slot[tid] == 2, pr0 + tid * F);
+    if (tid < a.group && slot[tid] != 0) {         // one lane per slot, over the stream's own frames
+        if constexpr (RG) tick_decide(a, m.ss[tid], slot[tid] == 2, pr0 + m.c0[tid], m.fj[tid]);
+        else tick_decide(a, g0 + tid, slot[tid] == 2, pr0 + tid * F, F);
+    }
     if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
 }
 }  // namespace firered
@@ -1214,15 +1332,81 @@ extern "C" int vadx_firered_stream_tick(const vadx_firered_cfg *cfg, const float
     d.T = a.group * a.F;                     // the kernel's columns: the group's streams side by side
     const unsigned grid = (unsigned)((streams + a.group - 1) / a.group);
     const size_t lds = TK_LDS_FLOATS * sizeof(float);
-    VADX_DYN_LDS(firered_stream_tick_kernel<0>, lds);
-    VADX_DYN_LDS(firered_stream_tick_kernel<1>, lds);
-    VADX_DYN_LDS(firered_stream_tick_kernel<2>, lds);
+    const TickNoTabs none;
+    VADX_DYN_LDS((firered_stream_tick_kernel<0, false>), lds);
+    VADX_DYN_LDS((firered_stream_tick_kernel<1, false>), lds);
+    VADX_DYN_LDS((firered_stream_tick_kernel<2, false>), lds);
     if (d.arith == vadx::VADX_AR_H2)
-        hipLaunchKernelGGL(firered_stream_tick_kernel<2>, dim3(grid), dim3(THREADS), lds, static_cast<hipStream_t>(stream), d, packed, a);
+        hipLaunchKernelGGL((firered_stream_tick_kernel<2, false>), dim3(grid), dim3(THREADS), lds, static_cast<hipStream_t>(stream), d, packed, a, none);
     else if (d.arith == vadx::VADX_AR_B3)
-        hipLaunchKernelGGL(firered_stream_tick_kernel<1>, dim3(grid), dim3(THREADS), lds, static_cast<hipStream_t>(stream), d, packed, a);
+        hipLaunchKernelGGL((firered_stream_tick_kernel<1, false>), dim3(grid), dim3(THREADS), lds, static_cast<hipStream_t>(stream), d, packed, a, none);
     else
-        hipLaunchKernelGGL(firered_stream_tick_kernel<0>, dim3(grid), dim3(THREADS), lds, static_cast<hipStream_t>(stream), d, packed, a);
+        hipLaunchKernelGGL((firered_stream_tick_kernel<0, false>), dim3(grid), dim3(THREADS), lds, static_cast<hipStream_t>(stream), d, packed, a, none);
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+// ---- ragged ticks: stream s advances by counts[s] chunks; every refusal names its argument and comes before any HIP call -------------------
+extern "C" int vadx_firered_stream_tick_ragged(const vadx_firered_cfg *cfg, const float *packed, const float *logmel, int streams, int n_rows,
+                                               const int32_t *counts, const int32_t *row_first, const int32_t *slot_stream,
+                                               const int32_t *wg_first, int n_wg, const vadx_stream_vadpost_params *post, const uint8_t *reset,
+                                               const void *state_in, void *state_out, float *probs, int32_t *segments, int32_t *counts_out,
+                                               int cap, int32_t *open_start, uint32_t *status, void *stream) {
+    const char *who = "vadx_firered_stream_tick_ragged";
+    Dev d;
+    VADX_REQUIRE(cfg, "%s: cfg is NULL", who);
+    VADX_REQUIRE(packed, "%s: packed is NULL", who);
+    VADX_REQUIRE(logmel, "%s: logmel is NULL", who);
+    VADX_REQUIRE(counts, "%s: counts is NULL", who);
+    VADX_REQUIRE(row_first, "%s: row_first is NULL", who);
+    VADX_REQUIRE(slot_stream, "%s: slot_stream is NULL", who);
+    VADX_REQUIRE(wg_first, "%s: wg_first is NULL", who);
+    VADX_REQUIRE(post, "%s: post is NULL", who);
+    VADX_REQUIRE(state_in, "%s: state_in is NULL", who);
+    VADX_REQUIRE(state_out, "%s: state_out is NULL", who);
+    VADX_REQUIRE(probs, "%s: probs is NULL", who);
+    VADX_REQUIRE(segments, "%s: segments is NULL", who);
+    VADX_REQUIRE(counts_out, "%s: counts_out is NULL", who);
+    VADX_REQUIRE(open_start, "%s: open_start is NULL", who);
+    VADX_REQUIRE(status, "%s: status is NULL", who);
+    VADX_REQUIRE(streams >= 1, "%s: streams=%d must be at least 1", who, streams);
+    VADX_REQUIRE(n_rows >= 1, "%s: n_rows=%d must be at least 1", who, n_rows);
+    VADX_REQUIRE(n_wg >= 1, "%s: n_wg=%d must be at least 1", who, n_wg);
+    VADX_REQUIRE(cap >= 1, "%s: cap=%d must be at least 1", who, cap);
+    VADX_REQUIRE(cfg->frames >= 1 && cfg->frames <= MAX_T, "%s: frames=%d outside [1, %d], the frames of a tick", who, cfg->frames, MAX_T);
+    VADX_REQUIRE((long long)n_rows * cfg->frames <= 0x7fffffffll, "%s: n_rows=%d rows of frames=%d frames pass 2^31 columns", who, n_rows, cfg->frames);
+    VADX_REQUIRE((long long)n_wg + streams <= 0x7fffffffll, "%s: n_wg=%d + streams=%d workgroups pass 2^31", who, n_wg, streams);
+    VADX_REQUIRE(derive(cfg, &d) == 0, "%s: unsupported cfg (or a split arithmetic on widths the split kernels do not take)", who);
+    VADX_REQUIRE(cfg->N2 == 0, "%s: the streaming model has no look-ahead filter (N2 must be 0)", who);
+    const int ws = post->smooth_window_size < 1 ? 1 : post->smooth_window_size;
+    VADX_REQUIRE(ws <= SP_MAXWS, "%s: smooth_window_size %d > %d", who, ws, SP_MAXWS);
+    const size_t cache_words = tick_cache_words(d, streams), bytes = (cache_words + (size_t)streams * TK_HDR) * 4;
+    VADX_REQUIRE(!vadx::records_overlap(state_in, state_out, bytes), "%s: state_in and state_out overlap", who);
+    VADX_REQUIRE(((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 15) == 0,
+                 "%s: the records state_in / state_out must be 16-byte aligned", who);
+    TickArgs a;
+    a.logmel = logmel; a.reset = reset; a.active = nullptr;
+    a.cin = static_cast<const unsigned *>(state_in); a.hin = a.cin + cache_words;
+    a.cout = static_cast<unsigned *>(state_out); a.hout = a.cout + cache_words;
+    a.probs = probs; a.segs = segments; a.counts = counts_out; a.open_start = open_start;
+    a.S = streams; a.F = 0; a.group = 0; a.cap = cap;          // F and group are per workgroup, set by the kernel
+    a.NC = d.R * d.P * (d.N1 - 1) * d.S1;
+    a.q.ws = ws; a.q.thr = post->speech_threshold; a.q.pad_start = post->pad_start_frame > ws ? post->pad_start_frame : ws;
+    a.q.min_sp = post->min_speech_frame; a.q.max_sp = post->max_speech_frame; a.q.min_si = post->min_silence_frame;
+    TickTabs rt;
+    rt.counts = counts; rt.row_first = row_first; rt.slot_stream = slot_stream; rt.wg_first = wg_first; rt.status = status;
+    rt.n_wg = n_wg; rt.n_rows = n_rows; rt.frames = cfg->frames;
+    const unsigned grid = (unsigned)n_wg + (unsigned)streams;    // the compute workgroups, then one per stream for the records without audio
+    const size_t lds = TKR_LDS_FLOATS * sizeof(float);
+    VADX_DYN_LDS((firered_stream_tick_kernel<0, true>), lds);
+    VADX_DYN_LDS((firered_stream_tick_kernel<1, true>), lds);
+    VADX_DYN_LDS((firered_stream_tick_kernel<2, true>), lds);
+    if (d.arith == vadx::VADX_AR_H2)
+        hipLaunchKernelGGL((firered_stream_tick_kernel<2, true>), dim3(grid), dim3(THREADS), lds, static_cast<hipStream_t>(stream), d, packed, a, rt);
+    else if (d.arith == vadx::VADX_AR_B3)
+        hipLaunchKernelGGL((firered_stream_tick_kernel<1, true>), dim3(grid), dim3(THREADS), lds, static_cast<hipStream_t>(stream), d, packed, a, rt);
+    else
+        hipLaunchKernelGGL((firered_stream_tick_kernel<0, true>), dim3(grid), dim3(THREADS), lds, static_cast<hipStream_t>(stream), d, packed, a, rt);
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }

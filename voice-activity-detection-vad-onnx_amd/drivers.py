@@ -269,10 +269,11 @@ def inference_firered_aed(test_aed_audio="./vad_sample.wav", engine=None, NORMAL
 def inference_firered_stream(test_vad_audio="./vad_sample.wav", engine=None, NORMALIZE_AUDIO=False, SMOOTH_WINDOW_SIZE=5,
                              STREAM_VAD_THRESHOLD=0.4, PAD_START_FRAME=5, MIN_SPEECH_FRAME_STREAM=8,
                              MAX_SPEECH_FRAME_STREAM=2000, MIN_SILENCE_FRAME_STREAM=20, STREAM_CHUNK_SAMPLES=2560, echo=print,
-                             batched=False):
+                             batched=False, CHUNKS_PER_TICK=1):
     """FireRedVAD/Inference_FireRed_ONNX.py:744-840 (RUN_STREAM_VAD): -> [(start_s, end_s)] per file.
     batched=True with a list of files runs them as the streams of one batch (FireRedEngine.stream_detect over the list: all files tick
-    together on the chunk grid) instead of one file after the other."""
+    together on the chunk grid) instead of one file after the other; CHUNKS_PER_TICK = k > 1 then advances every file by up to k
+    chunks per tick (ragged ticks: the same segments in a k-th of the launches)."""
     from . import firered
     engine = _engine_of(firered.FireRedEngine, engine, STREAM_CHUNK_SAMPLES)
     clips = _load(_as_list(test_vad_audio), NORMALIZE_AUDIO)
@@ -282,7 +283,7 @@ def inference_firered_stream(test_vad_audio="./vad_sample.wav", engine=None, NOR
             MIN_SILENCE_FRAME_STREAM)
     results = []
     if batched and isinstance(test_vad_audio, (list, tuple)):
-        results = engine.stream_detect(list(clips), chunk=STREAM_CHUNK_SAMPLES, post=post)
+        results = engine.stream_detect(list(clips), chunk=STREAM_CHUNK_SAMPLES, post=post, chunks_per_tick=CHUNKS_PER_TICK)
     else:
         for c in clips:
             results += engine.stream_detect(c[None, :], chunk=STREAM_CHUNK_SAMPLES, post=post)

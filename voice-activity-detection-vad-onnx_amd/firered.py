@@ -206,13 +206,20 @@ class FireRedEngine:
                                                           _lib.stream_ptr()))
         return probs, caches_out
 
-    def stream_detect(self, clips_i16, chunk=STREAM_CHUNK_SAMPLES, post=(5, 0.4, 5, 8, 2000, 20), return_probs=False):
+    def stream_detect(self, clips_i16, chunk=STREAM_CHUNK_SAMPLES, post=(5, 0.4, 5, 8, 2000, 20), return_probs=False, chunks_per_tick=1):
         """Equal-length clips int16 [B,N] (host): every clip is one stream, all streams advance one chunk per
         launch (Inference_FireRed_ONNX.py:788-822) -> per clip [(start_s, end_s)].
         A LIST (or tuple) of 1-D clips of any lengths runs as the streams of one `FireRedStreamBatch` on the chunk grid until the longest
-        is done (`_stream_detect_list`); return_probs then gives a per-clip LIST of tracks."""
+        is done (`_stream_detect_list`); return_probs then gives a per-clip LIST of tracks.  chunks_per_tick = k > 1 (lists only) advances
+        every stream by up to k whole chunks per tick (`FireRedStreamBatch.step_ragged`: stream b takes min(k, whole chunks left)); the
+        segments and the tracks are those of k = 1."""
+        k = int(chunks_per_tick)
+        if k < 1:
+            raise ValueError(f"chunks_per_tick={chunks_per_tick} must be at least 1")
         if isinstance(clips_i16, (list, tuple)):
-            return self._stream_detect_list(clips_i16, chunk, post, return_probs)
+            return self._stream_detect_list(clips_i16, chunk, post, return_probs, k)
+        if k != 1:
+            raise ValueError("chunks_per_tick above 1 takes a list of clips (equal-length arrays advance one chunk per launch)")
         t = self.torch
         clips = np.asarray(clips_i16)
         B, n = clips.shape
@@ -237,12 +244,14 @@ class FireRedEngine:
         track = track_dev.cpu().numpy()
         return (out, track) if return_probs else out
 
-    def _stream_detect_list(self, clips, chunk, post, return_probs):
+    def _stream_detect_list(self, clips, chunk, post, return_probs, chunks_per_tick=1):
         """`stream_detect` over clips of any lengths: clip b is stream b of one FireRedStreamBatch.  At every position of the chunk grid the
         streams that still have a whole chunk tick together; a stream's short last chunk runs in a tick of its own length (zero-padded to
         400 samples if shorter), streams elsewhere inactive.  A padded last chunk adds one frame; where that frame lies beyond
         valid_frame_count(len) -- a clip of whole chunks plus fewer than 80 samples, or one under 400 samples -- the reference cuts it off
-        the track again, so the tick is skipped.  Per clip: the events of all ticks, then the segment still open at its end."""
+        the track again, so the tick is skipped.  Per clip: the events of all ticks, then the segment still open at its end.
+        chunks_per_tick = k > 1: the grid steps by k chunks and the whole chunks of a step run as ONE ragged tick, stream b taking
+        min(k, whole chunks left); the short last chunks run as above, each where its stream's whole chunks end."""
         t = self.torch
         clips = [np.ascontiguousarray(np.asarray(c).reshape(-1), dtype=np.int16) for c in clips]
         S, chunk = len(clips), int(chunk)
@@ -260,7 +269,9 @@ class FireRedEngine:
         out, tracks = [[] for _ in range(S)], [[] for _ in range(S)]
         done = np.zeros(S, dtype=np.int64)                                        # frames each stream has run
         valid = np.array([valid_frame_count(int(n), self.in_sample_rate) for n in lens], dtype=np.int64)
-        for g in range(grid):
+        if chunks_per_tick > 1:
+            self._ragged_ticks(it, dev, lens, valid, done, chunk, chunks_per_tick, out, tracks, return_probs)
+        for g in range(grid if chunks_per_tick == 1 else 0):
             pos = g * chunk
             left = lens - pos
             ticks = [(chunk, left >= chunk)] + [(int(n), left == n) for n in sorted(set(left[(left > 0) & (left < chunk)].tolist()))]
@@ -284,6 +295,42 @@ class FireRedEngine:
         if not return_probs:
             return out
         return out, [np.concatenate(tr) if tr else np.zeros(0, np.float32) for tr in tracks]
+
+    def _ragged_ticks(self, it, dev, lens, valid, done, chunk, k, out, tracks, return_probs):
+        """The tick loop of `_stream_detect_list` at k > 1 chunks per tick (same arguments, filled in place)."""
+        S = len(lens)
+        frames = valid_frame_count(chunk, self.in_sample_rate)
+        if frames > MAX_FRAMES:
+            raise ValueError(f"a stream chunk holds at most {MAX_FRAMES} frames, {chunk} samples are {frames}")
+        k = min(k, MAX_FRAMES // frames)                                          # what a workgroup's columns hold
+        for pos in range(0, int(lens.max()), k * chunk):
+            whole = np.clip((lens - pos) // chunk, 0, k)
+            if whole.any():
+                probs, events, first = it.step_ragged(dev[:, pos:pos + k * chunk], whole, chunk=chunk)
+                done += whole * frames
+                track = probs[0].cpu().numpy() if return_probs else None
+                for b in np.flatnonzero(whole):
+                    out[b] += events[b]
+                    if return_probs:
+                        tracks[b].append(track[first[b] * frames:first[b + 1] * frames])
+            start = pos + whole * chunk                                           # where each stream's whole chunks of this step end
+            left = lens - start
+            tail = (whole < k) & (left > 0) & (left < chunk)
+            for p, n in sorted(set(zip(start[tail].tolist(), left[tail].tolist()))):
+                act = tail & (start == p) & (left == n)
+                width = max(n, WINDOW_LENGTH)
+                fr = valid_frame_count(width, self.in_sample_rate)
+                if n < WINDOW_LENGTH:
+                    act = act & (done + fr <= valid)
+                if not act.any():
+                    continue
+                probs, events = it.step(dev[:, p:p + width].contiguous(), active=None if act.all() else act)
+                done[act] += fr
+                track = probs[:, 0, :].cpu().numpy() if return_probs else None
+                for b in np.flatnonzero(act):
+                    out[b] += events[b]
+                    if return_probs:
+                        tracks[b].append(track[b])
 
     def detect(self, clips_i16, pad_noise=None, post=(5, 0.4, 20, 2000, 20, 5, 0), return_probs=False):
         """Equal-length clips int16 [B,N] (host) -> per clip [(start_s, end_s)] for output channel 0
@@ -465,6 +512,124 @@ class FireRedStreamBatch(StreamBatch):
         for s in np.flatnonzero(cn).tolist():                     # most streams end nothing in most ticks
             events[s] = [(int(a) * inv_fps, int(b) * inv_fps) for a, b in sg[s, :cn[s]].tolist()]
         return probs, events
+
+    def _ragged_rows(self, samples, counts, n, capacity):
+        """The samples and counts of a ragged tick -> (rows int16 [n_rows, n] or None, x int16 [S, >= max(counts) * n] tensor
+        or None, counts int32 [S]).  A list of S 1-D arrays gives its own counts, and its concatenation IS the row matrix (made on the
+        device when a listed row lies there)."""
+        S, t = self.streams, self.engine.torch
+        if isinstance(samples, (list, tuple)):
+            if len(samples) != S:
+                raise ValueError(f"samples lists {len(samples)} arrays for {S} streams")
+            resident = any(t.is_tensor(r) and r.device.type != "cpu" for r in samples)      # then the rows are concatenated where they are
+            rows = [(r if t.is_tensor(r) else t.from_numpy(np.ascontiguousarray(r))).reshape(-1) if resident else
+                    np.asarray(r.cpu() if hasattr(r, "cpu") else r).reshape(-1) for r in samples]
+            for s, r in enumerate(rows):
+                if r.dtype != (t.int16 if resident else np.int16):
+                    raise ValueError(f"samples[{s}] must be int16, got {r.dtype}")
+                if r.shape[0] % n:
+                    raise ValueError(f"samples[{s}] holds {r.shape[0]} samples: a stream takes whole chunks of {n}")
+            got = np.array([r.shape[0] // n for r in rows], dtype=np.int64)
+            if counts is not None and not np.array_equal(np.asarray(counts).reshape(-1), got):
+                raise ValueError("counts disagree with the lengths of the listed samples")
+            counts = _ragged.chunk_counts(got, S, capacity)
+            if resident:
+                return t.cat([r.to(self.engine.device) for r in rows]).view(-1, n), None, counts
+            return np.concatenate(rows).reshape(-1, n), None, counts
+        if counts is None:
+            raise ValueError("step_ragged needs counts with a [S, n] array")
+        counts = _ragged.chunk_counts(counts, S, capacity)
+        need = int(counts.max(initial=0)) * n
+        x = self._samples(samples, f"[{S}, >= max(counts) * chunk = {need}]", lambda x: x.shape[1] < need)
+        return None, x, counts
+
+    def step_ragged(self, samples_i16, counts=None, chunk=None, reset=None, group=0):
+        """A tick in which stream s advances by counts[s] chunks of `chunk` samples (default: the engine's input length; at least 400,
+        frames = valid_frame_count(chunk) <= 112), 0 <= counts[s] <= 112 // frames: the work is sum(counts) chunks behind the front-end
+        and ONE net launch (vadx_firered_stream_tick_ragged).  samples_i16: int16 [S, >= max(counts) * chunk] (host or device, numpy or
+        torch), row s holding that stream's counts[s] * chunk new samples from column 0 -- or a list of S 1-D arrays whose lengths are
+        multiples of `chunk` (the counts then come from the lengths, and the concatenation is staged as it is).
+        -> (probs f32 [odim, n_rows * frames] on the device: stream s owns the columns first[s] * frames .. first[s + 1] * frames - 1;
+        events: as `step`; first: host int64 [S + 1], the prefix sum of the counts).  self.open_start is as after `step`.  A stream with
+        count 0 costs nothing: it keeps its record and its pending reset, a reset request for it is ignored, it has no probabilities
+        and no events.  A tick whose counts are all 0 launches nothing and leaves the record and the pending resets alone.  Counts
+        outside [0, 112 // frames], a wrong shape or a non-integer dtype raise ValueError before anything is launched.  group: the most
+        streams per workgroup (0 = the library's choice); no result depends on it.  `step` and `step_ragged` interchange tick by tick
+        (one record); `step` stays the path for uniform ticks."""
+        eng, t = self.engine, self.engine.torch
+        S = self.streams
+        n = int(eng.L if chunk is None else chunk)
+        if n < WINDOW_LENGTH:
+            raise ValueError(f"a stream chunk needs at least {WINDOW_LENGTH} samples, got {n}")
+        T = valid_frame_count(n, eng.in_sample_rate)
+        if T > MAX_FRAMES:
+            raise ValueError(f"a stream chunk holds at most {MAX_FRAMES} frames, {n} samples are {T}")
+        capacity = MAX_FRAMES // T                                # vadx_firered_stream_group_max(T)
+        rows, x, counts = self._ragged_rows(samples_i16, counts, n, capacity)
+        first, order, wg_first = _ragged.column_stream_plan(counts, capacity, group)
+        n_rows, inv_fps = int(first[-1]), 1.0 / self.frames_per_second
+        if n_rows == 0:              # nobody delivered audio: no launch; the record and the pending resets stay
+            self.open_start = t.full((S,), -1, dtype=t.int32, device=eng.device)
+            return t.empty((eng.odim, 0), dtype=t.float32, device=eng.device), [[] for _ in range(S)], first
+        act = counts > 0
+        _, _, reset_d, _, src, dst = self._begin(reset, act, upload_active=False)
+        active, n_wg = int(np.count_nonzero(act)), int(wg_first.shape[0]) - 1
+        # (the status word is not read back: chunk_counts and column_stream_plan cannot produce a table the kernel skips, and a skipped
+        # stream would show in `frames_done`; a caller of the C entry point with tables of its own reads it)
+        # the tick's tables in ONE copy: [win_src int64 [n_rows] |] counts | row_first | slot_stream | wg_first | status (a zero the copy writes)
+        tabs = [counts, first[:S].astype(np.int32), order[:active], wg_first, np.zeros(1, np.int32)]
+        gather = rows is None
+        if gather:
+            x = x.to(eng.device)
+            if x.stride(1) != 1:
+                x = x.contiguous()
+            stride = int(x.stride(0)) if S > 1 else int(x.shape[1])
+            win_stream = np.repeat(np.arange(S, dtype=np.int64), counts)
+            win_src = win_stream * stride + (np.arange(n_rows, dtype=np.int64) - first[win_stream]) * n
+            tabs.insert(0, win_src.view(np.int32))
+        tab = t.from_numpy(np.concatenate(tabs).astype(np.int32, copy=False)).to(eng.device)
+        p_counts = tab.data_ptr() + (8 * n_rows if gather else 0)
+        p_first, p_slot, p_wg = p_counts + 4 * S, p_counts + 8 * S, p_counts + 4 * (2 * S + active)
+        p_status = p_wg + 4 * (n_wg + 1)
+        Lb = _lib.lib()
+        if gather:
+            wbuf = t.empty((n_rows, n), dtype=t.int16, device=eng.device)
+            pcm_len = (S - 1) * stride + int(x.shape[1])
+            runs = n % 8 == 0 and stride % 8 == 0 and x.data_ptr() % 16 == 0       # 16-byte runs: the aligned gather
+            with t.cuda.device(eng.device):
+                _lib.check((Lb.vadx_windows_gather if runs else Lb.vadx_windows_gather_any)(
+                    x.data_ptr(), pcm_len, tab.data_ptr(), n_rows, n, wbuf.data_ptr(), _lib.stream_ptr()))
+        else:
+            wbuf = rows if t.is_tensor(rows) else t.from_numpy(rows).to(eng.device)
+        fe = eng._frontend_for(n)
+        logmel = fe.logmel(wbuf, 1, n)
+        cap = int(self.cap) if self.cap else int(counts.max()) * T      # a forced split per frame is the most a tick can end
+        probs = t.empty((eng.odim, n_rows * T), dtype=t.float32, device=eng.device)
+        segs = t.empty((S, cap, 2), dtype=t.int32, device=eng.device)
+        cnt = t.empty((S,), dtype=t.int32, device=eng.device)
+        opened = t.empty((S,), dtype=t.int32, device=eng.device)
+
+        def launch(mode, cfg, packed):
+            c = _lib.FireRedCfg.from_buffer_copy(cfg)
+            c.frames = T
+            with t.cuda.device(eng.device):
+                _lib.check(Lb.vadx_firered_stream_tick_ragged(C.byref(c), packed.data_ptr(), logmel.data_ptr(), S, n_rows, p_counts, p_first,
+                                                              p_slot, p_wg, n_wg, C.byref(self._prm),
+                                                              None if reset_d is None else reset_d.data_ptr(), src.data_ptr(),
+                                                              dst.data_ptr(), probs.data_ptr(), segs.data_ptr(), cnt.data_ptr(), cap,
+                                                              opened.data_ptr(), p_status, _lib.stream_ptr()))
+        eng.blobs.guarded(launch)
+        self._end(act)
+        self.open_start = opened
+        cn = cnt.cpu().numpy()
+        used = int(cn.max())
+        if used > cap:
+            raise _lib.VadxError(f"FireRedStreamBatch: {used} segments ended in one tick, cap={cap} (the record has advanced)")
+        sg = segs[:, :used].cpu().numpy() if used else np.zeros((S, 0, 2), np.int32)
+        events = [[] for _ in range(S)]
+        for s in np.flatnonzero(cn).tolist():
+            events[s] = [(int(a) * inv_fps, int(b) * inv_fps) for a, b in sg[s, :cn[s]].tolist()]
+        return probs, events, first
 
 
 class FireRedSession(Session):

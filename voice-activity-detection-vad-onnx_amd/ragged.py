@@ -762,3 +762,71 @@ def stream_slots_mirror(counts, bucket_first, groups, window, max_windows):
         slot_clip[e], slot_off[e], slot_len[e] = -1, 0, 0
     probs_first = np.concatenate([[0], np.cumsum(key)]).astype(np.int64)
     return probs_first, slot_off, slot_len, slot_clip, status
+
+
+# ---- ragged ticks of the FireRed streams (include/vadx.h: vadx_firered_stream_tick_ragged) ----
+TICK_COLUMNS = 112           # LDS columns of a tick workgroup (csrc/firered.hip: MAX_T) = frames it holds
+
+
+def chunk_counts(counts, streams, capacity):
+    """A tick's per-stream chunk counts as int32 [streams], or ValueError: wrong shape, not integers, negative or above `capacity`
+    (= 112 // frames per chunk, vadx_firered_stream_group_max)."""
+    cap = int(capacity)
+    if not 1 <= cap <= TICK_COLUMNS:
+        raise ValueError(f"capacity={capacity} must be in [1, {TICK_COLUMNS}]")
+    c = np.asarray(counts.cpu() if hasattr(counts, "cpu") else counts)
+    if c.dtype.kind not in "iu":
+        raise ValueError(f"counts must be integers, got dtype {c.dtype}")
+    if c.shape != (int(streams),):
+        raise ValueError(f"counts must have shape ({int(streams)},), got {c.shape}")
+    if c.size and int(c.min()) < 0:
+        raise ValueError(f"counts[{int(np.argmin(c))}]={int(c.min())} is negative")
+    if c.size and int(c.max()) > cap:
+        raise ValueError(f"counts[{int(np.argmax(c))}]={int(c.max())} is above {cap}, the chunks a workgroup's {TICK_COLUMNS} columns hold")
+    return c.astype(np.int32)
+
+
+def column_stream_plan(counts, capacity, group=0):
+    """The host tables of a ragged FireRed tick: which streams share a workgroup's `capacity` chunks of LDS columns.  counts: int [S],
+    0 <= n_s <= capacity = 112 // frames.  -> (first int64 [S + 1] = prefix sum of the counts: stream s owns the rows first[s] ..
+    first[s + 1] - 1; order int32 [S] = np.argsort(-counts, kind="stable"), whose active prefix (the streams with n_s > 0) is the
+    slot_stream table; wg_first int32 [W + 1]: workgroup w serves the positions wg_first[w] .. wg_first[w + 1] - 1 of it).
+    Workgroups are formed by next-fit along that order: a workgroup takes consecutive positions while its counts sum to at most
+    `capacity` and it holds at most g streams, g = group or, for group = 0, clamp(active // 256, 1, capacity) -- the rule of the
+    rectangular tick (a compute unit with a workgroup beats a shared weight load).  The order is a counting sort and the boundaries have
+    a closed form per distinct count (at most `capacity` classes): no comparison sort, no loop over streams.  All-zero counts give W = 0."""
+    c = np.asarray(counts)
+    c = chunk_counts(c, c.shape[0] if c.ndim == 1 else -1, capacity)
+    S, cap = int(c.shape[0]), int(capacity)
+    if not 0 <= int(group) <= cap:
+        raise ValueError(f"group={group} outside [0, {cap}] (0 = the library's choice)")
+    first = np.zeros(S + 1, dtype=np.int64)
+    np.cumsum(c, out=first[1:])
+    idx = np.arange(S, dtype=np.int32)
+    hist = np.bincount(c, minlength=1)
+    active = S - int(hist[0])
+    g = int(group) if group else min(max(active // 256, 1), cap)
+    order = np.empty(S, dtype=np.int32)
+    bounds = [np.zeros(1, dtype=np.int64)]
+    at, used, held = 0, 0, 0                      # sorted position; chunks and streams of the workgroup still open
+    for v in np.flatnonzero(hist)[::-1].tolist():        # one class per count that occurs, largest first; a class keeps index order
+        n = int(hist[v])
+        order[at:at + n] = idx[c == v]
+        if v:
+            per = min(cap // v, g)                        # streams of this count in a workgroup of its own
+            fit = min(n, (cap - used) // v, g - held)     # those the open workgroup still takes
+            rest = n - fit
+            if rest:
+                new = -(-rest // per)
+                bounds.append(at + fit + per * np.arange(new, dtype=np.int64))
+                last = rest - (new - 1) * per
+                used, held = last * v, last
+            else:
+                used, held = used + fit * v, held + fit
+        at += n
+    if active:
+        bounds.append(np.array([active], dtype=np.int64))
+        wg_first = np.concatenate(bounds).astype(np.int32)
+    else:
+        wg_first = np.zeros(1, dtype=np.int32)
+    return first, order, wg_first
