@@ -68,7 +68,8 @@ extern "C" {
  *     ragged ticks of the Silero streams: vadx_silero_stream_ragged_max_windows, vadx_silero_stream_plan_bytes,
  *     vadx_silero_stream_ragged_workspace_bytes, vadx_silero_stream_plan, vadx_silero_stream_run_ragged; then ragged ticks of the FSMN
  *     streams: vadx_fsmn_stream_ragged_max_windows, vadx_fsmn_stream_windows_ragged, vadx_fsmn_stream_run_ragged; then ragged ticks of the FireRed
- *     streams: vadx_firered_stream_tick_ragged.
+ *     streams: vadx_firered_stream_tick_ragged; then FireRed windows of any length: vadx_firered_long_tables,
+ *     vadx_firered_long_workspace_bytes, vadx_firered_run_long, vadx_frontend_logmel_ragged_snip.
  *     A caller that needs them checks for the symbols (dlsym), not for a number. */
 #define VADX_ABI_VERSION 10
 
@@ -761,6 +762,47 @@ int vadx_firered_pack_host(const vadx_firered_cfg *cfg, const vadx_firered_weigh
 int vadx_firered_run(const vadx_firered_cfg *cfg, const float *packed, const float *logmel, int windows,
                      float *probs, void *stream);
 
+/* ---- FireRed windows of ANY length: the export at any INPUT_AUDIO_LENGTH or with DYNAMIC_AXES = True
+ * (FireRedVAD/Export_FireRedVAD.py:29,48,785-807), which the reference's drivers run as ONE window per file
+ * (INPUT_AUDIO_LENGTH_RUN = min(3600 s, audio_len): FireRedVAD/Inference_FireRed_ONNX.py:541-547 VAD, :644-650 AED).  A window of T
+ * frames no longer lives in one workgroup: the activations live in a caller-owned workspace and the grid is (window, tile of 64
+ * frames), R + 1 launches.  A long window is ANOTHER export than the 1 s one: every window edge zero-pads the look-ahead / look-back
+ * filters of all R blocks, so fewer edges give other numbers -- not a faster way to the same ones.  Where both apply (T <= 112) the
+ * probabilities are bit for bit those of vadx_firered_run. */
+#define VADX_FIRERED_LONG_MAX_FRAMES 360000   /* frames of one window: covers 3600 s at 16 kHz (359 998 frames), the reference's cap (:541) */
+#define VADX_FIRERED_LONG_TILE       64       /* frames per tile of the long launches and of the snip-edge ragged front-end */
+
+/* The tables of a batch of windows of any lengths (device pointers), in the style of vadx_marblenet_ragged.  Window b (one clip in
+ * the dynamic mode, one window of the grid in a static one; :541-547) has T_b = frame_first[b + 1] - frame_first[b] frames, 0 <= T_b <=
+ * VADX_FIRERED_LONG_MAX_FRAMES (0: a clip under 400 samples, no frame and no tile), and ceil(T_b / 64) tiles.  A rectangular batch is the same tables
+ * with equal counts. */
+typedef struct vadx_firered_long_tables {
+    const int32_t *frame_first;   /* [clips + 1], frame_first[clips] = frames_total */
+    const int32_t *tile_first;    /* [clips + 1], tile_first[clips] = n_tiles */
+    const int32_t *tile_clip;     /* [n_tiles]: the window of every tile */
+    int32_t clips, n_tiles, frames_total;
+} vadx_firered_long_tables;
+
+/* Bytes of the workspace of vadx_firered_run_long: p (two planes) and mem (one), each f32 [P][frames_total] = 3 * P * frames_total
+ * floats; 0 for a cfg outside vadx_firered_cfg's limits (cfg->frames aside) or frames_total outside [1, 2^31). */
+size_t vadx_firered_long_workspace_bytes(const vadx_firered_cfg *cfg, int64_t frames_total);
+/* logmel f32 [frames_total][80] (window b's rows from frame_first[b]: vadx_frontend_logmel at window_len = L for a rectangular batch,
+ * vadx_frontend_logmel_ragged_snip for a ragged one) -> probs f32 [odim][frames_total]: output o of window b's frame t at
+ * probs[o * frames_total + frame_first[b] + t] -- planes that suit vadx_tracks_gather(probs + o * frames_total, win_floats = 1,
+ * frames_per_window = 1, win_first = frame_first), as MarbleNet's ragged scores.  Replaces ort_session_A.run([probs], {audio}) on a
+ * dynamic or long export, FireRedVAD/Inference_FireRed_ONNX.py:567-572 (VAD), :668-673 (AED).  The blob is vadx_firered_pack_host's,
+ * unchanged; cfg->frames only has to lie in [1, VADX_FIRERED_LONG_MAX_FRAMES] (T comes from the tables).  All three arithmetics under the range
+ * protocol as it stands (an F16X2 call that raised vadx_firered_range_flag is repeated whole on BF16X3).  The look-ahead filter of a
+ * one-frame window is skipped, as in the reference (Export_FireRedVAD.py:229).
+ * Returns, before any HIP call: VADX_EINVAL naming the argument for a NULL pointer or table, cfg->frames outside its range, clips /
+ * n_tiles / frames_total < 1, counts that do not fit each other (n_tiles <= frames_total <= 64 * n_tiles), an unsupported cfg;
+ * VADX_ENOSPACE for workspace_bytes below vadx_firered_long_workspace_bytes.  Device-side guard of every launch: a workgroup whose table
+ * entries name a clip outside [0, clips), a tile outside its clip's tiles, an empty or decreasing prefix range, a range beyond
+ * frames_total, a window above the cap, or a tile count that disagrees with the frame count returns before its first read or write of
+ * the buffers: its rows keep what they held. */
+int vadx_firered_run_long(const vadx_firered_cfg *cfg, const float *packed, const float *logmel, const vadx_firered_long_tables *tables,
+                          float *probs, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Streaming variant (FireRed Stream-VAD): one chunk of cfg->frames frames for `streams`
  * independent streams; caches f32 [R][streams][P][(N1-1)*S1] in -> out (must not alias); cfg->N2 == 0.
  * Replaces ort_session_C.run([probs, caches_out], {audio, caches_in}), Inference_FireRed_ONNX.py:798-801
@@ -963,6 +1005,17 @@ int vadx_frontend_logmel_ragged(const vadx_frontend_cfg *cfg, const float *packe
                                 int64_t pcm_len, const int64_t *clip_off, const int32_t *clip_len, const int32_t *mel_first,
                                 const int32_t *tile_first, const int32_t *tile_clip, int clips, int n_tiles, int mel_total,
                                 float *out, void *stream);
+
+/* The same launch for a SNIP-EDGE preset (no centre pad: the FireRed front-end, FireRedVAD/Export_FireRedVAD.py:396-418, 428-461): clip b
+ * has (clip_len[b] - n_fft) / hop + 1 frames, n_fft = taps + 2 * tap0 -- none when it is shorter than n_fft samples, and then no tile
+ * and no row.  It is the front-end of the dynamic-axis FireRed call on B files of different lengths (one window per file,
+ * FireRedVAD/Inference_FireRed_ONNX.py:541-547, :644-650); mel_first / tile_first / tile_clip are vadx_firered_long_tables' frame_first /
+ * tile_first / tile_clip.  Arguments and refusals as above, with cfg->center_pad == 0 required instead and n_tiles <= mel_total <= 64 *
+ * n_tiles (clips may exceed n_tiles: a clip may have no frame).  vadx_frontend_logmel_ragged itself keeps refusing a centre pad of 0. */
+int vadx_frontend_logmel_ragged_snip(const vadx_frontend_cfg *cfg, const float *packed, const int32_t *mel_kb_host, const int16_t *pcm,
+                                     int64_t pcm_len, const int64_t *clip_off, const int32_t *clip_len, const int32_t *mel_first,
+                                     const int32_t *tile_first, const int32_t *tile_clip, int clips, int n_tiles, int mel_total,
+                                     float *out, void *stream);
 
 /* The encoder's tables (device pointers): the 32-frame tile tables, frame_first = enc_first, src_first = mel_first (read by
  * vadx_sepconv_block_ragged only; the other two ignore src_first / src_total). */

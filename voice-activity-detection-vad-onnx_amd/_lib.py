@@ -125,6 +125,15 @@ class FireRedWeightsHost(C.Structure):
                 ("dnn_b", C.c_void_p * 4), ("out_w", C.c_void_p), ("out_b", C.c_void_p)]
 
 
+FIRERED_LONG_MAX_FRAMES, FIRERED_LONG_TILE = 360000, 64      # include/vadx.h: VADX_FIRERED_LONG_MAX_FRAMES, VADX_FIRERED_LONG_TILE
+
+
+class FireRedLongTables(C.Structure):
+    """vadx_firered_long_tables (include/vadx.h): the tables of a batch of FireRed windows of any lengths (device pointers) and their counts"""
+    _fields_ = [("frame_first", C.c_void_p), ("tile_first", C.c_void_p), ("tile_clip", C.c_void_p),
+                ("clips", C.c_int32), ("n_tiles", C.c_int32), ("frames_total", C.c_int32)]
+
+
 class VadPostParams(C.Structure):
     _fields_ = [("smooth_window_size", C.c_int), ("prob_threshold", C.c_float), ("min_speech_frame", C.c_int),
                 ("max_speech_frame", C.c_int), ("min_silence_frame", C.c_int), ("merge_silence_frame", C.c_int),
@@ -242,6 +251,9 @@ SIGNATURES = {
     "vadx_firered_range_flag": (_I, [C.POINTER(FireRedCfg), _P, _I, _P, _P, _P]),
     "vadx_firered_pack_host": (_I, [C.POINTER(FireRedCfg), C.POINTER(FireRedWeightsHost), _P]),
     "vadx_firered_run": (_I, [C.POINTER(FireRedCfg), _P, _P, _I, _P, _P]),
+    "vadx_firered_long_workspace_bytes": (_Z, [C.POINTER(FireRedCfg), _L]),
+    "vadx_firered_run_long": (_I, [C.POINTER(FireRedCfg), _P, _P, C.POINTER(FireRedLongTables), _P, _P, _Z, _P]),
+    "vadx_frontend_logmel_ragged_snip": (_I, [C.POINTER(FrontendCfg), _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "vadx_ingest_out_frames": (C.c_int64, [C.c_int64, _I, _I]),
     "vadx_ingest_pcm16": (_I, [_P, C.c_int64, _I, C.c_int64, _I, _I, _P, C.c_int64, _I, _P]),
     "vadx_frag_major_floats": (C.c_size_t, [_I, _I]),

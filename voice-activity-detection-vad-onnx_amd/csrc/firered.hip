@@ -1410,3 +1410,260 @@ extern "C" int vadx_firered_stream_tick_ragged(const vadx_firered_cfg *cfg, cons
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;
 }
+
+
+// ---- windows of ANY length (include/vadx.h: vadx_firered_run_long).  The reference exports the graph at any INPUT_AUDIO_LENGTH or with
+// a dynamic axis (FireRedVAD/Export_FireRedVAD.py:29,48,785-807) and runs one window per file (Inference_FireRed_ONNX.py:541-547,
+// :644-650); a window of T frames no longer lives in one workgroup's LDS.  The activations live in a global workspace -- per batch `p`
+// (two planes, ping-pong) and `mem` (one plane), each f32 [P][frames_total], clip b's frames at columns frame_first[b] .. -- and the
+// grid is (window, tile of 64 frames).  R + 1 launches:
+//   head        log-mel tile -> fc1 / fc2 pair -> p_0 tile (point-wise: no halo)
+//   block r     FIR over p_r read from the workspace with guards (frames < 0 or >= T contribute nothing: a window edge zero-pads the
+//               filter), + the skip from the tile's own mem_(r-1), mem_r written in place; then the point-wise pair of block r + 1 on the
+//               tile -> the other p plane, or (r = R - 1) dnn + head + sigmoid -> the probabilities.
+// A launch boundary is the only ordering the FIR needs: block r reads p_r (all written by the launch before) and writes p_(r+1) to the
+// other plane; mem is read and written at the tile's own frames only.
+// The bytes of a frame do not depend on the tile or launch that computed it: the point-wise pairs are the device functions of
+// firered_kernel (every output column depends on its own input column only), and the FIR sums per frame in fsmn_memory's order --
+// look-back taps oldest first, look-ahead taps nearest first, (p + lb) + la, then the skip.  fma(w, 0, acc) = acc for finite w, so a
+// guarded tap and fsmn_memory_fast's zero-masked tap are the same number -- but for the sign of a zero: fma(w, 0, -0) is +0 where the
+// skipped tap keeps -0.  The accumulators start at +0 and +0 + -0 = +0, so an accumulator is -0 only after a product that underflowed
+// to -0, and the sign would show only in a frame whose p is -0 as well; the bitwise tests have not met it.
+namespace vadx {
+namespace firered {
+constexpr int LONG_TILE = VADX_FIRERED_LONG_TILE;
+static_assert(LONG_TILE == 64 && LONG_TILE <= MAX_T, "a tile's columns lie in the M_LD rows");
+
+struct LongTabs {
+    const int *frame_first, *tile_first, *tile_clip;
+    int clips, n_tiles, frames_total, max_frames;
+};
+
+struct LongTile {
+    long long col;          // the tile's first frame as a column of the workspace planes, the log-mel rows and the probabilities
+    int T, t0, n;           // the window's frames, the tile's first frame in its window, the tile's frames (0: the tables lie, do nothing)
+};
+
+// (clip, tile) of this workgroup by two uniform loads, as the other ragged kernels; a workgroup whose entries lie -- a clip outside
+// [0, clips), a tile outside its clip, an empty or decreasing prefix, a range beyond the totals, a window above the cap, a tile count that
+// disagrees with the frame count -- gets n = 0 and returns before its first read or write of the buffers
+__device__ __forceinline__ LongTile long_tile(const LongTabs &tb) {
+    LongTile k{0, 0, 0, 0};
+    const int w = blockIdx.x;
+    if (w >= tb.n_tiles) return k;
+    const int b = tb.tile_clip[w];
+    if (b < 0 || b >= tb.clips) return k;
+    const int tf0 = tb.tile_first[b], tf1 = tb.tile_first[b + 1], ff0 = tb.frame_first[b], ff1 = tb.frame_first[b + 1];
+    if (tf0 < 0 || w < tf0 || w >= tf1 || ff0 < 0 || ff1 <= ff0 || ff1 > tb.frames_total) return k;
+    const int T = ff1 - ff0;
+    if (T > tb.max_frames || tf1 - tf0 != (T + LONG_TILE - 1) / LONG_TILE) return k;
+    k.T = T;
+    k.t0 = (w - tf0) * LONG_TILE;
+    k.n = T - k.t0 < LONG_TILE ? T - k.t0 : LONG_TILE;
+    k.col = (long long)ff0 + k.t0;
+    return k;
+}
+
+// LDS rows [channel][tile column] <-> a workspace plane [P][frames_total] (64-bit offsets: 4096 clips of 10 s pass 2^31 bytes a plane)
+__device__ __forceinline__ void long_store_tile(const Dev &d, const LongTile &k, const LongTabs &tb, const float *rows, float *plane) {
+    for (int e = threadIdx.x; e < d.P * LONG_TILE; e += THREADS) {
+        const int ch = e / LONG_TILE, u = e - ch * LONG_TILE;
+        if (u < k.n) plane[(size_t)ch * tb.frames_total + k.col + u] = rows[ch * M_LD + u];
+    }
+}
+
+template <int AR>
+__global__ __launch_bounds__(THREADS, 2) void firered_long_head_kernel(Dev d, const float *__restrict__ Pk, const float *__restrict__ logmel,
+                                                                       LongTabs tb, float *__restrict__ ws) {
+    constexpr bool SPLIT = AR != vadx::VADX_AR_F32;
+    typedef typename vadx::SchemeFor<AR>::type SC;
+    float amax = 0.f;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *mem = lds, *p = lds + MEM_F, *h = p + P_F;
+    const int tid = threadIdx.x;
+    const LongTile k = long_tile(tb);
+    if (k.n == 0) return;
+    const TickDims dl{k.n, d.Hp, d.Pp};
+    for (int e = tid; e < MAXP * M_LD; e += THREADS) { mem[e] = 0.f; p[e] = 0.f; }
+    __syncthreads();
+    const float *lm = logmel + (size_t)k.col * NMEL;
+    for (int e = tid; e < k.n * NMEL; e += THREADS) {
+        const int u = e / NMEL, mel = e - u * NMEL;
+        mem[mel * M_LD + u] = lm[e];
+    }
+    __syncthreads();
+    if (SPLIT) pointwise_pair_split<SC, 3>(dl, Pk + d.q_fc1, Pk + d.off_fc1b, NMEL, mem, Pk + d.q_fc2, Pk + d.off_fc2b, true, p, h, amax);
+    else pointwise_pair(dl, Pk + d.off_fc1, Pk + d.off_fc1b, NMEL / 16, mem, Pk + d.off_fc2, Pk + d.off_fc2b, 1, p, h);
+    __syncthreads();
+    long_store_tile(d, k, tb, p, ws);                                  // p_0 -> plane 0
+    if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
+}
+
+template <int AR>
+__global__ __launch_bounds__(THREADS, 2) void firered_long_block_kernel(Dev d, const float *__restrict__ Pk, LongTabs tb, float *__restrict__ ws,
+                                                                        int r, float *__restrict__ probs) {
+    constexpr bool SPLIT = AR != vadx::VADX_AR_F32;
+    typedef typename vadx::SchemeFor<AR>::type SC;
+    float amax = 0.f;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *mem = lds, *p = lds + MEM_F, *h = p + P_F;
+    const int tid = threadIdx.x;
+    const LongTile k = long_tile(tb);
+    if (k.n == 0) return;
+    const TickDims dl{k.n, d.Hp, d.Pp};
+    const size_t plane = (size_t)d.P * tb.frames_total;
+    const float *pin = ws + (size_t)(r & 1) * plane;
+    float *pout = ws + (size_t)((r + 1) & 1) * plane, *gmem = ws + 2 * plane;
+    for (int e = tid; e < MAXP * M_LD; e += THREADS) { mem[e] = 0.f; p[e] = 0.f; }
+    __syncthreads();
+    {   // the FIR of block r and the skip: thread = (channel, frame of the tile), taps from the blob, p_r from the workspace
+        // the reference's T > 1 rule for the look-ahead (Export_FireRedVAD.py:229); where fsmn_memory takes its merged-window path the
+        // look-ahead sum is added even when it is empty, and so it is here
+        const bool ahead = d.N2 > 0 && k.T > 1;
+        const bool add_la = ahead || (d.S1 == 1 && d.N1 <= 20 && (d.N2 == 0 || d.S2 == 1) && d.N2 <= 20 && k.T > 1 && d.Pp <= 128);
+        const float *wl = Pk + d.off_lb[r], *wa = Pk + d.off_la[r];
+        for (int e = tid; e < d.P * LONG_TILE; e += THREADS) {
+            const int ch = e / LONG_TILE, u = e - ch * LONG_TILE;
+            if (u >= k.n) continue;
+            const int t = k.t0 + u;
+            const float *row = pin + (size_t)ch * tb.frames_total + (k.col - k.t0);      // the window's frame 0 of this channel
+            float lb = 0.f, la = 0.f;
+            for (int j = 0; j < d.N1; ++j) {
+                const long long idx = (long long)t + (long long)(j - (d.N1 - 1)) * d.S1;
+                if (idx >= 0) lb = fmaf(wl[ch * d.N1 + j], row[idx], lb);
+            }
+            float s = row[t] + lb;
+            if (ahead)
+                for (int j = 0; j < d.N2; ++j) {
+                    const long long idx = (long long)t + d.S2 + (long long)j * d.S2;
+                    if (idx < k.T) la = fmaf(wa[ch * d.N2 + j], row[idx], la);
+                }
+            if (add_la) s += la;
+            const size_t at = (size_t)ch * tb.frames_total + k.col + u;
+            if (r > 0) s += gmem[at];
+            gmem[at] = s;
+            mem[ch * M_LD + u] = s;
+        }
+    }
+    __syncthreads();
+    if (r + 1 < d.R) {       // DFSMNBlock r + 1: fc1 (P->H, ReLU) ; fc2 (H->P, no bias) -> p_(r+1), the other plane
+        if (SPLIT) pointwise_pair_split<SC, 4>(dl, Pk + d.q_bfc1[r + 1], Pk + d.off_bfc1b[r + 1], d.Pp, mem, Pk + d.q_bfc2[r + 1], nullptr, false, p, h, amax);
+        else pointwise_pair(dl, Pk + d.off_bfc1[r + 1], Pk + d.off_bfc1b[r + 1], d.Pp / 16, mem, Pk + d.off_bfc2[r + 1], nullptr, 0, p, h);
+        __syncthreads();
+        long_store_tile(d, k, tb, p, pout);
+        if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
+        return;
+    }
+    // dnn + output head + sigmoid, as firered_kernel's tail -> probs [odim][frames_total]
+    if (SPLIT && d.M == 1) {
+        pointwise_pair_split<SC, 4>(dl, Pk + d.q_dnn0, Pk + d.off_dnnb[0], d.Pp, mem, Pk + d.q_head, Pk + d.off_headb, false, p, h, amax);
+        __syncthreads();
+        for (int e = tid; e < d.odim * k.n; e += THREADS) {
+            const int o = e / k.n, u = e - o * k.n;
+            probs[(size_t)o * tb.frames_total + k.col + u] = sigmoidf_(p[o * M_LD + u]);
+        }
+        if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
+        return;
+    }
+    float *h2 = p;
+    const bool dnn_resident = d.Hp == 256 && d.Pp == 128 && blockDim.x == 512;
+    PairResident<8> RD;
+    if (dnn_resident) load_pair_resident<8, false>(RD, Pk + d.off_dnn[0], Pk + d.off_dnnb[0], nullptr, nullptr);
+    for (int f0 = 0; f0 < k.n; f0 += 32) {
+        const bool half = (k.n - f0) <= 16;
+        if (dnn_resident) {
+            if (half) pair_tile_resident<1, 8, false>(RD, mem, nullptr, h, f0, false);
+            else pair_tile_resident<2, 8, false>(RD, mem, nullptr, h, f0, false);
+        } else {
+            LayerArgs a{Pk + d.off_dnn[0], d.Pp, d.Hp / 16, 1, d.Pp / 16, 0, 0, Pk + d.off_dnnb[0], 1, mem, M_LD, f0, h, H_LD, 0, nullptr, nullptr};
+            if (half) layer<1, false>(a); else layer<2, false>(a);
+            __syncthreads();
+        }
+        float *cur = h, *nxt = h2;
+        for (int m = 1; m < d.M; ++m) {
+            LayerArgs c{Pk + d.off_dnn[m], d.Hp, d.Hp / 16, 1, d.Hp / 16, 0, 0, Pk + d.off_dnnb[m], 1, cur, H_LD, 0, nxt, H_LD, 0, nullptr, nullptr};
+            if (half) layer<1, false>(c); else layer<2, false>(c);
+            __syncthreads();
+            float *tmp = cur; cur = nxt; nxt = tmp;
+        }
+        float *lg = p + MAXH * H_LD;            // behind h2
+        {   LayerArgs o{Pk + d.off_out, d.Hp, 1, 1, d.Hp / 16, 0, 0, Pk + d.off_outb, 0, cur, H_LD, 0, lg, H_LD, 0, nullptr, nullptr};
+            if (half) layer<1, false>(o); else layer<2, false>(o); }
+        __syncthreads();
+        if (tid < 32 * d.odim) {
+            const int u = tid & 31, o = tid >> 5;
+            if (f0 + u < k.n) probs[(size_t)o * tb.frames_total + k.col + f0 + u] = sigmoidf_(lg[o * H_LD + u]);
+        }
+        __syncthreads();
+    }
+    if (AR == vadx::VADX_AR_H2) vadx::range_flag_raise(Pk + d.off_flag, amax);
+}
+}  // namespace firered
+}  // namespace vadx
+
+// cfg as the long entry points read it: every field under derive()'s limits but `frames`, which only has to be valid here (the tables say
+// T per window) -- 1 .. VADX_FIRERED_LONG_MAX_FRAMES
+static int derive_long(const vadx_firered_cfg *cfg, Dev *d) {
+    vadx_firered_cfg c = *cfg;
+    c.frames = 1;
+    return derive(&c, d);
+}
+
+extern "C" size_t vadx_firered_long_workspace_bytes(const vadx_firered_cfg *cfg, int64_t frames_total) {
+    Dev d;
+    if (!cfg || frames_total < 1 || frames_total > 0x7fffffffll || derive_long(cfg, &d)) return 0;
+    return (size_t)3 * d.P * (size_t)frames_total * sizeof(float);
+}
+
+extern "C" int vadx_firered_run_long(const vadx_firered_cfg *cfg, const float *packed, const float *logmel, const vadx_firered_long_tables *tables,
+                                     float *probs, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *who = "vadx_firered_run_long";
+    Dev d;
+    VADX_REQUIRE(cfg, "%s: cfg is NULL", who);
+    VADX_REQUIRE(packed, "%s: packed is NULL", who);
+    VADX_REQUIRE(logmel, "%s: logmel is NULL", who);
+    VADX_REQUIRE(tables, "%s: tables is NULL", who);
+    VADX_REQUIRE(tables->frame_first, "%s: tables->frame_first is NULL", who);
+    VADX_REQUIRE(tables->tile_first, "%s: tables->tile_first is NULL", who);
+    VADX_REQUIRE(tables->tile_clip, "%s: tables->tile_clip is NULL", who);
+    VADX_REQUIRE(probs, "%s: probs is NULL", who);
+    VADX_REQUIRE(workspace, "%s: workspace is NULL", who);
+    VADX_REQUIRE(cfg->frames >= 1 && cfg->frames <= VADX_FIRERED_LONG_MAX_FRAMES, "%s: cfg->frames=%d outside [1, %d], the frames of a long window", who,
+                 cfg->frames, VADX_FIRERED_LONG_MAX_FRAMES);
+    VADX_REQUIRE(tables->clips >= 1, "%s: tables->clips=%d must be at least 1", who, tables->clips);
+    VADX_REQUIRE(tables->n_tiles >= 1, "%s: tables->n_tiles=%d must be at least 1", who, tables->n_tiles);
+    VADX_REQUIRE(tables->frames_total >= 1, "%s: tables->frames_total=%d must be at least 1", who, tables->frames_total);
+    // every tile has at least one of its <= 64 frames (a clip may have none: fewer than 400 samples)
+    VADX_REQUIRE(tables->n_tiles <= tables->frames_total && (long long)tables->frames_total <= (long long)tables->n_tiles * LONG_TILE,
+                 "%s: tables->n_tiles=%d and tables->frames_total=%d do not fit each other (n_tiles <= frames_total <= %d * n_tiles)", who,
+                 tables->n_tiles, tables->frames_total, LONG_TILE);
+    VADX_REQUIRE(derive_long(cfg, &d) == 0, "%s: unsupported cfg (or a split arithmetic on widths the split kernels do not take)", who);
+    const size_t need = vadx_firered_long_workspace_bytes(cfg, tables->frames_total);
+    if (workspace_bytes < need) {
+        vadx::set_error("%s: workspace_bytes %zu B < required %zu B (vadx_firered_long_workspace_bytes)", who, workspace_bytes, need);
+        return VADX_ENOSPACE;
+    }
+    const LongTabs tb{tables->frame_first, tables->tile_first, tables->tile_clip, tables->clips, tables->n_tiles, tables->frames_total,
+                      VADX_FIRERED_LONG_MAX_FRAMES};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    const size_t lds = LDS_FLOATS * sizeof(float);
+    const dim3 grid((unsigned)tables->n_tiles), block(THREADS);
+    VADX_DYN_LDS(firered_long_head_kernel<0>, lds);
+    VADX_DYN_LDS(firered_long_head_kernel<1>, lds);
+    VADX_DYN_LDS(firered_long_head_kernel<2>, lds);
+    VADX_DYN_LDS(firered_long_block_kernel<0>, lds);
+    VADX_DYN_LDS(firered_long_block_kernel<1>, lds);
+    VADX_DYN_LDS(firered_long_block_kernel<2>, lds);
+    if (d.arith == vadx::VADX_AR_H2) hipLaunchKernelGGL(firered_long_head_kernel<2>, grid, block, lds, st, d, packed, logmel, tb, ws);
+    else if (d.arith == vadx::VADX_AR_B3) hipLaunchKernelGGL(firered_long_head_kernel<1>, grid, block, lds, st, d, packed, logmel, tb, ws);
+    else hipLaunchKernelGGL(firered_long_head_kernel<0>, grid, block, lds, st, d, packed, logmel, tb, ws);
+    VADX_HIP_TRY(hipGetLastError());
+    for (int r = 0; r < d.R; ++r) {
+        if (d.arith == vadx::VADX_AR_H2) hipLaunchKernelGGL(firered_long_block_kernel<2>, grid, block, lds, st, d, packed, tb, ws, r, probs);
+        else if (d.arith == vadx::VADX_AR_B3) hipLaunchKernelGGL(firered_long_block_kernel<1>, grid, block, lds, st, d, packed, tb, ws, r, probs);
+        else hipLaunchKernelGGL(firered_long_block_kernel<0>, grid, block, lds, st, d, packed, tb, ws, r, probs);
+        VADX_HIP_TRY(hipGetLastError());
+    }
+    return VADX_OK;
+}

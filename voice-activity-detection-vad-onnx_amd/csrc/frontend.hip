@@ -1309,6 +1309,35 @@ __global__ __launch_bounds__(SQ_THREADS, 2) void frontend_split_ragged_kernel(
     FE_TILE64_LADDER(dc, tile - first, split_tile<SC, MT>(dc, P, win, 0.f, f0, out_win, fsmem));
 }
 
+// frontend_split_ragged_kernel for a SNIP-EDGE preset (include/vadx.h: vadx_frontend_logmel_ragged_snip; FireRed: no centre pad): a
+// clip's frames = (clip_len - n_fft) / hop + 1, and a clip shorter than n_fft samples has no frame, no tile and no row.  A kernel of
+// its own, so that the centre-padded kernel above keeps its code object; the guards are the same.
+static_assert(TF_FOLD == VADX_FIRERED_LONG_TILE, "one tile_first / tile_clip table set serves this front-end and vadx_firered_run_long");
+template <typename SC>
+__global__ __launch_bounds__(SQ_THREADS, 2) void frontend_split_ragged_snip_kernel(
+    Dev d, const float *__restrict__ P, const int16_t *__restrict__ pcm, FeRagged r, float *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char fsmem[];
+    const int tile = blockIdx.x;
+    if (tile >= r.n_tiles) return;
+    const int b = r.tile_clip[tile];
+    if (b < 0 || b >= r.clips) return;
+    const int first = r.tile_first[b], next = r.tile_first[b + 1], m0 = r.mel_first[b], m1 = r.mel_first[b + 1], len = r.clip_len[b];
+    const long long off = r.clip_off[b];
+    if (first < 0 || tile < first || tile >= next || m0 < 0 || m1 <= m0 || m1 > r.mel_total) return;
+    const int n_fft = d.taps + 2 * d.tap0;
+    if (len < n_fft || off < 0 || off > r.pcm_len - len) return;
+    const int frames = (len - n_fft) / d.hop + 1;
+    if (frames != m1 - m0 || next - first != (frames + TF_FOLD - 1) / TF_FOLD) return;      // the tables disagree about this clip
+    Dev dc = d;                     // this clip's geometry in the uniform fields split_tile and mel_phase read
+    dc.window_len = len; dc.frames = frames;
+    dc.tiles64 = frames / TF_FOLD;
+    dc.tail_mt = (frames - dc.tiles64 * TF_FOLD + 15) / 16;
+    if (dc.tail_mt == 4) { dc.tiles64 += 1; dc.tail_mt = 0; }
+    const int16_t *win = pcm + off;
+    float *out_win = out + (size_t)m0 * d.out_stride;
+    FE_TILE64_LADDER(dc, tile - first, split_tile<SC, MT>(dc, P, win, 0.f, f0, out_win, fsmem));
+}
+
 // The split kernel over LIVE STREAMS (include/vadx.h: vadx_frontend_logmel_stream): one workgroup per (stream, 64-frame tile).  Stream
 // s's row = rows + s * row_stride holds `carry || new` samples with NO centre padding: sample 0 is the pre-emphasis tap of sample 1, and
 // frame i starts at row sample 1 + hop * i -- split_tile's window geometry with a centre pad of -1 (n0 = f0 * hop + tap0 + 1), so a frame
@@ -1707,6 +1736,49 @@ extern "C" int vadx_frontend_logmel_ragged(const vadx_frontend_cfg *cfg, const f
     } else {
         VADX_DYN_LDS(frontend_split_ragged_kernel<vadx::SchemeH2>, 160 * 1024);
         hipLaunchKernelGGL(frontend_split_ragged_kernel<vadx::SchemeH2>, dim3((unsigned)n_tiles), dim3(SQ_THREADS), slds, st, d, packed, pcm, r, out);
+    }
+    VADX_HIP_TRY(hipGetLastError());
+    return VADX_OK;
+}
+
+// vadx_frontend_logmel_ragged for a snip-edge preset (frames = (clip_len - n_fft) / hop + 1: FireRed's dynamic axis over B files); every
+// refusal names its argument and comes before any HIP call
+extern "C" int vadx_frontend_logmel_ragged_snip(const vadx_frontend_cfg *cfg, const float *packed, const int32_t *mel_kb_host, const int16_t *pcm,
+                                                int64_t pcm_len, const int64_t *clip_off, const int32_t *clip_len, const int32_t *mel_first,
+                                                const int32_t *tile_first, const int32_t *tile_clip, int clips, int n_tiles, int mel_total,
+                                                float *out, void *stream) {
+    static const char who[] = "vadx_frontend_logmel_ragged_snip";
+    VADX_REQUIRE(cfg, "%s: cfg is NULL", who);
+    VADX_REQUIRE(packed, "%s: packed is NULL", who);
+    VADX_REQUIRE(mel_kb_host, "%s: mel_kb_host is NULL", who);
+    VADX_REQUIRE(pcm, "%s: pcm is NULL", who);
+    VADX_REQUIRE(clip_off, "%s: clip_off is NULL", who);
+    VADX_REQUIRE(clip_len, "%s: clip_len is NULL", who);
+    VADX_REQUIRE(mel_first, "%s: mel_first is NULL", who);
+    VADX_REQUIRE(tile_first, "%s: tile_first is NULL", who);
+    VADX_REQUIRE(tile_clip, "%s: tile_clip is NULL", who);
+    VADX_REQUIRE(out, "%s: out is NULL", who);
+    VADX_REQUIRE(is_split(cfg->fold), "%s: DFT product kind %d is not built for ragged batches (VADX_FE_KIND_SPLIT_H2 = %d or VADX_FE_KIND_SPLIT_B3 = %d)",
+                 who, cfg->fold, (int)K_SPLIT_H2, (int)K_SPLIT_B3);
+    VADX_REQUIRE(cfg->prep == 1 && cfg->center_pad == 0, "%s: prep %d (centre pad %d) is not built for snip-edge ragged batches: the two-tap prep 1 "
+                 "of a preset without centre pad only (no in-graph resampling)", who, cfg->prep, cfg->center_pad);
+    VADX_REQUIRE(clips >= 1 && n_tiles >= 1 && mel_total >= 1 && pcm_len >= 1, "%s: clips=%d n_tiles=%d mel_total=%d pcm_len=%lld must be positive", who,
+                 clips, n_tiles, mel_total, (long long)pcm_len);
+    VADX_REQUIRE(n_tiles <= mel_total && (long long)mel_total <= (long long)n_tiles * TF_FOLD,
+                 "%s: n_tiles=%d and mel_total=%d do not fit each other (n_tiles <= mel_total <= %d * n_tiles)", who, n_tiles, mel_total, TF_FOLD);
+    Dev d;
+    VADX_REQUIRE(derive(cfg, &d) == 0, "%s: unsupported geometry", who);
+    for (int mt = 0; mt < d.nmt; ++mt) { d.mel_kb_lo[mt] = mel_kb_host[2 * mt]; d.mel_kb_hi[mt] = mel_kb_host[2 * mt + 1]; }
+    const size_t slds = split_lds_bytes(&d);
+    VADX_REQUIRE(slds <= 160 * 1024, "%s: geometry needs %zu B of LDS", who, slds);
+    const FeRagged r{tile_first, tile_clip, clip_len, mel_first, reinterpret_cast<const long long *>(clip_off), (long long)pcm_len, clips, n_tiles, mel_total};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (d.fold == K_SPLIT_B3) {
+        VADX_DYN_LDS(frontend_split_ragged_snip_kernel<vadx::SchemeB3>, 160 * 1024);
+        hipLaunchKernelGGL(frontend_split_ragged_snip_kernel<vadx::SchemeB3>, dim3((unsigned)n_tiles), dim3(SQ_THREADS), slds, st, d, packed, pcm, r, out);
+    } else {
+        VADX_DYN_LDS(frontend_split_ragged_snip_kernel<vadx::SchemeH2>, 160 * 1024);
+        hipLaunchKernelGGL(frontend_split_ragged_snip_kernel<vadx::SchemeH2>, dim3((unsigned)n_tiles), dim3(SQ_THREADS), slds, st, d, packed, pcm, r, out);
     }
     VADX_HIP_TRY(hipGetLastError());
     return VADX_OK;

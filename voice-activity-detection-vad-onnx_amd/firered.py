@@ -20,6 +20,9 @@ from .stream import StreamBatch
 SAMPLE_RATE, WINDOW_LENGTH, HOP_LENGTH = 16000, 400, 160
 STREAM_CHUNK_SAMPLES = 2560          # 160 ms (Export_FireRedVAD.py:52-53)
 MAX_FRAMES = 112                     # frames of one window / stream chunk the kernels keep in LDS (csrc/firered.hip: MAX_T)
+LONG_MAX_FRAMES = _lib.FIRERED_LONG_MAX_FRAMES      # frames of one window of the long path: 3600 s, the reference driver's cap (:541)
+LONG_MAX_SAMPLES = WINDOW_LENGTH + (LONG_MAX_FRAMES - 1) * HOP_LENGTH + HOP_LENGTH - 1      # the longest clip with that many frames
+WORKSPACE_CAP = 32 << 30             # bytes: the default `workspace_cap` of a long engine
 
 
 def valid_frame_count(num_samples, in_sample_rate=SAMPLE_RATE):
@@ -28,30 +31,56 @@ def valid_frame_count(num_samples, in_sample_rate=SAMPLE_RATE):
     return 0 if resampled < WINDOW_LENGTH else 1 + (resampled - WINDOW_LENGTH) // HOP_LENGTH
 
 
+def check_long_arguments(input_audio_length, in_sample_rate, long_windows):
+    """The refusals of FireRedEngine's long-window arguments, by name; needs no GPU."""
+    if input_audio_length is None:
+        if not long_windows:
+            raise ValueError("input_audio_length=None (the dynamic axis: one window per clip) needs long_windows=True")
+    elif long_windows and not WINDOW_LENGTH <= int(input_audio_length) <= LONG_MAX_SAMPLES:
+        raise ValueError(f"input_audio_length={int(input_audio_length)} outside [{WINDOW_LENGTH}, {LONG_MAX_SAMPLES}] samples: a long window "
+                         f"holds 1 to {LONG_MAX_FRAMES} frames (3600 s)")
+    if long_windows and int(in_sample_rate) != SAMPLE_RATE:
+        raise ValueError(f"long_windows=True with in_sample_rate={int(in_sample_rate)}: the long path has no in-graph resampling, "
+                         f"in_sample_rate must be {SAMPLE_RATE}")
+
+
 class FireRedEngine:
-    def __init__(self, weights=None, input_audio_length=16000, device="cuda:0", in_sample_rate=16000):
+    def __init__(self, weights=None, input_audio_length=16000, device="cuda:0", in_sample_rate=16000, long_windows=False,
+                 workspace_cap=WORKSPACE_CAP):
         """in_sample_rate: the export's IN_SAMPLE_RATE (FireRedVAD/Export_FireRedVAD.py:431-449): windows hold
-        `input_audio_length` samples at that rate and the graph resamples them to 16 kHz itself."""
+        `input_audio_length` samples at that rate and the graph resamples them to 16 kHz itself.
+        long_windows=True: the export at ANY `input_audio_length` from 400 samples to 3600 s (Export_FireRedVAD.py:29,48), or -- with
+        input_audio_length=None -- with the dynamic axis (DYNAMIC_AXES = True: one window per clip, as Inference_FireRed_ONNX.py:541-547
+        runs it).  Such an engine uses the long entry points (vadx_firered_run_long: activations in a global workspace, tiles of 64
+        frames) at every length; where the default engine applies too (<= 112 frames) the probabilities are bit for bit the same.  A
+        longer window is another export with fewer zero-padded window edges: other numbers, not a faster way to the same ones.
+        workspace_cap: bytes of workspace (3 * P * sum(T) floats) a call may ask for; a call above it is refused by that name."""
+        self.long = bool(long_windows)
+        check_long_arguments(input_audio_length, in_sample_rate, self.long)       # by name, before the GPU or the weights are touched
+        self.dynamic = input_audio_length is None
+        self.workspace_cap = int(workspace_cap)
+        self._workspace, self._rect = None, {}
         torch = _lib.require_gpu()
         self.torch = torch
         self.device = torch.device(device)
         w = _checkpoints.resolve("firered", weights)
         c = dict(w["cfg"])
         w = {k: (np.ascontiguousarray(np.asarray(v), dtype=np.float32) if k != "cfg" else v) for k, v in w.items()}
-        self.L = int(input_audio_length)
+        self.L = None if self.dynamic else int(input_audio_length)
         self.in_sample_rate = int(in_sample_rate)
-        if valid_frame_count(self.L, self.in_sample_rate) > MAX_FRAMES:      # refused by name, before anything is packed or uploaded
+        if not self.long and valid_frame_count(self.L, self.in_sample_rate) > MAX_FRAMES:      # refused by name, before anything is packed or uploaded
             raise ValueError(f"a FireRed window holds at most {MAX_FRAMES} frames, {self.L} samples at {self.in_sample_rate} Hz are "
                              f"{valid_frame_count(self.L, self.in_sample_rate)}")
-        self.fe = _frontend.Frontend("firered", self.L, device=device, in_sample_rate=self.in_sample_rate)
+        # (nothing in the front-end's tables depends on a window length: the dynamic engine's one Frontend serves every clip)
+        self.fe = _frontend.Frontend("firered", SAMPLE_RATE if self.dynamic else self.L, device=device, in_sample_rate=self.in_sample_rate)
         self._fes = {self.L: self.fe}
-        self.T = self.fe.frames
+        self.T = None if self.dynamic else self.fe.frames
         self.odim = c["odim"]
         self.cache_shape = (c["R"], 1, c["P"], (c["N1"] - 1) * c["S1"])
         cfg = _lib.FireRedCfg()
         for k in ("idim", "R", "M", "H", "P", "N1", "S1", "N2", "S2", "odim"):
             setattr(cfg, k, int(c[k]))
-        cfg.frames = self.T
+        cfg.frames = 1 if self.long else self.T          # (a long call's frame counts come with its tables; the blob does not depend on them)
         self._cfg0 = cfg
         hw = _lib.FireRedWeightsHost()
         hw.fc1_w, hw.fc1_b, hw.fc2_w, hw.fc2_b = (w[k].ctypes.data for k in ("fc1_w", "fc1_b", "fc2_w", "fc2_b"))
@@ -100,14 +129,82 @@ class FireRedEngine:
     def run(self, audio_i16, windows_per_clip=1):
         """audio int16 [B, W*L] -> probs f32 [B*W, odim, T] (each window stateless, as the reference)."""
         t = self.torch
+        if self.dynamic:
+            raise ValueError("a dynamic-axis engine (input_audio_length=None) has no window grid: use run_packed / detect on a list of clips")
         if not t.is_tensor(audio_i16):
             audio_i16 = t.from_numpy(np.ascontiguousarray(audio_i16, dtype=np.int16))
         return self._run_logmel(self.fe.logmel(audio_i16, windows_per_clip, self.L))
 
+    def workspace_bytes(self, frames_total):
+        """Bytes of workspace a long call over `frames_total` frames needs: 3 * P * frames_total floats (vadx_firered_long_workspace_bytes)"""
+        return int(_lib.lib().vadx_firered_long_workspace_bytes(C.byref(self._cfg0), int(frames_total)))
+
+    def _run_long(self, logmel, tables, frames_total):
+        """log-mel f32 [frames_total, 80] + a vadx_firered_long_tables -> probs f32 [odim, frames_total] (vadx_firered_run_long under the
+        range protocol).  The workspace is kept between calls and grows to the largest call, never above `workspace_cap`."""
+        t = self.torch
+        need = self.workspace_bytes(frames_total)
+        if need > self.workspace_cap:
+            raise ValueError(f"this call needs a workspace of {need} bytes (3 * P * {frames_total} frames * 4), above workspace_cap = "
+                             f"{self.workspace_cap}: run the batch in parts, or raise workspace_cap")
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = None
+            self._workspace = t.empty((need,), dtype=t.uint8, device=self.device)
+        ws = self._workspace
+        probs = t.empty((self.odim, frames_total), dtype=t.float32, device=self.device)
+
+        def launch(mode, cfg, packed):
+            with t.cuda.device(self.device):
+                _lib.check(_lib.lib().vadx_firered_run_long(C.byref(cfg), packed.data_ptr(), logmel.data_ptr(), C.byref(tables), probs.data_ptr(),
+                                                            ws.data_ptr(), int(ws.numel()), _lib.stream_ptr()))
+            return probs
+        return self.blobs.guarded(launch)
+
+    def release_workspace(self):
+        """Give the long path's workspace back to the allocator (it is kept between calls and grows to the largest call)."""
+        self._workspace = None
+
+    def _rect_tables(self, nwin):
+        """The long tables of a rectangular batch of nwin windows of T frames (equal counts), kept on the device per nwin"""
+        got = self._rect.get(nwin)
+        if got is None:
+            t = self.torch
+            if len(self._rect) >= 8:
+                self._rect.pop(next(iter(self._rect)))
+            tabs = [t.from_numpy(a).to(self.device) for a in _ragged.long_tables(np.full(nwin, self.T, dtype=np.int64))]
+            got = self._rect[nwin] = (tabs, _lib.FireRedLongTables(*(a.data_ptr() for a in tabs), nwin, int(tabs[2].numel()), nwin * self.T))
+        return got[1]
+
+    def pack(self, clips):
+        """The packed batch of a dynamic-axis engine: `clips` (list of 1-D int16 arrays of any lengths) end to end, no padding
+        (vadx.ragged.PackedClips).  A clip above 3600 s is refused by name (the reference's 3600 s windowing of such a file stays out)."""
+        return _ragged.PackedClips.from_clips(clips, self.device, LONG_MAX_FRAMES)
+
+    def run_packed(self, pc, return_logmel=False):
+        """vadx.ragged.PackedClips -> probs f32 [odim, sum T_b] on the device: clip b's T_b = pc.frames[b] frames at columns
+        pc.frame_first[b] .. (one snip-edge front-end launch, then vadx_firered_run_long); clip b's columns are bit for bit those of the
+        one-clip call.  A batch without a single frame gives [odim, 0] and launches nothing."""
+        if not self.dynamic:
+            raise ValueError(f"this engine cuts windows of {self.L} samples: run_packed is the dynamic-axis call (input_audio_length=None)")
+        if int(pc.frames.max()) > LONG_MAX_FRAMES:
+            raise ValueError(f"clip {int(np.argmax(pc.frames))} has {int(pc.frames.max())} frames: a window holds at most {LONG_MAX_FRAMES} (3600 s)")
+        if pc.device is None:
+            pc.to(self.device)
+        logmel = self.fe.logmel_ragged_snip(pc)
+        if pc.n_frames == 0:
+            probs = self.torch.empty((self.odim, 0), dtype=self.torch.float32, device=self.device)
+        else:
+            probs = self._run_long(logmel, pc.tables(), pc.n_frames)
+        return (probs, logmel) if return_logmel else probs
+
     def _run_logmel(self, logmel):
-        """log-mel f32 [windows, T, 80] -> probs f32 [windows, odim, T] (vadx_firered_run under the range protocol)"""
+        """log-mel f32 [windows, T, 80] -> probs f32 [windows, odim, T] (vadx_firered_run under the range protocol; a long engine:
+        vadx_firered_run_long over the same windows as a rectangular batch, its planes [odim, windows * T] turned window-major)"""
         t = self.torch
         nwin = logmel.shape[0]
+        if self.long:
+            planes = self._run_long(logmel, self._rect_tables(nwin), nwin * self.T)
+            return planes.view(self.odim, nwin, self.T).permute(1, 0, 2).contiguous()
         probs = t.empty((nwin, self.odim, self.T), dtype=t.float32, device=self.device)
 
         def launch(mode, cfg, packed):
@@ -125,12 +222,18 @@ class FireRedEngine:
     def ragged_packed(self, pcm, clip_offsets, lengths, pad_noise=None, normalize=None):
         """`ragged` for clips that already lie in device memory (RaggedBatch.from_packed: padded and packed on the device, bit for bit what
         `ragged` builds from the same clips and noise; normalize="rms" applies timestamps.normalise_audio on the way)."""
+        if self.dynamic:             # no grid, no padding: tables only around the clips where they lie
+            if normalize is not None:
+                raise ValueError(f"normalize={normalize!r}: a dynamic-axis batch takes the clips as they lie (tables only); normalise them first")
+            return _ragged.PackedClips.from_packed(pcm, clip_offsets, lengths, self.device, LONG_MAX_FRAMES)
         return _ragged.RaggedBatch.from_packed(pcm, clip_offsets, lengths, self.L, self.L, pad_noise, normalize, device=self.device)
 
     def run_ragged(self, rb):
         """RaggedBatch on this engine's grid -> probs f32 [sum W, odim, T]: rows win_first[b] .. win_first[b+1]-1 are clip b's windows
         (vadx_windows_gather, then the unchanged front-end and vadx_firered_run over sum W windows).  A host-only batch
         (device=None) is uploaded first, in place: `rb.to(self.device)` turns its pcm and tables into device tensors."""
+        if self.dynamic:
+            raise ValueError("a dynamic-axis engine (input_audio_length=None) has no window grid: use run_packed on a PackedClips")
         if rb.window != self.L or rb.stride != self.L:
             raise ValueError(f"the batch was packed for windows of {rb.window} every {rb.stride} samples, this engine cuts {self.L} every {self.L}")
         if rb.device is None:
@@ -143,6 +246,18 @@ class FireRedEngine:
         A list (or tuple) of 1-D clips takes the ragged route (`run_ragged`, one vadx_tracks_gather per channel: [B, max(n_frames, 1)],
         zeros past n_frames[b]); an array [B, N] the rectangular one (`run`: [B, n_frames], cut from the windows laid end to end).
         sample_rate: what a sample count means in frames and in seconds -- `detect` passes in_sample_rate, the AED driver 16 kHz."""
+        if self.dynamic:
+            # one window per clip (Inference_FireRed_ONNX.py:541-547): no padding, so pad_noise has nothing to fill; an array [B, N] is B
+            # clips of one length.  A clip under 400 samples has no frame and no segment.
+            is_list = isinstance(clips, (list, tuple, _ragged.PackedClips))
+            pc = clips if isinstance(clips, _ragged.PackedClips) else self.pack(list(clips) if is_list else [r for r in np.asarray(clips)])
+            probs = self.run_packed(pc)
+            nf = pc.frames.astype(np.int64)
+
+            def channel(k):
+                track = gather_tracks(self.device, probs[k], 1, 0, 1, pc.frame_first, nf)
+                return track if is_list else track[:, :int(nf[0])].contiguous()
+            return channel, nf, [int(n) / sample_rate for n in pc.lengths]
         if isinstance(clips, (list, tuple, _ragged.RaggedBatch)):
             # (a RaggedBatch is packed already: `ragged`, or RaggedBatch.from_packed on the device)
             rb = clips if isinstance(clips, _ragged.RaggedBatch) else self.ragged(clips, pad_noise)
@@ -343,7 +458,7 @@ class FireRedEngine:
         out, dec = track_segments(_vadpost.VadPostprocessor(*post, device=self.device), track, nf, durations)
         if not return_probs:
             return out
-        if isinstance(clips_i16, (list, tuple, _ragged.RaggedBatch)):
+        if isinstance(clips_i16, (list, tuple, _ragged.RaggedBatch, _ragged.PackedClips)):
             return out, [track[b, :nf[b]] for b in range(len(nf))], [dec[b, :nf[b]] for b in range(len(nf))]
         return (out, track, dec) if track.shape[1] else (out, track)      # an array without a valid frame: no decisions are returned
 
@@ -391,7 +506,7 @@ def _detect_events(self, clips_i16, pad_noise=None, thresholds=(0.4, 0.5, 0.5), 
             out[b][1][event] = round(float(ratio[b]), 3) if nf[b] else 0.0
     if not return_probs:
         return out
-    if isinstance(clips_i16, (list, tuple)):
+    if isinstance(clips_i16, (list, tuple, _ragged.PackedClips)):
         return out, [t.stack([tr[b, :nf[b]] for tr in tracks]) for b in range(B)]
     return out, t.stack(tracks, dim=1)
 
@@ -636,14 +751,26 @@ class FireRedSession(Session):
     """onnxruntime.InferenceSession look-alike: {'audio': int16 [1,1,L]} -> [probs f32 [1,odim,T]]
     (FireRedVAD/Export_FireRedVAD.py:785-807); a leading batch of windows is accepted."""
 
-    def __init__(self, weights=None, input_audio_length=16000, device="cuda:0", in_sample_rate=16000):
-        self.engine = FireRedEngine(weights, input_audio_length, device, in_sample_rate)
-        self._inputs_meta = [_Meta("audio", [1, 1, self.engine.L], "tensor(int16)")]
-        self._outputs_meta = [_Meta("probs", [1, self.engine.odim, self.engine.T], "tensor(float)")]
+    def __init__(self, weights=None, input_audio_length=16000, device="cuda:0", in_sample_rate=16000, long_windows=False):
+        """long_windows=True: a long or -- input_audio_length=None -- dynamic export (FireRedEngine).  The dynamic session reports
+        [1, 1, "audio_len"] and [1, odim, "n_frames"] (the reference's driver keys on the string, Inference_FireRed_ONNX.py:541-547)
+        and accepts any length from 400 samples."""
+        self.engine = FireRedEngine(weights, input_audio_length, device, in_sample_rate, long_windows=long_windows)
+        dyn = self.engine.dynamic
+        self._inputs_meta = [_Meta("audio", [1, 1, "audio_len" if dyn else self.engine.L], "tensor(int16)")]
+        self._outputs_meta = [_Meta("probs", [1, self.engine.odim, "n_frames" if dyn else self.engine.T], "tensor(float)")]
 
     def run(self, output_names, feeds):
         audio = np.asarray(feeds["audio"])
         require_int16(audio)
+        if self.engine.dynamic:
+            rows = audio.reshape(-1, audio.shape[-1])
+            if rows.shape[1] < WINDOW_LENGTH:
+                raise ValueError(f"Got invalid dimensions for input: audio, expected last dim >= {WINDOW_LENGTH}")
+            pc = self.engine.pack([r for r in rows])
+            T = int(pc.frames[0])
+            probs = self.engine.run_packed(pc).view(self.engine.odim, rows.shape[0], T).permute(1, 0, 2).contiguous()
+            return [probs.cpu().numpy()]
         if audio.shape[-1] != self.engine.L:
             raise ValueError(f"Got invalid dimensions for input: audio, expected last dim {self.engine.L}")
         probs = self.engine.run(audio.reshape(-1, audio.shape[-1])).cpu().numpy()

@@ -200,3 +200,29 @@ class Frontend:
                                                               rf.fe_tile_clip.data_ptr(), len(rf), rf.n_fe_tiles, rf.n_mel, out.data_ptr(),
                                                               _lib.stream_ptr()))
         return out
+
+    def logmel_ragged_snip(self, pc, out=None):
+        """vadx.ragged.PackedClips (clips of any lengths, one window = one clip, snip edges) -> log-mel f32 [sum F_b, n_mels] on the device,
+        clip b's (n_b - n_fft) // hop + 1 rows from pc.frame_first[b] (none for a clip under n_fft samples): one launch
+        (vadx_frontend_logmel_ragged_snip).  Built for the split-product kinds and the two-tap preset without centre pad at 16 kHz
+        (FireRed); anything else is a ValueError.  A batch without a single frame gives an empty tensor and launches nothing."""
+        t = self.torch
+        if self.fold not in self.RAGGED_KINDS:
+            raise ValueError(f"the ragged front-end is built for the split-product kinds {self.RAGGED_KINDS} (KIND_SPLIT_H2 / KIND_SPLIT_B3); this "
+                             f"Frontend was packed as kind {self.fold} (fold argument or VADX_FRONTEND_FOLD): no ragged form of that product")
+        if self.cfg.prep != 1 or self.cfg.center_pad != 0 or self.cfg.hop != 160:
+            raise ValueError(f"the snip-edge ragged front-end is built for the two-tap preset without centre pad at 16 kHz (prep 1, hop 160); this "
+                             f"Frontend has prep {self.cfg.prep}, centre pad {self.cfg.center_pad}, hop {self.cfg.hop}")
+        if pc.device is None:
+            pc.to(self.device)
+        if out is None:
+            out = t.empty((pc.n_frames, self.n_mels), dtype=t.float32, device=self.device)
+        if pc.n_frames == 0:
+            return out
+        with t.cuda.device(self.device):
+            _lib.check(_lib.lib().vadx_frontend_logmel_ragged_snip(C.byref(self.cfg), self.packed.data_ptr(), self.mel_kb.ctypes.data,
+                                                                   pc.pcm.data_ptr(), int(pc.pcm.numel()), pc.clip_off.data_ptr(),
+                                                                   pc.clip_len.data_ptr(), pc.frame_first.data_ptr(), pc.tile_first.data_ptr(),
+                                                                   pc.tile_clip.data_ptr(), len(pc), pc.n_tiles, pc.n_frames, out.data_ptr(),
+                                                                   _lib.stream_ptr()))
+        return out

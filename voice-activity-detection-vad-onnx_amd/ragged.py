@@ -389,6 +389,128 @@ class RaggedFrames:
                                     self.mel_first.data_ptr(), len(self), self.n_enc_tiles, self.n_enc, self.n_mel)
 
 
+SNIP_NFFT = 400              # the FireRed preset's analysis frame: a clip of n >= 400 samples has (n - 400) // HOP + 1 frames (snip edges)
+LONG_TILE = 64               # frames per tile of the FireRed long path and of its front-end (include/vadx.h: VADX_FIRERED_LONG_TILE)
+
+
+def long_tables(frames):
+    """The tables of vadx_firered_long_tables for windows of `frames` [B] frames each (0 allowed: no tile): (frame_first int32 [B+1],
+    tile_first int32 [B+1], tile_clip int32 [n_tiles]).  A rectangular batch is the same tables with equal counts."""
+    frames = np.asarray(frames, dtype=np.int64).reshape(-1)
+    if frames.shape[0] == 0:
+        raise ValueError("a batch needs at least one window")
+    if int(frames.min()) < 0:
+        raise ValueError(f"window {int(np.argmin(frames))} has a negative frame count")
+    tiles = (frames + LONG_TILE - 1) // LONG_TILE
+    return _prefix(frames, "frames"), _prefix(tiles, "tiles"), np.repeat(np.arange(frames.shape[0], dtype=np.int32), tiles)
+
+
+class PackedClips:
+    """FireRed's batch in the dynamic-axis mode (FireRedEngine(long_windows=True, input_audio_length=None): one window = one whole clip;
+    include/vadx.h, "FireRed windows of ANY length").  The clips lie end to end in one int16 vector `pcm`; no padding exists in this
+    mode.  Fields: pcm int16 [>= sum n_b]; clip_off int64 [B], clip_len int32 [B]; frames int64 [B] (host) = snip-edge frame counts
+    ((n - 400) // 160 + 1, 0 under 400 samples: no frame, no tile, no segment); frame_first / tile_first int32 [B+1], tile_clip int32
+    [n_tiles] (64-frame tiles: ONE table set serves the front-end and the net).  With a device every table is a tensor there and the
+    `*_host` attributes keep numpy; device=None keeps numpy only."""
+
+    TABLES = ("pcm", "clip_off", "clip_len", "frame_first", "tile_first", "tile_clip")
+
+    @classmethod
+    def from_clips(cls, clips, device="cuda:0", max_frames=None):
+        if len(clips) == 0:
+            raise ValueError("a packed batch needs at least one clip")
+        rows = []
+        for b, c in enumerate(clips):
+            a = np.asarray(c)
+            if a.dtype != np.int16:
+                raise ValueError(f"clip {b} must be int16, got {a.dtype}")
+            a = a.reshape(-1)
+            if a.shape[0] == 0:
+                raise ValueError(f"clip {b} is empty")
+            rows.append(a)
+        self = cls()
+        self._set_tables([len(r) for r in rows], None, max_frames)
+        self.pcm_host = np.concatenate(rows)
+        self.device = None
+        for name in self.TABLES:
+            setattr(self, name, getattr(self, name + "_host"))
+        if device is not None:
+            self.to(device)
+        return self
+
+    @classmethod
+    def from_lengths(cls, lengths, clip_offsets=None, max_frames=None):
+        """The host tables of clips of `lengths` samples (end to end, or at `clip_offsets`) without any PCM: what a caller with its own
+        device buffer hands to the C entry points, and where a clip above `max_frames` frames is refused before a sample is touched."""
+        self = cls()
+        self._set_tables(lengths, clip_offsets, max_frames)
+        self.device = self.pcm = self.pcm_host = None
+        for name in self.TABLES[1:]:
+            setattr(self, name, getattr(self, name + "_host"))
+        return self
+
+    @classmethod
+    def from_packed(cls, pcm, clip_offsets, lengths, device=None, max_frames=None):
+        """Tables only, around clips that already lie in device memory: pcm 1-D int16 tensor, clip b = lengths[b] samples from element
+        clip_offsets[b] (any element) -- the output of chunks.collect_chunks_batch or audio_io.ingest_ragged goes straight in; nothing is
+        copied.  clip_offsets / lengths: host arrays or device tensors (read back once)."""
+        from . import _lib, prepare
+        t = _lib.require_gpu()
+        src_off, lengths = prepare.read_tables(clip_offsets, lengths)
+        if lengths.shape[0] == 0:
+            raise ValueError("a packed batch needs at least one clip")
+        if src_off.shape[0] != lengths.shape[0]:
+            raise ValueError(f"{src_off.shape[0]} clip_offsets for {lengths.shape[0]} lengths")
+        if int(lengths.min()) < 1:
+            raise ValueError(f"clip {int(np.argmin(lengths))} is empty")
+        if pcm.dtype != t.int16 or pcm.dim() != 1:
+            raise ValueError(f"pcm must be a 1-D int16 tensor, got {pcm.dtype} {list(pcm.shape)}")
+        if int(src_off.min()) < 0 or int((src_off + lengths).max()) > int(pcm.numel()):
+            raise ValueError("a clip lies outside pcm")
+        pcm = (pcm.to(device) if device is not None else pcm).contiguous()
+        self = cls()
+        self._set_tables(lengths, src_off, max_frames)
+        self.device, self.pcm, self.pcm_host = pcm.device, pcm, None
+        for name in self.TABLES[1:]:
+            setattr(self, name, t.from_numpy(getattr(self, name + "_host")).to(self.device))
+        return self
+
+    def _set_tables(self, lengths, offsets=None, max_frames=None):
+        """Every table of the batch: a function of the clips' lengths (and of where they lie)."""
+        self.lengths = np.asarray(lengths, dtype=np.int64)
+        if int(self.lengths.max()) >= 2 ** 31:
+            raise ValueError("a clip of 2^31 samples or more does not fit the int32 clip_len table")
+        self.frames = np.where(self.lengths < SNIP_NFFT, 0, (self.lengths - SNIP_NFFT) // HOP + 1).astype(np.int64)
+        if max_frames is not None and int(self.frames.max()) > int(max_frames):
+            b = int(np.argmax(self.frames))
+            raise ValueError(f"clip {b} has {int(self.frames[b])} frames ({int(self.lengths[b])} samples): a window holds at most {int(max_frames)} "
+                             f"frames (3600 s); cut the file first")
+        self.clip_len_host = self.lengths.astype(np.int32)
+        self.clip_off_host = (np.concatenate([[0], np.cumsum(self.lengths)[:-1]]) if offsets is None else np.asarray(offsets)).astype(np.int64)
+        self.frame_first_host, self.tile_first_host, self.tile_clip_host = long_tables(self.frames)
+        self.n_frames, self.n_tiles = int(self.frame_first_host[-1]), int(self.tile_first_host[-1])
+
+    def to(self, device):
+        """Upload the packed PCM (once) and the tables."""
+        from . import _lib
+        t = _lib.require_gpu()
+        self.device = t.device(device)
+        for name in self.TABLES:
+            setattr(self, name, t.from_numpy(getattr(self, name + "_host")).to(self.device))
+        return self
+
+    def __len__(self):
+        return int(self.lengths.shape[0])
+
+    def tables(self):
+        """The vadx_firered_long_tables struct of this batch (device pointers: the batch must be on a device)."""
+        from . import _lib
+        if self.device is None:
+            raise ValueError("this batch is host-only: call .to(device) first")
+        return _lib.FireRedLongTables(self.frame_first.data_ptr(), self.tile_first.data_ptr(), self.tile_clip.data_ptr(), len(self),
+                                      self.n_tiles, self.n_frames)
+
+
 SILERO_WINDOW = 512          # samples per Silero window at 16 kHz
 SILERO_WINDOWS = {16000: 512, 8000: 256}     # samples per window of the network of each rate
 SILERO_GROUP = 16            # clips per group = columns of one MFMA tile
